@@ -7,6 +7,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -83,3 +84,27 @@ def test_three_rank_launch_as_the_driver_launches_it(hip_device):
     assert d["config"]["parallelism"] == "dp3" and "cpu_baseline" not in d and "kernel_families" not in d
     assert d["config"]["gradient_allreduce"]["messages_per_step"] >= 5
     assert abs(d["value"] - 24 * 192 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+
+
+def test_dump_outputs_of_the_last_timed_step(hip_device, tmp_path):
+    """--dump-outputs: float arrays of the last timed step, under 64 MB, and the same inputs from run to run (two runs
+    of the same command agree to within the run-to-run spread of the GPU's reduction order)."""
+    dumps = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--batch", "16", "--steps", "3", "--warmup", "1",
+                              "--no-cpu-baseline", "--no-native-ref", "--family-steps", "0", "--host-steps", "0",
+                              "--dump-outputs", str(tmp_path / run)], cwd=str(ROOT), capture_output=True, text=True,
+                             timeout=900)
+        d = _one_line(res)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        arrays = {p.stem: np.load(p) for p in (tmp_path / run).glob("*.npy")}
+        assert {"loss", "f0_pred", "sil_pred", "params_sample", "grads_sample", "bn_buffers"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert abs(arrays["loss"][0] - d["loss"]) <= 1e-6 * abs(d["loss"])       # the line's loss is the last step's
+        assert arrays["f0_pred"].shape[0] == 16 and arrays["sil_pred"].shape[0] == 16
+        dumps.append(arrays)
+    a, b = dumps
+    for k in a:
+        assert a[k].shape == b[k].shape
+        assert np.allclose(a[k], b[k], rtol=1e-3, atol=1e-5 * max(1.0, float(np.abs(a[k]).max()))), k
