@@ -467,6 +467,31 @@ long pe_resample_out_len(const pe_resample_plan* plan, long n_in);
 int pe_resample_forward(const pe_resample_plan* plan, const float* x, int batch, int n_in, long x_stride, float* y,
                         long y_stride, int n_out, void* stream);
 
+/* ---- pitch-shift augmentation (reference meldataset.py:324-517 -> librosa.effects.pitch_shift defaults) ----
+ * STFT 2048 / hop 512 / periodic Hann / centre zero padding -> phase vocoder at rate 2^(-n_steps/12) -> iSTFT to
+ * round(N / rate) samples -> resampy sinc resampling (res_type 0 = kaiser_best, 1 = kaiser_fast) back to N samples.
+ * pe_pitch_shift_plan (host only, no device call) lays out a ragged batch of n_rows rows: row r reads n[r] samples at
+ * x + x_off[r], shifts them by n_steps[r] (|n_steps| <= 24) and writes output samples [j_lo[r], j_lo[r] + j_cnt[r])
+ * (<= n[r]) to out + out_row[r] * out_stride (out_stride >= j_cnt[r]).  It fills meta (n_rows x
+ * pe_pitch_shift_plan_fields() int64), ratios (n_rows x {rate, resample ratio}) and totals {STFT frames, stretched
+ * columns, stretched samples, output samples}, the sizes of the workspaces the four stages below read and write:
+ * spec (frames x 1025 complex), cols (columns x 1025 complex), frames (columns x 2048), stretched (samples), out.
+ * Only the prefix of a row that the output window depends on is computed.  n_fft / hop other than 2048 / 512 are
+ * PE_E_UNSUPPORTED.  table: the resampling filter followed by its first differences (2 x (zeros * 512 + 1) floats).
+ * pe_pitch_shift_resample: out = resampled * gains[r] (+ noise, laid out like the output windows, optional). */
+int pe_pitch_shift_plan(int n_rows, const long* n, const float* n_steps, const long* x_off, const long* j_lo,
+                        const long* j_cnt, const long* out_row, long out_stride, int sr, int n_fft, int hop,
+                        int res_type, long* meta, double* ratios, long* totals);
+int pe_pitch_shift_plan_fields(void);
+int pe_pitch_shift_stft(const float* x, const long* meta, int n_rows, long n_frames, float* spec, void* stream);
+int pe_pitch_shift_vocoder(const float* spec, const long* meta, const double* ratios, int n_rows, long n_cols,
+                           float* cols, void* stream);
+int pe_pitch_shift_istft(const float* cols, const long* meta, int n_rows, long n_cols, long n_samples, float* frames,
+                         float* stretched, void* stream);
+int pe_pitch_shift_resample(const float* stretched, const long* meta, const double* ratios, const float* table,
+                            int res_type, const float* gains, const float* noise, int n_rows, long n_out, float* out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

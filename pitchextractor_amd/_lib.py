@@ -127,6 +127,12 @@ PROTOTYPES = {
     "pe_resample_plan_destroy": (_i, [_p]),
     "pe_resample_out_len": (_l, [_p, _l]),
     "pe_resample_forward": (_i, [_p, _p, _i, _i, _l, _p, _l, _i, _p]),
+    "pe_pitch_shift_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p]),
+    "pe_pitch_shift_plan_fields": (_i, []),
+    "pe_pitch_shift_stft": (_i, [_p, _p, _i, _l, _p, _p]),
+    "pe_pitch_shift_vocoder": (_i, [_p, _p, _p, _i, _l, _p, _p]),
+    "pe_pitch_shift_istft": (_i, [_p, _p, _i, _l, _l, _p, _p, _p]),
+    "pe_pitch_shift_resample": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _l, _p, _p]),
     "pe_f0_bins_ce_workspace_bytes": (_z, [_l]),
     "pe_f0_bins_ce_loss": (_i, [_p, _l, _i, _p, _p, _p, _f, _l, _f, _p, _p, _l, _p, _p, _z, _p]),
     "pe_gemm_nt_f16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p]),

@@ -12,8 +12,11 @@ to HBM once and ONE launch of the fused mel kernel does framing + FFT + mel + lo
 (meldataset.py:806-816).  All index arithmetic -- segment pre-crop (meldataset.py:178-201), F0
 alignment (f0_backends.py:788-806), crop offsets -- is reproduced exactly and runs on the host.
 
-Out of scope here: the F0 tracker backends and the WORLD / pitch-shift
-augmentation need packages that are not installable offline.  F0 labels therefore come from the
+Out of scope here: the F0 tracker backends and the WORLD-vocoder augmentation need
+packages that are not installable offline.  The pitch-shift augmentation (``synthetic_data.pitch_shift``,
+meldataset.py:324-517) runs on the GPU (``pitchextractor_amd.pitch_shift``): workers draw everything the reference
+draws, in its order, and ship the whole base file; the device shifts it and writes only the samples the cropped
+192 mel frames read into the batch row.  F0 labels therefore come from the
 reference's cache files under the reference's own contract (meldataset.py:519-604):
 ``<wav>_f0<cache_identifier>.npy`` validated by its sibling ``.json`` (cache_identifier, sample_rate,
 hop_length), then the legacy ``<wav>_f0.npy``; or from an ``f0_provider`` callable.  A cache whose
@@ -44,7 +47,10 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
+from typing import NamedTuple
+
 from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS, MelSpectrogram
+from .pitch_shift import check_res_type, pitch_shift_ragged
 from .resample import Resampler
 
 logger = logging.getLogger(__name__)
@@ -235,6 +241,47 @@ def f0_cache_identifier(f0_params: dict | None) -> str:
     return ("-" + "_".join(keys)) if keys else ""
 
 
+# --------------------------------------------------------------------------- synthetic pitch-shift items
+class PitchShiftRequest(NamedTuple):
+    """What a worker hands the device for one pitch-shifted item (last element of the item tuple).  ``n``: samples
+    of the base file at the model rate; the device writes shifted samples [out_start, out_start + out_len) to the
+    batch row, whose mel frame ``frame_start`` is then the item's first kept frame (``crop`` of the whole file)."""
+    path: str
+    n_steps: float
+    gain: float
+    n: int
+    crop: int
+    out_start: int
+    out_len: int
+    frame_start: int
+    noise: np.ndarray | None                   # float32 (out_len,) slice of the reference's full-length draw
+
+
+class PitchShiftBatch(NamedTuple):
+    """Collated synthetic rows: their base files packed back to back (no padding), plus per-row parameters."""
+    rows: torch.Tensor                         # int64 (K,) batch rows
+    src: torch.Tensor                          # float32 flat source audio at the files' own rate
+    src_len: torch.Tensor                      # int64 (K,)
+    n: torch.Tensor                            # int64 (K,) lengths at the model rate
+    n_steps: torch.Tensor                      # float32 (K,)
+    gains: torch.Tensor                        # float32 (K,)
+    out_start: torch.Tensor                    # int64 (K,)
+    out_len: torch.Tensor                      # int64 (K,)
+    noise: torch.Tensor | None                 # float32 flat, the windows back to back
+
+
+def synthetic_window(n: int, crop: int, hop: int, n_fft: int, max_frames: int = MAX_MEL_LENGTH):
+    """(out_start, out_len, frame_start): the shifted samples that mel frames crop .. crop + max_frames - 1 of an
+    n-sample wave read (centre padding n_fft // 2), laid out so that the batch row's frame ``frame_start`` is frame
+    ``crop`` of the whole wave and the row's reflect padding happens only where the whole wave's does."""
+    frames = 1 + n // hop
+    if frames <= max_frames:
+        return 0, n, 0
+    margin = -(-(n_fft // 2) // hop)
+    start, first = (hop * (crop - margin), margin) if crop >= margin else (0, crop)
+    return start, min(n - start, hop * (first + max_frames - 1) + n_fft // 2), first
+
+
 # --------------------------------------------------------------------------- dataset
 class MelDataset(torch.utils.data.Dataset):
     def __init__(self, data_list, sr=DEFAULT_MEL_PARAMS["sample_rate"], mel_params=None, f0_params=None,
@@ -270,13 +317,157 @@ class MelDataset(torch.utils.data.Dataset):
         self._mel_cache_suffix, self._mel_meta_suffix = "_mel.npy", "_mel_meta.json"      # meldataset.py:102-103
         self._cache_enabled = True
         self._mel_cache_warned = False
-        if synthetic_data and synthetic_data.get("enabled", False) and not validation:
-            logger.warning("synthetic_data augmentation (WORLD / pitch-shift) needs pyworld/librosa, which are "
-                           "not available: disabled")
-        self.synthetic_enabled = False
+        # synthetic augmentation (meldataset.py:139-143,324-381)
+        self._base_length = len(self.data_list)
+        self.synthetic_config = synthetic_data or {}
+        self.synthetic_enabled = bool(self.synthetic_config.get("enabled", False))
+        self.synthetic_apply_to_validation = bool(self.synthetic_config.get("apply_to_validation", False))
+        if validation and not self.synthetic_apply_to_validation:
+            self.synthetic_enabled = False
+        self._synthetic_generators = []
+        self._synthetic_count = 0
+        self.synthetic_pitch_shift_config = {}
+        if self.synthetic_enabled:
+            self._initialise_synthetic_generators()
+        if self.verbose and self.synthetic_enabled:
+            print(f"[MelDataset] Synthetic data enabled: {{'count': {self._synthetic_count}, "
+                  f"'strategies': {self._synthetic_generators}}}")
 
     def __len__(self):
-        return len(self.data_list)
+        if not self.synthetic_enabled:
+            return self._base_length
+        return self._base_length + self._synthetic_count
+
+    # ---- synthetic items ------------------------------------------------------------------
+    def _initialise_synthetic_generators(self):
+        config = self.synthetic_config
+        ratio = float(config.get("ratio", 0.0))
+        absolute_count = config.get("absolute_count")
+        max_items = config.get("max_items")
+        min_items = config.get("min_items", 0)
+        if absolute_count is not None:
+            self._synthetic_count = max(0, int(absolute_count))
+        else:
+            target = int(round(self._base_length * ratio))
+            if ratio > 0 and target == 0 and self._base_length > 0:
+                target = 1
+            self._synthetic_count = max(0, target)
+        if max_items is not None:
+            self._synthetic_count = min(self._synthetic_count, int(max_items))
+        if min_items:
+            self._synthetic_count = max(self._synthetic_count, int(min_items))
+
+        pitch_shift_cfg = config.get("pitch_shift", {}) or {}
+        if pitch_shift_cfg.get("enabled", True):
+            check_res_type(pitch_shift_cfg.get("resample_type", "kaiser_best"))
+            if not self.data_list:
+                if self.verbose:
+                    print("[MelDataset] Pitch-shift augmentation disabled: no base samples available.")
+            else:
+                self._synthetic_generators.append("pitch_shift")
+        self.synthetic_pitch_shift_config = pitch_shift_cfg
+
+        world_cfg = config.get("world_vocoder", {}) or {}
+        if world_cfg.get("enabled", False):
+            logger.warning("[MelDataset] WORLD vocoder synthetic generation disabled: pyworld unavailable")
+
+        if not self._synthetic_generators or self._synthetic_count <= 0:
+            self.synthetic_enabled = False
+            self._synthetic_generators = []
+            self._synthetic_count = 0
+            if self.verbose:
+                print("[MelDataset] Synthetic data disabled: no valid generators or count is zero.")
+
+    def _generate_synthetic_sample(self):
+        """meldataset.py:383-421; 'pitch_shift' is the only generator here."""
+        if not self._synthetic_generators:
+            raise RuntimeError("Synthetic generation requested but no generators are available")
+        random.choice(self._synthetic_generators)
+        result = self._generate_pitch_shift_sample()
+        if result is not None:
+            return result
+        result = self._generate_pitch_shift_sample(force=True)
+        if result is not None:
+            return result
+        raise RuntimeError("Unable to produce synthetic pitch-shift sample")
+
+    def _generate_pitch_shift_sample(self, force=False):
+        """meldataset.py:423-517 with the signal work left to the device: the same draws in the same order, the
+        labels built here, the shift itself requested through a ``PitchShiftRequest``."""
+        cfg = self.synthetic_pitch_shift_config or {}
+        semitone_choices = cfg.get("semitones") or [-4, -2, -1, 1, 2, 4]
+        max_attempts = max(1, int(cfg.get("max_attempts", 5)))
+        min_voiced_fraction = float(cfg.get("min_voiced_fraction", 0.05))
+        gain_db_range = cfg.get("gain_db_range", [-6.0, 3.0])
+        if isinstance(gain_db_range, (int, float)):
+            gain_db_range = (float(gain_db_range), float(gain_db_range))
+        elif gain_db_range is not None:
+            gain_db_range = tuple(float(v) for v in gain_db_range)
+        noise_db = cfg.get("noise_db", None)
+        noise_db = float(noise_db) if noise_db is not None else None
+        keep_original_when_zero = bool(cfg.get("keep_zero_pitch", True))
+        hop = int(self.mel_params["hop_length"])
+
+        for attempt in range(max_attempts):
+            available_paths = [p for p in self.data_list if p not in self._invalid_paths]
+            if not available_paths:
+                if force and attempt == max_attempts - 1:
+                    raise RuntimeError("No valid audio files available for pitch shifting")
+                return None
+            base_path = random.choice(available_paths)
+            try:
+                wave, wave_sr = read_wav(base_path)
+            except (RuntimeError, OSError, ValueError, struct.error) as exc:
+                self._invalid_paths.add(base_path)
+                logger.warning("[MelDataset] Skipping unreadable audio file: %s (%s)", base_path, exc)
+                continue
+            if wave.ndim > 1:
+                wave = np.mean(wave, axis=-1)
+            wave = wave.astype(np.float32)
+            n = Resampler(wave_sr, self.sr).out_len(len(wave)) if wave_sr != self.sr else len(wave)
+            try:
+                base_f0 = self._f0_for(base_path, wave, 0, None)
+            except RuntimeError as exc:          # the reference falls back to an empty track when F0 fails
+                logger.warning("[MelDataset] %s", exc)
+                base_f0 = np.zeros((0,), dtype=np.float32)
+            if base_f0.size == 0:
+                continue
+            voiced_fraction = float(np.count_nonzero(base_f0 > 0)) / max(1, base_f0.size)
+            if voiced_fraction < min_voiced_fraction:
+                continue
+            semitone = random.choice(semitone_choices)
+            if semitone == 0 and not force:
+                continue
+
+            ratio = float(2 ** (semitone / 12.0))
+            shifted_f0 = base_f0.astype(np.float32) * ratio
+            if keep_original_when_zero:
+                shifted_f0[base_f0 == 0] = 0.0
+            gain = 1.0
+            if gain_db_range is not None:
+                low, high = gain_db_range
+                if low > high:
+                    low, high = high, low
+                gain = 10.0 ** (random.uniform(low, high) / 20.0)
+            noise = None
+            if noise_db is not None:
+                noise = np.random.normal(scale=10.0 ** (noise_db / 20.0), size=(n,)).astype(np.float32)
+
+            # _build_training_example (meldataset.py:629-677) with caches off
+            mel_len = 1 + n // hop
+            f0 = align_length(shifted_f0, mel_len)
+            sil = (f0 == 0).astype(np.float32)
+            crop = 0
+            if mel_len > self.max_mel_length:
+                crop = int(np.random.randint(0, mel_len - self.max_mel_length))
+                f0 = f0[crop:crop + self.max_mel_length]
+                sil = sil[crop:crop + self.max_mel_length]
+            f0 = np.where(np.isnan(f0), np.float32(self.zero_value), f0).astype(np.float32)
+            start, count, first = synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
+            req = PitchShiftRequest(base_path, float(semitone), float(gain), int(n), crop, start, count, first,
+                                    None if noise is None else np.ascontiguousarray(noise[start:start + count]))
+            return torch.from_numpy(wave), torch.from_numpy(f0), torch.from_numpy(sil), first, int(wave_sr), req
+        return None
 
     # ---- labels ---------------------------------------------------------------------------
     def _f0_cache_paths(self, path):
@@ -432,6 +623,8 @@ class MelDataset(torch.utils.data.Dataset):
         return wave, f0, sil, crop
 
     def __getitem__(self, idx):
+        if self.synthetic_enabled and idx >= self._base_length:
+            return self._generate_synthetic_sample()
         total = len(self.data_list)
         if total == 0:
             raise IndexError("MelDataset is empty")
@@ -470,7 +663,9 @@ class Collater(object):
     Accepts the reference's ``(mel (80,L), f0, is_silence)`` items, or this build's raw-audio items
     ``(wave (N,), f0, is_silence, crop_start[, source_sr[, cached_mel (80,L<=192)]])``; for the latter it returns
     host tensors ``(waves (B,Nmax), lengths, crop_starts, f0s, is_silences, source_sr)`` for the device mel stage,
-    followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram."""
+    followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram and by a
+    ``PitchShiftBatch`` when any item is a pitch-shifted one.  A synthetic row's waveform is left zero (the device
+    writes its shifted window there) and its length is that window's; its base file is packed, not padded."""
 
     def __init__(self, return_wave=False):
         self.return_wave = return_wave
@@ -491,7 +686,9 @@ class Collater(object):
                 f0s[i, :n] = f0
                 sils[i, :n] = sil
             return mels.unsqueeze(1), f0s, sils
-        n_max = max(int(item[0].shape[0]) for item in batch)
+        syn = [i for i, item in enumerate(batch) if isinstance(item[-1], PitchShiftRequest)]
+        n_max = max(int(item[-1].out_len) if isinstance(item[-1], PitchShiftRequest) else int(item[0].shape[0])
+                    for item in batch)
         waves = torch.zeros((B, n_max), dtype=torch.float32)
         lengths = torch.zeros((B,), dtype=torch.int32)
         crops = torch.zeros((B,), dtype=torch.int32)
@@ -500,20 +697,34 @@ class Collater(object):
             raise RuntimeError(f"one batch mixes source sample rates {sorted(rates)}: group files by rate")
         for i, item in enumerate(batch):
             wave, f0, sil, crop = item[:4]
-            n = wave.shape[0]
-            waves[i, :n] = wave
+            if isinstance(item[-1], PitchShiftRequest):
+                n = item[-1].out_len
+            else:
+                n = wave.shape[0]
+                waves[i, :n] = wave
             lengths[i] = n
             crops[i] = int(crop)
             f0s[i, :f0.shape[0]] = f0
             sils[i, :sil.shape[0]] = sil
         out = (waves, lengths, crops, f0s, sils, (rates.pop() if rates else 0))
-        rows = [i for i, item in enumerate(batch) if len(item) > 5]
+        rows = [i for i, item in enumerate(batch) if len(item) > 5 and torch.is_tensor(item[5])]
         if rows:                                       # normalised, cropped cache rows, zero-padded like :812-816
             cached = torch.zeros((len(rows), batch[rows[0]][5].shape[0], L), dtype=torch.float32)
             for k, i in enumerate(rows):
                 m = batch[i][5]
                 cached[k, :, :m.shape[1]] = m
             out += (torch.tensor(rows, dtype=torch.int64), cached)
+        if syn:
+            reqs = [batch[i][-1] for i in syn]
+            noise = None
+            if reqs[0].noise is not None:
+                noise = torch.from_numpy(np.concatenate([r.noise for r in reqs]).astype(np.float32))
+            i64 = lambda v: torch.tensor(v, dtype=torch.int64)  # noqa: E731
+            out += (PitchShiftBatch(i64(syn), torch.cat([batch[i][0].reshape(-1) for i in syn]),
+                                    i64([int(batch[i][0].shape[0]) for i in syn]), i64([r.n for r in reqs]),
+                                    torch.tensor([r.n_steps for r in reqs], dtype=torch.float32),
+                                    torch.tensor([r.gain for r in reqs], dtype=torch.float32),
+                                    i64([r.out_start for r in reqs]), i64([r.out_len for r in reqs]), noise),)
         return out
 
 
@@ -530,8 +741,12 @@ class H2DPrefetcher:
         self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
 
     def submit(self, host_items):
+        def to_dev(t):
+            if isinstance(t, PitchShiftBatch):
+                return PitchShiftBatch(*(to_dev(x) for x in t))
+            return t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t
         with torch.cuda.stream(self.stream):
-            dev = tuple(t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t for t in host_items)
+            dev = tuple(to_dev(t) for t in host_items)
             ready = torch.cuda.Event()
             ready.record(self.stream)
         return dev, ready
@@ -541,8 +756,9 @@ class H2DPrefetcher:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ready)
         for t in dev:
-            if torch.is_tensor(t) and t.is_cuda:
-                t.record_stream(cur)              # allocated on the side stream, consumed on the compute stream
+            for x in (t if isinstance(t, PitchShiftBatch) else (t,)):
+                if torch.is_tensor(x) and x.is_cuda:
+                    x.record_stream(cur)          # allocated on the side stream, consumed on the compute stream
         return dev
 
 
@@ -565,8 +781,31 @@ class DeviceMelLoader:
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)
 
+    def _pitch_shift(self, waves, lengths, src_sr, pack, host):
+        """Synthetic rows: resample their packed base files (if needed), shift them and write each row's window."""
+        sr = self.mel.sample_rate
+        src = pack.src
+        if src_sr and src_sr != sr:
+            rs = self._resamplers.setdefault(src_sr, Resampler(src_sr, sr))
+            offs = np.concatenate([[0], np.cumsum(host.src_len.numpy())])
+            src = torch.cat([rs(src[int(offs[k]):int(offs[k + 1])]) for k in range(len(offs) - 1)])
+        need = int(host.out_len.max())
+        if waves.shape[1] < need:
+            waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
+        waves = waves.contiguous()
+        n = host.n.numpy()
+        res_type = (getattr(self.dataset, "synthetic_pitch_shift_config", None) or {}).get("resample_type",
+                                                                                            "kaiser_best")
+        pitch_shift_ragged(src, np.concatenate([[0], np.cumsum(n)[:-1]]), n, host.n_steps.numpy(), pack.gains, waves,
+                           host.rows.numpy(), host.out_start.numpy(), host.out_len.numpy(), sr=sr, res_type=res_type,
+                           noise=pack.noise)
+        lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
+        return waves, lengths
+
     def _finish(self, ticket):
         waves, lengths, crops, f0s, sils, src_sr, *cached = self._h2d.acquire(ticket)
+        pack = cached.pop() if cached and isinstance(cached[-1], PitchShiftBatch) else None
+        host_pack = self._host_packs.pop(0)
         if src_sr and src_sr != self.mel.sample_rate:
             rs = self._resamplers.setdefault(src_sr, Resampler(src_sr, self.mel.sample_rate))
             waves = rs(waves)                                 # zero-padded rows resample exactly like each item alone
@@ -574,6 +813,8 @@ class DeviceMelLoader:
                                    device=self.device)
         else:
             self._host_lengths.pop(0)
+        if pack is not None:                                  # after the resampler, before the one mel launch
+            waves, lengths = self._pitch_shift(waves, lengths, src_sr, pack, host_pack)
         mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
         if cached:                                            # rows whose spectrogram came from <wav>_mel.npy
             rows, cached_mels = cached
@@ -590,10 +831,11 @@ class DeviceMelLoader:
                 from .model import _side_stream
                 shared = _side_stream(self.device)
             self._h2d = H2DPrefetcher(self.device, stream=shared)
-        self._host_lengths = []
+        self._host_lengths, self._host_packs = [], []
         pending = None
         for host in self.loader:
             self._host_lengths.append(host[1].tolist())
+            self._host_packs.append(host[-1] if isinstance(host[-1], PitchShiftBatch) else None)
             ticket = self._h2d.submit(host)
             if pending is not None:
                 yield self._finish(pending)
