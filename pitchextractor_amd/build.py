@@ -37,23 +37,16 @@ def _needs(target: Path, deps) -> bool:
     return any(d.stat().st_mtime > t for d in deps)
 
 
-# sources whose single-term ("mixed precision") MFMA pipelines are compiled a second time for fp16 operands
-# (-DPE_F16_BUILD: same kernels, v_cvt_f16_f32 / v_mfma_f32_32x32x16_f16, exports pe_*_f16 only)
-F16_SOURCES = ("gemm", "conv", "lstm", "lstm_persistent")
-
-
 # per-source flags.  lstm_persistent: the cell / gate updates are issued in the shadow of MFMAs, where hipcc's SLP
 # packing of adjacent scalar f32 operations into v_pk_* costs more issue time than it saves (MI355X guide, constants
 # table; measured: forward item 11.4 -> 10.7 k cycles)
 EXTRA_FLAGS = {"lstm_persistent": ["-fno-slp-vectorize"]}      # (gemm.hip / lstm.hip: no difference, measured)
 
 
-def _compile(job, verbose: bool) -> Path:
-    src, f16 = job
-    obj = OBJ_DIR / (src.stem + ("_f16" if f16 else "") + ".o")
+def _compile(src: Path, verbose: bool) -> Path:
+    obj = OBJ_DIR / (src.stem + ".o")
     if _needs(obj, [src] + _headers() + [Path(__file__)]):
-        cmd = [HIPCC, *CXXFLAGS, *EXTRA_FLAGS.get(src.stem, []), *(["-DPE_F16_BUILD"] if f16 else []), "-c", str(src),
-               "-o", str(obj)]
+        cmd = [HIPCC, *CXXFLAGS, *EXTRA_FLAGS.get(src.stem, []), "-c", str(src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
@@ -68,9 +61,8 @@ def build_library(force: bool = False, verbose: bool = True, jobs: int = 4) -> P
     srcs = _sources()
     if not srcs:
         raise RuntimeError(f"no .hip sources under {CSRC}")
-    work = [(s, False) for s in srcs] + [(s, True) for s in srcs if s.stem in F16_SOURCES]
     with ThreadPoolExecutor(max_workers=jobs) as ex:
-        objs = list(ex.map(lambda j: _compile(j, verbose), work))
+        objs = list(ex.map(lambda s: _compile(s, verbose), srcs))
     if force or _needs(LIB_PATH, objs):
         cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
                "-o", str(LIB_PATH), *map(str, objs)]

@@ -63,7 +63,7 @@ template <class TO> __device__ __forceinline__ float stored_value(float v) {
   else return __uint_as_float(pack_bf16_rne(v, 0.f) << 16);
 }
 
-template <class TL, int MODE, class TA = float>
+template <class TL, int MODE, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256) void conv3x3_kernel(ConvLoader<TL::A_LOADS, TA> al, RowLoader bl, ConvEpiT<TA> ep,
                                                       int K, int tiles_m, int tiles_n, const unsigned* amax_x,
                                                       const unsigned* amax_w) {
@@ -77,11 +77,11 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvLoader<TL::A_LOADS, TA
   zero_acc<TL>(acc);
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_x, amax_w);
-  nt_mainloop_mode<TL, MODE>(al, bl, K, As, Bs, acc, hs.sa, hs.sb);
+  nt_mainloop_mode<TL, MODE, false, 1, TH>(al, bl, K, As, Bs, acc, hs.sa, hs.sb);
   for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? v * hs.inv : v); });
 }
 
-template <class TL, int MODE, class TA = float>
+template <class TL, int MODE, class TA = float, class TH = __bf16>
 int launch_conv(const TA* x, const float* wp, TA* y, int B, int T, int F, int C, int N, int accumulate,
                 hipStream_t st, const unsigned* amax_x = nullptr, const unsigned* amax_w = nullptr) {
   const int rows = B * T * F, K = 9 * C;
@@ -90,7 +90,7 @@ int launch_conv(const TA* x, const float* wp, TA* y, int B, int T, int F, int C,
   RowLoader bl{wp, (long)K, N, K, 0};
   ConvEpiT<TA> ep{y, rows, N, accumulate, nullptr};
   const int tm = pe_cdiv(rows, TL::BM), tn = pe_cdiv(N, TL::BN);
-  hipLaunchKernelGGL((conv3x3_kernel<TL, MODE, TA>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn, amax_x,
+  hipLaunchKernelGGL((conv3x3_kernel<TL, MODE, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn, amax_x,
                      amax_w);
   PE_LAUNCH_CHECK();
   return PE_OK;
@@ -121,7 +121,7 @@ int launch_conv(const TA* x, const float* wp, TA* y, int B, int T, int F, int C,
 // D steps ahead of the MFMAs that consume them.  LDS holds only the activation window: two barriers per
 // channel chunk (9 taps = 18 k-blocks) instead of per tap, no weight split, no weight LDS traffic.
 //   fragment (kb, nb, c), lane l = 32 h + r  <->  B[n = 32 nb + r][k = 16 kb + 8 h .. + 7] of term c.
-template <int NT>
+template <int NT, class TH = __bf16>
 __global__ void wfrag_pack_kernel(const float* __restrict__ w, long ld, int N, int K, uint4* __restrict__ out,
                                   const unsigned* __restrict__ amax = nullptr) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -148,27 +148,28 @@ __global__ void wfrag_pack_kernel(const float* __restrict__ w, long ld, int N, i
     dst[0] = make_uint4(a.hi.x, a.hi.y, b.hi.x, b.hi.y);
     dst[64] = make_uint4(a.lo.x, a.lo.y, b.lo.x, b.lo.y);
   } else {
-    const bf16x4 a = to_bf16x4(v0), b = to_bf16x4(v1);
+    const half4<TH> a = to_half4<TH>(v0), b = to_half4<TH>(v1);
     const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
     dst[0] = make_uint4(ua.x, ua.y, ub.x, ub.y);
   }
 }
 
-template <int BN, int MODE, int PASSES, int D, bool FA2, class TA = float>
+template <int BN, int MODE, int PASSES, int D, bool FA2, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __restrict__ x,
                                                                  const uint4* __restrict__ wf, ConvEpiT<TA> ep, int T,
                                                                  int F, int C, int N, int P, int tiles_m,
                                                                  int tiles_n, const unsigned* amax_x,
                                                                  const unsigned* amax_w) {
   constexpr int NT = mode_terms<MODE>();
+  using H = term_t<NT, TH>;
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_x, amax_w);
   constexpr int TM = 2, TN = BN / 64, WN = BN / 2;
   constexpr int ZR = PASSES * 32;                                  // an all-zero row behind the window
-  constexpr int AIMG = (ZR + 4) * 32;                              // bf16 elements per image
+  constexpr int AIMG = (ZR + 4) * 32;                              // 16-bit elements per image
   constexpr int S = 18 * TN;                                       // steps (tap, kk, j) per channel chunk
   static_assert(S % D == 0 && D >= 2, "the fragment ring wraps at chunk boundaries");
-  __shared__ __attribute__((aligned(16))) __bf16 As[NT * AIMG];
+  __shared__ __attribute__((aligned(16))) H As[NT * AIMG];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1, r = lane & 31, h = lane >> 5;
   const int tile = xcd_remap(blockIdx.x, tiles_m * tiles_n);
@@ -234,13 +235,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
     const int nb = (n0 + wn * WN + j * 32) >> 5;
     vow[j] = (unsigned)(((nb < NB32 ? nb : NB32 - 1) * NT * 64 + lane) * 16);
   }
-  bf16x8 ring[D][NT];
+  half8<H> ring[D][NT];
   auto issue = [&](int slot, int cc, int s) {                      // s = (tap * 2 + kk) * TN + j
     const int j = s % TN, kk = (s / TN) & 1, tap = s / (2 * TN);
     const unsigned so = (unsigned)((tap * kb_tap + cc * 2 + kk) * kb_stride) * 16u;      // wave-uniform
 #pragma unroll
     for (int c = 0; c < NT; ++c)
-      ring[slot][c] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, vow[j], so + (unsigned)c * 1024u, 0));
+      ring[slot][c] = __builtin_bit_cast(half8<H>, __builtin_amdgcn_raw_buffer_load_b128(wrs, vow[j], so + (unsigned)c * 1024u, 0));
   };
 
   f32x16 acc[TM][TN];
@@ -259,14 +260,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
 #pragma unroll
   for (int s = 0; s < D - 1; ++s) issue(s, 0, s);
 
-  auto load_fa = [&](bf16x8 (&fa)[TM][NT], int tap, int kk) {
+  auto load_fa = [&](half8<H> (&fa)[TM][NT], int tap, int kk) {
     const int shift = (tap / 3) * F + tap % 3;                     // (F + 1) + (dt * F + df)
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int row = (vbits[i] >> tap) & 1u ? wm * 64 + i * 32 + r + shift : ZR;
 #pragma unroll
       for (int c = 0; c < NT; ++c)
-        fa[i][c] = *reinterpret_cast<const bf16x8*>(As + c * AIMG + swz_off(row, kk * 2 + h));
+        fa[i][c] = *reinterpret_cast<const half8<H>*>(As + c * AIMG + swz_off(row, kk * 2 + h));
     }
   };
 
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
     __syncthreads();
     if (cc + 1 < nchunks) fetch_a(cc + 1);
     // FA2: the activation fragments of the next k-block are read under this block's MFMAs (24 more registers)
-    bf16x8 fa[FA2 ? 2 : 1][TM][NT];
+    half8<H> fa[FA2 ? 2 : 1][TM][NT];
     if (FA2) load_fa(fa[0], 0, 0);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -350,14 +351,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
   }
 }
 
-template <int BN, int MODE, int PASSES, int D, bool FA2, class TA = float>
+template <int BN, int MODE, int PASSES, int D, bool FA2, class TA = float, class TH = __bf16>
 int launch_conv_halo_wf(const TA* x, const void* wf, TA* y, int B, int T, int F, int C, int N, int accumulate,
                         double* stats, hipStream_t st, const unsigned* amax_x = nullptr,
                         const unsigned* amax_w = nullptr) {
   const int P = B * T * F;
   ConvEpiT<TA> ep{y, P, N, accumulate, stats};
   const int tm = pe_cdiv(P, 128), tn = pe_cdiv(N, BN);
-  hipLaunchKernelGGL((conv3x3_halo_wf_kernel<BN, MODE, PASSES, D, FA2, TA>), dim3(tm * tn), dim3(256), 0, st, x,
+  hipLaunchKernelGGL((conv3x3_halo_wf_kernel<BN, MODE, PASSES, D, FA2, TA, TH>), dim3(tm * tn), dim3(256), 0, st, x,
                      reinterpret_cast<const uint4*>(wf), ep, T, F, C, N, P, tm, tn, amax_x, amax_w);
   PE_LAUNCH_CHECK();
   return PE_OK;
@@ -527,7 +528,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_kernel(const float* __r
 // of one channel) come from ds_read_b64_tr_b16, and the border mask becomes a 16-bit AND mask per pixel:
 // Mk16[d][w][k] covers source row k + d of window w for column shift df = d - 1, so the 8 masks of a
 // fragment are one aligned 16-byte read.
-template <int NT, class TA = float>   // NT: 3 = exact three-term split, 2 = two scaled fp16 terms, 1 = operands rounded to bf16
+// NT: 3 = exact three-term split, 2 = two scaled fp16 terms, 1 = operands rounded to TH
+template <int NT, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __restrict__ dy,
                                                                    const TA* __restrict__ x,
                                                                    float* __restrict__ ws, int T, int F, int Cin,
@@ -535,10 +537,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
                                                                    const unsigned* amax_dy, const unsigned* amax_x) {
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (NT == 2) hs.load(amax_dy, amax_x);
-  constexpr int ST = 96;                                   // bf16 elements per staged row
+  using H = term_t<NT, TH>;
+  constexpr int ST = 96;                                   // 16-bit elements per staged row
   constexpr int YIMG = kBK * ST, XIMG = 102 * ST;
-  __shared__ __attribute__((aligned(16))) __bf16 Ys[NT * YIMG];
-  __shared__ __attribute__((aligned(16))) __bf16 Xs[NT * XIMG];
+  __shared__ __attribute__((aligned(16))) H Ys[NT * YIMG];
+  __shared__ __attribute__((aligned(16))) H Xs[NT * XIMG];
   __shared__ __attribute__((aligned(16))) unsigned short Mk16[9 * kBK];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1, r = lane & 31, h = lane >> 5;
@@ -587,9 +590,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
 #pragma unroll
     for (int i = 0; i < 7; ++i) rx[i] = ldraw_buffer<TA>(rsx, vox[i] + dlt, 0u);
   };
-  auto store3 = [&](__bf16* img, int img_elems, int off, const Raw& raw, float scale) {
+  auto store3 = [&](H* img, int img_elems, int off, const Raw& raw, float scale) {
     if constexpr (NT == 1 && !std::is_same<TA, float>::value) {
-      *reinterpret_cast<Raw*>(img + off) = raw;              // bf16 tensor, one rounded term: the bits as they are
+      *reinterpret_cast<half4<H>*>(img + off) = to_half4<H>(raw);   // bf16 tensor, one rounded term: the bits as they are
       return;
     }
     const float4 v = widen(raw);
@@ -603,12 +606,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
       *reinterpret_cast<uint2*>(img + off) = sp.hi;
       *reinterpret_cast<uint2*>(img + off + img_elems) = sp.lo;
     } else {
-      *reinterpret_cast<bf16x4*>(img + off) = to_bf16x4(v);
+      *reinterpret_cast<half4<H>*>(img + off) = to_half4<H>(v);
     }
   };
   fetch(kb);
-  const __bf16* a_rd = Ys + (8 * h + q4) * ST + wm * 32 + 16 * g1 + p4;
-  const __bf16* b_rd = Xs + (8 * h + q4) * ST + wn * 32 + 16 * g1 + p4;
+  const H* a_rd = Ys + (8 * h + q4) * ST + wm * 32 + 16 * g1 + p4;
+  const H* b_rd = Xs + (8 * h + q4) * ST + wn * 32 + 16 * g1 + p4;
   for (int k0 = kb; k0 < ke; k0 += kBK) {
     __syncthreads();
 #pragma unroll
@@ -639,7 +642,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
     if (k0 + kBK < ke) fetch(k0 + kBK);
 #pragma unroll
     for (int kk = 0; kk < kBK / 16; ++kk) {
-      bf16x8 fa[NT];
+      half8<H> fa[NT];
 #pragma unroll
       for (int c = 0; c < NT; ++c) fa[c] = tr_fragment(a_rd + c * YIMG + kk * 16 * ST, ST);
 #pragma unroll
@@ -647,12 +650,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
           const uint4 mk = *reinterpret_cast<const uint4*>(Mk16 + (d * 3 + w) * kBK + kk * 16 + 8 * h);
-          bf16x8 fb[NT];
+          half8<H> fb[NT];
 #pragma unroll
           for (int c = 0; c < NT; ++c) {
             uint4 v = __builtin_bit_cast(uint4, tr_fragment(b_rd + c * XIMG + (w * 34 + kk * 16 + d) * ST, ST));
             v.x &= mk.x; v.y &= mk.y; v.z &= mk.z; v.w &= mk.w;
-            fb[c] = __builtin_bit_cast(bf16x8, v);
+            fb[c] = __builtin_bit_cast(half8<H>, v);
           }
           acc[w * 3 + d] = mfma_terms<NT>(fa, fb, acc[w * 3 + d]);
         }
@@ -853,7 +856,6 @@ constexpr int kC1WgradBlocks = 2048;
 
 }  // namespace
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_conv3x3_repack(const float* w_oihw, float* w_fwd, float* w_dgrad, int Cout, int Cin,
                                  void* stream) {
   if (!w_oihw || Cout <= 0 || Cin <= 0) return PE_E_ARG;
@@ -871,9 +873,8 @@ extern "C" int pe_transpose2d(const float* in, float* out, int rows, int cols, v
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
-#endif
 
-template <int MODE, class TA = float>
+template <int MODE, class TA = float, class TH = __bf16>
 static int conv3x3_fwd_impl(const TA* x, const float* w_packed, TA* y, int B, int T, int F, int C, int N,
                             int accumulate, void* stream, const unsigned* amax_x = nullptr,
                             const unsigned* amax_w = nullptr) {
@@ -882,25 +883,27 @@ static int conv3x3_fwd_impl(const TA* x, const float* w_packed, TA* y, int B, in
   if (MODE == kSplit2 && (!amax_x || !amax_w)) return PE_E_ARG;
   hipStream_t st = pe_stream(stream);
   if (N <= 64)
-    return launch_conv<Tile<256, 64, 4, 1>, MODE, TA>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
+    return launch_conv<Tile<256, 64, 4, 1>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
   if (N % 192 == 0 && N % 128 != 0)
-    return launch_conv<Tile<128, 192, 2, 2>, MODE, TA>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
-  return launch_conv<Tile<128, 128, 2, 2>, MODE, TA>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
+    return launch_conv<Tile<128, 192, 2, 2>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
+  return launch_conv<Tile<128, 128, 2, 2>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_conv3x3_fwd(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
                               int accumulate, void* stream) {
   return conv3x3_fwd_impl<kNative>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
 }
-#endif
 
-extern "C" int PE_HALF(pe_conv3x3_fwd)(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
+extern "C" int pe_conv3x3_fwd_bf16(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
                                    int N, int accumulate, void* stream) {
   return conv3x3_fwd_impl<kBf16>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
 }
 
-#ifndef PE_F16_BUILD
+extern "C" int pe_conv3x3_fwd_f16(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
+                                  int N, int accumulate, void* stream) {
+  return conv3x3_fwd_impl<kBf16, float, _Float16>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
+}
+
 extern "C" int pe_conv3x3_fwd_x3(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
                                  int N, int accumulate, void* stream) {
   return conv3x3_fwd_impl<kSplit>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
@@ -910,16 +913,15 @@ extern "C" int pe_conv3x3_fwd_h2(const float* x, const float* w_packed, float* y
                                  int N, int accumulate, const unsigned* amax_x, const unsigned* amax_w, void* stream) {
   return conv3x3_fwd_impl<kSplit2>(x, w_packed, y, B, T, F, C, N, accumulate, stream, amax_x, amax_w);
 }
-#endif
 
-// ---- weights pre-packed as MFMA fragments (x3: three bf16 terms; bf16: one rounded term)
-#ifndef PE_F16_BUILD
+// ---- weights pre-packed as MFMA fragments (x3: three bf16 terms; bf16 / fp16: one rounded term)
 extern "C" size_t pe_wfrag_bytes(int N, int K, int terms) {
   if (N <= 0 || K <= 0 || (K & 15) || terms < 1 || terms > 3) return 0;
   return (size_t)((N + 31) / 32) * (K / 16) * terms * 1024;
 }
 
-extern "C" int pe_wfrag_pack(const float* w, long ld, int N, int K, int terms, void* out, void* stream) {
+template <class TH = __bf16>   // TH: the type of the one rounded term (terms = 1)
+static int wfrag_pack_impl(const float* w, long ld, int N, int K, int terms, void* out, void* stream) {
   if (!w || !out || N <= 0 || K <= 0 || ld < K) return PE_E_ARG;
   if ((K & 15) || (ld & 3) || (terms != 1 && terms != 3)) return PE_E_UNSUPPORTED;
   const long threads = (long)((N + 31) / 32) * (K / 16) * 64;
@@ -927,10 +929,19 @@ extern "C" int pe_wfrag_pack(const float* w, long ld, int N, int K, int terms, v
     hipLaunchKernelGGL(wfrag_pack_kernel<3>, dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld, N, K,
                        reinterpret_cast<uint4*>(out));
   else
-    hipLaunchKernelGGL(wfrag_pack_kernel<1>, dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld, N, K,
-                       reinterpret_cast<uint4*>(out));
+    hipLaunchKernelGGL((wfrag_pack_kernel<1, TH>), dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld,
+                       N, K, reinterpret_cast<uint4*>(out));
   PE_LAUNCH_CHECK();
   return PE_OK;
+}
+
+extern "C" int pe_wfrag_pack(const float* w, long ld, int N, int K, int terms, void* out, void* stream) {
+  return wfrag_pack_impl(w, ld, N, K, terms, out, stream);
+}
+
+// one RNE-rounded fp16 term per weight, same fragment order as pe_wfrag_pack(..., terms = 1, ...)
+extern "C" int pe_wfrag_pack_f16(const float* w, long ld, int N, int K, void* out, void* stream) {
+  return wfrag_pack_impl<_Float16>(w, ld, N, K, 1, out, stream);
 }
 
 // two scaled fp16 terms per weight ("h2"): the scale comes from *amax (pe_absmax of w)
@@ -950,21 +961,8 @@ extern "C" int pe_conv3x3_wf_supported(int F, int C, int N) {
 
 // number of per-tile BatchNorm partials pe_conv3x3_fwd_wf_* writes: bn_partials is [parts][2][N] doubles
 extern "C" int pe_conv3x3_wf_stat_parts(int B, int T, int F) { return pe_cdiv((long)B * T * F, 128); }
-#endif
 
-#ifdef PE_F16_BUILD
-// fp16 build: one RNE-rounded fp16 term per weight, same fragment order as pe_wfrag_pack(..., terms = 1, ...)
-extern "C" int pe_wfrag_pack_f16(const float* w, long ld, int N, int K, void* out, void* stream) {
-  if (!w || !out || N <= 0 || K <= 0 || ld < K) return PE_E_ARG;
-  if ((K & 15) || (ld & 3)) return PE_E_UNSUPPORTED;
-  const long threads = (long)((N + 31) / 32) * (K / 16) * 64;
-  hipLaunchKernelGGL(wfrag_pack_kernel<1>, dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld, N, K,
-                     reinterpret_cast<uint4*>(out));
-  PE_LAUNCH_CHECK();
-  return PE_OK;
-}
-#endif
-template <int MODE, class TA = float>
+template <int MODE, class TA = float, class TH = __bf16>
 static int conv3x3_fwd_wf_impl(const TA* x, const void* wfrag, TA* y, int B, int T, int F, int C, int N,
                                int accumulate, double* stats, void* stream, const unsigned* amax_x = nullptr,
                                const unsigned* amax_w = nullptr) {
@@ -977,19 +975,18 @@ static int conv3x3_fwd_wf_impl(const TA* x, const void* wfrag, TA* y, int B, int
   hipStream_t st = pe_stream(stream);
   const int passes = conv_halo_passes(F, N);
   if (passes == 10)
-    return launch_conv_halo_wf<64, MODE, 10, 6, true, TA>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
+    return launch_conv_halo_wf<64, MODE, 10, 6, true, TA, TH>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
                                                           amax_w);
   if (passes == 7) {
     if (N % 192 == 0 && N % 128 != 0)
-      return launch_conv_halo_wf<192, MODE, 7, 3, false, TA>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
+      return launch_conv_halo_wf<192, MODE, 7, 3, false, TA, TH>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
                                                              amax_w);
-    return launch_conv_halo_wf<128, MODE, 7, 3, true, TA>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
+    return launch_conv_halo_wf<128, MODE, 7, 3, true, TA, TH>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
                                                           amax_w);
   }
   return PE_E_UNSUPPORTED;
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_conv3x3_fwd_wf_x3(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
                                     int accumulate, double* bn_partials, void* stream) {
   return conv3x3_fwd_wf_impl<kSplit>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream);
@@ -1000,23 +997,25 @@ extern "C" int pe_conv3x3_fwd_wf_h2(const float* x, const void* wfrag, float* y,
                                     const unsigned* amax_w, void* stream) {
   return conv3x3_fwd_wf_impl<kSplit2>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream, amax_x, amax_w);
 }
-#endif
 
-extern "C" int PE_HALF(pe_conv3x3_fwd_wf)(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
+extern "C" int pe_conv3x3_fwd_wf_bf16(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
                                       int accumulate, double* bn_partials, void* stream) {
   return conv3x3_fwd_wf_impl<kBf16>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream);
 }
 
-#ifndef PE_F16_BUILD
+extern "C" int pe_conv3x3_fwd_wf_f16(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
+                                     int accumulate, double* bn_partials, void* stream) {
+  return conv3x3_fwd_wf_impl<kBf16, float, _Float16>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream);
+}
+
 extern "C" size_t pe_conv3x3_wgrad_workspace_bytes(int B, int T, int F, int Cin, int Cout) {
   if (Cin == 1) return (size_t)kC1WgradBlocks * 576 * sizeof(float);
   int bm, bn, splits, kps;
   wgrad_plan(B * T * F, Cout, Cin, &bm, &bn, &splits, &kps);
   return (size_t)splits * 9 * Cout * Cin * sizeof(float);
 }
-#endif
 
-template <int MODE, class TA = float>
+template <int MODE, class TA = float, class TH = __bf16>
 static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, int T, int F, int Cin,
                               int Cout, float* workspace, size_t workspace_bytes, void* stream,
                               const unsigned* amax_x = nullptr, const unsigned* amax_dy = nullptr) {
@@ -1036,7 +1035,7 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
       hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<2, TA>), dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
                          workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
     else if (MODE == kBf16)
-      hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<1, TA>), dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
+      hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<1, TA, TH>), dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
                          workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
     else if constexpr (std::is_same<TA, float>::value)
       hipLaunchKernelGGL(conv3x3_wgrad9_kernel<0>, dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
@@ -1058,19 +1057,22 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
   return PE_E_UNSUPPORTED;
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_conv3x3_wgrad(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
                                 int Cout, float* workspace, size_t workspace_bytes, void* stream) {
   return conv3x3_wgrad_impl<kNative>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
 }
-#endif
 
-extern "C" int PE_HALF(pe_conv3x3_wgrad)(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
+extern "C" int pe_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
                                      int Cout, float* workspace, size_t workspace_bytes, void* stream) {
   return conv3x3_wgrad_impl<kBf16>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
 }
 
-#ifndef PE_F16_BUILD
+extern "C" int pe_conv3x3_wgrad_f16(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
+                                    int Cout, float* workspace, size_t workspace_bytes, void* stream) {
+  return conv3x3_wgrad_impl<kBf16, float, _Float16>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes,
+                                                     stream);
+}
+
 // ---- mixed precision with bf16 ACTIVATION STORAGE (x, y, dy are bf16 tensors in HBM; weights / gradients fp32)
 extern "C" int pe_conv3x3_fwd_bf16_a16(const void* x, const float* w_packed, void* y, int B, int T, int F, int C, int N,
                                        int accumulate, void* stream) {
@@ -1089,9 +1091,7 @@ extern "C" int pe_conv3x3_wgrad_bf16_a16(const void* x, const void* dy, float* d
   return conv3x3_wgrad_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), dw_oihw,
                                             B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
 }
-#endif
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_conv3x3_wgrad_x3(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
                                    int Cout, float* workspace, size_t workspace_bytes, void* stream) {
   return conv3x3_wgrad_impl<kSplit>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
@@ -1163,4 +1163,3 @@ extern "C" int pe_conv3x3_c1_wgrad_a16(const float* x, long sb, long st, long sf
   return conv3x3_c1_wgrad_impl<act16_t>(x, sb, st, sf, static_cast<const act16_t*>(dy), dw_oihw, B, T, F, workspace,
                                         workspace_bytes, stream);
 }
-#endif

@@ -36,7 +36,7 @@ struct StoreEpiT {
 };
 typedef StoreEpiT<float> StoreEpi;
 
-template <class TL, int MODE, class TA = float>
+template <class TL, int MODE, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K,
                                                       int tiles_m, int tiles_n, const unsigned* amax_a,
                                                       const unsigned* amax_b) {
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(RowLoaderT<TA> al, RowLoad
   zero_acc<TL>(acc);
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
-  nt_mainloop_mode<TL, MODE>(al, bl, K, As, Bs, acc, hs.sa, hs.sb);
+  nt_mainloop_mode<TL, MODE, false, 1, TH>(al, bl, K, As, Bs, acc, hs.sa, hs.sb);
   for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? v * hs.inv : v); });
 }
 
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(RowLoaderT<TA> al, RowLoad
 // columns of one row instead of four rows of one column, and the epilogue writes 16-byte pieces (a quarter of the
 // store instructions, bias fetched once per column quad).  Bit-identical sums.  Needs N % 4 == 0 and a 16-byte
 // aligned C with ldc % 4 == 0 (checked by the host).
-template <class TL, int MODE, class TA = float>
+template <class TL, int MODE, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256, ((MODE == kSplit || MODE == kSplit2) && TL::BM == 128 && TL::BN == 128) ? 3 : 1)
 void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, int tiles_m, int tiles_n,
                       const unsigned* amax_a, const unsigned* amax_b) {
@@ -74,7 +74,7 @@ void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, 
   zero_acc<TT>(acc);
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
-  nt_mainloop_mode<TT, MODE, true>(bl, al, K, Bs, As, acc, hs.sb, hs.sa);
+  nt_mainloop_mode<TT, MODE, true, 1, TH>(bl, al, K, Bs, As, acc, hs.sb, hs.sa);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wn = wv / TT::WAVES_N, wm = wv % TT::WAVES_N;          // TT's "rows" are output columns
   const int r = lane & 31, h = lane >> 5;
@@ -102,24 +102,24 @@ void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, 
     }
 }
 
-template <class TL, int MODE, class TA = float>
+template <class TL, int MODE, class TA = float, class TH = __bf16>
 int launch_nt(const RowLoaderT<TA>& al, const RowLoader& bl, const StoreEpiT<TA>& ep, int M, int N, int K,
               hipStream_t st, const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr) {
   const int tm = pe_cdiv(M, TL::BM), tn = pe_cdiv(N, TL::BN);
   const bool vec = MODE != kNative && (N & 3) == 0 && (ep.ldc & 3) == 0 &&
                    (reinterpret_cast<uintptr_t>(ep.C) & (4 * sizeof(TA) - 1)) == 0;
   if (vec)
-    hipLaunchKernelGGL((gemm_nt_t_kernel<TL, MODE, TA>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn,
+    hipLaunchKernelGGL((gemm_nt_t_kernel<TL, MODE, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn,
                        amax_a, amax_b);
   else
-    hipLaunchKernelGGL((gemm_nt_kernel<TL, MODE, TA>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn, amax_a,
+    hipLaunchKernelGGL((gemm_nt_kernel<TL, MODE, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn, amax_a,
                        amax_b);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
 
 // ---- TN with split-K
-template <int BM, int BN, int MODE, class TA = float>
+template <int BM, int BN, int MODE, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(KRowLoader<BM, TA> al, KRowLoader<BN, TA> bl, float* out,
                                                       long ldo, long split_stride, int M, int N, int K,
                                                       int k_per_split, int tiles_n, int accumulate,
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(KRowLoader<BM, TA> al, KRo
       for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
-  tn_mainloop_mode<MODE, BM, BN>(al, bl, kb, ke, As, Bs, acc, hs.sa, hs.sb);
+  tn_mainloop_mode<MODE, BM, BN, 1, TH>(al, bl, kb, ke, As, Bs, acc, hs.sa, hs.sb);
   float* dst = out + (long)split_id * split_stride;
   tn_for_each_acc<BM, BN>(acc, [&](int r, int c, float v) {
     const int row = m0 + r, col = n0 + c;
@@ -181,7 +181,7 @@ void tn_plan(int M, int N, int K, int bm, int bn, int mode, int* splits, int* k_
   *k_per_split = kps;
 }
 
-template <int BM, int BN, int MODE, class TA = float>
+template <int BM, int BN, int MODE, class TA = float, class TH = __bf16>
 int launch_tn(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, int M, int N, int K,
               int accumulate, float* ws, size_t ws_bytes, hipStream_t st, const unsigned* amax_a = nullptr,
               const unsigned* amax_b = nullptr) {
@@ -191,14 +191,14 @@ int launch_tn(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, 
   KRowLoader<BN, TA> bl{B, ldb, N, 0};
   const int tm = pe_cdiv(M, BM), tn = pe_cdiv(N, BN);
   if (splits == 1) {
-    hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, MODE, TA>), dim3(tm * tn, 1), dim3(256), 0, st, al, bl, C, ldc, 0L, M, N,
+    hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, MODE, TA, TH>), dim3(tm * tn, 1), dim3(256), 0, st, al, bl, C, ldc, 0L, M, N,
                        K, kps, tn, accumulate, amax_a, amax_b);
     PE_LAUNCH_CHECK();
     return PE_OK;
   }
   const size_t need = (size_t)splits * M * N * sizeof(float);
   if (!ws || ws_bytes < need) return PE_E_WORKSPACE;
-  hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, MODE, TA>), dim3(tm * tn * splits), dim3(256), 0, st, al, bl, ws, (long)N,
+  hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, MODE, TA, TH>), dim3(tm * tn * splits), dim3(256), 0, st, al, bl, ws, (long)N,
                      (long)M * N, M, N, K, kps, tn, 0, amax_a, amax_b);
   PE_LAUNCH_CHECK();
   const long total = (long)M * N;
@@ -210,7 +210,7 @@ int launch_tn(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, 
 
 }  // namespace
 
-template <int MODE, class TA = float>
+template <int MODE, class TA = float, class TH = __bf16>
 static int gemm_nt_impl(const TA* A, long lda, const float* B, long ldb, TA* C, long ldc, int M, int N,
                         int K, const float* bias0, const float* bias1, int accumulate, void* stream,
                         const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr) {
@@ -225,36 +225,35 @@ static int gemm_nt_impl(const TA* A, long lda, const float* B, long ldb, TA* C, 
   RowLoader bl{B, ldb, N, K, 0};
   StoreEpiT<TA> ep{C, ldc, bias0, bias1, M, N, accumulate};
   hipStream_t st = pe_stream(stream);
-  if (N <= 32) return launch_nt<Tile<128, 32, 4, 1>, MODE, TA>(al, bl, ep, M, N, K, st, amax_a, amax_b);
-  if (N <= 64) return launch_nt<Tile<256, 64, 4, 1>, MODE, TA>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+  if (N <= 32) return launch_nt<Tile<128, 32, 4, 1>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+  if (N <= 64) return launch_nt<Tile<256, 64, 4, 1>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
   if (N % 192 == 0 && (N % 128 != 0 || MODE != kNative))   // 16-bit-term modes: the wider tile stages 17 % fewer rows per MFMA
-    return launch_nt<Tile<128, 192, 2, 2>, MODE, TA>(al, bl, ep, M, N, K, st, amax_a, amax_b);
-  return launch_nt<Tile<128, 128, 2, 2>, MODE, TA>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+    return launch_nt<Tile<128, 192, 2, 2>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+  return launch_nt<Tile<128, 128, 2, 2>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                           int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
   return gemm_nt_impl<kNative>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
 }
-#endif
 
-extern "C" int PE_HALF(pe_gemm_nt)(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M,
-                               int N, int K, const float* bias0, const float* bias1, int accumulate,
-                               void* stream) {
+extern "C" int pe_gemm_nt_bf16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
+                               int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
   return gemm_nt_impl<kBf16>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
 }
 
-#ifndef PE_F16_BUILD
+extern "C" int pe_gemm_nt_f16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
+                              int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
+  return gemm_nt_impl<kBf16, float, _Float16>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
+}
+
 // mixed precision with bf16 ACTIVATION STORAGE: A and C are bf16 tensors in HBM (weights and biases stay fp32)
 extern "C" int pe_gemm_nt_bf16_a16(const void* A, long lda, const float* B, long ldb, void* C, long ldc, int M, int N,
                                    int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
   return gemm_nt_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, B, ldb, static_cast<act16_t*>(C), ldc, M, N,
                                       K, bias0, bias1, accumulate, stream);
 }
-#endif
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_gemm_nt_x3(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                              int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
   return gemm_nt_impl<kSplit>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
@@ -265,9 +264,7 @@ extern "C" int pe_gemm_nt_h2(const float* A, long lda, const float* B, long ldb,
                              const unsigned* amax_b, void* stream) {
   return gemm_nt_impl<kSplit2>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream, amax_a, amax_b);
 }
-#endif
 
-#ifndef PE_F16_BUILD
 extern "C" size_t pe_gemm_tn_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   size_t need = 0;
@@ -279,9 +276,8 @@ extern "C" size_t pe_gemm_tn_workspace_bytes(int M, int N, int K) {
   }
   return need;
 }
-#endif
 
-template <int MODE, class TA = float>
+template <int MODE, class TA = float, class TH = __bf16>
 static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, int M, int N,
                         int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream,
                         const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr) {
@@ -294,19 +290,18 @@ static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, 
   if (lda < 0 || ldb < 0 || lda >= (1L << 24) || ldb >= (1L << 24)) return PE_E_UNSUPPORTED;   // 32-bit offsets per k-tile
   hipStream_t st = pe_stream(stream);
   if (M <= 64 && N <= 64)
-    return launch_tn<64, 64, MODE, TA>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+    return launch_tn<64, 64, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
                                    amax_b);
   if (M <= 64)
-    return launch_tn<64, 128, MODE, TA>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+    return launch_tn<64, 128, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
                                     amax_b);
   if (N <= 64)
-    return launch_tn<128, 64, MODE, TA>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+    return launch_tn<128, 64, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
                                     amax_b);
-  return launch_tn<128, 128, MODE, TA>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+  return launch_tn<128, 128, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
                                    amax_b);
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                           int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
   return gemm_tn_impl<kNative>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
@@ -323,17 +318,20 @@ extern "C" int pe_gemm_tn_h2(const float* A, long lda, const float* B, long ldb,
   return gemm_tn_impl<kSplit2>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream, amax_a,
                                amax_b);
 }
-#endif
 
-extern "C" int PE_HALF(pe_gemm_tn)(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
+extern "C" int pe_gemm_tn_bf16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
                                int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
   return gemm_tn_impl<kBf16>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
 }
 
-#ifndef PE_F16_BUILD
+extern "C" int pe_gemm_tn_f16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
+                              int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
+  return gemm_tn_impl<kBf16, float, _Float16>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes,
+                                              stream);
+}
+
 extern "C" int pe_gemm_tn_bf16_a16(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N,
                                    int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
   return gemm_tn_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, static_cast<const act16_t*>(B), ldb, C, ldc,
                                       M, N, K, accumulate, workspace, workspace_bytes, stream);
 }
-#endif

@@ -16,6 +16,7 @@
 // B operand lane l holds B[k = l >> 5][j = l & 31]; accumulator register g of lane l is
 // C[row = (g & 3) + 8 * (g >> 2) + 4 * (l >> 5)][col = l & 31].
 #pragma once
+#include <type_traits>
 #include <utility>
 #include "act16.h"
 
@@ -24,7 +25,7 @@ namespace pe {
 constexpr int kBK = 32;
 // precision modes of the tile engines
 constexpr int kNative = 0;    // v_mfma_f32_32x32x2_f32
-constexpr int kBf16 = 1;      // operands rounded to bf16 (mixed precision)
+constexpr int kBf16 = 1;      // operands rounded to one 16-bit type, bf16 or fp16 (mixed precision)
 constexpr int kSplit = 2;     // fp32 as three bf16 terms, six bf16 MFMAs per product block (fp32-accurate)
 constexpr int kSplit2 = 3;    // fp32 as two scaled fp16 terms, three fp16 MFMAs per product block ("h2", below)
 template <int MODE> constexpr int mode_terms() { return MODE == kSplit ? 3 : MODE == kSplit2 ? 2 : 1; }
@@ -174,51 +175,53 @@ __device__ __forceinline__ void nt_mainloop(AL& al, BL& bl, int K, float* As, fl
   }
 }
 
-// ------------------------------------------------------------------ NT main loop, bf16 operands
+// ------------------------------------------------------------------ NT main loop, 16-bit operands
 // Opt-in "mixed precision" variant (reference trainer.py:103 autocast): the fp32 operands are rounded
-// to bf16 (RNE, v_cvt_pk_bf16_f32) on their way into LDS and multiplied with
-// v_mfma_f32_32x32x16_bf16; accumulation, epilogue and every tensor in HBM stay fp32.
-// LDS images are [row][40] bf16 (32 + one 16-byte pad): lane (r, h) reads k = 16*kk + 8*h .. +7 of
+// (RNE) to a 16-bit operand type TH on their way into LDS and multiplied with v_mfma_f32_32x32x16_*;
+// accumulation, epilogue and every tensor in HBM stay fp32.
+// LDS images are [row][40] 16-bit elements (32 + one 16-byte pad): lane (r, h) reads k = 16*kk + 8*h .. +7 of
 // row r with one ds_read_b128, which is exactly the 32x32x16 A/B operand layout.
-// The single-term ("mixed precision") pipelines exist for two 16-bit operand types: bf16 (the default build) and
-// fp16 = the reference's literal autocast dtype (trainer.py:64-102).  The fp16 form is the SAME source compiled a
-// second time with -DPE_F16_BUILD (pitchextractor_amd/build.py): only the conversion instruction and the MFMA
-// opcode differ, and that build exports only the pe_*_f16 entry points (PE_HALF names).  The three-term split
-// paths are bf16 by construction and are not exported from the fp16 build.
-#ifdef PE_F16_BUILD
-typedef _Float16 pe_half_t;
-#define PE_HALF(name) name##_f16
-#else
-typedef __bf16 pe_half_t;
-#define PE_HALF(name) name##_bf16
-#endif
-typedef pe_half_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef pe_half_t bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int kLdsStrideH = kBK + 8;   // in bf16 elements
+// The single-term ("mixed precision") pipelines exist for two operand types, a template parameter of every kernel
+// that runs them: TH = __bf16 (the default) or _Float16 = the reference's literal autocast dtype (trainer.py:64-102).
+// Only the conversion instruction and the MFMA opcode differ.  The three-term split is bf16 and the two-term split
+// fp16 by construction, whatever TH says.
+template <class H> using half8 = H __attribute__((ext_vector_type(8)));
+template <class H> using half4 = H __attribute__((ext_vector_type(4)));
+typedef half8<__bf16> bf16x8;
+typedef half8<_Float16> f16x8;
+constexpr int kLdsStrideH = kBK + 8;   // in 16-bit elements
 
-__device__ __forceinline__ bf16x4 to_bf16x4(const float4& v) {     // RNE to the build's 16-bit operand type
-  bf16x4 o;
-  o[0] = (pe_half_t)v.x; o[1] = (pe_half_t)v.y; o[2] = (pe_half_t)v.z; o[3] = (pe_half_t)v.w;
+// element type of the NT 16-bit terms of a product: 3 = bf16 split, 2 = fp16 split, 1 = the operand type TH
+template <int NT, class TH> using term_t =
+    std::conditional_t<NT == 3, __bf16, std::conditional_t<NT == 2, _Float16, TH>>;
+
+template <class H>
+__device__ __forceinline__ half4<H> to_half4(const float4& v) {     // the LDS image's four operands: RNE of fp32 data
+  half4<H> o;
+  o[0] = (H)v.x; o[1] = (H)v.y; o[2] = (H)v.z; o[3] = (H)v.w;
   return o;
 }
 
-// the LDS image's four 16-bit operands of a raw quad: fp32 data is rounded (RNE); bf16 data is already there
-__device__ __forceinline__ bf16x4 to_half4(const float4& v) { return to_bf16x4(v); }
-__device__ __forceinline__ bf16x4 to_half4(const uint2& raw) { return __builtin_bit_cast(bf16x4, raw); }
-
-__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
-#ifdef PE_F16_BUILD
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-#else
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-#endif
+// the same for a quad that is still in its bf16 storage form: the bits are already the operands
+template <class H>
+__device__ __forceinline__ half4<H> to_half4(const uint2& raw) {
+  static_assert(std::is_same<H, __bf16>::value, "bf16 activation storage takes bf16 operands only");
+  return __builtin_bit_cast(half4<H>, raw);
 }
 
-template <class TL, class AL, class BL>
-__device__ __forceinline__ void nt_mainloop_bf16(AL& al, BL& bl, int K, float* As_f, float* Bs_f,
+// one 32x32x16 MFMA; the operand type picks the opcode
+__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+template <class TL, class TH, class AL, class BL>
+__device__ __forceinline__ void nt_mainloop_half(AL& al, BL& bl, int K, float* As_f, float* Bs_f,
                                                  f32x16 (&acc)[TL::TM][TL::TN]) {
-  __bf16* As = reinterpret_cast<__bf16*>(As_f);
-  __bf16* Bs = reinterpret_cast<__bf16*>(Bs_f);
+  TH* As = reinterpret_cast<TH*>(As_f);
+  TH* Bs = reinterpret_cast<TH*>(Bs_f);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv / TL::WAVES_N, wn = wv % TL::WAVES_N;
   const int r = lane & 31, h = lane >> 5;
@@ -231,17 +234,17 @@ __device__ __forceinline__ void nt_mainloop_bf16(AL& al, BL& bl, int K, float* A
   for (int i = 0; i < TL::B_LOADS; ++i) rb[i] = bl.load(i, 0);
 
   const int st_off = (tid >> 3) * kLdsStrideH + (tid & 7) * 4;
-  const __bf16* a_rd = As + (wm * TL::WM + r) * kLdsStrideH + h * 8;
-  const __bf16* b_rd = Bs + (wn * TL::WN + r) * kLdsStrideH + h * 8;
+  const TH* a_rd = As + (wm * TL::WM + r) * kLdsStrideH + h * 8;
+  const TH* b_rd = Bs + (wn * TL::WN + r) * kLdsStrideH + h * 8;
 
   for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < TL::A_LOADS; ++i)
-      *reinterpret_cast<bf16x4*>(As + st_off + i * 32 * kLdsStrideH) = to_half4(ra[i]);
+      *reinterpret_cast<half4<TH>*>(As + st_off + i * 32 * kLdsStrideH) = to_half4<TH>(ra[i]);
 #pragma unroll
     for (int i = 0; i < TL::B_LOADS; ++i)
-      *reinterpret_cast<bf16x4*>(Bs + st_off + i * 32 * kLdsStrideH) = to_half4(rb[i]);
+      *reinterpret_cast<half4<TH>*>(Bs + st_off + i * 32 * kLdsStrideH) = to_half4<TH>(rb[i]);
     __syncthreads();
     if (kt + 1 < nk) {
 #pragma unroll
@@ -251,18 +254,18 @@ __device__ __forceinline__ void nt_mainloop_bf16(AL& al, BL& bl, int K, float* A
     }
 #pragma unroll
     for (int kk = 0; kk < kBK / 16; ++kk) {
-      bf16x8 fa[TL::TM], fb[TL::TN];
+      half8<TH> fa[TL::TM], fb[TL::TN];
 #pragma unroll
       for (int i = 0; i < TL::TM; ++i)
-        fa[i] = *reinterpret_cast<const bf16x8*>(a_rd + i * 32 * kLdsStrideH + kk * 16);
+        fa[i] = *reinterpret_cast<const half8<TH>*>(a_rd + i * 32 * kLdsStrideH + kk * 16);
 #pragma unroll
       for (int j = 0; j < TL::TN; ++j)
-        fb[j] = *reinterpret_cast<const bf16x8*>(b_rd + j * 32 * kLdsStrideH + kk * 16);
+        fb[j] = *reinterpret_cast<const half8<TH>*>(b_rd + j * 32 * kLdsStrideH + kk * 16);
 #pragma unroll
       for (int i = 0; i < TL::TM; ++i)
 #pragma unroll
         for (int j = 0; j < TL::TN; ++j)
-          acc[i][j] = mfma_bf16(fa[i], fb[j], acc[i][j]);
+          acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
     }
   }
 }
@@ -299,23 +302,23 @@ __device__ __forceinline__ Split3 split3(const float4& v) {
 
 // acc += a * b to fp32 accuracy, a and b given as their three bf16 terms
 __device__ __forceinline__ f32x16 mfma_split(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
-  c = mfma_bf16(a[2], b[0], c);
-  c = mfma_bf16(a[0], b[2], c);
-  c = mfma_bf16(a[1], b[1], c);
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[0], b[0], c);
+  c = mfma16(a[2], b[0], c);
+  c = mfma16(a[0], b[2], c);
+  c = mfma16(a[1], b[1], c);
+  c = mfma16(a[1], b[0], c);
+  c = mfma16(a[0], b[1], c);
+  c = mfma16(a[0], b[0], c);
   return c;
 }
 
 // the same six products in the same order when the caller has swapped the roles of its two operands
 __device__ __forceinline__ f32x16 mfma_split_swapped(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
-  c = mfma_bf16(a[0], b[2], c);
-  c = mfma_bf16(a[2], b[0], c);
-  c = mfma_bf16(a[1], b[1], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[0], c);
+  c = mfma16(a[0], b[2], c);
+  c = mfma16(a[2], b[0], c);
+  c = mfma16(a[1], b[1], c);
+  c = mfma16(a[0], b[1], c);
+  c = mfma16(a[1], b[0], c);
+  c = mfma16(a[0], b[0], c);
   return c;
 }
 
@@ -330,12 +333,6 @@ __device__ __forceinline__ f32x16 mfma_split_swapped(const bf16x8 (&a)[3], const
 // (pe_absmax, or the producing kernel's epilogue): max |x| s lies in [2^13, 2^14), hi stays a normal fp16 down to
 // 2^-28 of the tensor's maximum and a subnormal with absolute resolution 2^-38 max below that.  The epilogue
 // multiplies the accumulator by 1 / (s_a s_b), again a power of two: nothing but exponents change.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_f16(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // scale of a tensor whose largest magnitude has the IEEE bits `amax_bits` (sign bit clear)
 __device__ __host__ __forceinline__ unsigned h2_scale_exp(unsigned amax_bits) {
   int es = 267 - (int)((amax_bits >> 23) & 0xffu);                  // biased exponent of 2^(140 - E)
@@ -382,26 +379,27 @@ __device__ __forceinline__ Split2 split2(const float4& v, float s) {
 }
 
 // acc += a * b from the two fp16 terms of each operand, small products first
-__device__ __forceinline__ f32x16 mfma_split2(const bf16x8 (&a)[2], const bf16x8 (&b)[2], f32x16 c) {
-  c = mfma_f16(a[1], b[0], c);
-  c = mfma_f16(a[0], b[1], c);
-  c = mfma_f16(a[0], b[0], c);
+__device__ __forceinline__ f32x16 mfma_split2(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x16 c) {
+  c = mfma16(a[1], b[0], c);
+  c = mfma16(a[0], b[1], c);
+  c = mfma16(a[0], b[0], c);
   return c;
 }
 // the same three products in the same order when the caller has swapped the roles of its two operands
-__device__ __forceinline__ f32x16 mfma_split2_swapped(const bf16x8 (&a)[2], const bf16x8 (&b)[2], f32x16 c) {
-  c = mfma_f16(a[0], b[1], c);
-  c = mfma_f16(a[1], b[0], c);
-  c = mfma_f16(a[0], b[0], c);
+__device__ __forceinline__ f32x16 mfma_split2_swapped(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x16 c) {
+  c = mfma16(a[0], b[1], c);
+  c = mfma16(a[1], b[0], c);
+  c = mfma16(a[0], b[0], c);
   return c;
 }
 
-// product block of an NT-term operand pair: NT = 3 bf16 split, 2 fp16 split, 1 rounded 16-bit operands
-template <int NT, bool SW = false>
-__device__ __forceinline__ f32x16 mfma_terms(const bf16x8 (&a)[NT], const bf16x8 (&b)[NT], f32x16 c) {
+// product block of an NT-term operand pair (V = half8<term_t<NT, TH>>): NT = 3 bf16 split, 2 fp16 split, 1 rounded
+// 16-bit operands
+template <int NT, bool SW = false, class V>
+__device__ __forceinline__ f32x16 mfma_terms(const V (&a)[NT], const V (&b)[NT], f32x16 c) {
   if constexpr (NT == 3) return SW ? mfma_split_swapped(a, b, c) : mfma_split(a, b, c);
   else if constexpr (NT == 2) return SW ? mfma_split2_swapped(a, b, c) : mfma_split2(a, b, c);
-  else return mfma_bf16(a[0], b[0], c);
+  else return mfma16(a[0], b[0], c);
 }
 
 // bf16-term images [row][32 k] with NO padding: 16-byte chunk c of a row sits at chunk c ^ ((row >> 2) & 3), which
@@ -411,9 +409,9 @@ __device__ __forceinline__ int swz_off(int row, int chunk) {        // in bf16 e
   return row * 32 + ((chunk ^ ((row >> 2) & 3)) << 3);
 }
 
-// 4 consecutive k (piece = float4 index 0..7 within the 32-k row) of one row -> NT term images
-template <int NT>
-__device__ __forceinline__ void halo_store(__bf16* img, int img_elems, int row, int piece, const float4& v,
+// 4 consecutive k (piece = float4 index 0..7 within the 32-k row) of one row -> NT term images of type H
+template <int NT, class H>
+__device__ __forceinline__ void halo_store(H* img, int img_elems, int row, int piece, const float4& v,
                                            float scale = 1.0f) {
   const int off = swz_off(row, piece >> 1) + (piece & 1) * 4;
   if constexpr (NT == 3) {
@@ -426,26 +424,27 @@ __device__ __forceinline__ void halo_store(__bf16* img, int img_elems, int row, 
     *reinterpret_cast<uint2*>(img + off) = sp.hi;
     *reinterpret_cast<uint2*>(img + off + img_elems) = sp.lo;
   } else {
-    *reinterpret_cast<bf16x4*>(img + off) = to_bf16x4(v);
+    *reinterpret_cast<half4<H>*>(img + off) = to_half4<H>(v);
   }
 }
 
 // the same for a quad that is still in its bf16 storage form: one rounded term needs no arithmetic at all
-template <int NT>
-__device__ __forceinline__ void halo_store(__bf16* img, int img_elems, int row, int piece, const uint2& raw,
+template <int NT, class H>
+__device__ __forceinline__ void halo_store(H* img, int img_elems, int row, int piece, const uint2& raw,
                                            float scale = 1.0f) {
-  if constexpr (NT == 1) *reinterpret_cast<uint2*>(img + swz_off(row, piece >> 1) + (piece & 1) * 4) = raw;
+  if constexpr (NT == 1) *reinterpret_cast<half4<H>*>(img + swz_off(row, piece >> 1) + (piece & 1) * 4) = to_half4<H>(raw);
   else halo_store<NT>(img, img_elems, row, piece, widen(raw), scale);
 }
 
-template <class TL, bool SW = false, int NT = 3, int PF = 1, class AL, class BL>
+template <class TL, bool SW = false, int NT = 3, int PF = 1, class TH = __bf16, class AL, class BL>
 __device__ __forceinline__ void nt_mainloop_split(AL& al, BL& bl, int K, float* As_f, float* Bs_f,
                                                   f32x16 (&acc)[TL::TM][TL::TN], float sa = 1.0f, float sb = 1.0f) {
   // unpadded, XOR-swizzled term images (swz_off): 64 B per row and term, so a 128 x 128 tile takes 48 KB (three
   // terms) and three workgroups share a CU (the padded 80-byte rows allowed two)
   constexpr int A_IMG = TL::BM * kBK, B_IMG = TL::BN * kBK;   // 16-bit elements per image
-  __bf16* As = reinterpret_cast<__bf16*>(As_f);
-  __bf16* Bs = reinterpret_cast<__bf16*>(Bs_f);
+  using H = term_t<NT, TH>;
+  H* As = reinterpret_cast<H*>(As_f);
+  H* Bs = reinterpret_cast<H*>(Bs_f);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv / TL::WAVES_N, wn = wv % TL::WAVES_N;
   const int r = lane & 31, h = lane >> 5;
@@ -483,17 +482,17 @@ __device__ __forceinline__ void nt_mainloop_split(AL& al, BL& bl, int K, float* 
     if constexpr (PF == 2) __builtin_amdgcn_sched_barrier(0);   // requests first, then the products: nothing of the next stage up here
 #pragma unroll
     for (int kk = 0; kk < kBK / 16; ++kk) {
-      bf16x8 fa[TL::TM][NT], fb[TL::TN][NT];
+      half8<H> fa[TL::TM][NT], fb[TL::TN][NT];
 #pragma unroll
       for (int i = 0; i < TL::TM; ++i)
 #pragma unroll
         for (int c = 0; c < NT; ++c)
-          fa[i][c] = *reinterpret_cast<const bf16x8*>(As + c * A_IMG + swz_off(wm * TL::WM + i * 32 + r, kk * 2 + h));
+          fa[i][c] = *reinterpret_cast<const half8<H>*>(As + c * A_IMG + swz_off(wm * TL::WM + i * 32 + r, kk * 2 + h));
 #pragma unroll
       for (int j = 0; j < TL::TN; ++j)
 #pragma unroll
         for (int c = 0; c < NT; ++c)
-          fb[j][c] = *reinterpret_cast<const bf16x8*>(Bs + c * B_IMG + swz_off(wn * TL::WN + j * 32 + r, kk * 2 + h));
+          fb[j][c] = *reinterpret_cast<const half8<H>*>(Bs + c * B_IMG + swz_off(wn * TL::WN + j * 32 + r, kk * 2 + h));
 #pragma unroll
       for (int i = 0; i < TL::TM; ++i)
 #pragma unroll
@@ -524,10 +523,10 @@ template <int MODE> constexpr int nt_row_floats() {
   return MODE == kSplit ? kSplitRowFloats : MODE == kSplit2 ? 2 * kBK / 2 : kLdsStride;
 }
 
-template <class TL, int MODE, bool SW = false, int PF = 1, class AL, class BL>
+template <class TL, int MODE, bool SW = false, int PF = 1, class TH = __bf16, class AL, class BL>
 __device__ __forceinline__ void nt_mainloop_mode(AL& al, BL& bl, int K, float* As, float* Bs,
                                                  f32x16 (&acc)[TL::TM][TL::TN], float sa = 1.0f, float sb = 1.0f) {
-  if constexpr (MODE == kBf16) nt_mainloop_bf16<TL>(al, bl, K, As, Bs, acc);
+  if constexpr (MODE == kBf16) nt_mainloop_half<TL, TH>(al, bl, K, As, Bs, acc);
   else if constexpr (MODE == kSplit) nt_mainloop_split<TL, SW, 3, PF>(al, bl, K, As, Bs, acc);
   else if constexpr (MODE == kSplit2) nt_mainloop_split<TL, SW, 2, PF>(al, bl, K, As, Bs, acc, sa, sb);
   else nt_mainloop<TL>(al, bl, K, As, Bs, acc);
@@ -710,23 +709,25 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <int COLS> constexpr int tn_split_stride() { return COLS + 32; }                 // bf16 elements per k-row
 template <int COLS, int NT = 3> constexpr int tn_split_floats() { return NT * kBK * tn_split_stride<COLS>() / 2; }
 
-__device__ __forceinline__ s16x4 lds_read_tr(const __bf16* p) {
+template <class H>
+__device__ __forceinline__ s16x4 lds_read_tr(const H* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4*)(reinterpret_cast<const short*>(p)));
 }
 
 // fragment of 16 k-rows starting at `p` (this lane's block-row address for rows +0..3; rows +4..7 one
 // 4-row block further): elements j = 0..7 <-> k = 8h + j
-__device__ __forceinline__ bf16x8 tr_fragment(const __bf16* p, int stride) {
+template <class H>
+__device__ __forceinline__ half8<H> tr_fragment(const H* p, int stride) {
   const s16x4 lo = lds_read_tr(p), hi = lds_read_tr(p + 4 * stride);
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return __builtin_bit_cast(half8<H>, v);
 }
 
-// NT = 3: the exact three-term split; 2: two scaled fp16 terms; 1: operands rounded to bf16 (mixed precision)
-template <int COLS, int NT>
-__device__ __forceinline__ void tn_split_store(__bf16* img, int off, const float4& v, float scale = 1.0f) {
+// NT = 3: the exact three-term split; 2: two scaled fp16 terms; 1: operands rounded to H (mixed precision)
+template <int COLS, int NT, class H>
+__device__ __forceinline__ void tn_split_store(H* img, int off, const float4& v, float scale = 1.0f) {
   constexpr int IMG = kBK * tn_split_stride<COLS>();
   if constexpr (NT == 3) {
     const Split3 sp = split3(v);
@@ -738,25 +739,26 @@ __device__ __forceinline__ void tn_split_store(__bf16* img, int off, const float
     *reinterpret_cast<uint2*>(img + off) = sp.hi;
     *reinterpret_cast<uint2*>(img + off + IMG) = sp.lo;
   } else {
-    *reinterpret_cast<bf16x4*>(img + off) = to_bf16x4(v);
+    *reinterpret_cast<half4<H>*>(img + off) = to_half4<H>(v);
   }
 }
 
-template <int COLS, int NT>
-__device__ __forceinline__ void tn_split_store(__bf16* img, int off, const uint2& raw, float scale = 1.0f) {
-  if constexpr (NT == 1) *reinterpret_cast<uint2*>(img + off) = raw;
+template <int COLS, int NT, class H>
+__device__ __forceinline__ void tn_split_store(H* img, int off, const uint2& raw, float scale = 1.0f) {
+  if constexpr (NT == 1) *reinterpret_cast<half4<H>*>(img + off) = to_half4<H>(raw);
   else tn_split_store<COLS, NT>(img, off, widen(raw), scale);
 }
 
-template <int BM, int BN, int NT, int PF = 1, class AL, class BL>
+template <int BM, int BN, int NT, int PF = 1, class TH = __bf16, class AL, class BL>
 __device__ __forceinline__ void tn_mainloop_split(AL& al, BL& bl, int k_begin, int k_end, float* As_f, float* Bs_f,
                                                   f32x16 (&acc)[BM / 64][BN / 64], float sa = 1.0f, float sb = 1.0f) {
   constexpr int TM = BM / 64, TN = BN / 64;
   constexpr int SA = TnGeom<BM>::SLOTS, SB = TnGeom<BN>::SLOTS;
   constexpr int STA = tn_split_stride<BM>(), STB = tn_split_stride<BN>();
   constexpr int IMGA = kBK * STA, IMGB = kBK * STB;
-  __bf16* As = reinterpret_cast<__bf16*>(As_f);
-  __bf16* Bs = reinterpret_cast<__bf16*>(Bs_f);
+  using H = term_t<NT, TH>;
+  H* As = reinterpret_cast<H*>(As_f);
+  H* Bs = reinterpret_cast<H*>(Bs_f);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1;
   const int h = lane >> 5, g1 = (lane >> 4) & 1, q = (lane & 15) >> 2, p4 = (lane & 3) * 4;
@@ -772,8 +774,8 @@ __device__ __forceinline__ void tn_mainloop_split(AL& al, BL& bl, int k_begin, i
   }
   const int sta = (tid / TnGeom<BM>::TPR) * STA + TnGeom<BM>::col4();
   const int stb = (tid / TnGeom<BN>::TPR) * STB + TnGeom<BN>::col4();
-  const __bf16* a_rd = As + (8 * h + q) * STA + wm * (BM / 2) + 16 * g1 + p4;
-  const __bf16* b_rd = Bs + (8 * h + q) * STB + wn * (BN / 2) + 16 * g1 + p4;
+  const H* a_rd = As + (8 * h + q) * STA + wm * (BM / 2) + 16 * g1 + p4;
+  const H* b_rd = Bs + (8 * h + q) * STB + wn * (BN / 2) + 16 * g1 + p4;
   auto tile = [&](auto uc, int k0) {
     constexpr int u = decltype(uc)::value;
     __syncthreads();
@@ -791,7 +793,7 @@ __device__ __forceinline__ void tn_mainloop_split(AL& al, BL& bl, int k_begin, i
     if constexpr (PF == 2) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int kk = 0; kk < kBK / 16; ++kk) {
-      bf16x8 fa[TM][NT], fb[TN][NT];
+      half8<H> fa[TM][NT], fb[TN][NT];
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -822,12 +824,12 @@ template <int MODE, int COLS> constexpr int tn_lds_floats() {
        : MODE == kBf16 ? tn_split_floats<COLS, 1>() : kBK * COLS;
 }
 
-template <int MODE, int BM, int BN, int PF = 1, class AL, class BL>
+template <int MODE, int BM, int BN, int PF = 1, class TH = __bf16, class AL, class BL>
 __device__ __forceinline__ void tn_mainloop_mode(AL& al, BL& bl, int k_begin, int k_end, float* As, float* Bs,
                                                  f32x16 (&acc)[BM / 64][BN / 64], float sa = 1.0f, float sb = 1.0f) {
   if constexpr (MODE == kSplit) tn_mainloop_split<BM, BN, 3, PF>(al, bl, k_begin, k_end, As, Bs, acc);
   else if constexpr (MODE == kSplit2) tn_mainloop_split<BM, BN, 2, PF>(al, bl, k_begin, k_end, As, Bs, acc, sa, sb);
-  else if constexpr (MODE == kBf16) tn_mainloop_split<BM, BN, 1, PF>(al, bl, k_begin, k_end, As, Bs, acc);
+  else if constexpr (MODE == kBf16) tn_mainloop_split<BM, BN, 1, PF, TH>(al, bl, k_begin, k_end, As, Bs, acc);
   else tn_mainloop<BM, BN>(al, bl, k_begin, k_end, As, Bs, acc);
 }
 

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const BwdCells cells
 }
 
 // ------------------------------------------------------------------ dW_hh = sum_t dgates_t^T h_{t-1}
-template <int BM, int BN, int MODE>
+template <int BM, int BN, int MODE, class TH = __bf16>
 __global__ __launch_bounds__(256) void lstm_whh_grad_kernel(KRowLoader<BM> al, ShiftedTimeLoader<BN> bl, float* out,
                                                             long ldo, long split_stride, int M, int N, int K,
                                                             int k_per_split, int tiles_n, const unsigned* amax_a,
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void lstm_whh_grad_kernel(KRowLoader<BM> al, S
       for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
-  tn_mainloop_mode<MODE, BM, BN>(al, bl, kb, ke, As, Bs, acc, hs.sa, hs.sb);
+  tn_mainloop_mode<MODE, BM, BN, 1, TH>(al, bl, kb, ke, As, Bs, acc, hs.sa, hs.sb);
   float* dst = out + (long)split_id * split_stride;
   tn_for_each_acc<BM, BN>(acc, [&](int r, int c, float v) {
     const int row = m0 + r, col = n0 + c;
@@ -294,7 +294,6 @@ constexpr int kColsumParts = 256;
 
 }  // namespace
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_lstm_fwd(int ncells, const float* const* whh, float* const* gates, float* const* y,
                            float* const* cbuf, const int* reverse, long ldy, int B, int T, int H, void* stream) {
   if (ncells < 1 || ncells > kMaxCells || !whh || !gates || !y || !cbuf || !reverse) return PE_E_ARG;
@@ -346,10 +345,9 @@ extern "C" size_t pe_lstm_whh_grad_workspace_bytes(int B, int T, int H) {
   }
   return need;
 }
-#endif
 
 // dW_hh[4H][H] = sum_{b,t} dgates[b][t][:]^T . y[b][t -/+ 1][:]   (y = this direction's output slice)
-template <int MODE>
+template <int MODE, class TH = __bf16>
 static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
                          int reverse, float* workspace, size_t workspace_bytes, void* stream,
                          const unsigned* amax_dg = nullptr, const unsigned* amax_y = nullptr) {
@@ -366,7 +364,7 @@ static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* d
   bl.p = y; bl.ld = ldy; bl.T = T; bl.dt = reverse ? 1 : -1; bl.cols = N; bl.col0 = 0;
   const int tm = pe_cdiv(M, 128), tn = pe_cdiv(N, 128);
   hipStream_t st = pe_stream(stream);
-  hipLaunchKernelGGL((lstm_whh_grad_kernel<128, 128, MODE>), dim3(tm * tn * splits), dim3(256), 0, st, al, bl,
+  hipLaunchKernelGGL((lstm_whh_grad_kernel<128, 128, MODE, TH>), dim3(tm * tn * splits), dim3(256), 0, st, al, bl,
                      workspace, (long)N, (long)M * N, M, N, K, kps, tn, amax_dg, amax_y);
   PE_LAUNCH_CHECK();
   const long n = (long)M * N;
@@ -375,7 +373,6 @@ static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* d
   return PE_OK;
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_lstm_whh_grad(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
                                 int reverse, float* workspace, size_t workspace_bytes, void* stream) {
   return whh_grad_impl<kNative>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
@@ -392,19 +389,20 @@ extern "C" int pe_lstm_whh_grad_h2(const float* dgates, const float* y, long ldy
   return whh_grad_impl<kSplit2>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream,
                                 amax_dgates, amax_y);
 }
-#endif
 
-extern "C" int PE_HALF(pe_lstm_whh_grad)(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                                   int reverse, float* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int pe_lstm_whh_grad_bf16(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
+                                     int reverse, float* workspace, size_t workspace_bytes, void* stream) {
   return whh_grad_impl<kBf16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
 }
 
-#ifndef PE_F16_BUILD
+extern "C" int pe_lstm_whh_grad_f16(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
+                                    int reverse, float* workspace, size_t workspace_bytes, void* stream) {
+  return whh_grad_impl<kBf16, _Float16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
+}
+
 extern "C" size_t pe_colsum_workspace_bytes(int cols) { return (size_t)kColsumParts * cols * sizeof(double); }
-#endif
 
 // out0[c] = out1[c] = sum_r x[r*ld + c]   (out1 optional: b_ih and b_hh share one gradient)
-#ifndef PE_F16_BUILD
 extern "C" int pe_colsum(const float* x, long rows, int cols, long ld, float* out0, float* out1, void* workspace,
                          size_t workspace_bytes, void* stream) {
   if (!x || !out0 || rows <= 0 || cols <= 0) return PE_E_ARG;
@@ -421,4 +419,3 @@ extern "C" int pe_colsum(const float* x, long rows, int cols, long ld, float* ou
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
-#endif

@@ -168,19 +168,16 @@ __device__ __forceinline__ void split4(const float4& p, u32x2 (&out)[3]) {
     out[2][i] = __builtin_amdgcn_perm(u2[1], u2[0], 0x07060302u);
   }
 }
-typedef pe_half_t half_x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 round4(const float4& p) {
-  half_x4 o;
-  o[0] = (pe_half_t)p.x; o[1] = (pe_half_t)p.y; o[2] = (pe_half_t)p.z; o[3] = (pe_half_t)p.w;
-  return __builtin_bit_cast(u32x2, o);
-}
+template <class TH>
+__device__ __forceinline__ u32x2 round4(const float4& p) { return __builtin_bit_cast(u32x2, to_half4<TH>(p)); }
 // (a term, b term) of the six products.  a_hi x W_lo goes last: W_lo may come from LDS, and its read then
 // completes under the five products that do not need it.
-// mixed precision: 8 consecutive k rounded to bf16 (RNE)
-__device__ __forceinline__ bf16x8 round8(const float4& p, const float4& q) {
-  bf16x8 o;
-  o[0] = (pe_half_t)p.x; o[1] = (pe_half_t)p.y; o[2] = (pe_half_t)p.z; o[3] = (pe_half_t)p.w;
-  o[4] = (pe_half_t)q.x; o[5] = (pe_half_t)q.y; o[6] = (pe_half_t)q.z; o[7] = (pe_half_t)q.w;
+// mixed precision: 8 consecutive k rounded to the operand type TH (RNE)
+template <class TH>
+__device__ __forceinline__ half8<TH> round8(const float4& p, const float4& q) {
+  half8<TH> o;
+  o[0] = (TH)p.x; o[1] = (TH)p.y; o[2] = (TH)p.z; o[3] = (TH)p.w;
+  o[4] = (TH)q.x; o[5] = (TH)q.y; o[6] = (TH)q.z; o[7] = (TH)q.w;
   return o;
 }
 constexpr int kTa[6] = {2, 1, 1, 0, 0, 0}, kTb[6] = {0, 1, 0, 1, 0, 2};
@@ -349,11 +346,12 @@ __device__ __forceinline__ unsigned long long stamp_now() {
     st_last = _n;                                           \
   }
 
-template <int H, int TERMS, int NBR_, bool STAMP = false>
+template <int H, int TERMS, int NBR_, bool STAMP = false, class TH = __bf16>
 __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PFwdCells cells, int B, int T, long ldy,
                                                                         unsigned y_bytes, unsigned g_bytes,
                                                                         unsigned c_bytes, unsigned* sync) {
-  static_assert(TERMS == 3 || TERMS == 1, "bf16-term pipelines only");
+  static_assert(TERMS == 3 || TERMS == 1, "one- or three-term pipelines only");
+  static_assert(TERMS == 1 || std::is_same<TH, __bf16>::value, "the three-term split is bf16");
   constexpr int KQ = H / 4, KH = KQ / 2, NJ = H / 32;
   constexpr int ASTR = H + 4, ROW4 = H / 4, NST = ROW4 / 8;
   constexpr int NB = KH / 8;                          // 8-k blocks per lane
@@ -378,7 +376,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
   const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(cells.gates[cell], 0, g_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(cells.c[cell], 0, c_bytes, 0x00020000);
 
-  bf16x8 bwhm[4][NB][TERMS == 3 ? 2 : 1], bwlo[4][NBR > 0 ? NBR : 1];
+  half8<TH> bwhm[4][NB][TERMS == 3 ? 2 : 1], bwlo[4][NBR > 0 ? NBR : 1];
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     const float* src = cells.whh[cell] + (long)(g * H + j0 + r) * H + wv * KQ + hh * KH;
@@ -387,14 +385,14 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
       const float4 w0 = *reinterpret_cast<const float4*>(src + 8 * b);
       const float4 w1 = *reinterpret_cast<const float4*>(src + 8 * b + 4);
       if constexpr (TERMS == 3) {
-        bf16x8 t3[3];
+        half8<TH> t3[3];
         split8(w0, w1, t3);
         bwhm[g][b][0] = t3[0];
         bwhm[g][b][1] = t3[1];
         if (b < NBR) bwlo[g][b < NBR ? b : 0] = t3[2];
         else wlo_lds[(g * (NB - NBR) + (b - NBR)) * 256 + tid] = __builtin_bit_cast(uint4, t3[2]);
       } else {
-        bwhm[g][b][0] = round8(w0, w1);
+        bwhm[g][b][0] = round8<TH>(w0, w1);
       }
     }
   }
@@ -531,22 +529,22 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
     const float4 a0 = *reinterpret_cast<const float4*>(asrc + 8 * b);
     const float4 a1 = *reinterpret_cast<const float4*>(asrc + 8 * b + 4);
     if constexpr (TERMS == 3) {
-      bf16x8 fa[3];
+      half8<TH> fa[3];
       split8(a0, a1, fa);
-      bf16x8 wl[4];
+      half8<TH> wl[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         wl[g] = b < NBR ? bwlo[g][b < NBR ? b : 0]
-                        : __builtin_bit_cast(bf16x8, wlo_lds[(g * (NB - NBR) + (b - NBR)) * 256 + tid]);
+                        : __builtin_bit_cast(half8<TH>, wlo_lds[(g * (NB - NBR) + (b - NBR)) * 256 + tid]);
 #pragma unroll
       for (int t6 = 0; t6 < 6; ++t6)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          acc[g] = mfma_bf16(kTb[t6] == 2 ? wl[g] : bwhm[g][b][kTb[t6]], fa[kTa[t6]], acc[g]);
+          acc[g] = mfma16(kTb[t6] == 2 ? wl[g] : bwhm[g][b][kTb[t6]], fa[kTa[t6]], acc[g]);
     } else {
-      const bf16x8 fa = round8(a0, a1);
+      const half8<TH> fa = round8<TH>(a0, a1);
 #pragma unroll
-      for (int g = 0; g < 4; ++g) acc[g] = mfma_bf16(bwhm[g][b][0], fa, acc[g]);
+      for (int g = 0; g < 4; ++g) acc[g] = mfma16(bwhm[g][b][0], fa, acc[g]);
     }
   };
   unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
@@ -649,7 +647,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
             store4(crs, oob(e_el, (e_el * (unsigned)H + (unsigned)(j0 + 4 * pq)) * 4u), 0u, cnv);
           }
         };
-        bf16x8 fa1[TERMS == 3 ? 3 : 1], wl1[4];
+        half8<TH> fa1[TERMS == 3 ? 3 : 1], wl1[4];
         static_for<NB1 * 24>([&](auto Q) {
           constexpr int q = decltype(Q)::value, b = q / 24, t6 = (q % 24) / 4, g = q % 4;
           if constexpr (q % 24 == 0) {                 // operands of block b
@@ -660,15 +658,15 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
 #pragma unroll
               for (int gg = 0; gg < 4; ++gg)
                 wl1[gg] = b < NBR ? bwlo[gg][b < NBR ? b : 0]
-                                  : __builtin_bit_cast(bf16x8, wlo_lds[(gg * (NB - NBR) + (b - NBR)) * 256 + tid]);
+                                  : __builtin_bit_cast(half8<TH>, wlo_lds[(gg * (NB - NBR) + (b - NBR)) * 256 + tid]);
             } else {
-              fa1[0] = round8(a0, a1);
+              fa1[0] = round8<TH>(a0, a1);
             }
           }
           if constexpr (TERMS == 3) {
-            acc[g] = mfma_bf16(kTb[t6] == 2 ? wl1[g] : bwhm[g][b][kTb[t6] == 2 ? 0 : kTb[t6]], fa1[kTa[t6]], acc[g]);
+            acc[g] = mfma16(kTb[t6] == 2 ? wl1[g] : bwhm[g][b][kTb[t6] == 2 ? 0 : kTb[t6]], fa1[kTa[t6]], acc[g]);
           } else {
-            if constexpr (t6 == 0) acc[g] = mfma_bf16(bwhm[g][b][0], fa1[0], acc[g]);
+            if constexpr (t6 == 0) acc[g] = mfma16(bwhm[g][b][0], fa1[0], acc[g]);
           }
           constexpr int gap = q - (q / 24 + 1);        // gaps that carry no operand preparation, numbered from 0
           if constexpr (q % 24 != 0 && gap < kEPieces) e_piece(std::integral_constant<int, gap>{});
@@ -708,7 +706,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
         const bool ok_n = want_fetch && brow_n < B;
         const unsigned base_n = ok_n ? ((unsigned)(brow_n * T + tp_n) * (unsigned)ldy + (unsigned)(tid & 7) * 4u) * 4u
                                      : 0xfffffff0u;
-        bf16x8 fa3[3], wl3[4];
+        half8<TH> fa3[3], wl3[4];
         {
           constexpr int b = NB - 1;
           const float4 a0 = *reinterpret_cast<const float4*>(asrc + 8 * b);
@@ -717,11 +715,11 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
 #pragma unroll
           for (int gg = 0; gg < 4; ++gg)
             wl3[gg] = b < NBR ? bwlo[gg][b < NBR ? b : 0]
-                              : __builtin_bit_cast(bf16x8, wlo_lds[(gg * (NB - NBR) + (b - NBR)) * 256 + tid]);
+                              : __builtin_bit_cast(half8<TH>, wlo_lds[(gg * (NB - NBR) + (b - NBR)) * 256 + tid]);
         }
         static_for<24>([&](auto Q) {
           constexpr int q = decltype(Q)::value, g = q / 6, t6 = q % 6, b = NB - 1;
-          acc[g] = mfma_bf16(kTb[t6] == 2 ? wl3[g] : bwhm[g][b][kTb[t6] == 2 ? 0 : kTb[t6]], fa3[kTa[t6]], acc[g]);
+          acc[g] = mfma16(kTb[t6] == 2 ? wl3[g] : bwhm[g][b][kTb[t6] == 2 ? 0 : kTb[t6]], fa3[kTa[t6]], acc[g]);
           if constexpr ((q & 1) == 1 && q / 2 < NST)
             stage[q / 2] = load_sc1(yrs, base_n + (ok_n ? (unsigned)(q / 2) * 128u : 0u));
           if constexpr ((q & 1) == 0 && q >= 6) {    // even gaps: gate (q - 6) / 8's tile, one float4 per gap
@@ -779,10 +777,11 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_v2_kernel(const PF
 constexpr int kXchgWord = 8192;          // flag blocks start this many words into the sync buffer ...
 constexpr int kFlagWords = 16384;        // ... [cell][batch tile][half][64 words]; the partial tiles follow
 
-template <int H, int TERMS, int NBR_, bool STAMP = false>
+template <int H, int TERMS, int NBR_, bool STAMP = false, class TH = __bf16>
 __global__ __launch_bounds__(256, 1) void lstm_bwd_persistent_ks_kernel(const PBwdCells cells, int B, int T, long lddy,
                                                                         unsigned g_bytes, unsigned* sync) {
-  static_assert(TERMS == 3 || TERMS == 1, "bf16-term pipelines only");
+  static_assert(TERMS == 3 || TERMS == 1, "one- or three-term pipelines only");
+  static_assert(TERMS == 1 || std::is_same<TH, __bf16>::value, "the three-term split is bf16");
   static_assert(H % 128 == 0, "each wave owns whole 32-column blocks of dh");
   constexpr int NJ = H / 32, K = 4 * H;
   constexpr int NBW = H / 128;                      // 32-column blocks of dh per wave
@@ -825,7 +824,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persistent_ks_kernel(const PB
   const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(gates, 0, g_bytes, 0x00020000);
 
   // W block (nb, kb): column n = wv * H/4 + nb * 32 + r of dh, k = gate (kb >> 1), hidden j0 + (kb & 1) * 16 + hh * 8 ..
-  bf16x8 bwhm[NBK][TERMS == 3 ? 2 : 1], bwlo[NBR > 0 ? NBR : 1];
+  half8<TH> bwhm[NBK][TERMS == 3 ? 2 : 1], bwlo[NBR > 0 ? NBR : 1];
 #pragma unroll
   for (int nb = 0; nb < NBW; ++nb) {
     const float* src = cells.whh_t[cell] + (long)(wv * (H / 4) + nb * 32 + r) * K + j0 + hh * 8;
@@ -836,14 +835,14 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persistent_ks_kernel(const PB
       const float4 w0 = *reinterpret_cast<const float4*>(sp);
       const float4 w1 = *reinterpret_cast<const float4*>(sp + 4);
       if constexpr (TERMS == 3) {
-        bf16x8 t3[3];
+        half8<TH> t3[3];
         split8(w0, w1, t3);
         bwhm[b][0] = t3[0];
         bwhm[b][1] = t3[1];
         if (b < NBR) bwlo[b < NBR ? b : 0] = t3[2];
         else wlo_lds[(b - NBR) * 256 + tid] = __builtin_bit_cast(uint4, t3[2]);
       } else {
-        bwhm[b][0] = round8(w0, w1);
+        bwhm[b][0] = round8<TH>(w0, w1);
       }
     }
   }
@@ -961,7 +960,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persistent_ks_kernel(const PB
         for (int t = 0; t < 3; ++t)
           *reinterpret_cast<u32x2*>(dl + (size_t)((t * NKB + 2 * g) * 2 * 32) * 16) = t3[t];
       } else {
-        *reinterpret_cast<u32x2*>(dl + (size_t)(2 * g * 2 * 32) * 16) = round4(og4[g]);
+        *reinterpret_cast<u32x2*>(dl + (size_t)(2 * g * 2 * 32) * 16) = round4<TH>(og4[g]);
       }
     }
     // the gradient tensor itself (input of the dW / dX GEMMs): nobody in this launch waits for these stores
@@ -1019,10 +1018,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persistent_ks_kernel(const PB
 #pragma unroll
       for (int kb = 0; kb < NKB; ++kb) {
         const int b = nb * NKB + kb;
-        bf16x8 fa[NT];
+        half8<TH> fa[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) fa[t] = __builtin_bit_cast(bf16x8, fn[t]);
-        const bf16x8 wl = b < NBR ? bwlo[b < NBR ? b : 0] : __builtin_bit_cast(bf16x8, wn);
+        for (int t = 0; t < NT; ++t) fa[t] = __builtin_bit_cast(half8<TH>, fn[t]);
+        const half8<TH> wl = b < NBR ? bwlo[b < NBR ? b : 0] : __builtin_bit_cast(half8<TH>, wn);
         // a poll is an L2 round trip (~700 cycles) even when the peers have long arrived: the first one is sent
         // four groups early and only looked at here
         if (b == LPEEK && pre && pre_part) seen = flags_peek(flags + 64 * pre_hf, 4 * NJ);
@@ -1059,13 +1058,13 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persistent_ks_kernel(const PB
         if constexpr (TERMS == 3) {
 #pragma unroll
           for (int t6 = 0; t6 < 6; ++t6) {
-            const bf16x8 wt = kTb[t6] == 2 ? wl : bwhm[b][kTb[t6]];
-            if (t6 & 1) acc2 = mfma_bf16(wt, fa[kTa[t6]], acc2);
-            else acc = mfma_bf16(wt, fa[kTa[t6]], acc);
+            const half8<TH> wt = kTb[t6] == 2 ? wl : bwhm[b][kTb[t6]];
+            if (t6 & 1) acc2 = mfma16(wt, fa[kTa[t6]], acc2);
+            else acc = mfma16(wt, fa[kTa[t6]], acc);
           }
         } else {
-          if (kb & 1) acc2 = mfma_bf16(bwhm[b][0], fa[0], acc2);
-          else acc = mfma_bf16(bwhm[b][0], fa[0], acc);
+          if (kb & 1) acc2 = mfma16(bwhm[b][0], fa[0], acc2);
+          else acc = mfma16(bwhm[b][0], fa[0], acc);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1166,19 +1165,19 @@ constexpr size_t fwd_v2_lds() {
   return (size_t)(32 * (H + 4) + 4 * 32 * kRs) * sizeof(float) + (size_t)4 * NBL * 256 * 16;
 }
 
-template <int H, int TERMS, int NBR, bool STAMP = false>
+template <int H, int TERMS, int NBR, bool STAMP = false, class TH = __bf16>
 int launch_fwd_v2(const PFwdCells& cells, int grid, int B, int T, long ldy, unsigned* sync, hipStream_t st) {
   static_assert(fwd_v2_lds<H, TERMS, NBR>() <= 160 * 1024, "LDS budget");
   static bool attr = false;
   if (!attr) {
-    PE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_persistent_v2_kernel<H, TERMS, NBR, STAMP>),
+    PE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_persistent_v2_kernel<H, TERMS, NBR, STAMP, TH>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_v2_lds<H, TERMS, NBR>()));
     attr = true;
   }
   const unsigned y_bytes = (unsigned)((size_t)B * T * ldy * sizeof(float));
   const unsigned g_bytes = (unsigned)((size_t)B * T * 4 * H * sizeof(float));
   const unsigned c_bytes = (unsigned)((size_t)B * T * H * sizeof(float));
-  hipLaunchKernelGGL((lstm_fwd_persistent_v2_kernel<H, TERMS, NBR, STAMP>), dim3(grid), dim3(256),
+  hipLaunchKernelGGL((lstm_fwd_persistent_v2_kernel<H, TERMS, NBR, STAMP, TH>), dim3(grid), dim3(256),
                      (fwd_v2_lds<H, TERMS, NBR>()), st, cells, B, T, ldy, y_bytes, g_bytes, c_bytes, sync);
   PE_LAUNCH_CHECK();
   return PE_OK;
@@ -1190,17 +1189,17 @@ constexpr size_t bwd_v2_lds() {
   return (size_t)(2 * (TERMS == 3 ? 3 : 1) * 8 * 2 * 32) * 16 + (size_t)NBL * 256 * 16;
 }
 
-template <int H, int TERMS, int NBR, bool STAMP = false>
+template <int H, int TERMS, int NBR, bool STAMP = false, class TH = __bf16>
 int launch_bwd_v2(const PBwdCells& cells, int grid, int B, int T, long lddy, unsigned* sync, hipStream_t st) {
   static_assert(bwd_v2_lds<H, TERMS, NBR>() <= 160 * 1024, "LDS budget");
   static bool attr = false;
   if (!attr) {
-    PE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_persistent_ks_kernel<H, TERMS, NBR, STAMP>),
+    PE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_persistent_ks_kernel<H, TERMS, NBR, STAMP, TH>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_v2_lds<H, TERMS, NBR>()));
     attr = true;
   }
   const unsigned g_bytes = (unsigned)((size_t)B * T * 4 * H * sizeof(float));
-  hipLaunchKernelGGL((lstm_bwd_persistent_ks_kernel<H, TERMS, NBR, STAMP>), dim3(grid), dim3(256),
+  hipLaunchKernelGGL((lstm_bwd_persistent_ks_kernel<H, TERMS, NBR, STAMP, TH>), dim3(grid), dim3(256),
                      (bwd_v2_lds<H, TERMS, NBR>()), st, cells, B, T, lddy, g_bytes, sync);
   PE_LAUNCH_CHECK();
   return PE_OK;
@@ -1217,7 +1216,6 @@ size_t xchg_bytes(int ncells, int B) { return (size_t)ncells * ((B + 63) / 64) *
 
 }  // namespace
 
-#ifndef PE_F16_BUILD
 // Bytes of the zero-initialised buffer every persistent launch takes as `sync`: [error word + group counters | pad to
 // kXchgWord words | the k-split backward kernel's flag blocks | its partial tiles].  Counters and flags are reset per
 // launch.
@@ -1226,14 +1224,12 @@ extern "C" size_t pe_lstm_persistent_sync_bytes(int ncells, int B) {
   if (ncells * ((B + 63) / 64) * 128 > kFlagWords) return 0;
   return (size_t)(kXchgWord + kFlagWords) * sizeof(unsigned) + xchg_bytes(ncells, B);
 }
-#endif
 
 // 1 if the persistent kernels can run this shape on the current device: the hidden size they are instantiated for
 // (H = 384, the reference's default, model.py:198), every tensor of a cell addressable with 32-bit offsets below 2 GiB,
 // the flag blocks within the sync buffer, and the whole grid co-resident at one workgroup per CU; else 0 (run the
 // one-launch-per-time-step kernels of lstm.hip).  The recurrent products are 16-bit-term MFMAs (three exact bf16 terms
 // or one rounded term): there is no native-fp32 persistent form.
-#ifndef PE_F16_BUILD
 extern "C" int pe_lstm_persistent_supported(int ncells, int B, int H) {
   if (ncells < 1 || ncells > kMaxCells || B <= 0 || H != 384) return 0;
   if (sync_words(ncells, B) > kXchgWord || ncells * ((B + 63) / 64) * 128 > kFlagWords) return 0;
@@ -1248,15 +1244,14 @@ extern "C" int pe_lstm_configure_stamps(int enable) {
   g_lstm_stamps = enable != 0;
   return old;
 }
-#else
-extern "C" int pe_lstm_persistent_supported(int ncells, int B, int H);
-#endif
 
 static bool small_enough(int B, int T, int H, long ld) {
   return (size_t)B * T * 4 * H * sizeof(float) < (1ull << 31) && (size_t)B * T * (size_t)ld * sizeof(float) < (1ull << 31);
 }
 
-static int lstm_fwd_persistent_impl(int terms, int ncells, const float* const* whh, float* const* gates,
+// TERMS = 3: the exact three-term bf16 split; 1: operands rounded to TH.  The stamped instances exist for bf16 only.
+template <int TERMS, class TH = __bf16>
+static int lstm_fwd_persistent_impl(int ncells, const float* const* whh, float* const* gates,
                                     float* const* y, float* const* cbuf, const int* reverse, long ldy, int B, int T,
                                     int H, unsigned* sync, void* stream) {
   if (!whh || !gates || !y || !cbuf || !reverse || !sync || T <= 0) return PE_E_ARG;
@@ -1271,21 +1266,20 @@ static int lstm_fwd_persistent_impl(int terms, int ncells, const float* const* w
   // word 0 is the sticky error flag (cleared only by the owner of the buffer); counters start at line 1
   PE_CHECK_HIP(hipMemsetAsync(sync + kCtrStride, 0, (size_t)(sync_words(ncells, B) - kCtrStride) * 4, st));
   const int grid = ncells * ((B + 63) / 64) * (H / 32);
-  if (terms == 3 && g_lstm_stamps && grid <= 128) return launch_fwd_v2<384, 3, 4, true>(cells, grid, B, T, ldy, sync, st);
-  if (terms == 1 && g_lstm_stamps && grid <= 128) return launch_fwd_v2<384, 1, 6, true>(cells, grid, B, T, ldy, sync, st);
-  return terms == 3 ? launch_fwd_v2<384, 3, 4>(cells, grid, B, T, ldy, sync, st)
-                    : launch_fwd_v2<384, 1, 6>(cells, grid, B, T, ldy, sync, st);
+  constexpr int NBR = TERMS == 3 ? 4 : 6;
+  if constexpr (std::is_same<TH, __bf16>::value)
+    if (g_lstm_stamps && grid <= 128) return launch_fwd_v2<384, TERMS, NBR, true>(cells, grid, B, T, ldy, sync, st);
+  return launch_fwd_v2<384, TERMS, NBR, false, TH>(cells, grid, B, T, ldy, sync, st);
 }
 
-#ifndef PE_F16_BUILD
 extern "C" int pe_lstm_fwd_persistent_x3(int ncells, const float* const* whh, float* const* gates, float* const* y,
                                          float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
                                          unsigned* sync, void* stream) {
-  return lstm_fwd_persistent_impl(3, ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+  return lstm_fwd_persistent_impl<3>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
 }
-#endif
 
-static int lstm_bwd_persistent_impl(int terms, int ncells, const float* const* whh_t, float* const* gates,
+template <int TERMS, class TH = __bf16>
+static int lstm_bwd_persistent_impl(int ncells, const float* const* whh_t, float* const* gates,
                                     const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
                                     int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
                                     unsigned* sync, void* stream) {
@@ -1303,13 +1297,12 @@ static int lstm_bwd_persistent_impl(int terms, int ncells, const float* const* w
   PE_CHECK_HIP(hipMemsetAsync(sync + kCtrStride, 0, (size_t)(sync_words(ncells, B) - kCtrStride) * 4, st));
   PE_CHECK_HIP(hipMemsetAsync(sync + kXchgWord, 0, (size_t)ncells * ((B + 63) / 64) * 128 * sizeof(unsigned), st));
   const int grid = ncells * ((B + 63) / 64) * (H / 32);
-  if (terms == 3 && g_lstm_stamps && grid <= 128) return launch_bwd_v2<384, 3, 8, true>(cells, grid, B, T, lddy, sync, st);
-  if (terms == 1 && g_lstm_stamps && grid <= 128) return launch_bwd_v2<384, 1, 24, true>(cells, grid, B, T, lddy, sync, st);
-  return terms == 3 ? launch_bwd_v2<384, 3, 8>(cells, grid, B, T, lddy, sync, st)
-                    : launch_bwd_v2<384, 1, 24>(cells, grid, B, T, lddy, sync, st);
+  constexpr int NBR = TERMS == 3 ? 8 : 24;
+  if constexpr (std::is_same<TH, __bf16>::value)
+    if (g_lstm_stamps && grid <= 128) return launch_bwd_v2<384, TERMS, NBR, true>(cells, grid, B, T, lddy, sync, st);
+  return launch_bwd_v2<384, TERMS, NBR, false, TH>(cells, grid, B, T, lddy, sync, st);
 }
 
-#ifndef PE_F16_BUILD
 // Rows ([ceil(B / 64)][4H] per cell) that pe_lstm_bwd_persistent_* writes into a non-null dbias_rows for this
 // configuration; 0 = the persistent kernel does not serve it (run pe_lstm_bwd and pe_colsum).
 extern "C" int pe_lstm_bwd_persistent_dbias_rows(int ncells, int B, int T, int H, long lddy) {
@@ -1321,21 +1314,34 @@ extern "C" int pe_lstm_bwd_persistent_x3(int ncells, const float* const* whh_t, 
                                          const float* const* cbuf, const float* const* dy, const int* reverse,
                                          long lddy, int B, int T, int H, float* const* dbias_rows,
                                          unsigned* const* dgates_amax, unsigned* sync, void* stream) {
-  return lstm_bwd_persistent_impl(3, ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax, sync,
-                                  stream);
+  return lstm_bwd_persistent_impl<3>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
+                                     sync, stream);
 }
-#endif
 
-extern "C" int PE_HALF(pe_lstm_fwd_persistent)(int ncells, const float* const* whh, float* const* gates, float* const* y,
+extern "C" int pe_lstm_fwd_persistent_bf16(int ncells, const float* const* whh, float* const* gates, float* const* y,
                                            float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
                                            unsigned* sync, void* stream) {
-  return lstm_fwd_persistent_impl(1, ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+  return lstm_fwd_persistent_impl<1>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
 }
 
-extern "C" int PE_HALF(pe_lstm_bwd_persistent)(int ncells, const float* const* whh_t, float* const* gates,
+extern "C" int pe_lstm_fwd_persistent_f16(int ncells, const float* const* whh, float* const* gates, float* const* y,
+                                          float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
+                                          unsigned* sync, void* stream) {
+  return lstm_fwd_persistent_impl<1, _Float16>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+}
+
+extern "C" int pe_lstm_bwd_persistent_bf16(int ncells, const float* const* whh_t, float* const* gates,
                                            const float* const* cbuf, const float* const* dy, const int* reverse,
                                            long lddy, int B, int T, int H, float* const* dbias_rows,
                                            unsigned* const* dgates_amax, unsigned* sync, void* stream) {
-  return lstm_bwd_persistent_impl(1, ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax, sync,
-                                  stream);
+  return lstm_bwd_persistent_impl<1>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
+                                     sync, stream);
+}
+
+extern "C" int pe_lstm_bwd_persistent_f16(int ncells, const float* const* whh_t, float* const* gates,
+                                          const float* const* cbuf, const float* const* dy, const int* reverse,
+                                          long lddy, int B, int T, int H, float* const* dbias_rows,
+                                          unsigned* const* dgates_amax, unsigned* sync, void* stream) {
+  return lstm_bwd_persistent_impl<1, _Float16>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows,
+                                               dgates_amax, sync, stream);
 }
