@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvLoader<TL::A_LOADS, TA
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_x, amax_w);
   nt_mainloop_mode<TL, MODE, false, 1, TH>(al, bl, K, As, Bs, acc, hs.sa, hs.sb);
-  for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? v * hs.inv : v); });
+  for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? hs.unscale(v) : v); });
 }
 
 template <class TL, int MODE, class TA = float, class TH = __bf16>
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
         const int row = p0 + wm * 64 + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * h, col = n0 + wn * WN + j * 32 + r;
         if (row < ep.rows && col < ep.N) {
           TA* d = ep.Y + (long)row * ep.N + col;
-          float v = MODE == kSplit2 ? acc[i][j][g] * hs.inv : acc[i][j][g];
+          float v = MODE == kSplit2 ? hs.unscale(acc[i][j][g]) : acc[i][j][g];
           if (ep.accumulate) v += ld1(d);
           st1(d, v);
           v = stored_value<TA>(v);
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
     for (int q = 0; q < 16; ++q) {
       const int co = m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
       const int ci = n0 + wn * 32 + r;
-      dst[(long)co * Cin + ci] = NT == 2 ? acc[tp][q] * hs.inv : acc[tp][q];
+      dst[(long)co * Cin + ci] = NT == 2 ? hs.unscale(acc[tp][q]) : acc[tp][q];
     }
   }
 }

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(RowLoaderT<TA> al, RowLoad
   H2Scales hs{1.f, 1.f, 1.f};
   if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
   nt_mainloop_mode<TL, MODE, false, 1, TH>(al, bl, K, As, Bs, acc, hs.sa, hs.sb);
-  for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? v * hs.inv : v); });
+  for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? hs.unscale(v) : v); });
 }
 
 // The same product with the operand roles swapped inside the tile engine (the NT main loop is symmetric in its two
@@ -93,7 +93,9 @@ void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, 
         if (row >= ep.M) continue;
         TA* dst = ep.C + (long)row * ep.ldc + col;
         float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        if constexpr (MODE == kSplit2) { v.x *= hs.inv; v.y *= hs.inv; v.z *= hs.inv; v.w *= hs.inv; }
+        if constexpr (MODE == kSplit2) {
+          v.x = hs.unscale(v.x); v.y = hs.unscale(v.y); v.z = hs.unscale(v.z); v.w = hs.unscale(v.w);
+        }
         if (ep.bias0) { v.x += b0.x; v.y += b0.y; v.z += b0.z; v.w += b0.w; }
         if (ep.bias1) { v.x += b1.x; v.y += b1.y; v.z += b1.z; v.w += b1.w; }
         if (ep.accumulate) { const float4 o = ld4(dst); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(KRowLoader<BM, TA> al, KRo
   float* dst = out + (long)split_id * split_stride;
   tn_for_each_acc<BM, BN>(acc, [&](int r, int c, float v) {
     const int row = m0 + r, col = n0 + c;
-    if constexpr (MODE == kSplit2) v *= hs.inv;
+    if constexpr (MODE == kSplit2) v = hs.unscale(v);
     if (row < M && col < N) {
       float* d = dst + (long)row * ldo + col;
       if (accumulate) v += *d;

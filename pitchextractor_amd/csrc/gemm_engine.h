@@ -344,13 +344,25 @@ __device__ __forceinline__ float h2_inv_scale(unsigned amax_bits) {
   return __uint_as_float((254u - h2_scale_exp(amax_bits)) << 23);
 }
 
-struct H2Scales {                                                   // s_a, s_b and 1 / (s_a s_b) of one product
-  float sa, sb, inv;
+struct H2Scales {                                                   // s_a, s_b and 1 / (s_a s_b) = inv * inv2
+  float sa, sb, inv, inv2 = 1.f;
   __device__ __forceinline__ void load(const unsigned* amax_a, const unsigned* amax_b) {
     const unsigned ba = __builtin_amdgcn_readfirstlane(*amax_a), bb = __builtin_amdgcn_readfirstlane(*amax_b);
     sa = h2_scale(ba); sb = h2_scale(bb);
-    inv = h2_inv_scale(ba) * h2_inv_scale(bb);
+    inv = h2_inv_scale(ba) * h2_inv_scale(bb);                      // exact while 2^e is a float (subnormal included)
+    // 1 / (s_a s_b) = 2^e with e in [-252, 228].  Below 2^-149 the single factor is 0 and would flush outputs that
+    // fp32 can hold (1e-20 x 1e-20 operands: e = -160, results ~1e-39); above 2^127 it is Inf.  Then the epilogue
+    // applies two normal powers of two instead, the first of which keeps the accumulator normal.
+    const int e = 254 - (int)h2_scale_exp(ba) - (int)h2_scale_exp(bb);
+    if (e < -149 || e > 127) {
+      const int e1 = e < 0 ? -126 : 127;
+      inv = __uint_as_float((unsigned)(e1 + 127) << 23);
+      inv2 = __uint_as_float((unsigned)(e - e1 + 127) << 23);
+    }
   }
+  // the accumulator in output units: (v * inv) * inv2, with inv2 == 1 (bit-identical to v * inv) in every case the
+  // single factor can represent
+  __device__ __forceinline__ float unscale(float v) const { return v * inv * inv2; }
 };
 
 struct Split2 { uint2 hi, lo; };                                    // 4 consecutive k of one row, packed fp16 pairs

@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void lstm_whh_grad_kernel(KRowLoader<BM> al, S
   float* dst = out + (long)split_id * split_stride;
   tn_for_each_acc<BM, BN>(acc, [&](int r, int c, float v) {
     const int row = m0 + r, col = n0 + c;
-    if (row < M && col < N) dst[(long)row * ldo + col] = MODE == kSplit2 ? v * hs.inv : v;
+    if (row < M && col < N) dst[(long)row * ldo + col] = MODE == kSplit2 ? hs.unscale(v) : v;
   });
 }
 
