@@ -467,6 +467,22 @@ long pe_resample_out_len(const pe_resample_plan* plan, long n_in);
 int pe_resample_forward(const pe_resample_plan* plan, const float* x, int batch, int n_in, long x_stride, float* y,
                         long y_stride, int n_out, void* stream);
 
+/* Multi-rate ragged resampler: one plan for a list of up to 16 source rates (a rate equal to new_freq copies;
+ * a plan of copies only allocates nothing on the device) and one target; same taps as pe_resample_plan_create.  pe_resample_ragged_forward resamples `batch` rows in one launch:
+ * row r reads n_in[r] samples at x + x_off[r] at source rate orig_freqs[rate_idx[r]] (device arrays) and writes
+ * its pe_resample_ragged_out_len outputs at y + r * y_stride, then zeros up to y_width.  Each row is bit-identical
+ * to pe_resample_forward on that row alone.  host_n_in / host_rate_idx are host copies of n_in / rate_idx, checked
+ * before any device call (PE_E_ARG: null pointer, rate index out of range, y_stride < y_width, a row longer than
+ * y_width).  Asynchronous on `stream`; no allocation. */
+typedef struct pe_resample_ragged_plan pe_resample_ragged_plan;
+int pe_resample_ragged_plan_create(pe_resample_ragged_plan** plan, const int* orig_freqs, int n_rates, int new_freq,
+                                   int lowpass_filter_width, float rolloff);
+int pe_resample_ragged_plan_destroy(pe_resample_ragged_plan* plan);
+long pe_resample_ragged_out_len(const pe_resample_ragged_plan* plan, int rate_index, long n_in);
+int pe_resample_ragged_forward(const pe_resample_ragged_plan* plan, const float* x, const long* x_off, const int* n_in,
+                               const int* rate_idx, const int* host_n_in, const int* host_rate_idx, int batch,
+                               float* y, long y_stride, int y_width, void* stream);
+
 /* ---- pitch-shift augmentation (reference meldataset.py:324-517 -> librosa.effects.pitch_shift defaults) ----
  * STFT 2048 / hop 512 / periodic Hann / centre zero padding -> phase vocoder at rate 2^(-n_steps/12) -> iSTFT to
  * round(N / rate) samples -> resampy sinc resampling (res_type 0 = kaiser_best, 1 = kaiser_fast) back to N samples.

@@ -30,8 +30,9 @@ reference's own float32 expression, cropped, and written over that batch row aft
 dataset trained with cached spectrograms keeps seeing exactly those values.  Caches are never written (the
 device recomputes the mel in one launch per batch) and a mismatching cache is skipped with a warning, not
 deleted (the reference clears every cache of the dataset on the first mismatch, :743-767).  Files at another sample rate are resampled on the GPU
-(meldataset.py:621-627 -> ``pitchextractor_amd.resample.Resampler``) right before the mel launch; one
-batch must come from one source rate.
+(meldataset.py:621-627 -> ``pitchextractor_amd.resample``) right before the mel launch; a batch may mix source
+rates: it is then resampled by one ragged launch at each row's own rate (``RaggedResampler``), every row bit-identical
+to resampling that item alone.
 """
 from __future__ import annotations
 
@@ -51,7 +52,7 @@ from typing import NamedTuple
 
 from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS, MelSpectrogram
 from .pitch_shift import check_res_type, pitch_shift_ragged
-from .resample import Resampler
+from .resample import RaggedResampler, Resampler
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.DEBUG)
@@ -268,6 +269,7 @@ class PitchShiftBatch(NamedTuple):
     out_start: torch.Tensor                    # int64 (K,)
     out_len: torch.Tensor                      # int64 (K,)
     noise: torch.Tensor | None                 # float32 flat, the windows back to back
+    src_sr: torch.Tensor | None = None         # int32 (K,) the base files' rates when the batch mixes rates
 
 
 def synthetic_window(n: int, crop: int, hop: int, n_fft: int, max_frames: int = MAX_MEL_LENGTH):
@@ -663,6 +665,8 @@ class Collater(object):
     Accepts the reference's ``(mel (80,L), f0, is_silence)`` items, or this build's raw-audio items
     ``(wave (N,), f0, is_silence, crop_start[, source_sr[, cached_mel (80,L<=192)]])``; for the latter it returns
     host tensors ``(waves (B,Nmax), lengths, crop_starts, f0s, is_silences, source_sr)`` for the device mel stage,
+    where ``source_sr`` is the batch's one source rate (``int``, 0 if unknown) or, when its items carry different
+    rates, an int32 ``(B,)`` tensor of per-row rates (0 for an item without one),
     followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram and by a
     ``PitchShiftBatch`` when any item is a pitch-shifted one.  A synthetic row's waveform is left zero (the device
     writes its shifted window there) and its length is that window's; its base file is packed, not padded."""
@@ -692,9 +696,9 @@ class Collater(object):
         waves = torch.zeros((B, n_max), dtype=torch.float32)
         lengths = torch.zeros((B,), dtype=torch.int32)
         crops = torch.zeros((B,), dtype=torch.int32)
+        row_rates = [int(item[4]) if len(item) > 4 else 0 for item in batch]
         rates = {int(item[4]) for item in batch if len(item) > 4}
-        if len(rates) > 1:
-            raise RuntimeError(f"one batch mixes source sample rates {sorted(rates)}: group files by rate")
+        mixed = len(rates) > 1
         for i, item in enumerate(batch):
             wave, f0, sil, crop = item[:4]
             if isinstance(item[-1], PitchShiftRequest):
@@ -706,7 +710,8 @@ class Collater(object):
             crops[i] = int(crop)
             f0s[i, :f0.shape[0]] = f0
             sils[i, :sil.shape[0]] = sil
-        out = (waves, lengths, crops, f0s, sils, (rates.pop() if rates else 0))
+        source_sr = torch.tensor(row_rates, dtype=torch.int32) if mixed else (rates.pop() if rates else 0)
+        out = (waves, lengths, crops, f0s, sils, source_sr)
         rows = [i for i, item in enumerate(batch) if len(item) > 5 and torch.is_tensor(item[5])]
         if rows:                                       # normalised, cropped cache rows, zero-padded like :812-816
             cached = torch.zeros((len(rows), batch[rows[0]][5].shape[0], L), dtype=torch.float32)
@@ -724,7 +729,8 @@ class Collater(object):
                                     i64([int(batch[i][0].shape[0]) for i in syn]), i64([r.n for r in reqs]),
                                     torch.tensor([r.n_steps for r in reqs], dtype=torch.float32),
                                     torch.tensor([r.gain for r in reqs], dtype=torch.float32),
-                                    i64([r.out_start for r in reqs]), i64([r.out_len for r in reqs]), noise),)
+                                    i64([r.out_start for r in reqs]), i64([r.out_len for r in reqs]), noise,
+                                    torch.tensor([row_rates[i] for i in syn], dtype=torch.int32) if mixed else None),)
         return out
 
 
@@ -769,7 +775,7 @@ class DeviceMelLoader:
     def __init__(self, loader: DataLoader, mel: MelSpectrogram, device):
         self.loader, self.mel, self.device = loader, mel, torch.device(device)
         self.dataset = loader.dataset
-        self._resamplers = {}
+        self._ragged = RaggedResampler(mel.sample_rate)
         self._h2d = None
 
     def __len__(self):
@@ -785,18 +791,20 @@ class DeviceMelLoader:
         """Synthetic rows: resample their packed base files (if needed), shift them and write each row's window."""
         sr = self.mel.sample_rate
         src = pack.src
-        if src_sr and src_sr != sr:
-            rs = self._resamplers.setdefault(src_sr, Resampler(src_sr, sr))
-            offs = np.concatenate([[0], np.cumsum(host.src_len.numpy())])
-            src = torch.cat([rs(src[int(offs[k]):int(offs[k + 1])]) for k in range(len(offs) - 1)])
+        n = host.n.numpy()
+        offsets = np.concatenate([[0], np.cumsum(n)[:-1]])
+        rates = host.src_sr.tolist() if host.src_sr is not None else [src_sr] * len(n)
+        if any(r and r != sr for r in rates):                 # base files at their own rates: one ragged launch
+            src, _ = self._ragged(src, [r or sr for r in rates], host.src_len.tolist())
+            offsets = np.arange(len(n), dtype=np.int64) * src.stride(0)
+            src = src.reshape(-1)
         need = int(host.out_len.max())
         if waves.shape[1] < need:
             waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
         waves = waves.contiguous()
-        n = host.n.numpy()
         res_type = (getattr(self.dataset, "synthetic_pitch_shift_config", None) or {}).get("resample_type",
                                                                                             "kaiser_best")
-        pitch_shift_ragged(src, np.concatenate([[0], np.cumsum(n)[:-1]]), n, host.n_steps.numpy(), pack.gains, waves,
+        pitch_shift_ragged(src, offsets, n, host.n_steps.numpy(), pack.gains, waves,
                            host.rows.numpy(), host.out_start.numpy(), host.out_len.numpy(), sr=sr, res_type=res_type,
                            noise=pack.noise)
         lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
@@ -806,13 +814,15 @@ class DeviceMelLoader:
         waves, lengths, crops, f0s, sils, src_sr, *cached = self._h2d.acquire(ticket)
         pack = cached.pop() if cached and isinstance(cached[-1], PitchShiftBatch) else None
         host_pack = self._host_packs.pop(0)
-        if src_sr and src_sr != self.mel.sample_rate:
-            rs = self._resamplers.setdefault(src_sr, Resampler(src_sr, self.mel.sample_rate))
-            waves = rs(waves)                                 # zero-padded rows resample exactly like each item alone
-            lengths = torch.tensor([rs.out_len(int(n)) for n in self._host_lengths.pop(0)], dtype=torch.int32,
-                                   device=self.device)
-        else:
-            self._host_lengths.pop(0)
+        host_lengths, host_rates = self._host_lengths.pop(0), self._host_rates.pop(0)
+        sr = self.mel.sample_rate
+        rates = host_rates if host_rates is not None else [src_sr] * len(host_lengths)
+        if any(r and r != sr for r in rates):
+            # one ragged launch, each row at its own rate and bit-identical to that item resampled alone; synthetic
+            # rows are left zero (length 0) for the pitch shift, which resamples their base files itself
+            syn = set(host_pack.rows.tolist()) if host_pack is not None else set()
+            waves, lengths = self._ragged(waves, [r or sr for r in rates],
+                                          [0 if i in syn else int(n) for i, n in enumerate(host_lengths)])
         if pack is not None:                                  # after the resampler, before the one mel launch
             waves, lengths = self._pitch_shift(waves, lengths, src_sr, pack, host_pack)
         mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
@@ -831,10 +841,11 @@ class DeviceMelLoader:
                 from .model import _side_stream
                 shared = _side_stream(self.device)
             self._h2d = H2DPrefetcher(self.device, stream=shared)
-        self._host_lengths, self._host_packs = [], []
+        self._host_lengths, self._host_rates, self._host_packs = [], [], []
         pending = None
         for host in self.loader:
             self._host_lengths.append(host[1].tolist())
+            self._host_rates.append(host[5].tolist() if torch.is_tensor(host[5]) else None)
             self._host_packs.append(host[-1] if isinstance(host[-1], PitchShiftBatch) else None)
             ticket = self._h2d.submit(host)
             if pending is not None:

@@ -52,3 +52,84 @@ class Resampler:
             ops._call("pe_resample_forward", self._get_plan(x.device), x.data_ptr(), x.shape[0], x.shape[1], x.stride(0),
                       y.data_ptr(), y.stride(0), n_out, _lib.stream_ptr())
         return y[0] if single else y
+
+
+class RaggedResampler:
+    """Rows at mixed source rates to one target rate in ONE launch (``pe_resample_ragged_forward``).  Row r equals
+    ``Resampler(rates[r], target_sr)`` on that row alone, bit for bit; a row already at the target is copied.  One
+    plan is cached per set of source rates and device."""
+
+    def __init__(self, target_sr: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        self.target_sr = int(target_sr)
+        self.lowpass_filter_width, self.rolloff = int(lowpass_filter_width), float(rolloff)
+        self._plans = {}
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_plans"] = {}
+        return st
+
+    def out_len(self, rate: int, n: int) -> int:
+        rate = int(rate)
+        if rate == self.target_sr:
+            return int(n)
+        g = math.gcd(rate, self.target_sr)
+        return -(-int(n) * (self.target_sr // g) // (rate // g))
+
+    def _get_plan(self, rates: tuple, device):
+        key = (rates, device)
+        if key not in self._plans:
+            handle = C.c_void_p()
+            arr = (C.c_int * len(rates))(*rates)
+            with torch.cuda.device(device):
+                _lib.check(_lib.load().pe_resample_ragged_plan_create(C.byref(handle), arr, len(rates), self.target_sr,
+                                                                      self.lowpass_filter_width, self.rolloff),
+                           "pe_resample_ragged_plan_create")
+            self._plans[key] = handle
+        return self._plans[key]
+
+    def __call__(self, x: torch.Tensor, rates, lengths=None, y_width: int | None = None):
+        """``x``: (B, N) padded rows (``lengths`` per row, default N) or a flat (N,) tensor of rows packed back to
+        back (``lengths`` required).  ``rates``, ``lengths``: host sequences.  Returns ``(y (B, y_width),
+        out_lengths int32 (B,) device)``; ``y_width`` defaults to the longest output and each row is zero past its
+        own output."""
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2) or x.stride(-1) != 1:
+            raise RuntimeError("RaggedResampler (HIP) needs contiguous-row float32 device audio; no CPU fallback exists")
+        rates = [int(r) for r in rates]
+        B = len(rates)
+        if x.dim() == 2:
+            if x.shape[0] != B:
+                raise ValueError("one rate per row")
+            lengths = [int(x.shape[1])] * B if lengths is None else [int(n) for n in lengths]
+            offsets = [r * x.stride(0) for r in range(B)]
+            if any(n > x.shape[1] for n in lengths):
+                raise ValueError("a row length exceeds the padded width")
+        else:
+            if lengths is None:
+                raise ValueError("packed rows need their lengths")
+            lengths = [int(n) for n in lengths]
+            offsets = [0] * B
+            for r in range(1, B):
+                offsets[r] = offsets[r - 1] + lengths[r - 1]
+            if B and offsets[-1] + lengths[-1] > x.numel():
+                raise ValueError("packed row lengths exceed the input")
+        if len(lengths) != B or any(n < 0 for n in lengths):
+            raise ValueError("one non-negative length per row")
+        distinct = tuple(sorted(set(rates)))
+        index = {r: k for k, r in enumerate(distinct)}
+        ridx = [index[r] for r in rates]
+        out_lengths = [self.out_len(r, n) for r, n in zip(rates, lengths)]
+        if y_width is None:
+            y_width = max(out_lengths, default=0)
+        # one pinned staging buffer per dtype: n_in, rate index and output lengths (int32), offsets (int64)
+        host32 = torch.tensor(lengths + ridx + out_lengths, dtype=torch.int32).pin_memory()
+        host64 = torch.tensor(offsets, dtype=torch.int64).pin_memory()
+        dev32 = host32.to(x.device, non_blocking=True)
+        dev64 = host64.to(x.device, non_blocking=True)
+        y = torch.empty((B, int(y_width)), dtype=torch.float32, device=x.device)
+        if B and y_width:                                    # (an empty y has no data pointer)
+            with torch.cuda.device(x.device):
+                ops._call("pe_resample_ragged_forward", self._get_plan(distinct, x.device), x.data_ptr(),
+                          dev64.data_ptr(), dev32.data_ptr(), dev32[B:].data_ptr(), host32[:B].data_ptr(),
+                          host32[B:2 * B].data_ptr(), B, y.data_ptr(), y.stride(0), int(y_width), _lib.stream_ptr())
+        return y, dev32[2 * B:]
