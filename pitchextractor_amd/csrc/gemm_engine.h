@@ -325,14 +325,16 @@ __device__ __forceinline__ f32x16 mfma_split_swapped(const bf16x8 (&a)[3], const
 // ------------------------------------------------------------------ fp32 as two scaled fp16 terms ("h2")
 // fp16 carries 11 significand bits, so TWO terms hold 22: x * s = hi + lo (+ a residual <= 2^-22 |x s|), hi =
 // RN_f16(x s), lo = RN_f16(x s - hi) (the subtraction is exact in fp32).  a * b is then hi_a hi_b + hi_a lo_b +
-// lo_a hi_b (every product exact in the fp32 accumulator of v_mfma_f32_32x32x16_f16) with lo_a lo_b <= 2^-24 |a b|
-// dropped: THREE MFMAs per product block instead of the six of the bf16 split, for a per-product error <= 2^-21
-// |a b|, unbiased (round to nearest) and so averaging out over a sum; the accumulation rounding of a K-long fp32
-// sum, common to every fp32 path, is ~2^-22 sqrt(K) |a b|.  What fp16 lacks is exponent range (5 bits), so every
+// lo_a hi_b (every product exact in the fp32 accumulator of v_mfma_f32_32x32x16_f16) with lo_a lo_b dropped: THREE
+// MFMAs per product block instead of the six of the bf16 split.  What fp16 lacks is exponent range (5 bits), so every
 // operand TENSOR carries a power-of-two scale s = 2^(140 - E), E = the biased exponent of its largest magnitude
-// (pe_absmax, or the producing kernel's epilogue): max |x| s lies in [2^13, 2^14), hi stays a normal fp16 down to
-// 2^-28 of the tensor's maximum and a subnormal with absolute resolution 2^-38 max below that.  The epilogue
-// multiplies the accumulator by 1 / (s_a s_b), again a power of two: nothing but exponents change.
+// (pe_absmax, or the producing kernel's epilogue): max |x| s lies in [2^13, 2^14).  The split is then accurate to
+// |(hi + lo) / s - x| <= 2^-23 |x| + 2^-38 max|x|: 2^-23 relative while lo is a normal fp16, i.e. for |x| >= 2^-16 max
+// (per-product error ~2^-22 |a b|, unbiased), but lo turns subnormal below 2^-16 max (and hi below 2^-27 max), where
+// the absolute resolution stays 2^-38 max and the relative precision falls by one bit per binade (2^-14.6 at
+// 2^-24 max, 2^-6.6 at 2^-32 max).  The accumulation rounding of a K-long fp32 sum, common to every fp32 path, is
+// ~2^-22 sqrt(K) |a b|.  The epilogue multiplies the accumulator by 1 / (s_a s_b), again a power of two: nothing but
+// exponents change.
 // scale of a tensor whose largest magnitude has the IEEE bits `amax_bits` (sign bit clear)
 __device__ __host__ __forceinline__ unsigned h2_scale_exp(unsigned amax_bits) {
   int es = 267 - (int)((amax_bits >> 23) & 0xffu);                  // biased exponent of 2^(140 - E)

@@ -155,10 +155,11 @@ HALF_DTYPE = "bf16"
 # How fp32 products run (always, for the weight-gradient products; when MATMUL_BF16 is off for the rest):
 #   "x3"     every fp32 operand is split exactly into three bf16 terms and six cross products are
 #            accumulated in fp32 on the bf16 MFMA pipe (16x the fp32 MFMA rate on gfx950); measured
-#            error against fp64 is the same as the native path's (tests/test_ops_gpu.py).  Default.
+#            error against fp64 is the same as the native path's (tests/test_ops_gpu.py).  The strict option.
 #   "h2"     every fp32 operand becomes TWO fp16 terms of the tensor scaled by a power of two (absmax below) and
-#            three cross products are accumulated in fp32: half the matrix work of "x3", per-product error
-#            <= 2^-21 (csrc/gemm_engine.h).
+#            three cross products are accumulated in fp32: half the matrix work of "x3".  Default.  Operand error
+#            |x^ - x| <= 2^-23 |x| + 2^-38 max|x| over x's tensor: 2^-23 relative within 2^-16 of the maximum,
+#            one bit less per binade below (csrc/gemm_engine.h, tests/split_ref.py).
 #   "native" v_mfma_f32_32x32x2_f32.
 FP32_MATMUL = os.environ.get("PE_FP32_MATMUL", "h2")
 _FP32_MODES = ("native", "x3", "h2")
@@ -462,7 +463,8 @@ def conv3x3_fwd(x, w_packed, out=None, accumulate=False, bn_stats=None, amax=Non
     h2 = ()
     if sfx == "_h2":
         amax_w = pw.amax if pw.amax is not None else absmax(w32)
-        h2 = ((absmax(x) if amax is None else amax).data_ptr(), amax_w.data_ptr())
+        amax = absmax(x) if amax is None else amax                      # (held: see conv3x3_wgrad)
+        h2 = (amax.data_ptr(), amax_w.data_ptr())
     if (pw.frag is not None and pw.terms == _mode_terms() and CONV_WFRAG
             and (pw.terms != 1 or pw.half == HALF_DTYPE) and _lib.load().pe_conv3x3_wf_supported(F, Cc, N)):
         parts = None
@@ -496,7 +498,11 @@ def conv3x3_wgrad(x, dy, dw, amax_x=None, amax_dy=None):
     ws = workspace(lib.pe_conv3x3_wgrad_workspace_bytes(B, T, F, Ci, Co), x.device)
     h2 = ()
     if _tn_suffix() == "_h2":
-        h2 = ((absmax(x) if amax_x is None else amax_x).data_ptr(), (absmax(dy) if amax_dy is None else amax_dy).data_ptr())
+        # both words stay referenced until the launch: a temporary dropped after .data_ptr() returns its memory to
+        # the caching allocator, the second absmax() can reuse it, and x is then scaled by dy's word (Inf / NaN)
+        amax_x = absmax(x) if amax_x is None else amax_x
+        amax_dy = absmax(dy) if amax_dy is None else amax_dy
+        h2 = (amax_x.data_ptr(), amax_dy.data_ptr())
     _call("pe_conv3x3_wgrad" + _tn_suffix(), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, T, F, Ci, Co,
           ws.data_ptr(), ws.numel(), *h2, _s(), work=2.0 * B * T * F * Co * 9 * Ci)
     return dw
@@ -851,7 +857,8 @@ def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H, amax_dg=None, amax_y=
     if _tn_suffix() == "_h2":
         if amax_y is None:                 # |h| < 1 by construction (o * tanh(c)): a constant bound is a valid amax
             amax_y = _unit_amax(dgates.device)
-        h2 = ((absmax(dgates) if amax_dg is None else amax_dg).data_ptr(), amax_y.data_ptr())
+        amax_dg = absmax(dgates) if amax_dg is None else amax_dg      # (held: see conv3x3_wgrad)
+        h2 = (amax_dg.data_ptr(), amax_y.data_ptr())
     _call("pe_lstm_whh_grad" + _tn_suffix(), dgates.data_ptr(), ys.data_ptr(), ys.stride(1), dwhh.data_ptr(), B, T, H,
           int(bool(reverse)), ws.data_ptr(), ws.numel(), *h2, _s(), work=2.0 * B * T * 4 * H * H)
     return dwhh

@@ -1,8 +1,9 @@
 """Each HIP op, called through the C ABI, against a plain PyTorch fp32/fp64 CPU reference of the same op.
 
-fp32 products run either on the native fp32 MFMA (an exact-f32 fmaf chain) or as the exact three-term
-bf16 split ("x3", the default); both are held to 1e-5 of the result scale (north_star: 1e-4 relative
-for fp32) and the GEMM / conv tests run in both modes.  Index/layout work is bit-exact.
+fp32 products run on the native fp32 MFMA (an exact-f32 fmaf chain), as the exact three-term bf16 split ("x3") or as
+two scaled fp16 terms ("h2", the default); all are held to 1e-5 of the result scale (north_star: 1e-4 relative for
+fp32) and the GEMM / conv tests run in every mode.  Per-element checks of the split modes against float64 models of
+their terms are in tests/test_split_products_gpu.py.  Index/layout work is bit-exact.
 """
 import numpy as np
 import pytest
