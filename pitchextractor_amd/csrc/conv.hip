@@ -523,13 +523,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_kernel(const float* __r
   }
 }
 
-// The same 9-tap tile on the bf16 MFMA pipe with the exact three-term split (gemm_engine.h): dY and the
-// X windows are staged as three [row][64 + 32 pad] bf16 images each, MFMA fragments (8 consecutive pixels
-// of one channel) come from ds_read_b64_tr_b16, and the border mask becomes a 16-bit AND mask per pixel:
-// Mk16[d][w][k] covers source row k + d of window w for column shift df = d - 1, so the 8 masks of a
-// fragment are one aligned 16-byte read.
+// The same 9-tap tile on the bf16 MFMA pipe with the exact three-term split (gemm_engine.h): dY and X are
+// staged as [row][64 + 32 pad] 16-bit term images, and MFMA fragments (8 consecutive pixels of one channel)
+// come from ds_read_b64_tr_b16.  X is staged either as ONE halo -- the 2F + 34 consecutive pixels
+// [k0 - F - 1, k0 + 33 + F), window row of tap (dt, df) for pixel k: (dt + 1) F + k + df + 1 -- where the
+// three row windows overlap (HALO, 2F + 34 <= 80: the F = 10 / 20 layers), or as three disjoint 34-row
+// windows [k0 + dt F - 1, k0 + dt F + 33) one after the other (F = 40 / 80).
+// Border taps: in ds_read_b64_tr_b16 every lane addresses one pixel row of a 4-row block, so a lane whose pixel
+// has no source for tap (dt, df) -- the shift leaves the utterance, or wraps past column 0 / F-1 -- points that
+// read at an all-zero row behind the staged rows.  The MFMAs see the bits an AND mask would leave (+0) without
+// any vector work on the fragments; validity comes from running (t, f) counters of the lane's 4 pixels per
+// k-tile.  Pixels at or past P need no test: every X row they can reach there is outside the tensor (zero) or
+// is masked by the counters, which run on as if more utterances followed.
 // NT: 3 = exact three-term split, 2 = two scaled fp16 terms, 1 = operands rounded to TH
-template <int NT, class TA = float, class TH = __bf16>
+template <int NT, bool HALO, class TA = float, class TH = __bf16>
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __restrict__ dy,
                                                                    const TA* __restrict__ x,
                                                                    float* __restrict__ ws, int T, int F, int Cin,
@@ -539,10 +546,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
   if constexpr (NT == 2) hs.load(amax_dy, amax_x);
   using H = term_t<NT, TH>;
   constexpr int ST = 96;                                   // 16-bit elements per staged row
-  constexpr int YIMG = kBK * ST, XIMG = 102 * ST;
+  constexpr int XP = HALO ? 5 : 7;                         // X staging passes of 16 rows
+  constexpr int XR = HALO ? 80 : 102;                      // staged X rows; row XR of every image is all zero
+  constexpr int YIMG = kBK * ST, XIMG = (XR + 1) * ST;
   __shared__ __attribute__((aligned(16))) H Ys[NT * YIMG];
   __shared__ __attribute__((aligned(16))) H Xs[NT * XIMG];
-  __shared__ __attribute__((aligned(16))) unsigned short Mk16[9 * kBK];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1, r = lane & 31, h = lane >> 5;
   const int g1 = (lane >> 4) & 1, q4 = (lane & 15) >> 2, p4 = (lane & 3) * 4;
@@ -553,6 +561,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
   const int m0 = (tile_id / tiles_n) * 64, n0 = (tile_id % tiles_n) * 64;
   const int kb = split_id * k_per_split;
   const int ke = min(P, kb + k_per_split);
+  const int XW = HALO ? 2 * F + 34 : 102;                  // X rows staged per k-tile
+  const int WS = HALO ? F : 34;                            // row distance of the dt windows
 
   f32x16 acc[9];
 #pragma unroll
@@ -562,19 +572,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
 
   const int c4 = (tid & 15) * 4;
   typedef typename RawQuad<TA>::type Raw;
-  Raw ry[2], rx[7];
+  Raw ry[2], rx[XP];
   // Branch-free requests (see RowLoaderT): the descriptors are re-based per k-tile in scalar registers -- dY at pixel
-  // k0 with the rows left in this split as its range, X at the first pixel of the three-row window (clamped to the
-  // tensor; offsets of pixels in front of it wrap to huge unsigned values) -- so every out-of-range pixel reads as zero.
+  // k0 with the rows left in this split as its range, X at the first staged pixel k0 - F - 1 (clamped to the tensor;
+  // offsets of pixels in front of it wrap to huge unsigned values) -- so every out-of-range pixel reads as zero.
   constexpr unsigned kEsz = (unsigned)sizeof(TA);
-  unsigned voy[2], vox[7];
+  unsigned voy[2], vox[XP];
 #pragma unroll
   for (int i = 0; i < 2; ++i) voy[i] = (unsigned)(((tid >> 4) + 16 * i) * Cout + m0 + c4) * kEsz;
 #pragma unroll
-  for (int i = 0; i < 7; ++i) {
+  for (int i = 0; i < XP; ++i) {
     const int wr = (tid >> 4) + 16 * i;
-    const int w = wr / 34, row = wr - w * 34;
-    vox[i] = wr < 102 ? (unsigned)((w * F + row) * Cin + n0 + c4) * kEsz : 0x80000000u;
+    const int w = HALO ? 0 : wr / 34, row = wr - w * 34;
+    vox[i] = wr < XW ? (unsigned)((w * F + row) * Cin + n0 + c4) * kEsz : 0x80000000u;
   }
   auto fetch = [&](int k0) {
     const int rows_y = min(ke - k0, kBK);
@@ -588,7 +598,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
         const_cast<TA*>(x + (long)base_row * Cin), 0, (unsigned)(nrows > 0 ? nrows * Cin : 0) * kEsz, 0x00020000);
     const unsigned dlt = (unsigned)((first - base_row) * Cin) * kEsz;        // <= 0: wraps
 #pragma unroll
-    for (int i = 0; i < 7; ++i) rx[i] = ldraw_buffer<TA>(rsx, vox[i] + dlt, 0u);
+    for (int i = 0; i < XP; ++i)
+      if (16 * i < XW) rx[i] = ldraw_buffer<TA>(rsx, vox[i] + dlt, 0u);    // (whole passes past the halo: skipped)
   };
   auto store3 = [&](H* img, int img_elems, int off, const Raw& raw, float scale) {
     if constexpr (NT == 1 && !std::is_same<TA, float>::value) {
@@ -609,37 +620,40 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
       *reinterpret_cast<half4<H>*>(img + off) = to_half4<H>(v);
     }
   };
+  if (tid < 16) {                                          // the zero row (64 columns) of every X image
+#pragma unroll
+    for (int c = 0; c < NT; ++c) *reinterpret_cast<uint2*>(Xs + c * XIMG + XR * ST + tid * 4) = make_uint2(0u, 0u);
+  }
+  // this lane's 4 pixels of a k-tile, k0 + 16 kk + 8 h + q4 + 4 e (j = 2 kk + e), as (t, f) counters
+  int tj[4], fj[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int p = kb + 16 * (j >> 1) + 8 * h + q4 + 4 * (j & 1);
+    fj[j] = p % F;
+    tj[j] = (p / F) % T;
+  }
+  const int f_step = kBK % F, t_step = (kBK / F) % T;
   fetch(kb);
   const H* a_rd = Ys + (8 * h + q4) * ST + wm * 32 + 16 * g1 + p4;
   const H* b_rd = Xs + (8 * h + q4) * ST + wn * 32 + 16 * g1 + p4;
+  const H* z_rd = Xs + XR * ST + wn * 32 + 16 * g1 + p4;
   for (int k0 = kb; k0 < ke; k0 += kBK) {
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 2; ++i) store3(Ys, YIMG, ((tid >> 4) + 16 * i) * ST + c4, ry[i], hs.sa);
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
+    for (int i = 0; i < XP; ++i) {
       const int wr = (tid >> 4) + 16 * i;
-      if (wr < 102) store3(Xs, XIMG, wr * ST + c4, rx[i], hs.sb);
-    }
-    if (tid < 102) {                                       // border masks of this k-tile's source rows
-      const int w = tid / 34, row = tid - w * 34;
-      const long q = (long)k0 + (long)(w - 1) * F + row - 1;
-      bool mv[3] = {false, false, false};
-      if (q >= 0 && q < P) {
-        const int fq = (int)(q % F), tq = (int)((q / F) % T);
-        const bool trow = !((w == 2 && tq == 0) || (w == 0 && tq == T - 1));   // dt = w - 1
-        mv[0] = trow && fq != F - 1;                       // df = -1: source column F-1 means the shift wrapped
-        mv[1] = trow;
-        mv[2] = trow && fq != 0;                           // df = +1
-      }
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const int k = row - d;
-        if (k >= 0 && k < kBK) Mk16[(d * 3 + w) * kBK + k] = mv[d] ? 0xffffu : 0u;
-      }
+      if (16 * i < XW && (HALO || wr < XR)) store3(Xs, XIMG, wr * ST + c4, rx[i], hs.sb);
     }
     __syncthreads();
     if (k0 + kBK < ke) fetch(k0 + kBK);
+    bool tv[4][2], fv[4][2];                               // sources for dt = -1 / +1, df = -1 / +1
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      tv[j][0] = tj[j] > 0; tv[j][1] = tj[j] < T - 1;
+      fv[j][0] = fj[j] > 0; fv[j][1] = fj[j] < F - 1;
+    }
 #pragma unroll
     for (int kk = 0; kk < kBK / 16; ++kk) {
       half8<H> fa[NT];
@@ -649,16 +663,30 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
       for (int w = 0; w < 3; ++w)
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-          const uint4 mk = *reinterpret_cast<const uint4*>(Mk16 + (d * 3 + w) * kBK + kk * 16 + 8 * h);
+          const H* rd[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int j = 2 * kk + e;
+            const bool ok = (w == 1 || tv[j][w >> 1]) && (d == 1 || fv[j][d >> 1]);
+            rd[e] = ok ? b_rd + (w * WS + kk * 16 + 4 * e + d) * ST : z_rd;
+          }
           half8<H> fb[NT];
 #pragma unroll
           for (int c = 0; c < NT; ++c) {
-            uint4 v = __builtin_bit_cast(uint4, tr_fragment(b_rd + c * XIMG + (w * 34 + kk * 16 + d) * ST, ST));
-            v.x &= mk.x; v.y &= mk.y; v.z &= mk.z; v.w &= mk.w;
+            const s16x4 lo = lds_read_tr(rd[0] + c * XIMG), hi = lds_read_tr(rd[1] + c * XIMG);
+            typedef short s16x8 __attribute__((ext_vector_type(8)));
+            const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             fb[c] = __builtin_bit_cast(half8<H>, v);
           }
           acc[w * 3 + d] = mfma_terms<NT>(fa, fb, acc[w * 3 + d]);
         }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                          // advance the pixels by one k-tile
+      fj[j] += f_step;
+      tj[j] += t_step;
+      if (fj[j] >= F) { fj[j] -= F; ++tj[j]; }
+      if (tj[j] >= T) tj[j] -= T;
     }
   }
 #pragma unroll
@@ -672,6 +700,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
     }
   }
 }
+
+// X staged as one halo (2F + 34 rows, XR = 80) when it fits, else as three 34-row windows
+static inline bool wgrad9_halo(int F) { return 2 * F + 34 <= 80; }
 
 // sum slabs in split order and scatter to OIHW: dw[(co*Cin + ci)*9 + tap]
 __global__ void conv3x3_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int splits,
@@ -1028,15 +1059,17 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
   hipStream_t st = pe_stream(stream);
   if (wgrad9_ok(Cout, Cin)) {
     const int P = B * T * F, tn = Cin / 64;
+    const dim3 grid((Cout / 64) * tn * splits);
+    const bool halo = wgrad9_halo(F);
     if (MODE == kSplit)
-      hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<3, TA>), dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
-                         workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
+      hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<3, true, TA> : conv3x3_wgrad9_x3_kernel<3, false, TA>), grid,
+                         dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
     else if (MODE == kSplit2)
-      hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<2, TA>), dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
-                         workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
+      hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<2, true, TA> : conv3x3_wgrad9_x3_kernel<2, false, TA>), grid,
+                         dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
     else if (MODE == kBf16)
-      hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<1, TA, TH>), dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
-                         workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
+      hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<1, true, TA, TH> : conv3x3_wgrad9_x3_kernel<1, false, TA, TH>),
+                         grid, dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
     else if constexpr (std::is_same<TA, float>::value)
       hipLaunchKernelGGL(conv3x3_wgrad9_kernel<0>, dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
                          workspace, T, F, Cin, Cout, P, kps, tn);
