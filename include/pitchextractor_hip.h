@@ -17,11 +17,13 @@
  *     the reference's OIHW order and repacked on the device;
  *   - return value: 0 = ok, negative = invalid argument (PE_E_*), positive =
  *     hipError_t of a failed runtime call;
- *   - MFMA-bound entry points come in up to three forms with one contract:
- *       name       fp32 products on v_mfma_f32_32x32x2_f32;
- *       name_x3    fp32-accurate products as an exact three-term bf16 split on
- *                  v_mfma_f32_32x32x16_bf16 (the host side's default);
- *       name_bf16  operands rounded to bf16, fp32 accumulate (mixed precision).
+ *   - MFMA-bound entry points take the product form as their first parameter,
+ *     `int products` (enum pe_products below), and keep one contract in every
+ *     form; entry points that read or write the conv stack's activations also
+ *     take `int act16` (0 = fp32 tensors, 1 = bf16 tensors, see "bf16
+ *     ACTIVATION STORAGE").  A form or activation type that none of an entry
+ *     point's kernels serves returns PE_E_UNSUPPORTED; a `products` value
+ *     outside the enum returns PE_E_ARG.
  */
 #ifndef PITCHEXTRACTOR_HIP_H
 #define PITCHEXTRACTOR_HIP_H
@@ -37,6 +39,16 @@ extern "C" {
 #define PE_E_ARG (-1)       /* bad size / null pointer            */
 #define PE_E_UNSUPPORTED (-2) /* shape outside what the kernels take */
 #define PE_E_WORKSPACE (-3) /* workspace too small                 */
+
+/* How the products of an MFMA-bound entry point run; accumulation is fp32 and tensors in memory keep their type in
+ * every form. */
+enum pe_products {
+  PE_PROD_NATIVE = 0, /* fp32 products on v_mfma_f32_32x32x2_f32 */
+  PE_PROD_X3 = 1,     /* fp32-accurate: operands split exactly into three bf16 terms, six bf16 MFMAs per product */
+  PE_PROD_H2 = 2,     /* two fp16 terms of each operand scaled by a power of two, three fp16 MFMAs (the default) */
+  PE_PROD_BF16 = 3,   /* operands rounded to bf16 (mixed precision) */
+  PE_PROD_F16 = 4     /* operands rounded to IEEE half (mixed precision; the caller scales the loss) */
+};
 
 /* library / device ------------------------------------------------------- */
 int pe_abi_version(void);
@@ -83,29 +95,20 @@ int pe_mel_forward_ragged(const pe_mel_plan* plan, const float* wave, int batch,
  * pe_gemm_nt: C[M][N] = A[M][K] . B[N][K]^T + bias0[n] + bias1[n] (+ C when accumulate).
  *   nn.Linear / LSTM input projection (model.py:220-227) / 1x1 convs (model.py:53,167).
  * pe_gemm_tn: C[M][N] = sum_k A[k][m] * B[k][n] (+ C): weight gradients, k split across
- *   workgroups into workspace slabs that are reduced in a fixed order (deterministic). */
-int pe_gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-               int K, const float* bias0, const float* bias1, int accumulate, void* stream);
-/* Opt-in mixed-precision variant (reference trainer.py:103 autocast): same contract, operands rounded to
- * bf16 on the way into LDS (v_mfma_f32_32x32x16_bf16), fp32 accumulate, fp32 tensors in HBM. */
-int pe_gemm_nt_bf16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                    int K, const float* bias0, const float* bias1, int accumulate, void* stream);
-/* fp32-accurate variant on the bf16 MFMA pipe: each fp32 operand is split exactly into three bf16 terms
- * (x = hi + mid + lo) and six of the nine cross products are accumulated in fp32; the dropped terms are
- * below 2^-23 of each product, i.e. under the rounding of an fp32 product.  Same contract as pe_gemm_nt. */
-int pe_gemm_nt_x3(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                  int K, const float* bias0, const float* bias1, int accumulate, void* stream);
-/* "h2": fp32 products from TWO fp16 terms per operand and three fp16 MFMAs per product block (half the matrix work of
- * the x3 split).  x * s = hi + lo with hi = RN_f16(x s), lo = RN_f16(x s - hi); hi_a lo_b + lo_a hi_b + hi_a hi_b is
- * accumulated in fp32 and lo_a lo_b (<= 2^-24 |a b|) dropped: per-product error <= 2^-21 |a b|, unbiased.  Each
- * operand tensor carries a power-of-two scale s = 2^(140 - E), E = biased exponent of its largest magnitude, which
- * the kernel derives from *amax_a / *amax_b (device words holding the IEEE bits of max |x|: pe_absmax, or the
- * epilogue of the kernel that produced the tensor); a value smaller than the tensor's true maximum makes fp16
- * overflow possible, a larger one only costs resolution (2^-38 of the stated maximum, absolute).  Same contract as
- * pe_gemm_nt otherwise. */
-int pe_gemm_nt_h2(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                  int K, const float* bias0, const float* bias1, int accumulate, const unsigned* amax_a,
-                  const unsigned* amax_b, void* stream);
+ *   workgroups into workspace slabs that are reduced in a fixed order (deterministic).
+ * Every form of pe_products.  PE_PROD_X3: x = hi + mid + lo exactly in bf16 and six of the nine cross products are
+ * accumulated; the dropped terms are below 2^-23 of each product, i.e. under the rounding of an fp32 product.
+ * PE_PROD_H2: x * s = hi + lo with hi = RN_f16(x s), lo = RN_f16(x s - hi); hi_a lo_b + lo_a hi_b + hi_a hi_b is
+ * accumulated and lo_a lo_b (<= 2^-24 |a b|) dropped: per-product error <= 2^-21 |a b|, unbiased.  Each operand tensor
+ * carries a power-of-two scale s = 2^(140 - E), E = biased exponent of its largest magnitude, which the kernel derives
+ * from *amax_a / *amax_b (device words holding the IEEE bits of max |x|: pe_absmax, or the epilogue of the kernel that
+ * produced the tensor); a value smaller than the tensor's true maximum makes fp16 overflow possible, a larger one only
+ * costs resolution (2^-38 of the stated maximum, absolute).  The scale words are read under PE_PROD_H2 only (PE_E_ARG
+ * without them) and may be NULL otherwise.  PE_PROD_BF16 / PE_PROD_F16 round the operands on the way into LDS
+ * (reference trainer.py:103 autocast).  act16 = 1 (PE_PROD_BF16 only): A and C (nt) or A and B (tn) are bf16 tensors. */
+int pe_gemm_nt(int products, int act16, const void* A, long lda, const float* B, long ldb, void* C, long ldc, int M,
+               int N, int K, const float* bias0, const float* bias1, int accumulate, const unsigned* amax_a,
+               const unsigned* amax_b, void* stream);
 /* out[0] = IEEE bits of max |x| over a [rows][cols] matrix with leading dimension ld (cols, ld % 4 == 0, x 16-byte
  * aligned); zeroes out[0] first.  Exact and order-independent (integer max of the magnitudes' bit patterns). */
 int pe_absmax(const float* x, long rows, int cols, long ld, unsigned* out, void* stream);
@@ -114,15 +117,9 @@ int pe_absmax(const float* x, long rows, int cols, long ld, unsigned* out, void*
 int pe_absmax_segments(const float* base, const long* seg_off, const long* seg_len, int nseg, unsigned* out,
                        void* stream);
 size_t pe_gemm_tn_workspace_bytes(int M, int N, int K);
-int pe_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-               int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream);
-int pe_gemm_tn_x3(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                  int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream);
-int pe_gemm_tn_bf16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                    int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream);  /* mixed precision */
-int pe_gemm_tn_h2(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                  int K, int accumulate, float* workspace, size_t workspace_bytes, const unsigned* amax_a,
-                  const unsigned* amax_b, void* stream);   /* two-term fp16 split, see pe_gemm_nt_h2 */
+int pe_gemm_tn(int products, int act16, const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M,
+               int N, int K, int accumulate, float* workspace, size_t workspace_bytes, const unsigned* amax_a,
+               const unsigned* amax_b, void* stream);
 int pe_transpose2d(const float* in, float* out, int rows, int cols, void* stream);
 
 /* ---- 3x3 / pad 1 convolutions (model.py:23-28,157-161), channels-last -------
@@ -131,104 +128,58 @@ int pe_transpose2d(const float* in, float* out, int rows, int cols, void* stream
  * pe_conv3x3_fwd:  y[B][T][F][N] (+)= conv(x[B][T][F][C], w_packed[N][9*C]); the data gradient
  *   is the same call with (dy, w_dgrad, C = Cout, N = Cin).
  * pe_conv3x3_wgrad: dw (OIHW) = sum_pixels dy (x) shifted x.
- * pe_conv3x3_c1_*: the Cin = 1 first layer; x element (b,t,f) at x[b*sb + t*st + f*sf]. */
+ * pe_conv3x3_c1_*: the Cin = 1 first layer; x element (b,t,f) at x[b*sb + t*st + f*sf].
+ * Forms and scale words as pe_gemm_nt (amax_x / amax_w / amax_dy: the absmax words of x, the weight and dy). */
 int pe_conv3x3_repack(const float* w_oihw, float* w_fwd, float* w_dgrad, int Cout, int Cin, void* stream);
-int pe_conv3x3_fwd(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
-                   int accumulate, void* stream);
-int pe_conv3x3_fwd_bf16(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
-                        int accumulate, void* stream);   /* bf16 operands, fp32 accumulate (see pe_gemm_nt_bf16) */
-int pe_conv3x3_fwd_x3(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
-                      int accumulate, void* stream);     /* fp32-accurate, three-term bf16 split (see pe_gemm_nt_x3) */
-int pe_conv3x3_fwd_h2(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
-                      int accumulate, const unsigned* amax_x, const unsigned* amax_w,
-                      void* stream);                       /* two scaled fp16 terms (see pe_gemm_nt_h2) */
-/* Weights pre-packed as MFMA B-operand fragments (x3: three exact bf16 terms, terms = 3; mixed precision: one
- * RNE-rounded term, terms = 1).  w is [N][K] row-major fp32 (K % 16 == 0); fragment (kb, nb, term) holds, for
- * lane 32 h + r, w[32 nb + r][16 kb + 8 h .. + 7] in 16 bytes, the 64 lanes contiguous (1 KB).  The halo
- * convolution then loads its weight operands straight from L2 into registers: LDS carries only activations.
- * pe_conv3x3_wf_supported: 1 if (F, C, N) is served by the fragment-fed kernel (else use pe_conv3x3_fwd_*). */
-size_t pe_wfrag_bytes(int N, int K, int terms);
-int pe_wfrag_pack(const float* w, long ld, int N, int K, int terms, void* wfrag, void* stream);
-/* "h2" form: two fp16 terms of w * 2^(140 - E) per weight, E from *amax (pe_absmax of w); pe_wfrag_bytes(N, K, 2). */
-int pe_wfrag_pack_h2(const float* w, long ld, int N, int K, const unsigned* amax, void* out, void* stream);
+int pe_conv3x3_fwd(int products, int act16, const void* x, const float* w_packed, void* y, int B, int T, int F, int C,
+                   int N, int accumulate, const unsigned* amax_x, const unsigned* amax_w, void* stream);
+/* Weights pre-packed as MFMA B-operand fragments in the terms of `products` (x3: three exact bf16 terms; h2: two fp16
+ * terms of w * 2^(140 - E), E from *amax = pe_absmax of w; bf16 / f16: one RNE-rounded term; no native form).  w is
+ * [N][K] row-major fp32 (K % 16 == 0); fragment (kb, nb, term) holds, for lane 32 h + r, w[32 nb + r][16 kb + 8 h .. + 7]
+ * in 16 bytes, the 64 lanes contiguous (1 KB).  The halo convolution pe_conv3x3_fwd_wf then loads its weight operands
+ * straight from L2 into registers: LDS carries only activations.  It takes fragments packed for the same form (under
+ * h2, with the same *amax_w).
+ * pe_conv3x3_wf_supported: 1 if (F, C, N) is served by the fragment-fed kernel (else use pe_conv3x3_fwd).
+ * pe_wfrag_bytes: 0 for a form without fragments or K % 16 != 0. */
+size_t pe_wfrag_bytes(int products, int N, int K);
+int pe_wfrag_pack(int products, const float* w, long ld, int N, int K, const unsigned* amax, void* wfrag, void* stream);
 int pe_conv3x3_wf_supported(int F, int C, int N);
-int pe_conv3x3_fwd_wf_x3(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                         int accumulate, double* bn_partials, void* stream);
-int pe_conv3x3_fwd_wf_h2(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                         int accumulate, double* bn_partials, const unsigned* amax_x, const unsigned* amax_w,
-                         void* stream);                    /* wfrag from pe_wfrag_pack_h2 with the same *amax_w */
-int pe_conv3x3_fwd_wf_bf16(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                           int accumulate, double* bn_partials, void* stream);
+int pe_conv3x3_fwd_wf(int products, int act16, const void* x, const void* wfrag, void* y, int B, int T, int F, int C,
+                      int N, int accumulate, double* bn_partials, const unsigned* amax_x, const unsigned* amax_w,
+                      void* stream);
 /* bn_partials (optional): [pe_conv3x3_wf_stat_parts(B,T,F)][2][N] doubles -- per pixel tile, the column sums and sums
  * of squares of the FINAL outputs; pe_bn_finalize_stats turns them into the statistics of the BatchNorm that follows
  * (no separate pass over the activation). */
 int pe_conv3x3_wf_stat_parts(int B, int T, int F);
 size_t pe_conv3x3_wgrad_workspace_bytes(int B, int T, int F, int Cin, int Cout);
-int pe_conv3x3_wgrad(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                     int Cout, float* workspace, size_t workspace_bytes, void* stream);
-int pe_conv3x3_wgrad_x3(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                        int Cout, float* workspace, size_t workspace_bytes, void* stream);
-int pe_conv3x3_wgrad_h2(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin, int Cout,
-                        float* workspace, size_t workspace_bytes, const unsigned* amax_x, const unsigned* amax_dy,
-                        void* stream);
-int pe_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                          int Cout, float* workspace, size_t workspace_bytes, void* stream);   /* mixed precision */
+int pe_conv3x3_wgrad(int products, int act16, const void* x, const void* dy, float* dw_oihw, int B, int T, int F,
+                     int Cin, int Cout, float* workspace, size_t workspace_bytes, const unsigned* amax_x,
+                     const unsigned* amax_dy, void* stream);
 /* first convolution (1 -> 64 channels).  bn_partials (nullable): [pe_conv3x3_c1_stat_parts()][2][64] doubles that
  * receive per-workgroup sums / sums of squares of the output channels (input of pe_bn_finalize_stats). */
 int pe_conv3x3_c1_stat_parts(int B, int T, int F);
-int pe_conv3x3_c1_fwd(const float* x, long sb, long st, long sf, const float* w_oihw, float* y, int B,
-                      int T, int F, double* bn_partials, void* stream);
-int pe_conv3x3_c1_wgrad(const float* x, long sb, long st, long sf, const float* dy, float* dw_oihw,
-                        int B, int T, int F, float* workspace, size_t workspace_bytes, void* stream);
+int pe_conv3x3_c1_fwd(int act16, const float* x, long sb, long st, long sf, const float* w_oihw, void* y, int B, int T,
+                      int F, double* bn_partials, void* stream);
+int pe_conv3x3_c1_wgrad(int act16, const float* x, long sb, long st, long sf, const void* dy, float* dw_oihw, int B,
+                        int T, int F, float* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- fused self-attention (model.py:231-239: nn.MultiheadAttention inside TransformerEncoderLayer) -------------
  * qkv [B*T][ld_qkv] packed projections (Q | K | V, head h at columns h*dh of each part); o [B*T][ld_o] merged
  * heads; lse [B*H*T]; masks [B*H*T][T] bytes (1 = kept), element quad i = row * T/4 + key/4 draws Philox counter
  * offset + i exactly like pe_dropout_fwd on the (B*H*T) x T probability matrix.  One workgroup per (batch, head),
  * scores stay in registers; the backward recomputes them from lse.  pe_attn_supported: 1 for T = 192, dh = 64
- * (other shapes: pe_bgemm + pe_softmax_*). */
+ * (other shapes: pe_bgemm + pe_softmax_*).
+ * PE_PROD_NATIVE: fp32 MFMAs.  PE_PROD_BF16: the matmul operands (Q, K, V, dO, the probabilities and the score
+ * gradients) rounded to bf16 and multiplied on v_mfma_f32_16x16x16_bf16, as torch.autocast runs the attention of
+ * trainer.py:226-235; softmax, log-sum-exp, accumulation and every tensor in memory stay fp32, masks and Philox counters
+ * as above.  No other form. */
 int pe_attn_supported(int T, int dh);
-int pe_attn_fwd(const float* qkv, long ld_qkv, float* o, long ld_o, float* lse, const unsigned char* mask_in,
-                unsigned char* mask_out, int B, int T, int H, int dh, float scale, float p_drop,
-                unsigned long long seed, unsigned long long offset, void* stream);
-int pe_attn_bwd(const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o, const float* lse,
-                const unsigned char* mask, float* dqkv, int B, int T, int H, int dh, float scale, float p_drop,
-                void* stream);
-/* The same two passes with the matmul operands (Q, K, V, dO, the probabilities and the score gradients) rounded to
- * bf16 and multiplied on v_mfma_f32_16x16x16_bf16, as torch.autocast runs the attention of trainer.py:226-235; softmax,
- * log-sum-exp, accumulation and every tensor in memory stay fp32, masks and Philox counters as above. */
-int pe_attn_fwd_bf16(const float* qkv, long ld_qkv, float* o, long ld_o, float* lse, const unsigned char* mask_in,
-                     unsigned char* mask_out, int B, int T, int H, int dh, float scale, float p_drop,
-                     unsigned long long seed, unsigned long long offset, void* stream);
-int pe_attn_bwd_bf16(const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o, const float* lse,
-                     const unsigned char* mask, float* dqkv, int B, int T, int H, int dh, float scale, float p_drop,
-                     void* stream);
-
-/* ---- fp16 operands (the reference's autocast default dtype, trainer.py:64-102) -------------------------------
- * Same contracts as the *_bf16 entry points above with operands rounded (RNE) to IEEE half instead of bf16 and
- * multiplied by v_mfma_f32_32x32x16_f16; accumulation and every tensor in memory stay fp32.  fp16 has 5 exponent
- * bits: the caller scales the loss (Trainer's GradScaler) so that gradients stay above 2^-24.
- * pe_wfrag_pack_f16: fragment order of pe_wfrag_pack with one fp16 term per weight. */
-int pe_gemm_nt_f16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                    int K, const float* bias0, const float* bias1, int accumulate, void* stream);
-int pe_gemm_tn_f16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                    int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream);
-int pe_conv3x3_fwd_f16(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
-                        int accumulate, void* stream);
-int pe_conv3x3_fwd_wf_f16(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                          int accumulate, double* bn_partials, void* stream);
-int pe_conv3x3_wgrad_f16(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                          int Cout, float* workspace, size_t workspace_bytes, void* stream);
-int pe_lstm_fwd_persistent_f16(int ncells, const float* const* whh, float* const* gates, float* const* y,
-                           float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
-                           unsigned* sync, void* stream);
-int pe_lstm_bwd_persistent_f16(int ncells, const float* const* whh_t, float* const* gates,
-                           const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
-                           int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
-                           unsigned* sync, void* stream);
-int pe_lstm_whh_grad_f16(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                     int reverse, float* workspace, size_t workspace_bytes, void* stream);
-int pe_wfrag_pack_f16(const float* w, long ld, int N, int K, void* wfrag, void* stream);
+int pe_attn_fwd(int products, const float* qkv, long ld_qkv, float* o, long ld_o, float* lse,
+                const unsigned char* mask_in, unsigned char* mask_out, int B, int T, int H, int dh, float scale,
+                float p_drop, unsigned long long seed, unsigned long long offset, void* stream);
+int pe_attn_bwd(int products, const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o,
+                const float* lse, const unsigned char* mask, float* dqkv, int B, int T, int H, int dh, float scale,
+                float p_drop, void* stream);
 
 /* ---- BatchNorm2d (train statistics) / LeakyReLU / MaxPool2d((1,k)) / dropout -
  * Activations are [rows = B*T][F][C].  pe_bn_train_stats: batch mean / biased variance over all
@@ -239,10 +190,12 @@ int pe_wfrag_pack_f16(const float* w, long ld, int N, int K, void* wfrag, void* 
  * pe_bn_act_pool_bwd: gradient of that block w.r.t. x, gamma, beta (train-mode BN).
  * amax_out (optional, these two and pe_maxpool_bwd_add): a device word the caller zeroed; the pass max-merges the
  *   IEEE bits of the largest magnitude it stored into it (atomicMax), which is the scale source an "h2" product
- *   reading the output needs (pe_gemm_nt_h2) -- no separate pe_absmax pass.  pe_maxpool_bwd_add merges the values it
- *   rewrote into dx's word: the result bounds max |dx| from above. */
+ *   reading the output needs (PE_PROD_H2) -- no separate pe_absmax pass.  pe_maxpool_bwd_add merges the values it
+ *   rewrote into dx's word: the result bounds max |dx| from above.
+ * act16 (every pass of this section but pe_bn_finalize_stats / pe_bn_eval_affine): 0 = fp32 activation tensors, 1 =
+ *   bf16 (see "bf16 ACTIVATION STORAGE").  pe_bn_act_pool_bwd with act16 = 1 takes pool in {1, 2, 4}. */
 size_t pe_bn_workspace_bytes(int C);
-int pe_bn_train_stats(const float* x, long n_pix, int C, const float* gamma, const float* beta, float eps,
+int pe_bn_train_stats(int act16, const void* x, long n_pix, int C, const float* gamma, const float* beta, float eps,
                       float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
                       float* scale, float* shift, void* workspace, size_t workspace_bytes, void* stream);
 int pe_bn_finalize_stats(const double* partials, int nparts, long n_pix, int C, const float* gamma, const float* beta,
@@ -251,29 +204,29 @@ int pe_bn_finalize_stats(const double* partials, int nparts, long n_pix, int C, 
                          void* stream);   /* workspace: pe_bn_workspace_bytes(C) */
 int pe_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
                       const float* running_var, float eps, int C, float* scale, float* shift, void* stream);
-int pe_bn_act_pool_fwd(const float* x, const float* scale, const float* shift, float slope, float* y,
-                       long rows, int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out, void* stream);
-int pe_bn_act_pool_bwd(const float* x, const float* dy, const float* scale, const float* shift,
-                       const float* mean, const float* invstd, float slope, float* dx, float* dgamma,
-                       float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
-                       void* workspace, size_t workspace_bytes, unsigned* amax_out, void* stream);
+int pe_bn_act_pool_fwd(int act16, const void* x, const float* scale, const float* shift, float slope, void* y, long rows,
+                       int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out, void* stream);
+int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
+                       const float* mean, const float* invstd, float slope, void* dx, float* dgamma, float* dbeta,
+                       long rows, int Fin, int C, int pool, long lddy, int coff, void* workspace,
+                       size_t workspace_bytes, unsigned* amax_out, void* stream);
 /* detector-branch MaxPool2d((1,40|20|10)) (model.py:45-49,103-105) into a channel slice.  argmax_out (optional,
  * [rows * (Fin / pool)][C] bytes): the window position of each maximum (the first one, as torch's backward routes it);
  * pe_maxpool_bwd_add given that array as `argmax` scatters dy without reading x (x may then be NULL). */
-int pe_maxpool_fwd(const float* x, float* y, long rows, int Fin, int C, int pool, long ldy, int coff,
+int pe_maxpool_fwd(int act16, const void* x, void* y, long rows, int Fin, int C, int pool, long ldy, int coff,
                    unsigned char* argmax_out, void* stream);
-int pe_maxpool_bwd_add(const float* x, const unsigned char* argmax, const float* dy, float* dx, long rows, int Fin,
-                       int C, int pool, long lddy, int coff, unsigned* amax_out, void* stream);
+int pe_maxpool_bwd_add(int act16, const void* x, const unsigned char* argmax, const void* dy, void* dx, long rows,
+                       int Fin, int C, int pool, long lddy, int coff, unsigned* amax_out, void* stream);
 /* nn.Dropout (model.py:40,56; LSTM inter-layer): Philox4x32-10 keyed by (seed, offset + quad index);
  * mask bytes (1 = kept) can be exported (mask_out) or replayed (mask_in). */
-int pe_dropout_fwd(const float* x, long ldx, float* y, long ldy, const unsigned char* mask_in,
+int pe_dropout_fwd(int act16, const void* x, long ldx, void* y, long ldy, const unsigned char* mask_in,
                    unsigned char* mask_out, long rows, int cols, float p, unsigned long long seed,
                    unsigned long long offset, void* stream);
-/* (B,256,T,2) -> permute(0,2,1,3) -> (B,T,512) of model.py:93,112 and its transpose */
-int pe_nhwc_to_seq(const float* x, long ldx, int coff, float* seq, long rows, int C, void* stream);
-int pe_seq_to_nhwc(const float* seq, float* x, long ldx, int coff, long rows, int C, int accumulate,
+/* (B,256,T,2) -> permute(0,2,1,3) -> (B,T,512) of model.py:93,112 and its transpose; seq is fp32 in both */
+int pe_nhwc_to_seq(int act16, const void* x, long ldx, int coff, float* seq, long rows, int C, void* stream);
+int pe_seq_to_nhwc(int act16, const float* seq, void* x, long ldx, int coff, long rows, int C, int accumulate,
                    void* stream);
-int pe_copy2d(const float* src, long lds, float* dst, long ldd, long rows, int cols, int accumulate,
+int pe_copy2d(int act16, const void* src, long lds, void* dst, long ldd, long rows, int cols, int accumulate,
               void* stream);
 
 /* ---- LSTM recurrence (nn.LSTM of model.py:218-227; gates i,f,g,o; zero initial state) ----
@@ -296,44 +249,32 @@ int pe_lstm_bwd(int ncells, const float* const* whh_t, float* const* gates, cons
 size_t pe_lstm_persistent_sync_bytes(int ncells, int B);
 int pe_lstm_persistent_supported(int ncells, int B, int H);
 /* Persistent recurrences (H = 384): ONE launch per layer for all cells, W_hh resident on chip, workgroups hand h /
- * partial dh tiles to each other through memory.  The recurrent products are 16-bit-term MFMAs: `_x3` = the exact
- * three-term bf16 split (fp32-accurate), `_bf16` / `_f16` = operands rounded to 16 bits (mixed precision).  There is
- * no native-fp32 persistent form: pe_lstm_fwd / pe_lstm_bwd (one launch per time step) serve that mode and every
- * shape pe_lstm_persistent_supported() declines.
+ * partial dh tiles to each other through memory.  The recurrent products are 16-bit-term MFMAs: PE_PROD_X3 (the exact
+ * three-term bf16 split, fp32-accurate), PE_PROD_BF16 / PE_PROD_F16 (W_hh and the h / dgates rows rounded to 16 bits,
+ * fp32 accumulate and cell state).  There is no native-fp32 or h2 persistent form (PE_E_UNSUPPORTED): pe_lstm_fwd /
+ * pe_lstm_bwd (one launch per time step) serve those modes and every shape pe_lstm_persistent_supported() declines.
  * dbias_rows (nullable): per cell a [pe_lstm_bwd_persistent_dbias_rows()][4H] buffer that receives the per-batch-tile
  * column sums of the gate gradients (their row sum is dL/db_ih = dL/db_hh), replacing a pe_colsum pass over the
  * [B*T][4H] gradient tensor.
  * dgates_amax (nullable): per cell a device word the caller zeroed; the kernel max-merges the IEEE bits of the largest
  * gate-gradient magnitude into it (the "h2" scale source of the dX / dW products). */
 int pe_lstm_bwd_persistent_dbias_rows(int ncells, int B, int T, int H, long lddy);
-int pe_lstm_fwd_persistent_x3(int ncells, const float* const* whh, float* const* gates, float* const* y,
-                           float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
-                           unsigned* sync, void* stream);
-int pe_lstm_bwd_persistent_x3(int ncells, const float* const* whh_t, float* const* gates,
-                           const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
-                           int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
-                           unsigned* sync, void* stream);
-/* mixed precision: W_hh and the h / dgates rows rounded to bf16, fp32 accumulate and cell state */
-int pe_lstm_fwd_persistent_bf16(int ncells, const float* const* whh, float* const* gates, float* const* y,
-                           float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
-                           unsigned* sync, void* stream);
-int pe_lstm_bwd_persistent_bf16(int ncells, const float* const* whh_t, float* const* gates,
-                           const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
-                           int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
-                           unsigned* sync, void* stream);
+int pe_lstm_fwd_persistent(int products, int ncells, const float* const* whh, float* const* gates, float* const* y,
+                           float* const* cbuf, const int* reverse, long ldy, int B, int T, int H, unsigned* sync,
+                           void* stream);
+int pe_lstm_bwd_persistent(int products, int ncells, const float* const* whh_t, float* const* gates,
+                           const float* const* cbuf, const float* const* dy, const int* reverse, long lddy, int B,
+                           int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax, unsigned* sync,
+                           void* stream);
 /* Diagnostic (tools/stamp_lstm.py): 1 = run the stamped instantiations of the x3 kernels (s_memtime per region of an
  * iteration; grid <= 128 workgroups).  Returns the previous setting.  The product path never calls it. */
 int pe_lstm_configure_stamps(int enable);
 size_t pe_lstm_whh_grad_workspace_bytes(int B, int T, int H);
-int pe_lstm_whh_grad(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                     int reverse, float* workspace, size_t workspace_bytes, void* stream);
-int pe_lstm_whh_grad_x3(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                     int reverse, float* workspace, size_t workspace_bytes, void* stream);   /* three-term bf16 split */
-int pe_lstm_whh_grad_h2(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H, int reverse,
-                        float* workspace, size_t workspace_bytes, const unsigned* amax_dgates, const unsigned* amax_y,
-                        void* stream);
-int pe_lstm_whh_grad_bf16(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                     int reverse, float* workspace, size_t workspace_bytes, void* stream);   /* mixed precision */
+/* dW_hh = sum over batch and time of dgates^T . y shifted one step; every form of pe_products (scale words as
+ * pe_gemm_nt: amax_dgates, amax_y) */
+int pe_lstm_whh_grad(int products, const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
+                     int reverse, float* workspace, size_t workspace_bytes, const unsigned* amax_dgates,
+                     const unsigned* amax_y, void* stream);
 size_t pe_colsum_workspace_bytes(int cols);
 int pe_colsum(const float* x, long rows, int cols, long ld, float* out0, float* out1, void* workspace,
               size_t workspace_bytes, void* stream);
@@ -370,48 +311,15 @@ int pe_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_av
 /* GradScaler support (reference trainer.py:241-244): *flag = 1 if any of x[0..n) is inf or nan, else 0. */
 int pe_nonfinite_flag(const float* x, long n, int* flag, void* stream);
 
-/* ---- bf16 ACTIVATION STORAGE for mixed precision (`*_a16`) ------------------------------------------------------
+/* ---- bf16 ACTIVATION STORAGE for mixed precision (`act16 = 1`) -----------------------------------------------------
  * The reference's autocast keeps conv / linear outputs and what backward saves of them in 16 bits (trainer.py:226-235,
- * README.md:36).  These entry points are the fp32-tensor functions of the same name with the conv stack's activation
- * and activation-gradient tensors (x, y, dy, dx, the GEMM operand A and result C) stored as bf16 in HBM: half the bytes
- * of every BatchNorm / pooling / staging pass and of the saved-for-backward footprint.  Arithmetic, BatchNorm
- * statistics, weights, weight gradients and biases stay fp32; a store rounds to nearest even.  Statistics a kernel
- * leaves behind (bn_partials) are those of the ROUNDED values, i.e. of the tensor BatchNorm then reads.  Layouts,
- * strides (in elements) and argument meaning are unchanged; activation pointers need 8-byte alignment. */
-int pe_conv3x3_c1_fwd_a16(const float* x, long sb, long st, long sf, const float* w_oihw, void* y, int B, int T, int F,
-                          double* bn_partials, void* stream);
-int pe_conv3x3_c1_wgrad_a16(const float* x, long sb, long st, long sf, const void* dy, float* dw_oihw, int B, int T,
-                            int F, float* workspace, size_t workspace_bytes, void* stream);
-int pe_conv3x3_fwd_bf16_a16(const void* x, const float* w_packed, void* y, int B, int T, int F, int C, int N,
-                            int accumulate, void* stream);
-int pe_conv3x3_fwd_wf_bf16_a16(const void* x, const void* wfrag, void* y, int B, int T, int F, int C, int N,
-                               int accumulate, double* bn_partials, void* stream);
-int pe_conv3x3_wgrad_bf16_a16(const void* x, const void* dy, float* dw_oihw, int B, int T, int F, int Cin, int Cout,
-                              float* workspace, size_t workspace_bytes, void* stream);
-int pe_gemm_nt_bf16_a16(const void* A, long lda, const float* B, long ldb, void* C, long ldc, int M, int N, int K,
-                        const float* bias0, const float* bias1, int accumulate, void* stream);
-int pe_gemm_tn_bf16_a16(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, int K,
-                        int accumulate, float* workspace, size_t workspace_bytes, void* stream);
-int pe_bn_train_stats_a16(const void* x, long n_pix, int C, const float* gamma, const float* beta, float eps,
-                          float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
-                          float* scale, float* shift, void* workspace, size_t workspace_bytes, void* stream);
-int pe_bn_act_pool_fwd_a16(const void* x, const float* scale, const float* shift, float slope, void* y, long rows,
-                           int Fin, int C, int pool, long ldy, int coff, void* stream);
-int pe_bn_act_pool_bwd_a16(const void* x, const void* dy, const float* scale, const float* shift, const float* mean,
-                           const float* invstd, float slope, void* dx, float* dgamma, float* dbeta, long rows, int Fin,
-                           int C, int pool, long lddy, int coff, void* workspace, size_t workspace_bytes,
-                           void* stream);          /* pool in {1, 2, 4} */
-int pe_maxpool_fwd_a16(const void* x, void* y, long rows, int Fin, int C, int pool, long ldy, int coff,
-                       unsigned char* argmax_out, void* stream);
-int pe_maxpool_bwd_add_a16(const void* x, const unsigned char* argmax, const void* dy, void* dx, long rows, int Fin,
-                           int C, int pool, long lddy, int coff, void* stream);
-int pe_dropout_fwd_a16(const void* x, long ldx, void* y, long ldy, const unsigned char* mask_in,
-                       unsigned char* mask_out, long rows, int cols, float p, unsigned long long seed,
-                       unsigned long long offset, void* stream);
-int pe_nhwc_to_seq_a16(const void* x, long ldx, int coff, float* seq, long rows, int C, void* stream);   /* bf16 -> fp32 */
-int pe_seq_to_nhwc_a16(const float* seq, void* x, long ldx, int coff, long rows, int C, int accumulate,
-                       void* stream);                                                                    /* fp32 -> bf16 */
-int pe_copy2d_a16(const void* src, long lds, void* dst, long ldd, long rows, int cols, int accumulate, void* stream);
+ * README.md:36).  Entry points with an `act16` parameter store the conv stack's activation and activation-gradient
+ * tensors (x, y, dy, dx, the GEMM operand A and result C) as bf16 in HBM when it is 1: half the bytes of every
+ * BatchNorm / pooling / staging pass and of the saved-for-backward footprint.  Arithmetic, BatchNorm statistics,
+ * weights, weight gradients and biases stay fp32; a store rounds to nearest even.  Statistics a kernel leaves behind
+ * (bn_partials) are those of the ROUNDED values, i.e. of the tensor BatchNorm then reads.  Layouts, strides (in
+ * elements) and argument meaning are unchanged; activation pointers need 8-byte alignment.  The product entry points
+ * serve act16 = 1 under PE_PROD_BF16 only. */
 
 /* ---- Transformer temporal head (model.py:178-193,229-241,253-255) ---------------------------
  * pe_bgemm: batched 64x64-tiled fp32 MFMA GEMM over `batch` matrices; matrix b of operand X lives

@@ -29,6 +29,9 @@ _u64 = C.c_ulonglong
 _pp = C.POINTER(C.c_void_p)
 _ip = C.POINTER(C.c_int)
 
+# enum pe_products: the product form, first argument of every MFMA-bound entry point
+PE_PROD_NATIVE, PE_PROD_X3, PE_PROD_H2, PE_PROD_BF16, PE_PROD_F16 = range(5)
+
 # name -> (restype, argtypes).  Mirrors include/pitchextractor_hip.h one to one;
 # tests/test_abi.py checks the two against each other and against the .so.
 PROTOTYPES = {
@@ -40,66 +43,46 @@ PROTOTYPES = {
     "pe_mel_num_frames": (_i, [_p, _i]),
     "pe_mel_forward": (_i, [_p, _p, _i, _i, _l, _p, _l, _l, _l, _i, _i, _f, _f, _f, _f, _p]),
     "pe_mel_forward_ragged": (_i, [_p, _p, _i, _i, _l, _p, _p, _p, _l, _l, _l, _i, _i, _f, _f, _f, _f, _p]),
-    "pe_gemm_nt": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p]),
-    "pe_gemm_nt_bf16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p]),
-    "pe_gemm_nt_x3": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p]),
-    "pe_gemm_nt_h2": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
+    "pe_gemm_nt": (_i, [_i, _i, _p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
     "pe_absmax": (_i, [_p, _l, _i, _l, _p, _p]),
     "pe_absmax_segments": (_i, [_p, _p, _p, _i, _p, _p]),
     "pe_gemm_tn_workspace_bytes": (_z, [_i, _i, _i]),
-    "pe_gemm_tn": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_gemm_tn_x3": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_gemm_tn_bf16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_gemm_tn_h2": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
+    "pe_gemm_tn": (_i, [_i, _i, _p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
     "pe_transpose2d": (_i, [_p, _p, _i, _i, _p]),
     "pe_conv3x3_repack": (_i, [_p, _p, _p, _i, _i, _p]),
-    "pe_conv3x3_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "pe_conv3x3_fwd_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "pe_conv3x3_fwd_x3": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "pe_conv3x3_fwd_h2": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "pe_conv3x3_fwd": (_i, [_i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "pe_wfrag_bytes": (_z, [_i, _i, _i]),
-    "pe_wfrag_pack_h2": (_i, [_p, _l, _i, _i, _p, _p, _p]),
-    "pe_conv3x3_fwd_wf_h2": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
-    "pe_conv3x3_wgrad_h2": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
-    "pe_lstm_whh_grad_h2": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
-    "pe_wfrag_pack": (_i, [_p, _l, _i, _i, _i, _p, _p]),
+    "pe_wfrag_pack": (_i, [_i, _p, _l, _i, _i, _p, _p, _p]),
     "pe_conv3x3_wf_supported": (_i, [_i, _i, _i]),
-    "pe_conv3x3_fwd_wf_x3": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "pe_conv3x3_fwd_wf_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "pe_conv3x3_fwd_wf": (_i, [_i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "pe_conv3x3_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "pe_conv3x3_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_conv3x3_wgrad_x3": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_conv3x3_wgrad_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "pe_conv3x3_wgrad": (_i, [_i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
     "pe_conv3x3_c1_stat_parts": (_i, [_i, _i, _i]),
-    "pe_conv3x3_c1_fwd": (_i, [_p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p]),
-    "pe_conv3x3_c1_wgrad": (_i, [_p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _z, _p]),
+    "pe_conv3x3_c1_fwd": (_i, [_i, _p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p]),
+    "pe_conv3x3_c1_wgrad": (_i, [_i, _p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _z, _p]),
     "pe_bn_workspace_bytes": (_z, [_i]),
-    "pe_bn_train_stats": (_i, [_p, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "pe_bn_train_stats": (_i, [_i, _p, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "pe_conv3x3_wf_stat_parts": (_i, [_i, _i, _i]),
     "pe_bn_finalize_stats": (_i, [_p, _i, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "pe_bn_eval_affine": (_i, [_p, _p, _p, _p, _f, _i, _p, _p, _p]),
-    "pe_bn_act_pool_fwd": (_i, [_p, _p, _p, _f, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
-    "pe_bn_act_pool_bwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _z, _p, _p]),
-    "pe_maxpool_fwd": (_i, [_p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
-    "pe_maxpool_bwd_add": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
-    "pe_dropout_fwd": (_i, [_p, _l, _p, _l, _p, _p, _l, _i, _f, _u64, _u64, _p]),
-    "pe_nhwc_to_seq": (_i, [_p, _l, _i, _p, _l, _i, _p]),
-    "pe_seq_to_nhwc": (_i, [_p, _p, _l, _i, _l, _i, _i, _p]),
-    "pe_copy2d": (_i, [_p, _l, _p, _l, _l, _i, _i, _p]),
+    "pe_bn_act_pool_fwd": (_i, [_i, _p, _p, _p, _f, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
+    "pe_bn_act_pool_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _z, _p, _p]),
+    "pe_maxpool_fwd": (_i, [_i, _p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
+    "pe_maxpool_bwd_add": (_i, [_i, _p, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
+    "pe_dropout_fwd": (_i, [_i, _p, _l, _p, _l, _p, _p, _l, _i, _f, _u64, _u64, _p]),
+    "pe_nhwc_to_seq": (_i, [_i, _p, _l, _i, _p, _l, _i, _p]),
+    "pe_seq_to_nhwc": (_i, [_i, _p, _p, _l, _i, _l, _i, _i, _p]),
+    "pe_copy2d": (_i, [_i, _p, _l, _p, _l, _l, _i, _i, _p]),
     "pe_lstm_fwd": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _p]),
     "pe_lstm_bwd": (_i, [_i, _pp, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _p]),
     "pe_lstm_persistent_sync_bytes": (_z, [_i, _i]),
     "pe_lstm_persistent_supported": (_i, [_i, _i, _i]),
-    "pe_lstm_fwd_persistent_x3": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _p, _p]),
+    "pe_lstm_fwd_persistent": (_i, [_i, _i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _p, _p]),
     "pe_lstm_bwd_persistent_dbias_rows": (_i, [_i, _i, _i, _i, _l]),
     "pe_lstm_configure_stamps": (_i, [_i]),
-    "pe_lstm_bwd_persistent_x3": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _pp, _pp, _p, _p]),
-    "pe_lstm_fwd_persistent_bf16": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _p, _p]),
-    "pe_lstm_bwd_persistent_bf16": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _pp, _pp, _p, _p]),
+    "pe_lstm_bwd_persistent": (_i, [_i, _i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _pp, _pp, _p, _p]),
     "pe_lstm_whh_grad_workspace_bytes": (_z, [_i, _i, _i]),
-    "pe_lstm_whh_grad": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_lstm_whh_grad_x3": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_lstm_whh_grad_bf16": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _z, _p]),
+    "pe_lstm_whh_grad": (_i, [_i, _p, _p, _l, _p, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
     "pe_colsum_workspace_bytes": (_z, [_i]),
     "pe_colsum": (_i, [_p, _l, _i, _l, _p, _p, _p, _z, _p]),
     "pe_head_fwd": (_i, [_p, _l, _p, _p, _i, _p, _l, _i, _p]),
@@ -108,10 +91,8 @@ PROTOTYPES = {
     "pe_f0_sil_loss": (_i, [_p, _p, _p, _p, _f, _l, _f, _p, _p, _p, _p]),
     "pe_bgemm": (_i, [_i, _p, _l, _l, _l, _p, _l, _l, _l, _p, _l, _l, _l, _i, _i, _i, _i, _i, _f, _i, _p]),
     "pe_attn_supported": (_i, [_i, _i]),
-    "pe_attn_fwd": (_i, [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _u64, _p]),
-    "pe_attn_bwd": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
-    "pe_attn_fwd_bf16": (_i, [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _u64, _p]),
-    "pe_attn_bwd_bf16": (_i, [_p, _l, _p, _p, _l, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
+    "pe_attn_fwd": (_i, [_i, _p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _u64, _p]),
+    "pe_attn_bwd": (_i, [_i, _p, _l, _p, _p, _l, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
     "pe_softmax_fwd": (_i, [_p, _l, _i, _f, _p]),
     "pe_softmax_bwd": (_i, [_p, _p, _l, _i, _f, _p]),
     "pe_layernorm_fwd": (_i, [_p, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p, _l, _i, _p]),
@@ -139,31 +120,6 @@ PROTOTYPES = {
     "pe_pitch_shift_resample": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _l, _p, _p]),
     "pe_f0_bins_ce_workspace_bytes": (_z, [_l]),
     "pe_f0_bins_ce_loss": (_i, [_p, _l, _i, _p, _p, _p, _f, _l, _f, _p, _p, _l, _p, _p, _z, _p]),
-    "pe_gemm_nt_f16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p]),
-    "pe_gemm_tn_f16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_conv3x3_fwd_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "pe_conv3x3_fwd_wf_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "pe_conv3x3_wgrad_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_lstm_fwd_persistent_f16": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _p, _p]),
-    "pe_lstm_bwd_persistent_f16": (_i, [_i, _pp, _pp, _pp, _pp, _ip, _l, _i, _i, _i, _pp, _pp, _p, _p]),
-    "pe_lstm_whh_grad_f16": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_wfrag_pack_f16": (_i, [_p, _l, _i, _i, _p, _p]),
-    "pe_conv3x3_c1_fwd_a16": (_i, [_p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p]),
-    "pe_conv3x3_c1_wgrad_a16": (_i, [_p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _z, _p]),
-    "pe_conv3x3_fwd_bf16_a16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "pe_conv3x3_fwd_wf_bf16_a16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-    "pe_conv3x3_wgrad_bf16_a16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_gemm_nt_bf16_a16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p]),
-    "pe_gemm_tn_bf16_a16": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _z, _p]),
-    "pe_bn_train_stats_a16": (_i, [_p, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "pe_bn_act_pool_fwd_a16": (_i, [_p, _p, _p, _f, _p, _l, _i, _i, _i, _l, _i, _p]),
-    "pe_bn_act_pool_bwd_a16": (_i, [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _z, _p]),
-    "pe_maxpool_fwd_a16": (_i, [_p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
-    "pe_maxpool_bwd_add_a16": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p]),
-    "pe_dropout_fwd_a16": (_i, [_p, _l, _p, _l, _p, _p, _l, _i, _f, _u64, _u64, _p]),
-    "pe_nhwc_to_seq_a16": (_i, [_p, _l, _i, _p, _l, _i, _p]),
-    "pe_seq_to_nhwc_a16": (_i, [_p, _p, _l, _i, _l, _i, _i, _p]),
-    "pe_copy2d_a16": (_i, [_p, _l, _p, _l, _l, _i, _i, _p]),
     "pe_nonfinite_flag": (_i, [_p, _l, _p, _p]),
     "pe_adamw_step": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _d, _d, _f, _p, _p]),
 }

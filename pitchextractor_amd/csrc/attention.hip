@@ -446,18 +446,19 @@ static int attn_fwd_impl(const float* qkv, long ld_qkv, float* o, long ld_o, flo
   return PE_OK;
 }
 
-extern "C" int pe_attn_fwd(const float* qkv, long ld_qkv, float* o, long ld_o, float* lse, const unsigned char* mask_in,
-                           unsigned char* mask_out, int B, int T, int H, int dh, float scale, float p_drop,
-                           unsigned long long seed, unsigned long long offset, void* stream) {
-  return attn_fwd_impl<false>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed, offset,
-                              stream);
-}
-extern "C" int pe_attn_fwd_bf16(const float* qkv, long ld_qkv, float* o, long ld_o, float* lse,
-                                const unsigned char* mask_in, unsigned char* mask_out, int B, int T, int H, int dh,
-                                float scale, float p_drop, unsigned long long seed, unsigned long long offset,
-                                void* stream) {
-  return attn_fwd_impl<true>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed, offset,
-                             stream);
+// fp32 products (BF = false) or bf16 operands (BF = true); no other form
+extern "C" int pe_attn_fwd(int products, const float* qkv, long ld_qkv, float* o, long ld_o, float* lse,
+                           const unsigned char* mask_in, unsigned char* mask_out, int B, int T, int H, int dh, float scale,
+                           float p_drop, unsigned long long seed, unsigned long long offset, void* stream) {
+  switch (products) {
+    case PE_PROD_NATIVE:
+      return attn_fwd_impl<false>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed, offset,
+                                  stream);
+    case PE_PROD_BF16:
+      return attn_fwd_impl<true>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed, offset,
+                                 stream);
+    default: return pe_unserved(products);
+  }
 }
 
 template <bool BF>
@@ -487,13 +488,14 @@ static int attn_bwd_impl(const float* qkv, long ld_qkv, const float* o, const fl
   return PE_OK;
 }
 
-extern "C" int pe_attn_bwd(const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o, const float* lse,
-                           const unsigned char* mask, float* dqkv, int B, int T, int H, int dh, float scale,
-                           float p_drop, void* stream) {
-  return attn_bwd_impl<false>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
-}
-extern "C" int pe_attn_bwd_bf16(const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o,
-                                const float* lse, const unsigned char* mask, float* dqkv, int B, int T, int H, int dh,
-                                float scale, float p_drop, void* stream) {
-  return attn_bwd_impl<true>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
+extern "C" int pe_attn_bwd(int products, const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o,
+                           const float* lse, const unsigned char* mask, float* dqkv, int B, int T, int H, int dh,
+                           float scale, float p_drop, void* stream) {
+  switch (products) {
+    case PE_PROD_NATIVE:
+      return attn_bwd_impl<false>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
+    case PE_PROD_BF16:
+      return attn_bwd_impl<true>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
+    default: return pe_unserved(products);
+  }
 }

@@ -19,6 +19,12 @@
 
 static inline hipStream_t pe_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Status of an entry point asked for a product form (pe_products) or activation type that none of its kernels serves:
+// PE_E_UNSUPPORTED, or PE_E_ARG for a `products` value outside the enum.
+static inline int pe_unserved(int products) {
+  return products >= PE_PROD_NATIVE && products <= PE_PROD_F16 ? PE_E_UNSUPPORTED : PE_E_ARG;
+}
+
 static inline int pe_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -920,77 +920,72 @@ static int conv3x3_fwd_impl(const TA* x, const float* w_packed, TA* y, int B, in
   return launch_conv<Tile<128, 128, 2, 2>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
 }
 
-extern "C" int pe_conv3x3_fwd(const float* x, const float* w_packed, float* y, int B, int T, int F, int C, int N,
-                              int accumulate, void* stream) {
-  return conv3x3_fwd_impl<kNative>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
+extern "C" int pe_conv3x3_fwd(int products, int act16, const void* x, const float* w_packed, void* y, int B, int T, int F,
+                              int C, int N, int accumulate, const unsigned* amax_x, const unsigned* amax_w, void* stream) {
+  if (act16) {   // x and y are bf16 tensors in HBM
+    if (products != PE_PROD_BF16) return pe_unserved(products);
+    return conv3x3_fwd_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), w_packed, static_cast<act16_t*>(y), B, T, F,
+                                            C, N, accumulate, stream);
+  }
+  const float* xf = static_cast<const float*>(x);
+  float* yf = static_cast<float*>(y);
+  switch (products) {
+    case PE_PROD_NATIVE: return conv3x3_fwd_impl<kNative>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
+    case PE_PROD_X3: return conv3x3_fwd_impl<kSplit>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
+    case PE_PROD_H2:
+      return conv3x3_fwd_impl<kSplit2>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream, amax_x, amax_w);
+    case PE_PROD_BF16: return conv3x3_fwd_impl<kBf16>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
+    case PE_PROD_F16:
+      return conv3x3_fwd_impl<kBf16, float, _Float16>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
+    default: return pe_unserved(products);
+  }
 }
 
-extern "C" int pe_conv3x3_fwd_bf16(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
-                                   int N, int accumulate, void* stream) {
-  return conv3x3_fwd_impl<kBf16>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
+// ---- weights pre-packed as MFMA fragments (x3: three bf16 terms; h2: two scaled fp16 terms; bf16 / fp16: one rounded
+// term).  Native fp32 products have no fragment form.
+static int wfrag_terms(int products) {
+  switch (products) {
+    case PE_PROD_X3: return 3;
+    case PE_PROD_H2: return 2;
+    case PE_PROD_BF16: case PE_PROD_F16: return 1;
+    default: return 0;
+  }
 }
 
-extern "C" int pe_conv3x3_fwd_f16(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
-                                  int N, int accumulate, void* stream) {
-  return conv3x3_fwd_impl<kBf16, float, _Float16>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
+extern "C" size_t pe_wfrag_bytes(int products, int N, int K) {
+  const int terms = wfrag_terms(products);
+  if (N <= 0 || K <= 0 || (K & 15) || terms == 0) return 0;
+  return pe_wfrag_bytes_host(N, K, terms);
 }
 
-extern "C" int pe_conv3x3_fwd_x3(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
-                                 int N, int accumulate, void* stream) {
-  return conv3x3_fwd_impl<kSplit>(x, w_packed, y, B, T, F, C, N, accumulate, stream);
-}
-
-extern "C" int pe_conv3x3_fwd_h2(const float* x, const float* w_packed, float* y, int B, int T, int F, int C,
-                                 int N, int accumulate, const unsigned* amax_x, const unsigned* amax_w, void* stream) {
-  return conv3x3_fwd_impl<kSplit2>(x, w_packed, y, B, T, F, C, N, accumulate, stream, amax_x, amax_w);
-}
-
-// ---- weights pre-packed as MFMA fragments (x3: three bf16 terms; bf16 / fp16: one rounded term)
-extern "C" size_t pe_wfrag_bytes(int N, int K, int terms) {
-  if (N <= 0 || K <= 0 || (K & 15) || terms < 1 || terms > 3) return 0;
-  return (size_t)((N + 31) / 32) * (K / 16) * terms * 1024;
-}
-
-template <class TH = __bf16>   // TH: the type of the one rounded term (terms = 1)
-static int wfrag_pack_impl(const float* w, long ld, int N, int K, int terms, void* out, void* stream) {
-  if (!w || !out || N <= 0 || K <= 0 || ld < K) return PE_E_ARG;
-  if ((K & 15) || (ld & 3) || (terms != 1 && terms != 3)) return PE_E_UNSUPPORTED;
-  const long threads = (long)((N + 31) / 32) * (K / 16) * 64;
-  if (terms == 3)
-    hipLaunchKernelGGL(wfrag_pack_kernel<3>, dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld, N, K,
-                       reinterpret_cast<uint4*>(out));
-  else
-    hipLaunchKernelGGL((wfrag_pack_kernel<1, TH>), dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld,
-                       N, K, reinterpret_cast<uint4*>(out));
-  PE_LAUNCH_CHECK();
-  return PE_OK;
-}
-
-extern "C" int pe_wfrag_pack(const float* w, long ld, int N, int K, int terms, void* out, void* stream) {
-  return wfrag_pack_impl(w, ld, N, K, terms, out, stream);
-}
-
-// one RNE-rounded fp16 term per weight, same fragment order as pe_wfrag_pack(..., terms = 1, ...)
-extern "C" int pe_wfrag_pack_f16(const float* w, long ld, int N, int K, void* out, void* stream) {
-  return wfrag_pack_impl<_Float16>(w, ld, N, K, 1, out, stream);
-}
-
-// two scaled fp16 terms per weight ("h2"): the scale comes from *amax (pe_absmax of w)
-extern "C" int pe_wfrag_pack_h2(const float* w, long ld, int N, int K, const unsigned* amax, void* out, void* stream) {
-  if (!w || !out || !amax || N <= 0 || K <= 0 || ld < K) return PE_E_ARG;
+// TERMS = 2: the scale comes from *amax (pe_absmax of w); TH: the type of the one rounded term (TERMS = 1)
+template <int TERMS, class TH = __bf16>
+static int wfrag_pack_impl(const float* w, long ld, int N, int K, const unsigned* amax, void* out, void* stream) {
+  if (!w || !out || N <= 0 || K <= 0 || ld < K || (TERMS == 2 && !amax)) return PE_E_ARG;
   if ((K & 15) || (ld & 3)) return PE_E_UNSUPPORTED;
   const long threads = (long)((N + 31) / 32) * (K / 16) * 64;
-  hipLaunchKernelGGL(wfrag_pack_kernel<2>, dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld, N, K,
-                     reinterpret_cast<uint4*>(out), amax);
+  hipLaunchKernelGGL((wfrag_pack_kernel<TERMS, TH>), dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld,
+                     N, K, reinterpret_cast<uint4*>(out), TERMS == 2 ? amax : nullptr);
   PE_LAUNCH_CHECK();
   return PE_OK;
+}
+
+extern "C" int pe_wfrag_pack(int products, const float* w, long ld, int N, int K, const unsigned* amax, void* wfrag,
+                             void* stream) {
+  switch (products) {
+    case PE_PROD_X3: return wfrag_pack_impl<3>(w, ld, N, K, amax, wfrag, stream);
+    case PE_PROD_H2: return wfrag_pack_impl<2>(w, ld, N, K, amax, wfrag, stream);
+    case PE_PROD_BF16: return wfrag_pack_impl<1>(w, ld, N, K, amax, wfrag, stream);
+    case PE_PROD_F16: return wfrag_pack_impl<1, _Float16>(w, ld, N, K, amax, wfrag, stream);
+    default: return pe_unserved(products);
+  }
 }
 
 extern "C" int pe_conv3x3_wf_supported(int F, int C, int N) {
   return (C % 32) == 0 && conv_halo_passes(F, N) != 0 ? 1 : 0;
 }
 
-// number of per-tile BatchNorm partials pe_conv3x3_fwd_wf_* writes: bn_partials is [parts][2][N] doubles
+// number of per-tile BatchNorm partials pe_conv3x3_fwd_wf writes: bn_partials is [parts][2][N] doubles
 extern "C" int pe_conv3x3_wf_stat_parts(int B, int T, int F) { return pe_cdiv((long)B * T * F, 128); }
 
 template <int MODE, class TA = float, class TH = __bf16>
@@ -1018,25 +1013,25 @@ static int conv3x3_fwd_wf_impl(const TA* x, const void* wfrag, TA* y, int B, int
   return PE_E_UNSUPPORTED;
 }
 
-extern "C" int pe_conv3x3_fwd_wf_x3(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                                    int accumulate, double* bn_partials, void* stream) {
-  return conv3x3_fwd_wf_impl<kSplit>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream);
-}
-
-extern "C" int pe_conv3x3_fwd_wf_h2(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                                    int accumulate, double* bn_partials, const unsigned* amax_x,
-                                    const unsigned* amax_w, void* stream) {
-  return conv3x3_fwd_wf_impl<kSplit2>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream, amax_x, amax_w);
-}
-
-extern "C" int pe_conv3x3_fwd_wf_bf16(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                                      int accumulate, double* bn_partials, void* stream) {
-  return conv3x3_fwd_wf_impl<kBf16>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream);
-}
-
-extern "C" int pe_conv3x3_fwd_wf_f16(const float* x, const void* wfrag, float* y, int B, int T, int F, int C, int N,
-                                     int accumulate, double* bn_partials, void* stream) {
-  return conv3x3_fwd_wf_impl<kBf16, float, _Float16>(x, wfrag, y, B, T, F, C, N, accumulate, bn_partials, stream);
+extern "C" int pe_conv3x3_fwd_wf(int products, int act16, const void* x, const void* wfrag, void* y, int B, int T, int F,
+                                 int C, int N, int accumulate, double* bn_partials, const unsigned* amax_x,
+                                 const unsigned* amax_w, void* stream) {
+  if (act16) {
+    if (products != PE_PROD_BF16) return pe_unserved(products);
+    return conv3x3_fwd_wf_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), wfrag, static_cast<act16_t*>(y), B, T, F,
+                                               C, N, accumulate, bn_partials, stream);
+  }
+  const float* xf = static_cast<const float*>(x);
+  float* yf = static_cast<float*>(y);
+  switch (products) {
+    case PE_PROD_X3: return conv3x3_fwd_wf_impl<kSplit>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream);
+    case PE_PROD_H2:
+      return conv3x3_fwd_wf_impl<kSplit2>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream, amax_x, amax_w);
+    case PE_PROD_BF16: return conv3x3_fwd_wf_impl<kBf16>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream);
+    case PE_PROD_F16:
+      return conv3x3_fwd_wf_impl<kBf16, float, _Float16>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream);
+    default: return pe_unserved(products);
+  }
 }
 
 extern "C" size_t pe_conv3x3_wgrad_workspace_bytes(int B, int T, int F, int Cin, int Cout) {
@@ -1090,51 +1085,31 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
   return PE_E_UNSUPPORTED;
 }
 
-extern "C" int pe_conv3x3_wgrad(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                                int Cout, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_wgrad_impl<kNative>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_conv3x3_wgrad_bf16(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                                     int Cout, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_wgrad_impl<kBf16>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_conv3x3_wgrad_f16(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                                    int Cout, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_wgrad_impl<kBf16, float, _Float16>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes,
-                                                     stream);
-}
-
-// ---- mixed precision with bf16 ACTIVATION STORAGE (x, y, dy are bf16 tensors in HBM; weights / gradients fp32)
-extern "C" int pe_conv3x3_fwd_bf16_a16(const void* x, const float* w_packed, void* y, int B, int T, int F, int C, int N,
-                                       int accumulate, void* stream) {
-  return conv3x3_fwd_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), w_packed, static_cast<act16_t*>(y), B, T, F,
-                                          C, N, accumulate, stream);
-}
-
-extern "C" int pe_conv3x3_fwd_wf_bf16_a16(const void* x, const void* wfrag, void* y, int B, int T, int F, int C, int N,
-                                          int accumulate, double* bn_partials, void* stream) {
-  return conv3x3_fwd_wf_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), wfrag, static_cast<act16_t*>(y), B, T, F,
-                                             C, N, accumulate, bn_partials, stream);
-}
-
-extern "C" int pe_conv3x3_wgrad_bf16_a16(const void* x, const void* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                                         int Cout, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_wgrad_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), dw_oihw,
-                                            B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_conv3x3_wgrad_x3(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                                   int Cout, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_wgrad_impl<kSplit>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_conv3x3_wgrad_h2(const float* x, const float* dy, float* dw_oihw, int B, int T, int F, int Cin,
-                                   int Cout, float* workspace, size_t workspace_bytes, const unsigned* amax_x,
-                                   const unsigned* amax_dy, void* stream) {
-  return conv3x3_wgrad_impl<kSplit2>(x, dy, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream, amax_x,
-                                     amax_dy);
+extern "C" int pe_conv3x3_wgrad(int products, int act16, const void* x, const void* dy, float* dw_oihw, int B, int T, int F,
+                                int Cin, int Cout, float* workspace, size_t workspace_bytes, const unsigned* amax_x,
+                                const unsigned* amax_dy, void* stream) {
+  if (act16) {   // x and dy are bf16 tensors in HBM
+    if (products != PE_PROD_BF16) return pe_unserved(products);
+    return conv3x3_wgrad_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), dw_oihw,
+                                              B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
+  }
+  const float* xf = static_cast<const float*>(x);
+  const float* dyf = static_cast<const float*>(dy);
+  switch (products) {
+    case PE_PROD_NATIVE:
+      return conv3x3_wgrad_impl<kNative>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
+    case PE_PROD_X3:
+      return conv3x3_wgrad_impl<kSplit>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
+    case PE_PROD_H2:
+      return conv3x3_wgrad_impl<kSplit2>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream, amax_x,
+                                         amax_dy);
+    case PE_PROD_BF16:
+      return conv3x3_wgrad_impl<kBf16>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
+    case PE_PROD_F16:
+      return conv3x3_wgrad_impl<kBf16, float, _Float16>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes,
+                                                        stream);
+    default: return pe_unserved(products);
+  }
 }
 
 static int c1_grid(int B, int T, int F) {
@@ -1161,14 +1136,11 @@ static int conv3x3_c1_fwd_impl(const float* x, long sb, long st, long sf, const 
   return PE_OK;
 }
 
-extern "C" int pe_conv3x3_c1_fwd(const float* x, long sb, long st, long sf, const float* w_oihw, float* y, int B,
+extern "C" int pe_conv3x3_c1_fwd(int act16, const float* x, long sb, long st, long sf, const float* w_oihw, void* y, int B,
                                  int T, int F, double* bn_partials, void* stream) {
-  return conv3x3_c1_fwd_impl<float>(x, sb, st, sf, w_oihw, y, B, T, F, bn_partials, stream);
-}
-
-extern "C" int pe_conv3x3_c1_fwd_a16(const float* x, long sb, long st, long sf, const float* w_oihw, void* y, int B,
-                                     int T, int F, double* bn_partials, void* stream) {
-  return conv3x3_c1_fwd_impl<act16_t>(x, sb, st, sf, w_oihw, static_cast<act16_t*>(y), B, T, F, bn_partials, stream);
+  if (act16)
+    return conv3x3_c1_fwd_impl<act16_t>(x, sb, st, sf, w_oihw, static_cast<act16_t*>(y), B, T, F, bn_partials, stream);
+  return conv3x3_c1_fwd_impl<float>(x, sb, st, sf, w_oihw, static_cast<float*>(y), B, T, F, bn_partials, stream);
 }
 
 template <class TA>
@@ -1186,13 +1158,11 @@ static int conv3x3_c1_wgrad_impl(const float* x, long sb, long st, long sf, cons
   return PE_OK;
 }
 
-extern "C" int pe_conv3x3_c1_wgrad(const float* x, long sb, long st, long sf, const float* dy, float* dw_oihw,
+extern "C" int pe_conv3x3_c1_wgrad(int act16, const float* x, long sb, long st, long sf, const void* dy, float* dw_oihw,
                                    int B, int T, int F, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_c1_wgrad_impl<float>(x, sb, st, sf, dy, dw_oihw, B, T, F, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_conv3x3_c1_wgrad_a16(const float* x, long sb, long st, long sf, const void* dy, float* dw_oihw,
-                                       int B, int T, int F, float* workspace, size_t workspace_bytes, void* stream) {
-  return conv3x3_c1_wgrad_impl<act16_t>(x, sb, st, sf, static_cast<const act16_t*>(dy), dw_oihw, B, T, F, workspace,
-                                        workspace_bytes, stream);
+  if (act16)
+    return conv3x3_c1_wgrad_impl<act16_t>(x, sb, st, sf, static_cast<const act16_t*>(dy), dw_oihw, B, T, F, workspace,
+                                          workspace_bytes, stream);
+  return conv3x3_c1_wgrad_impl<float>(x, sb, st, sf, static_cast<const float*>(dy), dw_oihw, B, T, F, workspace,
+                                      workspace_bytes, stream);
 }

@@ -648,25 +648,20 @@ static int bn_train_stats_impl(const TA* x, long n_pix, int C, const float* gamm
   return PE_OK;
 }
 
-extern "C" int pe_bn_train_stats(const float* x, long n_pix, int C, const float* gamma, const float* beta, float eps,
-                                 float momentum, float* running_mean, float* running_var, float* mean,
+extern "C" int pe_bn_train_stats(int act16, const void* x, long n_pix, int C, const float* gamma, const float* beta,
+                                 float eps, float momentum, float* running_mean, float* running_var, float* mean,
                                  float* invstd, float* scale, float* shift, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-  return bn_train_stats_impl<float>(x, n_pix, C, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
-                                    scale, shift, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_bn_train_stats_a16(const void* x, long n_pix, int C, const float* gamma, const float* beta, float eps,
-                                     float momentum, float* running_mean, float* running_var, float* mean,
-                                     float* invstd, float* scale, float* shift, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-  return bn_train_stats_impl<act16_t>(static_cast<const act16_t*>(x), n_pix, C, gamma, beta, eps, momentum,
-                                      running_mean, running_var, mean, invstd, scale, shift, workspace,
-                                      workspace_bytes, stream);
+  if (act16)
+    return bn_train_stats_impl<act16_t>(static_cast<const act16_t*>(x), n_pix, C, gamma, beta, eps, momentum,
+                                        running_mean, running_var, mean, invstd, scale, shift, workspace,
+                                        workspace_bytes, stream);
+  return bn_train_stats_impl<float>(static_cast<const float*>(x), n_pix, C, gamma, beta, eps, momentum, running_mean,
+                                    running_var, mean, invstd, scale, shift, workspace, workspace_bytes, stream);
 }
 
 // BatchNorm training statistics from partials a producer kernel left behind ([nparts][2][C] doubles: column sums
-// and sums of squares, e.g. pe_conv3x3_fwd_wf_*'s bn_partials): the finalize half of pe_bn_train_stats.
+// and sums of squares, e.g. pe_conv3x3_fwd_wf's bn_partials): the finalize half of pe_bn_train_stats.
 extern "C" int pe_bn_finalize_stats(const double* partials, int nparts, long n_pix, int C, const float* gamma,
                                     const float* beta, float eps, float momentum, float* running_mean,
                                     float* running_var, float* mean, float* invstd, float* scale, float* shift,
@@ -715,16 +710,14 @@ static int bn_act_pool_fwd_impl(const TA* x, const float* scale, const float* sh
   return PE_OK;
 }
 
-extern "C" int pe_bn_act_pool_fwd(const float* x, const float* scale, const float* shift, float slope, float* y,
+extern "C" int pe_bn_act_pool_fwd(int act16, const void* x, const float* scale, const float* shift, float slope, void* y,
                                   long rows, int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out,
                                   void* stream) {
-  return bn_act_pool_fwd_impl<float>(x, scale, shift, slope, y, rows, Fin, C, pool, ldy, coff, amax_out, stream);
-}
-
-extern "C" int pe_bn_act_pool_fwd_a16(const void* x, const float* scale, const float* shift, float slope, void* y,
-                                      long rows, int Fin, int C, int pool, long ldy, int coff, void* stream) {
-  return bn_act_pool_fwd_impl<act16_t>(static_cast<const act16_t*>(x), scale, shift, slope, static_cast<act16_t*>(y),
-                                       rows, Fin, C, pool, ldy, coff, nullptr, stream);
+  if (act16)
+    return bn_act_pool_fwd_impl<act16_t>(static_cast<const act16_t*>(x), scale, shift, slope, static_cast<act16_t*>(y),
+                                         rows, Fin, C, pool, ldy, coff, amax_out, stream);
+  return bn_act_pool_fwd_impl<float>(static_cast<const float*>(x), scale, shift, slope, static_cast<float*>(y), rows, Fin,
+                                     C, pool, ldy, coff, amax_out, stream);
 }
 
 template <class TA>
@@ -777,21 +770,17 @@ static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, c
   return PE_OK;
 }
 
-extern "C" int pe_bn_act_pool_bwd(const float* x, const float* dy, const float* scale, const float* shift,
-                                  const float* mean, const float* invstd, float slope, float* dx, float* dgamma,
+extern "C" int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
+                                  const float* mean, const float* invstd, float slope, void* dx, float* dgamma,
                                   float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
                                   void* workspace, size_t workspace_bytes, unsigned* amax_out, void* stream) {
-  return bn_act_pool_bwd_impl<float>(x, dy, scale, shift, mean, invstd, slope, dx, dgamma, dbeta, rows, Fin, C, pool,
-                                     lddy, coff, workspace, workspace_bytes, amax_out, stream);
-}
-
-extern "C" int pe_bn_act_pool_bwd_a16(const void* x, const void* dy, const float* scale, const float* shift,
-                                      const float* mean, const float* invstd, float slope, void* dx, float* dgamma,
-                                      float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-  return bn_act_pool_bwd_impl<act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), scale, shift,
-                                       mean, invstd, slope, static_cast<act16_t*>(dx), dgamma, dbeta, rows, Fin, C,
-                                       pool, lddy, coff, workspace, workspace_bytes, nullptr, stream);
+  if (act16)
+    return bn_act_pool_bwd_impl<act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), scale, shift,
+                                         mean, invstd, slope, static_cast<act16_t*>(dx), dgamma, dbeta, rows, Fin, C,
+                                         pool, lddy, coff, workspace, workspace_bytes, amax_out, stream);
+  return bn_act_pool_bwd_impl<float>(static_cast<const float*>(x), static_cast<const float*>(dy), scale, shift, mean,
+                                     invstd, slope, static_cast<float*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy,
+                                     coff, workspace, workspace_bytes, amax_out, stream);
 }
 
 template <class TA>
@@ -806,15 +795,13 @@ static int maxpool_fwd_impl(const TA* x, TA* y, long rows, int Fin, int C, int p
   return PE_OK;
 }
 
-extern "C" int pe_maxpool_fwd(const float* x, float* y, long rows, int Fin, int C, int pool, long ldy, int coff,
+extern "C" int pe_maxpool_fwd(int act16, const void* x, void* y, long rows, int Fin, int C, int pool, long ldy, int coff,
                               unsigned char* argmax_out, void* stream) {
-  return maxpool_fwd_impl<float>(x, y, rows, Fin, C, pool, ldy, coff, argmax_out, stream);
-}
-
-extern "C" int pe_maxpool_fwd_a16(const void* x, void* y, long rows, int Fin, int C, int pool, long ldy, int coff,
-                                  unsigned char* argmax_out, void* stream) {
-  return maxpool_fwd_impl<act16_t>(static_cast<const act16_t*>(x), static_cast<act16_t*>(y), rows, Fin, C, pool, ldy,
-                                   coff, argmax_out, stream);
+  if (act16)
+    return maxpool_fwd_impl<act16_t>(static_cast<const act16_t*>(x), static_cast<act16_t*>(y), rows, Fin, C, pool, ldy,
+                                     coff, argmax_out, stream);
+  return maxpool_fwd_impl<float>(static_cast<const float*>(x), static_cast<float*>(y), rows, Fin, C, pool, ldy, coff,
+                                 argmax_out, stream);
 }
 
 template <class TA>
@@ -829,15 +816,14 @@ static int maxpool_bwd_add_impl(const TA* x, const unsigned char* argmax, const 
   return PE_OK;
 }
 
-extern "C" int pe_maxpool_bwd_add(const float* x, const unsigned char* argmax, const float* dy, float* dx, long rows,
-                                  int Fin, int C, int pool, long lddy, int coff, unsigned* amax_out, void* stream) {
-  return maxpool_bwd_add_impl<float>(x, argmax, dy, dx, rows, Fin, C, pool, lddy, coff, amax_out, stream);
-}
-
-extern "C" int pe_maxpool_bwd_add_a16(const void* x, const unsigned char* argmax, const void* dy, void* dx, long rows,
-                                      int Fin, int C, int pool, long lddy, int coff, void* stream) {
-  return maxpool_bwd_add_impl<act16_t>(static_cast<const act16_t*>(x), argmax, static_cast<const act16_t*>(dy),
-                                       static_cast<act16_t*>(dx), rows, Fin, C, pool, lddy, coff, nullptr, stream);
+extern "C" int pe_maxpool_bwd_add(int act16, const void* x, const unsigned char* argmax, const void* dy, void* dx,
+                                  long rows, int Fin, int C, int pool, long lddy, int coff, unsigned* amax_out,
+                                  void* stream) {
+  if (act16)
+    return maxpool_bwd_add_impl<act16_t>(static_cast<const act16_t*>(x), argmax, static_cast<const act16_t*>(dy),
+                                         static_cast<act16_t*>(dx), rows, Fin, C, pool, lddy, coff, amax_out, stream);
+  return maxpool_bwd_add_impl<float>(static_cast<const float*>(x), argmax, static_cast<const float*>(dy),
+                                     static_cast<float*>(dx), rows, Fin, C, pool, lddy, coff, amax_out, stream);
 }
 
 template <class TA>
@@ -852,51 +838,43 @@ static int dropout_fwd_impl(const TA* x, long ldx, TA* y, long ldy, const unsign
   return PE_OK;
 }
 
-extern "C" int pe_dropout_fwd(const float* x, long ldx, float* y, long ldy, const unsigned char* mask_in,
+extern "C" int pe_dropout_fwd(int act16, const void* x, long ldx, void* y, long ldy, const unsigned char* mask_in,
                               unsigned char* mask_out, long rows, int cols, float p, unsigned long long seed,
                               unsigned long long offset, void* stream) {
-  return dropout_fwd_impl<float>(x, ldx, y, ldy, mask_in, mask_out, rows, cols, p, seed, offset, stream);
+  if (act16)
+    return dropout_fwd_impl<act16_t>(static_cast<const act16_t*>(x), ldx, static_cast<act16_t*>(y), ldy, mask_in,
+                                     mask_out, rows, cols, p, seed, offset, stream);
+  return dropout_fwd_impl<float>(static_cast<const float*>(x), ldx, static_cast<float*>(y), ldy, mask_in, mask_out, rows,
+                                 cols, p, seed, offset, stream);
 }
 
-extern "C" int pe_dropout_fwd_a16(const void* x, long ldx, void* y, long ldy, const unsigned char* mask_in,
-                                  unsigned char* mask_out, long rows, int cols, float p, unsigned long long seed,
-                                  unsigned long long offset, void* stream) {
-  return dropout_fwd_impl<act16_t>(static_cast<const act16_t*>(x), ldx, static_cast<act16_t*>(y), ldy, mask_in,
-                                   mask_out, rows, cols, p, seed, offset, stream);
-}
-
-extern "C" int pe_nhwc_to_seq(const float* x, long ldx, int coff, float* seq, long rows, int C, void* stream) {
+template <class TA>
+static int nhwc_to_seq_impl(const TA* x, long ldx, int coff, float* seq, long rows, int C, void* stream) {
   if (!x || !seq || rows <= 0 || C <= 0) return PE_E_ARG;
-  hipLaunchKernelGGL(nhwc_to_seq_kernel<float>, dim3(ew_grid(rows * C)), dim3(256), 0, pe_stream(stream), x, ldx, coff,
-                     seq, rows, C);
+  hipLaunchKernelGGL(nhwc_to_seq_kernel<TA>, dim3(ew_grid(rows * C)), dim3(256), 0, pe_stream(stream), x, ldx, coff, seq,
+                     rows, C);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
 
-extern "C" int pe_nhwc_to_seq_a16(const void* x, long ldx, int coff, float* seq, long rows, int C, void* stream) {
+extern "C" int pe_nhwc_to_seq(int act16, const void* x, long ldx, int coff, float* seq, long rows, int C, void* stream) {
+  if (act16) return nhwc_to_seq_impl(static_cast<const act16_t*>(x), ldx, coff, seq, rows, C, stream);
+  return nhwc_to_seq_impl(static_cast<const float*>(x), ldx, coff, seq, rows, C, stream);
+}
+
+template <class TA>
+static int seq_to_nhwc_impl(const float* seq, TA* x, long ldx, int coff, long rows, int C, int accumulate, void* stream) {
   if (!x || !seq || rows <= 0 || C <= 0) return PE_E_ARG;
-  hipLaunchKernelGGL(nhwc_to_seq_kernel<act16_t>, dim3(ew_grid(rows * C)), dim3(256), 0, pe_stream(stream),
-                     static_cast<const act16_t*>(x), ldx, coff, seq, rows, C);
+  hipLaunchKernelGGL(seq_to_nhwc_kernel<TA>, dim3(ew_grid(rows * C)), dim3(256), 0, pe_stream(stream), seq, x, ldx, coff,
+                     rows, C, accumulate);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
 
-extern "C" int pe_seq_to_nhwc(const float* seq, float* x, long ldx, int coff, long rows, int C, int accumulate,
+extern "C" int pe_seq_to_nhwc(int act16, const float* seq, void* x, long ldx, int coff, long rows, int C, int accumulate,
                               void* stream) {
-  if (!x || !seq || rows <= 0 || C <= 0) return PE_E_ARG;
-  hipLaunchKernelGGL(seq_to_nhwc_kernel<float>, dim3(ew_grid(rows * C)), dim3(256), 0, pe_stream(stream), seq, x, ldx,
-                     coff, rows, C, accumulate);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
-}
-
-extern "C" int pe_seq_to_nhwc_a16(const float* seq, void* x, long ldx, int coff, long rows, int C, int accumulate,
-                                  void* stream) {
-  if (!x || !seq || rows <= 0 || C <= 0) return PE_E_ARG;
-  hipLaunchKernelGGL(seq_to_nhwc_kernel<act16_t>, dim3(ew_grid(rows * C)), dim3(256), 0, pe_stream(stream), seq,
-                     static_cast<act16_t*>(x), ldx, coff, rows, C, accumulate);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  if (act16) return seq_to_nhwc_impl(seq, static_cast<act16_t*>(x), ldx, coff, rows, C, accumulate, stream);
+  return seq_to_nhwc_impl(seq, static_cast<float*>(x), ldx, coff, rows, C, accumulate, stream);
 }
 
 template <class TA>
@@ -909,15 +887,13 @@ static int copy2d_impl(const TA* src, long lds, TA* dst, long ldd, long rows, in
   return PE_OK;
 }
 
-extern "C" int pe_copy2d(const float* src, long lds, float* dst, long ldd, long rows, int cols, int accumulate,
+extern "C" int pe_copy2d(int act16, const void* src, long lds, void* dst, long ldd, long rows, int cols, int accumulate,
                          void* stream) {
-  return copy2d_impl<float>(src, lds, dst, ldd, rows, cols, accumulate, stream);
-}
-
-extern "C" int pe_copy2d_a16(const void* src, long lds, void* dst, long ldd, long rows, int cols, int accumulate,
-                             void* stream) {
-  return copy2d_impl<act16_t>(static_cast<const act16_t*>(src), lds, static_cast<act16_t*>(dst), ldd, rows, cols,
-                              accumulate, stream);
+  if (act16)
+    return copy2d_impl<act16_t>(static_cast<const act16_t*>(src), lds, static_cast<act16_t*>(dst), ldd, rows, cols,
+                                accumulate, stream);
+  return copy2d_impl<float>(static_cast<const float*>(src), lds, static_cast<float*>(dst), ldd, rows, cols, accumulate,
+                            stream);
 }
 
 extern "C" int pe_absmax(const float* x, long rows, int cols, long ld, unsigned* out, void* stream) {

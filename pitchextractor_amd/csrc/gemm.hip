@@ -234,43 +234,32 @@ static int gemm_nt_impl(const TA* A, long lda, const float* B, long ldb, TA* C, 
   return launch_nt<Tile<128, 128, 2, 2>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
 }
 
-extern "C" int pe_gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                          int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
-  return gemm_nt_impl<kNative>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
-}
-
-extern "C" int pe_gemm_nt_bf16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                               int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
-  return gemm_nt_impl<kBf16>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
-}
-
-extern "C" int pe_gemm_nt_f16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                              int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
-  return gemm_nt_impl<kBf16, float, _Float16>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
-}
-
-// mixed precision with bf16 ACTIVATION STORAGE: A and C are bf16 tensors in HBM (weights and biases stay fp32)
-extern "C" int pe_gemm_nt_bf16_a16(const void* A, long lda, const float* B, long ldb, void* C, long ldc, int M, int N,
-                                   int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
-  return gemm_nt_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, B, ldb, static_cast<act16_t*>(C), ldc, M, N,
-                                      K, bias0, bias1, accumulate, stream);
-}
-
-extern "C" int pe_gemm_nt_x3(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                             int K, const float* bias0, const float* bias1, int accumulate, void* stream) {
-  return gemm_nt_impl<kSplit>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream);
-}
-
-extern "C" int pe_gemm_nt_h2(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                             int K, const float* bias0, const float* bias1, int accumulate, const unsigned* amax_a,
-                             const unsigned* amax_b, void* stream) {
-  return gemm_nt_impl<kSplit2>(A, lda, B, ldb, C, ldc, M, N, K, bias0, bias1, accumulate, stream, amax_a, amax_b);
+extern "C" int pe_gemm_nt(int products, int act16, const void* A, long lda, const float* B, long ldb, void* C, long ldc,
+                          int M, int N, int K, const float* bias0, const float* bias1, int accumulate,
+                          const unsigned* amax_a, const unsigned* amax_b, void* stream) {
+  if (act16) {   // bf16 ACTIVATION STORAGE: A and C are bf16 tensors in HBM (weights and biases stay fp32)
+    if (products != PE_PROD_BF16) return pe_unserved(products);
+    return gemm_nt_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, B, ldb, static_cast<act16_t*>(C), ldc, M,
+                                        N, K, bias0, bias1, accumulate, stream);
+  }
+  const float* a = static_cast<const float*>(A);
+  float* c = static_cast<float*>(C);
+  switch (products) {
+    case PE_PROD_NATIVE: return gemm_nt_impl<kNative>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
+    case PE_PROD_X3: return gemm_nt_impl<kSplit>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
+    case PE_PROD_H2:
+      return gemm_nt_impl<kSplit2>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream, amax_a, amax_b);
+    case PE_PROD_BF16: return gemm_nt_impl<kBf16>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
+    case PE_PROD_F16:
+      return gemm_nt_impl<kBf16, float, _Float16>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
+    default: return pe_unserved(products);
+  }
 }
 
 extern "C" size_t pe_gemm_tn_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   size_t need = 0;
-  for (int mode : {kNative, kSplit}) {                   // one size serves every pe_gemm_tn* (bf16 plans like native)
+  for (int mode : {kNative, kSplit}) {                   // one size serves every form of pe_gemm_tn (bf16 plans like native)
     int splits, kps;
     tn_plan(M, N, K, M <= 64 ? 64 : 128, N <= 64 ? 64 : 128, mode, &splits, &kps);
     const size_t b = splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
@@ -304,36 +293,29 @@ static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, 
                                    amax_b);
 }
 
-extern "C" int pe_gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                          int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
-  return gemm_tn_impl<kNative>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_gemm_tn_x3(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                             int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
-  return gemm_tn_impl<kSplit>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_gemm_tn_h2(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                             int K, int accumulate, float* workspace, size_t workspace_bytes, const unsigned* amax_a,
-                             const unsigned* amax_b, void* stream) {
-  return gemm_tn_impl<kSplit2>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream, amax_a,
-                               amax_b);
-}
-
-extern "C" int pe_gemm_tn_bf16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                               int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
-  return gemm_tn_impl<kBf16>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_gemm_tn_f16(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
-                              int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
-  return gemm_tn_impl<kBf16, float, _Float16>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes,
-                                              stream);
-}
-
-extern "C" int pe_gemm_tn_bf16_a16(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N,
-                                   int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream) {
-  return gemm_tn_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, static_cast<const act16_t*>(B), ldb, C, ldc,
-                                      M, N, K, accumulate, workspace, workspace_bytes, stream);
+extern "C" int pe_gemm_tn(int products, int act16, const void* A, long lda, const void* B, long ldb, float* C, long ldc,
+                          int M, int N, int K, int accumulate, float* workspace, size_t workspace_bytes,
+                          const unsigned* amax_a, const unsigned* amax_b, void* stream) {
+  if (act16) {   // A and B are bf16 tensors in HBM
+    if (products != PE_PROD_BF16) return pe_unserved(products);
+    return gemm_tn_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, static_cast<const act16_t*>(B), ldb, C, ldc,
+                                        M, N, K, accumulate, workspace, workspace_bytes, stream);
+  }
+  const float* a = static_cast<const float*>(A);
+  const float* b = static_cast<const float*>(B);
+  switch (products) {
+    case PE_PROD_NATIVE:
+      return gemm_tn_impl<kNative>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
+    case PE_PROD_X3:
+      return gemm_tn_impl<kSplit>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
+    case PE_PROD_H2:
+      return gemm_tn_impl<kSplit2>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream,
+                                   amax_a, amax_b);
+    case PE_PROD_BF16:
+      return gemm_tn_impl<kBf16>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
+    case PE_PROD_F16:
+      return gemm_tn_impl<kBf16, float, _Float16>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace,
+                                                  workspace_bytes, stream);
+    default: return pe_unserved(products);
+  }
 }

@@ -373,31 +373,23 @@ static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* d
   return PE_OK;
 }
 
-extern "C" int pe_lstm_whh_grad(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                                int reverse, float* workspace, size_t workspace_bytes, void* stream) {
-  return whh_grad_impl<kNative>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_lstm_whh_grad_x3(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                                   int reverse, float* workspace, size_t workspace_bytes, void* stream) {
-  return whh_grad_impl<kSplit>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_lstm_whh_grad_h2(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                                   int reverse, float* workspace, size_t workspace_bytes, const unsigned* amax_dgates,
-                                   const unsigned* amax_y, void* stream) {
-  return whh_grad_impl<kSplit2>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream,
-                                amax_dgates, amax_y);
-}
-
-extern "C" int pe_lstm_whh_grad_bf16(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                                     int reverse, float* workspace, size_t workspace_bytes, void* stream) {
-  return whh_grad_impl<kBf16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pe_lstm_whh_grad_f16(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
-                                    int reverse, float* workspace, size_t workspace_bytes, void* stream) {
-  return whh_grad_impl<kBf16, _Float16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
+extern "C" int pe_lstm_whh_grad(int products, const float* dgates, const float* y, long ldy, float* dwhh, int B, int T,
+                                int H, int reverse, float* workspace, size_t workspace_bytes,
+                                const unsigned* amax_dgates, const unsigned* amax_y, void* stream) {
+  switch (products) {
+    case PE_PROD_NATIVE:
+      return whh_grad_impl<kNative>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
+    case PE_PROD_X3:
+      return whh_grad_impl<kSplit>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
+    case PE_PROD_H2:
+      return whh_grad_impl<kSplit2>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream,
+                                    amax_dgates, amax_y);
+    case PE_PROD_BF16:
+      return whh_grad_impl<kBf16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
+    case PE_PROD_F16:
+      return whh_grad_impl<kBf16, _Float16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
+    default: return pe_unserved(products);
+  }
 }
 
 extern "C" size_t pe_colsum_workspace_bytes(int cols) { return (size_t)kColsumParts * cols * sizeof(double); }

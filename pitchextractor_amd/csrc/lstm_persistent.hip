@@ -1272,10 +1272,18 @@ static int lstm_fwd_persistent_impl(int ncells, const float* const* whh, float* 
   return launch_fwd_v2<384, TERMS, NBR, false, TH>(cells, grid, B, T, ldy, sync, st);
 }
 
-extern "C" int pe_lstm_fwd_persistent_x3(int ncells, const float* const* whh, float* const* gates, float* const* y,
-                                         float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
-                                         unsigned* sync, void* stream) {
-  return lstm_fwd_persistent_impl<3>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+// Persistent recurrences run 16-bit-term products only: x3 (TERMS = 3) and bf16 / f16 (TERMS = 1).
+extern "C" int pe_lstm_fwd_persistent(int products, int ncells, const float* const* whh, float* const* gates,
+                                      float* const* y, float* const* cbuf, const int* reverse, long ldy, int B, int T,
+                                      int H, unsigned* sync, void* stream) {
+  switch (products) {
+    case PE_PROD_X3: return lstm_fwd_persistent_impl<3>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+    case PE_PROD_BF16:
+      return lstm_fwd_persistent_impl<1>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+    case PE_PROD_F16:
+      return lstm_fwd_persistent_impl<1, _Float16>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+    default: return pe_unserved(products);
+  }
 }
 
 template <int TERMS, class TH = __bf16>
@@ -1303,45 +1311,27 @@ static int lstm_bwd_persistent_impl(int ncells, const float* const* whh_t, float
   return launch_bwd_v2<384, TERMS, NBR, false, TH>(cells, grid, B, T, lddy, sync, st);
 }
 
-// Rows ([ceil(B / 64)][4H] per cell) that pe_lstm_bwd_persistent_* writes into a non-null dbias_rows for this
+// Rows ([ceil(B / 64)][4H] per cell) that pe_lstm_bwd_persistent writes into a non-null dbias_rows for this
 // configuration; 0 = the persistent kernel does not serve it (run pe_lstm_bwd and pe_colsum).
 extern "C" int pe_lstm_bwd_persistent_dbias_rows(int ncells, int B, int T, int H, long lddy) {
   if (!pe_lstm_persistent_supported(ncells, B, H) || (lddy & 3) || T <= 0 || !small_enough(B, T, H, lddy)) return 0;
   return (B + 63) / 64;
 }
 
-extern "C" int pe_lstm_bwd_persistent_x3(int ncells, const float* const* whh_t, float* const* gates,
-                                         const float* const* cbuf, const float* const* dy, const int* reverse,
-                                         long lddy, int B, int T, int H, float* const* dbias_rows,
-                                         unsigned* const* dgates_amax, unsigned* sync, void* stream) {
-  return lstm_bwd_persistent_impl<3>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
-                                     sync, stream);
-}
-
-extern "C" int pe_lstm_fwd_persistent_bf16(int ncells, const float* const* whh, float* const* gates, float* const* y,
-                                           float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
-                                           unsigned* sync, void* stream) {
-  return lstm_fwd_persistent_impl<1>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
-}
-
-extern "C" int pe_lstm_fwd_persistent_f16(int ncells, const float* const* whh, float* const* gates, float* const* y,
-                                          float* const* cbuf, const int* reverse, long ldy, int B, int T, int H,
-                                          unsigned* sync, void* stream) {
-  return lstm_fwd_persistent_impl<1, _Float16>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
-}
-
-extern "C" int pe_lstm_bwd_persistent_bf16(int ncells, const float* const* whh_t, float* const* gates,
-                                           const float* const* cbuf, const float* const* dy, const int* reverse,
-                                           long lddy, int B, int T, int H, float* const* dbias_rows,
-                                           unsigned* const* dgates_amax, unsigned* sync, void* stream) {
-  return lstm_bwd_persistent_impl<1>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
-                                     sync, stream);
-}
-
-extern "C" int pe_lstm_bwd_persistent_f16(int ncells, const float* const* whh_t, float* const* gates,
-                                          const float* const* cbuf, const float* const* dy, const int* reverse,
-                                          long lddy, int B, int T, int H, float* const* dbias_rows,
-                                          unsigned* const* dgates_amax, unsigned* sync, void* stream) {
-  return lstm_bwd_persistent_impl<1, _Float16>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows,
-                                               dgates_amax, sync, stream);
+extern "C" int pe_lstm_bwd_persistent(int products, int ncells, const float* const* whh_t, float* const* gates,
+                                      const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
+                                      int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
+                                      unsigned* sync, void* stream) {
+  switch (products) {
+    case PE_PROD_X3:
+      return lstm_bwd_persistent_impl<3>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
+                                         sync, stream);
+    case PE_PROD_BF16:
+      return lstm_bwd_persistent_impl<1>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
+                                         sync, stream);
+    case PE_PROD_F16:
+      return lstm_bwd_persistent_impl<1, _Float16>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows,
+                                                   dgates_amax, sync, stream);
+    default: return pe_unserved(products);
+  }
 }

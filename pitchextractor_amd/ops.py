@@ -37,8 +37,8 @@ def _dense(t: torch.Tensor, name: str) -> torch.Tensor:
 
 # Mixed precision with bf16 ACTIVATION STORAGE (reference trainer.py:226-235 / README.md:36: autocast keeps conv and
 # linear outputs in 16 bits): when True (Trainer's mixed-precision scope with the bf16 dtype turns it on) the first
-# convolution writes a bf16 tensor and every pass of the conv stack follows the dtype of its inputs -- the `*_a16`
-# entry points of the C ABI.  The temporal heads, the losses and all parameters stay fp32.
+# convolution writes a bf16 tensor and every pass of the conv stack follows the dtype of its inputs -- `act16 = 1`
+# in the C ABI.  The temporal heads, the losses and all parameters stay fp32.
 ACT_BF16 = False
 
 
@@ -59,11 +59,11 @@ def _actd(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
-def _a16(*tensors) -> str:
-    """"_a16" if the given activation tensors are bfloat16, "" if float32; mixing is an error."""
+def _act16(*tensors) -> bool:
+    """True if the given activation tensors are bfloat16, False if float32; mixing is an error."""
     kinds = {t.dtype for t in tensors if t is not None}
     _chk(len(kinds) == 1, "activation tensors of one call must share a dtype")
-    return "_a16" if kinds.pop() == torch.bfloat16 else ""
+    return kinds.pop() == torch.bfloat16
 
 
 def _rows2d(t: torch.Tensor, name: str, act=False):
@@ -88,7 +88,10 @@ def workspace(nbytes: int, device) -> torch.Tensor:
 
 class KernelTimer:
     """Optional HIP-event timing of every C-ABI call (bench.py): events are recorded on the stream
-    the kernels are launched on and read back after the timed region, so nothing synchronises."""
+    the kernels are launched on and read back after the timed region, so nothing synchronises.
+    The key names the entry point and the product form it ran: the entry point, the form's suffix ("_x3", "_h2",
+    "_bf16", "_f16"; none for native fp32) and "_a16" for bf16 activation tensors, e.g. ``pe_conv3x3_fwd_wf_h2`` or
+    ``pe_gemm_tn_bf16_a16`` (bench.py reads the form and its peak from these keys)."""
 
     def __init__(self, only=None):
         self.records = {}
@@ -128,16 +131,29 @@ class timer_tag:
         TIMER_TAG = self.prev
 
 
-def _call(name, *args, work=0.0):
+# timer-key suffix of each pe_products value (KernelTimer)
+_FORM_SUFFIX = {_lib.PE_PROD_NATIVE: "", _lib.PE_PROD_X3: "_x3", _lib.PE_PROD_H2: "_h2", _lib.PE_PROD_BF16: "_bf16",
+                _lib.PE_PROD_F16: "_f16"}
+
+
+def _call(name, *args, products=None, act16=None, work=0.0, key=None):
+    """Launch entry point ``name``.  ``products`` and then ``act16`` go in front of ``args`` for the entry points that
+    take them; ``key`` (default: see KernelTimer) is what the launch is timed and reported under."""
+    if act16 is not None:
+        args = (int(act16),) + args
+    if products is not None:
+        args = (products,) + args
+    if key is None:
+        key = name + ("" if products is None else _FORM_SUFFIX[products]) + ("_a16" if act16 else "")
     lib = _lib.load()
-    if TIMER is None or (TIMER.only is not None and name not in TIMER.only):
-        _lib.check(getattr(lib, name)(*args), name)
+    if TIMER is None or (TIMER.only is not None and key not in TIMER.only):
+        _lib.check(getattr(lib, name)(*args), key)
         return
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
-    _lib.check(getattr(lib, name)(*args), name)
+    _lib.check(getattr(lib, name)(*args), key)
     b.record()
-    TIMER.add(name + ("#" + TIMER_TAG if TIMER_TAG else ""), a, b, work)
+    TIMER.add(key + ("#" + TIMER_TAG if TIMER_TAG else ""), a, b, work)
 
 
 def _s():
@@ -248,32 +264,31 @@ def absmax(t, out=None):
     return out
 
 
-def _tn_suffix():
-    """Weight-gradient / k-major products: bf16 operands under mixed precision (what autocast's backward does),
-    otherwise fp32-accurate (native or three-term split)."""
-    _chk(FP32_MATMUL in _FP32_MODES, "ops.FP32_MATMUL must be 'native', 'x3' or 'h2'")
-    if MATMUL_BF16:
-        return "_" + HALF_DTYPE
-    return "_" + FP32_MATMUL if FP32_MATMUL != "native" else ""
-
-
 # which persistent LSTM recurrences use the three-term split when FP32_MATMUL == "x3" (tools/bench_lstm.py)
 LSTM_X3 = {"fwd": os.environ.get("PE_LSTM_X3_FWD", "1") == "1", "bwd": os.environ.get("PE_LSTM_X3_BWD", "1") == "1"}
 
 
-def _lstm_suffix(which):
+def products_for(op="gemm"):
+    """The pe_products value (``_lib.PE_PROD_*``) the module state selects for one kind of product.
+    "gemm": GEMMs, convolutions and weight gradients -- the 16-bit type under mixed precision (what autocast runs,
+      its backward included), else FP32_MATMUL.
+    "lstm_fwd" / "lstm_bwd": the persistent recurrences -- the 16-bit type under mixed precision (as autocast runs
+      nn.LSTM); x3 under x3 and h2 ("h2" products need a tensor-wide scale before the first element is produced, and
+      the recurrences make their operands step by step); PE_PROD_NATIVE = the one-launch-per-step kernels, which also
+      serve native fp32, LSTM_X3 off and USE_PERSISTENT_LSTM off.
+    "attn": the fused attention -- bf16 under bf16 mixed precision, as autocast runs it; exact fp32 MFMAs otherwise
+      (the fp16 mode included)."""
+    if op == "attn":
+        return _lib.PE_PROD_BF16 if (MATMUL_BF16 and HALF_DTYPE == "bf16") else _lib.PE_PROD_NATIVE
+    if op != "gemm" and not USE_PERSISTENT_LSTM:
+        return _lib.PE_PROD_NATIVE
     if MATMUL_BF16:
-        return "_" + HALF_DTYPE        # mixed precision: 16-bit recurrent products (as autocast runs nn.LSTM)
-    # "h2" products need a tensor-wide scale before the first element is produced; the recurrences make their
-    # operands step by step, so they keep the three-term bf16 split in that mode
-    return "_x3" if (FP32_MATMUL in ("x3", "h2") and LSTM_X3[which]) else ""
-
-
-def _nt_suffix():
-    if MATMUL_BF16:
-        return "_" + HALF_DTYPE
+        return _lib.PE_PROD_BF16 if HALF_DTYPE == "bf16" else _lib.PE_PROD_F16
     _chk(FP32_MATMUL in _FP32_MODES, "ops.FP32_MATMUL must be 'native', 'x3' or 'h2'")
-    return "_" + FP32_MATMUL if FP32_MATMUL != "native" else ""
+    if op == "gemm":
+        return {"native": _lib.PE_PROD_NATIVE, "x3": _lib.PE_PROD_X3, "h2": _lib.PE_PROD_H2}[FP32_MATMUL]
+    x3 = FP32_MATMUL != "native" and LSTM_X3[op[len("lstm_"):]]
+    return _lib.PE_PROD_X3 if x3 else _lib.PE_PROD_NATIVE
 
 
 class matmul_bf16:
@@ -310,25 +325,17 @@ def gemm_nt(A, B, bias0=None, bias1=None, out=None, accumulate=False, amax_a=Non
         out = torch.empty((M, N), dtype=A.dtype, device=A.device)
     Mo, No, ldc = _rows2d(out, "out", act=True)
     _chk((Mo, No) == (M, N), "gemm_nt: out shape")
-    a16 = _a16(A, out)
-    if a16:
-        _chk(_nt_suffix() == "_bf16", "bfloat16 activations need the bf16 mixed-precision mode")
-        _call("pe_gemm_nt_bf16_a16", A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-              _lib.ptr(bias0), _lib.ptr(bias1), int(bool(accumulate)), _s(), work=2.0 * M * N * K)
-        return out
     for b in (bias0, bias1):
         if b is not None:
             _chk(_dense(b, "bias").numel() == N, "bias size")
-    sfx = _nt_suffix()
-    if sfx == "_h2":
+    p, a16 = products_for(), _act16(A, out)
+    _chk(not a16 or p == _lib.PE_PROD_BF16, "bfloat16 activations need the bf16 mixed-precision mode")
+    if p == _lib.PE_PROD_H2:
         amax_a = absmax(A) if amax_a is None else amax_a
         amax_b = absmax(B) if amax_b is None else amax_b
-        _call("pe_gemm_nt_h2", A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-              _lib.ptr(bias0), _lib.ptr(bias1), int(bool(accumulate)), amax_a.data_ptr(), amax_b.data_ptr(), _s(),
-              work=2.0 * M * N * K)
-        return out
-    _call("pe_gemm_nt" + sfx, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-          _lib.ptr(bias0), _lib.ptr(bias1), int(bool(accumulate)), _s(), work=2.0 * M * N * K)
+    _call("pe_gemm_nt", A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K, _lib.ptr(bias0),
+          _lib.ptr(bias1), int(bool(accumulate)), _lib.ptr(amax_a), _lib.ptr(amax_b), _s(), products=p, act16=a16,
+          work=2.0 * M * N * K)
     return out
 
 
@@ -342,23 +349,15 @@ def gemm_tn(A, B, out=None, accumulate=False, amax_a=None, amax_b=None):
         out = torch.empty((M, N), dtype=torch.float32, device=A.device)
     Mo, No, ldc = _rows2d(out, "out")
     _chk((Mo, No) == (M, N), "gemm_tn: out shape")
-    lib = _lib.load()
-    need = lib.pe_gemm_tn_workspace_bytes(M, N, K)
-    ws = workspace(need, A.device)
-    if _a16(A, B):
-        _chk(_tn_suffix() == "_bf16", "bfloat16 activations need the bf16 mixed-precision mode")
-        _call("pe_gemm_tn_bf16_a16", A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-              int(bool(accumulate)), ws.data_ptr(), ws.numel(), _s(), work=2.0 * M * N * K)
-        return out
-    if _tn_suffix() == "_h2":
+    p, a16 = products_for(), _act16(A, B)
+    _chk(not a16 or p == _lib.PE_PROD_BF16, "bfloat16 activations need the bf16 mixed-precision mode")
+    ws = workspace(_lib.load().pe_gemm_tn_workspace_bytes(M, N, K), A.device)
+    if p == _lib.PE_PROD_H2:
         amax_a = absmax(A) if amax_a is None else amax_a
         amax_b = absmax(B) if amax_b is None else amax_b
-        _call("pe_gemm_tn_h2", A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-              int(bool(accumulate)), ws.data_ptr(), ws.numel(), amax_a.data_ptr(), amax_b.data_ptr(), _s(),
-              work=2.0 * M * N * K)
-        return out
-    _call("pe_gemm_tn" + _tn_suffix(), A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-          int(bool(accumulate)), ws.data_ptr(), ws.numel(), _s(), work=2.0 * M * N * K)
+    _call("pe_gemm_tn", A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K, int(bool(accumulate)),
+          ws.data_ptr(), ws.numel(), _lib.ptr(amax_a), _lib.ptr(amax_b), _s(), products=p, act16=a16,
+          work=2.0 * M * N * K)
     return out
 
 
@@ -373,45 +372,36 @@ def transpose2d(x, out=None):
 
 
 # ------------------------------------------------------------------ conv
-# x3 / bf16 modes: 3x3 weights are packed once per step into MFMA B-fragment order (three exact bf16 terms, or
-# one rounded term) and the halo kernel loads them straight from L2 into registers (csrc/conv.hip).
+# x3 / h2 / bf16 / f16 modes: 3x3 weights are packed once per step into MFMA B-fragment order (the form's 16-bit
+# terms) and the halo kernel loads them straight from L2 into registers (csrc/conv.hip).
 CONV_WFRAG = os.environ.get("PE_CONV_WFRAG", "1") == "1"
 
 
 class PackedWeight:
     """One packed 3x3 weight: ``fp32`` [N, 9*C] (native MFMA path, fallback shapes) and, in the x3 / h2 / bf16 / f16
-    modes, ``frag`` = the same matrix as 16-bit MFMA fragments (``terms`` = 3 exact bf16 terms, 2 scaled fp16 terms
-    with ``amax`` = the weight's absmax word, or 1 rounded term of ``half``)."""
+    modes, ``frag`` = the same matrix as 16-bit MFMA fragments packed for the pe_products value ``products`` (h2:
+    scaled by ``amax``, the weight's absmax word)."""
 
-    def __init__(self, fp32, frag=None, terms=0, half=None, amax=None):
-        self.fp32, self.frag, self.terms, self.half, self.amax = fp32, frag, terms, half, amax
+    def __init__(self, fp32, frag=None, products=None, amax=None):
+        self.fp32, self.frag, self.products, self.amax = fp32, frag, products, amax
 
     @property
     def shape(self):
         return self.fp32.shape
 
 
-def wfrag_pack(w2d, terms, amax=None):
-    """[N, K] float32 (K % 16 == 0) -> fragment-ordered 16-bit terms (uint8 buffer); terms == 2 needs the weight's
-    absmax word."""
+def wfrag_pack(w2d, products, amax=None):
+    """[N, K] float32 (K % 16 == 0) -> fragment-ordered 16-bit terms of the form ``products`` (uint8 buffer); h2 needs
+    the weight's absmax word."""
     N, K, ld = _rows2d(w2d, "w")
-    lib = _lib.load()
-    nbytes = lib.pe_wfrag_bytes(N, K, terms)
-    _chk(nbytes > 0, "wfrag_pack: K must be a multiple of 16 and terms 1, 2 or 3")
+    nbytes = _lib.load().pe_wfrag_bytes(products, N, K)
+    _chk(nbytes > 0, "wfrag_pack: K must be a multiple of 16 and the form x3, h2, bf16 or f16")
+    _chk(products != _lib.PE_PROD_H2 or amax is not None, "wfrag_pack: two-term fragments need amax")
     out = torch.empty((nbytes,), dtype=torch.uint8, device=w2d.device)
-    if terms == 2:
-        _chk(amax is not None, "wfrag_pack: two-term fragments need amax")
-        _call("pe_wfrag_pack_h2", w2d.data_ptr(), ld, N, K, amax.data_ptr(), out.data_ptr(), _s())
-    elif terms == 1 and MATMUL_BF16 and HALF_DTYPE == "f16":
-        _call("pe_wfrag_pack_f16", w2d.data_ptr(), ld, N, K, out.data_ptr(), _s())
-    else:
-        _call("pe_wfrag_pack", w2d.data_ptr(), ld, N, K, int(terms), out.data_ptr(), _s())
+    # timer key: x3 and bf16 fragments are reported together under the bare name
+    _call("pe_wfrag_pack", products, w2d.data_ptr(), ld, N, K, _lib.ptr(amax), out.data_ptr(), _s(),
+          key="pe_wfrag_pack" + {_lib.PE_PROD_H2: "_h2", _lib.PE_PROD_F16: "_f16"}.get(products, ""))
     return out
-
-
-def _mode_terms():
-    sfx = _nt_suffix()
-    return 3 if sfx == "_x3" else 2 if sfx == "_h2" else 1 if sfx in ("_bf16", "_f16") else 0
 
 
 def conv3x3_repack(w, want_fwd=True, want_dgrad=True, amax=None):
@@ -423,8 +413,8 @@ def conv3x3_repack(w, want_fwd=True, want_dgrad=True, amax=None):
     wf = torch.empty((co, 9 * ci), dtype=torch.float32, device=w.device) if want_fwd else None
     wd = torch.empty((ci, 9 * co), dtype=torch.float32, device=w.device) if want_dgrad else None
     _call("pe_conv3x3_repack", w.data_ptr(), _lib.ptr(wf), _lib.ptr(wd), co, ci, _s())
-    terms = _mode_terms() if CONV_WFRAG else 0
-    if _mode_terms() != 2:
+    p = products_for()
+    if p != _lib.PE_PROD_H2:
         amax = None
     elif amax is None:
         amax = absmax(w.view(co, ci * 9))                               # forward and data-gradient forms share it
@@ -432,8 +422,8 @@ def conv3x3_repack(w, want_fwd=True, want_dgrad=True, amax=None):
     for t in (wf, wd):
         if t is None:
             out.append(None)
-        elif terms and t.shape[1] % 16 == 0:
-            out.append(PackedWeight(t, wfrag_pack(t, terms, amax), terms, HALF_DTYPE if terms == 1 else None, amax))
+        elif CONV_WFRAG and p != _lib.PE_PROD_NATIVE and t.shape[1] % 16 == 0:
+            out.append(PackedWeight(t, wfrag_pack(t, p, amax), p, amax))
         else:
             out.append(PackedWeight(t, amax=amax))
     return out[0], out[1]
@@ -456,26 +446,24 @@ def conv3x3_fwd(x, w_packed, out=None, accumulate=False, bn_stats=None, amax=Non
         _chk(not accumulate, "accumulate needs out")
         out = torch.empty((B, T, F, N), dtype=x.dtype, device=x.device)
     _chk(_actd(out, "out").shape == (B, T, F, N), "conv3x3_fwd: out shape")
-    a16 = _a16(x, out)
-    sfx = _nt_suffix()
-    _chk(not a16 or sfx == "_bf16", "bfloat16 activations need the bf16 mixed-precision mode")
-    sfx += a16
-    h2 = ()
-    if sfx == "_h2":
+    p, a16 = products_for(), _act16(x, out)
+    _chk(not a16 or p == _lib.PE_PROD_BF16, "bfloat16 activations need the bf16 mixed-precision mode")
+    amax_w = None
+    if p == _lib.PE_PROD_H2:
         amax_w = pw.amax if pw.amax is not None else absmax(w32)
         amax = absmax(x) if amax is None else amax                      # (held: see conv3x3_wgrad)
-        h2 = (amax.data_ptr(), amax_w.data_ptr())
-    if (pw.frag is not None and pw.terms == _mode_terms() and CONV_WFRAG
-            and (pw.terms != 1 or pw.half == HALF_DTYPE) and _lib.load().pe_conv3x3_wf_supported(F, Cc, N)):
+    h2 = (_lib.ptr(amax), _lib.ptr(amax_w))
+    work = 2.0 * B * T * F * N * 9 * Cc
+    if pw.frag is not None and pw.products == p and CONV_WFRAG and _lib.load().pe_conv3x3_wf_supported(F, Cc, N):
         parts = None
         if bn_stats:
             parts = torch.empty((_lib.load().pe_conv3x3_wf_stat_parts(B, T, F), 2, N), dtype=torch.float64,
                                 device=x.device)
-        _call("pe_conv3x3_fwd_wf" + sfx, x.data_ptr(), pw.frag.data_ptr(), out.data_ptr(), B, T, F, Cc, N,
-              int(bool(accumulate)), _lib.ptr(parts), *h2, _s(), work=2.0 * B * T * F * N * 9 * Cc)
+        _call("pe_conv3x3_fwd_wf", x.data_ptr(), pw.frag.data_ptr(), out.data_ptr(), B, T, F, Cc, N,
+              int(bool(accumulate)), _lib.ptr(parts), *h2, _s(), products=p, act16=a16, work=work)
         return (out, parts) if bn_stats is not None else out
-    _call("pe_conv3x3_fwd" + sfx, x.data_ptr(), w32.data_ptr(), out.data_ptr(), B, T, F, Cc, N,
-          int(bool(accumulate)), *h2, _s(), work=2.0 * B * T * F * N * 9 * Cc)
+    _call("pe_conv3x3_fwd", x.data_ptr(), w32.data_ptr(), out.data_ptr(), B, T, F, Cc, N, int(bool(accumulate)), *h2,
+          _s(), products=p, act16=a16, work=work)
     return (out, None) if bn_stats is not None else out
 
 
@@ -487,24 +475,17 @@ def conv3x3_wgrad(x, dy, dw, amax_x=None, amax_dy=None):
     B, T, F, Ci = x.shape
     Co = dy.shape[3]
     _chk(dy.shape[:3] == (B, T, F), "conv3x3_wgrad: dy shape")
-    if _a16(x, dy):
-        _chk(_tn_suffix() == "_bf16", "bfloat16 activations need the bf16 mixed-precision mode")
-        ws = workspace(_lib.load().pe_conv3x3_wgrad_workspace_bytes(B, T, F, Ci, Co), x.device)
-        _call("pe_conv3x3_wgrad_bf16_a16", x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, T, F, Ci, Co, ws.data_ptr(),
-              ws.numel(), _s(), work=2.0 * B * T * F * Co * 9 * Ci)
-        return dw
     _chk(dw.shape == (Co, Ci, 3, 3), "conv3x3_wgrad: dw shape")
-    lib = _lib.load()
-    ws = workspace(lib.pe_conv3x3_wgrad_workspace_bytes(B, T, F, Ci, Co), x.device)
-    h2 = ()
-    if _tn_suffix() == "_h2":
+    p, a16 = products_for(), _act16(x, dy)
+    _chk(not a16 or p == _lib.PE_PROD_BF16, "bfloat16 activations need the bf16 mixed-precision mode")
+    ws = workspace(_lib.load().pe_conv3x3_wgrad_workspace_bytes(B, T, F, Ci, Co), x.device)
+    if p == _lib.PE_PROD_H2:
         # both words stay referenced until the launch: a temporary dropped after .data_ptr() returns its memory to
         # the caching allocator, the second absmax() can reuse it, and x is then scaled by dy's word (Inf / NaN)
         amax_x = absmax(x) if amax_x is None else amax_x
         amax_dy = absmax(dy) if amax_dy is None else amax_dy
-        h2 = (amax_x.data_ptr(), amax_dy.data_ptr())
-    _call("pe_conv3x3_wgrad" + _tn_suffix(), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, T, F, Ci, Co,
-          ws.data_ptr(), ws.numel(), *h2, _s(), work=2.0 * B * T * F * Co * 9 * Ci)
+    _call("pe_conv3x3_wgrad", x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, T, F, Ci, Co, ws.data_ptr(), ws.numel(),
+          _lib.ptr(amax_x), _lib.ptr(amax_dy), _s(), products=p, act16=a16, work=2.0 * B * T * F * Co * 9 * Ci)
     return dw
 
 
@@ -529,8 +510,8 @@ def conv3x3_c1_fwd(x_btf, w, out=None, bn_stats=None):
     if bn_stats:
         parts = torch.empty((_lib.load().pe_conv3x3_c1_stat_parts(B, T, F), 2, 64), dtype=torch.float64,
                             device=x_btf.device)
-    _call("pe_conv3x3_c1_fwd" + _a16(out), x_btf.data_ptr(), sb, st, sf, w.data_ptr(), out.data_ptr(), B, T, F, _lib.ptr(parts),
-          _s())
+    _call("pe_conv3x3_c1_fwd", x_btf.data_ptr(), sb, st, sf, w.data_ptr(), out.data_ptr(), B, T, F, _lib.ptr(parts), _s(),
+          act16=_act16(out))
     return out if bn_stats is None else (out, parts)
 
 
@@ -541,8 +522,8 @@ def conv3x3_c1_wgrad(x_btf, dy, dw):
     _chk(dy.shape == (B, T, F, 64) and dw.shape == (64, 1, 3, 3), "conv3x3_c1_wgrad: shapes")
     lib = _lib.load()
     ws = workspace(lib.pe_conv3x3_wgrad_workspace_bytes(B, T, F, 1, 64), dy.device)
-    _call("pe_conv3x3_c1_wgrad" + _a16(dy), x_btf.data_ptr(), sb, st, sf, dy.data_ptr(), dw.data_ptr(), B, T, F,
-          ws.data_ptr(), ws.numel(), _s())
+    _call("pe_conv3x3_c1_wgrad", x_btf.data_ptr(), sb, st, sf, dy.data_ptr(), dw.data_ptr(), B, T, F, ws.data_ptr(),
+          ws.numel(), _s(), act16=_act16(dy))
     return dw
 
 
@@ -574,9 +555,9 @@ def bn_train_stats(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum
               st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), ws.data_ptr(), ws.numel(), _s())
         return st
     ws = workspace(lib.pe_bn_workspace_bytes(Cc), x.device)
-    _call("pe_bn_train_stats" + _a16(x), x.data_ptr(), x.numel() // Cc, Cc, gamma.data_ptr(), beta.data_ptr(), eps, momentum,
+    _call("pe_bn_train_stats", x.data_ptr(), x.numel() // Cc, Cc, gamma.data_ptr(), beta.data_ptr(), eps, momentum,
           _lib.ptr(running_mean), _lib.ptr(running_var), st.mean.data_ptr(), st.invstd.data_ptr(),
-          st.scale.data_ptr(), st.shift.data_ptr(), ws.data_ptr(), ws.numel(), _s())
+          st.scale.data_ptr(), st.shift.data_ptr(), ws.data_ptr(), ws.numel(), _s(), act16=_act16(x))
     return st
 
 
@@ -607,12 +588,8 @@ def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_o
     if out is None:
         out = torch.empty((B, T, Fo, Cc), dtype=x.dtype, device=x.device)
     ld = _slice_target(out, B, T, Fo, Cc, coff)
-    if _a16(x, out):
-        _call("pe_bn_act_pool_fwd_a16", x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), slope, out.data_ptr(),
-              B * T, F, Cc, pool, ld, coff, _s())
-        return out
     _call("pe_bn_act_pool_fwd", x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), slope, out.data_ptr(),
-          B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s())
+          B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s(), act16=_act16(x, out))
     return out
 
 
@@ -626,14 +603,9 @@ def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=
     _chk(_dense(dgamma, "dgamma").numel() == Cc and _dense(dbeta, "dbeta").numel() == Cc, "dgamma/dbeta size")
     lib = _lib.load()
     ws = workspace(lib.pe_bn_workspace_bytes(Cc) + 8 * Cc, x.device)
-    if _a16(x, dy, dx):
-        _call("pe_bn_act_pool_bwd_a16", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-              st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-              B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _s())
-        return dx
     _call("pe_bn_act_pool_bwd", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
           st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-          B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _lib.ptr(amax_out), _s())
+          B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _lib.ptr(amax_out), _s(), act16=_act16(x, dy, dx))
     return dx
 
 
@@ -647,7 +619,8 @@ def maxpool_fwd(x, pool, out=None, coff=0, want_argmax=False):
         out = torch.empty((B, T, Fo, Cc), dtype=x.dtype, device=x.device)
     ld = _slice_target(out, B, T, Fo, Cc, coff)
     arg = torch.empty((B, T, Fo, Cc), dtype=torch.uint8, device=x.device) if want_argmax else None
-    _call("pe_maxpool_fwd" + _a16(x, out), x.data_ptr(), out.data_ptr(), B * T, F, Cc, pool, ld, coff, _lib.ptr(arg), _s())
+    _call("pe_maxpool_fwd", x.data_ptr(), out.data_ptr(), B * T, F, Cc, pool, ld, coff, _lib.ptr(arg), _s(),
+          act16=_act16(x, out))
     return (out, arg) if want_argmax else out
 
 
@@ -661,12 +634,8 @@ def maxpool_bwd_add(x, dy, dx, pool, coff=0, amax_out=None, argmax=None):
              and argmax.shape == (B, T, F // pool, Cc), "maxpool_bwd_add: argmax shape")
     ld = _slice_target(dy, B, T, F // pool, Cc, coff)
     _chk(_actd(dx, "dx").shape == x.shape, "dx shape")
-    if _a16(dy, dx, x if argmax is None else None):
-        _call("pe_maxpool_bwd_add_a16", x.data_ptr() if argmax is None else 0, _lib.ptr(argmax), dy.data_ptr(),
-              dx.data_ptr(), B * T, F, Cc, pool, ld, coff, _s())
-        return dx
     _call("pe_maxpool_bwd_add", x.data_ptr() if argmax is None else 0, _lib.ptr(argmax), dy.data_ptr(), dx.data_ptr(),
-          B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s())
+          B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s(), act16=_act16(dy, dx, x if argmax is None else None))
     return dx
 
 
@@ -683,8 +652,8 @@ def dropout(x2d, p, out2d=None, mask_in=None, want_mask=True, seed=0, offset=0):
              and mask_in.numel() == rows * cols, "dropout: mask_in")
     elif want_mask:
         mask_out = torch.empty((rows, cols), dtype=torch.uint8, device=x2d.device)
-    _call("pe_dropout_fwd" + _a16(x2d, out2d), x2d.data_ptr(), ldx, out2d.data_ptr(), ldy, _lib.ptr(mask_in), _lib.ptr(mask_out),
-          rows, cols, float(p), int(seed), int(offset), _s())
+    _call("pe_dropout_fwd", x2d.data_ptr(), ldx, out2d.data_ptr(), ldy, _lib.ptr(mask_in), _lib.ptr(mask_out), rows, cols,
+          float(p), int(seed), int(offset), _s(), act16=_act16(x2d, out2d))
     return out2d, (mask_in if mask_in is not None else mask_out)
 
 
@@ -696,7 +665,7 @@ def nhwc_to_seq(x, Cc, coff=0, out=None):
     if out is None:
         out = torch.empty((B, T, 2 * Cc), dtype=torch.float32, device=x.device)
     _chk(_dense(out, "out").shape == (B, T, 2 * Cc), "nhwc_to_seq: out shape")       # the temporal heads read fp32
-    _call("pe_nhwc_to_seq" + _a16(x), x.data_ptr(), ld, coff, out.data_ptr(), B * T, Cc, _s())
+    _call("pe_nhwc_to_seq", x.data_ptr(), ld, coff, out.data_ptr(), B * T, Cc, _s(), act16=_act16(x))
     return out
 
 
@@ -705,7 +674,8 @@ def seq_to_nhwc(seq, out, Cc, coff=0, accumulate=False):
     out = _actd(out, "out")
     B, T, two, ld = out.shape
     _chk(two == 2 and coff + Cc <= ld and seq.shape == (B, T, 2 * Cc), "seq_to_nhwc: shape")
-    _call("pe_seq_to_nhwc" + _a16(out), seq.data_ptr(), out.data_ptr(), ld, coff, B * T, Cc, int(bool(accumulate)), _s())
+    _call("pe_seq_to_nhwc", seq.data_ptr(), out.data_ptr(), ld, coff, B * T, Cc, int(bool(accumulate)), _s(),
+          act16=_act16(out))
     return out
 
 
@@ -713,7 +683,8 @@ def copy2d(src2d, dst2d, accumulate=False):
     r, c, lds = _rows2d(src2d, "src", act=True)
     r2, c2, ldd = _rows2d(dst2d, "dst", act=True)
     _chk((r, c) == (r2, c2), "copy2d: shape")
-    _call("pe_copy2d" + _a16(src2d, dst2d), src2d.data_ptr(), lds, dst2d.data_ptr(), ldd, r, c, int(bool(accumulate)), _s())
+    _call("pe_copy2d", src2d.data_ptr(), lds, dst2d.data_ptr(), ldd, r, c, int(bool(accumulate)), _s(),
+          act16=_act16(src2d, dst2d))
     return dst2d
 
 
@@ -769,9 +740,9 @@ def clear_persistent_lstm_error(device) -> None:
 
 
 def _persistent_ok(ncells, B, H, device, which="fwd"):
-    """The persistent recurrence kernels serve this configuration: enabled, a 16-bit-term product form selected (x3 /
-    bf16 / f16: there is no native-fp32 persistent kernel) and the shape / device admitted by the library."""
-    if not USE_PERSISTENT_LSTM or _lstm_suffix(which) == "":
+    """The persistent recurrence kernels serve this configuration: a persistent product form selected (x3 / bf16 /
+    f16, see ``products_for``) and the shape / device admitted by the library."""
+    if products_for("lstm_" + which) == _lib.PE_PROD_NATIVE:
         return False
     with torch.cuda.device(device):
         return bool(_lib.load().pe_lstm_persistent_supported(ncells, B, H))
@@ -794,8 +765,8 @@ def lstm_fwd(whh, gates, y_slices, cbuf, reverse, B, T, H):
     dev = gates[0].device
     if _persistent_ok(n, B, H, dev, "fwd"):
         sync = _lstm_sync(n, B, dev)
-        _call("pe_lstm_fwd_persistent" + _lstm_suffix("fwd"), n, _ptr_array(whh), _ptr_array(gates), _ptr_array(y_slices),
-              _ptr_array(cbuf), _int_array(reverse), ldy, B, T, H, sync.data_ptr(), _s(),
+        _call("pe_lstm_fwd_persistent", n, _ptr_array(whh), _ptr_array(gates), _ptr_array(y_slices), _ptr_array(cbuf),
+              _int_array(reverse), ldy, B, T, H, sync.data_ptr(), _s(), products=products_for("lstm_fwd"),
               work=2.0 * n * B * (T - 1) * 4 * H * H)
         return
     _call("pe_lstm_fwd", n, _ptr_array(whh), _ptr_array(gates), _ptr_array(y_slices), _ptr_array(cbuf),
@@ -828,10 +799,10 @@ def lstm_bwd(whh_t, gates, cbuf, dy_slices, dcarry, reverse, B, T, H, dbias_rows
         if rows:
             _chk(len(dbias_rows) == n and all(_dense(d, "dbias_rows").shape == (rows, 4 * H) for d in dbias_rows),
                  "lstm_bwd: dbias_rows shape")
-        _call("pe_lstm_bwd_persistent" + _lstm_suffix("bwd"), n, _ptr_array(whh_t), _ptr_array(gates), _ptr_array(cbuf),
+        _call("pe_lstm_bwd_persistent", n, _ptr_array(whh_t), _ptr_array(gates), _ptr_array(cbuf),
               _ptr_array(dy_slices), _int_array(reverse), ld, B, T, H, _ptr_array(dbias_rows) if rows else None,
               _ptr_array(amax_out) if (rows and amax_out is not None) else None,
-              sync.data_ptr(), _s(), work=2.0 * n * B * (T - 1) * 4 * H * H)
+              sync.data_ptr(), _s(), products=products_for("lstm_bwd"), work=2.0 * n * B * (T - 1) * 4 * H * H)
         return bool(rows)
     _call("pe_lstm_bwd", n, _ptr_array(whh_t), _ptr_array(gates), _ptr_array(cbuf), _ptr_array(dy_slices),
           _ptr_array(dcarry), _int_array(reverse), ld, B, T, H, _s(), work=2.0 * n * B * (T - 1) * 4 * H * H)
@@ -853,14 +824,14 @@ def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H, amax_dg=None, amax_y=
     _chk(_dense(dwhh, "dwhh").shape == (4 * H, H), "dwhh shape")
     lib = _lib.load()
     ws = workspace(lib.pe_lstm_whh_grad_workspace_bytes(B, T, H), dgates.device)
-    h2 = ()
-    if _tn_suffix() == "_h2":
+    p = products_for()
+    if p == _lib.PE_PROD_H2:
         if amax_y is None:                 # |h| < 1 by construction (o * tanh(c)): a constant bound is a valid amax
             amax_y = _unit_amax(dgates.device)
         amax_dg = absmax(dgates) if amax_dg is None else amax_dg      # (held: see conv3x3_wgrad)
-        h2 = (amax_dg.data_ptr(), amax_y.data_ptr())
-    _call("pe_lstm_whh_grad" + _tn_suffix(), dgates.data_ptr(), ys.data_ptr(), ys.stride(1), dwhh.data_ptr(), B, T, H,
-          int(bool(reverse)), ws.data_ptr(), ws.numel(), *h2, _s(), work=2.0 * B * T * 4 * H * H)
+    _call("pe_lstm_whh_grad", dgates.data_ptr(), ys.data_ptr(), ys.stride(1), dwhh.data_ptr(), B, T, H,
+          int(bool(reverse)), ws.data_ptr(), ws.numel(), _lib.ptr(amax_dg), _lib.ptr(amax_y), _s(), products=p,
+          work=2.0 * B * T * 4 * H * H)
     return dwhh
 
 
@@ -992,12 +963,6 @@ def attn_supported(T, dh):
     return bool(FUSED_ATTENTION and _lib.load().pe_attn_supported(int(T), int(dh)))
 
 
-def _attn_suffix():
-    """Mixed precision with bf16 operands runs the attention matmuls on the bf16 MFMA as autocast does (softmax, the
-    log-sum-exp and every tensor in memory stay fp32); the fp16 mode and the fp32 modes keep the exact-fp32 MFMAs."""
-    return "_bf16" if (MATMUL_BF16 and HALF_DTYPE == "bf16") else ""
-
-
 def attn_fwd(qkv, B, T, H, scale, p=0.0, mask_in=None, seed=0, offset=0):
     """Fused softmax(Q K^T * scale) -> dropout(p) -> . V for packed projections qkv [B*T, 3*H*dh].
     Returns (o [B*T, H*dh], lse [B*H*T], keep mask uint8 [B*H*T, T] or None)."""
@@ -1015,9 +980,9 @@ def attn_fwd(qkv, B, T, H, scale, p=0.0, mask_in=None, seed=0, offset=0):
                  and mask_in.numel() == B * H * T * T, "attn_fwd: mask_in")
         else:
             mask_out = torch.empty((B * H * T, T), dtype=torch.uint8, device=qkv.device)
-    _call("pe_attn_fwd" + _attn_suffix(), qkv.data_ptr(), D3, o.data_ptr(), D, lse.data_ptr(), _lib.ptr(mask_in if p > 0.0 else None),
+    _call("pe_attn_fwd", qkv.data_ptr(), D3, o.data_ptr(), D, lse.data_ptr(), _lib.ptr(mask_in if p > 0.0 else None),
           _lib.ptr(mask_out), B, T, H, dh, float(scale), float(p), int(seed), int(offset), _s(),
-          work=4.0 * B * H * T * T * dh)
+          products=products_for("attn"), work=4.0 * B * H * T * T * dh)
     return o, lse, (mask_in if (p > 0.0 and mask_in is not None) else mask_out)
 
 
@@ -1032,9 +997,9 @@ def attn_bwd(qkv, o, d_o, lse, mask, B, T, H, scale, p=0.0):
         _chk(mask is not None and mask.is_cuda and mask.dtype == torch.uint8 and mask.numel() == B * H * T * T,
              "attn_bwd: mask")
     dqkv = torch.empty_like(qkv)
-    _call("pe_attn_bwd" + _attn_suffix(), qkv.data_ptr(), D3, o.data_ptr(), d_o.data_ptr(), D, lse.data_ptr(),
+    _call("pe_attn_bwd", qkv.data_ptr(), D3, o.data_ptr(), d_o.data_ptr(), D, lse.data_ptr(),
           _lib.ptr(mask if p > 0.0 else None), dqkv.data_ptr(), B, T, H, dh, float(scale), float(p), _s(),
-          work=10.0 * B * H * T * T * dh)
+          products=products_for("attn"), work=10.0 * B * H * T * T * dh)
     return dqkv
 
 

@@ -41,10 +41,17 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
         _lib.load()
 
 
-def test_argument_checks_run_before_any_device_call(lib):
+def test_product_forms_agree_with_the_header():
+    text = (ROOT / "include" / "pitchextractor_hip.h").read_text()
+    enum = dict(re.findall(r"\b(PE_PROD_[A-Z0-9]+)\s*=\s*(\d+)", text))
+    assert enum and {k: int(v) for k, v in enum.items()} == {k: getattr(_lib, k) for k in enum}
+
+
+def test_argument_and_form_checks_run_before_any_device_call(lib):
     """The entry points validate their arguments on the host (no GPU in this test): a leading dimension the 32-bit
-    buffer offsets of the operand loaders cannot address, a 3x3 convolution whose tensor passes 2 GiB and a missing
-    operand-scale word are refused with the documented codes instead of being launched."""
+    buffer offsets of the operand loaders cannot address, a 3x3 convolution whose tensor passes 2 GiB, a missing
+    operand-scale word, and a product form / activation type that no kernel of the entry point serves or that is not a
+    form at all are refused with the documented codes instead of being launched."""
     import ctypes
     buf = (ctypes.c_float * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
@@ -52,10 +59,20 @@ def test_argument_checks_run_before_any_device_call(lib):
     unsupported, bad_arg = -2, -1
     codes = {c: getattr(_lib, c) for c in ("PE_E_UNSUPPORTED", "PE_E_ARG") if hasattr(_lib, c)}
     unsupported, bad_arg = codes.get("PE_E_UNSUPPORTED", unsupported), codes.get("PE_E_ARG", bad_arg)
+    h2 = _lib.PE_PROD_H2
     # NT: lda = 2^21 floats; TN: ldb = 2^24
-    assert lib.pe_gemm_nt_h2(p, 1 << 21, p, 64, p, 64, 128, 64, 64, None, None, 0, word, word, None) == unsupported
-    assert lib.pe_gemm_tn_h2(p, 64, p, 1 << 24, p, 64, 64, 64, 64, 0, None, 0, word, word, None) == unsupported
+    assert lib.pe_gemm_nt(h2, 0, p, 1 << 21, p, 64, p, 64, 128, 64, 64, None, None, 0, word, word, None) == unsupported
+    assert lib.pe_gemm_tn(h2, 0, p, 64, p, 1 << 24, p, 64, 64, 64, 64, 0, None, 0, word, word, None) == unsupported
     # h2 without the scale words
-    assert lib.pe_gemm_nt_h2(p, 64, p, 64, p, 64, 128, 64, 64, None, None, 0, None, None, None) == bad_arg
+    assert lib.pe_gemm_nt(h2, 0, p, 64, p, 64, p, 64, 128, 64, 64, None, None, 0, None, None, None) == bad_arg
     # staged-window convolution: 2^31 bytes of input
-    assert lib.pe_conv3x3_fwd_wf_h2(p, p, p, 4096, 192, 80, 64, 64, 0, None, None, word, word) == unsupported
+    assert lib.pe_conv3x3_fwd_wf(h2, 0, p, p, p, 4096, 192, 80, 64, 64, 0, None, word, word, None) == unsupported
+    # bf16 activation tensors with any form but bf16
+    assert lib.pe_gemm_nt(h2, 1, p, 64, p, 64, p, 64, 128, 64, 64, None, None, 0, word, word, None) == unsupported
+    # there is no native-fp32 persistent recurrence
+    cells = (ctypes.c_void_p * 1)(p)
+    rev = (ctypes.c_int * 1)(0)
+    assert lib.pe_lstm_fwd_persistent(_lib.PE_PROD_NATIVE, 1, cells, cells, cells, cells, rev, 384, 64, 8, 384, p,
+                                      None) == unsupported
+    # not a product form
+    assert lib.pe_gemm_nt(5, 0, p, 64, p, 64, p, 64, 128, 64, 64, None, None, 0, word, word, None) == bad_arg

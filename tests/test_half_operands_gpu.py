@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from pitchextractor_amd import ops
+from pitchextractor_amd import _lib, ops
 from tests import half_ref as R
 from tests.test_ops_gpu import close, nchw, nhwc, rnd
 
@@ -234,15 +234,14 @@ def test_conv3x3_epilogue_bn_statistics_half(hip_device, B, T, Fq, Ci, Co, acc, 
         close(v, u.cpu(), 1e-6)
 
 
-def test_wfrag_pack_f16_is_rne_fp16_in_fragment_layout(hip_device):
-    """pe_wfrag_pack_f16: fragment (kb, nb), lane 32 h + r  <->  w[32 nb + r][16 kb + 8 h .. + 7], bit-equal to the
+def test_wfrag_pack_products_f16_is_rne_fp16_in_fragment_layout(hip_device):
+    """pe_wfrag_pack (f16): fragment (kb, nb), lane 32 h + r  <->  w[32 nb + r][16 kb + 8 h .. + 7], bit-equal to the
     RNE fp16 of w (tail rows zero), including values that round to 65504, overflow, and fp16 subnormals"""
     N, K = 70, 96
     w = rnd(N, K, seed=3) * torch.exp(rnd(N, K, seed=4) * 2)
     w[0, :4] = torch.tensor([65519.0, 65520.0, -1e5, 3 * 2.0 ** -26])
     w[1, :3] = torch.tensor([2.0 ** -20, -(2.0 ** -24), 1 + 2.0 ** -11])
-    with ops.matmul_bf16(True, "f16"):
-        raw = ops.wfrag_pack(w.to(hip_device), 1).cpu()
+    raw = ops.wfrag_pack(w.to(hip_device), _lib.PE_PROD_F16).cpu()
     frag = raw.view(torch.int16).view(K // 16, 3, 1, 64, 8)[:, :, 0]                      # [kb][nb][lane][8]
     wpad = torch.zeros(96, K, dtype=torch.float16)
     wpad[:N] = w.to(torch.float16)
@@ -250,14 +249,14 @@ def test_wfrag_pack_f16_is_rne_fp16_in_fragment_layout(hip_device):
     assert torch.equal(frag, ref.view(torch.int16))
 
 
-def test_bf16_packed_weight_used_under_f16_falls_back_to_the_implicit_gemm(hip_device):
+def test_products_bf16_packed_weight_used_under_f16_falls_back_to_the_implicit_gemm(hip_device):
     """A weight packed under bf16 carries bf16 fragments; used inside an f16 scope ops.conv3x3_fwd must not feed them
-    to the f16 kernel (the `pw.half == HALF_DTYPE` guard) and gives the f16 result of the implicit GEMM"""
+    to the f16 kernel (the `pw.products` guard) and gives the f16 result of the implicit GEMM"""
     B, T, Fq, Ci, Co = 2, 12, 10, 64, 128
     x, w = rnd(B, Ci, T, Fq, seed=1), rnd(Co, Ci, 3, 3, seed=2, scale=0.1)
     with ops.matmul_bf16(True, "bf16"):
         wf, _ = ops.conv3x3_repack(w.to(hip_device))
-    assert wf.frag is not None and wf.half == "bf16"
+    assert wf.frag is not None and wf.products == _lib.PE_PROD_BF16
     with ops.matmul_bf16(True, "f16"):
         got = ops.conv3x3_fwd(nhwc(x).to(hip_device), wf)
     ref = F.conv2d(R.hr(x, "f16"), R.hr(w, "f16"), padding=1)

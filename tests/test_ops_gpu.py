@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from pitchextractor_amd import ops
+from pitchextractor_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -224,13 +224,13 @@ def test_conv3x3_fwd_dgrad_wgrad(hip_device, B, T, Fq, Ci, Co, fp32_mode, monkey
     close(nchw(ops.conv3x3_fwd(xd, wf, out=acc, accumulate=True)), ref_acc)
 
 
-def test_weight_fragment_pack_layout(hip_device):
+def test_weight_fragment_pack_layout_by_products(hip_device):
     """pe_wfrag_pack: fragment (kb, nb, term), lane 32 h + r  <->  w[32 nb + r][16 kb + 8 h .. + 7]; the three
     terms are the exact truncation split (hi + mid + lo == w bit for bit), one term = RNE bf16."""
     N, K = 70, 96                                            # N not a multiple of 32: the tail rows pack as zeros
     w = rnd(N, K, seed=3) * torch.exp(rnd(N, K, seed=4) * 3)
-    for terms in (3, 1):
-        raw = ops.wfrag_pack(w.to(hip_device), terms).cpu()
+    for products, terms in ((_lib.PE_PROD_X3, 3), (_lib.PE_PROD_BF16, 1)):
+        raw = ops.wfrag_pack(w.to(hip_device), products).cpu()
         frag = raw.view(torch.bfloat16).view(K // 16, 3, terms, 64, 8).float()        # [kb][nb][term][lane][8]
         wpad = torch.zeros(96, K)
         wpad[:N] = w

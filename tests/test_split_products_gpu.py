@@ -40,7 +40,7 @@ import numpy as np
 import pytest
 import torch
 
-from pitchextractor_amd import ops
+from pitchextractor_amd import _lib, ops
 from tests import split_ref as S
 from tests.half_ref import shifted_y
 from tests.test_half_operands_gpu import CONV_SHAPES, NT_SHAPES, TN_SHAPES, halo_kernel
@@ -270,21 +270,21 @@ def _frag_ref(t, N, K, terms):
     return pad.view(nb, 32, K // 16, 2, 8).permute(2, 0, 3, 1, 4).reshape(K // 16, nb, 64, 8)
 
 
-def test_wfrag_pack_h2_and_x3_terms_are_the_split_in_fragment_layout(hip_device):
-    """pe_wfrag_pack_h2 (two fp16 terms of the weight scaled by its absmax word) and pe_wfrag_pack terms=3 (three
+def test_wfrag_pack_h2_and_x3_products_are_the_split_in_fragment_layout(hip_device):
+    """pe_wfrag_pack under PE_PROD_H2 (two fp16 terms of the weight scaled by its absmax word) and PE_PROD_X3 (three
     truncated bf16 terms): every fragment word bit-equal to the split, fp16 / fp32 subnormals included"""
     N, K = 70, 96
     w = S.heavy((N, K), 0, seed=9)
     w[1, :3] = torch.tensor([2.0 ** -130, -(2.0 ** -120), 1 + 2.0 ** -11])
     amax = ops.absmax(w.to(hip_device))
     assert amax.item() == S.absmax_bits(w)
-    raw = ops.wfrag_pack(w.to(hip_device), 2, amax).cpu()
+    raw = ops.wfrag_pack(w.to(hip_device), _lib.PE_PROD_H2, amax).cpu()
     frag = raw.view(torch.int16).view(K // 16, (N + 31) // 32, 2, 64, 8)
     hi, lo, _ = S.split_h2(w)
     for i, t in enumerate((hi, lo)):
         assert torch.equal(frag[:, :, i], _frag_ref(t.to(torch.float16), N, K, 2).view(torch.int16)), i
     assert ((hi.abs() < 2.0 ** -14) & (hi != 0)).any() and ((lo.abs() < 2.0 ** -14) & (lo != 0)).any()
-    raw = ops.wfrag_pack(w.to(hip_device), 3).cpu()
+    raw = ops.wfrag_pack(w.to(hip_device), _lib.PE_PROD_X3).cpu()
     frag = raw.view(torch.int16).view(K // 16, (N + 31) // 32, 3, 64, 8)
     for i, t in enumerate(S.split_x3(w)):
         ref = _frag_ref(t.float(), N, K, 3).view(torch.int32) >> 16
@@ -467,7 +467,7 @@ def test_h2_words_computed_inside_the_op_belong_to_their_operand(hip_device, op_
 # ------------------------------------------------------------------ x3 persistent LSTM (H = 384), teacher forcing
 @pytest.mark.parametrize("B,reverse", [(1, (0,)), (65, (1,)), (130, (0, 1))])
 def test_persistent_lstm_x3_step_by_step(hip_device, B, reverse, monkeypatch):
-    """pe_lstm_fwd_persistent_x3 / pe_lstm_bwd_persistent_x3 one float64 step at a time from the kernel's own stored
+    """pe_lstm_fwd_persistent / pe_lstm_bwd_persistent (x3) one float64 step at a time from the kernel's own stored
     state (tests/half_ref.py, half=None: the x3 split rebuilds every operand and the kept products miss at most
     2^-23 of sum|w h|; the backward exchanges its partial sums as fp32).
 

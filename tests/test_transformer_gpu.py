@@ -258,7 +258,7 @@ def test_fused_attention_fwd_bwd(hip_device, p):
 
 @pytest.mark.parametrize("p", [0.0, 0.1])
 def test_fused_attention_bf16_operands(hip_device, p):
-    """Mixed precision (bf16): pe_attn_fwd_bf16 / pe_attn_bwd_bf16 round the matmul operands to bf16 and keep softmax,
+    """Mixed precision (bf16): pe_attn_fwd / pe_attn_bwd under PE_PROD_BF16 round the matmul operands to bf16 and keep softmax,
     log-sum-exp and accumulation in fp32.  Forward against a float64 restatement that rounds at the same points (Q, K, V
     and the dropped-out probabilities): 1e-3 of the tensor maximum (a probability that sits near a bf16 rounding boundary
     rounds differently from fp32 than from float64: measured 3.5e-4); log-sum-exp likewise; gradients against the EXACT
