@@ -416,6 +416,37 @@ int pe_pitch_shift_resample(const float* stretched, const long* meta, const doub
                             int res_type, const float* gains, const float* noise, int n_rows, long n_out, float* out,
                             void* stream);
 
+/* ---- F0 bin decoding (build-defined; the inverse of pe_f0_bins_ce_loss) and pitch metrics --------------------
+ * logits: N sequences of T frames of C bins, frame (n, t) at logits + n * ld_n + t * ld_t (2 <= C <= 1024, more is
+ * PE_E_UNSUPPORTED).  Bin b stands for cents(b) = 20 b + 1997.3794084376191, f(b) = 10 * 2^(cents(b) / 1200) Hz.
+ * lengths (nullable, N int32 on the device, 1 <= lengths[n] <= T): frames at t >= lengths[n] are ignored and their
+ * outputs are 0.  Outputs are dense (N, T).
+ *
+ * pe_f0_decode_frames: per frame, the bin (bins_in[n * T + t] when bins_in is given, else the arg max of the row, the
+ * LOWEST index on ties), its frequency and confidence = softmax(row)[bin].  PE_F0_ARGMAX: f0 = f(bin);
+ * PE_F0_WEIGHTED: f0 = 10 * 2^(cents / 1200) with cents the average of cents(c) over c in [bin - 4, bin + 4] (cut at
+ * the row ends) under the weights exp(l_c - l_bin).  bins_out may be NULL when bins_in is given; the two must not overlap.
+ *
+ * pe_f0_viterbi: bins_out[n][0 .. L) = the path maximising l_0[b_0] + sum_t (log A(b_{t-1}, b_t) + l_t[b_t]) with
+ * A(i, j) = max(12 - |i - j|, 0) / sum_j' max(12 - |i - j'|, 0), ties to the lowest index.  One workgroup per
+ * sequence; back-pointers stay in LDS when T * C bytes fit beside the two delta rows, else they go to `workspace`
+ * (pe_f0_viterbi_workspace_bytes, 0 when none is needed; PE_E_WORKSPACE when it is needed and too small).
+ *
+ * pe_pitch_metrics (reference Utils/dynamic_pitch_tools.py:79-104): over n frames, voiced = f0_ref > 0, cents re
+ * 55 Hz in double.  out6 (device doubles) = {rms cents error over voiced frames with the prediction clipped below
+ * at 1e-5 (rms_cents_error), share of voiced frames with a positive prediction within threshold_cents, the same on
+ * the circular (octave-forgiving) distance, share of frames whose voicing differs, voiced frames, frames}; the
+ * first three are NaN when no frame is voiced.  One workgroup. */
+#define PE_F0_ARGMAX 0
+#define PE_F0_WEIGHTED 1
+int pe_f0_decode_frames(const float* logits, long ld_t, long ld_n, int C, const int* lengths, const int* bins_in,
+                        int N, int T, int method, int* bins_out, float* f0_out, float* conf_out, void* stream);
+size_t pe_f0_viterbi_workspace_bytes(int N, int T, int C);
+int pe_f0_viterbi(const float* logits, long ld_t, long ld_n, int C, const int* lengths, int N, int T, int* bins_out,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int pe_pitch_metrics(const float* f0_pred, const float* f0_ref, long n, double threshold_cents, double* out6,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

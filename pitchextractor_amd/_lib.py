@@ -31,6 +31,8 @@ _ip = C.POINTER(C.c_int)
 
 # enum pe_products: the product form, first argument of every MFMA-bound entry point
 PE_PROD_NATIVE, PE_PROD_X3, PE_PROD_H2, PE_PROD_BF16, PE_PROD_F16 = range(5)
+# method of pe_f0_decode_frames
+PE_F0_ARGMAX, PE_F0_WEIGHTED = range(2)
 
 # name -> (restype, argtypes).  Mirrors include/pitchextractor_hip.h one to one;
 # tests/test_abi.py checks the two against each other and against the .so.
@@ -122,6 +124,10 @@ PROTOTYPES = {
     "pe_f0_bins_ce_loss": (_i, [_p, _l, _i, _p, _p, _p, _f, _l, _f, _p, _p, _l, _p, _p, _z, _p]),
     "pe_nonfinite_flag": (_i, [_p, _l, _p, _p]),
     "pe_adamw_step": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _d, _d, _f, _p, _p]),
+    "pe_f0_decode_frames": (_i, [_p, _l, _l, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "pe_f0_viterbi_workspace_bytes": (_z, [_i, _i, _i]),
+    "pe_f0_viterbi": (_i, [_p, _l, _l, _i, _p, _i, _i, _p, _p, _z, _p]),
+    "pe_pitch_metrics": (_i, [_p, _p, _l, _d, _p, _p]),
 }
 
 

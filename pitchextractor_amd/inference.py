@@ -71,7 +71,25 @@ def waveform_to_mel(audio, mel_transform: MelSpectrogram | None = None, device="
 
 @torch.no_grad()
 def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
-               mel_transform: MelSpectrogram | None = None) -> np.ndarray:
+               mel_transform: MelSpectrogram | None = None, *, decoder: str | None = None,
+               silence_threshold: float | None = None, return_confidence: bool = False):
+    """The notebook's recipe.  With the keyword arguments left alone it returns what the notebook returns: Hz for a
+    regression model (``num_class == 1``), the raw ``(frames, num_class)`` logits otherwise.
+
+    ``decoder`` ("argmax", "weighted", "viterbi", "weighted_viterbi"; ``ops.decode_f0_bins``) turns a classifier's
+    logits into Hz on the device: every chunk is one sequence of ``end - start`` frames (chunks are independent and
+    the un-blended concatenation repeats ``overlap`` frames at each seam, so no path runs across seams), all chunks
+    are decoded in one call and concatenated as the Hz of a regression model are.  ``silence_threshold=p`` returns
+    0 Hz where ``sigmoid(detector logit) > p`` (the detector head predicts ``is_silence``).
+    ``return_confidence=True`` returns ``(f0, confidence)``, confidence = softmax(frame)[decoded bin]."""
+    if decoder is not None and decoder not in ops.F0_DECODERS:
+        raise ValueError(f"decoder must be one of {ops.F0_DECODERS}, got {decoder!r}")
+    if decoder is not None and model.num_class == 1:
+        raise ValueError("decoder: the model is a regression model (num_class == 1), there are no bins to decode")
+    if return_confidence and decoder is None:
+        raise ValueError("return_confidence needs a decoder")
+    if silence_threshold is not None and decoder is None and model.num_class != 1:
+        raise ValueError("silence_threshold on a classifier needs a decoder")
     device = model.flat_parameters.device
     mel = waveform_to_mel(audio, mel_transform, device)
     total = mel.shape[-1]
@@ -85,12 +103,58 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
         batch[i, 0, :, :e - s] = mel[:, s:e]
     was_training = model.training
     model.eval()
-    f0, _ = model(batch.transpose(-1, -2))
+    f0, sil = model(batch.transpose(-1, -2))
     if ops.persistent_lstm_error(device):          # a timed-out group barrier voids the outputs: redo on the safe kernels
         ops.clear_persistent_lstm_error(device)
         ops.USE_PERSISTENT_LSTM = False
-        f0, _ = model(batch.transpose(-1, -2))
+        f0, sil = model(batch.transpose(-1, -2))
     if was_training:
         model.train()
+    if decoder is not None or silence_threshold is not None:
+        ends = [min(s + chunk_size, total) - s for s in starts]
+        conf = None
+        if decoder is not None:
+            lengths = torch.tensor(ends, dtype=torch.int32, device=device)
+            hz, conf, _ = ops.decode_f0_bins(f0.detach().contiguous(), lengths, decoder)
+        else:
+            hz = f0[..., 0]
+        if silence_threshold is not None:
+            # sigmoid(z) > p  <=>  z > logit(p); the comparison is exact, the zeros are written on the device
+            p = float(silence_threshold)
+            cut = -np.inf if p <= 0.0 else (np.inf if p >= 1.0 else float(np.log(p) - np.log1p(-p)))
+            hz = torch.where(sil.reshape(hz.shape) > cut, torch.zeros_like(hz), hz)
+        hz = hz.cpu().numpy()
+        out = np.concatenate([hz[i][:e] for i, e in enumerate(ends)])
+        if not return_confidence:
+            return out
+        conf = conf.cpu().numpy()
+        return out, np.concatenate([conf[i][:e] for i, e in enumerate(ends)])
     f0 = f0[..., 0].cpu().numpy() if f0.shape[-1] == 1 else f0.cpu().numpy()
     return np.concatenate([f0[i][:min(s + chunk_size, total) - s] for i, s in enumerate(starts)])
+
+
+def pitch_metrics(f0_pred, f0_ref, *, threshold_cents: float = 50.0, device="cuda") -> dict:
+    """How far a predicted F0 track (Hz, 0 = unvoiced) is from a reference track, over their first ``min(len)``
+    frames, reduced on the device.  Device tensors or arrays.  With ``voiced = f0_ref > 0`` and cents re 55 Hz:
+
+    * ``rms_cents``: the reference's ``rms_cents_error`` (Utils/dynamic_pitch_tools.py:92-104): RMS cents error over
+      the voiced frames, the prediction clipped below at 1e-5; NaN when no frame is voiced;
+    * ``rpa``: share of voiced frames predicted within ``threshold_cents`` (a predicted 0 Hz is a miss);
+      ``rca``: the same on ``circular_cents_distance`` (octave errors forgiven);
+    * ``vuv_error``: share of all frames whose voicing decision differs; ``n_voiced``, ``n_frames``."""
+    def as_track(x):
+        if isinstance(x, torch.Tensor):
+            return x.detach().reshape(-1)
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1)))
+
+    pred, ref = as_track(f0_pred), as_track(f0_ref)
+    n = min(pred.numel(), ref.numel())
+    nan = float("nan")
+    if n == 0:
+        return dict(rms_cents=nan, rpa=nan, rca=nan, vuv_error=nan, n_voiced=0, n_frames=0)
+    dev = pred.device if pred.is_cuda else (ref.device if ref.is_cuda else torch.device(device))
+    pred = pred[:n].to(dev, torch.float32).contiguous()
+    ref = ref[:n].to(dev, torch.float32).contiguous()
+    out = ops.pitch_metrics(pred, ref, threshold_cents).cpu().tolist()
+    return dict(rms_cents=out[0], rpa=out[1], rca=out[2], vuv_error=out[3], n_voiced=int(out[4]),
+                n_frames=int(out[5]))

@@ -909,6 +909,59 @@ def f0_bins_ce_loss(logits, f0, sil_pred, sil, lambda_f0, grad_scale=1.0, want_g
     return out4, d_logits, d_sil
 
 
+F0_DECODERS = ("argmax", "weighted", "viterbi", "weighted_viterbi")
+
+
+def decode_f0_bins(logits, lengths=None, method="argmax"):
+    """Read a pitch out of F0 classifier logits (the inverse of ``f0_bins_ce_loss``; build-defined).
+    logits (N, T, C) or (T, C) float32 with unit bin stride; ``lengths`` optional (N,) int32 device tensor with
+    1 <= lengths[n] <= T (frames beyond it give 0).  ``method``: "argmax" (lowest index on ties), "weighted"
+    (softmax-weighted cents over the +-4 bins around the arg max), "viterbi" (triangular 12-bin transition band,
+    each sequence on its own), "weighted_viterbi" (the same local average around the Viterbi bin).
+    Returns (f0_hz, confidence = softmax(frame)[bin], bins): (N, T) float32 / float32 / int32 device tensors."""
+    _chk(method in F0_DECODERS, f"decode_f0_bins: method must be one of {F0_DECODERS}, got {method!r}")
+    _f32c(logits, "logits")
+    squeeze = logits.dim() == 2
+    if squeeze:
+        logits = logits.unsqueeze(0)
+    _chk(logits.dim() == 3, "logits: expected (N, T, C) or (T, C)")
+    N, T, C = logits.shape
+    _chk(N > 0 and T > 0 and 2 <= C <= 1024, "logits: need N, T >= 1 and 2 <= C <= 1024")
+    _chk(logits.stride(2) == 1, "logits: expected unit stride over the bins")
+    ld_t = logits.stride(1) if T > 1 else max(C, logits.stride(1))
+    ld_n = logits.stride(0) if N > 1 else max((T - 1) * ld_t + C, logits.stride(0))
+    _chk(ld_t >= C and ld_n >= (T - 1) * ld_t + C, "logits: frames or sequences overlap in memory")
+    if lengths is not None:
+        _chk(lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == N,
+             "lengths: expected a contiguous int32 device tensor of N entries")
+    dev = logits.device
+    bins = torch.empty((N, T), dtype=torch.int32, device=dev)
+    f0 = torch.empty((N, T), dtype=torch.float32, device=dev)
+    conf = torch.empty((N, T), dtype=torch.float32, device=dev)
+    path = None
+    if method in ("viterbi", "weighted_viterbi"):
+        nbytes = _lib.load().pe_f0_viterbi_workspace_bytes(N, T, C)
+        ws = workspace(nbytes, dev) if nbytes else None
+        _call("pe_f0_viterbi", logits.data_ptr(), ld_t, ld_n, C, _lib.ptr(lengths), N, T, bins.data_ptr(),
+              _lib.ptr(ws), ws.numel() if ws is not None else 0, _s())
+        path = bins
+    frame_method = _lib.PE_F0_WEIGHTED if method.startswith("weighted") else _lib.PE_F0_ARGMAX
+    _call("pe_f0_decode_frames", logits.data_ptr(), ld_t, ld_n, C, _lib.ptr(lengths), _lib.ptr(path), N, T,
+          frame_method, 0 if path is not None else bins.data_ptr(), f0.data_ptr(), conf.data_ptr(), _s())
+    return (f0[0], conf[0], bins[0]) if squeeze else (f0, conf, bins)
+
+
+def pitch_metrics(f0_pred, f0_ref, threshold_cents=50.0):
+    """float64 device tensor [rms_cents, rpa, rca, vuv_error, n_voiced, n_frames] of a predicted F0 track against a
+    reference, both (n,) float32 device tensors of one length (see ``inference.pitch_metrics``)."""
+    n = _dense(f0_pred, "f0_pred").numel()
+    _chk(n > 0 and _dense(f0_ref, "f0_ref").numel() == n, "pitch_metrics: need two tracks of one non-zero length")
+    _chk(threshold_cents >= 0, "pitch_metrics: threshold_cents must not be negative")
+    out = torch.empty((6,), dtype=torch.float64, device=f0_pred.device)
+    _call("pe_pitch_metrics", f0_pred.data_ptr(), f0_ref.data_ptr(), n, float(threshold_cents), out.data_ptr(), _s())
+    return out
+
+
 def nonfinite_flag(x, flag=None):
     """int32 device scalar: 1 if any element of the flat float32 tensor ``x`` is inf / nan (GradScaler's test)."""
     x = _dense(x, "x")
