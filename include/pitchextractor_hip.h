@@ -447,6 +447,42 @@ int pe_f0_viterbi(const float* logits, long ld_t, long ld_n, int C, const int* l
 int pe_pitch_metrics(const float* f0_pred, const float* f0_ref, long n, double threshold_cents, double* out6,
                      void* stream);
 
+/* ---- F0 tracking: Boersma's autocorrelation method (Praat "Sound: To Pitch (ac)"), ragged batches --------------
+ * config7 = {min_pitch, max_pitch, silence_threshold, voicing_threshold, octave_cost, octave_jump_cost,
+ * voiced_unvoiced_cost} (doubles).  PE_E_ARG: null pointer, sr <= 0, hop <= 0, a non-finite value, min_pitch <= 0,
+ * min_pitch >= min(max_pitch, sr / 2), a non-positive threshold, a negative cost.  PE_E_UNSUPPORTED: an FFT length
+ * (the power of two >= 1.5 x window samples) outside 1024 .. 8192.  Every check runs before any device call.
+ *
+ * pe_f0_track_plan (host only, no device call): row r has n[r] samples at x + x_off[r].  consts8 = {window samples,
+ * period samples, FFT length, lag bound (exclusive), half window, half period, table floats, frames whose
+ * back-pointers stay in LDS}; dconsts2 = {ceiling = min(max_pitch, sr / 2), time step}; meta (n_rows x
+ * pe_f0_track_plan_fields() int64, to be copied to the device) holds each row's sample offset / length, frame count
+ * floor((n / sr - 3 / min_pitch) / time_step) + 1 (0 when the row is shorter than one window), frame prefix offset
+ * and back-pointer spill offset (-1: LDS); t1[r] = centre time of the row's first frame; totals2 = {frames of the
+ * batch, workspace bytes of pe_f0_track_path}.  Frame counts and times are float64 expressions evaluated in one
+ * fixed order (tests/f0_track_ref.py states them).
+ *
+ * tables (device, consts8[6] floats): exp(-2 pi i m / C), m < C = FFT length / 2; exp(-2 pi i k / (2 C)), k <= C;
+ * the Hann window 0.5 - 0.5 cos(2 pi (j + 1) / (window + 1)); its normalised autocorrelation for lags 0 .. half
+ * window.  pe_f0_track_stats: stats[r] = {mean, max |x - mean|}, each row reduced in 64 pieces in a fixed order
+ * through `workspace` (pe_f0_track_stats_workspace_bytes; PE_E_WORKSPACE when too small).  pe_f0_track_frames: per frame g (rows back to
+ * back) up to 15 candidates, cand_f / cand_s [g][15] (Hz, strength; [0] is the unvoiced candidate, voiced ones in
+ * lag order) and their count cand_n[g].  pe_f0_track_path: f0[g] = frequency of the best path's candidate, 0 where
+ * it is unvoiced (frequency 0 or >= ceiling); rows with more than consts8[7] frames keep 16 bytes of back-pointers
+ * per frame in `workspace` (PE_E_WORKSPACE when too small).  host_meta: the host copy of meta. */
+int pe_f0_track_plan_fields(void);
+int pe_f0_track_plan(int n_rows, const long* n, const long* x_off, int sr, int hop, const double* config7,
+                     long* consts8, double* dconsts2, long* meta, double* t1, long* totals2);
+size_t pe_f0_track_stats_workspace_bytes(int n_rows);
+int pe_f0_track_stats(const float* x, const long* meta, int n_rows, float* stats, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int pe_f0_track_frames(const float* x, const long* meta, const long* host_meta, const double* t1,
+                       const float* stats, const float* tables, long n_table, int n_rows, int sr, int hop,
+                       const double* config7, float* cand_f, float* cand_s, int* cand_n, void* stream);
+int pe_f0_track_path(const float* cand_f, const float* cand_s, const int* cand_n, const long* meta,
+                     const long* host_meta, int n_rows, int sr, int hop, const double* config7, float* f0,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,12 @@ PROTOTYPES = {
     "pe_f0_viterbi_workspace_bytes": (_z, [_i, _i, _i]),
     "pe_f0_viterbi": (_i, [_p, _l, _l, _i, _p, _i, _i, _p, _p, _z, _p]),
     "pe_pitch_metrics": (_i, [_p, _p, _l, _d, _p, _p]),
+    "pe_f0_track_plan_fields": (_i, []),
+    "pe_f0_track_plan": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "pe_f0_track_stats_workspace_bytes": (_z, [_i]),
+    "pe_f0_track_stats": (_i, [_p, _p, _i, _p, _p, _z, _p]),
+    "pe_f0_track_frames": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "pe_f0_track_path": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
 }
 
 

@@ -133,6 +133,25 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
     return np.concatenate([f0[i][:min(s + chunk_size, total) - s] for i, s in enumerate(starts)])
 
 
+_TRACKERS = {}
+
+
+def track_f0(wave, *, sr: int, hop_length: int, device="cuda", **config) -> np.ndarray:
+    """F0 contour (Hz, 0 = unvoiced; float32) of one wave at ``sr`` by the on-device Praat-style autocorrelation
+    tracker (``f0_tracker.PraatACTracker``; ``config``: the reference's ``praat`` backend keys).  One value every
+    ``hop_length / sr`` seconds over the frames whose window lies inside the wave -- not the mel frame count:
+    ``pitch_metrics(predict_f0(...), align_length(track_f0(...), L))`` scores a model against it."""
+    from .f0_tracker import PraatACTracker
+    key = (int(sr), int(hop_length), tuple(sorted((k, str(v)) for k, v in config.items())))
+    if key not in _TRACKERS:
+        _TRACKERS[key] = PraatACTracker(sr, hop_length, **config)
+    if isinstance(wave, torch.Tensor):
+        w = wave.detach().reshape(-1).to(device, torch.float32).contiguous()
+    else:
+        w = torch.from_numpy(np.ascontiguousarray(np.asarray(wave, dtype=np.float32).reshape(-1))).to(device)
+    return _TRACKERS[key].track(w)[0]
+
+
 def pitch_metrics(f0_pred, f0_ref, *, threshold_cents: float = 50.0, device="cuda") -> dict:
     """How far a predicted F0 track (Hz, 0 = unvoiced) is from a reference track, over their first ``min(len)``
     frames, reduced on the device.  Device tensors or arrays.  With ``voiced = f0_ref > 0`` and cents re 55 Hz:

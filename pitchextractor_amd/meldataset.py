@@ -12,17 +12,25 @@ to HBM once and ONE launch of the fused mel kernel does framing + FFT + mel + lo
 (meldataset.py:806-816).  All index arithmetic -- segment pre-crop (meldataset.py:178-201), F0
 alignment (f0_backends.py:788-806), crop offsets -- is reproduced exactly and runs on the host.
 
-Out of scope here: the F0 tracker backends and the WORLD-vocoder augmentation need
-packages that are not installable offline.  The pitch-shift augmentation (``synthetic_data.pitch_shift``,
+Out of scope here: the pyworld / CREPE / SwiftF0 tracker backends and the WORLD-vocoder augmentation
+need packages that are not installable offline.  The pitch-shift augmentation (``synthetic_data.pitch_shift``,
 meldataset.py:324-517) runs on the GPU (``pitchextractor_amd.pitch_shift``): workers draw everything the reference
 draws, in its order, and ship the whole base file; the device shifts it and writes only the samples the cropped
-192 mel frames read into the batch row.  F0 labels therefore come from the
-reference's cache files under the reference's own contract (meldataset.py:519-604):
-``<wav>_f0<cache_identifier>.npy`` validated by its sibling ``.json`` (cache_identifier, sample_rate,
-hop_length), then the legacy ``<wav>_f0.npy``; or from an ``f0_provider`` callable.  A cache whose
-metadata does not match is skipped with a warning and left on disk (the reference deletes and
-recomputes it; this build cannot recompute).  An item with no usable label source fails loudly, as the
-reference does when no backend is usable (meldataset.py:80-88).  ``<wav>_mel.npy`` caches
+192 mel frames read into the batch row.  F0 labels come from the reference's cache files under the reference's own
+contract (meldataset.py:519-604): ``<wav>_f0<cache_identifier>.npy`` validated by its sibling ``.json``
+(cache_identifier, sample_rate, hop_length), then the legacy ``<wav>_f0.npy``; or from an ``f0_provider`` callable.
+When the enabled backend chain of ``f0_params`` holds a ``praat`` / ``parselmouth`` entry (method ``ac``), the caches
+need not exist beforehand: ``prepare_f0_caches`` -- run once by ``build_dataloader`` in the main process, before any
+worker starts -- reads every listed file that has no valid cache, resamples it to the dataset rate on the device,
+tracks whole batches of files with the on-device autocorrelation tracker (``pitchextractor_amd.f0_tracker``), applies
+the reference's acceptance rule (fewer than ``bad_f0_threshold`` non-zero frames = that backend failed; every native
+entry failed = empty track) and writes ``.npy`` + ``.json`` as meldataset.py:606-619 does, through temporary names.
+Workers keep reading caches only.  Entries of the chain that need pyworld / CREPE / SwiftF0 are skipped with a
+warning each, as the reference skips a backend whose package is missing.  Existing valid caches are never recomputed,
+overwritten or deleted.  A cache whose metadata does not match is skipped with a warning and left on disk (the
+reference deletes and recomputes it; this build recomputes only under a name that is free).  Without a native entry
+an item with no usable label source fails loudly, as the reference does when no backend is usable
+(meldataset.py:80-88).  ``<wav>_mel.npy`` caches
 (meldataset.py:679-741) are honoured read-only under the reference's rule: whole-file items without
 augmentation whose ``<wav>_mel_meta.json`` equals the expected metadata (audio/dataset sample rate, sample
 count, channel count, mel_params) take their spectrogram from the cache -- normalised on the host with the
@@ -51,6 +59,7 @@ from torch.utils.data import DataLoader
 from typing import NamedTuple
 
 from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS, MelSpectrogram
+from .f0_tracker import NATIVE_TYPES, check_config
 from .pitch_shift import check_res_type, pitch_shift_ragged
 from .resample import RaggedResampler, Resampler
 
@@ -194,14 +203,10 @@ def _enabled(value) -> bool:
     return bool(value)
 
 
-def f0_cache_identifier(f0_params: dict | None) -> str:
-    """The reference's ``F0Extractor.cache_identifier`` (f0_backends.py:661-757) for an ``f0_params``
-    block: "-" + the cache keys of the enabled backends in chain order, joined by "_" (the shipped
-    config.yml -> "-swiftf0").  The reference drops backends whose package is missing on the machine that
-    computed the cache; set ``f0_params['cache_identifier']`` to name such a cache explicitly."""
+def f0_backend_chain(f0_params: dict | None):
+    """The enabled backend chain of an ``f0_params`` block as the reference builds it (f0_backends.py:661-757):
+    list of (normalised name, type, config dict) in chain order."""
     cfg = f0_params or {}
-    if cfg.get("cache_identifier") is not None:
-        return str(cfg["cache_identifier"])
     backends = cfg.get("backends") or {}
     if cfg.get("backend_order"):
         sequence = list(cfg["backend_order"])
@@ -210,7 +215,7 @@ def f0_cache_identifier(f0_params: dict | None) -> str:
     else:
         sequence = [e["name"] for e in _DEFAULT_BACKENDS]
     defaults = {e["name"]: e for e in _DEFAULT_BACKENDS}
-    keys = []
+    chain = []
     for raw in sequence:
         if isinstance(raw, dict):
             entry = dict(raw)
@@ -232,11 +237,26 @@ def f0_cache_identifier(f0_params: dict | None) -> str:
             entry.setdefault("type", entry.get("backend", entry.get("type", name)))
         if not _enabled(entry.get("enabled", True)):
             continue
-        if str(entry.get("type") or entry.get("backend") or "pyworld").lower() not in _BACKEND_TYPES:
+        btype = str(entry.get("type") or entry.get("backend") or "pyworld").lower()
+        if btype not in _BACKEND_TYPES:
             continue
         name = _norm_backend(entry.get("name") or entry.get("type") or "backend")
         bconf = entry.get("config") or {k: v for k, v in entry.items()
                                         if k not in {"name", "type", "backend", "enabled"}}
+        chain.append((name, btype, bconf))
+    return chain
+
+
+def f0_cache_identifier(f0_params: dict | None) -> str:
+    """The reference's ``F0Extractor.cache_identifier`` (f0_backends.py:661-757) for an ``f0_params``
+    block: "-" + the cache keys of the enabled backends in chain order, joined by "_" (the shipped
+    config.yml -> "-swiftf0").  The reference drops backends whose package is missing on the machine that
+    computed the cache; set ``f0_params['cache_identifier']`` to name such a cache explicitly."""
+    cfg = f0_params or {}
+    if cfg.get("cache_identifier") is not None:
+        return str(cfg["cache_identifier"])
+    keys = []
+    for name, _, bconf in f0_backend_chain(cfg):
         suffix = bconf.get("cache_key_suffix") if isinstance(bconf, dict) else None
         keys.append(_norm_backend(f"{name}-{suffix}" if suffix else name))
     return ("-" + "_".join(keys)) if keys else ""
@@ -314,6 +334,10 @@ class MelDataset(torch.utils.data.Dataset):
         self.zero_value = float(self.f0_params.get("zero_fill_value", 0.0))
         self.bad_F0 = int(self.f0_params.get("bad_f0_threshold", 5))
         self.requires_cuda_backend = False
+        # native (on-device) entries of the backend chain: validated now, run by prepare_f0_caches
+        self._f0_chain = f0_backend_chain(self.f0_params)
+        self._native_f0 = [(name, check_config(cfg if isinstance(cfg, dict) else {}, require_method=True))
+                           for name, btype, cfg in self._f0_chain if btype in NATIVE_TYPES]
         self._audio_metadata_cache = {}
         self._invalid_paths = set()
         self._mel_cache_suffix, self._mel_meta_suffix = "_mel.npy", "_mel_meta.json"      # meldataset.py:102-103
@@ -475,20 +499,26 @@ class MelDataset(torch.utils.data.Dataset):
     def _f0_cache_paths(self, path):
         return path + self.f0_cache_suffix, path + self.f0_meta_suffix, path + "_f0.npy"
 
+    def _f0_cache_metadata(self, path):
+        """(metadata of the identifier-named cache or None, the metadata this dataset expects)."""
+        meta_path = self._f0_cache_paths(path)[1]
+        metadata = None
+        if os.path.isfile(meta_path):
+            try:
+                with open(meta_path, "r", encoding="utf-8") as fh:
+                    metadata = json.load(fh)
+            except (OSError, json.JSONDecodeError):
+                metadata = None
+        expected = {"cache_identifier": self.f0_cache_identifier, "sample_rate": int(self.sr),
+                    "hop_length": int(self.mel_params["hop_length"])}
+        return metadata, expected
+
     def _load_cached_f0(self, path):
         """meldataset.py:566-604: the identifier-named cache if its .json agrees on (cache_identifier,
         sample_rate, hop_length); else the legacy ``_f0.npy``; else None.  Nothing is deleted."""
         data_path, meta_path, legacy_path = self._f0_cache_paths(path)
         if os.path.isfile(data_path) and data_path != legacy_path:
-            metadata = None
-            if os.path.isfile(meta_path):
-                try:
-                    with open(meta_path, "r", encoding="utf-8") as fh:
-                        metadata = json.load(fh)
-                except (OSError, json.JSONDecodeError):
-                    metadata = None
-            expected = {"cache_identifier": self.f0_cache_identifier, "sample_rate": int(self.sr),
-                        "hop_length": int(self.mel_params["hop_length"])}
+            metadata, expected = self._f0_cache_metadata(path)
             if metadata and all(metadata.get(k) == v for k, v in expected.items()):
                 try:
                     return np.load(data_path).astype(np.float32)
@@ -505,6 +535,135 @@ class MelDataset(torch.utils.data.Dataset):
                 logger.warning("[MelDataset] unreadable legacy F0 cache %s: skipped", legacy_path)
         return None
 
+    # ---- label pre-pass (meldataset.py:525-564,606-619 for whole files, on the device) ---------------------
+    @property
+    def has_native_f0(self) -> bool:
+        """True when the enabled backend chain holds a ``praat`` / ``parselmouth`` entry this build can run."""
+        return bool(self._native_f0)
+
+    def _save_f0_cache(self, path, f0, backend_name):
+        """meldataset.py:606-619 through temporary names.  After a return or an exception both files exist under their
+        final names or neither does.  The .json goes first: a process killed between the two renames leaves a lone
+        .json, which is not a cache (the loader asks for the .npy first) and is replaced by the next pass."""
+        data_path, meta_path, _ = self._f0_cache_paths(path)
+        metadata = {"cache_identifier": self.f0_cache_identifier, "backend": backend_name,
+                    "sample_rate": int(self.sr), "hop_length": int(self.mel_params["hop_length"])}
+        tmp = [f"{data_path}.tmp{os.getpid()}", f"{meta_path}.tmp{os.getpid()}"]
+        had_meta = os.path.exists(meta_path)
+        placed = False
+        try:
+            with open(tmp[0], "wb") as fh:
+                np.save(fh, np.asarray(f0, dtype=np.float32))
+            with open(tmp[1], "w", encoding="utf-8") as fh:
+                json.dump(metadata, fh, sort_keys=True)
+            os.replace(tmp[1], meta_path)
+            placed = True
+            os.replace(tmp[0], data_path)
+        except BaseException:
+            if placed and not had_meta:                # only what this call put there
+                os.remove(meta_path)
+            raise
+        finally:
+            for t in tmp:
+                if os.path.exists(t):
+                    os.remove(t)
+
+    def files_to_label(self, rank: int = 0, world: int = 1):
+        """Listed files (each once, in list order) of shard ``rank::world`` that have no valid F0 cache and whose
+        cache name is free."""
+        todo = []
+        for path in list(dict.fromkeys(self.data_list))[int(rank)::max(int(world), 1)]:
+            data_path, _, legacy_path = self._f0_cache_paths(path)
+            if os.path.isfile(data_path) and data_path != legacy_path:
+                metadata, expected = self._f0_cache_metadata(path)           # the metadata alone; no array is read
+                if not (metadata and all(metadata.get(k) == v for k, v in expected.items())) and \
+                        not os.path.isfile(legacy_path):
+                    logger.warning("[MelDataset] %s does not match this dataset and is in the way: %s is not labelled",
+                                   data_path, path)
+                continue
+            if os.path.isfile(legacy_path) or os.path.exists(data_path):
+                continue
+            todo.append(path)
+        return todo
+
+    def prepare_f0_caches(self, device="cuda", files_per_batch: int = 16, rank: int = 0, world: int = 1,
+                          tracker_factory=None):
+        """Label every listed file without a valid cache with the native backend chain and write its cache.
+        Whole files are read, packed, resampled to ``self.sr`` in one ragged launch per batch and tracked in a fixed
+        number of launches per batch.  ``tracker_factory(sr, hop, **config)`` (default ``PraatACTracker``) lets a
+        test substitute a stub.  Returns the files labelled."""
+        if not self._native_f0:
+            raise RuntimeError("prepare_f0_caches: f0_params enables no praat / parselmouth backend; the other "
+                               "backends are outside this build")
+        for name, btype, _ in self._f0_chain:
+            if btype not in NATIVE_TYPES:
+                logger.warning("[MelDataset] F0 backend '%s' (%s) is not part of this build: skipped", name, btype)
+        todo = self.files_to_label(rank, world)
+        if not todo:
+            return []
+        if tracker_factory is None:
+            from .f0_tracker import PraatACTracker as tracker_factory
+        hop = int(self.mel_params["hop_length"])
+        trackers = [(name, tracker_factory(self.sr, hop, **cfg)) for name, cfg in self._native_f0]
+        resampler = RaggedResampler(self.sr)
+        done = []
+        for lo in range(0, len(todo), max(int(files_per_batch), 1)):
+            paths, waves, rates = [], [], []
+            for path in todo[lo:lo + max(int(files_per_batch), 1)]:
+                try:
+                    wave, wave_sr = read_wav(path)
+                except (RuntimeError, OSError, ValueError, struct.error) as exc:
+                    logger.warning("[MelDataset] Skipping unreadable audio file: %s (%s)", path, exc)
+                    continue
+                if wave.ndim > 1:
+                    wave = np.mean(wave, axis=-1)
+                paths.append(path)
+                waves.append(np.ascontiguousarray(wave, dtype=np.float32))
+                rates.append(int(wave_sr))
+            if not paths:
+                continue
+            lengths = [int(w.shape[0]) for w in waves]
+            flat = torch.from_numpy(np.concatenate(waves)).to(device)
+            if any(r != self.sr for r in rates):
+                flat, _ = resampler(flat, rates, lengths)                  # (B, width), each row at its own rate
+                lengths = [resampler.out_len(r, n) for r, n in zip(rates, lengths)]
+            result = [(np.zeros((0,), dtype=np.float32), "")] * len(paths)
+            pending = list(range(len(paths)))
+            for name, tracker in trackers:
+                if not pending:
+                    break
+                if flat.dim() == 2:
+                    sub, sub_len = flat[pending].contiguous(), [lengths[i] for i in pending]
+                elif len(pending) == len(paths):
+                    sub, sub_len = flat, lengths
+                else:
+                    off = np.concatenate([[0], np.cumsum(lengths)])
+                    sub = torch.cat([flat[off[i]:off[i + 1]] for i in pending])
+                    sub_len = [lengths[i] for i in pending]
+                contours = tracker.track(sub, sub_len)
+                still = []
+                for i, f0 in zip(pending, contours):
+                    f0 = np.asarray(f0, dtype=np.float32)
+                    if np.count_nonzero(f0) < self.bad_F0:                 # f0_backends.py:776-782
+                        logger.warning("Backend '%s' returned only %d voiced frames for %s; attempting next backend.",
+                                       name, int(np.count_nonzero(f0)), paths[i])
+                        still.append(i)
+                    else:
+                        result[i] = (f0, name)
+                pending = still
+            for i in pending:
+                logger.warning("All configured F0 backends failed for %s", paths[i])
+            for path, (f0, name) in zip(paths, result):
+                try:
+                    self._save_f0_cache(path, f0, name)
+                    done.append(path)
+                except OSError as exc:
+                    logger.warning("Failed to cache F0 for %s: %s", path, exc)
+        if self.verbose:
+            print(f"[MelDataset] F0 labels written for {len(done)} file(s) "
+                  f"(backends: {', '.join(n for n, _ in self._native_f0)})")
+        return done
+
     def _f0_for(self, path, waveform, start_sample, expected_frames):
         cached = self._load_cached_f0(path)
         if cached is not None:
@@ -518,8 +677,8 @@ class MelDataset(torch.utils.data.Dataset):
         if self.f0_provider is not None:
             return np.asarray(self.f0_provider(path, waveform, self.sr), dtype=np.float32)
         raise RuntimeError(f"no F0 labels for {path}: no valid '{os.path.basename(path)}{self.f0_cache_suffix}' "
-                           "(+ .json) cache, no legacy '_f0.npy' and no f0_provider (the reference's tracker "
-                           "backends are outside this build)")
+                           "(+ .json) cache, no legacy '_f0.npy' and no f0_provider (of the reference's tracker "
+                           "backends only praat / parselmouth with method 'ac' is part of this build)")
 
     # ---- cached spectrograms (meldataset.py:679-741), read-only ------------------------------
     def _build_mel_metadata(self, num_samples: int, wave_sr: int) -> dict:
@@ -866,6 +1025,14 @@ def build_dataloader(path_list, validation=False, batch_size=4, num_workers=1, d
         raise RuntimeError("build_dataloader (HIP path): device must be a HIP ('cuda') device; the mel stage has "
                            "no CPU fallback")
     dataset = MelDataset(path_list, validation=validation, **dataset_config)
+    if dataset.has_native_f0:
+        # label pass: once, in this process, before any worker exists (workers only ever read caches); in
+        # data-parallel runs every rank labels its share of the files and the ranks meet before the first batch
+        rank, world = (int(shard[0]), int(shard[1])) if shard is not None else (0, 1)
+        dataset.prepare_f0_caches(device, files_per_batch=int(dataloader_options.get("f0_files_per_batch", 16)),
+                                  rank=rank, world=world)
+        if world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.barrier()
     collate_fn = Collater(**(collate_config or {}))
     kwargs = dict(batch_size=batch_size, shuffle=(not validation), num_workers=num_workers,
                   drop_last=(not validation), collate_fn=collate_fn, pin_memory=True)
