@@ -175,6 +175,19 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+_tables = {}
+
+
+def device_table(key, device, build):
+    """Device copy of the float32 table that ``build()`` returns (numpy), made once per (key, device)."""
+    import numpy as np
+    import torch
+    k = (key, str(device))
+    if k not in _tables:
+        _tables[k] = torch.from_numpy(np.ascontiguousarray(build(), dtype=np.float32)).to(device)
+    return _tables[k]
+
+
 def stream_ptr() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream

@@ -10,16 +10,19 @@
 //      then max |x - mean| per piece and per row (three small launches).
 //   2. frames: one workgroup per (row, frame), found by a binary search over the frame offsets.  The window is staged
 //      from HBM once into LDS; local mean and peak; Hann window; the real FFT runs as a packed half-length complex
-//      radix-4 Stockham FFT in place in LDS (each thread holds its butterflies' inputs in registers across the
-//      barrier); power spectrum; inverse transform; r[lag] = ac[lag] / (ac[0] window_r[lag]); ordered compaction of
-//      the local maxima; parabolic vertex + depth-30 sinc strength one maximum per thread; the best 14 by rank;
-//      depth-70 sinc refinement one candidate per 16-lane group, evaluated in double.
+//      radix-4 Stockham FFT in place in LDS (fft_lds, dsp.h; each thread holds its butterflies' inputs in registers
+//      across the barrier); power spectrum; inverse transform; r[lag] = ac[lag] / (ac[0] window_r[lag]); ordered
+//      compaction of the local maxima; parabolic vertex + depth-30 sinc strength one maximum per thread; the best 14
+//      by rank; depth-70 sinc refinement one candidate per 16-lane group, evaluated in double.
 //   3. path:   one wave per row walks the frames (15 x 15 transitions per step); back-pointers are one byte per
 //      candidate, in LDS (sized by the batch's longest row that fits) and in the caller's workspace otherwise.  This pass is a chain of
 //      dependent steps: it is latency-bound by construction.
 // No atomics, no cross-workgroup communication: a row's result does not depend on the batch around it.
 #include <math.h>
 #include "common.h"
+#include "dsp.h"
+
+using namespace pe;
 
 namespace {
 
@@ -103,22 +106,6 @@ void frame_layout(long n, const TrackConsts& k, double minp, long* frames, doubl
   *t1 = d + k.dt / 2.0;
 }
 
-__device__ __forceinline__ int find_row(const long* __restrict__ meta, int n_rows, long g) {
-  int lo = 0, hi = n_rows - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (meta[(long)mid * T_K + T_FOFF] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 conj2(float2 a) { return make_float2(a.x, -a.y); }
-
 // ---- 1. per-row statistics -------------------------------------------------------------------------------------------
 // A row is cut into kChunks equal pieces (by its own length only, so the result does not depend on the batch); one
 // workgroup per (row, piece).  Partial sums are doubles added in a fixed order; no atomics.
@@ -182,73 +169,6 @@ __global__ __launch_bounds__(kThreads) void f0_peak_final_kernel(const float* __
 }
 
 // ---- 2. frames ---------------------------------------------------------------------------------------------------------
-// In-place C-point complex FFT of the workgroup's LDS buffer: radix-4 Stockham passes and one radix-2 pass when
-// log2 C is odd (natural order in and out).  Every thread reads all inputs of its butterflies, the workgroup meets at
-// a barrier, then it writes: one buffer suffices.
-template <int LOG2C, bool INV>
-__device__ __forceinline__ void fft_block(float2* buf, const float2* __restrict__ tw, int tid) {
-  constexpr int C = 1 << LOG2C, P4 = LOG2C / 2;
-  constexpr int NB4 = (C / 4 + kThreads - 1) / kThreads;
-#pragma unroll
-  for (int p = 0; p < P4; ++p) {
-    const int ns = 1 << (2 * p), shift = LOG2C - 2 - 2 * p;        // twiddle index r k C / (4 ns)
-    float2 v[NB4][4];
-#pragma unroll
-    for (int b = 0; b < NB4; ++b) {
-      const int j = tid + kThreads * b;
-      if (j < C / 4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[b][r] = buf[j + (C / 4) * r];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < NB4; ++b) {
-      const int j = tid + kThreads * b;
-      if (j < C / 4) {
-        const int k = j & (ns - 1);
-#pragma unroll
-        for (int r = 1; r < 4; ++r) {
-          const float2 w = tw[(r * k) << shift];
-          v[b][r] = cmul(v[b][r], INV ? conj2(w) : w);
-        }
-        const float2 t0 = cadd(v[b][0], v[b][2]), t1 = csub(v[b][0], v[b][2]), t2 = cadd(v[b][1], v[b][3]);
-        const float2 d = csub(v[b][1], v[b][3]);
-        const float2 t3 = INV ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);
-        const int o = ((j >> (2 * p)) << (2 * p + 2)) + k;
-        buf[o] = cadd(t0, t2);
-        buf[o + ns] = cadd(t1, t3);
-        buf[o + 2 * ns] = csub(t0, t2);
-        buf[o + 3 * ns] = csub(t1, t3);
-      }
-    }
-    __syncthreads();
-  }
-  if (LOG2C & 1) {                                                  // last pass, ns = C / 2: out index = in index
-    constexpr int NB2 = (C / 2 + kThreads - 1) / kThreads;
-    float2 a[NB2], b2[NB2];
-#pragma unroll
-    for (int b = 0; b < NB2; ++b) {
-      const int j = tid + kThreads * b;
-      if (j < C / 2) {
-        const float2 w = tw[j];
-        a[b] = buf[j];
-        b2[b] = cmul(buf[j + C / 2], INV ? conj2(w) : w);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < NB2; ++b) {
-      const int j = tid + kThreads * b;
-      if (j < C / 2) {
-        buf[j] = cadd(a[b], b2[b]);
-        buf[j + C / 2] = csub(a[b], b2[b]);
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // Sinc interpolation of the symmetric r (r[-k] = r[k], known for |k| <= hw) at x > 0 with a raised-cosine taper that
 // reaches zero one sample beyond `depth` taps on either side (Praat's NUM_interpolate_sinc):
 //   sum over taps at distance d of r[tap] * sin(pi d) / (pi d) * (0.5 + 0.5 cos(pi d / (d_nearest + depth))).
@@ -377,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __rest
   const float srf = (float)K.sr;
 
   for (long g = blockIdx.x; g < total; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, g);
+    const int row = find_row(meta, n_rows, T_K, T_FOFF, g);
     const long* m = meta + (long)row * T_K;
     const long n = m[T_N];
     const float* xr = x + m[T_XOFF];
@@ -421,7 +341,7 @@ __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __rest
     }
     for (int j = tid; j < nw; j += kThreads) fb[j] = (fb[j] - lmean) * win[j];
     __syncthreads();
-    fft_block<LOG2C, false>(s_buf, tw, tid);
+    fft_lds<LOG2C, false, kThreads>(s_buf, tw, tid);
 
     // power spectrum of the N-point real transform, bins 0 .. C
     float p[NQ], pC = 0.f;
@@ -429,9 +349,8 @@ __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __rest
     for (int q = 0; q < NQ; ++q) {
       const int k = tid + kThreads * q;
       const float2 zk = s_buf[k], zc = conj2(s_buf[(C - k) & (C - 1)]);
-      const float2 e = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-      const float2 dd = csub(zk, zc);
-      const float2 o = make_float2(0.5f * dd.y, -0.5f * dd.x);
+      float2 e, o;
+      real_fft_split(zk, zc, e, o);
       const float2 X = cadd(e, cmul(tr[k], o));
       p[q] = X.x * X.x + X.y * X.y;
       if (k == 0) {                                                 // bin C: E - O
@@ -458,7 +377,7 @@ __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __rest
 #pragma unroll
     for (int q = 0; q < NQ; ++q) s_buf[tid + kThreads * q] = y[q];
     __syncthreads();
-    fft_block<LOG2C, true>(s_buf, tw, tid);
+    fft_lds<LOG2C, true, kThreads>(s_buf, tw, tid);
 
     // r[lag] = ac[lag] / (ac[0] window_r[lag]), lag 0 .. hw; the transform's scale cancels
     const float ac0 = fb[0];

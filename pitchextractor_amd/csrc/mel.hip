@@ -16,6 +16,9 @@
 #include <string.h>
 #include <vector>
 #include "common.h"
+#include "dsp.h"
+
+using namespace pe;
 
 namespace {
 
@@ -47,14 +50,6 @@ struct MelArgs {
   const int* frame_start;      // optional [batch]: output frame t shows source frame t + frame_start[b]
 };
 
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-// multiply by -i
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }
-
 __device__ __forceinline__ void fft4(const float2 u0, const float2 u1, const float2 u2, const float2 u3,
                                      float2& o0, float2& o1, float2& o2, float2& o3) {
   const float2 t0 = cadd(u0, u2), t1 = csub(u0, u2), t2 = cadd(u1, u3), t3 = mul_mi(csub(u1, u3));
@@ -72,16 +67,6 @@ __device__ __forceinline__ void fft8(float2 (&v)[8]) {
   const float2 d3 = make_float2(c * (e3.y - e3.x), -c * (e3.x + e3.y));
   fft4(s0, s1, s2, s3, v[0], v[2], v[4], v[6]);
   fft4(d0, d1, d2, d3, v[1], v[3], v[5], v[7]);
-}
-
-// The 4 waves of a workgroup share only read-only LDS (audio chunk, filterbank); the exchange
-// regions A/B/P are private to a wave, and one wave's DS instructions execute in program order, so
-// the passes below need no s_barrier -- only a compiler fence that keeps LDS writes ahead of the
-// dependent LDS reads (waves then drift freely instead of marching in lockstep).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Persistent form: the grid is sized to the chip (4 workgroups per CU fit: 29 KB of LDS, 126 VGPRs) and every

@@ -10,7 +10,7 @@
 // (its phase is a running sum), nothing after it is needed.
 //
 //   1. STFT: one wave per frame; the 2048 real samples are packed as 1024 complex points and run through five radix-4
-//      Stockham passes in LDS, then split into the 1025 bins of the real transform.
+//      Stockham passes in LDS (fft_lds, dsp.h), then split into the 1025 bins of the real transform.
 //   2. Phase vocoder: one lane per (row, bin) walks the output columns.  The phase advance of bin k per column is
 //      k * pi / 2 exactly, so the accumulated phase is carried as an integer quarter-turn count (t * k) mod 4 plus an
 //      fp32 residual reduced to [-pi, pi) every column; a plain fp32 running phase grows to 1e5-1e6 rad on long files.
@@ -22,13 +22,18 @@
 #include <float.h>
 #include <math.h>
 #include "common.h"
+#include "dsp.h"
+
+using namespace pe;
 
 namespace {
 
 constexpr int kN = 2048;          // n_fft
 constexpr int kHop = 512;
 constexpr int kBins = kN / 2 + 1;
-constexpr int kC = kN / 2;         // complex FFT length
+constexpr int kLog2C = 10;
+constexpr int kC = 1 << kLog2C;    // complex FFT length kN / 2; one wave per transform: fft_lds<kLog2C, INV, 64>
+static_assert(2 * kC == kN, "the real frame is packed as kN / 2 complex points");
 constexpr int kP = 512;           // resampy table precision 2^9
 constexpr int kMaxRows = 65535;
 constexpr float kPi = 3.14159265358979323846f;
@@ -40,30 +45,6 @@ enum {
   M_N, M_XOFF, M_FUSE, M_FOFF, M_CLO, M_CHI, M_COFF, M_M, M_NOLA, M_SLO, M_SHI, M_SOFF, M_NRES, M_JLO, M_JCNT,
   M_JOFF, M_OOFF, M_NCOLS, M_K
 };
-
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 conj2(float2 a) { return make_float2(a.x, -a.y); }
-
-// A wave's LDS region is private to it and its DS instructions execute in program order: a compiler fence is enough.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// largest row whose prefix offset meta[row][field] <= g (rows with no work share the next row's offset)
-__device__ __forceinline__ int find_row(const long* __restrict__ meta, int n_rows, int field, long g) {
-  int lo = 0, hi = n_rows - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (meta[(long)mid * M_K + field] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // block-shared tables: 1024th roots of unity (forward sign), 2048th roots for the real split, Hann window
 __device__ void init_tables(float2* s_tw, float2* s_tr, float* s_win) {
@@ -81,40 +62,6 @@ __device__ void init_tables(float2* s_tw, float2* s_tr, float* s_win) {
     for (int i = threadIdx.x; i < kN; i += blockDim.x) s_win[i] = (float)(0.5 - 0.5 * cospi(2.0 * i / kN));
 }
 
-// In-place 1024-point complex FFT of one wave's LDS buffer: five radix-4 Stockham passes (natural order in and out).
-// Each lane owns butterflies j = lane + 64 b; it reads all 16 inputs before any write, so one buffer suffices.
-template <bool INV>
-__device__ __forceinline__ void fft1024(float2* buf, const float2* tw, int lane) {
-#pragma unroll
-  for (int p = 0; p < 5; ++p) {
-    const int ns = 1 << (2 * p), shift = 8 - 2 * p;      // twiddle index m = r k 256 / ns
-    float2 v[4][4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[b][r] = buf[lane + 64 * b + 256 * r];
-    wave_lds_sync();
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int j = lane + 64 * b, k = j & (ns - 1);
-#pragma unroll
-      for (int r = 1; r < 4; ++r) {
-        const float2 w = tw[(r * k) << shift];
-        v[b][r] = cmul(v[b][r], INV ? conj2(w) : w);
-      }
-      const float2 t0 = cadd(v[b][0], v[b][2]), t1 = csub(v[b][0], v[b][2]), t2 = cadd(v[b][1], v[b][3]);
-      const float2 d = csub(v[b][1], v[b][3]);
-      const float2 t3 = INV ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);      // * (+i) / * (-i)
-      const int o = ((j >> (2 * p)) << (2 * p + 2)) + k;
-      buf[o] = cadd(t0, t2);
-      buf[o + ns] = cadd(t1, t3);
-      buf[o + 2 * ns] = csub(t0, t2);
-      buf[o + 3 * ns] = csub(t1, t3);
-    }
-    wave_lds_sync();
-  }
-}
-
 // ---- 1. STFT ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ps_stft_kernel(const float* __restrict__ x, const long* __restrict__ meta,
                                                       int n_rows, long total, float2* __restrict__ spec) {
@@ -127,7 +74,7 @@ __global__ __launch_bounds__(256) void ps_stft_kernel(const float* __restrict__ 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float2* buf = s_buf[wv];
   for (long g = (long)blockIdx.x * 4 + wv; g < total; g += (long)gridDim.x * 4) {
-    const int row = find_row(meta, n_rows, M_FOFF, g);
+    const int row = find_row(meta, n_rows, M_K, M_FOFF, g);
     const long* m = meta + (long)row * M_K;
     const long f = g - m[M_FOFF], n = m[M_N];
     const float* xr = x + m[M_XOFF];
@@ -141,16 +88,15 @@ __global__ __launch_bounds__(256) void ps_stft_kernel(const float* __restrict__ 
       buf[i >> 1] = make_float2(v0 * s_win[i], v1 * s_win[i + 1]);
     }
     wave_lds_sync();
-    fft1024<false>(buf, s_tw, lane);
+    fft_lds<kLog2C, false, 64>(buf, s_tw, lane);
     float2* out = spec + g * kBins;
 #pragma unroll
     for (int q = 0; q < 17; ++q) {
       const int k = lane + 64 * q;
       if (k > kC) break;
       const float2 zk = buf[k & (kC - 1)], zc = conj2(buf[(kC - k) & (kC - 1)]);
-      const float2 e = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-      const float2 dd = csub(zk, zc);
-      const float2 o = make_float2(0.5f * dd.y, -0.5f * dd.x);                    // (zk - zc) / 2i
+      float2 e, o;
+      real_fft_split(zk, zc, e, o);
       out[k] = cadd(e, cmul(s_tr[k], o));
     }
     wave_lds_sync();                                      // buffer reads done before the next frame's writes
@@ -234,7 +180,7 @@ __global__ __launch_bounds__(256) void ps_irfft_kernel(const float2* __restrict_
       buf[k] = make_float2(e.x - o.y, e.y + o.x);           // E + i O
     }
     wave_lds_sync();
-    fft1024<true>(buf, s_tw, lane);
+    fft_lds<kLog2C, true, 64>(buf, s_tw, lane);
     float* out = frames + g * kN;
     constexpr float inv = 1.f / kC;
 #pragma unroll
@@ -256,7 +202,7 @@ __global__ __launch_bounds__(256) void ps_ola_kernel(const float* __restrict__ f
   }
   __syncthreads();
   for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long)gridDim.x * 256) {
-    const int row = find_row(meta, n_rows, M_SOFF, g);
+    const int row = find_row(meta, n_rows, M_K, M_SOFF, g);
     const long* m = meta + (long)row * M_K;
     const long p = m[M_SLO] + (g - m[M_SOFF]) + kN / 2;    // position in the overlap-add buffer (centre dropped)
     const long n_ola = m[M_NOLA], c_lo = m[M_CLO], c_hi = m[M_CHI];
@@ -282,7 +228,7 @@ __global__ __launch_bounds__(256) void ps_resample_kernel(const float* __restric
                                                           const float* __restrict__ noise, int n_rows, long total,
                                                           float* __restrict__ out) {
   for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long)gridDim.x * 256) {
-    const int row = find_row(meta, n_rows, M_JOFF, g);
+    const int row = find_row(meta, n_rows, M_K, M_JOFF, g);
     const long* m = meta + (long)row * M_K;
     const long i = g - m[M_JOFF], j = m[M_JLO] + i;
     float v = 0.f;

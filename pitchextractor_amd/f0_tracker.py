@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ragged import packed_offsets, row_layout
 
 logger = logging.getLogger(__name__)
 
@@ -67,7 +68,6 @@ class PraatACTracker:
         self.sr, self.hop_length = int(sr), int(hop_length)
         self.config = check_config(config)
         self._cfg = np.array([self.config[k] for k in _CONFIG_ORDER], dtype=np.float64)
-        self._tables = {}
         # the constants of the configuration (host only): also validates (sr, hop, config) against the kernels' range
         plan = self.plan([0])
         (self.nsamp_window, self.nsamp_period, self.n_fft, self.max_lag, self.half_window, self.half_period,
@@ -84,7 +84,7 @@ class PraatACTracker:
         lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
         R = lengths.size
         if offsets is None:
-            offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]) if R else np.zeros(0)
+            offsets = packed_offsets(lengths)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         if offsets.size != R:
             raise ValueError("f0 tracker: one offset per row")
@@ -122,12 +122,6 @@ class PraatACTracker:
         assert out.size == self.n_table
         return out
 
-    def _device_tables(self, device):
-        key = str(device)
-        if key not in self._tables:
-            self._tables[key] = torch.from_numpy(self.host_tables()).to(device)
-        return self._tables[key]
-
     # ---- device side --------------------------------------------------------------------------------------------
     def track(self, waves: torch.Tensor, lengths=None, *, return_candidates: bool = False):
         """``waves``: float32 device audio at ``sr``: one 1-D wave, rows packed back to back in a 1-D tensor
@@ -137,17 +131,7 @@ class PraatACTracker:
         if not isinstance(waves, torch.Tensor) or not waves.is_cuda or waves.dtype != torch.float32 or \
                 waves.dim() not in (1, 2) or waves.stride(-1) != 1:
             raise RuntimeError("PraatACTracker (HIP) needs contiguous-row float32 device audio; no CPU fallback exists")
-        if waves.dim() == 2:
-            B = waves.shape[0]
-            lengths = [int(waves.shape[1])] * B if lengths is None else [int(n) for n in lengths]
-            if len(lengths) != B or any(n < 0 or n > waves.shape[1] for n in lengths):
-                raise ValueError("f0 tracker: one length per row, at most the padded width")
-            offsets = [r * waves.stride(0) for r in range(B)]
-        else:
-            lengths = [int(waves.numel())] if lengths is None else [int(n) for n in lengths]
-            if any(n < 0 for n in lengths) or sum(lengths) > waves.numel():
-                raise ValueError("f0 tracker: packed row lengths exceed the input")
-            offsets = None
+        lengths, offsets = row_layout(waves, lengths, whole_by_default=True)
         pl = self.plan(lengths, offsets)
         R, G = pl["n_rows"], pl["n_frames"]
         dev = waves.device
@@ -160,7 +144,7 @@ class PraatACTracker:
             meta = torch.from_numpy(meta_h).to(dev)
             t1 = torch.from_numpy(t1_h).to(dev)
             stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
-            tables = self._device_tables(dev)
+            tables = _lib.device_table(("f0_track", self.n_fft, self.nsamp_window), dev, self.host_tables)
             ws_bytes = pl["workspace_bytes"]
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
             cfg = self._cfg.ctypes.data

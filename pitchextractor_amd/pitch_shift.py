@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ragged import packed_offsets
 
 N_FFT, HOP = 2048, 512
 N_BINS = N_FFT // 2 + 1
@@ -82,7 +83,7 @@ class Plan:
         self.res_type = check_res_type(res_type)
         self.lengths = lengths
         self.n_steps = np.ascontiguousarray(n_steps, dtype=np.float32).reshape(-1)
-        self.x_offsets = (np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64) if x_offsets is None
+        self.x_offsets = (packed_offsets(lengths) if x_offsets is None
                           else np.ascontiguousarray(x_offsets, dtype=np.int64).reshape(-1))
         self.out_start = np.zeros(R, np.int64) if out_start is None else np.ascontiguousarray(out_start, np.int64)
         self.out_len = lengths.copy() if out_len is None else np.ascontiguousarray(out_len, np.int64)
@@ -105,19 +106,15 @@ class Plan:
 
 
 class PitchShifter:
-    """Holds the device copies of the resampling filters; ``run`` executes the four stages for a ``Plan``."""
-
-    def __init__(self):
-        self._tables = {}
+    """``table``: the device copy of a resampling filter; ``run`` executes the four stages for a ``Plan``."""
 
     def table(self, res_type, device):
-        key = (res_type, str(device))
-        if key not in self._tables:
+        def build():                                      # the filter's right wing, then its forward differences
             w = resample_filter(res_type)
             d = np.zeros_like(w)
             d[:-1] = np.diff(w)
-            self._tables[key] = torch.from_numpy(np.concatenate([w, d]).astype(np.float32)).to(device)
-        return self._tables[key]
+            return np.concatenate([w, d])
+        return _lib.device_table(("resampy", res_type), device, build)
 
     def run(self, plan: Plan, waves, gains, out, noise=None, keep=False, spec=None):
         """waves: flat float32 device audio addressed by the plan's x offsets; gains (R,) float32 device; out: float32

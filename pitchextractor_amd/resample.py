@@ -9,6 +9,7 @@ import math
 import torch
 
 from . import _lib, ops
+from .ragged import row_layout
 
 
 class Resampler:
@@ -96,25 +97,10 @@ class RaggedResampler:
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2) or x.stride(-1) != 1:
             raise RuntimeError("RaggedResampler (HIP) needs contiguous-row float32 device audio; no CPU fallback exists")
         rates = [int(r) for r in rates]
+        lengths, offsets = row_layout(x, lengths)
         B = len(rates)
-        if x.dim() == 2:
-            if x.shape[0] != B:
-                raise ValueError("one rate per row")
-            lengths = [int(x.shape[1])] * B if lengths is None else [int(n) for n in lengths]
-            offsets = [r * x.stride(0) for r in range(B)]
-            if any(n > x.shape[1] for n in lengths):
-                raise ValueError("a row length exceeds the padded width")
-        else:
-            if lengths is None:
-                raise ValueError("packed rows need their lengths")
-            lengths = [int(n) for n in lengths]
-            offsets = [0] * B
-            for r in range(1, B):
-                offsets[r] = offsets[r - 1] + lengths[r - 1]
-            if B and offsets[-1] + lengths[-1] > x.numel():
-                raise ValueError("packed row lengths exceed the input")
-        if len(lengths) != B or any(n < 0 for n in lengths):
-            raise ValueError("one non-negative length per row")
+        if len(lengths) != B:
+            raise ValueError("one rate per row")
         distinct = tuple(sorted(set(rates)))
         index = {r: k for k, r in enumerate(distinct)}
         ridx = [index[r] for r in rates]

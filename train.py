@@ -158,6 +158,8 @@ def main(config_path):
                     writer.add_scalar(key, value, epoch)
             if (epoch % save_freq) == 0:
                 trainer.save_checkpoint(osp.join(log_dir, "epoch_%05d.pth" % epoch))
+    if dp_on:                                       # as bench.py does: RCCL's watchdog must not outlive the runtime
+        torch.distributed.destroy_process_group()
     return 0
 
 
