@@ -416,6 +416,38 @@ int pe_pitch_shift_resample(const float* stretched, const long* meta, const doub
                             int res_type, const float* gains, const float* noise, int n_rows, long n_out, float* out,
                             void* stream);
 
+/* ---- WORLD vocoder synthesis (reference Utils/synthetic.py:194-220 -> pyworld.synthesize, WORLD's Synthesis) ----
+ * One minimum-phase impulse response of fft_size samples per glottal pulse, overlap-added; fft_size 512 / 1024 / 2048
+ * (another power of two is PE_E_UNSUPPORTED, anything else PE_E_ARG).  The pulse positions are a sequential float64
+ * recurrence and come from the host (pitchextractor_amd/world.py: time_base).
+ * pe_world_plan (host only, no device call) lays out a ragged batch: row r has n_frames[r] frames (f0, nullable: the
+ * rows' curves back to back, checked to be finite) and pulse_cnt[r] pulses, the rows' tables back to back in index
+ * (sample, strictly increasing, inside the row's int(n_frames * frame_period_ms * fs / 1000) samples, consecutive
+ * pulses at most fft_size apart), shift (seconds, 0 <= shift * fs <= 1) and voiced.  Frame f of the row's spectral
+ * envelope is the fft_size / 2 + 1 floats at sp + sp_off[r] + f * sp_stride[r]; a stride of 0 broadcasts one template to
+ * every frame.  ap likewise (ap_off NULL or ap_off[r] < 0: all zeros).  The aperiodic noise of the row is the standard
+ * normals at noise + noise_off[r], one per sample of the row (noise_off NULL or < 0: drawn in the kernel, Philox4x32-10
+ * keyed by (seeds[r], sample) and Box-Muller).  Output samples [j_lo[r], j_lo[r] + j_cnt[r]) go to
+ * out + out_row[r] * out_stride (out_stride >= j_cnt[r]).  Only pulses whose response meets the window are planned.
+ * The plan fills meta (n_rows x pe_world_plan_fields() int64), pulses (planned pulses x 6 int64: sample, the two
+ * frames, noise samples, voiced, row), pulse_f (planned pulses x {frame fraction, shift * fs}; size both for the
+ * batch's pulse count) and totals {planned pulses, output samples}.
+ * pe_world_responses: responses (planned pulses x fft_size floats), one workgroup per pulse; table: exp(-2 pi i m /
+ * fft_size) for m < fft_size (re, im), then the fft_size floats of WORLD's DC remover.
+ * pe_world_overlap_add: out = gains[r] * sum of the responses covering the sample, in ascending pulse order (no
+ * atomics: a row is bit-identical alone and in any batch) + out_noise (optional, laid out like the output windows). */
+int pe_world_plan_fields(void);
+int pe_world_plan(int n_rows, const long* n_frames, const double* f0, const long* pulse_cnt, const long* index,
+                  const double* shift, const unsigned char* voiced, const long* sp_off, const long* sp_stride,
+                  const long* ap_off, const long* ap_stride, const long* noise_off, const long* seeds,
+                  const long* j_lo, const long* j_cnt, const long* out_row, long out_stride, double fs,
+                  double frame_period_ms, int fft_size, long* meta, long* pulses, double* pulse_f, long* totals);
+int pe_world_responses(const float* sp, const float* ap, const float* noise, const long* meta, const long* pulses,
+                       const double* pulse_f, const float* table, int n_rows, long n_pulses, int fft_size,
+                       float* responses, void* stream);
+int pe_world_overlap_add(const float* responses, const long* meta, const long* pulses, const float* gains,
+                         const float* out_noise, int n_rows, long n_out, int fft_size, float* out, void* stream);
+
 /* ---- F0 bin decoding (build-defined; the inverse of pe_f0_bins_ce_loss) and pitch metrics --------------------
  * logits: N sequences of T frames of C bins, frame (n, t) at logits + n * ld_n + t * ld_t (2 <= C <= 1024, more is
  * PE_E_UNSUPPORTED).  Bin b stands for cents(b) = 20 b + 1997.3794084376191, f(b) = 10 * 2^(cents(b) / 1200) Hz.

@@ -120,6 +120,11 @@ PROTOTYPES = {
     "pe_pitch_shift_vocoder": (_i, [_p, _p, _p, _i, _l, _p, _p]),
     "pe_pitch_shift_istft": (_i, [_p, _p, _i, _l, _l, _p, _p, _p]),
     "pe_pitch_shift_resample": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _l, _p, _p]),
+    "pe_world_plan_fields": (_i, []),
+    "pe_world_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _d, _d, _i, _p, _p, _p,
+                           _p]),
+    "pe_world_responses": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _p, _p]),
+    "pe_world_overlap_add": (_i, [_p, _p, _p, _p, _p, _i, _l, _i, _p, _p]),
     "pe_f0_bins_ce_workspace_bytes": (_z, [_l]),
     "pe_f0_bins_ce_loss": (_i, [_p, _l, _i, _p, _p, _p, _f, _l, _f, _p, _p, _l, _p, _p, _z, _p]),
     "pe_nonfinite_flag": (_i, [_p, _l, _p, _p]),

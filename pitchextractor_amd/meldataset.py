@@ -12,8 +12,13 @@ to HBM once and ONE launch of the fused mel kernel does framing + FFT + mel + lo
 (meldataset.py:806-816).  All index arithmetic -- segment pre-crop (meldataset.py:178-201), F0
 alignment (f0_backends.py:788-806), crop offsets -- is reproduced exactly and runs on the host.
 
-Out of scope here: the pyworld / CREPE / SwiftF0 tracker backends and the WORLD-vocoder augmentation
-need packages that are not installable offline.  The pitch-shift augmentation (``synthetic_data.pitch_shift``,
+Out of scope here: the pyworld / CREPE / SwiftF0 tracker backends need packages that are not
+installable offline.  The WORLD-vocoder augmentation (``synthetic_data.world_vocoder``, Utils/synthetic.py) runs on the
+GPU when its block carries ``backend: hip`` (``pitchextractor_amd.world``): a worker makes the generator's draws in the
+reference's order, computes the pulse positions of the drawn F0 curve (a sequential float64 recurrence) and the labels,
+and ships a ``WorldRequest`` instead of audio; the device synthesizes only the samples the cropped 192 mel frames read
+into the batch row.  With ``enabled: true`` alone the generator is logged as disabled, as the reference does without
+pyworld.  The pitch-shift augmentation (``synthetic_data.pitch_shift``,
 meldataset.py:324-517) runs on the GPU (``pitchextractor_amd.pitch_shift``): workers draw everything the reference
 draws, in its order, and ship the whole base file; the device shifts it and writes only the samples the cropped
 192 mel frames read into the batch row.  F0 labels come from the reference's cache files under the reference's own
@@ -62,6 +67,7 @@ from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS,
 from .f0_tracker import NATIVE_TYPES, check_config
 from .pitch_shift import check_res_type, pitch_shift_ragged
 from .resample import RaggedResampler, Resampler
+from .world import WorldGenerator, noise_seed, output_length, world_synthesize_ragged
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.DEBUG)
@@ -292,6 +298,42 @@ class PitchShiftBatch(NamedTuple):
     src_sr: torch.Tensor | None = None         # int32 (K,) the base files' rates when the batch mixes rates
 
 
+class WorldRequest(NamedTuple):
+    """What a worker hands the device for one WORLD-vocoder item (last element of the item tuple): the drawn curve's
+    pulse table instead of audio.  ``n``: samples of the whole utterance; the device writes synthesized samples
+    [out_start, out_start + out_len) to the batch row, as for a ``PitchShiftRequest``."""
+    template: int
+    gain: float
+    n: int
+    crop: int
+    out_start: int
+    out_len: int
+    frame_start: int
+    curve: np.ndarray                          # float64 (frames,) the drawn F0 curve
+    index: np.ndarray                          # the pulse table (world.time_base)
+    shift: np.ndarray
+    vuv: np.ndarray
+    seed: int                                  # of the aperiodic noise, drawn on the device
+    noise: np.ndarray | None                   # float32 (out_len,) slice of the reference's full-length draw
+
+
+class WorldBatch(NamedTuple):
+    """Collated WORLD-vocoder rows.  Only what the kernels read travels to the device as tensors; the curves and
+    their pulse tables feed the host-side plan and stay numpy arrays."""
+    rows: torch.Tensor                         # int64 (K,) batch rows
+    gains: torch.Tensor                        # float32 (K,)
+    out_len: torch.Tensor                      # int64 (K,)
+    noise: torch.Tensor | None                 # float32 flat, the windows back to back
+    templates: np.ndarray                      # int64 (K,)
+    out_start: np.ndarray                      # int64 (K,)
+    curves: tuple                              # K float64 curves
+    tables: tuple                              # K (index, shift, vuv)
+    seeds: tuple                               # K ints
+
+
+_SYNTHETIC_REQUESTS = (PitchShiftRequest, WorldRequest)
+
+
 def synthetic_window(n: int, crop: int, hop: int, n_fft: int, max_frames: int = MAX_MEL_LENGTH):
     """(out_start, out_len, frame_start): the shifted samples that mel frames crop .. crop + max_frames - 1 of an
     n-sample wave read (centre padding n_fft // 2), laid out so that the batch row's frame ``frame_start`` is frame
@@ -394,8 +436,16 @@ class MelDataset(torch.utils.data.Dataset):
         self.synthetic_pitch_shift_config = pitch_shift_cfg
 
         world_cfg = config.get("world_vocoder", {}) or {}
+        self._world_generator = None
         if world_cfg.get("enabled", False):
-            logger.warning("[MelDataset] WORLD vocoder synthetic generation disabled: pyworld unavailable")
+            if str(world_cfg.get("backend", "")).lower() == "hip":
+                # the reference builds its WorldSynthesizer here (meldataset.py:357-373); a configuration it would
+                # refuse, or an fft_size the kernel lacks, is an error rather than a silently missing generator
+                self._world_generator = WorldGenerator(self.sr, int(self.mel_params["hop_length"]),
+                                                       self.mel_params.get("n_fft", 1024), world_cfg)
+                self._synthetic_generators.append("world_vocoder")
+            else:
+                logger.warning("[MelDataset] WORLD vocoder synthetic generation disabled: pyworld unavailable")
 
         if not self._synthetic_generators or self._synthetic_count <= 0:
             self.synthetic_enabled = False
@@ -405,17 +455,47 @@ class MelDataset(torch.utils.data.Dataset):
                 print("[MelDataset] Synthetic data disabled: no valid generators or count is zero.")
 
     def _generate_synthetic_sample(self):
-        """meldataset.py:383-421; 'pitch_shift' is the only generator here."""
+        """meldataset.py:382-418, draw for draw."""
         if not self._synthetic_generators:
             raise RuntimeError("Synthetic generation requested but no generators are available")
-        random.choice(self._synthetic_generators)
-        result = self._generate_pitch_shift_sample()
-        if result is not None:
-            return result
-        result = self._generate_pitch_shift_sample(force=True)
-        if result is not None:
-            return result
-        raise RuntimeError("Unable to produce synthetic pitch-shift sample")
+        generator_name = random.choice(self._synthetic_generators)
+        if generator_name == "pitch_shift":
+            result = self._generate_pitch_shift_sample()
+            if result is not None:
+                return result
+            remaining = [g for g in self._synthetic_generators if g != "pitch_shift"]
+            if remaining:
+                generator_name = random.choice(remaining)
+            else:
+                result = self._generate_pitch_shift_sample(force=True)
+                if result is not None:
+                    return result
+                raise RuntimeError("Unable to produce synthetic pitch-shift sample")
+        if generator_name == "world_vocoder" and self._world_generator is not None:
+            return self._generate_world_sample()
+        raise RuntimeError(f"Unknown synthetic generator '{generator_name}'")
+
+    def _generate_world_sample(self):
+        """Utils/synthetic.py:194-220 + _build_training_example (meldataset.py:629-677) with the synthesis left to the
+        device: the generator's draws in its order, then the crop draw; labels built here from the drawn curve."""
+        draw = self._world_generator.draw()
+        hop = int(self.mel_params["hop_length"])
+        n = output_length(draw.curve.shape[0], self.sr, self._world_generator.frame_period)
+        mel_len = 1 + n // hop
+        f0 = align_length(draw.curve.astype(np.float32), mel_len)
+        sil = (f0 == 0).astype(np.float32)
+        crop = 0
+        if mel_len > self.max_mel_length:
+            crop = int(np.random.randint(0, mel_len - self.max_mel_length))
+            f0 = f0[crop:crop + self.max_mel_length]
+            sil = sil[crop:crop + self.max_mel_length]
+        f0 = np.where(np.isnan(f0), np.float32(self.zero_value), f0).astype(np.float32)
+        start, count, first = synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
+        noise = None if draw.noise is None else np.ascontiguousarray(draw.noise[start:start + count], dtype=np.float32)
+        req = WorldRequest(int(draw.template), float(draw.gain), n, crop, start, count, first, draw.curve,
+                           draw.table.index, draw.table.shift, draw.table.vuv, noise_seed(draw.curve), noise)
+        return (torch.zeros(0, dtype=torch.float32), torch.from_numpy(f0), torch.from_numpy(sil), first, int(self.sr),
+                req)
 
     def _generate_pitch_shift_sample(self, force=False):
         """meldataset.py:423-517 with the signal work left to the device: the same draws in the same order, the
@@ -827,8 +907,9 @@ class Collater(object):
     where ``source_sr`` is the batch's one source rate (``int``, 0 if unknown) or, when its items carry different
     rates, an int32 ``(B,)`` tensor of per-row rates (0 for an item without one),
     followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram and by a
-    ``PitchShiftBatch`` when any item is a pitch-shifted one.  A synthetic row's waveform is left zero (the device
-    writes its shifted window there) and its length is that window's; its base file is packed, not padded."""
+    ``PitchShiftBatch`` when any item is a pitch-shifted one, then by a ``WorldBatch`` when any item is a WORLD-vocoder
+    one.  A synthetic row's waveform is left zero (the device writes its window there) and its length is that
+    window's; a pitch-shifted row's base file is packed, not padded."""
 
     def __init__(self, return_wave=False):
         self.return_wave = return_wave
@@ -850,7 +931,8 @@ class Collater(object):
                 sils[i, :n] = sil
             return mels.unsqueeze(1), f0s, sils
         syn = [i for i, item in enumerate(batch) if isinstance(item[-1], PitchShiftRequest)]
-        n_max = max(int(item[-1].out_len) if isinstance(item[-1], PitchShiftRequest) else int(item[0].shape[0])
+        wld = [i for i, item in enumerate(batch) if isinstance(item[-1], WorldRequest)]
+        n_max = max(int(item[-1].out_len) if isinstance(item[-1], _SYNTHETIC_REQUESTS) else int(item[0].shape[0])
                     for item in batch)
         waves = torch.zeros((B, n_max), dtype=torch.float32)
         lengths = torch.zeros((B,), dtype=torch.int32)
@@ -860,7 +942,7 @@ class Collater(object):
         mixed = len(rates) > 1
         for i, item in enumerate(batch):
             wave, f0, sil, crop = item[:4]
-            if isinstance(item[-1], PitchShiftRequest):
+            if isinstance(item[-1], _SYNTHETIC_REQUESTS):
                 n = item[-1].out_len
             else:
                 n = wave.shape[0]
@@ -890,6 +972,18 @@ class Collater(object):
                                     torch.tensor([r.gain for r in reqs], dtype=torch.float32),
                                     i64([r.out_start for r in reqs]), i64([r.out_len for r in reqs]), noise,
                                     torch.tensor([row_rates[i] for i in syn], dtype=torch.int32) if mixed else None),)
+        if wld:
+            reqs = [batch[i][-1] for i in wld]
+            noise = None
+            if reqs[0].noise is not None:
+                noise = torch.from_numpy(np.concatenate([r.noise for r in reqs]).astype(np.float32))
+            out += (WorldBatch(torch.tensor(wld, dtype=torch.int64),
+                               torch.tensor([r.gain for r in reqs], dtype=torch.float32),
+                               torch.tensor([r.out_len for r in reqs], dtype=torch.int64), noise,
+                               np.array([r.template for r in reqs], dtype=np.int64),
+                               np.array([r.out_start for r in reqs], dtype=np.int64),
+                               tuple(r.curve for r in reqs), tuple((r.index, r.shift, r.vuv) for r in reqs),
+                               tuple(r.seed for r in reqs)),)
         return out
 
 
@@ -907,8 +1001,8 @@ class H2DPrefetcher:
 
     def submit(self, host_items):
         def to_dev(t):
-            if isinstance(t, PitchShiftBatch):
-                return PitchShiftBatch(*(to_dev(x) for x in t))
+            if isinstance(t, (PitchShiftBatch, WorldBatch)):
+                return type(t)(*(to_dev(x) for x in t))
             return t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t
         with torch.cuda.stream(self.stream):
             dev = tuple(to_dev(t) for t in host_items)
@@ -921,7 +1015,7 @@ class H2DPrefetcher:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ready)
         for t in dev:
-            for x in (t if isinstance(t, PitchShiftBatch) else (t,)):
+            for x in (t if isinstance(t, (PitchShiftBatch, WorldBatch)) else (t,)):
                 if torch.is_tensor(x) and x.is_cuda:
                     x.record_stream(cur)          # allocated on the side stream, consumed on the compute stream
         return dev
@@ -969,10 +1063,27 @@ class DeviceMelLoader:
         lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
         return waves, lengths
 
+    def _world(self, waves, lengths, pack, host):
+        """WORLD-vocoder rows: synthesize each row's window from its pulse table and vowel template."""
+        gen = self.dataset._world_generator
+        need = int(host.out_len.max())
+        if waves.shape[1] < need:
+            waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
+        waves = waves.contiguous()
+        bins = gen.fft_size // 2 + 1
+        world_synthesize_ragged(pack.curves, gen.device_templates(self.device).reshape(-1), pack.templates * bins,
+                                np.zeros(len(pack.curves), np.int64), pack.gains, waves, host.rows.numpy(),
+                                pack.out_start, host.out_len.numpy(), fs=gen.sample_rate,
+                                frame_period=gen.frame_period, fft_size=gen.fft_size, tables=pack.tables,
+                                seeds=pack.seeds, out_noise=pack.noise)
+        lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
+        return waves, lengths
+
     def _finish(self, ticket):
         waves, lengths, crops, f0s, sils, src_sr, *cached = self._h2d.acquire(ticket)
+        world = cached.pop() if cached and isinstance(cached[-1], WorldBatch) else None
         pack = cached.pop() if cached and isinstance(cached[-1], PitchShiftBatch) else None
-        host_pack = self._host_packs.pop(0)
+        host_pack, host_world = self._host_packs.pop(0)
         host_lengths, host_rates = self._host_lengths.pop(0), self._host_rates.pop(0)
         sr = self.mel.sample_rate
         rates = host_rates if host_rates is not None else [src_sr] * len(host_lengths)
@@ -980,10 +1091,14 @@ class DeviceMelLoader:
             # one ragged launch, each row at its own rate and bit-identical to that item resampled alone; synthetic
             # rows are left zero (length 0) for the pitch shift, which resamples their base files itself
             syn = set(host_pack.rows.tolist()) if host_pack is not None else set()
+            if host_world is not None:
+                syn |= set(host_world.rows.tolist())
             waves, lengths = self._ragged(waves, [r or sr for r in rates],
                                           [0 if i in syn else int(n) for i, n in enumerate(host_lengths)])
         if pack is not None:                                  # after the resampler, before the one mel launch
             waves, lengths = self._pitch_shift(waves, lengths, src_sr, pack, host_pack)
+        if world is not None:
+            waves, lengths = self._world(waves, lengths, world, host_world)
         mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
         if cached:                                            # rows whose spectrogram came from <wav>_mel.npy
             rows, cached_mels = cached
@@ -1005,7 +1120,9 @@ class DeviceMelLoader:
         for host in self.loader:
             self._host_lengths.append(host[1].tolist())
             self._host_rates.append(host[5].tolist() if torch.is_tensor(host[5]) else None)
-            self._host_packs.append(host[-1] if isinstance(host[-1], PitchShiftBatch) else None)
+            packs = [t for t in host[6:] if isinstance(t, (PitchShiftBatch, WorldBatch))]
+            self._host_packs.append((next((t for t in packs if isinstance(t, PitchShiftBatch)), None),
+                                     next((t for t in packs if isinstance(t, WorldBatch)), None)))
             ticket = self._h2d.submit(host)
             if pending is not None:
                 yield self._finish(pending)

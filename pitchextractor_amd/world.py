@@ -1,0 +1,450 @@
+"""WORLD vocoder synthesis on the GPU: ``pyworld.synthesize(f0, sp, ap, fs, frame_period)`` (WORLD's ``Synthesis``) and
+the vowel generator the reference builds on it (Utils/synthetic.py).
+
+The time base -- where the glottal pulses fall -- is a sequential float64 recurrence (a running phase wrapped at 2 pi)
+whose rounding decides a pulse's sample wherever a period is a whole number of samples, so it runs here on the host
+(``time_base``), in WORLD's order of operations.  The device gets the finished pulse table and does the heavy part:
+one minimum-phase impulse response of ``fft_size`` samples per pulse and their overlap-add (``csrc/world_synth.hip``);
+there is no CPU path.  Two stated deviations from WORLD: pulse p's aperiodic noise is ``noise[index[p] : index[p] +
+noise_size[p]]`` of a caller-given array of standard normals, or drawn in the kernel from Philox keyed by ``(seed,
+sample)`` (WORLD draws from a process-global xorshift stream), and the per-pulse arithmetic is float32.  pyworld is not
+available here: parity with its binary is unpinned, the yardstick is a float64 restatement of the published algorithm
+(``tests/world_ref.py``), see DESIGN.md.
+"""
+from __future__ import annotations
+
+import hashlib
+import math
+import random
+from dataclasses import dataclass
+from typing import NamedTuple, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+FFT_SIZES = (512, 1024, 2048)
+WORKSPACE_BYTES = 256 << 20                                 # responses of one launch; more rows go to further launches
+UNVOICED_F0 = 500.0                                         # WORLD's pulse rate for unvoiced stretches
+
+DEFAULT_VOWELS = (
+    {"label": "ah", "formants": ((730.0, 90.0, 1.0), (1090.0, 110.0, 0.6), (2440.0, 150.0, 0.4))},
+    {"label": "ih", "formants": ((390.0, 80.0, 1.0), (1990.0, 120.0, 0.6), (2550.0, 160.0, 0.4))},
+    {"label": "uh", "formants": ((440.0, 70.0, 1.0), (1020.0, 90.0, 0.6), (2240.0, 150.0, 0.4))},
+)
+
+
+def check_fft_size(fft_size) -> int:
+    if int(fft_size) not in FFT_SIZES:
+        raise ValueError(f"WORLD synthesis fft_size {fft_size!r} is not supported on the HIP path: use one of "
+                         f"{list(FFT_SIZES)}")
+    return int(fft_size)
+
+
+# --------------------------------------------------------------------------- host side: lengths and the time base
+def output_length(n_frames: int, fs, frame_period_ms: float) -> int:
+    """WORLD's y_length = int(f0_length * frame_period * fs / 1000)."""
+    return int(int(n_frames) * frame_period_ms * fs / 1000)
+
+
+def lowest_f0(fs, fft_size: int) -> float:
+    return fs / fft_size + 1.0
+
+
+class PulseTable(NamedTuple):
+    index: np.ndarray                          # int64 (P,) sample of each pulse, strictly increasing
+    shift: np.ndarray                          # float64 (P,) fractional delay in seconds, 0 <= shift * fs <= 1
+    vuv: np.ndarray                            # bool (P,) voicing at the pulse's sample
+    noise_size: np.ndarray                     # int64 (P,) samples to the next pulse, 0 for the last
+
+
+def time_base(f0, fs, frame_period_ms: float, fft_size: int) -> PulseTable:
+    """WORLD's GetTimeBase + GetPulseLocationsForTimeBase, numpy float64 in WORLD's order: frames below ``lowest_f0``
+    are unvoiced; F0 and voicing get one extrapolated frame and are interpolated linearly to the sample times; the
+    phase is the running sum of 2 pi f0 / fs (500 Hz where unvoiced), wrapped with fmod; a pulse sits wherever the
+    wrapped phase drops by more than pi, its fractional position from the two samples around the wrap."""
+    f0 = np.asarray(f0, dtype=np.float64).reshape(-1)
+    L = f0.shape[0]
+    if L < 2:
+        raise ValueError("WORLD synthesis needs at least two frames")
+    if not np.all(np.isfinite(f0)):
+        raise ValueError("WORLD synthesis: f0 must be finite")
+    fp = frame_period_ms / 1000.0
+    n = output_length(L, fs, frame_period_ms)
+    coarse_f0 = np.where(f0 >= lowest_f0(fs, fft_size), f0, 0.0)
+    coarse_vuv = (coarse_f0 != 0.0).astype(np.float64)
+    coarse_f0 = np.append(coarse_f0, 2 * coarse_f0[L - 1] - coarse_f0[L - 2])
+    coarse_vuv = np.append(coarse_vuv, 2 * coarse_vuv[L - 1] - coarse_vuv[L - 2])
+    coarse_t = np.arange(L + 1) * fp
+    t = np.arange(n) / fs
+    vuv = np.interp(t, coarse_t, coarse_vuv) > 0.5
+    f0i = np.where(vuv, np.interp(t, coarse_t, coarse_f0), UNVOICED_F0)
+    total = np.cumsum(2 * np.pi * f0i / fs)
+    wrap = np.fmod(total, 2 * np.pi)
+    index = np.flatnonzero(np.abs(wrap[1:] - wrap[:-1]) > np.pi).astype(np.int64)
+    y1 = wrap[index] - 2 * np.pi
+    y2 = wrap[index + 1]
+    shift = (-y1 / (y2 - y1)) / fs
+    noise_size = np.zeros_like(index)
+    noise_size[:-1] = np.diff(index)
+    return PulseTable(index, shift, vuv[index], noise_size)
+
+
+def dc_remover(fft_size: int) -> np.ndarray:
+    """WORLD's GetDCRemover: a Hann-like window over both halves, normalised to remove a unit sum."""
+    half = fft_size // 2
+    w = np.zeros(fft_size)
+    w[:half] = 0.5 - 0.5 * np.cos(2 * np.pi * (np.arange(half) + 1.0) / (1.0 + fft_size))
+    w[fft_size - 1 - np.arange(half)] = w[:half]
+    return w / (2 * w[:half].sum())
+
+
+def noise_seed(curve) -> int:
+    """Seed of a generated item's aperiodic noise: 8 bytes of a digest of the curve, so that neither ``random`` nor
+    ``np.random`` is consumed for it."""
+    data = np.ascontiguousarray(curve, dtype=np.float64).tobytes()
+    return int.from_bytes(hashlib.blake2b(data, digest_size=8).digest(), "little")
+
+
+# --------------------------------------------------------------------------- batch layout
+def _i64(a, n=None):
+    a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    if n is not None and a.size != n:
+        raise ValueError("WORLD plan: per-row arrays differ in length")
+    return a
+
+
+class Plan:
+    """Host layout of a ragged batch (``pe_world_plan``): per-row int64 fields, the planned pulses and the workspace
+    sizes {planned pulses, output samples}.  ``tables``: one ``PulseTable`` (or (index, shift, vuv, ...)) per row."""
+
+    def __init__(self, n_frames, tables, sp_offsets, sp_strides, ap_offsets=None, ap_strides=None, noise_offsets=None,
+                 seeds=None, out_start=None, out_len=None, out_rows=None, out_stride=None, *, fs, frame_period_ms,
+                 fft_size, f0s=None):
+        self.n_frames = _i64(n_frames)
+        R = self.n_rows = self.n_frames.size
+        self.fs, self.frame_period_ms, self.fft_size = fs, float(frame_period_ms), int(fft_size)
+        if len(tables) != R:
+            raise ValueError("WORLD plan: one pulse table per row")
+        self.pulse_cnt = _i64([len(t[0]) for t in tables], R)
+        cat = lambda k, dt: np.ascontiguousarray(  # noqa: E731
+            np.concatenate([np.asarray(t[k]).reshape(-1) for t in tables]) if R else np.zeros(0), dtype=dt)
+        self.index, self.shift, self.vuv = cat(0, np.int64), cat(1, np.float64), cat(2, np.uint8)
+        self.y_len = _i64([output_length(n, fs, self.frame_period_ms) for n in self.n_frames], R)
+        self.sp_offsets, self.sp_strides = _i64(sp_offsets, R), _i64(sp_strides, R)
+        self.ap_offsets = np.full(R, -1, np.int64) if ap_offsets is None else _i64(ap_offsets, R)
+        self.ap_strides = np.zeros(R, np.int64) if ap_strides is None else _i64(ap_strides, R)
+        self.noise_offsets = np.full(R, -1, np.int64) if noise_offsets is None else _i64(noise_offsets, R)
+        self.seeds = (np.zeros(R, np.int64) if seeds is None else
+                      np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64).view(np.int64))
+        self.out_start = np.zeros(R, np.int64) if out_start is None else _i64(out_start, R)
+        self.out_len = self.y_len - self.out_start if out_len is None else _i64(out_len, R)
+        self.out_rows = np.arange(R, dtype=np.int64) if out_rows is None else _i64(out_rows, R)
+        self.out_stride = int(self.out_len.max(initial=0) if out_stride is None else out_stride)
+        if self.seeds.size != R:
+            raise ValueError("WORLD plan: per-row arrays differ in length")
+        f0 = None
+        if f0s is not None:
+            f0 = np.ascontiguousarray(np.concatenate([np.asarray(f, np.float64).reshape(-1) for f in f0s])
+                                      if R else np.zeros(0))
+            if f0.size != int(self.n_frames.sum()):
+                raise ValueError("WORLD plan: f0 curves do not match the frame counts")
+        lib = _lib.load()
+        K = lib.pe_world_plan_fields()
+        P = max(int(self.index.size), 1)
+        self.meta = np.zeros((max(R, 1), K), np.int64)
+        self.pulses = np.zeros((P, 6), np.int64)
+        self.pulse_f = np.zeros((P, 2), np.float64)
+        self.totals = np.zeros(2, np.int64)
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        _lib.check(lib.pe_world_plan(R, p(self.n_frames), p(f0), p(self.pulse_cnt), p(self.index), p(self.shift),
+                                     p(self.vuv), p(self.sp_offsets), p(self.sp_strides), p(self.ap_offsets),
+                                     p(self.ap_strides), p(self.noise_offsets), p(self.seeds), p(self.out_start),
+                                     p(self.out_len), p(self.out_rows), self.out_stride, float(fs),
+                                     self.frame_period_ms, self.fft_size, p(self.meta), p(self.pulses),
+                                     p(self.pulse_f), p(self.totals)), "pe_world_plan")
+        self.n_pulses, self.n_out = (int(v) for v in self.totals)
+        self.pulses, self.pulse_f = self.pulses[:max(self.n_pulses, 1)], self.pulse_f[:max(self.n_pulses, 1)]
+
+
+class WorldSynth:
+    """``table``: the device copy of the transform's roots of unity and the DC remover; ``run`` executes the two
+    stages for a ``Plan``."""
+
+    def table(self, fft_size, device):
+        def build():
+            m = np.arange(fft_size)
+            ang = -2.0 * np.pi * m / fft_size
+            return np.concatenate([np.stack([np.cos(ang), np.sin(ang)], axis=1).reshape(-1), dc_remover(fft_size)])
+        return _lib.device_table(("world", int(fft_size)), device, build)
+
+    def run(self, plan: Plan, sp, ap, gains, out, noise=None, out_noise=None, keep=False):
+        """sp / ap / noise: flat float32 device tensors addressed by the plan's offsets (ap, noise optional); gains
+        (R,) float32 device; out: float32 device tensor addressed by out_row * out_stride + i; out_noise: the output
+        windows' additive noise back to back.  Returns the responses when ``keep``."""
+        dev = out.device
+        for name, t in (("sp", sp), ("ap", ap), ("gains", gains), ("out", out), ("noise", noise),
+                        ("out_noise", out_noise)):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise RuntimeError(f"WORLD synthesis: {name} must be a contiguous float32 device tensor (no CPU path)")
+        if plan.n_rows == 0 or plan.n_out == 0:
+            return {} if keep else None
+        N, R = plan.fft_size, plan.n_rows
+        bins = N // 2 + 1
+        if gains.numel() != R:
+            raise ValueError("WORLD synthesis: one gain per row")
+        if out_noise is not None and out_noise.numel() != plan.n_out:
+            raise ValueError("WORLD synthesis: out_noise must hold one value per output sample")
+        if out.numel() < int((plan.out_rows * plan.out_stride + plan.out_len).max(initial=0)):
+            raise ValueError("WORLD synthesis: output buffer smaller than the plan addresses")
+        if sp.numel() < int((plan.sp_offsets + (plan.n_frames - 1) * plan.sp_strides).max(initial=0)) + bins:
+            raise ValueError("WORLD synthesis: sp smaller than the plan addresses")
+        has_ap = plan.ap_offsets >= 0
+        if has_ap.any() and (ap is None or ap.numel() < int(
+                (plan.ap_offsets + (plan.n_frames - 1) * plan.ap_strides)[has_ap].max()) + bins):
+            raise ValueError("WORLD synthesis: ap smaller than the plan addresses")
+        has_noise = plan.noise_offsets >= 0
+        if has_noise.any() and (noise is None or noise.numel() < int((plan.noise_offsets + plan.y_len)[has_noise].max())):
+            raise ValueError("WORLD synthesis: noise must hold one value per sample of the row")
+        meta = torch.from_numpy(plan.meta).to(dev)
+        pulses = torch.from_numpy(plan.pulses).to(dev)
+        pulse_f = torch.from_numpy(plan.pulse_f).to(dev)
+        resp = torch.empty((plan.n_pulses, N), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ops._call("pe_world_responses", sp.data_ptr(), _lib.ptr(ap), _lib.ptr(noise), meta.data_ptr(),
+                      pulses.data_ptr(), pulse_f.data_ptr(), self.table(N, dev).data_ptr(), R, plan.n_pulses, N,
+                      resp.data_ptr(), _lib.stream_ptr(), work=float(plan.n_pulses * (N * 4 + 4 * bins * 4)))
+            ops._call("pe_world_overlap_add", resp.data_ptr(), meta.data_ptr(), pulses.data_ptr(), gains.data_ptr(),
+                      _lib.ptr(out_noise), R, plan.n_out, N, out.data_ptr(), _lib.stream_ptr(),
+                      work=float(plan.n_out * 8))
+        if keep:
+            return {"responses": resp, "meta": plan.meta, "pulses": plan.pulses, "pulse_f": plan.pulse_f}
+        return None
+
+
+_SYNTH = WorldSynth()
+
+
+def _device_f32(name, t):
+    if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32):
+        raise RuntimeError(f"WORLD synthesis: {name} must be a contiguous float32 device tensor (no CPU path)")
+    return None if t is None else t.contiguous()
+
+
+def _host_f0(f0):
+    if torch.is_tensor(f0):
+        f0 = f0.detach().cpu().numpy()
+    return np.asarray(f0, dtype=np.float64).reshape(-1)
+
+
+def world_synthesize_ragged(f0s, sp, sp_offsets, sp_strides, gains: torch.Tensor, out: torch.Tensor, out_rows=None,
+                            out_start=None, out_len=None, *, fs, frame_period: float, fft_size: int, ap=None,
+                            ap_offsets=None, ap_strides=None, tables=None, noise=None, noise_offsets=None, seeds=None,
+                            out_noise=None) -> torch.Tensor:
+    """Ragged batch.  Row r has the host curve ``f0s[r]`` (``tables[r]`` its pulse table; computed here when not
+    given); frame f of its envelope is the ``fft_size // 2 + 1`` floats of the flat float32 device tensor ``sp`` at
+    ``sp_offsets[r] + f * sp_strides[r]`` (stride 0: one template for every frame), ``ap`` likewise (``ap_offsets[r] <
+    0`` or no ``ap``: zeros).  The row's aperiodic noise is ``noise`` at ``noise_offsets[r]`` (one standard normal per
+    sample of the row) or, without it, drawn on the device from ``seeds[r]``.  Samples ``[out_start[r], out_start[r] +
+    out_len[r])`` of row r (default: all) times ``gains[r]`` go to ``out[out_rows[r], :out_len[r]]`` of the 2-D
+    ``out``, plus ``out_noise`` (flat, the windows back to back) when given.  Rows whose responses would not fit one
+    256 MiB workspace run in several launches.  Returns ``out``."""
+    if out.dim() != 2:
+        raise ValueError("out must be 2-D (rows, samples)")
+    if out.stride(1) != 1:
+        raise ValueError("out rows must be contiguous")
+    fft_size = check_fft_size(fft_size)
+    sp, ap, noise, out_noise = (_device_f32(n, t) for n, t in (("sp", sp), ("ap", ap), ("noise", noise),
+                                                              ("out_noise", out_noise)))
+    f0s = [_host_f0(f) for f in f0s]
+    R = len(f0s)
+    if tables is None:
+        tables = [time_base(f, fs, frame_period, fft_size) for f in f0s]
+    n_frames = [f.size for f in f0s]
+    y_len = np.array([output_length(n, fs, frame_period) for n in n_frames], dtype=np.int64)
+    out_start = np.zeros(R, np.int64) if out_start is None else _i64(out_start, R)
+    out_len = y_len - out_start if out_len is None else _i64(out_len, R)
+    out_rows = np.arange(R, dtype=np.int64) if out_rows is None else _i64(out_rows, R)
+    gains = gains.to(out.device, torch.float32).contiguous()
+    # rows per launch: the planned pulses' responses stay within the workspace
+    half = fft_size // 2
+    planned = [int(np.searchsorted(t[0], out_start[r] + out_len[r] - 1 + half, "left") -
+                   np.searchsorted(t[0], out_start[r] - half, "left")) if out_len[r] > 0 else 0
+               for r, t in enumerate(tables)]
+    limit = WORKSPACE_BYTES // (4 * fft_size)
+    groups, cur, used = [], [], 0
+    for r in range(R):
+        if cur and used + planned[r] > limit:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(r)
+        used += planned[r]
+    if cur:
+        groups.append(cur)
+    pick = lambda a, g, dflt=None: dflt if a is None else [a[r] for r in g]  # noqa: E731
+    n_off = np.concatenate([[0], np.cumsum(out_len)])
+    for g in groups:
+        plan = Plan(pick(n_frames, g), pick(tables, g), pick(sp_offsets, g), pick(sp_strides, g),
+                    pick(ap_offsets, g) if ap is not None else None, pick(ap_strides, g) if ap is not None else None,
+                    pick(noise_offsets, g) if noise is not None else None, pick(seeds, g), out_start[g], out_len[g],
+                    out_rows[g], out.stride(0), fs=fs, frame_period_ms=frame_period, fft_size=fft_size,
+                    f0s=pick(f0s, g))
+        _SYNTH.run(plan, sp, ap, gains[g[0]:g[-1] + 1], out, noise,
+                   None if out_noise is None else out_noise[int(n_off[g[0]]):int(n_off[g[-1] + 1])])
+    return out
+
+
+def world_synthesize(f0, sp: torch.Tensor, ap: torch.Tensor | None = None, fs=24000, frame_period: float = 5.0, *,
+                     noise: torch.Tensor | None = None, seed: int = 0) -> torch.Tensor:
+    """pyworld's ``synthesize(f0, sp, ap, fs, frame_period)`` on the device.  ``f0``: host curve (a tensor is brought
+    to the host); ``sp`` / ``ap``: float32 device tensors ``(len(f0), fft_size / 2 + 1)``, or one ``(fft_size / 2 +
+    1,)`` template for every frame; ``ap=None`` is all zeros.  ``noise``: one standard normal per output sample (device
+    float32) for the aperiodic part; drawn on the device from ``seed`` when not given.  Returns a 1-D float32 device
+    tensor of ``int(len(f0) * frame_period * fs / 1000)`` samples."""
+    f0 = _host_f0(f0)
+    sp = _device_f32("sp", sp)
+    ap = _device_f32("ap", ap)
+    noise = _device_f32("noise", noise)
+    bins = sp.shape[-1]
+    fft_size = check_fft_size(2 * (bins - 1))
+    for name, t in (("sp", sp), ("ap", ap)):
+        if t is not None and not ((t.dim() == 1 and t.shape[0] == bins) or
+                                  (t.dim() == 2 and tuple(t.shape) == (f0.size, bins))):
+            raise ValueError(f"world_synthesize: {name} must be (len(f0), {bins}) or ({bins},)")
+    n = output_length(f0.size, fs, frame_period)
+    if noise is not None and noise.numel() != n:
+        raise ValueError("world_synthesize: noise must hold one value per output sample")
+    out = torch.zeros((1, max(n, 1)), dtype=torch.float32, device=sp.device)
+    stride = lambda t: [bins if t.dim() == 2 else 0]  # noqa: E731
+    world_synthesize_ragged([f0], sp.reshape(-1), [0], stride(sp), torch.ones(1), out, fs=fs,
+                            frame_period=frame_period, fft_size=fft_size,
+                            ap=None if ap is None else ap.reshape(-1), ap_offsets=None if ap is None else [0],
+                            ap_strides=None if ap is None else stride(ap),
+                            noise=None if noise is None else noise.reshape(-1),
+                            noise_offsets=None if noise is None else [0], seeds=[seed])
+    return out[0, :n]
+
+
+# --------------------------------------------------------------------------- the reference's vowel generator
+def formant_templates(profiles, fs, fft_size: int):
+    """Utils/synthetic.py:122-147: one spectral envelope per profile, a sum of Gaussians floored at 1e-3."""
+    freq_axis = np.linspace(0, fs / 2, fft_size // 2 + 1)
+    templates = []
+    for profile in profiles:
+        formants = profile.get("formants", [])
+        if not formants:
+            continue
+        envelope = np.zeros_like(freq_axis)
+        for formant in formants:
+            if len(formant) < 2:
+                continue
+            freq, bandwidth = float(formant[0]), float(formant[1])
+            amplitude = float(formant[2]) if len(formant) > 2 else 1.0
+            if bandwidth <= 0:
+                bandwidth = 60.0
+            envelope += amplitude * np.exp(-0.5 * ((freq_axis - freq) / (bandwidth / 2.0)) ** 2)
+        templates.append(np.maximum(envelope, 1e-3).astype(np.float64))
+    if not templates:
+        raise ValueError("No valid vowel templates provided for WORLD synthesis")
+    return templates
+
+
+@dataclass
+class ModulationConfig:
+    vibrato_probability: float = 0.6
+    vibrato_semitones: float = 0.35
+    vibrato_rate_range: Tuple[float, float] = (4.0, 7.0)
+    max_segments: int = 4
+
+
+class WorldDraw(NamedTuple):
+    curve: np.ndarray                          # float64 (L,) the drawn F0 curve, one value per hop
+    template: int
+    gain: float
+    noise: np.ndarray | None                   # float64 (n,) additive noise of the whole utterance
+    table: PulseTable
+
+
+class WorldGenerator:
+    """The host half of the reference's ``WorldSynthesizer`` (Utils/synthetic.py:71-220): the same configuration, the
+    same validation, and ``draw`` consuming ``random`` and ``np.random`` exactly as ``generate`` does.  The synthesis
+    itself is left to the device (``world_synthesize_ragged``)."""
+
+    def __init__(self, sample_rate, hop_length, fft_size=None, config=None):
+        self.sample_rate, self.hop_length = int(sample_rate), int(hop_length)
+        self.fft_size = check_fft_size(int(fft_size or 1024))
+        cfg = dict(config or {})
+        duration_cfg = cfg.get("duration", {}) or {}
+        self.min_duration = float(duration_cfg.get("min", 0.5))
+        self.max_duration = float(duration_cfg.get("max", 1.8))
+        if self.max_duration <= 0:
+            raise ValueError("Synthetic duration must be positive")
+        pitch_range = cfg.get("pitch_range", [110.0, 320.0])
+        if len(pitch_range) != 2:
+            raise ValueError("pitch_range must contain two values")
+        self.pitch_min, self.pitch_max = float(min(pitch_range)), float(max(pitch_range))
+        noise_db_cfg = cfg.get("noise_db", -60.0)
+        self.noise_db = None if noise_db_cfg is None else float(noise_db_cfg)
+        gain_cfg = cfg.get("gain_db_range", [-18.0, -6.0])
+        if isinstance(gain_cfg, (int, float)):
+            gain_cfg = [gain_cfg, gain_cfg]
+        if len(gain_cfg) != 2:
+            raise ValueError("gain_db_range must provide two values")
+        gain_min, gain_max = float(gain_cfg[0]), float(gain_cfg[1])
+        if gain_min > gain_max:
+            gain_min, gain_max = gain_max, gain_min
+        self.gain_db_range = (gain_min, gain_max)
+        self.modulation = ModulationConfig(**(cfg.get("modulation", {}) or {}))
+        self.templates = formant_templates(cfg.get("vowel_profiles") or DEFAULT_VOWELS, self.sample_rate,
+                                           self.fft_size)
+        self.frame_period = 1000.0 * self.hop_length / self.sample_rate
+        table = np.stack(self.templates).astype(np.float32)
+        self._table_key = ("world_templates", self.fft_size, hashlib.blake2b(table.tobytes(), digest_size=8).hexdigest())
+        self._table = table
+
+    def device_templates(self, device) -> torch.Tensor:
+        """The templates as one float32 device table (T, fft_size / 2 + 1), copied once per device."""
+        return _lib.device_table(self._table_key, device, lambda: self._table)
+
+    def _sample_duration(self) -> float:
+        if self.max_duration <= self.min_duration:
+            return max(self.max_duration, 0.1)
+        return random.uniform(self.min_duration, self.max_duration)
+
+    def _sample_f0_curve(self, num_frames: int) -> np.ndarray:
+        base = random.uniform(self.pitch_min, self.pitch_max)
+        curve = np.full(num_frames, base, dtype=np.float64)
+        num_segments = random.randint(1, max(1, int(self.modulation.max_segments)))
+        if num_segments > 1 and num_frames > 2:
+            available = max(1, num_frames - 1)
+            positions = sorted(random.sample(range(1, available), min(num_segments - 1, available - 1)))
+            positions = [0] + positions + [num_frames - 1]
+            values = [random.uniform(self.pitch_min, self.pitch_max) for _ in range(len(positions))]
+            for i in range(len(positions) - 1):
+                start, end = positions[i], positions[i + 1]
+                if end <= start:
+                    continue
+                curve[start:end + 1] = np.linspace(values[i], values[i + 1], end - start + 1)
+        if random.random() < self.modulation.vibrato_probability:
+            depth = max(float(self.modulation.vibrato_semitones), 0.0)
+            if depth > 0:
+                rate = random.uniform(*self.modulation.vibrato_rate_range)
+                t = np.arange(num_frames, dtype=np.float64) * (self.frame_period / 1000.0)
+                curve *= 2.0 ** (np.sin(2.0 * math.pi * rate * t) * (depth / 12.0))
+        return curve
+
+    def draw(self) -> WorldDraw:
+        duration = self._sample_duration()
+        num_frames = max(2, int(np.ceil((duration * 1000.0) / self.frame_period)))
+        template = random.choice(range(len(self.templates)))
+        curve = self._sample_f0_curve(num_frames)
+        gain = float(10.0 ** (random.uniform(*self.gain_db_range) / 20.0))
+        n = output_length(num_frames, self.sample_rate, self.frame_period)
+        noise = None
+        if self.noise_db is not None:
+            noise_gain = float(10.0 ** (self.noise_db / 20.0))
+            if noise_gain > 0:
+                noise = np.random.normal(scale=noise_gain, size=(n,))
+        return WorldDraw(curve, template, gain, noise,
+                         time_base(curve, self.sample_rate, self.frame_period, self.fft_size))
