@@ -23,7 +23,18 @@
  *     take `int act16` (0 = fp32 tensors, 1 = bf16 tensors, see "bf16
  *     ACTIVATION STORAGE").  A form or activation type that none of an entry
  *     point's kernels serves returns PE_E_UNSUPPORTED; a `products` value
- *     outside the enum returns PE_E_ARG.
+ *     outside the enum returns PE_E_ARG.  Both are answered before any
+ *     pointer is looked at; a served form sees the entry point's own argument
+ *     checks first.  Served forms (act16 = 1: under PE_PROD_BF16 only):
+ *
+ *       entry point                                   NATIVE X3 H2 BF16 F16  act16
+ *       pe_gemm_nt, pe_gemm_tn                           x    x  x   x    x    x
+ *       pe_conv3x3_fwd, pe_conv3x3_wgrad                 x    x  x   x    x    x
+ *       pe_conv3x3_fwd_wf                                -    x  x   x    x    x
+ *       pe_wfrag_pack, pe_wfrag_bytes (else 0 bytes)     -    x  x   x    x
+ *       pe_lstm_whh_grad                                 x    x  x   x    x
+ *       pe_lstm_fwd_persistent, pe_lstm_bwd_persistent   -    x  -   x    x
+ *       pe_attn_fwd, pe_attn_bwd                         x    -  -   x    -
  */
 #ifndef PITCHEXTRACTOR_HIP_H
 #define PITCHEXTRACTOR_HIP_H

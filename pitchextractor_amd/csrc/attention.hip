@@ -19,8 +19,7 @@
 //                S^T again (keys x queries)     ->  dQ^T = K^T dS^T       (sum over keys)
 // and no score tile is ever transposed through LDS.  The backward recomputes S twice (two kernels) instead:
 // deterministic, no atomics, no cross-workgroup reduction.
-#include "common.h"
-#include "act16.h"
+#include "forms.h"
 
 // XCD-aware block order (workgroups b and b + 8 share an XCD and its L2): give every XCD a contiguous run of
 // logical blocks, so the workgroups that read the same K / V rows hit the same L2.  Bijective for any grid size.
@@ -427,7 +426,10 @@ int set_lds(K kernel, size_t bytes) {
 
 extern "C" int pe_attn_supported(int T, int dh) { return attn_shape_ok(T, dh) ? 1 : 0; }
 
-template <bool BF>
+// fp32 products (BF = false) or bf16 operands (BF = true); no other form
+constexpr unsigned kAttnForms = pe::form_bit(PE_PROD_NATIVE) | pe::form_bit(PE_PROD_BF16);
+
+template <class F>
 static int attn_fwd_impl(const float* qkv, long ld_qkv, float* o, long ld_o, float* lse, const unsigned char* mask_in,
                          unsigned char* mask_out, int B, int T, int H, int dh, float scale, float p_drop,
                          unsigned long long seed, unsigned long long offset, void* stream) {
@@ -438,6 +440,7 @@ static int attn_fwd_impl(const float* qkv, long ld_qkv, float* o, long ld_o, flo
   a.qkv = qkv; a.ld_qkv = ld_qkv; a.D = H * dh; a.o = o; a.ld_o = ld_o; a.lse = lse;
   a.mask_in = mask_in; a.mask_out = mask_out; a.B = B; a.H = H; a.scale = scale; a.p_drop = p_drop;
   a.keep_scale = 1.0f / (1.0f - p_drop); a.seed = seed; a.offset = offset;
+  constexpr bool BF = F::MODE == pe::kBf16;
   const size_t lds = (size_t)2 * 96 * kStr * sizeof(float);
   static bool attr = false;
   if (!attr) { PE_CHECK_HIP((hipError_t)set_lds(&attn_fwd_kernel<192, BF>, lds)); attr = true; }
@@ -446,22 +449,16 @@ static int attn_fwd_impl(const float* qkv, long ld_qkv, float* o, long ld_o, flo
   return PE_OK;
 }
 
-// fp32 products (BF = false) or bf16 operands (BF = true); no other form
 extern "C" int pe_attn_fwd(int products, const float* qkv, long ld_qkv, float* o, long ld_o, float* lse,
                            const unsigned char* mask_in, unsigned char* mask_out, int B, int T, int H, int dh, float scale,
                            float p_drop, unsigned long long seed, unsigned long long offset, void* stream) {
-  switch (products) {
-    case PE_PROD_NATIVE:
-      return attn_fwd_impl<false>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed, offset,
-                                  stream);
-    case PE_PROD_BF16:
-      return attn_fwd_impl<true>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed, offset,
-                                 stream);
-    default: return pe_unserved(products);
-  }
+  return pe::with_form<kAttnForms, false>(products, 0, [&](auto f) {
+    return attn_fwd_impl<decltype(f)>(qkv, ld_qkv, o, ld_o, lse, mask_in, mask_out, B, T, H, dh, scale, p_drop, seed,
+                                      offset, stream);
+  });
 }
 
-template <bool BF>
+template <class F>
 static int attn_bwd_impl(const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o, const float* lse,
                          const unsigned char* mask, float* dqkv, int B, int T, int H, int dh, float scale,
                          float p_drop, void* stream) {
@@ -473,6 +470,7 @@ static int attn_bwd_impl(const float* qkv, long ld_qkv, const float* o, const fl
   a.qkv = qkv; a.ld_qkv = ld_qkv; a.D = H * dh; a.o = const_cast<float*>(o); a.ld_o = ld_o;
   a.lse = const_cast<float*>(lse); a.d_o = d_o; a.dqkv = dqkv; a.mask = p_drop > 0.f ? mask : nullptr;
   a.B = B; a.H = H; a.scale = scale; a.p_drop = p_drop; a.keep_scale = 1.0f / (1.0f - p_drop);
+  constexpr bool BF = F::MODE == pe::kBf16;
   const size_t lds_kv = (size_t)(2 * 96 * kStr + 2 * 192) * sizeof(float), lds_q = (size_t)2 * 96 * kStr * sizeof(float);
   static bool attr = false;
   if (!attr) {
@@ -491,11 +489,7 @@ static int attn_bwd_impl(const float* qkv, long ld_qkv, const float* o, const fl
 extern "C" int pe_attn_bwd(int products, const float* qkv, long ld_qkv, const float* o, const float* d_o, long ld_o,
                            const float* lse, const unsigned char* mask, float* dqkv, int B, int T, int H, int dh,
                            float scale, float p_drop, void* stream) {
-  switch (products) {
-    case PE_PROD_NATIVE:
-      return attn_bwd_impl<false>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
-    case PE_PROD_BF16:
-      return attn_bwd_impl<true>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
-    default: return pe_unserved(products);
-  }
+  return pe::with_form<kAttnForms, false>(products, 0, [&](auto f) {
+    return attn_bwd_impl<decltype(f)>(qkv, ld_qkv, o, d_o, ld_o, lse, mask, dqkv, B, T, H, dh, scale, p_drop, stream);
+  });
 }

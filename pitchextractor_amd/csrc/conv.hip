@@ -8,7 +8,7 @@
 //       pixels split across workgroups, per-split slabs reduced in a fixed order -> deterministic);
 //   first layer (Cin = 1, model.py:24): 9 FMAs per output, HBM-bound on the 64-channel write.
 #include <type_traits>
-#include "gemm_engine.h"
+#include "forms.h"
 
 namespace {
 using namespace pe;
@@ -81,17 +81,17 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvLoader<TL::A_LOADS, TA
   for_each_acc<TL>(acc, [&](int r, int c, float v) { ep(m0 + r, n0 + c, MODE == kSplit2 ? hs.unscale(v) : v); });
 }
 
-template <class TL, int MODE, class TA = float, class TH = __bf16>
+template <class TL, class FM, class TA = typename FM::TA>
 int launch_conv(const TA* x, const float* wp, TA* y, int B, int T, int F, int C, int N, int accumulate,
-                hipStream_t st, const unsigned* amax_x = nullptr, const unsigned* amax_w = nullptr) {
+                hipStream_t st, const unsigned* amax_x, const unsigned* amax_w) {
   const int rows = B * T * F, K = 9 * C;
   ConvLoader<TL::A_LOADS, TA> al;
   al.p = x; al.T = T; al.F = F; al.C = C; al.rows = rows;
   RowLoader bl{wp, (long)K, N, K, 0};
   ConvEpiT<TA> ep{y, rows, N, accumulate, nullptr};
   const int tm = pe_cdiv(rows, TL::BM), tn = pe_cdiv(N, TL::BN);
-  hipLaunchKernelGGL((conv3x3_kernel<TL, MODE, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn, amax_x,
-                     amax_w);
+  hipLaunchKernelGGL((conv3x3_kernel<TL, FM::MODE, TA, typename FM::TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K,
+                     tm, tn, amax_x, amax_w);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
@@ -351,15 +351,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
   }
 }
 
-template <int BN, int MODE, int PASSES, int D, bool FA2, class TA = float, class TH = __bf16>
+template <int BN, class FM, int PASSES, int D, bool FA2, class TA = typename FM::TA>
 int launch_conv_halo_wf(const TA* x, const void* wf, TA* y, int B, int T, int F, int C, int N, int accumulate,
-                        double* stats, hipStream_t st, const unsigned* amax_x = nullptr,
-                        const unsigned* amax_w = nullptr) {
+                        double* stats, hipStream_t st, const unsigned* amax_x, const unsigned* amax_w) {
   const int P = B * T * F;
   ConvEpiT<TA> ep{y, P, N, accumulate, stats};
   const int tm = pe_cdiv(P, 128), tn = pe_cdiv(N, BN);
-  hipLaunchKernelGGL((conv3x3_halo_wf_kernel<BN, MODE, PASSES, D, FA2, TA, TH>), dim3(tm * tn), dim3(256), 0, st, x,
-                     reinterpret_cast<const uint4*>(wf), ep, T, F, C, N, P, tm, tn, amax_x, amax_w);
+  hipLaunchKernelGGL((conv3x3_halo_wf_kernel<BN, FM::MODE, PASSES, D, FA2, TA, typename FM::TH>), dim3(tm * tn),
+                     dim3(256), 0, st, x, reinterpret_cast<const uint4*>(wf), ep, T, F, C, N, P, tm, tn, amax_x, amax_w);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
@@ -905,80 +904,57 @@ extern "C" int pe_transpose2d(const float* in, float* out, int rows, int cols, v
   return PE_OK;
 }
 
-template <int MODE, class TA = float, class TH = __bf16>
+template <class FM, class TA = typename FM::TA>
 static int conv3x3_fwd_impl(const TA* x, const float* w_packed, TA* y, int B, int T, int F, int C, int N,
-                            int accumulate, void* stream, const unsigned* amax_x = nullptr,
-                            const unsigned* amax_w = nullptr) {
+                            int accumulate, void* stream, const unsigned* amax_x, const unsigned* amax_w) {
+  constexpr int MODE = FM::MODE;
   if (!x || !w_packed || !y || B <= 0 || T <= 0 || F <= 0 || C <= 0 || N <= 0) return PE_E_ARG;
   if ((C % 32) != 0 || (long)B * T * F * (C > N ? C : N) >= (1L << 31)) return PE_E_UNSUPPORTED;
   if (MODE == kSplit2 && (!amax_x || !amax_w)) return PE_E_ARG;
   hipStream_t st = pe_stream(stream);
   if (N <= 64)
-    return launch_conv<Tile<256, 64, 4, 1>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
+    return launch_conv<Tile<256, 64, 4, 1>, FM>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
   if (N % 192 == 0 && N % 128 != 0)
-    return launch_conv<Tile<128, 192, 2, 2>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
-  return launch_conv<Tile<128, 128, 2, 2>, MODE, TA, TH>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
+    return launch_conv<Tile<128, 192, 2, 2>, FM>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
+  return launch_conv<Tile<128, 128, 2, 2>, FM>(x, w_packed, y, B, T, F, C, N, accumulate, st, amax_x, amax_w);
 }
 
 extern "C" int pe_conv3x3_fwd(int products, int act16, const void* x, const float* w_packed, void* y, int B, int T, int F,
                               int C, int N, int accumulate, const unsigned* amax_x, const unsigned* amax_w, void* stream) {
-  if (act16) {   // x and y are bf16 tensors in HBM
-    if (products != PE_PROD_BF16) return pe_unserved(products);
-    return conv3x3_fwd_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), w_packed, static_cast<act16_t*>(y), B, T, F,
-                                            C, N, accumulate, stream);
-  }
-  const float* xf = static_cast<const float*>(x);
-  float* yf = static_cast<float*>(y);
-  switch (products) {
-    case PE_PROD_NATIVE: return conv3x3_fwd_impl<kNative>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
-    case PE_PROD_X3: return conv3x3_fwd_impl<kSplit>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
-    case PE_PROD_H2:
-      return conv3x3_fwd_impl<kSplit2>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream, amax_x, amax_w);
-    case PE_PROD_BF16: return conv3x3_fwd_impl<kBf16>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
-    case PE_PROD_F16:
-      return conv3x3_fwd_impl<kBf16, float, _Float16>(xf, w_packed, yf, B, T, F, C, N, accumulate, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kAllForms, true>(products, act16, [&](auto f) {   // act16: x and y are bf16 tensors in HBM
+    using TA = typename decltype(f)::TA;
+    return conv3x3_fwd_impl<decltype(f)>(static_cast<const TA*>(x), w_packed, static_cast<TA*>(y), B, T, F, C, N,
+                                         accumulate, stream, amax_x, amax_w);
+  });
 }
 
 // ---- weights pre-packed as MFMA fragments (x3: three bf16 terms; h2: two scaled fp16 terms; bf16 / fp16: one rounded
 // term).  Native fp32 products have no fragment form.
-static int wfrag_terms(int products) {
-  switch (products) {
-    case PE_PROD_X3: return 3;
-    case PE_PROD_H2: return 2;
-    case PE_PROD_BF16: case PE_PROD_F16: return 1;
-    default: return 0;
-  }
-}
-
 extern "C" size_t pe_wfrag_bytes(int products, int N, int K) {
-  const int terms = wfrag_terms(products);
-  if (N <= 0 || K <= 0 || (K & 15) || terms == 0) return 0;
-  return pe_wfrag_bytes_host(N, K, terms);
+  if (N <= 0 || K <= 0 || (K & 15)) return 0;
+  // the terms of a served form, or pe_unserved's negative status
+  const int terms = with_form<kTermForms, false>(products, 0, [](auto f) { return mode_terms<decltype(f)::MODE>(); });
+  return terms > 0 ? pe_wfrag_bytes_host(N, K, terms) : 0;
 }
 
-// TERMS = 2: the scale comes from *amax (pe_absmax of w); TH: the type of the one rounded term (TERMS = 1)
-template <int TERMS, class TH = __bf16>
+// h2: the scale comes from *amax (pe_absmax of w)
+template <class FM>
 static int wfrag_pack_impl(const float* w, long ld, int N, int K, const unsigned* amax, void* out, void* stream) {
+  constexpr int TERMS = mode_terms<FM::MODE>();
   if (!w || !out || N <= 0 || K <= 0 || ld < K || (TERMS == 2 && !amax)) return PE_E_ARG;
   if ((K & 15) || (ld & 3)) return PE_E_UNSUPPORTED;
   const long threads = (long)((N + 31) / 32) * (K / 16) * 64;
-  hipLaunchKernelGGL((wfrag_pack_kernel<TERMS, TH>), dim3(pe_cdiv(threads, 256)), dim3(256), 0, pe_stream(stream), w, ld,
-                     N, K, reinterpret_cast<uint4*>(out), TERMS == 2 ? amax : nullptr);
+  hipLaunchKernelGGL((wfrag_pack_kernel<TERMS, typename FM::TH>), dim3(pe_cdiv(threads, 256)), dim3(256), 0,
+                     pe_stream(stream), w, ld, N, K, reinterpret_cast<uint4*>(out), TERMS == 2 ? amax : nullptr);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
 
 extern "C" int pe_wfrag_pack(int products, const float* w, long ld, int N, int K, const unsigned* amax, void* wfrag,
                              void* stream) {
-  switch (products) {
-    case PE_PROD_X3: return wfrag_pack_impl<3>(w, ld, N, K, amax, wfrag, stream);
-    case PE_PROD_H2: return wfrag_pack_impl<2>(w, ld, N, K, amax, wfrag, stream);
-    case PE_PROD_BF16: return wfrag_pack_impl<1>(w, ld, N, K, amax, wfrag, stream);
-    case PE_PROD_F16: return wfrag_pack_impl<1, _Float16>(w, ld, N, K, amax, wfrag, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kTermForms, false>(products, 0, [&](auto f) {
+    return wfrag_pack_impl<decltype(f)>(w, ld, N, K, amax, wfrag, stream);
+  });
 }
 
 extern "C" int pe_conv3x3_wf_supported(int F, int C, int N) {
@@ -988,10 +964,11 @@ extern "C" int pe_conv3x3_wf_supported(int F, int C, int N) {
 // number of per-tile BatchNorm partials pe_conv3x3_fwd_wf writes: bn_partials is [parts][2][N] doubles
 extern "C" int pe_conv3x3_wf_stat_parts(int B, int T, int F) { return pe_cdiv((long)B * T * F, 128); }
 
-template <int MODE, class TA = float, class TH = __bf16>
+template <class FM, class TA = typename FM::TA>
 static int conv3x3_fwd_wf_impl(const TA* x, const void* wfrag, TA* y, int B, int T, int F, int C, int N,
-                               int accumulate, double* stats, void* stream, const unsigned* amax_x = nullptr,
-                               const unsigned* amax_w = nullptr) {
+                               int accumulate, double* stats, void* stream, const unsigned* amax_x,
+                               const unsigned* amax_w) {
+  constexpr int MODE = FM::MODE;
   if (!x || !wfrag || !y || B <= 0 || T <= 0 || F <= 0 || C <= 0 || N <= 0) return PE_E_ARG;
   if ((C % 32) != 0 || (long)B * T * F * (C > N ? C : N) >= (1L << 31)) return PE_E_UNSUPPORTED;
   // the kernel addresses x and the fragment buffer through 32-bit buffer offsets, out-of-range = past 2 GiB
@@ -1001,14 +978,12 @@ static int conv3x3_fwd_wf_impl(const TA* x, const void* wfrag, TA* y, int B, int
   hipStream_t st = pe_stream(stream);
   const int passes = conv_halo_passes(F, N);
   if (passes == 10)
-    return launch_conv_halo_wf<64, MODE, 10, 6, true, TA, TH>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
-                                                          amax_w);
+    return launch_conv_halo_wf<64, FM, 10, 6, true>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x, amax_w);
   if (passes == 7) {
     if (N % 192 == 0 && N % 128 != 0)
-      return launch_conv_halo_wf<192, MODE, 7, 3, false, TA, TH>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
-                                                             amax_w);
-    return launch_conv_halo_wf<128, MODE, 7, 3, true, TA, TH>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
-                                                          amax_w);
+      return launch_conv_halo_wf<192, FM, 7, 3, false>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x,
+                                                       amax_w);
+    return launch_conv_halo_wf<128, FM, 7, 3, true>(x, wfrag, y, B, T, F, C, N, accumulate, stats, st, amax_x, amax_w);
   }
   return PE_E_UNSUPPORTED;
 }
@@ -1016,22 +991,11 @@ static int conv3x3_fwd_wf_impl(const TA* x, const void* wfrag, TA* y, int B, int
 extern "C" int pe_conv3x3_fwd_wf(int products, int act16, const void* x, const void* wfrag, void* y, int B, int T, int F,
                                  int C, int N, int accumulate, double* bn_partials, const unsigned* amax_x,
                                  const unsigned* amax_w, void* stream) {
-  if (act16) {
-    if (products != PE_PROD_BF16) return pe_unserved(products);
-    return conv3x3_fwd_wf_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), wfrag, static_cast<act16_t*>(y), B, T, F,
-                                               C, N, accumulate, bn_partials, stream);
-  }
-  const float* xf = static_cast<const float*>(x);
-  float* yf = static_cast<float*>(y);
-  switch (products) {
-    case PE_PROD_X3: return conv3x3_fwd_wf_impl<kSplit>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream);
-    case PE_PROD_H2:
-      return conv3x3_fwd_wf_impl<kSplit2>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream, amax_x, amax_w);
-    case PE_PROD_BF16: return conv3x3_fwd_wf_impl<kBf16>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream);
-    case PE_PROD_F16:
-      return conv3x3_fwd_wf_impl<kBf16, float, _Float16>(xf, wfrag, yf, B, T, F, C, N, accumulate, bn_partials, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kTermForms, true>(products, act16, [&](auto f) {   // native fp32 products have no fragment form
+    using TA = typename decltype(f)::TA;
+    return conv3x3_fwd_wf_impl<decltype(f)>(static_cast<const TA*>(x), wfrag, static_cast<TA*>(y), B, T, F, C, N,
+                                            accumulate, bn_partials, stream, amax_x, amax_w);
+  });
 }
 
 extern "C" size_t pe_conv3x3_wgrad_workspace_bytes(int B, int T, int F, int Cin, int Cout) {
@@ -1041,10 +1005,12 @@ extern "C" size_t pe_conv3x3_wgrad_workspace_bytes(int B, int T, int F, int Cin,
   return (size_t)splits * 9 * Cout * Cin * sizeof(float);
 }
 
-template <int MODE, class TA = float, class TH = __bf16>
+template <class FM, class TA = typename FM::TA>
 static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, int T, int F, int Cin,
                               int Cout, float* workspace, size_t workspace_bytes, void* stream,
-                              const unsigned* amax_x = nullptr, const unsigned* amax_dy = nullptr) {
+                              const unsigned* amax_x, const unsigned* amax_dy) {
+  constexpr int MODE = FM::MODE;
+  using TH = typename FM::TH;
   if (!x || !dy || !dw_oihw || B <= 0 || T <= 0 || F <= 0 || Cin <= 0 || Cout <= 0) return PE_E_ARG;
   if (MODE == kSplit2 && (!amax_x || !amax_dy)) return PE_E_ARG;
   if ((Cin & 3) || (Cout & 3)) return PE_E_UNSUPPORTED;
@@ -1058,13 +1024,13 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
     const bool halo = wgrad9_halo(F);
     if (MODE == kSplit)
       hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<3, true, TA> : conv3x3_wgrad9_x3_kernel<3, false, TA>), grid,
-                         dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
+                         dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
     else if (MODE == kSplit2)
       hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<2, true, TA> : conv3x3_wgrad9_x3_kernel<2, false, TA>), grid,
                          dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
     else if (MODE == kBf16)
       hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<1, true, TA, TH> : conv3x3_wgrad9_x3_kernel<1, false, TA, TH>),
-                         grid, dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, nullptr, nullptr);
+                         grid, dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
     else if constexpr (std::is_same<TA, float>::value)
       hipLaunchKernelGGL(conv3x3_wgrad9_kernel<0>, dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
                          workspace, T, F, Cin, Cout, P, kps, tn);
@@ -1088,28 +1054,11 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
 extern "C" int pe_conv3x3_wgrad(int products, int act16, const void* x, const void* dy, float* dw_oihw, int B, int T, int F,
                                 int Cin, int Cout, float* workspace, size_t workspace_bytes, const unsigned* amax_x,
                                 const unsigned* amax_dy, void* stream) {
-  if (act16) {   // x and dy are bf16 tensors in HBM
-    if (products != PE_PROD_BF16) return pe_unserved(products);
-    return conv3x3_wgrad_impl<kBf16, act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), dw_oihw,
-                                              B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-  }
-  const float* xf = static_cast<const float*>(x);
-  const float* dyf = static_cast<const float*>(dy);
-  switch (products) {
-    case PE_PROD_NATIVE:
-      return conv3x3_wgrad_impl<kNative>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-    case PE_PROD_X3:
-      return conv3x3_wgrad_impl<kSplit>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-    case PE_PROD_H2:
-      return conv3x3_wgrad_impl<kSplit2>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream, amax_x,
-                                         amax_dy);
-    case PE_PROD_BF16:
-      return conv3x3_wgrad_impl<kBf16>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes, stream);
-    case PE_PROD_F16:
-      return conv3x3_wgrad_impl<kBf16, float, _Float16>(xf, dyf, dw_oihw, B, T, F, Cin, Cout, workspace, workspace_bytes,
-                                                        stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kAllForms, true>(products, act16, [&](auto f) {   // act16: x and dy are bf16 tensors in HBM
+    using TA = typename decltype(f)::TA;
+    return conv3x3_wgrad_impl<decltype(f)>(static_cast<const TA*>(x), static_cast<const TA*>(dy), dw_oihw, B, T, F, Cin,
+                                           Cout, workspace, workspace_bytes, stream, amax_x, amax_dy);
+  });
 }
 
 static int c1_grid(int B, int T, int F) {
@@ -1138,9 +1087,10 @@ static int conv3x3_c1_fwd_impl(const float* x, long sb, long st, long sf, const 
 
 extern "C" int pe_conv3x3_c1_fwd(int act16, const float* x, long sb, long st, long sf, const float* w_oihw, void* y, int B,
                                  int T, int F, double* bn_partials, void* stream) {
-  if (act16)
-    return conv3x3_c1_fwd_impl<act16_t>(x, sb, st, sf, w_oihw, static_cast<act16_t*>(y), B, T, F, bn_partials, stream);
-  return conv3x3_c1_fwd_impl<float>(x, sb, st, sf, w_oihw, static_cast<float*>(y), B, T, F, bn_partials, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return conv3x3_c1_fwd_impl(x, sb, st, sf, w_oihw, static_cast<TA*>(y), B, T, F, bn_partials, stream);
+  });
 }
 
 template <class TA>
@@ -1160,9 +1110,9 @@ static int conv3x3_c1_wgrad_impl(const float* x, long sb, long st, long sf, cons
 
 extern "C" int pe_conv3x3_c1_wgrad(int act16, const float* x, long sb, long st, long sf, const void* dy, float* dw_oihw,
                                    int B, int T, int F, float* workspace, size_t workspace_bytes, void* stream) {
-  if (act16)
-    return conv3x3_c1_wgrad_impl<act16_t>(x, sb, st, sf, static_cast<const act16_t*>(dy), dw_oihw, B, T, F, workspace,
-                                          workspace_bytes, stream);
-  return conv3x3_c1_wgrad_impl<float>(x, sb, st, sf, static_cast<const float*>(dy), dw_oihw, B, T, F, workspace,
-                                      workspace_bytes, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return conv3x3_c1_wgrad_impl(x, sb, st, sf, static_cast<const TA*>(dy), dw_oihw, B, T, F, workspace, workspace_bytes,
+                                 stream);
+  });
 }

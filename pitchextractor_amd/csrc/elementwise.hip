@@ -4,7 +4,7 @@
 // the detector-branch max-pools (model.py:45-49), dropout (model.py:40,56) and the
 // (B,256,T,2) -> (B,T,512) re-layout of model.py:93,112.  Everything moves float4 (4 channels).
 #include <type_traits>
-#include "act16.h"
+#include "forms.h"
 
 namespace {
 using namespace pe;
@@ -652,12 +652,11 @@ extern "C" int pe_bn_train_stats(int act16, const void* x, long n_pix, int C, co
                                  float eps, float momentum, float* running_mean, float* running_var, float* mean,
                                  float* invstd, float* scale, float* shift, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-  if (act16)
-    return bn_train_stats_impl<act16_t>(static_cast<const act16_t*>(x), n_pix, C, gamma, beta, eps, momentum,
-                                        running_mean, running_var, mean, invstd, scale, shift, workspace,
-                                        workspace_bytes, stream);
-  return bn_train_stats_impl<float>(static_cast<const float*>(x), n_pix, C, gamma, beta, eps, momentum, running_mean,
-                                    running_var, mean, invstd, scale, shift, workspace, workspace_bytes, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return bn_train_stats_impl(static_cast<const TA*>(x), n_pix, C, gamma, beta, eps, momentum, running_mean,
+                               running_var, mean, invstd, scale, shift, workspace, workspace_bytes, stream);
+  });
 }
 
 // BatchNorm training statistics from partials a producer kernel left behind ([nparts][2][C] doubles: column sums
@@ -713,11 +712,11 @@ static int bn_act_pool_fwd_impl(const TA* x, const float* scale, const float* sh
 extern "C" int pe_bn_act_pool_fwd(int act16, const void* x, const float* scale, const float* shift, float slope, void* y,
                                   long rows, int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out,
                                   void* stream) {
-  if (act16)
-    return bn_act_pool_fwd_impl<act16_t>(static_cast<const act16_t*>(x), scale, shift, slope, static_cast<act16_t*>(y),
-                                         rows, Fin, C, pool, ldy, coff, amax_out, stream);
-  return bn_act_pool_fwd_impl<float>(static_cast<const float*>(x), scale, shift, slope, static_cast<float*>(y), rows, Fin,
-                                     C, pool, ldy, coff, amax_out, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return bn_act_pool_fwd_impl(static_cast<const TA*>(x), scale, shift, slope, static_cast<TA*>(y), rows, Fin, C, pool,
+                                ldy, coff, amax_out, stream);
+  });
 }
 
 template <class TA>
@@ -774,13 +773,12 @@ extern "C" int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, cons
                                   const float* mean, const float* invstd, float slope, void* dx, float* dgamma,
                                   float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
                                   void* workspace, size_t workspace_bytes, unsigned* amax_out, void* stream) {
-  if (act16)
-    return bn_act_pool_bwd_impl<act16_t>(static_cast<const act16_t*>(x), static_cast<const act16_t*>(dy), scale, shift,
-                                         mean, invstd, slope, static_cast<act16_t*>(dx), dgamma, dbeta, rows, Fin, C,
-                                         pool, lddy, coff, workspace, workspace_bytes, amax_out, stream);
-  return bn_act_pool_bwd_impl<float>(static_cast<const float*>(x), static_cast<const float*>(dy), scale, shift, mean,
-                                     invstd, slope, static_cast<float*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy,
-                                     coff, workspace, workspace_bytes, amax_out, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return bn_act_pool_bwd_impl(static_cast<const TA*>(x), static_cast<const TA*>(dy), scale, shift, mean, invstd, slope,
+                                static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, workspace,
+                                workspace_bytes, amax_out, stream);
+  });
 }
 
 template <class TA>
@@ -797,11 +795,11 @@ static int maxpool_fwd_impl(const TA* x, TA* y, long rows, int Fin, int C, int p
 
 extern "C" int pe_maxpool_fwd(int act16, const void* x, void* y, long rows, int Fin, int C, int pool, long ldy, int coff,
                               unsigned char* argmax_out, void* stream) {
-  if (act16)
-    return maxpool_fwd_impl<act16_t>(static_cast<const act16_t*>(x), static_cast<act16_t*>(y), rows, Fin, C, pool, ldy,
-                                     coff, argmax_out, stream);
-  return maxpool_fwd_impl<float>(static_cast<const float*>(x), static_cast<float*>(y), rows, Fin, C, pool, ldy, coff,
-                                 argmax_out, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return maxpool_fwd_impl(static_cast<const TA*>(x), static_cast<TA*>(y), rows, Fin, C, pool, ldy, coff, argmax_out,
+                            stream);
+  });
 }
 
 template <class TA>
@@ -819,11 +817,11 @@ static int maxpool_bwd_add_impl(const TA* x, const unsigned char* argmax, const 
 extern "C" int pe_maxpool_bwd_add(int act16, const void* x, const unsigned char* argmax, const void* dy, void* dx,
                                   long rows, int Fin, int C, int pool, long lddy, int coff, unsigned* amax_out,
                                   void* stream) {
-  if (act16)
-    return maxpool_bwd_add_impl<act16_t>(static_cast<const act16_t*>(x), argmax, static_cast<const act16_t*>(dy),
-                                         static_cast<act16_t*>(dx), rows, Fin, C, pool, lddy, coff, amax_out, stream);
-  return maxpool_bwd_add_impl<float>(static_cast<const float*>(x), argmax, static_cast<const float*>(dy),
-                                     static_cast<float*>(dx), rows, Fin, C, pool, lddy, coff, amax_out, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return maxpool_bwd_add_impl(static_cast<const TA*>(x), argmax, static_cast<const TA*>(dy), static_cast<TA*>(dx),
+                                rows, Fin, C, pool, lddy, coff, amax_out, stream);
+  });
 }
 
 template <class TA>
@@ -841,11 +839,11 @@ static int dropout_fwd_impl(const TA* x, long ldx, TA* y, long ldy, const unsign
 extern "C" int pe_dropout_fwd(int act16, const void* x, long ldx, void* y, long ldy, const unsigned char* mask_in,
                               unsigned char* mask_out, long rows, int cols, float p, unsigned long long seed,
                               unsigned long long offset, void* stream) {
-  if (act16)
-    return dropout_fwd_impl<act16_t>(static_cast<const act16_t*>(x), ldx, static_cast<act16_t*>(y), ldy, mask_in,
-                                     mask_out, rows, cols, p, seed, offset, stream);
-  return dropout_fwd_impl<float>(static_cast<const float*>(x), ldx, static_cast<float*>(y), ldy, mask_in, mask_out, rows,
-                                 cols, p, seed, offset, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return dropout_fwd_impl(static_cast<const TA*>(x), ldx, static_cast<TA*>(y), ldy, mask_in, mask_out, rows, cols, p,
+                            seed, offset, stream);
+  });
 }
 
 template <class TA>
@@ -858,8 +856,10 @@ static int nhwc_to_seq_impl(const TA* x, long ldx, int coff, float* seq, long ro
 }
 
 extern "C" int pe_nhwc_to_seq(int act16, const void* x, long ldx, int coff, float* seq, long rows, int C, void* stream) {
-  if (act16) return nhwc_to_seq_impl(static_cast<const act16_t*>(x), ldx, coff, seq, rows, C, stream);
-  return nhwc_to_seq_impl(static_cast<const float*>(x), ldx, coff, seq, rows, C, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return nhwc_to_seq_impl(static_cast<const TA*>(x), ldx, coff, seq, rows, C, stream);
+  });
 }
 
 template <class TA>
@@ -873,8 +873,10 @@ static int seq_to_nhwc_impl(const float* seq, TA* x, long ldx, int coff, long ro
 
 extern "C" int pe_seq_to_nhwc(int act16, const float* seq, void* x, long ldx, int coff, long rows, int C, int accumulate,
                               void* stream) {
-  if (act16) return seq_to_nhwc_impl(seq, static_cast<act16_t*>(x), ldx, coff, rows, C, accumulate, stream);
-  return seq_to_nhwc_impl(seq, static_cast<float*>(x), ldx, coff, rows, C, accumulate, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return seq_to_nhwc_impl(seq, static_cast<TA*>(x), ldx, coff, rows, C, accumulate, stream);
+  });
 }
 
 template <class TA>
@@ -889,11 +891,10 @@ static int copy2d_impl(const TA* src, long lds, TA* dst, long ldd, long rows, in
 
 extern "C" int pe_copy2d(int act16, const void* src, long lds, void* dst, long ldd, long rows, int cols, int accumulate,
                          void* stream) {
-  if (act16)
-    return copy2d_impl<act16_t>(static_cast<const act16_t*>(src), lds, static_cast<act16_t*>(dst), ldd, rows, cols,
-                                accumulate, stream);
-  return copy2d_impl<float>(static_cast<const float*>(src), lds, static_cast<float*>(dst), ldd, rows, cols, accumulate,
-                            stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return copy2d_impl(static_cast<const TA*>(src), lds, static_cast<TA*>(dst), ldd, rows, cols, accumulate, stream);
+  });
 }
 
 extern "C" int pe_absmax(const float* x, long rows, int cols, long ld, unsigned* out, void* stream) {

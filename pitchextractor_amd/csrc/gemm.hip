@@ -8,7 +8,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
-#include "gemm_engine.h"
+#include "forms.h"
 
 
 namespace {
@@ -104,9 +104,11 @@ void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, 
     }
 }
 
-template <class TL, int MODE, class TA = float, class TH = __bf16>
+template <class TL, class F, class TA = typename F::TA>
 int launch_nt(const RowLoaderT<TA>& al, const RowLoader& bl, const StoreEpiT<TA>& ep, int M, int N, int K,
-              hipStream_t st, const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr) {
+              hipStream_t st, const unsigned* amax_a, const unsigned* amax_b) {
+  constexpr int MODE = F::MODE;
+  using TH = typename F::TH;
   const int tm = pe_cdiv(M, TL::BM), tn = pe_cdiv(N, TL::BN);
   const bool vec = MODE != kNative && (N & 3) == 0 && (ep.ldc & 3) == 0 &&
                    (reinterpret_cast<uintptr_t>(ep.C) & (4 * sizeof(TA) - 1)) == 0;
@@ -183,10 +185,12 @@ void tn_plan(int M, int N, int K, int bm, int bn, int mode, int* splits, int* k_
   *k_per_split = kps;
 }
 
-template <int BM, int BN, int MODE, class TA = float, class TH = __bf16>
+template <int BM, int BN, class F, class TA = typename F::TA>
 int launch_tn(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, int M, int N, int K,
-              int accumulate, float* ws, size_t ws_bytes, hipStream_t st, const unsigned* amax_a = nullptr,
-              const unsigned* amax_b = nullptr) {
+              int accumulate, float* ws, size_t ws_bytes, hipStream_t st, const unsigned* amax_a,
+              const unsigned* amax_b) {
+  constexpr int MODE = F::MODE;
+  using TH = typename F::TH;
   int splits, kps;
   tn_plan(M, N, K, BM, BN, MODE, &splits, &kps);
   KRowLoader<BM, TA> al{A, lda, M, 0};
@@ -212,10 +216,11 @@ int launch_tn(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, 
 
 }  // namespace
 
-template <int MODE, class TA = float, class TH = __bf16>
+template <class F, class TA = typename F::TA>
 static int gemm_nt_impl(const TA* A, long lda, const float* B, long ldb, TA* C, long ldc, int M, int N,
                         int K, const float* bias0, const float* bias1, int accumulate, void* stream,
-                        const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr) {
+                        const unsigned* amax_a, const unsigned* amax_b) {
+  constexpr int MODE = F::MODE;
   if (!A || !B || !C || M < 0 || N < 0 || K <= 0) return PE_E_ARG;
   if (MODE == kSplit2 && (!amax_a || !amax_b)) return PE_E_ARG;
   if (M == 0 || N == 0) return PE_OK;
@@ -227,33 +232,22 @@ static int gemm_nt_impl(const TA* A, long lda, const float* B, long ldb, TA* C, 
   RowLoader bl{B, ldb, N, K, 0};
   StoreEpiT<TA> ep{C, ldc, bias0, bias1, M, N, accumulate};
   hipStream_t st = pe_stream(stream);
-  if (N <= 32) return launch_nt<Tile<128, 32, 4, 1>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
-  if (N <= 64) return launch_nt<Tile<256, 64, 4, 1>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+  if (N <= 32) return launch_nt<Tile<128, 32, 4, 1>, F>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+  if (N <= 64) return launch_nt<Tile<256, 64, 4, 1>, F>(al, bl, ep, M, N, K, st, amax_a, amax_b);
   if (N % 192 == 0 && (N % 128 != 0 || MODE != kNative))   // 16-bit-term modes: the wider tile stages 17 % fewer rows per MFMA
-    return launch_nt<Tile<128, 192, 2, 2>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
-  return launch_nt<Tile<128, 128, 2, 2>, MODE, TA, TH>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+    return launch_nt<Tile<128, 192, 2, 2>, F>(al, bl, ep, M, N, K, st, amax_a, amax_b);
+  return launch_nt<Tile<128, 128, 2, 2>, F>(al, bl, ep, M, N, K, st, amax_a, amax_b);
 }
 
 extern "C" int pe_gemm_nt(int products, int act16, const void* A, long lda, const float* B, long ldb, void* C, long ldc,
                           int M, int N, int K, const float* bias0, const float* bias1, int accumulate,
                           const unsigned* amax_a, const unsigned* amax_b, void* stream) {
-  if (act16) {   // bf16 ACTIVATION STORAGE: A and C are bf16 tensors in HBM (weights and biases stay fp32)
-    if (products != PE_PROD_BF16) return pe_unserved(products);
-    return gemm_nt_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, B, ldb, static_cast<act16_t*>(C), ldc, M,
-                                        N, K, bias0, bias1, accumulate, stream);
-  }
-  const float* a = static_cast<const float*>(A);
-  float* c = static_cast<float*>(C);
-  switch (products) {
-    case PE_PROD_NATIVE: return gemm_nt_impl<kNative>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
-    case PE_PROD_X3: return gemm_nt_impl<kSplit>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
-    case PE_PROD_H2:
-      return gemm_nt_impl<kSplit2>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream, amax_a, amax_b);
-    case PE_PROD_BF16: return gemm_nt_impl<kBf16>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
-    case PE_PROD_F16:
-      return gemm_nt_impl<kBf16, float, _Float16>(a, lda, B, ldb, c, ldc, M, N, K, bias0, bias1, accumulate, stream);
-    default: return pe_unserved(products);
-  }
+  // act16: bf16 ACTIVATION STORAGE, A and C are bf16 tensors in HBM (weights and biases stay fp32)
+  return with_form<kAllForms, true>(products, act16, [&](auto f) {
+    using TA = typename decltype(f)::TA;
+    return gemm_nt_impl<decltype(f)>(static_cast<const TA*>(A), lda, B, ldb, static_cast<TA*>(C), ldc, M, N, K, bias0,
+                                     bias1, accumulate, stream, amax_a, amax_b);
+  });
 }
 
 extern "C" size_t pe_gemm_tn_workspace_bytes(int M, int N, int K) {
@@ -268,10 +262,11 @@ extern "C" size_t pe_gemm_tn_workspace_bytes(int M, int N, int K) {
   return need;
 }
 
-template <int MODE, class TA = float, class TH = __bf16>
+template <class F, class TA = typename F::TA>
 static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, int M, int N,
                         int K, int accumulate, float* workspace, size_t workspace_bytes, void* stream,
-                        const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr) {
+                        const unsigned* amax_a, const unsigned* amax_b) {
+  constexpr int MODE = F::MODE;
   if (!A || !B || !C || M < 0 || N < 0 || K <= 0) return PE_E_ARG;
   if (MODE == kSplit2 && (!amax_a || !amax_b)) return PE_E_ARG;
   if (M == 0 || N == 0) return PE_OK;
@@ -281,41 +276,24 @@ static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, 
   if (lda < 0 || ldb < 0 || lda >= (1L << 24) || ldb >= (1L << 24)) return PE_E_UNSUPPORTED;   // 32-bit offsets per k-tile
   hipStream_t st = pe_stream(stream);
   if (M <= 64 && N <= 64)
-    return launch_tn<64, 64, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                   amax_b);
+    return launch_tn<64, 64, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+                                amax_b);
   if (M <= 64)
-    return launch_tn<64, 128, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                    amax_b);
+    return launch_tn<64, 128, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+                                 amax_b);
   if (N <= 64)
-    return launch_tn<128, 64, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                    amax_b);
-  return launch_tn<128, 128, MODE, TA, TH>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                   amax_b);
+    return launch_tn<128, 64, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+                                 amax_b);
+  return launch_tn<128, 128, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
+                                amax_b);
 }
 
 extern "C" int pe_gemm_tn(int products, int act16, const void* A, long lda, const void* B, long ldb, float* C, long ldc,
                           int M, int N, int K, int accumulate, float* workspace, size_t workspace_bytes,
                           const unsigned* amax_a, const unsigned* amax_b, void* stream) {
-  if (act16) {   // A and B are bf16 tensors in HBM
-    if (products != PE_PROD_BF16) return pe_unserved(products);
-    return gemm_tn_impl<kBf16, act16_t>(static_cast<const act16_t*>(A), lda, static_cast<const act16_t*>(B), ldb, C, ldc,
-                                        M, N, K, accumulate, workspace, workspace_bytes, stream);
-  }
-  const float* a = static_cast<const float*>(A);
-  const float* b = static_cast<const float*>(B);
-  switch (products) {
-    case PE_PROD_NATIVE:
-      return gemm_tn_impl<kNative>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
-    case PE_PROD_X3:
-      return gemm_tn_impl<kSplit>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
-    case PE_PROD_H2:
-      return gemm_tn_impl<kSplit2>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream,
-                                   amax_a, amax_b);
-    case PE_PROD_BF16:
-      return gemm_tn_impl<kBf16>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, stream);
-    case PE_PROD_F16:
-      return gemm_tn_impl<kBf16, float, _Float16>(a, lda, b, ldb, C, ldc, M, N, K, accumulate, workspace,
-                                                  workspace_bytes, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kAllForms, true>(products, act16, [&](auto f) {   // act16: A and B are bf16 tensors in HBM
+    using TA = typename decltype(f)::TA;
+    return gemm_tn_impl<decltype(f)>(static_cast<const TA*>(A), lda, static_cast<const TA*>(B), ldb, C, ldc, M, N, K,
+                                     accumulate, workspace, workspace_bytes, stream, amax_a, amax_b);
+  });
 }

@@ -13,7 +13,7 @@
 //   backward step: dh_t = dY_t + dgates_{t+1}.W_hh  (K = 4H, split 4 ways over the waves of the
 //                  workgroup and reduced in LDS), then the gate derivatives overwrite the
 //                  activations in place, leaving dgates for the batched weight-gradient GEMMs.
-#include "gemm_engine.h"
+#include "forms.h"
 
 namespace {
 using namespace pe;
@@ -347,10 +347,11 @@ extern "C" size_t pe_lstm_whh_grad_workspace_bytes(int B, int T, int H) {
 }
 
 // dW_hh[4H][H] = sum_{b,t} dgates[b][t][:]^T . y[b][t -/+ 1][:]   (y = this direction's output slice)
-template <int MODE, class TH = __bf16>
+template <class F>
 static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
                          int reverse, float* workspace, size_t workspace_bytes, void* stream,
-                         const unsigned* amax_dg = nullptr, const unsigned* amax_y = nullptr) {
+                         const unsigned* amax_dg, const unsigned* amax_y) {
+  constexpr int MODE = F::MODE;
   if (!dgates || !y || !dwhh || B <= 0 || T <= 0 || H <= 0) return PE_E_ARG;
   if (MODE == kSplit2 && (!amax_dg || !amax_y)) return PE_E_ARG;
   if ((H & 3) || (ldy & 3)) return PE_E_UNSUPPORTED;
@@ -364,8 +365,8 @@ static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* d
   bl.p = y; bl.ld = ldy; bl.T = T; bl.dt = reverse ? 1 : -1; bl.cols = N; bl.col0 = 0;
   const int tm = pe_cdiv(M, 128), tn = pe_cdiv(N, 128);
   hipStream_t st = pe_stream(stream);
-  hipLaunchKernelGGL((lstm_whh_grad_kernel<128, 128, MODE, TH>), dim3(tm * tn * splits), dim3(256), 0, st, al, bl,
-                     workspace, (long)N, (long)M * N, M, N, K, kps, tn, amax_dg, amax_y);
+  hipLaunchKernelGGL((lstm_whh_grad_kernel<128, 128, MODE, typename F::TH>), dim3(tm * tn * splits), dim3(256), 0, st,
+                     al, bl, workspace, (long)N, (long)M * N, M, N, K, kps, tn, amax_dg, amax_y);
   PE_LAUNCH_CHECK();
   const long n = (long)M * N;
   hipLaunchKernelGGL(slab_reduce_kernel, dim3(pe_cdiv(n / 4, 256)), dim3(256), 0, st, workspace, n, splits, dwhh);
@@ -376,20 +377,10 @@ static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* d
 extern "C" int pe_lstm_whh_grad(int products, const float* dgates, const float* y, long ldy, float* dwhh, int B, int T,
                                 int H, int reverse, float* workspace, size_t workspace_bytes,
                                 const unsigned* amax_dgates, const unsigned* amax_y, void* stream) {
-  switch (products) {
-    case PE_PROD_NATIVE:
-      return whh_grad_impl<kNative>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-    case PE_PROD_X3:
-      return whh_grad_impl<kSplit>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-    case PE_PROD_H2:
-      return whh_grad_impl<kSplit2>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream,
-                                    amax_dgates, amax_y);
-    case PE_PROD_BF16:
-      return whh_grad_impl<kBf16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-    case PE_PROD_F16:
-      return whh_grad_impl<kBf16, _Float16>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kAllForms, false>(products, 0, [&](auto f) {
+    return whh_grad_impl<decltype(f)>(dgates, y, ldy, dwhh, B, T, H, reverse, workspace, workspace_bytes, stream,
+                                      amax_dgates, amax_y);
+  });
 }
 
 extern "C" size_t pe_colsum_workspace_bytes(int cols) { return (size_t)kColsumParts * cols * sizeof(double); }

@@ -29,7 +29,7 @@
 // twice the cycles.  Everything about the hand-off protocol is identical in both forms.
 #include <stdlib.h>
 #include <type_traits>
-#include "gemm_engine.h"
+#include "forms.h"
 
 namespace {
 using namespace pe;
@@ -1249,8 +1249,9 @@ static bool small_enough(int B, int T, int H, long ld) {
   return (size_t)B * T * 4 * H * sizeof(float) < (1ull << 31) && (size_t)B * T * (size_t)ld * sizeof(float) < (1ull << 31);
 }
 
-// TERMS = 3: the exact three-term bf16 split; 1: operands rounded to TH.  The stamped instances exist for bf16 only.
-template <int TERMS, class TH = __bf16>
+// Terms of the form: 3 = the exact three-term bf16 split; 1 = operands rounded to TH.  The stamped instances exist for
+// bf16 only.
+template <class F>
 static int lstm_fwd_persistent_impl(int ncells, const float* const* whh, float* const* gates,
                                     float* const* y, float* const* cbuf, const int* reverse, long ldy, int B, int T,
                                     int H, unsigned* sync, void* stream) {
@@ -1266,27 +1267,25 @@ static int lstm_fwd_persistent_impl(int ncells, const float* const* whh, float* 
   // word 0 is the sticky error flag (cleared only by the owner of the buffer); counters start at line 1
   PE_CHECK_HIP(hipMemsetAsync(sync + kCtrStride, 0, (size_t)(sync_words(ncells, B) - kCtrStride) * 4, st));
   const int grid = ncells * ((B + 63) / 64) * (H / 32);
-  constexpr int NBR = TERMS == 3 ? 4 : 6;
+  using TH = typename F::TH;
+  constexpr int TERMS = mode_terms<F::MODE>(), NBR = TERMS == 3 ? 4 : 6;
   if constexpr (std::is_same<TH, __bf16>::value)
     if (g_lstm_stamps && grid <= 128) return launch_fwd_v2<384, TERMS, NBR, true>(cells, grid, B, T, ldy, sync, st);
   return launch_fwd_v2<384, TERMS, NBR, false, TH>(cells, grid, B, T, ldy, sync, st);
 }
 
-// Persistent recurrences run 16-bit-term products only: x3 (TERMS = 3) and bf16 / f16 (TERMS = 1).
+// Persistent recurrences run 16-bit-term products only: x3 (three terms) and bf16 / f16 (one).
+constexpr unsigned kPersistentForms = form_bit(PE_PROD_X3) | form_bit(PE_PROD_BF16) | form_bit(PE_PROD_F16);
+
 extern "C" int pe_lstm_fwd_persistent(int products, int ncells, const float* const* whh, float* const* gates,
                                       float* const* y, float* const* cbuf, const int* reverse, long ldy, int B, int T,
                                       int H, unsigned* sync, void* stream) {
-  switch (products) {
-    case PE_PROD_X3: return lstm_fwd_persistent_impl<3>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
-    case PE_PROD_BF16:
-      return lstm_fwd_persistent_impl<1>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
-    case PE_PROD_F16:
-      return lstm_fwd_persistent_impl<1, _Float16>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kPersistentForms, false>(products, 0, [&](auto f) {
+    return lstm_fwd_persistent_impl<decltype(f)>(ncells, whh, gates, y, cbuf, reverse, ldy, B, T, H, sync, stream);
+  });
 }
 
-template <int TERMS, class TH = __bf16>
+template <class F>
 static int lstm_bwd_persistent_impl(int ncells, const float* const* whh_t, float* const* gates,
                                     const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
                                     int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
@@ -1305,7 +1304,8 @@ static int lstm_bwd_persistent_impl(int ncells, const float* const* whh_t, float
   PE_CHECK_HIP(hipMemsetAsync(sync + kCtrStride, 0, (size_t)(sync_words(ncells, B) - kCtrStride) * 4, st));
   PE_CHECK_HIP(hipMemsetAsync(sync + kXchgWord, 0, (size_t)ncells * ((B + 63) / 64) * 128 * sizeof(unsigned), st));
   const int grid = ncells * ((B + 63) / 64) * (H / 32);
-  constexpr int NBR = TERMS == 3 ? 8 : 24;
+  using TH = typename F::TH;
+  constexpr int TERMS = mode_terms<F::MODE>(), NBR = TERMS == 3 ? 8 : 24;
   if constexpr (std::is_same<TH, __bf16>::value)
     if (g_lstm_stamps && grid <= 128) return launch_bwd_v2<384, TERMS, NBR, true>(cells, grid, B, T, lddy, sync, st);
   return launch_bwd_v2<384, TERMS, NBR, false, TH>(cells, grid, B, T, lddy, sync, st);
@@ -1322,16 +1322,8 @@ extern "C" int pe_lstm_bwd_persistent(int products, int ncells, const float* con
                                       const float* const* cbuf, const float* const* dy, const int* reverse, long lddy,
                                       int B, int T, int H, float* const* dbias_rows, unsigned* const* dgates_amax,
                                       unsigned* sync, void* stream) {
-  switch (products) {
-    case PE_PROD_X3:
-      return lstm_bwd_persistent_impl<3>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
-                                         sync, stream);
-    case PE_PROD_BF16:
-      return lstm_bwd_persistent_impl<1>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows, dgates_amax,
-                                         sync, stream);
-    case PE_PROD_F16:
-      return lstm_bwd_persistent_impl<1, _Float16>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows,
-                                                   dgates_amax, sync, stream);
-    default: return pe_unserved(products);
-  }
+  return with_form<kPersistentForms, false>(products, 0, [&](auto f) {
+    return lstm_bwd_persistent_impl<decltype(f)>(ncells, whh_t, gates, cbuf, dy, reverse, lddy, B, T, H, dbias_rows,
+                                                 dgates_amax, sync, stream);
+  });
 }

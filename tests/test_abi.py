@@ -76,3 +76,45 @@ def test_argument_and_form_checks_run_before_any_device_call(lib):
                                       None) == unsupported
     # not a product form
     assert lib.pe_gemm_nt(5, 0, p, 64, p, 64, p, 64, 128, 64, 64, None, None, 0, word, word, None) == bad_arg
+
+
+# Status of each form-taking entry point called with null operands and positive sizes, for products = -1, 0 .. 4, 5:
+# null operands return before any device call, so a served form answers its impl's null check (PE_E_ARG, -1), a valid
+# form that no kernel of the entry point serves PE_E_UNSUPPORTED (-2), a value outside the enum PE_E_ARG.  Second row:
+# the same with act16 = 1, which exists under PE_PROD_BF16 only.
+_ALL = [-1, -1, -1, -1, -1, -1, -1]
+_ACT16 = [-1, -2, -2, -2, -1, -2, -1]
+_TERMS = [-1, -2, -1, -1, -1, -1, -1]              # no native-fp32 fragment form
+_PERSISTENT = [-1, -2, -1, -2, -1, -1, -1]         # x3, bf16, f16
+_ATTN = [-1, -1, -2, -2, -1, -2, -1]               # native, bf16
+# name -> (arguments after `products` [and `act16`], expected with act16 = 0 / absent, expected with act16 = 1 or None)
+_SERVED_FORMS = {
+    "pe_gemm_nt": ((None, 64, None, 64, None, 64, 128, 64, 64, None, None, 0, None, None, None), _ALL, _ACT16),
+    "pe_gemm_tn": ((None, 64, None, 64, None, 64, 64, 64, 64, 0, None, 0, None, None, None), _ALL, _ACT16),
+    "pe_conv3x3_fwd": ((None, None, None, 1, 4, 8, 32, 32, 0, None, None, None), _ALL, _ACT16),
+    "pe_conv3x3_wgrad": ((None, None, None, 1, 4, 8, 32, 32, None, 0, None, None, None), _ALL, _ACT16),
+    "pe_conv3x3_fwd_wf": ((None, None, None, 1, 4, 8, 32, 32, 0, None, None, None, None), _TERMS, _ACT16),
+    "pe_wfrag_pack": ((None, 32, 32, 32, None, None, None), _TERMS, None),
+    "pe_lstm_whh_grad": ((None, None, 384, None, 1, 4, 384, 0, None, 0, None, None, None), _ALL, None),
+    "pe_lstm_fwd_persistent": ((1, None, None, None, None, None, 384, 1, 4, 384, None, None), _PERSISTENT, None),
+    "pe_lstm_bwd_persistent": ((1, None, None, None, None, None, 384, 1, 4, 384, None, None, None, None),
+                               _PERSISTENT, None),
+    "pe_attn_fwd": ((None, 192, None, 64, None, None, None, 1, 192, 1, 64, 0.125, 0.0, 0, 0, None), _ATTN, None),
+    "pe_attn_bwd": ((None, 192, None, None, 64, None, None, None, 1, 192, 1, 64, 0.125, 0.0, None), _ATTN, None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_SERVED_FORMS))
+def test_served_forms_of_every_entry_point(lib, name):
+    args, plain, act16 = _SERVED_FORMS[name]
+    fn = getattr(lib, name)
+    forms = range(-1, 6)
+    if act16 is None:
+        assert [fn(f, *args) for f in forms] == plain
+    else:
+        assert [fn(f, 0, *args) for f in forms] == plain
+        assert [fn(f, 1, *args) for f in forms] == act16
+
+
+def test_fragment_bytes_of_every_form(lib):
+    assert [lib.pe_wfrag_bytes(f, 32, 32) for f in range(-1, 6)] == [0, 0, 6144, 4096, 2048, 2048, 0]
