@@ -58,6 +58,36 @@ template <> __device__ __forceinline__ uint2 ldraw_buffer<act16_t>(__amdgpu_buff
   const u2 d = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
   return make_uint2(d.x, d.y);
 }
+// One output element / quad through a buffer descriptor (epilogues): `voff` in bytes, a request past the descriptor's
+// range reads zero / is dropped, so a tile's overhang costs no branch.  Same bytes as ld1 / st1 / st4.
+// (a load comes back in its storage form; widen1 at the point of use keeps the wait for it out of the issue phase)
+__device__ __forceinline__ unsigned ld1raw_buffer(const float*, __amdgpu_buffer_rsrc_t rs, unsigned voff) {
+  return __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, 0);
+}
+__device__ __forceinline__ unsigned ld1raw_buffer(const act16_t*, __amdgpu_buffer_rsrc_t rs, unsigned voff) {
+  return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs, voff, 0, 0);
+}
+__device__ __forceinline__ float widen1(const float*, unsigned raw) { return __uint_as_float(raw); }
+__device__ __forceinline__ float widen1(const act16_t*, unsigned raw) { return __uint_as_float(raw << 16); }
+__device__ __forceinline__ void st1_buffer(float*, __amdgpu_buffer_rsrc_t rs, unsigned voff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, voff, 0, 0);
+}
+__device__ __forceinline__ void st1_buffer(act16_t*, __amdgpu_buffer_rsrc_t rs, unsigned voff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (act16_t)v), rs, voff, 0, 0);
+}
+__device__ __forceinline__ void st4_buffer(float*, __amdgpu_buffer_rsrc_t rs, unsigned voff, const float4& v) {
+  typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+  const u4 d = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff, 0, 0);
+}
+__device__ __forceinline__ void st4_buffer(act16_t*, __amdgpu_buffer_rsrc_t rs, unsigned voff, const float4& v) {
+  typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+  const u2 d = {pack_bf16_rne(v.x, v.y), pack_bf16_rne(v.z, v.w)};
+  __builtin_amdgcn_raw_buffer_store_b64(d, rs, voff, 0, 0);
+}
+// Offsets of such a descriptor are 32 bits with bit 31 as the "outside" marker: it serves tensors below 2 GiB.
+constexpr unsigned kBufferOutside = 0x80000000u;
+
 template <class R> __device__ __forceinline__ R zero_raw();
 template <> __device__ __forceinline__ float4 zero_raw<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 template <> __device__ __forceinline__ uint2 zero_raw<uint2>() { return make_uint2(0u, 0u); }

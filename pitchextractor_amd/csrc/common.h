@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include "../../include/pitchextractor_hip.h"
 
 #define PE_CHECK_HIP(expr)                              \
@@ -26,6 +28,17 @@ static inline int pe_unserved(int products) {
 }
 
 static inline int pe_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Which epilogue the halo convolution and the transposed NT GEMM run on an output of `out_bytes` bytes: 1 = addressed
+// through a buffer descriptor (32-bit offsets, so the output ends below 2 GiB), 0 = the pointer-addressed form.
+// PE_EPILOGUE=pointer in the environment (read once) forces the pointer form, for tests and A/B runs.
+static inline int pe_epilogue_buffer(long out_bytes) {
+  static const int forced_pointer = [] {
+    const char* e = getenv("PE_EPILOGUE");
+    return e && strcmp(e, "pointer") == 0 ? 1 : 0;
+  }();
+  return !forced_pointer && out_bytes < (1L << 31);
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

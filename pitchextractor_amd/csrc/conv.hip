@@ -46,6 +46,7 @@ struct ConvEpiT {
   TO* Y;
   int rows, N, accumulate;
   double* stats;          // optional [tiles_m][2][N]: per-tile column sums / sums of squares of the final outputs
+  int buffer;             // halo kernel: Y is addressed through a buffer descriptor (pe_epilogue_buffer)
   __device__ __forceinline__ void operator()(int row, int col, float v) const {
     if (row < rows && col < N) {
       TO* d = Y + (long)row * N + col;
@@ -305,26 +306,85 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_wf_kernel(const TA* __res
   // 150,159) are a by-product: per-column sum and sum of squares of the FINAL values (after the residual add) over
   // this tile's 128 pixels, in double, written as one partial per (pixel tile, column) -- the separate 1 GB
   // statistics pass over the activation disappears (pe_bn_finalize_stats sums the partials in a fixed order).
+  //
+  // Element (i, j, g) of a lane is output (row0 + 32 i + (g & 3) + 8 (g >> 2), column n0 + wn WN + 32 j + r), with
+  // row0 = p0 + 64 wm + 4 h.  Buffer form (ep.buffer, outputs below 2 GiB): Y goes through a buffer descriptor of
+  // exactly rows * N elements, so a row past `rows` lies past its range by itself and a column past N is sent there
+  // (kBufferOutside): loads read zero, stores are dropped, no branch per element.  The old values of an accumulate
+  // launch are requested one 32 x 32 block ahead (16 loads, one wait) instead of load - wait - add - store per
+  // element -- vmcnt counts stores too, so each element used to wait for its predecessor's store as well.  accumulate
+  // picks one of two straight-line copies; the statistics of a block sit behind one wave-uniform branch, so a launch
+  // without them runs no f64 instruction.  The sums keep their order: i, j, g, then the lane halves, then wm 0 + 1.
   double s1[TN], s2[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) s1[j] = s2[j] = 0.0;
+  const int row0 = p0 + wm * 64 + 4 * h;
+  auto add_stat = [&](int j, int row, float v) {                   // (a mask, not a branch: rows past the tensor add 0)
+    v = __uint_as_float(__float_as_uint(stored_value<TA>(v)) & (row < ep.rows ? 0xffffffffu : 0u));
+    s1[j] += (double)v;
+    s2[j] += (double)v * (double)v;
+  };
+  const bool stats = ep.stats != nullptr;
+  auto epilogue_buffer = [&](auto acc_tag) {
+    constexpr bool ACC = decltype(acc_tag)::value;
+    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
+        ep.Y, 0, (unsigned)((long)ep.rows * ep.N * (long)sizeof(TA)), 0x00020000);
+    const unsigned rowb = (unsigned)ep.N * (unsigned)sizeof(TA);
+    unsigned vo[TN];
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
+    for (int j = 0; j < TN; ++j) {
+      const int col = n0 + wn * WN + j * 32 + r;
+      vo[j] = col < ep.N ? (unsigned)row0 * rowb + (unsigned)col * (unsigned)sizeof(TA) : kBufferOutside;
+    }
+    auto voff = [&](int i, int j, int g) { return vo[j] + (unsigned)(i * 32 + (g & 3) + 8 * (g >> 2)) * rowb; };
+    unsigned old[2][16];
+    auto fetch_old = [&](int b) {
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
+      for (int g = 0; g < 16; ++g) old[b & 1][g] = ld1raw_buffer(ep.Y, yrs, voff(b / TN, b % TN, g));
+    };
+    if constexpr (ACC) fetch_old(0);
+#pragma unroll
+    for (int b = 0; b < TM * TN; ++b) {
+      const int i = b / TN, j = b % TN;
+      if constexpr (ACC) {
+        if (b + 1 < TM * TN) fetch_old(b + 1);
+        __builtin_amdgcn_sched_barrier(0);                         // keep the next block's loads in front of the stores
+      }
+      float v[16];
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int row = p0 + wm * 64 + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * h, col = n0 + wn * WN + j * 32 + r;
-        if (row < ep.rows && col < ep.N) {
-          TA* d = ep.Y + (long)row * ep.N + col;
-          float v = MODE == kSplit2 ? hs.unscale(acc[i][j][g]) : acc[i][j][g];
-          if (ep.accumulate) v += ld1(d);
-          st1(d, v);
-          v = stored_value<TA>(v);
-          s1[j] += (double)v;
-          s2[j] += (double)v * (double)v;
-        }
+        v[g] = MODE == kSplit2 ? hs.unscale(acc[i][j][g]) : acc[i][j][g];
+        if constexpr (ACC) v[g] += widen1(ep.Y, old[b & 1][g]);
+        st1_buffer(ep.Y, yrs, voff(i, j, g), v[g]);
       }
+      if (stats) {
+#pragma unroll
+        for (int g = 0; g < 16; ++g) add_stat(j, row0 + i * 32 + (g & 3) + 8 * (g >> 2), v[g]);
+      }
+      if constexpr (ACC) __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // pointer form: outputs of 2 GiB and more, PE_EPILOGUE=pointer
+  auto epilogue_pointer = [&]() {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+          const int row = row0 + i * 32 + (g & 3) + 8 * (g >> 2), col = n0 + wn * WN + j * 32 + r;
+          if (row < ep.rows && col < ep.N) {
+            TA* d = ep.Y + (long)row * ep.N + col;
+            float v = MODE == kSplit2 ? hs.unscale(acc[i][j][g]) : acc[i][j][g];
+            if (ep.accumulate) v += ld1(d);
+            st1(d, v);
+            if (stats) add_stat(j, row, v);
+          }
+        }
+  };
+  if (!ep.buffer) epilogue_pointer();
+  else if (ep.accumulate) epilogue_buffer(std::true_type{});
+  else epilogue_buffer(std::false_type{});
   if (ep.stats) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -355,7 +415,8 @@ template <int BN, class FM, int PASSES, int D, bool FA2, class TA = typename FM:
 int launch_conv_halo_wf(const TA* x, const void* wf, TA* y, int B, int T, int F, int C, int N, int accumulate,
                         double* stats, hipStream_t st, const unsigned* amax_x, const unsigned* amax_w) {
   const int P = B * T * F;
-  ConvEpiT<TA> ep{y, P, N, accumulate, stats};
+  // (the descriptor's 32-bit offsets must also hold the rows the last tile hangs over P by)
+  ConvEpiT<TA> ep{y, P, N, accumulate, stats, pe_epilogue_buffer((long)(P + 128) * N * (long)sizeof(TA))};
   const int tm = pe_cdiv(P, 128), tn = pe_cdiv(N, BN);
   hipLaunchKernelGGL((conv3x3_halo_wf_kernel<BN, FM::MODE, PASSES, D, FA2, TA, typename FM::TH>), dim3(tm * tn),
                      dim3(256), 0, st, x, reinterpret_cast<const uint4*>(wf), ep, T, F, C, N, P, tm, tn, amax_x, amax_w);

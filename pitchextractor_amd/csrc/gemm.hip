@@ -59,8 +59,15 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(RowLoaderT<TA> al, RowLoad
 // columns of one row instead of four rows of one column, and the epilogue writes 16-byte pieces (a quarter of the
 // store instructions, bias fetched once per column quad).  Bit-identical sums.  Needs N % 4 == 0 and a 16-byte
 // aligned C with ldc % 4 == 0 (checked by the host).
-template <class TL, int MODE, class TA = float, class TH = __bf16>
-__global__ __launch_bounds__(256, ((MODE == kSplit || MODE == kSplit2) && TL::BM == 128 && TL::BN == 128) ? 3 : 1)
+// BUF picks the epilogue at compile time (with both in one kernel hipcc reads every accumulator out of the AGPRs in
+// front of the choice, which costs the 128 x 128 and 256 x 64 instances their third workgroup per CU).
+// Three workgroups per CU is what the 128 x 128 and 256 x 64 main loops fit (all but the x3 256 x 64 one); the bound
+// keeps the epilogue's loads in flight from taking a register or two more than that allows.
+template <class TL, int MODE> constexpr int nt_t_min_blocks() {
+  return TL::BM * TL::BN == 128 * 128 && !(MODE == kSplit && TL::BM == 256) ? 3 : 1;
+}
+template <class TL, int MODE, bool BUF, class TA = float, class TH = __bf16>
+__global__ __launch_bounds__(256, (nt_t_min_blocks<TL, MODE>()))
 void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, int tiles_m, int tiles_n,
                       const unsigned* amax_a, const unsigned* amax_b) {
   using TT = Tile<TL::BN, TL::BM, TL::WAVES_N, TL::WAVES_M>;
@@ -78,30 +85,96 @@ void gemm_nt_t_kernel(RowLoaderT<TA> al, RowLoader bl, StoreEpiT<TA> ep, int K, 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int wn = wv / TT::WAVES_N, wm = wv % TT::WAVES_N;          // TT's "rows" are output columns
   const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int i = 0; i < TT::TM; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int col = n0 + wn * TT::WM + i * 32 + 8 * q + 4 * h;
-      if (col >= ep.N) continue;
-      float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;        // (acc + bias0) + bias1, as the scalar epilogue
-      if (ep.bias0) b0 = make_float4(ep.bias0[col], ep.bias0[col + 1], ep.bias0[col + 2], ep.bias0[col + 3]);
-      if (ep.bias1) b1 = make_float4(ep.bias1[col], ep.bias1[col + 1], ep.bias1[col + 2], ep.bias1[col + 3]);
-#pragma unroll
-      for (int j = 0; j < TT::TN; ++j) {
-        const int row = m0 + wm * TT::WN + j * 32 + r;
-        if (row >= ep.M) continue;
-        TA* dst = ep.C + (long)row * ep.ldc + col;
-        float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        if constexpr (MODE == kSplit2) {
-          v.x = hs.unscale(v.x); v.y = hs.unscale(v.y); v.z = hs.unscale(v.z); v.w = hs.unscale(v.w);
-        }
-        if (ep.bias0) { v.x += b0.x; v.y += b0.y; v.z += b0.z; v.w += b0.w; }
-        if (ep.bias1) { v.x += b1.x; v.y += b1.y; v.z += b1.z; v.w += b1.w; }
-        if (ep.accumulate) { const float4 o = ld4(dst); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-        st4(dst, v);
-      }
+  // A lane's quads: group (i, q) = output columns n0 + wn WM + 32 i + 8 q + 4 h .. + 3, rows m0 + wm WN + 32 j + r.
+  auto quad = [&](int i, int q, int j) {
+    float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+    if constexpr (MODE == kSplit2) {
+      v.x = hs.unscale(v.x); v.y = hs.unscale(v.y); v.z = hs.unscale(v.z); v.w = hs.unscale(v.w);
     }
+    return v;
+  };
+  auto add4 = [](float4& v, const float4& o) { v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; };
+  if constexpr (BUF) {
+    // Buffer form (C ends below 2 GiB): C and the biases go through buffer descriptors.  C's covers the rows below M
+    // exactly, so a row past M lies past its range by itself; a column quad past N is sent there (kBufferOutside):
+    // loads read zero, stores are dropped, no branch per quad -- and the guard columns of an ldc > N view are never
+    // touched, because quads are whole (N % 4 == 0).  The old values of an accumulate launch and the bias quads are
+    // requested one group ahead of their use and waited for once per group, not once per load.
+    // Order of the sums as in the scalar epilogue: ((acc + bias0) + bias1) + old.
+    typedef typename RawQuad<TA>::type Raw;
+    const unsigned esz = (unsigned)sizeof(TA), rowb = (unsigned)ep.ldc * esz;
+    const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
+        ep.C, 0, (unsigned)(((long)(ep.M - 1) * ep.ldc + ep.N) * (long)sizeof(TA)), 0x00020000);
+    const unsigned nbytes = (unsigned)ep.N * 4u;
+    const __amdgpu_buffer_rsrc_t b0rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ep.bias0), 0, ep.bias0 ? nbytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t b1rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ep.bias1), 0, ep.bias1 ? nbytes : 0u, 0x00020000);
+    const unsigned rowo = (unsigned)(m0 + wm * TT::WN + r) * rowb;
+    constexpr int G = TT::TM * 4;
+    auto col_of = [&](int g) { return n0 + wn * TT::WM + (g >> 2) * 32 + 8 * (g & 3) + 4 * h; };
+    auto voff = [&](int g, int j) {
+      const int col = col_of(g);
+      return (col < ep.N ? rowo + (unsigned)col * esz : kBufferOutside) + (unsigned)(j * 32) * rowb;
+    };
+    // An absent bias adds -0.0f, which changes no value (the biases' uniform choice without a branch per group);
+    // accumulate picks one of two straight-line copies.
+    const float4 nz = make_float4(-0.f, -0.f, -0.f, -0.f);
+    const bool has0 = ep.bias0 != nullptr, has1 = ep.bias1 != nullptr;
+    auto run = [&](auto acc_tag) {
+      constexpr bool ACC = decltype(acc_tag)::value;
+      Raw old[2][TT::TN];
+      float4 b0[2], b1[2];
+      auto fetch = [&](int g) {
+        const int col = col_of(g);
+        const unsigned bo = col < ep.N ? (unsigned)col * 4u : kBufferOutside;
+        b0[g & 1] = ldraw_buffer<float>(b0rs, bo, 0u);             // (a null bias: an empty descriptor, nothing is read)
+        b1[g & 1] = ldraw_buffer<float>(b1rs, bo, 0u);
+        if constexpr (ACC) {
+#pragma unroll
+          for (int j = 0; j < TT::TN; ++j) old[g & 1][j] = ldraw_buffer<TA>(crs, voff(g, j), 0u);
+        }
+      };
+      fetch(0);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (g + 1 < G) fetch(g + 1);
+        __builtin_amdgcn_sched_barrier(0);                         // keep the next group's loads in front of the stores
+        const float4 c0 = has0 ? b0[g & 1] : nz, c1 = has1 ? b1[g & 1] : nz;
+#pragma unroll
+        for (int j = 0; j < TT::TN; ++j) {
+          float4 v = quad(g >> 2, g & 3, j);
+          add4(v, c0);
+          add4(v, c1);
+          if constexpr (ACC) add4(v, widen(old[g & 1][j]));
+          st4_buffer(ep.C, crs, voff(g, j), v);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if (ep.accumulate) run(std::true_type{});
+    else run(std::false_type{});
+  } else {                                                         // pointer form: C past 2 GiB, PE_EPILOGUE=pointer
+#pragma unroll
+    for (int i = 0; i < TT::TM; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int col = n0 + wn * TT::WM + i * 32 + 8 * q + 4 * h;
+        if (col >= ep.N) continue;
+        float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;        // (acc + bias0) + bias1, as the scalar epilogue
+        if (ep.bias0) b0 = make_float4(ep.bias0[col], ep.bias0[col + 1], ep.bias0[col + 2], ep.bias0[col + 3]);
+        if (ep.bias1) b1 = make_float4(ep.bias1[col], ep.bias1[col + 1], ep.bias1[col + 2], ep.bias1[col + 3]);
+#pragma unroll
+        for (int j = 0; j < TT::TN; ++j) {
+          const int row = m0 + wm * TT::WN + j * 32 + r;
+          if (row >= ep.M) continue;
+          TA* dst = ep.C + (long)row * ep.ldc + col;
+          float4 v = quad(i, q, j);
+          if (ep.bias0) add4(v, b0);
+          if (ep.bias1) add4(v, b1);
+          if (ep.accumulate) add4(v, ld4(dst));
+          st4(dst, v);
+        }
+      }
+  }
 }
 
 template <class TL, class F, class TA = typename F::TA>
@@ -112,9 +185,15 @@ int launch_nt(const RowLoaderT<TA>& al, const RowLoader& bl, const StoreEpiT<TA>
   const int tm = pe_cdiv(M, TL::BM), tn = pe_cdiv(N, TL::BN);
   const bool vec = MODE != kNative && (N & 3) == 0 && (ep.ldc & 3) == 0 &&
                    (reinterpret_cast<uintptr_t>(ep.C) & (4 * sizeof(TA) - 1)) == 0;
-  if (vec)
-    hipLaunchKernelGGL((gemm_nt_t_kernel<TL, MODE, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn,
-                       amax_a, amax_b);
+  if (vec) {
+    // buffer form: the descriptor's 32-bit offsets must also hold the rows a tile hangs over M by
+    if (ep.ldc >= N && pe_epilogue_buffer((long)(M + TL::BM) * ep.ldc * (long)sizeof(TA)))
+      hipLaunchKernelGGL((gemm_nt_t_kernel<TL, MODE, true, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm,
+                         tn, amax_a, amax_b);
+    else
+      hipLaunchKernelGGL((gemm_nt_t_kernel<TL, MODE, false, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm,
+                         tn, amax_a, amax_b);
+  }
   else
     hipLaunchKernelGGL((gemm_nt_kernel<TL, MODE, TA, TH>), dim3(tm * tn), dim3(256), 0, st, al, bl, ep, K, tm, tn, amax_a,
                        amax_b);
