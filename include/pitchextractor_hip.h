@@ -526,6 +526,52 @@ int pe_f0_track_path(const float* cand_f, const float* cand_s, const int* cand_n
                      const long* host_meta, int n_rows, int sr, int hop, const double* config7, float* f0,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- F0 tracking: WORLD DIO + StoneMask (pyworld's defaults, no decimation), ragged batches ---------------------
+ * config4 = {f0_floor, f0_ceil, channels_in_octave, allowed_range} (doubles).  PE_E_ARG: null pointer, sr <= 0,
+ * hop <= 0, a non-finite value, f0_floor <= 0, f0_floor >= f0_ceil, channels_in_octave <= 0, allowed_range <= 0, a
+ * host_meta that is not the plan's.  PE_E_UNSUPPORTED: sr outside 8000 .. 48000, f0_ceil >= sr / 2, hop > sr, more
+ * than 16 bands, a combined filter (2 round(sr / 50) + 4 half_average_length[0] taps) that needs a block transform
+ * above 8192 points, an f0_floor whose StoneMask transform exceeds 4096 points.  Every check runs before any device
+ * call.  The restatement tests/dio_ref.py states every convention.
+ *
+ * pe_f0_dio_plan (host only): consts10 = {bands, block transform N, taps of the longest combined filter, block step
+ * N - taps + 1, samples read ahead of a block, voice_range_minimum, table floats, samples per event chunk,
+ * round(sr / 50), StoneMask root-table floats}; half16[b] = half_average_length; dconsts17 = {frame_period ms,
+ * boundary[b]}; meta (n_rows x pe_f0_dio_plan_fields() int64, to be copied to the device) = per row {sample offset,
+ * samples, frames = (int)(1000 n / sr / frame_period) + 1, frame prefix, sample prefix, blocks, block prefix, event
+ * slot prefix (n / 2 + 1 slots per row, band and kind), event chunks, chunk prefix}; totals6 = {frames, samples,
+ * blocks, event slots, chunks, workspace bytes of pe_f0_dio_events}.
+ *
+ * tables (device, consts10[6] floats): exp(-2 pi i m / C), m < C = N / 2; exp(-2 pi i k / N), k <= C; per band the
+ * spectrum (C + 1 complex bins, divided by C) of the low-cut filter convolved with the band's Nuttall low-pass, delayed
+ * to the longest band's delay.  stats: pe_f0_track_stats' output (the row mean).
+ * pe_f0_dio_bands: band_signals[b][sample prefix + i], bands x totals6[1] floats.
+ * pe_f0_dio_events: per (row, band, kind; kind 0 .. 3 = signal, negation, first difference, negated difference) the
+ * fine edges in order as e_idx (integer part, i + 1) and e_frac (fraction in (0, 1]) at slot
+ * (event slot prefix x bands x 4) + (band x 4 + kind) x (n / 2 + 1); e_count[row][band][kind] edges.
+ * pe_f0_dio_candidates: cand / score [band][frame] (0 / 100000 = rejected), best[frame] and best_band[frame] of the
+ * lowest score (first band on a tie).  pe_f0_dio_fix: steps4[s][frame] = the contour after FixF0Contour's step
+ * s + 1; all zero for a row of at most voice_range_minimum frames.  pe_f0_stonemask: f0_out[frame] refined from
+ * f0_in (0 stays 0; roots = the 128, 256, .. 4096-th roots of unity back to back, consts10[9] floats); every
+ * f0_in > 0 must be >= f0_min, which bounds the transform (a smaller one yields 0). */
+int pe_f0_dio_plan_fields(void);
+int pe_f0_dio_plan(int n_rows, const long* n, const long* x_off, int sr, int hop, const double* config4,
+                   long* consts10, long* half16, double* dconsts17, long* meta, long* totals6);
+int pe_f0_dio_bands(const float* x, const long* meta, const long* host_meta, const float* stats,
+                    const float* tables, long n_table, int n_rows, int sr, int hop, const double* config4,
+                    float* band_signals, void* stream);
+int pe_f0_dio_events(const float* band_signals, const long* meta, const long* host_meta, int n_rows, int sr,
+                     int hop, const double* config4, int* e_idx, float* e_frac, int* e_count,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int pe_f0_dio_candidates(const int* e_idx, const float* e_frac, const int* e_count, const long* meta,
+                         const long* host_meta, int n_rows, int sr, int hop, const double* config4,
+                         float* cand, float* score, float* best, int* best_band, void* stream);
+int pe_f0_dio_fix(const float* best, const float* cand, const long* meta, const long* host_meta, int n_rows,
+                  int sr, int hop, const double* config4, float* steps4, void* stream);
+int pe_f0_stonemask(const float* x, const long* meta, const long* host_meta, const float* f0_in,
+                    const float* roots, long n_roots, int n_rows, int sr, int hop, double f0_min,
+                    float* f0_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

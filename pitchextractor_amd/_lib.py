@@ -139,6 +139,13 @@ PROTOTYPES = {
     "pe_f0_track_stats": (_i, [_p, _p, _i, _p, _p, _z, _p]),
     "pe_f0_track_frames": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
     "pe_f0_track_path": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "pe_f0_dio_plan_fields": (_i, []),
+    "pe_f0_dio_plan": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "pe_f0_dio_bands": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p]),
+    "pe_f0_dio_events": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "pe_f0_dio_candidates": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "pe_f0_dio_fix": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "pe_f0_stonemask": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, C.c_double, _p, _p]),
 }
 
 

@@ -5,6 +5,9 @@ binary is unpinned (DESIGN.md "F0 tracking"), the float64 restatement in ``tests
 
 Only ``method: ac`` / ``autocorrelation``, ``unit: Hertz`` and ``very_accurate: false`` are built; anything else is
 refused with ``NotImplementedError`` when the tracker (or a dataset that names it) is constructed.
+
+``WorldDioTracker`` (below) is the reference's ``pyworld`` backend with ``algorithm: dio``: WORLD's DIO + StoneMask
+(``csrc/f0_dio.hip``), pinned by ``tests/dio_ref.py`` in the same way.
 """
 from __future__ import annotations
 
@@ -19,7 +22,7 @@ from .ragged import packed_offsets, row_layout
 
 logger = logging.getLogger(__name__)
 
-NATIVE_TYPES = ("praat", "parselmouth")
+NATIVE_TYPES = ("praat", "parselmouth")            # always native; a `pyworld` entry is when its config says dio
 DEFAULT_CONFIG = dict(min_pitch=40.0, max_pitch=1100.0, silence_threshold=0.03, voicing_threshold=0.45,
                       octave_cost=0.01, octave_jump_cost=1.0, voiced_unvoiced_cost=0.3, very_accurate=False)
 _CONFIG_ORDER = ("min_pitch", "max_pitch", "silence_threshold", "voicing_threshold", "octave_cost",
@@ -168,3 +171,262 @@ class PraatACTracker:
             return contours
         return dict(f0=contours, cand_f=cand_f.cpu().numpy(), cand_s=cand_s.cpu().numpy(),
                     cand_n=cand_n.cpu().numpy(), frames=frames, frame_offsets=foff)
+
+
+# --------------------------------------------------------------------------- WORLD DIO + StoneMask (pyworld backend)
+DIO_DEFAULTS = dict(f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, allowed_range=0.1)
+_DIO_ORDER = ("f0_floor", "f0_ceil", "channels_in_octave", "allowed_range")
+_DIO_NUTTALL = (0.355768, 0.487396, 0.144232, 0.012604)
+_DIO_KINDS = 4
+
+
+def _flag(value) -> bool:
+    if isinstance(value, str):
+        return value.strip().lower() in {"1", "true", "yes", "on"}
+    return bool(value)
+
+
+def dio_fallback_ok(fallback) -> bool:
+    """A ``dio`` run whose fallback is ``dio`` reruns the same computation: a no-op."""
+    return fallback is None or str(fallback).strip().lower() in ("", "none", "dio")
+
+
+def check_dio_config(config: dict | None, sr: int, hop: int, require_algorithm: bool = False) -> dict:
+    """Validated copy of a ``pyworld`` backend config (f0_backends.py's PyWorldBackend keys plus the DIO options for
+    direct users).  ``require_algorithm``: a dataset entry without ``algorithm`` means ``harvest`` in the reference,
+    which is not built; the tracker class itself defaults to the one algorithm it has."""
+    cfg = dict(config or {})
+    algorithm = cfg.pop("algorithm", None if require_algorithm else "dio")
+    if str(algorithm).strip().lower() != "dio":
+        raise NotImplementedError(f"pyworld F0 backend: algorithm {algorithm!r} is not built on the HIP path; only "
+                                  "'dio' is (the reference's default without the key is 'harvest')")
+    fallback = cfg.pop("fallback", None)
+    if not dio_fallback_ok(fallback):
+        raise NotImplementedError(f"pyworld F0 backend: fallback {fallback!r} is not built; only none / 'dio' is")
+    speed = cfg.pop("speed", 1)
+    if int(speed) != 1:
+        raise NotImplementedError("pyworld F0 backend: speed (decimation) other than 1 is not built")
+    period = cfg.pop("frame_period_ms", None)
+    if period is not None and abs(float(period) - hop * 1000.0 / sr) > 1e-9 * max(1.0, abs(float(period))):
+        raise NotImplementedError(f"pyworld F0 backend: frame_period_ms {period!r} is not hop * 1000 / sr = "
+                                  f"{hop * 1000.0 / sr!r}; labels on another grid are not built")
+    out = dict(DIO_DEFAULTS, stonemask=_flag(cfg.pop("stonemask", True)),
+               min_voiced_frames=int(cfg.pop("min_voiced_frames", 5)))
+    for k, v in cfg.items():
+        if k in DIO_DEFAULTS:
+            out[k] = float(v)
+        elif k not in _IGNORED_KEYS:
+            logger.warning("pyworld F0 backend: option %r is not read (the reference ignores it too)", k)
+    return out
+
+
+class WorldDioTracker:
+    """``WorldDioTracker(sr, hop_length, **config)``: ``pyworld.dio`` + ``pyworld.stonemask`` with pyworld's defaults
+    at ``frame_period = hop_length * 1000 / sr`` as HIP launches over a ragged batch (``csrc/f0_dio.hip``).  A row's
+    contour is bit-identical whether it is tracked alone or inside any batch.  There is no CPU path."""
+
+    def __init__(self, sr: int, hop_length: int, **config):
+        self.sr, self.hop_length = int(sr), int(hop_length)
+        if self.sr <= 0 or self.hop_length <= 0:
+            raise ValueError("WorldDioTracker: sr and hop_length must be positive")
+        self.config = check_dio_config(config, self.sr, self.hop_length)
+        self.stonemask = self.config["stonemask"]
+        self.min_voiced_frames = self.config["min_voiced_frames"]
+        self._cfg = np.array([self.config[k] for k in _DIO_ORDER], dtype=np.float64)
+        plan = self.plan([0])
+        (self.bands, self.n_fft, self.taps, self.block_step, self.lead, self.voice_range_minimum, self.n_table,
+         self.event_chunk, self.cut, self.n_roots) = (int(v) for v in plan["consts"])
+        self.half_average_length = [int(v) for v in plan["half"][:self.bands]]
+        self.frame_period = float(plan["dconsts"][0])
+        self.boundary = [float(v) for v in plan["dconsts"][1:1 + self.bands]]
+
+    @property
+    def cache_key(self) -> str:
+        return "pyworld"
+
+    # ---- host side ----------------------------------------------------------------------------------------------
+    def plan(self, lengths, offsets=None) -> dict:
+        """``pe_f0_dio_plan``: the constants and the per-row layout for rows of ``lengths``."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+        R = lengths.size
+        if offsets is None:
+            offsets = packed_offsets(lengths)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size != R:
+            raise ValueError("f0 tracker: one offset per row")
+        lib = _lib.load()
+        K = lib.pe_f0_dio_plan_fields()
+        meta = np.zeros((max(R, 1), K), np.int64)
+        consts, half = np.zeros(10, np.int64), np.zeros(16, np.int64)
+        dconsts, totals = np.zeros(17, np.float64), np.zeros(6, np.int64)
+        p = lambda a: a.ctypes.data  # noqa: E731
+        _lib.check(lib.pe_f0_dio_plan(R, p(lengths), p(offsets), self.sr, self.hop_length, p(self._cfg), p(consts),
+                                      p(half), p(dconsts), p(meta), p(totals)), "pe_f0_dio_plan")
+        return dict(n_rows=R, lengths=lengths, offsets=offsets, meta=meta, consts=consts, half=half, dconsts=dconsts,
+                    frames=meta[:R, 2].copy(), frame_offsets=meta[:R, 3].copy(), sample_offsets=meta[:R, 4].copy(),
+                    event_offsets=meta[:R, 7].copy(), n_frames=int(totals[0]), n_samples=int(totals[1]),
+                    n_blocks=int(totals[2]), n_event_slots=int(totals[3]), n_chunks=int(totals[4]),
+                    workspace_bytes=int(totals[5]))
+
+    def frame_count(self, n_samples: int) -> int:
+        return int(self.plan([int(n_samples)])["frames"][0])
+
+    def frame_times(self, n_samples: int) -> np.ndarray:
+        return np.arange(self.frame_count(n_samples), dtype=np.float64) * self.frame_period / 1000.0
+
+    def host_tables(self) -> np.ndarray:
+        """float32 tables of the band kernel, built in float64: FFT roots, real-split roots, and per band the
+        spectrum (divided by C) of low-cut filter * Nuttall low-pass, delayed to the longest band's delay."""
+        N, C = self.n_fft, self.n_fft // 2
+        m = np.arange(C, dtype=np.float64)
+        k = np.arange(C + 1, dtype=np.float64)
+        tw = np.stack([np.cos(2 * np.pi * m / C), -np.sin(2 * np.pi * m / C)], axis=1)
+        tr = np.stack([np.cos(np.pi * k / C), -np.sin(np.pi * k / C)], axis=1)
+        n_cut = 2 * self.cut + 1
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(1, n_cut + 1, dtype=np.float64) / (n_cut + 1))
+        low_cut = -w / np.sum(w)
+        low_cut[self.cut] += 1.0
+        parts = [tw.reshape(-1), tr.reshape(-1)]
+        a = _DIO_NUTTALL
+        for h in self.half_average_length:
+            t = np.arange(4 * h, dtype=np.float64) / (4 * h - 1.0)
+            nut = a[0] - a[1] * np.cos(2 * np.pi * t) + a[2] * np.cos(4 * np.pi * t) - a[3] * np.cos(6 * np.pi * t)
+            g = np.zeros(N)
+            shift = 2 * (self.half_average_length[0] - h)
+            taps = np.convolve(low_cut, nut)
+            g[shift:shift + taps.size] = taps
+            G = np.fft.rfft(g) / C
+            parts.append(np.stack([G.real, G.imag], axis=1).reshape(-1))
+        out = np.concatenate(parts).astype(np.float32)
+        assert out.size == self.n_table
+        return out
+
+    def host_roots(self) -> np.ndarray:
+        parts = []
+        for lg in range(7, 13):
+            m = np.arange(1 << lg, dtype=np.float64) / (1 << lg)
+            parts.append(np.stack([np.cos(2 * np.pi * m), -np.sin(2 * np.pi * m)], axis=1).reshape(-1))
+        out = np.concatenate(parts).astype(np.float32)
+        assert out.size == self.n_roots
+        return out
+
+    # ---- device side: one method per stage ----------------------------------------------------------------------
+    def _device_plan(self, waves, lengths):
+        if not isinstance(waves, torch.Tensor) or not waves.is_cuda or waves.dtype != torch.float32 or \
+                waves.dim() not in (1, 2) or (waves.numel() > 0 and waves.stride(-1) != 1):
+            raise RuntimeError("WorldDioTracker (HIP) needs contiguous-row float32 device audio; no CPU fallback "
+                               "exists")
+        lengths, offsets = row_layout(waves, lengths, whole_by_default=True)
+        pl = self.plan(lengths, offsets)
+        pl["meta_d"] = torch.from_numpy(pl["meta"]).to(waves.device)
+        return pl
+
+    def _args(self, pl):
+        return (pl["n_rows"], self.sr, self.hop_length, self._cfg.ctypes.data)
+
+    def stage_bands(self, waves, pl):
+        """(bands, samples of the batch) float32 band signals, rows back to back."""
+        dev, R = waves.device, pl["n_rows"]
+        sig = torch.zeros((self.bands, max(pl["n_samples"], 1)), dtype=torch.float32, device=dev)
+        stats = torch.zeros((max(R, 1), 2), dtype=torch.float32, device=dev)
+        tables = _lib.device_table(("f0_dio", self.sr, tuple(self.half_average_length)), dev, self.host_tables)
+        s = _lib.stream_ptr()
+        if R and pl["n_samples"]:
+            # pe_f0_track_stats reads fields 0 / 1 of a row's plan (offset, length) at the stride of its own plan
+            tmeta = np.zeros((R, _lib.load().pe_f0_track_plan_fields()), np.int64)
+            tmeta[:, 0], tmeta[:, 1] = pl["meta"][:R, 0], pl["meta"][:R, 1]
+            tmeta_d = torch.from_numpy(tmeta).to(dev)
+            sws_bytes = _lib.load().pe_f0_track_stats_workspace_bytes(R)
+            sws = torch.empty((sws_bytes,), dtype=torch.uint8, device=dev)
+            ops._call("pe_f0_track_stats", waves.data_ptr(), tmeta_d.data_ptr(), R, stats.data_ptr(), sws.data_ptr(),
+                      sws_bytes, s, work=float(pl["n_samples"] * 8))
+        if pl["n_samples"]:
+            ops._call("pe_f0_dio_bands", waves.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data,
+                      stats.data_ptr(), tables.data_ptr(), int(tables.numel()), *self._args(pl), sig.data_ptr(), s,
+                      work=float(pl["n_blocks"] * (1 + self.bands) * 2.5 * self.n_fft * np.log2(self.n_fft)))
+        return sig[:, :pl["n_samples"]] if pl["n_samples"] else sig[:, :0]
+
+    def stage_events(self, sig, pl):
+        """(e_idx, e_frac, e_count (rows, bands, 4)) from band signals (a view of at least the batch's samples)."""
+        dev, R = sig.device, pl["n_rows"]
+        slots = max(pl["n_event_slots"] * self.bands * _DIO_KINDS, 1)
+        e_idx = torch.zeros((slots,), dtype=torch.int32, device=dev)
+        e_frac = torch.zeros((slots,), dtype=torch.float32, device=dev)
+        e_count = torch.zeros((max(R, 1), self.bands, _DIO_KINDS), dtype=torch.int32, device=dev)
+        if R:
+            sig = sig.contiguous()
+            ws = torch.empty((max(pl["workspace_bytes"], 4),), dtype=torch.uint8, device=dev)
+            ops._call("pe_f0_dio_events", sig.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data,
+                      *self._args(pl), e_idx.data_ptr(), e_frac.data_ptr(), e_count.data_ptr(), ws.data_ptr(),
+                      pl["workspace_bytes"], _lib.stream_ptr(), work=float(2 * self.bands * pl["n_samples"] * 4))
+        return e_idx, e_frac, e_count[:R]
+
+    def stage_candidates(self, e_idx, e_frac, e_count, pl):
+        """(cand (bands, frames), score, best (frames,), best_band)."""
+        dev, G = e_idx.device, pl["n_frames"]
+        cand = torch.zeros((self.bands, G), dtype=torch.float32, device=dev)
+        score = torch.zeros((self.bands, G), dtype=torch.float32, device=dev)
+        best = torch.zeros((G,), dtype=torch.float32, device=dev)
+        band = torch.zeros((G,), dtype=torch.int32, device=dev)
+        if pl["n_rows"] and G:
+            ops._call("pe_f0_dio_candidates", e_idx.data_ptr(), e_frac.data_ptr(), e_count.contiguous().data_ptr(),
+                      pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, *self._args(pl), cand.data_ptr(),
+                      score.data_ptr(), best.data_ptr(), band.data_ptr(), _lib.stream_ptr(),
+                      work=float(G * self.bands * 64))
+        return cand, score, best, band
+
+    def stage_fix(self, best, cand, pl):
+        """(4, frames): the contour after FixF0Contour's steps 1 .. 4."""
+        G = pl["n_frames"]
+        steps = torch.zeros((4, G), dtype=torch.float32, device=best.device)
+        if pl["n_rows"] and G:
+            ops._call("pe_f0_dio_fix", best.contiguous().data_ptr(), cand.contiguous().data_ptr(),
+                      pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, *self._args(pl), steps.data_ptr(),
+                      _lib.stream_ptr(), work=float(G * self.bands * 8))
+        return steps
+
+    def stage_stonemask(self, waves, f0, pl):
+        G = pl["n_frames"]
+        out = torch.zeros((G,), dtype=torch.float32, device=waves.device)
+        if pl["n_rows"] and G and pl["n_samples"]:
+            roots = _lib.device_table(("f0_stonemask_roots",), waves.device, self.host_roots)
+            ops._call("pe_f0_stonemask", waves.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data,
+                      f0.contiguous().data_ptr(), roots.data_ptr(), int(roots.numel()), pl["n_rows"], self.sr,
+                      self.hop_length, float(self.config["f0_floor"]), out.data_ptr(), _lib.stream_ptr(),
+                      work=float(G * 5 * 1024 * 10))
+        return out
+
+    def track(self, waves: torch.Tensor, lengths=None, *, return_stages: bool = False):
+        """``waves``: float32 device audio at ``sr``, in one of ``PraatACTracker.track``'s three layouts.  Returns one
+        float32 contour per row (Hz, 0 = unvoiced; ``(int)(1000 n / sr / frame_period) + 1`` frames), or with
+        ``return_stages`` a dict with every stage's output as well (host arrays)."""
+        pl = self._device_plan(waves, lengths)
+        with torch.cuda.device(waves.device):
+            sig = self.stage_bands(waves, pl)
+            e_idx, e_frac, e_count = self.stage_events(sig, pl)
+            cand, score, best, band = self.stage_candidates(e_idx, e_frac, e_count, pl)
+            steps = self.stage_fix(best, cand, pl)
+            f0 = self.stage_stonemask(waves, steps[3], pl) if self.stonemask else steps[3]
+        frames, foff = pl["frames"], pl["frame_offsets"]
+        f0_h = f0.cpu().numpy()
+        contours = [f0_h[int(o):int(o) + int(n)].copy() for o, n in zip(foff, frames)]
+        if not return_stages:
+            return contours
+        return dict(f0=contours, plan=pl, bands=sig.cpu().numpy(), e_idx=e_idx.cpu().numpy(),
+                    e_frac=e_frac.cpu().numpy(), e_count=e_count.cpu().numpy(), cand=cand.cpu().numpy(),
+                    score=score.cpu().numpy(), best=best.cpu().numpy(), best_band=band.cpu().numpy(),
+                    steps=steps.cpu().numpy(), frames=frames, frame_offsets=foff)
+
+    def row_events(self, e_idx, e_frac, e_count, pl, row):
+        """Host view of one row's events: [band][kind] -> (idx, frac)."""
+        n = int(pl["lengths"][row])
+        cap = n // 2 + 1
+        base = int(pl["event_offsets"][row]) * self.bands * _DIO_KINDS
+        out = []
+        for b in range(self.bands):
+            kinds = []
+            for k in range(_DIO_KINDS):
+                at, c = base + (b * _DIO_KINDS + k) * cap, int(e_count[row, b, k])
+                kinds.append((np.asarray(e_idx[at:at + c], np.int64), np.asarray(e_frac[at:at + c])))
+            out.append(kinds)
+        return out

@@ -136,15 +136,20 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
 _TRACKERS = {}
 
 
-def track_f0(wave, *, sr: int, hop_length: int, device="cuda", **config) -> np.ndarray:
-    """F0 contour (Hz, 0 = unvoiced; float32) of one wave at ``sr`` by the on-device Praat-style autocorrelation
-    tracker (``f0_tracker.PraatACTracker``; ``config``: the reference's ``praat`` backend keys).  One value every
-    ``hop_length / sr`` seconds over the frames whose window lies inside the wave -- not the mel frame count:
-    ``pitch_metrics(predict_f0(...), align_length(track_f0(...), L))`` scores a model against it."""
-    from .f0_tracker import PraatACTracker
-    key = (int(sr), int(hop_length), tuple(sorted((k, str(v)) for k, v in config.items())))
+def track_f0(wave, *, sr: int, hop_length: int, device="cuda", backend: str = "praat", **config) -> np.ndarray:
+    """F0 contour (Hz, 0 = unvoiced; float32) of one wave at ``sr`` by an on-device tracker: ``backend="praat"``, the
+    Praat-style autocorrelation tracker (``f0_tracker.PraatACTracker``; ``config``: the reference's ``praat`` backend
+    keys), or ``backend="dio"``, WORLD's DIO + StoneMask (``f0_tracker.WorldDioTracker``; the ``pyworld`` keys).  One
+    value every ``hop_length / sr`` seconds -- praat: over the frames whose window lies inside the wave; dio: from
+    time 0 -- not the mel frame count: ``pitch_metrics(predict_f0(...), align_length(track_f0(...), L))`` scores a
+    model against it."""
+    from .f0_tracker import PraatACTracker, WorldDioTracker
+    classes = {"praat": PraatACTracker, "dio": WorldDioTracker}
+    if backend not in classes:
+        raise ValueError(f"track_f0: backend {backend!r} is not one of {sorted(classes)}")
+    key = (backend, int(sr), int(hop_length), tuple(sorted((k, str(v)) for k, v in config.items())))
     if key not in _TRACKERS:
-        _TRACKERS[key] = PraatACTracker(sr, hop_length, **config)
+        _TRACKERS[key] = classes[backend](sr, hop_length, **config)
     if isinstance(wave, torch.Tensor):
         w = wave.detach().reshape(-1).to(device, torch.float32).contiguous()
     else:

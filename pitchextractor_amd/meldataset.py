@@ -12,8 +12,8 @@ to HBM once and ONE launch of the fused mel kernel does framing + FFT + mel + lo
 (meldataset.py:806-816).  All index arithmetic -- segment pre-crop (meldataset.py:178-201), F0
 alignment (f0_backends.py:788-806), crop offsets -- is reproduced exactly and runs on the host.
 
-Out of scope here: the pyworld / CREPE / SwiftF0 tracker backends need packages that are not
-installable offline.  The WORLD-vocoder augmentation (``synthetic_data.world_vocoder``, Utils/synthetic.py) runs on the
+Out of scope here: the pyworld harvest / CREPE / SwiftF0 tracker backends (packages or weights that
+are not available; pyworld's ``algorithm: dio`` is native, ``f0_tracker.WorldDioTracker``).  The WORLD-vocoder augmentation (``synthetic_data.world_vocoder``, Utils/synthetic.py) runs on the
 GPU when its block carries ``backend: hip`` (``pitchextractor_amd.world``): a worker makes the generator's draws in the
 reference's order, computes the pulse positions of the drawn F0 curve (a sequential float64 recurrence) and the labels,
 and ships a ``WorldRequest`` instead of audio; the device synthesizes only the samples the cropped 192 mel frames read
@@ -27,10 +27,11 @@ contract (meldataset.py:519-604): ``<wav>_f0<cache_identifier>.npy`` validated b
 When the enabled backend chain of ``f0_params`` holds a ``praat`` / ``parselmouth`` entry (method ``ac``), the caches
 need not exist beforehand: ``prepare_f0_caches`` -- run once by ``build_dataloader`` in the main process, before any
 worker starts -- reads every listed file that has no valid cache, resamples it to the dataset rate on the device,
-tracks whole batches of files with the on-device autocorrelation tracker (``pitchextractor_amd.f0_tracker``), applies
+tracks whole batches of files with the on-device trackers (``pitchextractor_amd.f0_tracker``: praat ``ac``, pyworld
+``dio``), applies
 the reference's acceptance rule (fewer than ``bad_f0_threshold`` non-zero frames = that backend failed; every native
 entry failed = empty track) and writes ``.npy`` + ``.json`` as meldataset.py:606-619 does, through temporary names.
-Workers keep reading caches only.  Entries of the chain that need pyworld / CREPE / SwiftF0 are skipped with a
+Workers keep reading caches only.  Entries of the chain that need pyworld harvest / CREPE / SwiftF0 are skipped with a
 warning each, as the reference skips a backend whose package is missing.  Existing valid caches are never recomputed,
 overwritten or deleted.  A cache whose metadata does not match is skipped with a warning and left on disk (the
 reference deletes and recomputes it; this build recomputes only under a name that is free).  Without a native entry
@@ -64,7 +65,7 @@ from torch.utils.data import DataLoader
 from typing import NamedTuple
 
 from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS, MelSpectrogram
-from .f0_tracker import NATIVE_TYPES, check_config
+from .f0_tracker import NATIVE_TYPES, check_config, check_dio_config, dio_fallback_ok
 from .pitch_shift import check_res_type, pitch_shift_ragged
 from .resample import RaggedResampler, Resampler
 from .world import WorldGenerator, noise_seed, output_length, world_synthesize_ragged
@@ -253,6 +254,14 @@ def f0_backend_chain(f0_params: dict | None):
     return chain
 
 
+def _native_pyworld(btype: str, config) -> bool:
+    """A ``pyworld`` entry runs on the device iff it asks for DIO alone: ``algorithm: dio`` (a missing key means
+    harvest in the reference) and a fallback that reruns dio or is none."""
+    if btype != "pyworld" or not isinstance(config, dict):
+        return False
+    return str(config.get("algorithm", "harvest")).strip().lower() == "dio" and dio_fallback_ok(config.get("fallback"))
+
+
 def f0_cache_identifier(f0_params: dict | None) -> str:
     """The reference's ``F0Extractor.cache_identifier`` (f0_backends.py:661-757) for an ``f0_params``
     block: "-" + the cache keys of the enabled backends in chain order, joined by "_" (the shipped
@@ -378,8 +387,15 @@ class MelDataset(torch.utils.data.Dataset):
         self.requires_cuda_backend = False
         # native (on-device) entries of the backend chain: validated now, run by prepare_f0_caches
         self._f0_chain = f0_backend_chain(self.f0_params)
-        self._native_f0 = [(name, check_config(cfg if isinstance(cfg, dict) else {}, require_method=True))
-                           for name, btype, cfg in self._f0_chain if btype in NATIVE_TYPES]
+        hop = int(self.mel_params["hop_length"])
+        self._native_f0 = []                              # (name, tracker class name, validated config), chain order
+        for name, btype, cfg in self._f0_chain:
+            cfg = cfg if isinstance(cfg, dict) else {}
+            if btype in NATIVE_TYPES:
+                self._native_f0.append((name, "PraatACTracker", check_config(cfg, require_method=True)))
+            elif _native_pyworld(btype, cfg):
+                self._native_f0.append((name, "WorldDioTracker",
+                                        check_dio_config(cfg, self.sr, hop, require_algorithm=True)))
         self._audio_metadata_cache = {}
         self._invalid_paths = set()
         self._mel_cache_suffix, self._mel_meta_suffix = "_mel.npy", "_mel_meta.json"      # meldataset.py:102-103
@@ -670,21 +686,22 @@ class MelDataset(torch.utils.data.Dataset):
                           tracker_factory=None):
         """Label every listed file without a valid cache with the native backend chain and write its cache.
         Whole files are read, packed, resampled to ``self.sr`` in one ragged launch per batch and tracked in a fixed
-        number of launches per batch.  ``tracker_factory(sr, hop, **config)`` (default ``PraatACTracker``) lets a
-        test substitute a stub.  Returns the files labelled."""
+        number of launches per batch.  Each native entry runs its own tracker class (``PraatACTracker`` for praat /
+        parselmouth, ``WorldDioTracker`` for a pyworld entry with ``algorithm: dio``), in the chain's order;
+        ``tracker_factory(sr, hop, **config)`` replaces all of them (a test's stub).  Returns the files labelled."""
         if not self._native_f0:
             raise RuntimeError("prepare_f0_caches: f0_params enables no praat / parselmouth backend; the other "
                                "backends are outside this build")
-        for name, btype, _ in self._f0_chain:
-            if btype not in NATIVE_TYPES:
+        for name, btype, cfg in self._f0_chain:
+            if btype not in NATIVE_TYPES and not _native_pyworld(btype, cfg):
                 logger.warning("[MelDataset] F0 backend '%s' (%s) is not part of this build: skipped", name, btype)
         todo = self.files_to_label(rank, world)
         if not todo:
             return []
-        if tracker_factory is None:
-            from .f0_tracker import PraatACTracker as tracker_factory
+        from . import f0_tracker
         hop = int(self.mel_params["hop_length"])
-        trackers = [(name, tracker_factory(self.sr, hop, **cfg)) for name, cfg in self._native_f0]
+        trackers = [(name, (tracker_factory or getattr(f0_tracker, cls))(self.sr, hop, **cfg))
+                    for name, cls, cfg in self._native_f0]
         resampler = RaggedResampler(self.sr)
         done = []
         for lo in range(0, len(todo), max(int(files_per_batch), 1)):
@@ -741,7 +758,7 @@ class MelDataset(torch.utils.data.Dataset):
                     logger.warning("Failed to cache F0 for %s: %s", path, exc)
         if self.verbose:
             print(f"[MelDataset] F0 labels written for {len(done)} file(s) "
-                  f"(backends: {', '.join(n for n, _ in self._native_f0)})")
+                  f"(backends: {', '.join(n for n, _, _ in self._native_f0)})")
         return done
 
     def _f0_for(self, path, waveform, start_sample, expected_frames):
@@ -758,7 +775,8 @@ class MelDataset(torch.utils.data.Dataset):
             return np.asarray(self.f0_provider(path, waveform, self.sr), dtype=np.float32)
         raise RuntimeError(f"no F0 labels for {path}: no valid '{os.path.basename(path)}{self.f0_cache_suffix}' "
                            "(+ .json) cache, no legacy '_f0.npy' and no f0_provider (of the reference's tracker "
-                           "backends only praat / parselmouth with method 'ac' is part of this build)")
+                           "backends only praat / parselmouth with method 'ac' and pyworld with algorithm 'dio' are "
+                           "part of this build)")
 
     # ---- cached spectrograms (meldataset.py:679-741), read-only ------------------------------
     def _build_mel_metadata(self, num_samples: int, wave_sr: int) -> dict:
