@@ -490,6 +490,16 @@ int pe_f0_viterbi(const float* logits, long ld_t, long ld_n, int C, const int* l
 int pe_pitch_metrics(const float* f0_pred, const float* f0_ref, long n, double threshold_cents, double* out6,
                      void* stream);
 
+/* ---- Row statistics of a ragged batch, for any row plan ---------------------------------------------------------
+ * Every row plan of the F0 trackers (pe_f0_track_plan, pe_f0_dio_plan) is n_rows x K int64 and opens with the same
+ * header: field 0 = the row's offset in x, field 1 = its length in samples.  pe_row_stats reads only that header, at
+ * the caller's stride meta_fields = K (PE_E_ARG below 2): stats[r] = {mean, max |x - mean|}, each row reduced in 64
+ * pieces in a fixed order through `workspace` (pe_row_stats_workspace_bytes; PE_E_WORKSPACE when too small), so a
+ * row's statistics depend on neither the batch around it nor the plan that describes it. */
+size_t pe_row_stats_workspace_bytes(int n_rows);
+int pe_row_stats(const float* x, const long* meta, int meta_fields, int n_rows, float* stats, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ---- F0 tracking: Boersma's autocorrelation method (Praat "Sound: To Pitch (ac)"), ragged batches --------------
  * config7 = {min_pitch, max_pitch, silence_threshold, voicing_threshold, octave_cost, octave_jump_cost,
  * voiced_unvoiced_cost} (doubles).  PE_E_ARG: null pointer, sr <= 0, hop <= 0, a non-finite value, min_pitch <= 0,
@@ -507,8 +517,7 @@ int pe_pitch_metrics(const float* f0_pred, const float* f0_ref, long n, double t
  *
  * tables (device, consts8[6] floats): exp(-2 pi i m / C), m < C = FFT length / 2; exp(-2 pi i k / (2 C)), k <= C;
  * the Hann window 0.5 - 0.5 cos(2 pi (j + 1) / (window + 1)); its normalised autocorrelation for lags 0 .. half
- * window.  pe_f0_track_stats: stats[r] = {mean, max |x - mean|}, each row reduced in 64 pieces in a fixed order
- * through `workspace` (pe_f0_track_stats_workspace_bytes; PE_E_WORKSPACE when too small).  pe_f0_track_frames: per frame g (rows back to
+ * window.  stats: pe_row_stats' output for this plan.  pe_f0_track_frames: per frame g (rows back to
  * back) up to 15 candidates, cand_f / cand_s [g][15] (Hz, strength; [0] is the unvoiced candidate, voiced ones in
  * lag order) and their count cand_n[g].  pe_f0_track_path: f0[g] = frequency of the best path's candidate, 0 where
  * it is unvoiced (frequency 0 or >= ceiling); rows with more than consts8[7] frames keep 16 bytes of back-pointers
@@ -516,9 +525,6 @@ int pe_pitch_metrics(const float* f0_pred, const float* f0_ref, long n, double t
 int pe_f0_track_plan_fields(void);
 int pe_f0_track_plan(int n_rows, const long* n, const long* x_off, int sr, int hop, const double* config7,
                      long* consts8, double* dconsts2, long* meta, double* t1, long* totals2);
-size_t pe_f0_track_stats_workspace_bytes(int n_rows);
-int pe_f0_track_stats(const float* x, const long* meta, int n_rows, float* stats, void* workspace,
-                      size_t workspace_bytes, void* stream);
 int pe_f0_track_frames(const float* x, const long* meta, const long* host_meta, const double* t1,
                        const float* stats, const float* tables, long n_table, int n_rows, int sr, int hop,
                        const double* config7, float* cand_f, float* cand_s, int* cand_n, void* stream);
@@ -544,7 +550,7 @@ int pe_f0_track_path(const float* cand_f, const float* cand_s, const int* cand_n
  *
  * tables (device, consts10[6] floats): exp(-2 pi i m / C), m < C = N / 2; exp(-2 pi i k / N), k <= C; per band the
  * spectrum (C + 1 complex bins, divided by C) of the low-cut filter convolved with the band's Nuttall low-pass, delayed
- * to the longest band's delay.  stats: pe_f0_track_stats' output (the row mean).
+ * to the longest band's delay.  stats: pe_row_stats' output for this plan (the row mean).
  * pe_f0_dio_bands: band_signals[b][sample prefix + i], bands x totals6[1] floats.
  * pe_f0_dio_events: per (row, band, kind; kind 0 .. 3 = signal, negation, first difference, negated difference) the
  * fine edges in order as e_idx (integer part, i + 1) and e_frac (fraction in (0, 1]) at slot

@@ -135,8 +135,8 @@ PROTOTYPES = {
     "pe_pitch_metrics": (_i, [_p, _p, _l, _d, _p, _p]),
     "pe_f0_track_plan_fields": (_i, []),
     "pe_f0_track_plan": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "pe_f0_track_stats_workspace_bytes": (_z, [_i]),
-    "pe_f0_track_stats": (_i, [_p, _p, _i, _p, _p, _z, _p]),
+    "pe_row_stats_workspace_bytes": (_z, [_i]),
+    "pe_row_stats": (_i, [_p, _p, _i, _i, _p, _p, _z, _p]),
     "pe_f0_track_frames": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
     "pe_f0_track_path": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
     "pe_f0_dio_plan_fields": (_i, []),

@@ -1,10 +1,29 @@
-// Signal-processing device helpers shared by the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip): float2
-// complex arithmetic, the wave-private LDS fence, the in-place radix-4 Stockham FFT in LDS, the split of a packed
-// half-length transform into the bins of the real one, and the row search of the ragged batch plans.
+// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip) share.  Host: the row
+// bound and launch-grid clamp of the ragged entry points, the header every row plan opens with, and with_log2 (transform
+// size -> kernel instance).  Device: float2 complex arithmetic, the wave-private LDS fence, the in-place radix-4 Stockham
+// FFT in LDS, the split of a packed half-length transform into the real one's bins, and the row search of ragged plans.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace pe {
+
+constexpr int kMaxRows = 65535;           // rows of one ragged batch (a launch grid's y / x extent)
+constexpr float kPiF = 3.14159265358979323846f;
+// workgroups of a grid-stride launch over `items` work items
+inline unsigned grid_of(long items) { return (unsigned)(items < (1L << 20) ? items : (1L << 20)); }
+
+// Every row plan (n_rows x K int64, K the plan's own field count) opens with the row's offset in `x` and its length in
+// samples.  A plan's enum static_asserts this; what reads only this header (pe_row_stats) serves any plan given its K.
+enum { kRowOffset = 0, kRowLength = 1, kRowHeader = 2 };
+
+// Calls fn(std::integral_constant<int, L>{}) for L == lg in [LO, HI] and returns its status; PE_E_UNSUPPORTED outside the
+// range (what with_form of forms.h is for product forms).  The one other fft_lds dispatch is stonemask_kernel's switch.
+template <int LO, int HI, class Fn>
+int with_log2(int lg, Fn&& fn) {
+  if constexpr (LO <= HI) return lg == LO ? fn(std::integral_constant<int, LO>{}) : with_log2<LO + 1, HI>(lg, fn);
+  return PE_E_UNSUPPORTED;
+}
 
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }

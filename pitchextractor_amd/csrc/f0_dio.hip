@@ -27,17 +27,16 @@ using namespace pe;
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxRows = 65535;
 constexpr int kMaxBands = 16;
 constexpr int kChunk = 2048;              // samples of a band signal per event workgroup (4 waves x 8 x 64)
 constexpr int kKinds = 4;
 constexpr double kLowCut = 50.0;
-constexpr float kPiF = 3.14159265358979323846f;
 constexpr float kRejected = 100000.f;
 constexpr int kSmMaxLog2 = 12;            // StoneMask transforms: 128 .. 4096 points
 constexpr int kSmMinLog2 = 7;
 
 enum { D_XOFF, D_N, D_FRAMES, D_FOFF, D_SOFF, D_BLOCKS, D_BOFF, D_EOFF, D_CHUNKS, D_COFF, D_K };
+static_assert(D_XOFF == kRowOffset && D_N == kRowLength, "the plan opens with the shared row header");
 
 struct DioConsts {
   int sr, hop, bands, nfft, log2c, taps, step, lead, vrm, cut;
@@ -49,6 +48,16 @@ struct DioConsts {
 };
 
 double round_half_away(double v) { return v < 0.0 ? -floor(-v + 0.5) : floor(v + 0.5); }
+
+// StoneMask's largest transform is the one of the lowest F0 a contour may hold, f0_min: does it fit 2^kSmMaxLog2 points?
+bool stonemask_fits(int sr, double f0_min) {
+#pragma clang fp contract(off)
+  const double lowest = f0_min > 40.0 ? f0_min : 40.0;
+  const int hw = (int)(1.5 * (double)sr / lowest + 1.0);
+  int lg = 0;
+  while ((2 << lg) <= 2 * hw + 1) ++lg;
+  return 2 + lg <= kSmMaxLog2;
+}
 
 // step 1 of the algorithm for (sr, hop, config4 = {f0_floor, f0_ceil, channels_in_octave, allowed_range})
 int derive(int sr, int hop, const double* cfg, DioConsts* k) {
@@ -85,12 +94,7 @@ int derive(int sr, int hop, const double* cfg, DioConsts* k) {
   k->step = k->nfft - k->taps + 1;
   k->lead = k->cut + 2 * k->half[0] - 1;
   k->vrm = (int)(0.5 + 1000.0 / k->frame_period / flo) * 2 + 1;
-  // StoneMask's largest transform is the one of the lowest F0 a contour may hold, f0_floor
-  const double lowest = flo > 40.0 ? flo : 40.0;
-  const int hw = (int)(1.5 * (double)sr / lowest + 1.0);
-  int lg = 0;
-  while ((2 << lg) <= 2 * hw + 1) ++lg;
-  if (2 + lg > kSmMaxLog2) return PE_E_UNSUPPORTED;
+  if (!stonemask_fits(sr, flo)) return PE_E_UNSUPPORTED;
   k->floor_d = flo;
   k->floor_f = (float)flo;
   k->ceil_f = (float)cei;
@@ -103,11 +107,8 @@ long table_floats(const DioConsts& k) {       // twiddles (C float2), split root
   return 2 * C + 2 * (C + 1) + (long)k.bands * 2 * (C + 1);
 }
 
-long stonemask_table_floats() {               // roots of the 128 .. 4096-point transforms, back to back
-  long n = 0;
-  for (int l = kSmMinLog2; l <= kSmMaxLog2; ++l) n += 2L << l;
-  return n;
-}
+// roots of the 128 .. 4096-point transforms, back to back: the sum of 2 x 2^l floats over l
+long stonemask_table_floats() { return (4L << kSmMaxLog2) - (2L << kSmMinLog2); }
 
 long frame_count(long n, const DioConsts& k) {
 #pragma clang fp contract(off)
@@ -115,10 +116,14 @@ long frame_count(long n, const DioConsts& k) {
   return (long)(ms / k.frame_period) + 1;
 }
 
-bool meta_ok(const long* hm, int n_rows, long* totals5) {
+constexpr unsigned kCheckBlocks = 1, kCheckFrames = 2;     // `checks`: also hold a row to k's block / frame count
+
+bool meta_ok(const long* hm, int n_rows, unsigned checks, const DioConsts& k, long* totals5) {
   long f = 0, s = 0, b = 0, e = 0, c = 0;
   for (int r = 0; r < n_rows; ++r) {
     const long* m = hm + (long)r * D_K;
+    if ((checks & kCheckBlocks) && m[D_BLOCKS] != (m[D_N] + k.step - 1) / k.step) return false;
+    if ((checks & kCheckFrames) && m[D_FRAMES] != frame_count(m[D_N], k)) return false;
     if (m[D_N] < 0 || m[D_N] > (1L << 31) - 8 || m[D_XOFF] < 0 || m[D_FRAMES] < 0 || m[D_BLOCKS] < 0 || m[D_CHUNKS] < 0)
       return false;
     if (m[D_FOFF] != f || m[D_SOFF] != s || m[D_BOFF] != b || m[D_EOFF] != e || m[D_COFF] != c) return false;
@@ -128,8 +133,6 @@ bool meta_ok(const long* hm, int n_rows, long* totals5) {
   totals5[0] = f; totals5[1] = s; totals5[2] = b; totals5[3] = e; totals5[4] = c;
   return true;
 }
-
-inline unsigned grid_of(long items) { return (unsigned)(items < (1L << 20) ? items : (1L << 20)); }
 
 // ---- bands -------------------------------------------------------------------------------------------------------------
 template <int LOG2C>
@@ -529,7 +532,7 @@ __global__ __launch_bounds__(kThreads) void stonemask_kernel(const float* __rest
     long ro = 0;
     for (int l = kSmMinLog2; l < lg; ++l) ro += 1L << l;
     const float2* tw = reinterpret_cast<const float2*>(roots) + ro;
-    switch (lg) {                                                   // uniform over the workgroup
+    switch (lg) {                                                   // uniform over the workgroup (host: with_log2)
       case 7: fft_lds<7, false, kThreads>(s_buf, tw, tid); break;
       case 8: fft_lds<8, false, kThreads>(s_buf, tw, tid); break;
       case 9: fft_lds<9, false, kThreads>(s_buf, tw, tid); break;
@@ -551,6 +554,25 @@ __global__ __launch_bounds__(kThreads) void stonemask_kernel(const float* __rest
     }
     __syncthreads();
   }
+}
+
+// ---- what every stage entry point checks before its own pointers: host_meta is the plan's; `work`: the total a launch
+// needs (-1: none) ----------------------------------------------------------------------------------------------------------
+struct DioBatch { DioConsts k; long tot[5]; };        // tot: the batch's totals by meta_ok, indexed by TOT_*
+enum { TOT_FRAMES, TOT_SAMPLES, TOT_BLOCKS, TOT_SLOTS, TOT_CHUNKS };
+constexpr int kNothing = 1;               // valid, and nothing to launch: PE_OK to the caller
+
+int open_rows(int n_rows, const long* host_meta, unsigned checks, int work, DioBatch* b) {
+  if (n_rows == 0) return kNothing;
+  if (!host_meta || !meta_ok(host_meta, n_rows, checks, b->k, b->tot)) return PE_E_ARG;
+  return work >= 0 && b->tot[work] == 0 ? kNothing : PE_OK;
+}
+
+int open_batch(int n_rows, int sr, int hop, const double* config4, const long* host_meta, unsigned checks, int work,
+               DioBatch* b) {
+  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
+  const int st = derive(sr, hop, config4, &b->k);
+  return st != PE_OK ? st : open_rows(n_rows, host_meta, checks, work, b);
 }
 
 }  // namespace
@@ -594,62 +616,47 @@ extern "C" int pe_f0_dio_plan(int n_rows, const long* n, const long* x_off, int 
 extern "C" int pe_f0_dio_bands(const float* x, const long* meta, const long* host_meta, const float* stats,
                                const float* tables, long n_table, int n_rows, int sr, int hop, const double* config4,
                                float* band_signals, void* stream) {
-  DioConsts k;
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config4, &k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return PE_OK;
-  long tot[5];
-  if (!host_meta || !meta_ok(host_meta, n_rows, tot)) return PE_E_ARG;
-  for (int r = 0; r < n_rows; ++r)
-    if (host_meta[(long)r * D_K + D_BLOCKS] != (host_meta[(long)r * D_K + D_N] + k.step - 1) / k.step) return PE_E_ARG;
-  if (tot[2] == 0) return PE_OK;
+  DioBatch b;
+  const int st = open_batch(n_rows, sr, hop, config4, host_meta, kCheckBlocks, TOT_BLOCKS, &b);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!x || !meta || !stats || !tables || !band_signals) return PE_E_ARG;
-  if (n_table != table_floats(k)) return PE_E_ARG;
-#define PE_DIO_LAUNCH(L)                                                                                             \
-  hipLaunchKernelGGL(dio_bands_kernel<L>, dim3(grid_of(tot[2])), dim3(kThreads), 0, pe_stream(stream), x, meta, stats, \
-                     tables, n_rows, tot[2], tot[1], k, band_signals)
-  switch (k.log2c) {
-    case 9: PE_DIO_LAUNCH(9); break;
-    case 10: PE_DIO_LAUNCH(10); break;
-    case 11: PE_DIO_LAUNCH(11); break;
-    case 12: PE_DIO_LAUNCH(12); break;
-    default: return PE_E_UNSUPPORTED;
-  }
-#undef PE_DIO_LAUNCH
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  if (n_table != table_floats(b.k)) return PE_E_ARG;
+  return with_log2<9, 12>(b.k.log2c, [&](auto L) {
+    hipLaunchKernelGGL(dio_bands_kernel<decltype(L)::value>, dim3(grid_of(b.tot[TOT_BLOCKS])), dim3(kThreads), 0,
+                       pe_stream(stream), x, meta, stats, tables, n_rows, b.tot[TOT_BLOCKS], b.tot[TOT_SAMPLES], b.k,
+                       band_signals);
+    PE_LAUNCH_CHECK();
+    return PE_OK;
+  });
 }
 
 extern "C" int pe_f0_dio_events(const float* band_signals, const long* meta, const long* host_meta, int n_rows, int sr,
                                 int hop, const double* config4, int* e_idx, float* e_frac, int* e_count,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  DioConsts k;
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config4, &k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return PE_OK;
-  long tot[5];
-  if (!host_meta || !meta_ok(host_meta, n_rows, tot)) return PE_E_ARG;
+  DioBatch b;
+  const int st = open_batch(n_rows, sr, hop, config4, host_meta, 0, -1, &b);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!meta || !e_count) return PE_E_ARG;
-  const size_t half_ws = (size_t)tot[4] * k.bands * kKinds * sizeof(int);
-  if (tot[4] > 0) {
+  const long chunks = b.tot[TOT_CHUNKS], samples = b.tot[TOT_SAMPLES];
+  const int bands = b.k.bands;
+  const size_t half_ws = (size_t)chunks * bands * kKinds * sizeof(int);
+  if (chunks > 0) {
     if (!band_signals || !e_idx || !e_frac) return PE_E_ARG;
     if (!workspace || workspace_bytes < 2 * half_ws) return PE_E_WORKSPACE;
   }
   int* counts = static_cast<int*>(workspace);
-  int* base = counts + (size_t)tot[4] * k.bands * kKinds;
-  if (tot[4] > 0) {
-    hipLaunchKernelGGL(dio_events_kernel<false>, dim3(grid_of(tot[4])), dim3(kThreads), 0, pe_stream(stream),
-                       band_signals, meta, n_rows, tot[4], tot[1], k.bands, counts, base, e_idx, e_frac);
+  int* base = counts + (size_t)chunks * bands * kKinds;
+  if (chunks > 0) {
+    hipLaunchKernelGGL(dio_events_kernel<false>, dim3(grid_of(chunks)), dim3(kThreads), 0, pe_stream(stream),
+                       band_signals, meta, n_rows, chunks, samples, bands, counts, base, e_idx, e_frac);
     PE_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(dio_prefix_kernel, dim3(pe_cdiv((long)n_rows * k.bands * kKinds, kThreads)), dim3(kThreads), 0,
-                     pe_stream(stream), counts, meta, n_rows, k.bands, base, e_count);
+  hipLaunchKernelGGL(dio_prefix_kernel, dim3(pe_cdiv((long)n_rows * bands * kKinds, kThreads)), dim3(kThreads), 0,
+                     pe_stream(stream), counts, meta, n_rows, bands, base, e_count);
   PE_LAUNCH_CHECK();
-  if (tot[4] > 0) {
-    hipLaunchKernelGGL(dio_events_kernel<true>, dim3(grid_of(tot[4])), dim3(kThreads), 0, pe_stream(stream),
-                       band_signals, meta, n_rows, tot[4], tot[1], k.bands, counts, base, e_idx, e_frac);
+  if (chunks > 0) {
+    hipLaunchKernelGGL(dio_events_kernel<true>, dim3(grid_of(chunks)), dim3(kThreads), 0, pe_stream(stream),
+                       band_signals, meta, n_rows, chunks, samples, bands, counts, base, e_idx, e_frac);
     PE_LAUNCH_CHECK();
   }
   return PE_OK;
@@ -658,38 +665,28 @@ extern "C" int pe_f0_dio_events(const float* band_signals, const long* meta, con
 extern "C" int pe_f0_dio_candidates(const int* e_idx, const float* e_frac, const int* e_count, const long* meta,
                                     const long* host_meta, int n_rows, int sr, int hop, const double* config4,
                                     float* cand, float* score, float* best, int* best_band, void* stream) {
-  DioConsts k;
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config4, &k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return PE_OK;
-  long tot[5];
-  if (!host_meta || !meta_ok(host_meta, n_rows, tot)) return PE_E_ARG;
-  for (int r = 0; r < n_rows; ++r)
-    if (host_meta[(long)r * D_K + D_FRAMES] != frame_count(host_meta[(long)r * D_K + D_N], k)) return PE_E_ARG;
-  if (tot[0] == 0) return PE_OK;
+  DioBatch b;
+  const int st = open_batch(n_rows, sr, hop, config4, host_meta, kCheckFrames, TOT_FRAMES, &b);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!e_idx || !e_frac || !e_count || !meta || !cand || !score || !best || !best_band) return PE_E_ARG;
-  hipLaunchKernelGGL(dio_candidates_kernel, dim3(grid_of(pe_cdiv(tot[0] * k.bands, kThreads))), dim3(kThreads), 0,
-                     pe_stream(stream), e_idx, e_frac, e_count, meta, n_rows, tot[0], k, cand, score);
+  const long frames = b.tot[TOT_FRAMES];
+  hipLaunchKernelGGL(dio_candidates_kernel, dim3(grid_of(pe_cdiv(frames * b.k.bands, kThreads))), dim3(kThreads), 0,
+                     pe_stream(stream), e_idx, e_frac, e_count, meta, n_rows, frames, b.k, cand, score);
   PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(dio_best_kernel, dim3(grid_of(pe_cdiv(tot[0], kThreads))), dim3(kThreads), 0, pe_stream(stream),
-                     cand, score, tot[0], k.bands, best, best_band);
+  hipLaunchKernelGGL(dio_best_kernel, dim3(grid_of(pe_cdiv(frames, kThreads))), dim3(kThreads), 0, pe_stream(stream),
+                     cand, score, frames, b.k.bands, best, best_band);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
 
 extern "C" int pe_f0_dio_fix(const float* best, const float* cand, const long* meta, const long* host_meta, int n_rows,
                              int sr, int hop, const double* config4, float* steps4, void* stream) {
-  DioConsts k;
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config4, &k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return PE_OK;
-  long tot[5];
-  if (!host_meta || !meta_ok(host_meta, n_rows, tot)) return PE_E_ARG;
-  if (tot[0] == 0) return PE_OK;
+  DioBatch b;
+  const int st = open_batch(n_rows, sr, hop, config4, host_meta, 0, TOT_FRAMES, &b);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!best || !cand || !meta || !steps4) return PE_E_ARG;
-  hipLaunchKernelGGL(dio_fix_kernel, dim3(n_rows), dim3(64), 0, pe_stream(stream), best, cand, meta, tot[0], k, steps4);
+  hipLaunchKernelGGL(dio_fix_kernel, dim3(n_rows), dim3(64), 0, pe_stream(stream), best, cand, meta, b.tot[TOT_FRAMES],
+                     b.k, steps4);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
@@ -698,23 +695,15 @@ extern "C" int pe_f0_stonemask(const float* x, const long* meta, const long* hos
                                const float* roots, long n_roots, int n_rows, int sr, int hop, double f0_min,
                                float* f0_out, void* stream) {
   if (n_rows < 0 || n_rows > kMaxRows || sr <= 0 || hop <= 0 || !isfinite(f0_min) || !(f0_min > 0.0)) return PE_E_ARG;
-  if (sr < 8000 || sr > 48000 || hop > sr) return PE_E_UNSUPPORTED;
-  {
-    const double lowest = f0_min > 40.0 ? f0_min : 40.0;
-    const int hw = (int)(1.5 * (double)sr / lowest + 1.0);
-    int lg = 0;
-    while ((2 << lg) <= 2 * hw + 1) ++lg;
-    if (2 + lg > kSmMaxLog2) return PE_E_UNSUPPORTED;
-  }
-  if (n_rows == 0) return PE_OK;
-  long tot[5];
-  if (!host_meta || !meta_ok(host_meta, n_rows, tot)) return PE_E_ARG;
-  if (tot[0] == 0) return PE_OK;
+  if (sr < 8000 || sr > 48000 || hop > sr || !stonemask_fits(sr, f0_min)) return PE_E_UNSUPPORTED;
+  DioBatch b;
+  const int st = open_rows(n_rows, host_meta, 0, TOT_FRAMES, &b);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!x || !meta || !f0_in || !roots || !f0_out) return PE_E_ARG;
   if (n_roots != stonemask_table_floats()) return PE_E_ARG;
   const double frame_period = (double)hop * 1000.0 / (double)sr;
-  hipLaunchKernelGGL(stonemask_kernel, dim3(grid_of(tot[0])), dim3(kThreads), 0, pe_stream(stream), x, meta, f0_in,
-                     roots, n_rows, tot[0], sr, frame_period, (float)f0_min, f0_out);
+  hipLaunchKernelGGL(stonemask_kernel, dim3(grid_of(b.tot[TOT_FRAMES])), dim3(kThreads), 0, pe_stream(stream), x, meta,
+                     f0_in, roots, n_rows, b.tot[TOT_FRAMES], sr, frame_period, (float)f0_min, f0_out);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }

@@ -6,8 +6,8 @@
 //
 // Ragged batches: pe_f0_track_plan (host only) derives the constants of a configuration and lays the rows out by
 // prefix offsets of their frame counts; five launches then serve any batch:
-//   1. stats:  every row in 64 pieces, one workgroup each: double partial sums, added in a fixed order to the mean;
-//      then max |x - mean| per piece and per row (three small launches).
+//   1. stats:  pe_row_stats, for any plan (row header of dsp.h): every row in 64 pieces, one workgroup each: double
+//      partial sums, added in a fixed order to the mean; then max |x - mean| per piece and per row (three launches).
 //   2. frames: one workgroup per (row, frame), found by a binary search over the frame offsets.  The window is staged
 //      from HBM once into LDS; local mean and peak; Hann window; the real FFT runs as a packed half-length complex
 //      radix-4 Stockham FFT in place in LDS (fft_lds, dsp.h; each thread holds its butterflies' inputs in registers
@@ -29,13 +29,12 @@ namespace {
 constexpr int kCand = 15;                 // candidates per frame, [0] = unvoiced
 constexpr int kThreads = 256;
 constexpr int kLdsFrames = 4000;          // back-pointer rows of 16 bytes that stay in LDS (64 000 bytes)
-constexpr int kMaxRows = 65535;
 constexpr int kDepthFirst = 30, kDepthRefine = 70;
 constexpr int kRefineSteps = 4;
-constexpr float kPiF = 3.14159265358979323846f;
 constexpr float kSilentRatio = 9.5367431640625e-07f;     // 2^-20
 
 enum { T_XOFF, T_N, T_FRAMES, T_FOFF, T_BPOFF, T_K };
+static_assert(T_XOFF == kRowOffset && T_N == kRowLength, "the plan opens with the shared row header");
 
 struct TrackConsts {
   int nw, hw, nper, hper, nfft, log2c, maxlag, sr;
@@ -108,17 +107,17 @@ void frame_layout(long n, const TrackConsts& k, double minp, long* frames, doubl
 
 // ---- 1. per-row statistics -------------------------------------------------------------------------------------------
 // A row is cut into kChunks equal pieces (by its own length only, so the result does not depend on the batch); one
-// workgroup per (row, piece).  Partial sums are doubles added in a fixed order; no atomics.
+// workgroup per (row, piece).  Partial sums are doubles added in a fixed order; no atomics.  Reads the row header only.
 constexpr int kChunks = 64;
 
 __global__ __launch_bounds__(kThreads) void f0_sum_kernel(const float* __restrict__ x, const long* __restrict__ meta,
-                                                          double* __restrict__ part) {
+                                                          int fields, double* __restrict__ part) {
   __shared__ double s_sum[kThreads];
   const int row = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
-  const long* m = meta + (long)row * T_K;
-  const long n = m[T_N], per = (n + kChunks - 1) / kChunks;
+  const long* m = meta + (long)row * fields;
+  const long n = m[kRowLength], per = (n + kChunks - 1) / kChunks;
   const long lo = c * per, hi = lo + per < n ? lo + per : n;
-  const float* xr = x + m[T_XOFF];
+  const float* xr = x + m[kRowOffset];
   double s = 0.0;
   for (long i = lo + tid; i < hi; i += kThreads) s += (double)xr[i];
   s_sum[tid] = s;
@@ -131,15 +130,15 @@ __global__ __launch_bounds__(kThreads) void f0_sum_kernel(const float* __restric
 }
 
 __global__ __launch_bounds__(kThreads) void f0_peak_kernel(const float* __restrict__ x, const long* __restrict__ meta,
-                                                           const double* __restrict__ part, float* __restrict__ pk,
-                                                           float* __restrict__ stats) {
+                                                           int fields, const double* __restrict__ part,
+                                                           float* __restrict__ pk, float* __restrict__ stats) {
   __shared__ float s_max[kThreads];
   __shared__ float s_mean;
   const int row = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
-  const long* m = meta + (long)row * T_K;
-  const long n = m[T_N], per = (n + kChunks - 1) / kChunks;
+  const long* m = meta + (long)row * fields;
+  const long n = m[kRowLength], per = (n + kChunks - 1) / kChunks;
   const long lo = c * per, hi = lo + per < n ? lo + per : n;
-  const float* xr = x + m[T_XOFF];
+  const float* xr = x + m[kRowOffset];
   if (tid == 0) {
     double s = 0.0;
     for (int k = 0; k < kChunks; ++k) s += part[(long)row * kChunks + k];
@@ -589,6 +588,16 @@ bool meta_ok(const long* hm, int n_rows, long* total) {
   return true;
 }
 
+constexpr int kNothing = 1;               // open_batch: valid, and no frame to work on (PE_OK to the caller)
+int open_batch(int n_rows, int sr, int hop, const double* config7, const long* host_meta, TrackConsts* k, long* total) {
+  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
+  const int st = derive(sr, hop, config7, k);
+  if (st != PE_OK) return st;
+  if (n_rows == 0) return kNothing;
+  if (!host_meta || !meta_ok(host_meta, n_rows, total)) return PE_E_ARG;
+  return *total == 0 ? kNothing : PE_OK;
+}
+
 }  // namespace
 
 extern "C" int pe_f0_track_plan_fields(void) { return T_K; }
@@ -622,25 +631,25 @@ extern "C" int pe_f0_track_plan(int n_rows, const long* n, const long* x_off, in
   return PE_OK;
 }
 
-extern "C" size_t pe_f0_track_stats_workspace_bytes(int n_rows) {
+extern "C" size_t pe_row_stats_workspace_bytes(int n_rows) {
   return n_rows > 0 ? (size_t)n_rows * kChunks * (sizeof(double) + sizeof(float)) : 0;
 }
 
-extern "C" int pe_f0_track_stats(const float* x, const long* meta, int n_rows, float* stats, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
+extern "C" int pe_row_stats(const float* x, const long* meta, int meta_fields, int n_rows, float* stats,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_rows < 0 || n_rows > kMaxRows || meta_fields < kRowHeader) return PE_E_ARG;
   if (n_rows == 0) return PE_OK;
   if (!x || !meta || !stats) return PE_E_ARG;
-  if (!workspace || workspace_bytes < pe_f0_track_stats_workspace_bytes(n_rows)) return PE_E_WORKSPACE;
+  if (!workspace || workspace_bytes < pe_row_stats_workspace_bytes(n_rows)) return PE_E_WORKSPACE;
   double* part = static_cast<double*>(workspace);
   float* pk = reinterpret_cast<float*>(part + (size_t)n_rows * kChunks);
-  hipLaunchKernelGGL(f0_sum_kernel, dim3(kChunks, n_rows), dim3(kThreads), 0, pe_stream(stream), x, meta, part);
+  const dim3 pieces(kChunks, n_rows), block(kThreads);
+  hipLaunchKernelGGL(f0_sum_kernel, pieces, block, 0, pe_stream(stream), x, meta, meta_fields, part);
   PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(f0_peak_kernel, dim3(kChunks, n_rows), dim3(kThreads), 0, pe_stream(stream), x, meta, part, pk,
+  hipLaunchKernelGGL(f0_peak_kernel, pieces, block, 0, pe_stream(stream), x, meta, meta_fields, part, pk, stats);
+  PE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(f0_peak_final_kernel, dim3(pe_cdiv(n_rows, kThreads)), block, 0, pe_stream(stream), pk, n_rows,
                      stats);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(f0_peak_final_kernel, dim3(pe_cdiv(n_rows, kThreads)), dim3(kThreads), 0, pe_stream(stream), pk,
-                     n_rows, stats);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
@@ -649,49 +658,32 @@ extern "C" int pe_f0_track_frames(const float* x, const long* meta, const long* 
                                   const float* stats, const float* tables, long n_table, int n_rows, int sr, int hop,
                                   const double* config7, float* cand_f, float* cand_s, int* cand_n, void* stream) {
   TrackConsts k;
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config7, &k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return PE_OK;
   long total = 0;
-  if (!host_meta || !meta_ok(host_meta, n_rows, &total)) return PE_E_ARG;
-  if (total == 0) return PE_OK;
+  const int st = open_batch(n_rows, sr, hop, config7, host_meta, &k, &total);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!x || !meta || !t1 || !stats || !tables || !cand_f || !cand_s || !cand_n) return PE_E_ARG;
   if (n_table != table_floats(k)) return PE_E_ARG;
-  const long grid = total < (1L << 20) ? total : (1L << 20);
-#define PE_F0_LAUNCH(L)                                                                                              \
-  hipLaunchKernelGGL(f0_frames_kernel<L>, dim3((unsigned)grid), dim3(kThreads), 0, pe_stream(stream), x, meta, t1,    \
-                     stats, tables, n_rows, total, k, cand_f, cand_s, cand_n)
-  switch (k.log2c) {
-    case 9: PE_F0_LAUNCH(9); break;
-    case 10: PE_F0_LAUNCH(10); break;
-    case 11: PE_F0_LAUNCH(11); break;
-    case 12: PE_F0_LAUNCH(12); break;
-    default: return PE_E_UNSUPPORTED;
-  }
-#undef PE_F0_LAUNCH
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  return with_log2<9, 12>(k.log2c, [&](auto L) {
+    hipLaunchKernelGGL(f0_frames_kernel<decltype(L)::value>, dim3(grid_of(total)), dim3(kThreads), 0, pe_stream(stream),
+                       x, meta, t1, stats, tables, n_rows, total, k, cand_f, cand_s, cand_n);
+    PE_LAUNCH_CHECK();
+    return PE_OK;
+  });
 }
 
 extern "C" int pe_f0_track_path(const float* cand_f, const float* cand_s, const int* cand_n, const long* meta,
                                 const long* host_meta, int n_rows, int sr, int hop, const double* config7, float* f0,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   TrackConsts k;
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config7, &k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return PE_OK;
   long total = 0;
-  if (!host_meta || !meta_ok(host_meta, n_rows, &total)) return PE_E_ARG;
-  if (total == 0) return PE_OK;
+  const int st = open_batch(n_rows, sr, hop, config7, host_meta, &k, &total);
+  if (st != PE_OK) return st == kNothing ? PE_OK : st;
   if (!cand_f || !cand_s || !cand_n || !meta || !f0) return PE_E_ARG;
   long lds_frames = 1;
   const size_t need = spill_bytes(host_meta, n_rows, &lds_frames);
   if (need > 0 && (!workspace || workspace_bytes < need)) return PE_E_WORKSPACE;
   hipLaunchKernelGGL(f0_path_kernel, dim3(n_rows), dim3(64), (size_t)lds_frames * 16, pe_stream(stream), cand_f, cand_s,
-                     cand_n, meta, k, f0,
-                     static_cast<unsigned char*>(workspace));
+                     cand_n, meta, k, f0, static_cast<unsigned char*>(workspace));
   PE_LAUNCH_CHECK();
   return PE_OK;
 }

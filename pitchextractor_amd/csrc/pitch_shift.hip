@@ -35,7 +35,6 @@ constexpr int kLog2C = 10;
 constexpr int kC = 1 << kLog2C;    // complex FFT length kN / 2; one wave per transform: fft_lds<kLog2C, INV, 64>
 static_assert(2 * kC == kN, "the real frame is packed as kN / 2 complex points");
 constexpr int kP = 512;           // resampy table precision 2^9
-constexpr int kMaxRows = 65535;
 constexpr float kPi = 3.14159265358979323846f;
 constexpr float kTwoPiHi = 6.28318548202514648438f;       // float(2 pi)
 constexpr float kTwoPiLo = -1.74845553e-7f;                // 2 pi - float(2 pi)

@@ -27,7 +27,6 @@ using namespace pe;
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxRows = 65535;
 
 // per-row plan fields (int64); see pe_world_plan
 enum {
@@ -318,15 +317,12 @@ extern "C" int pe_world_responses(const float* sp, const float* ap, const float*
   if (n_pulses == 0 || n_rows == 0) return PE_OK;
   if (!sp || !meta || !pulses || !pulse_f || !table || !responses) return PE_E_ARG;
   const dim3 grid(grid_for(n_pulses, 1, 8192)), block(kThreads);
-#define PE_WORLD_RESP(LOG2N)                                                                                       \
-  hipLaunchKernelGGL(world_responses_kernel<LOG2N>, grid, block, 0, pe_stream(stream), sp, ap, noise, meta, pulses, \
-                     pulse_f, table, n_pulses, responses)
-  if (fft_size == 512) PE_WORLD_RESP(9);
-  else if (fft_size == 1024) PE_WORLD_RESP(10);
-  else PE_WORLD_RESP(11);
-#undef PE_WORLD_RESP
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  return with_log2<9, 11>(__builtin_ctz(fft_size), [&](auto L) {
+    hipLaunchKernelGGL(world_responses_kernel<decltype(L)::value>, grid, block, 0, pe_stream(stream), sp, ap, noise,
+                       meta, pulses, pulse_f, table, n_pulses, responses);
+    PE_LAUNCH_CHECK();
+    return PE_OK;
+  });
 }
 
 extern "C" int pe_world_overlap_add(const float* responses, const long* meta, const long* pulses, const float* gains,
@@ -337,13 +333,10 @@ extern "C" int pe_world_overlap_add(const float* responses, const long* meta, co
   if (n_out == 0 || n_rows == 0) return PE_OK;
   if (!meta || !gains || !out) return PE_E_ARG;               // responses / pulses may be empty: a window no pulse meets
   const dim3 grid(grid_for(n_out, kThreads, 8192)), block(kThreads);
-#define PE_WORLD_OLA(LOG2N)                                                                                      \
-  hipLaunchKernelGGL(world_ola_kernel<LOG2N>, grid, block, 0, pe_stream(stream), responses, meta, pulses, gains, \
-                     out_noise, n_rows, n_out, out)
-  if (fft_size == 512) PE_WORLD_OLA(9);
-  else if (fft_size == 1024) PE_WORLD_OLA(10);
-  else PE_WORLD_OLA(11);
-#undef PE_WORLD_OLA
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  return with_log2<9, 11>(__builtin_ctz(fft_size), [&](auto L) {
+    hipLaunchKernelGGL(world_ola_kernel<decltype(L)::value>, grid, block, 0, pe_stream(stream), responses, meta, pulses,
+                       gains, out_noise, n_rows, n_out, out);
+    PE_LAUNCH_CHECK();
+    return PE_OK;
+  });
 }

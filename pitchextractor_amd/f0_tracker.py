@@ -8,11 +8,14 @@ refused with ``NotImplementedError`` when the tracker (or a dataset that names i
 
 ``WorldDioTracker`` (below) is the reference's ``pyworld`` backend with ``algorithm: dio``: WORLD's DIO + StoneMask
 (``csrc/f0_dio.hip``), pinned by ``tests/dio_ref.py`` in the same way.
+
+Both stand on ``_RaggedTracker``; ``NATIVE_BACKENDS`` alone says which entries of a backend chain run on the device.
 """
 from __future__ import annotations
 
 import logging
 import re
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -22,13 +25,23 @@ from .ragged import packed_offsets, row_layout
 
 logger = logging.getLogger(__name__)
 
-NATIVE_TYPES = ("praat", "parselmouth")            # always native; a `pyworld` entry is when its config says dio
+NATIVE_TYPES = ("praat", "parselmouth")            # native whatever the config says; see NATIVE_BACKENDS
 DEFAULT_CONFIG = dict(min_pitch=40.0, max_pitch=1100.0, silence_threshold=0.03, voicing_threshold=0.45,
                       octave_cost=0.01, octave_jump_cost=1.0, voiced_unvoiced_cost=0.3, very_accurate=False)
 _CONFIG_ORDER = ("min_pitch", "max_pitch", "silence_threshold", "voicing_threshold", "octave_cost",
                  "octave_jump_cost", "voiced_unvoiced_cost")
 _IGNORED_KEYS = {"name", "type", "backend", "enabled", "cache_key_suffix"}
 N_CAND = 15
+
+
+def _p(*arrays):
+    return [a.ctypes.data for a in arrays]
+
+
+def _flag(value) -> bool:
+    if isinstance(value, str):
+        return value.strip().lower() in {"1", "true", "yes", "on"}
+    return bool(value)
 
 
 def check_config(config: dict | None, require_method: bool = False) -> dict:
@@ -53,22 +66,79 @@ def check_config(config: dict | None, require_method: bool = False) -> dict:
             out[k] = v
         elif k not in _IGNORED_KEYS:                  # the reference's PraatBackend reads no other key either
             logger.warning("praat F0 backend: option %r is not read (the reference ignores it too)", k)
-    va = out.pop("very_accurate")
-    if isinstance(va, str):
-        va = va.strip().lower() in {"1", "true", "yes", "on"}
-    if va:
+    if _flag(out.pop("very_accurate")):
         raise NotImplementedError("praat F0 backend: very_accurate (Gaussian window, 6 periods) is not built")
     return {k: float(out[k]) for k in _CONFIG_ORDER}
 
 
-class PraatACTracker:
+def fft_roots(C: int) -> np.ndarray:
+    """The C-th roots of unity with the forward sign, exp(-2 pi i m / C) for m < C: float64, shape (C, 2)."""
+    m = np.arange(C, dtype=np.float64)
+    return np.stack([np.cos(2 * np.pi * m / C), -np.sin(2 * np.pi * m / C)], axis=1)
+
+
+def real_split_roots(C: int) -> np.ndarray:
+    """exp(-2 pi i k / 2C) for k <= C (a packed C-point transform -> the real 2C-point one): float64, (C + 1, 2)."""
+    k = np.arange(C + 1, dtype=np.float64)
+    return np.stack([np.cos(np.pi * k / C), -np.sin(np.pi * k / C)], axis=1)
+
+
+class _RaggedTracker:
+    """What the trackers share: device audio at ``sr`` goes through a host-side row plan (a row's fields 0 .. 3: offset,
+    length, frames, frame prefix offset) and comes back as one contour per row.  A subclass has ``plan()``."""
+
+    def __init__(self, sr: int, hop_length: int):
+        self.sr, self.hop_length = int(sr), int(hop_length)
+
+    def _plan_rows(self, lengths, offsets, fields_fn: str):
+        """``(R, lengths, offsets, meta)``: int64 arrays (packed when ``offsets`` is None) and the zeroed plan."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+        R = lengths.size
+        if offsets is None:
+            offsets = packed_offsets(lengths)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size != R:
+            raise ValueError("f0 tracker: one offset per row")
+        meta = np.zeros((max(R, 1), getattr(_lib.load(), fields_fn)()), np.int64)
+        return R, lengths, offsets, meta
+
+    def _check_waves(self, waves):
+        if not isinstance(waves, torch.Tensor) or not waves.is_cuda or waves.dtype != torch.float32 or \
+                waves.dim() not in (1, 2) or (waves.numel() > 0 and waves.stride(-1) != 1):
+            raise RuntimeError(f"{type(self).__name__} (HIP) needs contiguous-row float32 device audio; no CPU "
+                               "fallback exists")
+
+    def _device_plan(self, waves, lengths):
+        """The plan of ``waves`` in one of ``track``'s three layouts, with its device copy as ``meta_d``."""
+        self._check_waves(waves)
+        pl = self.plan(*row_layout(waves, lengths, whole_by_default=True))
+        pl["meta_d"] = torch.from_numpy(pl["meta"]).to(waves.device)
+        return pl
+
+    def frame_count(self, n_samples: int) -> int:
+        return int(self.plan([int(n_samples)])["frames"][0])
+
+    def _contours(self, f0, plan):
+        f0_h = f0.cpu().numpy()
+        return [f0_h[int(o):int(o) + int(n)].copy() for o, n in zip(plan["frame_offsets"], plan["frames"])]
+
+    def _row_stats(self, waves, meta_d, R, stats, stream, work):
+        """``pe_row_stats``: stats[r] = {mean, max |x - mean|} of the R rows of a device plan, at the plan's own stride."""
+        ws_bytes = _lib.load().pe_row_stats_workspace_bytes(R)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=waves.device)
+        ops._call("pe_row_stats", waves.data_ptr(), meta_d.data_ptr(), int(meta_d.shape[1]), R, stats.data_ptr(),
+                  ws.data_ptr(), ws_bytes, stream, work=float(work))
+
+
+class PraatACTracker(_RaggedTracker):
     """``PraatACTracker(sr, hop_length, method="ac", **config)``: time step ``hop_length / sr`` (f0_backends.py:497).
 
     ``track`` runs a ragged batch in a fixed number of launches; a row's contour is bit-identical whether it is
     tracked alone or inside any batch."""
+    cache_key = "praat"
 
     def __init__(self, sr: int, hop_length: int, **config):
-        self.sr, self.hop_length = int(sr), int(hop_length)
+        super().__init__(sr, hop_length)
         self.config = check_config(config)
         self._cfg = np.array([self.config[k] for k in _CONFIG_ORDER], dtype=np.float64)
         # the constants of the configuration (host only): also validates (sr, hop, config) against the kernels' range
@@ -77,34 +147,17 @@ class PraatACTracker:
          self.n_table, self.lds_frames) = (int(v) for v in plan["consts"])
         self.ceiling, self.time_step = (float(v) for v in plan["dconsts"])
 
-    @property
-    def cache_key(self) -> str:
-        return "praat"
-
     # ---- host side ----------------------------------------------------------------------------------------------
     def plan(self, lengths, offsets=None) -> dict:
         """``pe_f0_track_plan``: per-row frame counts / offsets / first frame centres for rows of ``lengths``."""
-        lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-        R = lengths.size
-        if offsets is None:
-            offsets = packed_offsets(lengths)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-        if offsets.size != R:
-            raise ValueError("f0 tracker: one offset per row")
-        lib = _lib.load()
-        K = lib.pe_f0_track_plan_fields()
-        meta = np.zeros((max(R, 1), K), np.int64)
+        R, lengths, offsets, meta = self._plan_rows(lengths, offsets, "pe_f0_track_plan_fields")
         t1 = np.zeros(max(R, 1), np.float64)
         consts, dconsts, totals = np.zeros(8, np.int64), np.zeros(2, np.float64), np.zeros(2, np.int64)
-        p = lambda a: a.ctypes.data  # noqa: E731
-        _lib.check(lib.pe_f0_track_plan(R, p(lengths), p(offsets), self.sr, self.hop_length, p(self._cfg), p(consts),
-                                        p(dconsts), p(meta), p(t1), p(totals)), "pe_f0_track_plan")
+        _lib.check(_lib.load().pe_f0_track_plan(R, *_p(lengths, offsets), self.sr, self.hop_length,
+                                                *_p(self._cfg, consts, dconsts, meta, t1, totals)), "pe_f0_track_plan")
         return dict(n_rows=R, lengths=lengths, offsets=offsets, meta=meta, t1=t1, consts=consts, dconsts=dconsts,
                     frames=meta[:R, 2].copy(), frame_offsets=meta[:R, 3].copy(), n_frames=int(totals[0]),
                     workspace_bytes=int(totals[1]))
-
-    def frame_count(self, n_samples: int) -> int:
-        return int(self.plan([int(n_samples)])["frames"][0])
 
     def frame_times(self, n_samples: int) -> np.ndarray:
         pl = self.plan([int(n_samples)])
@@ -113,15 +166,12 @@ class PraatACTracker:
     def host_tables(self) -> np.ndarray:
         """float32 tables of the frame kernel, built in float64: FFT roots, real-split roots, window, window_r."""
         C, nw, hw = self.n_fft // 2, self.nsamp_window, self.half_window
-        m = np.arange(C, dtype=np.float64)
-        k = np.arange(C + 1, dtype=np.float64)
-        tw = np.stack([np.cos(2 * np.pi * m / C), -np.sin(2 * np.pi * m / C)], axis=1)
-        tr = np.stack([np.cos(np.pi * k / C), -np.sin(np.pi * k / C)], axis=1)
         window = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(1, nw + 1, dtype=np.float64) / (nw + 1))
         spec = np.fft.rfft(window, self.n_fft)
         ac = np.fft.irfft(spec.real ** 2 + spec.imag ** 2, self.n_fft)
         window_r = ac[:hw + 1] / ac[0]
-        out = np.concatenate([tw.reshape(-1), tr.reshape(-1), window, window_r]).astype(np.float32)
+        out = np.concatenate([fft_roots(C).reshape(-1), real_split_roots(C).reshape(-1), window,
+                              window_r]).astype(np.float32)
         assert out.size == self.n_table
         return out
 
@@ -131,11 +181,7 @@ class PraatACTracker:
         (``lengths`` required) or a padded 2-D batch (``lengths`` per row, default the width).  Returns one float32
         contour per row (Hz, 0 = unvoiced; empty when the row is shorter than one window), or with
         ``return_candidates`` a dict with the candidate tables as well."""
-        if not isinstance(waves, torch.Tensor) or not waves.is_cuda or waves.dtype != torch.float32 or \
-                waves.dim() not in (1, 2) or waves.stride(-1) != 1:
-            raise RuntimeError("PraatACTracker (HIP) needs contiguous-row float32 device audio; no CPU fallback exists")
-        lengths, offsets = row_layout(waves, lengths, whole_by_default=True)
-        pl = self.plan(lengths, offsets)
+        pl = self._device_plan(waves, lengths)
         R, G = pl["n_rows"], pl["n_frames"]
         dev = waves.device
         cand_f = torch.zeros((G, N_CAND), dtype=torch.float32, device=dev)
@@ -143,9 +189,7 @@ class PraatACTracker:
         cand_n = torch.zeros((G,), dtype=torch.int32, device=dev)
         f0 = torch.zeros((G,), dtype=torch.float32, device=dev)
         if R and G:
-            meta_h, t1_h = pl["meta"], pl["t1"]
-            meta = torch.from_numpy(meta_h).to(dev)
-            t1 = torch.from_numpy(t1_h).to(dev)
+            meta_h, meta, t1 = pl["meta"], pl["meta_d"], torch.from_numpy(pl["t1"]).to(dev)
             stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
             tables = _lib.device_table(("f0_track", self.n_fft, self.nsamp_window), dev, self.host_tables)
             ws_bytes = pl["workspace_bytes"]
@@ -154,23 +198,18 @@ class PraatACTracker:
             flop = 2 * 2.5 * self.n_fft * np.log2(self.n_fft)
             with torch.cuda.device(dev):
                 s = _lib.stream_ptr()
-                sws_bytes = _lib.load().pe_f0_track_stats_workspace_bytes(R)
-                sws = torch.empty((sws_bytes,), dtype=torch.uint8, device=dev)
-                ops._call("pe_f0_track_stats", waves.data_ptr(), meta.data_ptr(), R, stats.data_ptr(), sws.data_ptr(),
-                          sws_bytes, s, work=float(sum(lengths) * 8))
+                self._row_stats(waves, meta, R, stats, s, int(pl["lengths"].sum()) * 8)
                 ops._call("pe_f0_track_frames", waves.data_ptr(), meta.data_ptr(), meta_h.ctypes.data, t1.data_ptr(),
                           stats.data_ptr(), tables.data_ptr(), int(tables.numel()), R, self.sr, self.hop_length, cfg,
                           cand_f.data_ptr(), cand_s.data_ptr(), cand_n.data_ptr(), s, work=float(G * flop))
                 ops._call("pe_f0_track_path", cand_f.data_ptr(), cand_s.data_ptr(), cand_n.data_ptr(),
                           meta.data_ptr(), meta_h.ctypes.data, R, self.sr, self.hop_length, cfg, f0.data_ptr(),
                           _lib.ptr(ws), ws_bytes, s, work=float(G * (2 * N_CAND * 4 + 8)))
-        frames, foff = pl["frames"], pl["frame_offsets"]
-        f0_h = f0.cpu().numpy()
-        contours = [f0_h[int(o):int(o) + int(n)].copy() for o, n in zip(foff, frames)]
+        contours = self._contours(f0, pl)
         if not return_candidates:
             return contours
         return dict(f0=contours, cand_f=cand_f.cpu().numpy(), cand_s=cand_s.cpu().numpy(),
-                    cand_n=cand_n.cpu().numpy(), frames=frames, frame_offsets=foff)
+                    cand_n=cand_n.cpu().numpy(), frames=pl["frames"], frame_offsets=pl["frame_offsets"])
 
 
 # --------------------------------------------------------------------------- WORLD DIO + StoneMask (pyworld backend)
@@ -178,12 +217,6 @@ DIO_DEFAULTS = dict(f0_floor=71.0, f0_ceil=800.0, channels_in_octave=2.0, allowe
 _DIO_ORDER = ("f0_floor", "f0_ceil", "channels_in_octave", "allowed_range")
 _DIO_NUTTALL = (0.355768, 0.487396, 0.144232, 0.012604)
 _DIO_KINDS = 4
-
-
-def _flag(value) -> bool:
-    if isinstance(value, str):
-        return value.strip().lower() in {"1", "true", "yes", "on"}
-    return bool(value)
 
 
 def dio_fallback_ok(fallback) -> bool:
@@ -220,13 +253,15 @@ def check_dio_config(config: dict | None, sr: int, hop: int, require_algorithm: 
     return out
 
 
-class WorldDioTracker:
+class WorldDioTracker(_RaggedTracker):
     """``WorldDioTracker(sr, hop_length, **config)``: ``pyworld.dio`` + ``pyworld.stonemask`` with pyworld's defaults
     at ``frame_period = hop_length * 1000 / sr`` as HIP launches over a ragged batch (``csrc/f0_dio.hip``).  A row's
     contour is bit-identical whether it is tracked alone or inside any batch.  There is no CPU path."""
 
+    cache_key = "pyworld"
+
     def __init__(self, sr: int, hop_length: int, **config):
-        self.sr, self.hop_length = int(sr), int(hop_length)
+        super().__init__(sr, hop_length)
         if self.sr <= 0 or self.hop_length <= 0:
             raise ValueError("WorldDioTracker: sr and hop_length must be positive")
         self.config = check_dio_config(config, self.sr, self.hop_length)
@@ -240,36 +275,19 @@ class WorldDioTracker:
         self.frame_period = float(plan["dconsts"][0])
         self.boundary = [float(v) for v in plan["dconsts"][1:1 + self.bands]]
 
-    @property
-    def cache_key(self) -> str:
-        return "pyworld"
-
     # ---- host side ----------------------------------------------------------------------------------------------
     def plan(self, lengths, offsets=None) -> dict:
         """``pe_f0_dio_plan``: the constants and the per-row layout for rows of ``lengths``."""
-        lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-        R = lengths.size
-        if offsets is None:
-            offsets = packed_offsets(lengths)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-        if offsets.size != R:
-            raise ValueError("f0 tracker: one offset per row")
-        lib = _lib.load()
-        K = lib.pe_f0_dio_plan_fields()
-        meta = np.zeros((max(R, 1), K), np.int64)
+        R, lengths, offsets, meta = self._plan_rows(lengths, offsets, "pe_f0_dio_plan_fields")
         consts, half = np.zeros(10, np.int64), np.zeros(16, np.int64)
         dconsts, totals = np.zeros(17, np.float64), np.zeros(6, np.int64)
-        p = lambda a: a.ctypes.data  # noqa: E731
-        _lib.check(lib.pe_f0_dio_plan(R, p(lengths), p(offsets), self.sr, self.hop_length, p(self._cfg), p(consts),
-                                      p(half), p(dconsts), p(meta), p(totals)), "pe_f0_dio_plan")
+        _lib.check(_lib.load().pe_f0_dio_plan(R, *_p(lengths, offsets), self.sr, self.hop_length,
+                                              *_p(self._cfg, consts, half, dconsts, meta, totals)), "pe_f0_dio_plan")
         return dict(n_rows=R, lengths=lengths, offsets=offsets, meta=meta, consts=consts, half=half, dconsts=dconsts,
                     frames=meta[:R, 2].copy(), frame_offsets=meta[:R, 3].copy(), sample_offsets=meta[:R, 4].copy(),
                     event_offsets=meta[:R, 7].copy(), n_frames=int(totals[0]), n_samples=int(totals[1]),
                     n_blocks=int(totals[2]), n_event_slots=int(totals[3]), n_chunks=int(totals[4]),
                     workspace_bytes=int(totals[5]))
-
-    def frame_count(self, n_samples: int) -> int:
-        return int(self.plan([int(n_samples)])["frames"][0])
 
     def frame_times(self, n_samples: int) -> np.ndarray:
         return np.arange(self.frame_count(n_samples), dtype=np.float64) * self.frame_period / 1000.0
@@ -278,15 +296,11 @@ class WorldDioTracker:
         """float32 tables of the band kernel, built in float64: FFT roots, real-split roots, and per band the
         spectrum (divided by C) of low-cut filter * Nuttall low-pass, delayed to the longest band's delay."""
         N, C = self.n_fft, self.n_fft // 2
-        m = np.arange(C, dtype=np.float64)
-        k = np.arange(C + 1, dtype=np.float64)
-        tw = np.stack([np.cos(2 * np.pi * m / C), -np.sin(2 * np.pi * m / C)], axis=1)
-        tr = np.stack([np.cos(np.pi * k / C), -np.sin(np.pi * k / C)], axis=1)
         n_cut = 2 * self.cut + 1
         w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(1, n_cut + 1, dtype=np.float64) / (n_cut + 1))
         low_cut = -w / np.sum(w)
         low_cut[self.cut] += 1.0
-        parts = [tw.reshape(-1), tr.reshape(-1)]
+        parts = [fft_roots(C).reshape(-1), real_split_roots(C).reshape(-1)]
         a = _DIO_NUTTALL
         for h in self.half_average_length:
             t = np.arange(4 * h, dtype=np.float64) / (4 * h - 1.0)
@@ -302,25 +316,11 @@ class WorldDioTracker:
         return out
 
     def host_roots(self) -> np.ndarray:
-        parts = []
-        for lg in range(7, 13):
-            m = np.arange(1 << lg, dtype=np.float64) / (1 << lg)
-            parts.append(np.stack([np.cos(2 * np.pi * m), -np.sin(2 * np.pi * m)], axis=1).reshape(-1))
-        out = np.concatenate(parts).astype(np.float32)
+        out = np.concatenate([fft_roots(1 << lg).reshape(-1) for lg in range(7, 13)]).astype(np.float32)
         assert out.size == self.n_roots
         return out
 
     # ---- device side: one method per stage ----------------------------------------------------------------------
-    def _device_plan(self, waves, lengths):
-        if not isinstance(waves, torch.Tensor) or not waves.is_cuda or waves.dtype != torch.float32 or \
-                waves.dim() not in (1, 2) or (waves.numel() > 0 and waves.stride(-1) != 1):
-            raise RuntimeError("WorldDioTracker (HIP) needs contiguous-row float32 device audio; no CPU fallback "
-                               "exists")
-        lengths, offsets = row_layout(waves, lengths, whole_by_default=True)
-        pl = self.plan(lengths, offsets)
-        pl["meta_d"] = torch.from_numpy(pl["meta"]).to(waves.device)
-        return pl
-
     def _args(self, pl):
         return (pl["n_rows"], self.sr, self.hop_length, self._cfg.ctypes.data)
 
@@ -332,14 +332,7 @@ class WorldDioTracker:
         tables = _lib.device_table(("f0_dio", self.sr, tuple(self.half_average_length)), dev, self.host_tables)
         s = _lib.stream_ptr()
         if R and pl["n_samples"]:
-            # pe_f0_track_stats reads fields 0 / 1 of a row's plan (offset, length) at the stride of its own plan
-            tmeta = np.zeros((R, _lib.load().pe_f0_track_plan_fields()), np.int64)
-            tmeta[:, 0], tmeta[:, 1] = pl["meta"][:R, 0], pl["meta"][:R, 1]
-            tmeta_d = torch.from_numpy(tmeta).to(dev)
-            sws_bytes = _lib.load().pe_f0_track_stats_workspace_bytes(R)
-            sws = torch.empty((sws_bytes,), dtype=torch.uint8, device=dev)
-            ops._call("pe_f0_track_stats", waves.data_ptr(), tmeta_d.data_ptr(), R, stats.data_ptr(), sws.data_ptr(),
-                      sws_bytes, s, work=float(pl["n_samples"] * 8))
+            self._row_stats(waves, pl["meta_d"], R, stats, s, pl["n_samples"] * 8)
         if pl["n_samples"]:
             ops._call("pe_f0_dio_bands", waves.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data,
                       stats.data_ptr(), tables.data_ptr(), int(tables.numel()), *self._args(pl), sig.data_ptr(), s,
@@ -407,15 +400,13 @@ class WorldDioTracker:
             cand, score, best, band = self.stage_candidates(e_idx, e_frac, e_count, pl)
             steps = self.stage_fix(best, cand, pl)
             f0 = self.stage_stonemask(waves, steps[3], pl) if self.stonemask else steps[3]
-        frames, foff = pl["frames"], pl["frame_offsets"]
-        f0_h = f0.cpu().numpy()
-        contours = [f0_h[int(o):int(o) + int(n)].copy() for o, n in zip(foff, frames)]
+        contours = self._contours(f0, pl)
         if not return_stages:
             return contours
         return dict(f0=contours, plan=pl, bands=sig.cpu().numpy(), e_idx=e_idx.cpu().numpy(),
                     e_frac=e_frac.cpu().numpy(), e_count=e_count.cpu().numpy(), cand=cand.cpu().numpy(),
                     score=score.cpu().numpy(), best=best.cpu().numpy(), best_band=band.cpu().numpy(),
-                    steps=steps.cpu().numpy(), frames=frames, frame_offsets=foff)
+                    steps=steps.cpu().numpy(), frames=pl["frames"], frame_offsets=pl["frame_offsets"])
 
     def row_events(self, e_idx, e_frac, e_count, pl, row):
         """Host view of one row's events: [band][kind] -> (idx, frac)."""
@@ -430,3 +421,29 @@ class WorldDioTracker:
                 kinds.append((np.asarray(e_idx[at:at + c], np.int64), np.asarray(e_frac[at:at + c])))
             out.append(kinds)
         return out
+
+
+# --------------------------------------------------------------------------- the backends this build runs on the device
+# key: what ``inference.track_f0(backend=...)`` takes; types: the chain-entry ``type`` values served; accepts(config): is
+# such an entry this backend's (else it is outside this build); check(config, sr, hop): a dataset entry's validated config
+NativeBackend = namedtuple("NativeBackend", "key tracker types accepts check")
+
+
+def _asks_for_dio(config: dict) -> bool:
+    """A ``pyworld`` entry runs on the device iff it asks for DIO alone: ``algorithm: dio`` (a missing key means
+    harvest in the reference) and a fallback that reruns dio or is none."""
+    return str(config.get("algorithm", "harvest")).strip().lower() == "dio" and dio_fallback_ok(config.get("fallback"))
+
+
+NATIVE_BACKENDS = (
+    NativeBackend("praat", PraatACTracker, NATIVE_TYPES, lambda config: True,
+                  lambda config, sr, hop: check_config(config, require_method=True)),
+    NativeBackend("dio", WorldDioTracker, ("pyworld",), _asks_for_dio,
+                  lambda config, sr, hop: check_dio_config(config, sr, hop, require_algorithm=True)),
+)
+
+
+def native_backend(btype: str, config):
+    """The row of ``NATIVE_BACKENDS`` that runs a backend-chain entry of type ``btype`` with ``config``, or None."""
+    config = config if isinstance(config, dict) else {}
+    return next((row for row in NATIVE_BACKENDS if btype in row.types and row.accepts(config)), None)

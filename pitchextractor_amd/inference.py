@@ -143,8 +143,8 @@ def track_f0(wave, *, sr: int, hop_length: int, device="cuda", backend: str = "p
     value every ``hop_length / sr`` seconds -- praat: over the frames whose window lies inside the wave; dio: from
     time 0 -- not the mel frame count: ``pitch_metrics(predict_f0(...), align_length(track_f0(...), L))`` scores a
     model against it."""
-    from .f0_tracker import PraatACTracker, WorldDioTracker
-    classes = {"praat": PraatACTracker, "dio": WorldDioTracker}
+    from .f0_tracker import NATIVE_BACKENDS
+    classes = {row.key: row.tracker for row in NATIVE_BACKENDS}
     if backend not in classes:
         raise ValueError(f"track_f0: backend {backend!r} is not one of {sorted(classes)}")
     key = (backend, int(sr), int(hop_length), tuple(sorted((k, str(v)) for k, v in config.items())))

@@ -65,7 +65,7 @@ from torch.utils.data import DataLoader
 from typing import NamedTuple
 
 from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS, MelSpectrogram
-from .f0_tracker import NATIVE_TYPES, check_config, check_dio_config, dio_fallback_ok
+from . import f0_tracker
 from .pitch_shift import check_res_type, pitch_shift_ragged
 from .resample import RaggedResampler, Resampler
 from .world import WorldGenerator, noise_seed, output_length, world_synthesize_ragged
@@ -254,14 +254,6 @@ def f0_backend_chain(f0_params: dict | None):
     return chain
 
 
-def _native_pyworld(btype: str, config) -> bool:
-    """A ``pyworld`` entry runs on the device iff it asks for DIO alone: ``algorithm: dio`` (a missing key means
-    harvest in the reference) and a fallback that reruns dio or is none."""
-    if btype != "pyworld" or not isinstance(config, dict):
-        return False
-    return str(config.get("algorithm", "harvest")).strip().lower() == "dio" and dio_fallback_ok(config.get("fallback"))
-
-
 def f0_cache_identifier(f0_params: dict | None) -> str:
     """The reference's ``F0Extractor.cache_identifier`` (f0_backends.py:661-757) for an ``f0_params``
     block: "-" + the cache keys of the enabled backends in chain order, joined by "_" (the shipped
@@ -388,14 +380,10 @@ class MelDataset(torch.utils.data.Dataset):
         # native (on-device) entries of the backend chain: validated now, run by prepare_f0_caches
         self._f0_chain = f0_backend_chain(self.f0_params)
         hop = int(self.mel_params["hop_length"])
-        self._native_f0 = []                              # (name, tracker class name, validated config), chain order
-        for name, btype, cfg in self._f0_chain:
-            cfg = cfg if isinstance(cfg, dict) else {}
-            if btype in NATIVE_TYPES:
-                self._native_f0.append((name, "PraatACTracker", check_config(cfg, require_method=True)))
-            elif _native_pyworld(btype, cfg):
-                self._native_f0.append((name, "WorldDioTracker",
-                                        check_dio_config(cfg, self.sr, hop, require_algorithm=True)))
+        rows = [(name, f0_tracker.native_backend(btype, cfg), cfg if isinstance(cfg, dict) else {})
+                for name, btype, cfg in self._f0_chain]
+        # (name, tracker class name, validated config), chain order
+        self._native_f0 = [(name, row.tracker.__name__, row.check(cfg, self.sr, hop)) for name, row, cfg in rows if row]
         self._audio_metadata_cache = {}
         self._invalid_paths = set()
         self._mel_cache_suffix, self._mel_meta_suffix = "_mel.npy", "_mel_meta.json"      # meldataset.py:102-103
@@ -693,12 +681,11 @@ class MelDataset(torch.utils.data.Dataset):
             raise RuntimeError("prepare_f0_caches: f0_params enables no praat / parselmouth backend; the other "
                                "backends are outside this build")
         for name, btype, cfg in self._f0_chain:
-            if btype not in NATIVE_TYPES and not _native_pyworld(btype, cfg):
+            if f0_tracker.native_backend(btype, cfg) is None:
                 logger.warning("[MelDataset] F0 backend '%s' (%s) is not part of this build: skipped", name, btype)
         todo = self.files_to_label(rank, world)
         if not todo:
             return []
-        from . import f0_tracker
         hop = int(self.mel_params["hop_length"])
         trackers = [(name, (tracker_factory or getattr(f0_tracker, cls))(self.sr, hop, **cfg))
                     for name, cls, cfg in self._native_f0]

@@ -1,5 +1,7 @@
-"""Host-side layout of a ragged batch, shared by the kernels that take one (``RaggedResampler``, ``PraatACTracker``,
-the pitch-shift ``Plan``): rows packed back to back in a 1-D tensor or padded in a 2-D one, as lengths and offsets."""
+"""Host-side layout of a ragged batch: rows packed back to back in a 1-D tensor or padded in a 2-D one, as lengths and
+offsets.  Everything that takes such a batch reads it through here: ``RaggedResampler``, the pitch-shift ``Plan``, and
+the F0 trackers through ``f0_tracker._RaggedTracker`` (``PraatACTracker``, ``WorldDioTracker``), whose C row plans then
+open with exactly these two numbers per row (offset, length)."""
 from __future__ import annotations
 
 import numpy as np

@@ -258,15 +258,16 @@ def test_track_argument_checks_run_before_any_device_call(lib):
     d = ctypes.cast(buf, ctypes.c_void_p)
     ntab = int(consts[6])
     gc = p(good)
-    sws = lib.pe_f0_track_stats_workspace_bytes(2)
-    assert sws == 2 * 64 * 12 and lib.pe_f0_track_stats_workspace_bytes(0) == 0
-    assert lib.pe_f0_track_stats(None, d, 2, d, d, sws, None) == ARG
-    assert lib.pe_f0_track_stats(d, None, 2, d, d, sws, None) == ARG
-    assert lib.pe_f0_track_stats(d, d, 2, None, d, sws, None) == ARG
-    assert lib.pe_f0_track_stats(d, d, -1, d, d, sws, None) == ARG
-    assert lib.pe_f0_track_stats(d, d, 2, d, None, sws, None) == WORKSPACE
-    assert lib.pe_f0_track_stats(d, d, 2, d, d, sws - 1, None) == WORKSPACE
-    assert lib.pe_f0_track_stats(None, None, 0, None, None, 0, None) == 0
+    sws, K = lib.pe_row_stats_workspace_bytes(2), lib.pe_f0_track_plan_fields()
+    assert sws == 2 * 64 * 12 and lib.pe_row_stats_workspace_bytes(0) == 0
+    assert lib.pe_row_stats(None, d, K, 2, d, d, sws, None) == ARG
+    assert lib.pe_row_stats(d, None, K, 2, d, d, sws, None) == ARG
+    assert lib.pe_row_stats(d, d, K, 2, None, d, sws, None) == ARG
+    assert lib.pe_row_stats(d, d, K, -1, d, d, sws, None) == ARG
+    assert lib.pe_row_stats(d, d, 1, 2, d, d, sws, None) == ARG            # a plan row holds at least offset and length
+    assert lib.pe_row_stats(d, d, K, 2, d, None, sws, None) == WORKSPACE
+    assert lib.pe_row_stats(d, d, K, 2, d, d, sws - 1, None) == WORKSPACE
+    assert lib.pe_row_stats(None, None, K, 0, None, None, 0, None) == 0
 
     def frames(x=d, m=d, hm=p(meta), t=d, st=d, tab=d, nt=ntab, rows=2, sr=24000, hop=300, c=gc, cf=d, cs=d, cn=d):
         return lib.pe_f0_track_frames(x, m, hm, t, st, tab, nt, rows, sr, hop, c, cf, cs, cn, None)

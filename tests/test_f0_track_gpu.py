@@ -132,3 +132,51 @@ def test_track_f0_feeds_pitch_metrics():
     L = 1 + len(y) // hop
     m = inference.pitch_metrics(align_length(f0, L), align_length(ref["f0"], L))
     assert m["vuv_error"] == 0.0 and m["rpa"] == 1.0 and m["rms_cents"] < 0.1
+
+
+def _stats_in_kernel_order(x):
+    """{mean, max |x - mean|} of one row as ``pe_row_stats`` documents it: 64 pieces of ceil(n / 64) samples; in a piece
+    thread t of 256 adds samples t, t + 256, .. in float64, the threads are summed as a binary tree (t += t + h,
+    h = 128 .. 1), the pieces in order; mean = float32(sum / n); the peak is a float32 maximum."""
+    n = x.size
+    if n == 0:
+        return np.float32(0.0), np.float32(0.0)
+    per = -(-n // 64)
+    total = np.float64(0.0)
+    for c in range(64):
+        piece = x[c * per:min(c * per + per, n)].astype(np.float64)
+        lanes = np.zeros(256, np.float64)
+        for k in range(0, piece.size, 256):
+            part = piece[k:k + 256]
+            lanes[:part.size] += part
+        h = 128
+        while h:
+            lanes[:h] += lanes[h:2 * h]
+            h >>= 1
+        total = total + lanes[0]
+    mean = np.float32(total / np.float64(n))
+    return mean, np.max(np.abs(x - mean)).astype(np.float32)
+
+
+def test_row_stats_do_not_depend_on_the_plan_stride():
+    from pitchextractor_amd import _lib
+    from pitchextractor_amd.f0_tracker import PraatACTracker, WorldDioTracker
+    lengths = [0, 1, 255, 70001]                                      # the last: all 64 pieces, a ragged tail
+    rng = np.random.default_rng(5)
+    rows = [(rng.standard_normal(n) * 0.2 + 0.25).astype(np.float32) for n in lengths]
+    flat, _ = _pack(rows)
+    trackers = [PraatACTracker(24000, 300), WorldDioTracker(24000, 300)]
+    plans = [tr.plan(lengths) for tr in trackers]
+    assert plans[0]["meta"].shape[1] != plans[1]["meta"].shape[1]
+    got = []
+    for tr, pl in zip(trackers, plans):
+        meta_d = torch.from_numpy(pl["meta"]).cuda()
+        stats = torch.full((len(lengths), 2), float("nan"), dtype=torch.float32, device="cuda")
+        tr._row_stats(flat, meta_d, len(lengths), stats, _lib.stream_ptr(), 0)
+        got.append(stats.cpu().numpy())
+    assert np.array_equal(got[0].view(np.uint32), got[1].view(np.uint32))
+    for r, x in enumerate(rows):
+        mean, peak = _stats_in_kernel_order(x)
+        print(f"[row_stats] row {r}: n {x.size} mean {got[0][r, 0]!r} (numpy {mean!r}) peak {got[0][r, 1]!r} "
+              f"(numpy {peak!r})")
+        assert got[0][r, 0] == mean and got[0][r, 1] == peak
