@@ -8,7 +8,7 @@
 //       pixels split across workgroups, per-split slabs reduced in a fixed order -> deterministic);
 //   first layer (Cin = 1, model.py:24): 9 FMAs per output, HBM-bound on the 64-channel write.
 #include <type_traits>
-#include "forms.h"
+#include "splitk.h"
 
 namespace {
 using namespace pe;
@@ -460,12 +460,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(const float* __restr
   al.init(m0, kb);
   bl.init(n0, kb);
   f32x16 acc[BM / 64][BN / 64];
-#pragma unroll
-  for (int i = 0; i < BM / 64; ++i)
-#pragma unroll
-    for (int j = 0; j < BN / 64; ++j)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
+  tn_zero_acc<BM, BN>(acc);
   tn_mainloop<BM, BN>(al, bl, kb, ke, As, Bs, acc);
   // slab layout: [split][tap][Cout][Cin]
   float* dst = ws + ((long)split * 9 + tap) * Cout * Cin;
@@ -494,13 +489,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_kernel(const float* __r
   __shared__ float Mk[3 * 34 * 4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1, r = lane & 31, h = lane >> 5;
-  // 1-D grid over (split, tile), XCD-contiguous (as gemm_tn_kernel): the tiles of a pixel range share an XCD's L2
-  const int tiles_mn = (Cout / 64) * tiles_n;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile_id = lin % tiles_mn, split_id = lin / tiles_mn;
-  const int m0 = (tile_id / tiles_n) * 64, n0 = (tile_id % tiles_n) * 64;
-  const int kb = split_id * k_per_split;
-  const int ke = min(P, kb + k_per_split);
+  const SplitKBlock blk = splitk_block<64, 64>(Cout / 64, tiles_n, P, k_per_split);
+  const int m0 = blk.m0, n0 = blk.n0, kb = blk.kb, ke = blk.ke, split_id = blk.split_id;
 
   f32x16 acc[9];
 #pragma unroll
@@ -614,13 +604,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1, r = lane & 31, h = lane >> 5;
   const int g1 = (lane >> 4) & 1, q4 = (lane & 15) >> 2, p4 = (lane & 3) * 4;
-  // 1-D grid over (split, tile), XCD-contiguous (as gemm_tn_kernel): the tiles of a pixel range share an XCD's L2
-  const int tiles_mn = (Cout / 64) * tiles_n;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile_id = lin % tiles_mn, split_id = lin / tiles_mn;
-  const int m0 = (tile_id / tiles_n) * 64, n0 = (tile_id % tiles_n) * 64;
-  const int kb = split_id * k_per_split;
-  const int ke = min(P, kb + k_per_split);
+  const SplitKBlock blk = splitk_block<64, 64>(Cout / 64, tiles_n, P, k_per_split);
+  const int m0 = blk.m0, n0 = blk.n0, kb = blk.kb, ke = blk.ke, split_id = blk.split_id;
   const int XW = HALO ? 2 * F + 34 : 102;                  // X rows staged per k-tile
   const int WS = HALO ? F : 34;                            // row distance of the dt windows
 
@@ -764,48 +749,39 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3_kernel(const TA* __r
 // X staged as one halo (2F + 34 rows, XR = 80) when it fits, else as three 34-row windows
 static inline bool wgrad9_halo(int F) { return 2 * F + 34 <= 80; }
 
-// sum slabs in split order and scatter to OIHW: dw[(co*Cin + ci)*9 + tap]
-__global__ void conv3x3_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int splits,
-                                            int Cout, int Cin) {
-  const int i4 = blockIdx.x * blockDim.x + threadIdx.x;        // float4 index over [tap][co][ci] (Cin % 4 == 0)
-  const int n = 9 * Cout * Cin;
-  if (i4 * 4 >= n) return;
-  const float4 s = pe_ordered_slab_sum4(ws, n, splits, i4);
-  const int idx = i4 * 4;
-  const int ci = idx % Cin, co = (idx / Cin) % Cout, tap = idx / (Cin * Cout);
-  float* d = dw + ((long)co * Cin + ci) * 9 + tap;
-  d[0] = s.x; d[9] = s.y; d[18] = s.z; d[27] = s.w;
-}
+// reduce destination: the summed [tap][co][ci] slab scattered to OIHW, dw[(co*Cin + ci)*9 + tap]
+struct OihwDst {
+  float* dw;
+  int Cout, Cin;
+  __host__ __device__ long elems() const { return 9L * Cout * Cin; }
+  __device__ __forceinline__ void operator()(long i4, const float4& s) const {   // Cin % 4 == 0: one tap, one co
+    const int idx = (int)i4 * 4;
+    const int ci = idx % Cin, co = (idx / Cin) % Cout, tap = idx / (Cin * Cout);
+    float* d = dw + ((long)co * Cin + ci) * 9 + tap;
+    d[0] = s.x; d[9] = s.y; d[18] = s.z; d[27] = s.w;
+  }
+};
 
 bool wgrad9_ok(int Cout, int Cin) { return (Cout % 64) == 0 && (Cin % 64) == 0; }
 
-void wgrad_plan(int P, int Cout, int Cin, int* bm, int* bn, int* splits, int* kps) {
+struct WgradPlan { int bm, bn; SplitK k; };
+
+WgradPlan wgrad_plan(int P, int Cout, int Cin) {
   const bool nine = wgrad9_ok(Cout, Cin);
-  *bm = (nine || Cout <= 64) ? 64 : 128;
-  *bn = (nine || Cin <= 64) ? 64 : 128;
-  const int tiles = pe_cdiv(Cout, *bm) * pe_cdiv(Cin, *bn) * (nine ? 1 : 9);
-  const int s = pe_pick_splits(tiles, P, 1024, nine ? 512 : 768);   // resident: 2 (9-tap) or 3 workgroups per CU
-  int k = pe_cdiv(P, s);
-  k = (k + kBK - 1) / kBK * kBK;
-  *kps = k;
-  *splits = pe_cdiv(P, k);
+  const int bm = (nine || Cout <= 64) ? 64 : 128, bn = (nine || Cin <= 64) ? 64 : 128;
+  const int tiles = pe_cdiv(Cout, bm) * pe_cdiv(Cin, bn) * (nine ? 1 : 9);
+  // at least 1024 pixels per split; resident: 2 (9-tap) or 3 workgroups per CU
+  return {bm, bn, splitk_plan(tiles, P, 1024, resident_wgs(nine ? 2 : 3))};
 }
 
 template <int BM, int BN>
-int launch_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int T, int F, int Cin, int Cout,
-                 int splits, int kps, hipStream_t st) {
-  const int P = B * T * F;
+void launch_wgrad(const float* x, const float* dy, float* ws, int T, int F, int Cin, int Cout, int P, SplitK k,
+                 hipStream_t st) {
   const int tm = pe_cdiv(Cout, BM), tn = pe_cdiv(Cin, BN);
-  const int n_tiles = tm * tn, n_chunks = n_tiles * splits;
+  const int n_tiles = tm * tn, n_chunks = n_tiles * k.splits;
   const int grid = 8 * 9 * pe_cdiv(n_chunks, 8);
-  hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN>), dim3(grid), dim3(256), 0, st, dy, x, ws, T, F, Cin, Cout, P, kps,
+  hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN>), dim3(grid), dim3(256), 0, st, dy, x, ws, T, F, Cin, Cout, P, k.kps,
                      tn, n_tiles, n_chunks);
-  PE_LAUNCH_CHECK();
-  const int n = 9 * Cout * Cin;
-  hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(pe_cdiv(n / 4, 256)), dim3(256), 0, st, ws, dw, splits, Cout,
-                     Cin);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
 }
 
 // ---------------------------------------------------------------- first layer, Cin = 1 -> Cout = 64
@@ -1061,9 +1037,7 @@ extern "C" int pe_conv3x3_fwd_wf(int products, int act16, const void* x, const v
 
 extern "C" size_t pe_conv3x3_wgrad_workspace_bytes(int B, int T, int F, int Cin, int Cout) {
   if (Cin == 1) return (size_t)kC1WgradBlocks * 576 * sizeof(float);
-  int bm, bn, splits, kps;
-  wgrad_plan(B * T * F, Cout, Cin, &bm, &bn, &splits, &kps);
-  return (size_t)splits * 9 * Cout * Cin * sizeof(float);
+  return (size_t)wgrad_plan(B * T * F, Cout, Cin).k.splits * 9 * Cout * Cin * sizeof(float);
 }
 
 template <class FM, class TA = typename FM::TA>
@@ -1076,40 +1050,33 @@ static int conv3x3_wgrad_impl(const TA* x, const TA* dy, float* dw_oihw, int B, 
   if (MODE == kSplit2 && (!amax_x || !amax_dy)) return PE_E_ARG;
   if ((Cin & 3) || (Cout & 3)) return PE_E_UNSUPPORTED;
   if (!workspace || workspace_bytes < pe_conv3x3_wgrad_workspace_bytes(B, T, F, Cin, Cout)) return PE_E_WORKSPACE;
-  int bm, bn, splits, kps;
-  wgrad_plan(B * T * F, Cout, Cin, &bm, &bn, &splits, &kps);
+  const int P = B * T * F;
+  const WgradPlan pl = wgrad_plan(P, Cout, Cin);
+  const SplitK k = pl.k;
   hipStream_t st = pe_stream(stream);
   if (wgrad9_ok(Cout, Cin)) {
-    const int P = B * T * F, tn = Cin / 64;
-    const dim3 grid((Cout / 64) * tn * splits);
-    const bool halo = wgrad9_halo(F);
-    if (MODE == kSplit)
-      hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<3, true, TA> : conv3x3_wgrad9_x3_kernel<3, false, TA>), grid,
-                         dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
-    else if (MODE == kSplit2)
-      hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<2, true, TA> : conv3x3_wgrad9_x3_kernel<2, false, TA>), grid,
-                         dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
-    else if (MODE == kBf16)
-      hipLaunchKernelGGL((halo ? conv3x3_wgrad9_x3_kernel<1, true, TA, TH> : conv3x3_wgrad9_x3_kernel<1, false, TA, TH>),
-                         grid, dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, kps, tn, amax_dy, amax_x);
-    else if constexpr (std::is_same<TA, float>::value)
-      hipLaunchKernelGGL(conv3x3_wgrad9_kernel<0>, dim3((Cout / 64) * tn * splits), dim3(256), 0, st, dy, x,
-                         workspace, T, F, Cin, Cout, P, kps, tn);
-    PE_LAUNCH_CHECK();
-    const int n = 9 * Cout * Cin;
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(pe_cdiv(n / 4, 256)), dim3(256), 0, st, workspace, dw_oihw,
-                       splits, Cout, Cin);
-    PE_LAUNCH_CHECK();
-    return PE_OK;
+    const int tn = Cin / 64;
+    const dim3 grid((Cout / 64) * tn * k.splits);
+    if constexpr (MODE != kNative) {
+      constexpr int NT = mode_terms<MODE>();
+      hipLaunchKernelGGL((wgrad9_halo(F) ? conv3x3_wgrad9_x3_kernel<NT, true, TA, TH>
+                                         : conv3x3_wgrad9_x3_kernel<NT, false, TA, TH>),
+                         grid, dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, k.kps, tn, amax_dy, amax_x);
+    } else {
+      hipLaunchKernelGGL(conv3x3_wgrad9_kernel<0>, grid, dim3(256), 0, st, dy, x, workspace, T, F, Cin, Cout, P, k.kps,
+                         tn);
+    }
+  } else if constexpr (std::is_same<TA, float>::value) {
+    // channel counts that are not multiples of 64: per-tap kernels on the native fp32 MFMA in every mode (fp32 tensors)
+    if (pl.bm == 64 && pl.bn == 64) launch_wgrad<64, 64>(x, dy, workspace, T, F, Cin, Cout, P, k, st);
+    else if (pl.bm == 64) launch_wgrad<64, 128>(x, dy, workspace, T, F, Cin, Cout, P, k, st);
+    else if (pl.bn == 64) launch_wgrad<128, 64>(x, dy, workspace, T, F, Cin, Cout, P, k, st);
+    else launch_wgrad<128, 128>(x, dy, workspace, T, F, Cin, Cout, P, k, st);
+  } else {
+    return PE_E_UNSUPPORTED;
   }
-  // channel counts that are not multiples of 64: per-tap kernels on the native fp32 MFMA in every mode (fp32 tensors)
-  if constexpr (std::is_same<TA, float>::value) {
-    if (bm == 64 && bn == 64) return launch_wgrad<64, 64>(x, dy, dw_oihw, workspace, B, T, F, Cin, Cout, splits, kps, st);
-    if (bm == 64) return launch_wgrad<64, 128>(x, dy, dw_oihw, workspace, B, T, F, Cin, Cout, splits, kps, st);
-    if (bn == 64) return launch_wgrad<128, 64>(x, dy, dw_oihw, workspace, B, T, F, Cin, Cout, splits, kps, st);
-    return launch_wgrad<128, 128>(x, dy, dw_oihw, workspace, B, T, F, Cin, Cout, splits, kps, st);
-  }
-  return PE_E_UNSUPPORTED;
+  PE_LAUNCH_CHECK();
+  return launch_splitk_reduce(workspace, k.splits, OihwDst{dw_oihw, Cout, Cin}, st);
 }
 
 extern "C" int pe_conv3x3_wgrad(int products, int act16, const void* x, const void* dy, float* dw_oihw, int B, int T, int F,

@@ -8,7 +8,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
-#include "forms.h"
+#include "splitk.h"
 
 
 namespace {
@@ -201,98 +201,6 @@ int launch_nt(const RowLoaderT<TA>& al, const RowLoader& bl, const StoreEpiT<TA>
   return PE_OK;
 }
 
-// ---- TN with split-K
-template <int BM, int BN, int MODE, class TA = float, class TH = __bf16>
-__global__ __launch_bounds__(256) void gemm_tn_kernel(KRowLoader<BM, TA> al, KRowLoader<BN, TA> bl, float* out,
-                                                      long ldo, long split_stride, int M, int N, int K,
-                                                      int k_per_split, int tiles_n, int accumulate,
-                                                      const unsigned* amax_a, const unsigned* amax_b) {
-  __shared__ __attribute__((aligned(16))) float As[tn_lds_floats<MODE, BM>()];
-  __shared__ __attribute__((aligned(16))) float Bs[tn_lds_floats<MODE, BN>()];
-  // 1-D grid over (split, tile) with every XCD taking a CONTIGUOUS run of it: the tiles of one k-split then share
-  // an XCD's L2 for the operand rows they all read (PMC: 2.3 GB of fabric reads per dW_ih launch, 5x the operands,
-  // with the (tile, split) grid whose consecutive workgroups go round-robin over the eight XCDs)
-  const int tiles_mn = ((M + BM - 1) / BM) * tiles_n;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);                // grid = tiles_mn * splits workgroups
-  const int tile_id = lin % tiles_mn, split_id = lin / tiles_mn;
-  const int m0 = (tile_id / tiles_n) * BM, n0 = (tile_id % tiles_n) * BN;
-  const int kb = split_id * k_per_split;
-  const int ke = min(K, kb + k_per_split);
-  al.init(m0, kb);
-  bl.init(n0, kb);
-  f32x16 acc[BM / 64][BN / 64];
-#pragma unroll
-  for (int i = 0; i < BM / 64; ++i)
-#pragma unroll
-    for (int j = 0; j < BN / 64; ++j)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
-  H2Scales hs{1.f, 1.f, 1.f};
-  if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
-  tn_mainloop_mode<MODE, BM, BN, 1, TH>(al, bl, kb, ke, As, Bs, acc, hs.sa, hs.sb);
-  float* dst = out + (long)split_id * split_stride;
-  tn_for_each_acc<BM, BN>(acc, [&](int r, int c, float v) {
-    const int row = m0 + r, col = n0 + c;
-    if constexpr (MODE == kSplit2) v = hs.unscale(v);
-    if (row < M && col < N) {
-      float* d = dst + (long)row * ldo + col;
-      if (accumulate) v += *d;
-      *d = v;
-    }
-  });
-}
-
-__global__ void splitk_reduce_kernel(const float* ws, long split_stride, int splits, float* C, long ldc,
-                                     int M, int N, int accumulate) {   // N % 4 == 0: a float4 stays inside one row
-  const long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i4 * 4 >= (long)M * N) return;
-  const float4 s = pe_ordered_slab_sum4(ws, split_stride, splits, i4);
-  const long idx = i4 * 4;
-  const int row = (int)(idx / N), col = (int)(idx - (long)row * N);
-  float* d = C + (long)row * ldc + col;                          // C may be an unaligned view: scalar stores
-  if (accumulate) { d[0] += s.x; d[1] += s.y; d[2] += s.z; d[3] += s.w; }
-  else { d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = s.w; }
-}
-
-void tn_plan(int M, int N, int K, int bm, int bn, int mode, int* splits, int* k_per_split) {
-  const int tiles = pe_cdiv(M, bm) * pe_cdiv(N, bn);
-  // resident workgroups: 3 per CU (native), 2 per CU when the three-term images fill the LDS
-  const int s = pe_pick_splits(tiles, K, 512, (mode == kSplit || mode == kSplit2) ? 512 : 768);   // (bf16: LDS is small, 768 too)
-  int kps = pe_cdiv(K, s);
-  kps = (kps + kBK - 1) / kBK * kBK;
-  *splits = pe_cdiv(K, kps);
-  *k_per_split = kps;
-}
-
-template <int BM, int BN, class F, class TA = typename F::TA>
-int launch_tn(const TA* A, long lda, const TA* B, long ldb, float* C, long ldc, int M, int N, int K,
-              int accumulate, float* ws, size_t ws_bytes, hipStream_t st, const unsigned* amax_a,
-              const unsigned* amax_b) {
-  constexpr int MODE = F::MODE;
-  using TH = typename F::TH;
-  int splits, kps;
-  tn_plan(M, N, K, BM, BN, MODE, &splits, &kps);
-  KRowLoader<BM, TA> al{A, lda, M, 0};
-  KRowLoader<BN, TA> bl{B, ldb, N, 0};
-  const int tm = pe_cdiv(M, BM), tn = pe_cdiv(N, BN);
-  if (splits == 1) {
-    hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, MODE, TA, TH>), dim3(tm * tn, 1), dim3(256), 0, st, al, bl, C, ldc, 0L, M, N,
-                       K, kps, tn, accumulate, amax_a, amax_b);
-    PE_LAUNCH_CHECK();
-    return PE_OK;
-  }
-  const size_t need = (size_t)splits * M * N * sizeof(float);
-  if (!ws || ws_bytes < need) return PE_E_WORKSPACE;
-  hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, MODE, TA, TH>), dim3(tm * tn * splits), dim3(256), 0, st, al, bl, ws, (long)N,
-                     (long)M * N, M, N, K, kps, tn, 0, amax_a, amax_b);
-  PE_LAUNCH_CHECK();
-  const long total = (long)M * N;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(pe_cdiv(total / 4, 256)), dim3(256), 0, st, ws, (long)M * N, splits,
-                     C, ldc, M, N, accumulate);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
-}
-
 }  // namespace
 
 template <class F, class TA = typename F::TA>
@@ -331,14 +239,8 @@ extern "C" int pe_gemm_nt(int products, int act16, const void* A, long lda, cons
 
 extern "C" size_t pe_gemm_tn_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  size_t need = 0;
-  for (int mode : {kNative, kSplit}) {                   // one size serves every form of pe_gemm_tn (bf16 plans like native)
-    int splits, kps;
-    tn_plan(M, N, K, M <= 64 ? 64 : 128, N <= 64 ? 64 : 128, mode, &splits, &kps);
-    const size_t b = splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
-    need = b > need ? b : need;
-  }
-  return need;
+  const int s = tn_max_splits(pe_cdiv(M, M <= 64 ? 64 : 128) * pe_cdiv(N, N <= 64 ? 64 : 128), K);
+  return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;            // one split stores to C directly
 }
 
 template <class F, class TA = typename F::TA>
@@ -354,17 +256,17 @@ static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, 
     return PE_E_UNSUPPORTED;
   if (lda < 0 || ldb < 0 || lda >= (1L << 24) || ldb >= (1L << 24)) return PE_E_UNSUPPORTED;   // 32-bit offsets per k-tile
   hipStream_t st = pe_stream(stream);
-  if (M <= 64 && N <= 64)
-    return launch_tn<64, 64, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                amax_b);
-  if (M <= 64)
-    return launch_tn<64, 128, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                 amax_b);
-  if (N <= 64)
-    return launch_tn<128, 64, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                 amax_b);
-  return launch_tn<128, 128, F>(A, lda, B, ldb, C, ldc, M, N, K, accumulate, workspace, workspace_bytes, st, amax_a,
-                                amax_b);
+  auto launch = [&](auto bm, auto bn) {
+    constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+    return launch_tn<BM, BN, F>(KRowLoader<BM, TA>{A, lda, M, 0}, KRowLoader<BN, TA>{B, ldb, N, 0}, C, ldc, M, N, K,
+                                accumulate, workspace, workspace_bytes, st, amax_a, amax_b);
+  };
+  std::integral_constant<int, 64> t64;
+  std::integral_constant<int, 128> t128;
+  if (M <= 64 && N <= 64) return launch(t64, t64);
+  if (M <= 64) return launch(t64, t128);
+  if (N <= 64) return launch(t128, t64);
+  return launch(t128, t128);
 }
 
 extern "C" int pe_gemm_tn(int products, int act16, const void* A, long lda, const void* B, long ldb, float* C, long ldc,

@@ -886,6 +886,16 @@ __device__ __forceinline__ void nn_mainloop_64(AL& al, BL& bl, int K, float* As,
   }
 }
 
+template <int BM, int BN>
+__device__ __forceinline__ void tn_zero_acc(f32x16 (&acc)[BM / 64][BN / 64]) {
+#pragma unroll
+  for (int i = 0; i < BM / 64; ++i)
+#pragma unroll
+    for (int j = 0; j < BN / 64; ++j)
+#pragma unroll
+      for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
+}
+
 // Visit the accumulators of a TN tile: fn(row_in_tile, col_in_tile, value).
 template <int BM, int BN, class FN>
 __device__ __forceinline__ void tn_for_each_acc(const f32x16 (&acc)[BM / 64][BN / 64], FN&& fn) {

@@ -13,7 +13,7 @@
 //   backward step: dh_t = dY_t + dgates_{t+1}.W_hh  (K = 4H, split 4 ways over the waves of the
 //                  workgroup and reduced in LDS), then the gate derivatives overwrite the
 //                  activations in place, leaving dgates for the batched weight-gradient GEMMs.
-#include "forms.h"
+#include "splitk.h"
 
 namespace {
 using namespace pe;
@@ -192,59 +192,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const BwdCells cells
   }
 }
 
-// ------------------------------------------------------------------ dW_hh = sum_t dgates_t^T h_{t-1}
-template <int BM, int BN, int MODE, class TH = __bf16>
-__global__ __launch_bounds__(256) void lstm_whh_grad_kernel(KRowLoader<BM> al, ShiftedTimeLoader<BN> bl, float* out,
-                                                            long ldo, long split_stride, int M, int N, int K,
-                                                            int k_per_split, int tiles_n, const unsigned* amax_a,
-                                                            const unsigned* amax_b) {
-  __shared__ __attribute__((aligned(16))) float As[tn_lds_floats<MODE, BM>()];
-  __shared__ __attribute__((aligned(16))) float Bs[tn_lds_floats<MODE, BN>()];
-  // 1-D grid over (split, tile) with every XCD taking a CONTIGUOUS run of it: the tiles of one k-split then share
-  // an XCD's L2 for the operand rows they all read (PMC: 2.3 GB of fabric reads per dW_ih launch, 5x the operands,
-  // with the (tile, split) grid whose consecutive workgroups go round-robin over the eight XCDs)
-  const int tiles_mn = ((M + BM - 1) / BM) * tiles_n;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);                // grid = tiles_mn * splits workgroups
-  const int tile_id = lin % tiles_mn, split_id = lin / tiles_mn;
-  const int m0 = (tile_id / tiles_n) * BM, n0 = (tile_id % tiles_n) * BN;
-  const int kb = split_id * k_per_split;
-  const int ke = min(K, kb + k_per_split);
-  al.init(m0, kb);
-  bl.init(n0, kb);
-  f32x16 acc[BM / 64][BN / 64];
-#pragma unroll
-  for (int i = 0; i < BM / 64; ++i)
-#pragma unroll
-    for (int j = 0; j < BN / 64; ++j)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
-  H2Scales hs{1.f, 1.f, 1.f};
-  if constexpr (MODE == kSplit2) hs.load(amax_a, amax_b);
-  tn_mainloop_mode<MODE, BM, BN, 1, TH>(al, bl, kb, ke, As, Bs, acc, hs.sa, hs.sb);
-  float* dst = out + (long)split_id * split_stride;
-  tn_for_each_acc<BM, BN>(acc, [&](int r, int c, float v) {
-    const int row = m0 + r, col = n0 + c;
-    if (row < M && col < N) dst[(long)row * ldo + col] = MODE == kSplit2 ? hs.unscale(v) : v;
-  });
-}
-
-__global__ void slab_reduce_kernel(const float* ws, long n, int splits, float* out) {   // n % 4 == 0
-  const long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i4 * 4 >= n) return;
-  const float4 s = pe_ordered_slab_sum4(ws, n, splits, i4);
-  float* d = out + 4 * i4;                             // `out` may be an unaligned view of the flat gradient buffer
-  d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = s.w;
-}
-
-void whh_plan(int M, int N, int K, int mode, int* splits, int* kps) {
-  const int tiles = pe_cdiv(M, 128) * pe_cdiv(N, 128);
-  const int s = pe_pick_splits(tiles, K, 512, (mode == kSplit || mode == kSplit2) ? 512 : 768);
-  int k = pe_cdiv(K, s);
-  k = (k + kBK - 1) / kBK * kBK;
-  *kps = k;
-  *splits = pe_cdiv(K, k);
-}
-
 // ------------------------------------------------------------------ column sums (bias gradients)
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ x, long rows, int cols,
                                                              long ld, double* __restrict__ partial) {
@@ -335,43 +282,26 @@ extern "C" int pe_lstm_bwd(int ncells, const float* const* whh_t, float* const* 
   return PE_OK;
 }
 
+// dW_hh[4H][H] = sum_{b,t} dgates[b][t][:]^T . y[b][t -/+ 1][:]   (y = this direction's output slice): the TN split-K
+// product (splitk.h) with y behind a time-shifted loader, on the 128 x 128 tile at every H.
 extern "C" size_t pe_lstm_whh_grad_workspace_bytes(int B, int T, int H) {
-  size_t need = 0;
-  for (int mode : {kNative, kSplit}) {
-    int splits, kps;
-    whh_plan(4 * H, H, B * T, mode, &splits, &kps);
-    const size_t b = (size_t)splits * 4 * H * H * sizeof(float);
-    need = b > need ? b : need;
-  }
-  return need;
+  // (a whole slab also where every form plans one split and stores to dW_hh directly)
+  return (size_t)tn_max_splits(pe_cdiv(4 * H, 128) * pe_cdiv(H, 128), B * T) * 4 * H * H * sizeof(float);
 }
 
-// dW_hh[4H][H] = sum_{b,t} dgates[b][t][:]^T . y[b][t -/+ 1][:]   (y = this direction's output slice)
 template <class F>
 static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* dwhh, int B, int T, int H,
                          int reverse, float* workspace, size_t workspace_bytes, void* stream,
                          const unsigned* amax_dg, const unsigned* amax_y) {
-  constexpr int MODE = F::MODE;
   if (!dgates || !y || !dwhh || B <= 0 || T <= 0 || H <= 0) return PE_E_ARG;
-  if (MODE == kSplit2 && (!amax_dg || !amax_y)) return PE_E_ARG;
+  if (F::MODE == kSplit2 && (!amax_dg || !amax_y)) return PE_E_ARG;
   if ((H & 3) || (ldy & 3)) return PE_E_UNSUPPORTED;
-  const int M = 4 * H, N = H, K = B * T;
-  int splits, kps;
-  whh_plan(M, N, K, MODE, &splits, &kps);
-  const size_t need = (size_t)splits * M * N * sizeof(float);
-  if (!workspace || workspace_bytes < need) return PE_E_WORKSPACE;
+  const int M = 4 * H, N = H;
   KRowLoader<128> al{dgates, (long)M, M, 0};
   ShiftedTimeLoader<128> bl;
   bl.p = y; bl.ld = ldy; bl.T = T; bl.dt = reverse ? 1 : -1; bl.cols = N; bl.col0 = 0;
-  const int tm = pe_cdiv(M, 128), tn = pe_cdiv(N, 128);
-  hipStream_t st = pe_stream(stream);
-  hipLaunchKernelGGL((lstm_whh_grad_kernel<128, 128, MODE, typename F::TH>), dim3(tm * tn * splits), dim3(256), 0, st,
-                     al, bl, workspace, (long)N, (long)M * N, M, N, K, kps, tn, amax_dg, amax_y);
-  PE_LAUNCH_CHECK();
-  const long n = (long)M * N;
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(pe_cdiv(n / 4, 256)), dim3(256), 0, st, workspace, n, splits, dwhh);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  return launch_tn<128, 128, F>(al, bl, dwhh, (long)N, M, N, B * T, 0, workspace, workspace_bytes, pe_stream(stream),
+                                amax_dg, amax_y);
 }
 
 extern "C" int pe_lstm_whh_grad(int products, const float* dgates, const float* y, long ldy, float* dwhh, int B, int T,

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from pitchextractor_amd import _lib, ops
 from tests import half_ref as R
+from tests.plan_ref import tn_tile_and_splits
 from tests.test_ops_gpu import close, nchw, nhwc, rnd
 
 pytestmark = pytest.mark.gpu
@@ -85,27 +86,6 @@ def test_gemm_nt_half_strided_rows(hip_device, half):
 
 
 # ------------------------------------------------------------------ GEMM TN
-def _pick_splits(tiles, K, min_k, resident):          # common.h pe_pick_splits
-    max_s = min(max(K // min_k, 1), 1024)
-    best, best_score = 1, -1.0
-    for sp in range(1, max_s + 1):
-        wgs = tiles * sp
-        waves = (wgs + resident - 1) // resident
-        score = wgs / (waves * resident) - 0.0001 * sp + (0.05 if wgs >= 2 * resident else 0.0)
-        if score > best_score:
-            best, best_score = sp, score
-    return best
-
-
-def tn_tile_and_splits(M, N, K):
-    """(BM, BN) and k-splits gemm_tn_impl / tn_plan choose for a 16-bit operand product"""
-    bm, bn = (64, 64) if M <= 64 and N <= 64 else (64, 128) if M <= 64 else (128, 64) if N <= 64 else (128, 128)
-    s = _pick_splits(-(-M // bm) * -(-N // bn), K, 512, 768)
-    kps = -(-K // s)
-    kps = -(-kps // 32) * 32
-    return (bm, bn), -(-K // kps)
-
-
 TN_SHAPES = [   # (K, M, N): tile, splits
     (5000, 64, 64),      # 64x64, split
     (3001, 192, 128),    # 128x128, split, K ragged

@@ -13,6 +13,7 @@ import torch
 from pitchextractor_amd import ops
 from tests import half_ref as R
 from tests import split_ref as S
+from tests.plan_ref import wgrad_tile_and_splits
 from tests.test_ops_gpu import close, nhwc, rnd
 from tests.test_split_products_gpu import ACC_EXTRA, acc_tol, check, model
 
@@ -24,8 +25,8 @@ BORDER_SHAPES = [(41, 5, 10, 64, 64), (103, 1, 20, 64, 128), (37, 3, 20, 128, 64
 
 
 def _splits(P):
-    """k-splits of wgrad_plan for a single 64 x 64 tile (csrc/conv.hip, common.h pe_pick_splits)"""
-    return max(1, min(P // 1024, 1024))
+    """k-splits of wgrad_plan for a single 64 x 64 tile (csrc/conv.hip)"""
+    return wgrad_tile_and_splits(P, 64, 64)[1]
 
 
 def test_border_shapes_are_border_heavy():
