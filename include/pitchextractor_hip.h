@@ -578,6 +578,63 @@ int pe_f0_stonemask(const float* x, const long* meta, const long* host_meta, con
                     const float* roots, long n_roots, int n_rows, int sr, int hop, double f0_min,
                     float* f0_out, void* stream);
 
+/* ---- Robustness stress conditions (reference Utils/room_and_microphone_stress.ipynb, amplitude_pathologies.ipynb)
+ * and the notebooks' melody metrics, ragged batches ------------------------------------------------------------------
+ * pe_stress_plan (host only): row r has n[r] samples at x + x_off[r] and is written to y + y_off[r].  consts4 =
+ * {block step S = 2048, table floats, samples per biquad / AGC piece, samples per histogram chunk}; meta (n_rows x
+ * pe_stress_plan_fields() int64, to be copied to the device) = per row {sample offset, samples, output offset, sample
+ * prefix, blocks = ceil(n / S), block prefix}; totals2 = {samples, blocks}.  Every entry point below checks its
+ * arguments and host_meta (the host copy of meta) before any device call: PE_E_ARG for a null pointer, a plan that is
+ * not pe_stress_plan's or a value out of range, PE_E_WORKSPACE for a workspace that is missing or too small.  Rows of
+ * length 0 are valid.  A row's output depends on the row alone, not on the batch or the layout around it.
+ *
+ * tables (device, consts4[1] floats): exp(-2 pi i m / C), m < C = 2048; exp(-2 pi i k / 2C), k <= C.
+ * pe_stress_spectra: spectra (blocks x C complex) of every block of every row, one launch.  partition = 0: block b is
+ * the real 2S-point transform of samples [(b - 1) S, (b + 1) S), zero outside the row; partition = 1: of samples
+ * [b S, (b + 1) S) followed by S zeros, divided by C (a filter's partitions).  Bin 0 holds {X[0], X[C]}.
+ * pe_stress_rir: y[n] = sum_k h[k] x[n - k] for n < len(x), h = RIR rir_index[r] of a set of n_rirs ragged RIRs (each
+ * of length >= 1) given by their plan (rir_meta on the device, host_rir_meta) and their partition spectra
+ * (pe_stress_spectra, partition = 1); then with p = max |y| of the row, y /= p + 1e-6 if p > 0.99 (float32).  Uniformly
+ * partitioned overlap-save, three launches.  workspace: pe_stress_rir_workspace_bytes(totals2[1]).  PE_E_ARG also for an
+ * index outside the set.
+ * pe_stress_biquad: a cascade of n_stages <= 8 biquads, coeffs (host) = per stage {b0, b1, b2, a1, a2} with a0 = 1:
+ * v[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 v[n-1] - a2 v[n-2] in double, the stage's output float32(v) clamped to
+ * [-1, 1] (the clamp is never fed back).  PE_E_UNSUPPORTED for a stage with a pole on or outside the unit circle.
+ * pe_stress_clip: copy != 0: y = x.  Else thr (thresholds[r], nullable) = numpy's linear quantile of |x| at q, in the
+ * float32 arithmetic numpy 2 uses for a float32 array and a Python float q; y = clip(x, -thr, thr), or x if thr <= 0.
+ * pe_stress_agc: params4 = {attack coefficient, release coefficient, target_rms, max_gain (< 256)}: the envelope
+ * follower in double, gain = float32(clip(target_rms / (env + 1e-6), 1 / max_gain, max_gain)), for smoothing > 1
+ * np.convolve(gain, ones / smoothing, "same") with exact window sums rounded once to float32, y = clip(float32(x gain),
+ * -1, 1).  PE_E_ARG also for a row shorter than smoothing > 1.  workspace: pe_stress_agc_workspace_bytes(totals2[0]).
+ *
+ * pe_melody_metrics (the notebooks' compute_metrics, in double): tracks (n_rows x pe_melody_metrics_fields() int64;
+ * host_tracks its host copy) = per row {offset in f0_pred, frames n, offset in f0_ref, offset in f0_base, frames
+ * compared with the baseline}.  out7[r] = {RPA, RCA, VUV accuracy, OctaveError, VUV_flips, voiced frames, frames}:
+ * voiced = f0_ref > 0, predicted voiced = f0_pred > voicing_threshold_hz, cents re 55 Hz with the prediction clipped
+ * below at 1e-5, a hit within 50 cents (RCA: on the circular distance), an octave error = a miss within 50 cents of a
+ * non-zero multiple of 1200 (round half even).  RPA, RCA and OctaveError are NaN when no frame is voiced; VUV_flips =
+ * share of frames whose voicing differs from f0_base's, NaN without a baseline (f0_base NULL) or frames to compare. */
+int pe_stress_plan_fields(void);
+int pe_stress_plan(int n_rows, const long* n, const long* x_off, const long* y_off, long* consts4, long* meta,
+                   long* totals2);
+size_t pe_stress_rir_workspace_bytes(long blocks);
+int pe_stress_spectra(const float* x, const long* meta, const long* host_meta, int n_rows, int partition,
+                      const float* tables, long n_table, float* spectra, void* stream);
+int pe_stress_rir(const float* x, const long* meta, const long* host_meta, int n_rows, const float* rir_spectra,
+                  const long* rir_meta, const long* host_rir_meta, int n_rirs, const int* rir_index,
+                  const int* host_rir_index, const float* tables, long n_table, float* y, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int pe_stress_biquad(const float* x, const long* meta, const long* host_meta, int n_rows, const double* coeffs,
+                     int n_stages, float* y, void* stream);
+int pe_stress_clip(const float* x, const long* meta, const long* host_meta, int n_rows, double q, int copy, float* y,
+                   float* thresholds, void* stream);
+size_t pe_stress_agc_workspace_bytes(long samples);
+int pe_stress_agc(const float* x, const long* meta, const long* host_meta, int n_rows, const double* params4,
+                  int smoothing, float* y, void* workspace, size_t workspace_bytes, void* stream);
+int pe_melody_metrics_fields(void);
+int pe_melody_metrics(const float* f0_pred, const float* f0_ref, const float* f0_base, const long* tracks,
+                      const long* host_tracks, int n_rows, double voicing_threshold_hz, double* out7, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

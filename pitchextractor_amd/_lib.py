@@ -146,6 +146,17 @@ PROTOTYPES = {
     "pe_f0_dio_candidates": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "pe_f0_dio_fix": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "pe_f0_stonemask": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, C.c_double, _p, _p]),
+    "pe_stress_plan_fields": (_i, []),
+    "pe_stress_plan": (_i, [_i, _p, _p, _p, _p, _p, _p]),
+    "pe_stress_rir_workspace_bytes": (_z, [_l]),
+    "pe_stress_spectra": (_i, [_p, _p, _p, _i, _i, _p, _l, _p, _p]),
+    "pe_stress_rir": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _l, _p, _p, _z, _p]),
+    "pe_stress_biquad": (_i, [_p, _p, _p, _i, _p, _i, _p, _p]),
+    "pe_stress_clip": (_i, [_p, _p, _p, _i, _d, _i, _p, _p, _p]),
+    "pe_stress_agc_workspace_bytes": (_z, [_l]),
+    "pe_stress_agc": (_i, [_p, _p, _p, _i, _p, _i, _p, _p, _z, _p]),
+    "pe_melody_metrics_fields": (_i, []),
+    "pe_melody_metrics": (_i, [_p, _p, _p, _p, _p, _i, _d, _p, _p]),
 }
 
 

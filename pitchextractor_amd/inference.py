@@ -182,3 +182,52 @@ def pitch_metrics(f0_pred, f0_ref, *, threshold_cents: float = 50.0, device="cud
     out = ops.pitch_metrics(pred, ref, threshold_cents).cpu().tolist()
     return dict(rms_cents=out[0], rpa=out[1], rca=out[2], vuv_error=out[3], n_voiced=int(out[4]),
                 n_frames=int(out[5]))
+
+
+def melody_metrics(pred, ref, baseline=None, voicing_threshold_hz: float = 10.0, device="cuda") -> dict:
+    """The evaluation notebooks' ``compute_metrics`` (e.g. Utils/room_and_microphone_stress.ipynb) of one predicted
+    track against its reference over their first ``min(len)`` frames, reduced on the device in double:
+    ``{RPA, RCA, VUV, OctaveError, VUV_flips, n_voiced, n_frames}``.  ``voiced = ref > 0``, predicted voiced =
+    ``pred > voicing_threshold_hz``; cents re 55 Hz with the prediction clipped below at 1e-5; RPA / RCA: share of
+    voiced frames within 50 cents (RCA: on the circular distance); VUV: share of frames whose voicing agrees;
+    OctaveError: share of voiced frames that miss but lie within 50 cents of a non-zero whole number of octaves.  The
+    three shares over voiced frames are NaN when none is voiced.  ``VUV_flips`` (Utils/amplitude_pathologies.ipynb):
+    share of frames whose predicted voicing differs from ``baseline``'s (the clean run's prediction); NaN without one."""
+    from .stress import melody_metrics_rows
+    return melody_metrics_rows([pred], [ref], None if baseline is None else [baseline], voicing_threshold_hz, device)[0]
+
+
+@torch.no_grad()
+def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voicing_threshold_hz: float = 10.0,
+                 **predict_kwargs) -> dict:
+    """The notebooks' sweep: ``items`` (a list of ``{"audio", "reference_f0"}`` at the model rate ``sr``, default the
+    mel front end's) are scored clean, then every ``stress.Condition`` degrades the whole set as one ragged batch on
+    the device and each degraded row goes through ``predict_f0`` (``predict_kwargs``: its keyword arguments; a
+    classifier needs a ``decoder``).  Returns ``{"baseline": [...], "conditions": [...]}``: one record per item, and
+    one per (condition, item) in order, each ``{"condition", "kind", "item"}`` plus ``melody_metrics``; a condition's
+    ``VUV_flips`` is measured against the item's clean prediction, the baseline's own is 0."""
+    from . import stress
+    device = model.flat_parameters.device
+    sr = int(sr or DEFAULT_MEL_PARAMS["sample_rate"])
+    waves = [np.ascontiguousarray(np.asarray(it["audio"], dtype=np.float32).reshape(-1)) for it in items]
+    refs = [np.asarray(it["reference_f0"], dtype=np.float32).reshape(-1) for it in items]
+    lengths = [int(w.size) for w in waves]
+    batch = torch.zeros((len(waves), max(lengths, default=0)), dtype=torch.float32, device=device)
+    for r, w in enumerate(waves):
+        batch[r, :w.size] = torch.from_numpy(w).to(device)
+
+    def run(rows, row_lengths):
+        return [np.asarray(predict_f0(model, rows[r, :n].cpu().numpy(), **predict_kwargs), dtype=np.float32)
+                for r, n in enumerate(row_lengths)]
+
+    def records(cond, preds):
+        ms = stress.melody_metrics_rows(preds, refs, clean, voicing_threshold_hz, device) if preds else []
+        return [dict(condition=cond.label if cond else "clean", kind=cond.kind if cond else "clean", item=i, **m)
+                for i, m in enumerate(ms)]
+
+    clean = run(batch, lengths)
+    out = {"baseline": records(None, clean), "conditions": []}
+    for cond in conditions:
+        degraded, row_lengths = stress.apply_condition(cond, batch, sr, lengths)
+        out["conditions"] += records(cond, run(degraded, row_lengths))
+    return out
