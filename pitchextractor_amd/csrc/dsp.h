@@ -1,7 +1,10 @@
-// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip) share.  Host: the row
-// bound and launch-grid clamp of the ragged entry points, the header every row plan opens with, and with_log2 (transform
-// size -> kernel instance).  Device: float2 complex arithmetic, the wave-private LDS fence, the in-place radix-4 Stockham
-// FFT in LDS, the split of a packed half-length transform into the real one's bins, and the row search of ragged plans.
+// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip, stress.hip) share.
+// Host: the row bound and the launch-grid clamps of the ragged entry points, the header every row plan opens with, the
+// gate every entry point that takes a host plan passes before its own checks (open_rows, kNothing, PE_OPEN), the size
+// of the transform roots every table opens with, and with_log2 (transform size -> kernel instance).  Device: float2
+// complex arithmetic, the wave-private LDS fence, the in-place radix-4 Stockham FFT in LDS, a packed half-length
+// transform's bins as the real one's and back (real_fft_split, real_fft_bin, real_fft_pack), the 256-thread workgroup
+// reductions in a fixed order, and the row search of ragged plans.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -10,12 +13,43 @@ namespace pe {
 
 constexpr int kMaxRows = 65535;           // rows of one ragged batch (a launch grid's y / x extent)
 constexpr float kPiF = 3.14159265358979323846f;
-// workgroups of a grid-stride launch over `items` work items
-inline unsigned grid_of(long items) { return (unsigned)(items < (1L << 20) ? items : (1L << 20)); }
+// workgroups of a grid-stride launch: one per `per_block` work items, `cap` at the most
+inline int grid_for(long work, int per_block, int cap) {
+  const long b = (work + per_block - 1) / per_block;
+  return (int)(b < cap ? b : cap);
+}
+inline unsigned grid_of(long items) { return (unsigned)grid_for(items, 1, 1 << 20); }
+// floats of the roots every LDS-FFT table opens with: C float2 of the packed C-point transform (fft_lds's `tw`), then
+// C + 1 float2 of its split into the real 2C-point one (`tr` of real_fft_bin)
+constexpr long fft_table_floats(long C) { return 2 * C + 2 * (C + 1); }
 
 // Every row plan (n_rows x K int64, K the plan's own field count) opens with the row's offset in `x` and its length in
 // samples.  A plan's enum static_asserts this; what reads only this header (pe_row_stats) serves any plan given its K.
 enum { kRowOffset = 0, kRowLength = 1, kRowHeader = 2 };
+
+// The gate of an entry point that takes a ragged plan's host copy, in this order: n_rows outside [0, kMaxRows] is
+// PE_E_ARG; `config` (the status of the plan's derive(sr, hop, config), PE_OK where there is none) is returned if it is
+// an error, a bad one with no rows included; no rows is kNothing; a null host_meta, or one that consistent() (the plan's
+// own walk over it, which also fills the totals) refuses, is PE_E_ARG; *work == 0 (the total a launch needs; null: none)
+// is kNothing; else PE_OK, and the entry point's own pointer and size checks follow.  That is the order of the answers,
+// not of evaluation: a caller's derive() has run, as an argument, before the range check, so it must be free of side
+// effects and safe on null.  An entry point with host checks of its own between the plan and the work total
+// (pe_stress_rir, pe_stress_agc) takes the status and answers kNothing itself after them.
+constexpr int kNothing = 1;               // valid, and nothing to launch: PE_OK to the caller
+template <class Consistent>
+int open_rows(int n_rows, int config, const long* host_meta, Consistent&& consistent, const long* work) {
+  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
+  if (config != PE_OK) return config;
+  if (n_rows == 0) return kNothing;
+  if (!host_meta || !consistent()) return PE_E_ARG;
+  return work && *work == 0 ? kNothing : PE_OK;
+}
+// leaves the entry point unless the gate says go
+#define PE_OPEN(gate)                                           \
+  do {                                                          \
+    const int pe_st_ = (gate);                                  \
+    if (pe_st_ != PE_OK) return pe_st_ == kNothing ? PE_OK : pe_st_; \
+  } while (0)
 
 // Calls fn(std::integral_constant<int, L>{}) for L == lg in [LO, HI] and returns its status; PE_E_UNSUPPORTED outside the
 // range (what with_form of forms.h is for product forms).  The one other fft_lds dispatch is stonemask_kernel's switch.
@@ -122,6 +156,48 @@ __device__ __forceinline__ void real_fft_split(float2 zk, float2 zc, float2& e, 
   e = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
   const float2 dd = csub(zk, zc);
   o = make_float2(0.5f * dd.y, -0.5f * dd.x);
+}
+
+// Bin k < C of the real transform from the packed one in `z`, in halves: e and o as real_fft_split gives them, and
+// the return value t = w o with w = tr[k] = exp(-2 pi i k / 2C).  X[k] = e + t and conj(X[C - k]) = e - t; at k = 0,
+// X[0] = e.x + o.x and X[C] = e.x - o.x, both real (or X[C] = e + t from k = 0 with w = tr[C]).  How the halves are put
+// together is the caller's.
+__device__ __forceinline__ float2 real_fft_bin(const float2* z, float2 w, int C, int k, float2& e, float2& o) {
+  real_fft_split(z[k], conj2(z[(C - k) & (C - 1)]), e, o);
+  return cmul(w, o);
+}
+
+// The way back: the packed transform's bin k, E + i O, from y1 = Y[k] and y2 = conj(Y[C - k]) of a real signal's
+// spectrum Y and w = tr[k]; the inverse C-point transform of these is the signal (times C).
+__device__ __forceinline__ float2 real_fft_pack(float2 y1, float2 y2, float2 w) {
+  const float2 ye = make_float2(0.5f * (y1.x + y2.x), 0.5f * (y1.y + y2.y));
+  const float2 yo = cmul(make_float2(0.5f * (y1.x - y2.x), 0.5f * (y1.y - y2.y)), conj2(w));
+  return make_float2(ye.x - yo.y, ye.y + yo.x);
+}
+
+// Reductions over a workgroup of 256 threads (four waves) in a fixed order; every thread gets the result.  s_red: 4
+// floats that nothing else uses; the barrier ahead of the store lets a loop call these again without one of its own.
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+__device__ __forceinline__ float block_sum(float v, float* s_red, int tid) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();
+  if ((tid & 63) == 0) s_red[tid >> 6] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+__device__ __forceinline__ float block_max(float v, float* s_red, int tid) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((tid & 63) == 0) s_red[tid >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
 }
 
 // Largest row whose prefix offset meta[row][field] <= g, in a plan of `fields` int64 per row (rows with no work share

@@ -104,7 +104,7 @@ int derive(int sr, int hop, const double* cfg, DioConsts* k) {
 
 long table_floats(const DioConsts& k) {       // twiddles (C float2), split roots (C + 1), bands x filter spectrum (C + 1)
   const long C = k.nfft / 2;
-  return 2 * C + 2 * (C + 1) + (long)k.bands * 2 * (C + 1);
+  return fft_table_floats(C) + (long)k.bands * 2 * (C + 1);
 }
 
 // roots of the 128 .. 4096-point transforms, back to back: the sum of 2 x 2^l floats over l
@@ -166,8 +166,7 @@ __global__ __launch_bounds__(kThreads) void dio_bands_kernel(const float* __rest
     for (int q = 0; q < NQ; ++q) {
       const int k = tid + kThreads * q;
       float2 o2;
-      real_fft_split(s_buf[k], conj2(s_buf[(C - k) & (C - 1)]), e[q], o2);
-      t[q] = cmul(tr[k], o2);
+      t[q] = real_fft_bin(s_buf, tr[k], C, k, e[q], o2);
     }
     __syncthreads();
     for (int b = 0; b < K.bands; ++b) {
@@ -177,9 +176,7 @@ __global__ __launch_bounds__(kThreads) void dio_bands_kernel(const float* __rest
         const int k = tid + kThreads * q;
         const float2 y1 = cmul(cadd(e[q], t[q]), G[k]);
         const float2 y2 = cmul(csub(e[q], t[q]), conj2(G[C - k]));
-        const float2 ye = make_float2(0.5f * (y1.x + y2.x), 0.5f * (y1.y + y2.y));
-        const float2 yo = cmul(make_float2(0.5f * (y1.x - y2.x), 0.5f * (y1.y - y2.y)), conj2(tr[k]));
-        s_buf[k] = make_float2(ye.x - yo.y, ye.y + yo.x);
+        s_buf[k] = real_fft_pack(y1, y2, tr[k]);
       }
       __syncthreads();
       fft_lds<LOG2C, true, kThreads>(s_buf, tw, tid);
@@ -560,19 +557,16 @@ __global__ __launch_bounds__(kThreads) void stonemask_kernel(const float* __rest
 // needs (-1: none) ----------------------------------------------------------------------------------------------------------
 struct DioBatch { DioConsts k; long tot[5]; };        // tot: the batch's totals by meta_ok, indexed by TOT_*
 enum { TOT_FRAMES, TOT_SAMPLES, TOT_BLOCKS, TOT_SLOTS, TOT_CHUNKS };
-constexpr int kNothing = 1;               // valid, and nothing to launch: PE_OK to the caller
 
-int open_rows(int n_rows, const long* host_meta, unsigned checks, int work, DioBatch* b) {
-  if (n_rows == 0) return kNothing;
-  if (!host_meta || !meta_ok(host_meta, n_rows, checks, b->k, b->tot)) return PE_E_ARG;
-  return work >= 0 && b->tot[work] == 0 ? kNothing : PE_OK;
+// `config`: derive's status for b->k (PE_OK where an entry point has no config and `checks` none of b->k)
+int open_batch(int n_rows, int config, const long* host_meta, unsigned checks, int work, DioBatch* b) {
+  return open_rows(n_rows, config, host_meta, [&] { return meta_ok(host_meta, n_rows, checks, b->k, b->tot); },
+                   work >= 0 ? &b->tot[work] : nullptr);
 }
 
 int open_batch(int n_rows, int sr, int hop, const double* config4, const long* host_meta, unsigned checks, int work,
                DioBatch* b) {
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config4, &b->k);
-  return st != PE_OK ? st : open_rows(n_rows, host_meta, checks, work, b);
+  return open_batch(n_rows, derive(sr, hop, config4, &b->k), host_meta, checks, work, b);
 }
 
 }  // namespace
@@ -617,8 +611,7 @@ extern "C" int pe_f0_dio_bands(const float* x, const long* meta, const long* hos
                                const float* tables, long n_table, int n_rows, int sr, int hop, const double* config4,
                                float* band_signals, void* stream) {
   DioBatch b;
-  const int st = open_batch(n_rows, sr, hop, config4, host_meta, kCheckBlocks, TOT_BLOCKS, &b);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, sr, hop, config4, host_meta, kCheckBlocks, TOT_BLOCKS, &b));
   if (!x || !meta || !stats || !tables || !band_signals) return PE_E_ARG;
   if (n_table != table_floats(b.k)) return PE_E_ARG;
   return with_log2<9, 12>(b.k.log2c, [&](auto L) {
@@ -634,8 +627,7 @@ extern "C" int pe_f0_dio_events(const float* band_signals, const long* meta, con
                                 int hop, const double* config4, int* e_idx, float* e_frac, int* e_count,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   DioBatch b;
-  const int st = open_batch(n_rows, sr, hop, config4, host_meta, 0, -1, &b);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, sr, hop, config4, host_meta, 0, -1, &b));
   if (!meta || !e_count) return PE_E_ARG;
   const long chunks = b.tot[TOT_CHUNKS], samples = b.tot[TOT_SAMPLES];
   const int bands = b.k.bands;
@@ -666,8 +658,7 @@ extern "C" int pe_f0_dio_candidates(const int* e_idx, const float* e_frac, const
                                     const long* host_meta, int n_rows, int sr, int hop, const double* config4,
                                     float* cand, float* score, float* best, int* best_band, void* stream) {
   DioBatch b;
-  const int st = open_batch(n_rows, sr, hop, config4, host_meta, kCheckFrames, TOT_FRAMES, &b);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, sr, hop, config4, host_meta, kCheckFrames, TOT_FRAMES, &b));
   if (!e_idx || !e_frac || !e_count || !meta || !cand || !score || !best || !best_band) return PE_E_ARG;
   const long frames = b.tot[TOT_FRAMES];
   hipLaunchKernelGGL(dio_candidates_kernel, dim3(grid_of(pe_cdiv(frames * b.k.bands, kThreads))), dim3(kThreads), 0,
@@ -682,8 +673,7 @@ extern "C" int pe_f0_dio_candidates(const int* e_idx, const float* e_frac, const
 extern "C" int pe_f0_dio_fix(const float* best, const float* cand, const long* meta, const long* host_meta, int n_rows,
                              int sr, int hop, const double* config4, float* steps4, void* stream) {
   DioBatch b;
-  const int st = open_batch(n_rows, sr, hop, config4, host_meta, 0, TOT_FRAMES, &b);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, sr, hop, config4, host_meta, 0, TOT_FRAMES, &b));
   if (!best || !cand || !meta || !steps4) return PE_E_ARG;
   hipLaunchKernelGGL(dio_fix_kernel, dim3(n_rows), dim3(64), 0, pe_stream(stream), best, cand, meta, b.tot[TOT_FRAMES],
                      b.k, steps4);
@@ -697,8 +687,7 @@ extern "C" int pe_f0_stonemask(const float* x, const long* meta, const long* hos
   if (n_rows < 0 || n_rows > kMaxRows || sr <= 0 || hop <= 0 || !isfinite(f0_min) || !(f0_min > 0.0)) return PE_E_ARG;
   if (sr < 8000 || sr > 48000 || hop > sr || !stonemask_fits(sr, f0_min)) return PE_E_UNSUPPORTED;
   DioBatch b;
-  const int st = open_rows(n_rows, host_meta, 0, TOT_FRAMES, &b);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, PE_OK, host_meta, 0, TOT_FRAMES, &b));
   if (!x || !meta || !f0_in || !roots || !f0_out) return PE_E_ARG;
   if (n_roots != stonemask_table_floats()) return PE_E_ARG;
   const double frame_period = (double)hop * 1000.0 / (double)sr;

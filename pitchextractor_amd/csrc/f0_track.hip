@@ -85,8 +85,7 @@ int derive(int sr, int hop, const double* cfg, TrackConsts* k) {
 }
 
 long table_floats(const TrackConsts& k) {     // twiddles (C float2), split roots (C + 1 float2), window, window_r
-  const long C = k.nfft / 2;
-  return 2 * C + 2 * (C + 1) + k.nw + k.hw + 1;
+  return fft_table_floats(k.nfft / 2) + k.nw + k.hw + 1;
 }
 
 // step 2: frames and first centre of a row of n samples, in float64 in exactly this order
@@ -248,24 +247,6 @@ __device__ __noinline__ double sinc_refine(const float* r, int hw, double x, int
   return acc * (sinpi(frac) * 0.31830988618379067154);
 }
 
-__device__ __forceinline__ float block_sum(float v, float* s_red, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) s_red[tid >> 6] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-
-__device__ __forceinline__ float block_max(float v, float* s_red, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if ((tid & 63) == 0) s_red[tid >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-}
-
 template <int LOG2C>
 __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __restrict__ x,
                                                              const long* __restrict__ meta,
@@ -289,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __rest
   float* l_sc = fb + C + 3 * (N / 8);
   const float2* tw = reinterpret_cast<const float2*>(tables);
   const float2* tr = tw + C;
-  const float* win = tables + 2 * C + 2 * (C + 1);
+  const float* win = tables + fft_table_floats(C);
   const float* wr = win + K.nw;
   const int tid = threadIdx.x, lane = tid & 63;
   const int nw = K.nw, hw = K.hw;
@@ -347,10 +328,9 @@ __global__ __launch_bounds__(kThreads) void f0_frames_kernel(const float* __rest
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int k = tid + kThreads * q;
-      const float2 zk = s_buf[k], zc = conj2(s_buf[(C - k) & (C - 1)]);
       float2 e, o;
-      real_fft_split(zk, zc, e, o);
-      const float2 X = cadd(e, cmul(tr[k], o));
+      const float2 t = real_fft_bin(s_buf, tr[k], C, k, e, o);
+      const float2 X = cadd(e, t);
       p[q] = X.x * X.x + X.y * X.y;
       if (k == 0) {                                                 // bin C: E - O
         const float2 Xc = csub(e, o);
@@ -588,14 +568,9 @@ bool meta_ok(const long* hm, int n_rows, long* total) {
   return true;
 }
 
-constexpr int kNothing = 1;               // open_batch: valid, and no frame to work on (PE_OK to the caller)
 int open_batch(int n_rows, int sr, int hop, const double* config7, const long* host_meta, TrackConsts* k, long* total) {
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  const int st = derive(sr, hop, config7, k);
-  if (st != PE_OK) return st;
-  if (n_rows == 0) return kNothing;
-  if (!host_meta || !meta_ok(host_meta, n_rows, total)) return PE_E_ARG;
-  return *total == 0 ? kNothing : PE_OK;
+  return open_rows(n_rows, derive(sr, hop, config7, k), host_meta, [&] { return meta_ok(host_meta, n_rows, total); },
+                   total);
 }
 
 }  // namespace
@@ -659,8 +634,7 @@ extern "C" int pe_f0_track_frames(const float* x, const long* meta, const long* 
                                   const double* config7, float* cand_f, float* cand_s, int* cand_n, void* stream) {
   TrackConsts k;
   long total = 0;
-  const int st = open_batch(n_rows, sr, hop, config7, host_meta, &k, &total);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, sr, hop, config7, host_meta, &k, &total));
   if (!x || !meta || !t1 || !stats || !tables || !cand_f || !cand_s || !cand_n) return PE_E_ARG;
   if (n_table != table_floats(k)) return PE_E_ARG;
   return with_log2<9, 12>(k.log2c, [&](auto L) {
@@ -676,8 +650,7 @@ extern "C" int pe_f0_track_path(const float* cand_f, const float* cand_s, const 
                                 void* workspace, size_t workspace_bytes, void* stream) {
   TrackConsts k;
   long total = 0;
-  const int st = open_batch(n_rows, sr, hop, config7, host_meta, &k, &total);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, sr, hop, config7, host_meta, &k, &total));
   if (!cand_f || !cand_s || !cand_n || !meta || !f0) return PE_E_ARG;
   long lds_frames = 1;
   const size_t need = spill_bytes(host_meta, n_rows, &lds_frames);

@@ -93,10 +93,9 @@ __global__ __launch_bounds__(256) void ps_stft_kernel(const float* __restrict__ 
     for (int q = 0; q < 17; ++q) {
       const int k = lane + 64 * q;
       if (k > kC) break;
-      const float2 zk = buf[k & (kC - 1)], zc = conj2(buf[(kC - k) & (kC - 1)]);
       float2 e, o;
-      real_fft_split(zk, zc, e, o);
-      out[k] = cadd(e, cmul(s_tr[k], o));
+      const float2 t = real_fft_bin(buf, s_tr[k], kC, k & (kC - 1), e, o);
+      out[k] = cadd(e, t);
     }
     wave_lds_sync();                                      // buffer reads done before the next frame's writes
   }
@@ -173,10 +172,7 @@ __global__ __launch_bounds__(256) void ps_irfft_kernel(const float2* __restrict_
       const int k = lane + 64 * q;
       float2 xk = X[k], xc = conj2(X[kC - k]);
       if (k == 0) { xk.y = 0.f; xc.y = 0.f; }               // numpy irfft drops Im of the DC and Nyquist bins
-      const float2 e = make_float2(0.5f * (xk.x + xc.x), 0.5f * (xk.y + xc.y));
-      const float2 d = csub(xk, xc);
-      const float2 o = cmul(conj2(s_tr[k]), make_float2(0.5f * d.x, 0.5f * d.y));
-      buf[k] = make_float2(e.x - o.y, e.y + o.x);           // E + i O
+      buf[k] = real_fft_pack(xk, xc, s_tr[k]);              // E + i O
     }
     wave_lds_sync();
     fft_lds<kLog2C, true, 64>(buf, s_tw, lane);
@@ -266,11 +262,6 @@ __global__ __launch_bounds__(256) void ps_resample_kernel(const float* __restric
 }
 
 constexpr int kZeros[2] = {64, 16};                          // kaiser_best, kaiser_fast zero crossings
-
-int grid_for(long work, int per_block, int cap) {
-  const long b = (work + per_block - 1) / per_block;
-  return (int)(b < cap ? b : cap);
-}
 
 }  // namespace
 

@@ -41,7 +41,7 @@ enum { S_XOFF, S_N, S_YOFF, S_SOFF, S_BLOCKS, S_BOFF, S_K };
 static_assert(S_XOFF == kRowOffset && S_N == kRowLength, "the plan opens with the shared row header");
 enum { TOT_SAMPLES, TOT_BLOCKS };
 
-long table_floats() { return 2L * kC + 2L * (kC + 1); }       // roots of the packed transform, split roots
+constexpr long kTableFloats = fft_table_floats(kC);           // roots of the packed transform, split roots
 
 bool meta_ok(const long* hm, int n_rows, long* totals2) {
   long s = 0, b = 0;
@@ -55,19 +55,9 @@ bool meta_ok(const long* hm, int n_rows, long* totals2) {
   return true;
 }
 
-constexpr int kNothing = 1;               // valid, and nothing to launch: PE_OK to the caller
-
-int open_rows(int n_rows, const long* host_meta, long* totals2) {
-  if (n_rows < 0 || n_rows > kMaxRows) return PE_E_ARG;
-  if (n_rows == 0) return kNothing;
-  if (!host_meta || !meta_ok(host_meta, n_rows, totals2)) return PE_E_ARG;
-  return totals2[TOT_SAMPLES] == 0 ? kNothing : PE_OK;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
+int open_batch(int n_rows, const long* host_meta, long* totals2) {
+  return open_rows(n_rows, PE_OK, host_meta, [&] { return meta_ok(host_meta, n_rows, totals2); },
+                   &totals2[TOT_SAMPLES]);
 }
 
 // ---- rir -----------------------------------------------------------------------------------------------------------
@@ -104,8 +94,8 @@ __global__ __launch_bounds__(kThreads) void stress_spectra_kernel(const float* _
     for (int q = 0; q < kNQ; ++q) {
       const int k = tid + kThreads * q;
       float2 e, o;
-      real_fft_split(s_buf[k], conj2(s_buf[(kC - k) & (kC - 1)]), e, o);
-      const float2 v = cadd(e, cmul(tr[k], o));
+      const float2 t = real_fft_bin(s_buf, tr[k], kC, k, e, o);
+      const float2 v = cadd(e, t);
       out[k] = k == 0 ? make_float2(e.x + o.x, e.x - o.x) : v;
     }
     __syncthreads();
@@ -162,9 +152,7 @@ __global__ __launch_bounds__(kThreads) void stress_rir_convolve_kernel(const flo
       const int k = tid + kThreads * q;
       const float2 y1 = k == 0 ? make_float2(s_buf[0].x, 0.f) : s_buf[k];
       const float2 y2 = k == 0 ? make_float2(s_buf[0].y, 0.f) : conj2(s_buf[kC - k]);
-      const float2 ye = make_float2(0.5f * (y1.x + y2.x), 0.5f * (y1.y + y2.y));
-      const float2 yo = cmul(make_float2(0.5f * (y1.x - y2.x), 0.5f * (y1.y - y2.y)), conj2(tr[k]));
-      z[q] = make_float2(ye.x - yo.y, ye.y + yo.x);
+      z[q] = real_fft_pack(y1, y2, tr[k]);
     }
     __syncthreads();
 #pragma unroll
@@ -179,11 +167,8 @@ __global__ __launch_bounds__(kThreads) void stress_rir_convolve_kernel(const flo
         out[r] = v;
         pk = fmaxf(pk, fabsf(v));
       }
-    pk = wave_max(pk);
-    if ((tid & 63) == 0) s_red[tid >> 6] = pk;
-    __syncthreads();
-    if (tid == 0) peak[g] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    __syncthreads();
+    pk = block_max(pk, s_red, tid);             // its barrier: every read of fb is done before the next block's writes
+    if (tid == 0) peak[g] = pk;
   }
 }
 
@@ -200,11 +185,7 @@ __global__ __launch_bounds__(kThreads) void stress_rir_normalize_kernel(const lo
     const long n = m[S_N], b = g - m[S_BOFF];
     float pk = 0.f;
     for (long i = tid; i < m[S_BLOCKS]; i += kThreads) pk = fmaxf(pk, peak[m[S_BOFF] + i]);
-    pk = wave_max(pk);
-    if ((tid & 63) == 0) s_red[tid >> 6] = pk;
-    __syncthreads();
-    const float p = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    __syncthreads();
+    const float p = block_max(pk, s_red, tid);
     if (p > 0.99f) {
       const float d = p + 1e-6f;
       float* out = y + m[S_YOFF] + b * kStep;
@@ -516,7 +497,7 @@ extern "C" int pe_stress_plan(int n_rows, const long* n, const long* x_off, cons
   if (n_rows > 0 && (!n || !x_off || !y_off || !meta)) return PE_E_ARG;
   for (int r = 0; r < n_rows; ++r)
     if (n[r] < 0 || n[r] > kMaxSamples || x_off[r] < 0 || y_off[r] < 0) return PE_E_ARG;
-  consts4[0] = kStep; consts4[1] = table_floats(); consts4[2] = kPiece; consts4[3] = kClipChunk;
+  consts4[0] = kStep; consts4[1] = kTableFloats; consts4[2] = kPiece; consts4[3] = kClipChunk;
   long s = 0, b = 0;
   for (int r = 0; r < n_rows; ++r) {
     long* m = meta + (long)r * S_K;
@@ -536,9 +517,8 @@ extern "C" int pe_stress_spectra(const float* x, const long* meta, const long* h
                                  const float* tables, long n_table, float* spectra, void* stream) {
   long tot[2];
   if (partition != 0 && partition != 1) return PE_E_ARG;
-  const int st = open_rows(n_rows, host_meta, tot);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
-  if (!x || !meta || !tables || !spectra || n_table != table_floats()) return PE_E_ARG;
+  PE_OPEN(open_batch(n_rows, host_meta, tot));
+  if (!x || !meta || !tables || !spectra || n_table != kTableFloats) return PE_E_ARG;
   hipLaunchKernelGGL(stress_spectra_kernel, dim3(grid_of(tot[TOT_BLOCKS])), dim3(kThreads), 0, pe_stream(stream), x,
                      meta, tables, n_rows, tot[TOT_BLOCKS], partition, reinterpret_cast<float2*>(spectra));
   PE_LAUNCH_CHECK();
@@ -550,7 +530,7 @@ extern "C" int pe_stress_rir(const float* x, const long* meta, const long* host_
                              const int* rir_index, const int* host_rir_index, const float* tables, long n_table, float* y,
                              void* workspace, size_t workspace_bytes, void* stream) {
   long tot[2], rtot[2];
-  const int st = open_rows(n_rows, host_meta, tot);
+  const int st = open_batch(n_rows, host_meta, tot);
   if (st != PE_OK && st != kNothing) return st;
   if (n_rirs < 1 || n_rirs > kMaxRows || !host_rir_meta || !meta_ok(host_rir_meta, n_rirs, rtot)) return PE_E_ARG;
   for (int k = 0; k < n_rirs; ++k)
@@ -559,7 +539,7 @@ extern "C" int pe_stress_rir(const float* x, const long* meta, const long* host_
   for (int r = 0; r < n_rows; ++r)
     if (host_rir_index[r] < 0 || host_rir_index[r] >= n_rirs) return PE_E_ARG;
   if (st == kNothing) return PE_OK;
-  if (!x || !meta || !rir_spectra || !rir_meta || !rir_index || !tables || !y || n_table != table_floats())
+  if (!x || !meta || !rir_spectra || !rir_meta || !rir_index || !tables || !y || n_table != kTableFloats)
     return PE_E_ARG;
   const long blocks = tot[TOT_BLOCKS];
   if (!workspace || workspace_bytes < pe_stress_rir_workspace_bytes(blocks)) return PE_E_WORKSPACE;
@@ -592,8 +572,7 @@ extern "C" int pe_stress_biquad(const float* x, const long* meta, const long* ho
     const double a1 = K.c[s][3], a2 = K.c[s][4];
     if (!(fabs(a2) < 1.0) || !(fabs(a1) < 1.0 + a2)) return PE_E_UNSUPPORTED;
   }
-  const int st = open_rows(n_rows, host_meta, tot);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, host_meta, tot));
   if (!x || !meta || !y) return PE_E_ARG;
   hipLaunchKernelGGL(stress_biquad_kernel, dim3(n_rows), dim3(64), 0, pe_stream(stream), x, meta, K, y);
   PE_LAUNCH_CHECK();
@@ -604,8 +583,7 @@ extern "C" int pe_stress_clip(const float* x, const long* meta, const long* host
                               float* y, float* thresholds, void* stream) {
   long tot[2];
   if (!copy && !(q >= 0.0 && q <= 1.0)) return PE_E_ARG;
-  const int st = open_rows(n_rows, host_meta, tot);
-  if (st != PE_OK) return st == kNothing ? PE_OK : st;
+  PE_OPEN(open_batch(n_rows, host_meta, tot));
   if (!x || !meta || !y) return PE_E_ARG;
   hipLaunchKernelGGL(stress_clip_kernel, dim3(n_rows), dim3(kThreads), 0, pe_stream(stream), x, meta, (float)q,
                      copy ? 1 : 0, y, thresholds);
@@ -626,7 +604,7 @@ extern "C" int pe_stress_agc(const float* x, const long* meta, const long* host_
   AgcParams P{params4[0], params4[1], params4[2], params4[3], smoothing};
   if (!(P.attack > 0.0 && P.attack < 1.0) || !(P.release > 0.0 && P.release < 1.0) || !(P.target > 0.0)) return PE_E_ARG;
   if (!(P.max_gain >= 1.0) || !(P.max_gain < 256.0)) return PE_E_ARG;        // the exact window sums need < 2^8
-  const int st = open_rows(n_rows, host_meta, tot);
+  const int st = open_batch(n_rows, host_meta, tot);
   if (st != PE_OK && st != kNothing) return st;
   if (smoothing > 1)
     for (int r = 0; r < n_rows; ++r)

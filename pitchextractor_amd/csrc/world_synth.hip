@@ -46,16 +46,6 @@ __device__ __forceinline__ float world_randn(uint64_t seed, uint64_t i) {
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
 
-// sum over the workgroup in a fixed order; every thread gets the result.  s_red: 4 floats, free on entry
-__device__ __forceinline__ float block_sum(float v, float* s_red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-
 __device__ __forceinline__ float2 cexp2(float2 z) {           // exp(z), full-accuracy exp / sin / cos
   float s, c;
   sincosf(z.y, &s, &c);
@@ -119,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void world_responses_kernel(
       zv[q] = v;
       part += v;
     }
-    const float mean = ns > 0 ? block_sum(part, s_red) / (float)ns : 0.f;
+    const float mean = ns > 0 ? block_sum(part, s_red, tid) / (float)ns : 0.f;
 #pragma unroll
     for (int q = 0; q < N / kThreads; ++q) {
       const int j = tid + kThreads * q;
@@ -184,7 +174,7 @@ __global__ __launch_bounds__(kThreads) void world_responses_kernel(
     // fftshift, DC removal over the causal half, sum
     float dpart = 0.f;
     for (int j = tid; j < H; j += kThreads) dpart += s_buf[j].x;
-    const float dc = block_sum(dpart, s_red);
+    const float dc = block_sum(dpart, s_red, tid);
     const float root = sqrtf((float)ns);
     float* out = resp + g * N;
 #pragma unroll
@@ -227,11 +217,6 @@ __global__ __launch_bounds__(kThreads) void world_ola_kernel(const float* __rest
     if (out_noise) y += out_noise[g];
     out[m[W_OOFF] + (g - m[W_JOFF])] = y;
   }
-}
-
-int grid_for(long work, int per_block, int cap) {
-  const long b = (work + per_block - 1) / per_block;
-  return (int)(b < cap ? b : cap);
 }
 
 bool fft_size_ok(int n) { return n == 512 || n == 1024 || n == 2048; }

@@ -9,7 +9,8 @@ refused with ``NotImplementedError`` when the tracker (or a dataset that names i
 ``WorldDioTracker`` (below) is the reference's ``pyworld`` backend with ``algorithm: dio``: WORLD's DIO + StoneMask
 (``csrc/f0_dio.hip``), pinned by ``tests/dio_ref.py`` in the same way.
 
-Both stand on ``_RaggedTracker``; ``NATIVE_BACKENDS`` alone says which entries of a backend chain run on the device.
+Both stand on ``_RaggedTracker``, and that on ``ragged`` (the host layer of every ragged audio entry point);
+``NATIVE_BACKENDS`` alone says which entries of a backend chain run on the device.
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .ragged import packed_offsets, row_layout
+from .ragged import device_plan, fft_roots, host_ptrs, plan_arrays, real_split_roots, workspace
 
 logger = logging.getLogger(__name__)
 
@@ -32,10 +33,6 @@ _CONFIG_ORDER = ("min_pitch", "max_pitch", "silence_threshold", "voicing_thresho
                  "octave_jump_cost", "voiced_unvoiced_cost")
 _IGNORED_KEYS = {"name", "type", "backend", "enabled", "cache_key_suffix"}
 N_CAND = 15
-
-
-def _p(*arrays):
-    return [a.ctypes.data for a in arrays]
 
 
 def _flag(value) -> bool:
@@ -71,18 +68,6 @@ def check_config(config: dict | None, require_method: bool = False) -> dict:
     return {k: float(out[k]) for k in _CONFIG_ORDER}
 
 
-def fft_roots(C: int) -> np.ndarray:
-    """The C-th roots of unity with the forward sign, exp(-2 pi i m / C) for m < C: float64, shape (C, 2)."""
-    m = np.arange(C, dtype=np.float64)
-    return np.stack([np.cos(2 * np.pi * m / C), -np.sin(2 * np.pi * m / C)], axis=1)
-
-
-def real_split_roots(C: int) -> np.ndarray:
-    """exp(-2 pi i k / 2C) for k <= C (a packed C-point transform -> the real 2C-point one): float64, (C + 1, 2)."""
-    k = np.arange(C + 1, dtype=np.float64)
-    return np.stack([np.cos(np.pi * k / C), -np.sin(np.pi * k / C)], axis=1)
-
-
 class _RaggedTracker:
     """What the trackers share: device audio at ``sr`` goes through a host-side row plan (a row's fields 0 .. 3: offset,
     length, frames, frame prefix offset) and comes back as one contour per row.  A subclass has ``plan()``."""
@@ -90,30 +75,9 @@ class _RaggedTracker:
     def __init__(self, sr: int, hop_length: int):
         self.sr, self.hop_length = int(sr), int(hop_length)
 
-    def _plan_rows(self, lengths, offsets, fields_fn: str):
-        """``(R, lengths, offsets, meta)``: int64 arrays (packed when ``offsets`` is None) and the zeroed plan."""
-        lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-        R = lengths.size
-        if offsets is None:
-            offsets = packed_offsets(lengths)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-        if offsets.size != R:
-            raise ValueError("f0 tracker: one offset per row")
-        meta = np.zeros((max(R, 1), getattr(_lib.load(), fields_fn)()), np.int64)
-        return R, lengths, offsets, meta
-
-    def _check_waves(self, waves):
-        if not isinstance(waves, torch.Tensor) or not waves.is_cuda or waves.dtype != torch.float32 or \
-                waves.dim() not in (1, 2) or (waves.numel() > 0 and waves.stride(-1) != 1):
-            raise RuntimeError(f"{type(self).__name__} (HIP) needs contiguous-row float32 device audio; no CPU "
-                               "fallback exists")
-
     def _device_plan(self, waves, lengths):
         """The plan of ``waves`` in one of ``track``'s three layouts, with its device copy as ``meta_d``."""
-        self._check_waves(waves)
-        pl = self.plan(*row_layout(waves, lengths, whole_by_default=True))
-        pl["meta_d"] = torch.from_numpy(pl["meta"]).to(waves.device)
-        return pl
+        return device_plan(waves, lengths, self.plan, type(self).__name__)
 
     def frame_count(self, n_samples: int) -> int:
         return int(self.plan([int(n_samples)])["frames"][0])
@@ -125,7 +89,7 @@ class _RaggedTracker:
     def _row_stats(self, waves, meta_d, R, stats, stream, work):
         """``pe_row_stats``: stats[r] = {mean, max |x - mean|} of the R rows of a device plan, at the plan's own stride."""
         ws_bytes = _lib.load().pe_row_stats_workspace_bytes(R)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=waves.device)
+        ws = workspace(ws_bytes, waves.device)
         ops._call("pe_row_stats", waves.data_ptr(), meta_d.data_ptr(), int(meta_d.shape[1]), R, stats.data_ptr(),
                   ws.data_ptr(), ws_bytes, stream, work=float(work))
 
@@ -150,11 +114,13 @@ class PraatACTracker(_RaggedTracker):
     # ---- host side ----------------------------------------------------------------------------------------------
     def plan(self, lengths, offsets=None) -> dict:
         """``pe_f0_track_plan``: per-row frame counts / offsets / first frame centres for rows of ``lengths``."""
-        R, lengths, offsets, meta = self._plan_rows(lengths, offsets, "pe_f0_track_plan_fields")
+        R, lengths, offsets, meta = plan_arrays("pe_f0_track_plan_fields", lengths, offsets,
+                                                 "f0 tracker: one offset per row")
         t1 = np.zeros(max(R, 1), np.float64)
         consts, dconsts, totals = np.zeros(8, np.int64), np.zeros(2, np.float64), np.zeros(2, np.int64)
-        _lib.check(_lib.load().pe_f0_track_plan(R, *_p(lengths, offsets), self.sr, self.hop_length,
-                                                *_p(self._cfg, consts, dconsts, meta, t1, totals)), "pe_f0_track_plan")
+        _lib.check(_lib.load().pe_f0_track_plan(R, *host_ptrs(lengths, offsets), self.sr, self.hop_length,
+                                                *host_ptrs(self._cfg, consts, dconsts, meta, t1, totals)),
+                   "pe_f0_track_plan")
         return dict(n_rows=R, lengths=lengths, offsets=offsets, meta=meta, t1=t1, consts=consts, dconsts=dconsts,
                     frames=meta[:R, 2].copy(), frame_offsets=meta[:R, 3].copy(), n_frames=int(totals[0]),
                     workspace_bytes=int(totals[1]))
@@ -193,7 +159,7 @@ class PraatACTracker(_RaggedTracker):
             stats = torch.empty((R, 2), dtype=torch.float32, device=dev)
             tables = _lib.device_table(("f0_track", self.n_fft, self.nsamp_window), dev, self.host_tables)
             ws_bytes = pl["workspace_bytes"]
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+            ws = workspace(ws_bytes, dev) if ws_bytes else None
             cfg = self._cfg.ctypes.data
             flop = 2 * 2.5 * self.n_fft * np.log2(self.n_fft)
             with torch.cuda.device(dev):
@@ -278,11 +244,13 @@ class WorldDioTracker(_RaggedTracker):
     # ---- host side ----------------------------------------------------------------------------------------------
     def plan(self, lengths, offsets=None) -> dict:
         """``pe_f0_dio_plan``: the constants and the per-row layout for rows of ``lengths``."""
-        R, lengths, offsets, meta = self._plan_rows(lengths, offsets, "pe_f0_dio_plan_fields")
+        R, lengths, offsets, meta = plan_arrays("pe_f0_dio_plan_fields", lengths, offsets,
+                                                 "f0 tracker: one offset per row")
         consts, half = np.zeros(10, np.int64), np.zeros(16, np.int64)
         dconsts, totals = np.zeros(17, np.float64), np.zeros(6, np.int64)
-        _lib.check(_lib.load().pe_f0_dio_plan(R, *_p(lengths, offsets), self.sr, self.hop_length,
-                                              *_p(self._cfg, consts, half, dconsts, meta, totals)), "pe_f0_dio_plan")
+        _lib.check(_lib.load().pe_f0_dio_plan(R, *host_ptrs(lengths, offsets), self.sr, self.hop_length,
+                                              *host_ptrs(self._cfg, consts, half, dconsts, meta, totals)),
+                   "pe_f0_dio_plan")
         return dict(n_rows=R, lengths=lengths, offsets=offsets, meta=meta, consts=consts, half=half, dconsts=dconsts,
                     frames=meta[:R, 2].copy(), frame_offsets=meta[:R, 3].copy(), sample_offsets=meta[:R, 4].copy(),
                     event_offsets=meta[:R, 7].copy(), n_frames=int(totals[0]), n_samples=int(totals[1]),
@@ -348,7 +316,7 @@ class WorldDioTracker(_RaggedTracker):
         e_count = torch.zeros((max(R, 1), self.bands, _DIO_KINDS), dtype=torch.int32, device=dev)
         if R:
             sig = sig.contiguous()
-            ws = torch.empty((max(pl["workspace_bytes"], 4),), dtype=torch.uint8, device=dev)
+            ws = workspace(max(pl["workspace_bytes"], 4), dev)
             ops._call("pe_f0_dio_events", sig.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data,
                       *self._args(pl), e_idx.data_ptr(), e_frac.data_ptr(), e_count.data_ptr(), ws.data_ptr(),
                       pl["workspace_bytes"], _lib.stream_ptr(), work=float(2 * self.bands * pl["n_samples"] * 4))

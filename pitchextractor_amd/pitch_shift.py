@@ -9,14 +9,13 @@ available here): parity with librosa / resampy is unpinned, see DESIGN.md.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .ragged import packed_offsets
+from .ragged import host_ptrs, plan_arrays
 
 N_FFT, HOP = 2048, 512
 N_BINS = N_FFT // 2 + 1
@@ -77,31 +76,24 @@ class Plan:
 
     def __init__(self, lengths, n_steps, x_offsets=None, out_start=None, out_len=None, out_rows=None,
                  out_stride=None, *, sr: int, res_type: str = "kaiser_best"):
-        lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-        R = lengths.size
-        self.n_rows = R
         self.res_type = check_res_type(res_type)
+        mismatch = "pitch shift plan: per-row arrays differ in length"
+        R, lengths, self.x_offsets, self.meta = plan_arrays("pe_pitch_shift_plan_fields", lengths, x_offsets, mismatch)
+        self.n_rows = R
         self.lengths = lengths
         self.n_steps = np.ascontiguousarray(n_steps, dtype=np.float32).reshape(-1)
-        self.x_offsets = (packed_offsets(lengths) if x_offsets is None
-                          else np.ascontiguousarray(x_offsets, dtype=np.int64).reshape(-1))
         self.out_start = np.zeros(R, np.int64) if out_start is None else np.ascontiguousarray(out_start, np.int64)
         self.out_len = lengths.copy() if out_len is None else np.ascontiguousarray(out_len, np.int64)
         self.out_rows = np.arange(R, dtype=np.int64) if out_rows is None else np.ascontiguousarray(out_rows, np.int64)
         self.out_stride = int(self.out_len.max(initial=0) if out_stride is None else out_stride)
-        if not (self.n_steps.size == self.x_offsets.size == self.out_start.size == self.out_len.size ==
-                self.out_rows.size == R):
-            raise ValueError("pitch shift plan: per-row arrays differ in length")
-        lib = _lib.load()
-        K = lib.pe_pitch_shift_plan_fields()
-        self.meta = np.zeros((max(R, 1), K), np.int64)
+        if not (self.n_steps.size == self.out_start.size == self.out_len.size == self.out_rows.size == R):
+            raise ValueError(mismatch)
         self.ratios = np.zeros((max(R, 1), 2), np.float64)
         self.totals = np.zeros(4, np.int64)
-        p = lambda a: a.ctypes.data  # noqa: E731
-        _lib.check(lib.pe_pitch_shift_plan(R, p(self.lengths), p(self.n_steps), p(self.x_offsets), p(self.out_start),
-                                           p(self.out_len), p(self.out_rows), self.out_stride, int(sr), N_FFT, HOP,
-                                           list(RES_TYPES).index(self.res_type), p(self.meta), p(self.ratios),
-                                           p(self.totals)), "pe_pitch_shift_plan")
+        _lib.check(_lib.load().pe_pitch_shift_plan(
+            R, *host_ptrs(self.lengths, self.n_steps, self.x_offsets, self.out_start, self.out_len, self.out_rows),
+            self.out_stride, int(sr), N_FFT, HOP, list(RES_TYPES).index(self.res_type),
+            *host_ptrs(self.meta, self.ratios, self.totals)), "pe_pitch_shift_plan")
         self.n_frames, self.n_cols, self.n_stretched, self.n_out = (int(v) for v in self.totals)
 
 

@@ -9,7 +9,7 @@ import math
 import torch
 
 from . import _lib, ops
-from .ragged import row_layout
+from .ragged import check_waves, row_layout
 
 
 class Resampler:
@@ -94,8 +94,7 @@ class RaggedResampler:
         back (``lengths`` required).  ``rates``, ``lengths``: host sequences.  Returns ``(y (B, y_width),
         out_lengths int32 (B,) device)``; ``y_width`` defaults to the longest output and each row is zero past its
         own output."""
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2) or x.stride(-1) != 1:
-            raise RuntimeError("RaggedResampler (HIP) needs contiguous-row float32 device audio; no CPU fallback exists")
+        check_waves(x, "RaggedResampler")
         rates = [int(r) for r in rates]
         lengths, offsets = row_layout(x, lengths)
         B = len(rates)

@@ -3,7 +3,7 @@ impulse responses and microphone colouration (Utils/room_and_microphone_stress.i
 (Utils/amplitude_pathologies.ipynb) and the down/up resample (Utils/codec_and_bandwidth_torture.ipynb).  There is no CPU
 path.  ``tests/stress_ref.py`` is the float64 restatement that pins every one of them.
 
-Every condition takes a ragged batch the way the F0 trackers do (``ragged.row_layout``): a 1-D wave of rows packed back
+Every condition takes a ragged batch the way the F0 trackers do (``ragged.device_plan``): a 1-D wave of rows packed back
 to back with ``lengths``, or a padded 2-D batch.  The result has the input's shape (dense; zero outside the rows) and a
 row of it is bit-identical whether the row is processed alone, packed or padded.  The launch count of a condition does
 not depend on the rows.  ``inference.stress_sweep`` runs a model over a list of ``Condition``.
@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .f0_tracker import _p, fft_roots, real_split_roots
-from .ragged import row_layout
+from .ragged import (check_waves, device_plan, fft_roots, host_ptrs, i64, plan_arrays, real_split_roots, row_layout,
+                     workspace)
 from .resample import RaggedResampler
 
 MAX_STAGES = 8
@@ -119,16 +119,13 @@ def agc_parameters(level_db: float, sr: int, target_rms: float) -> dict:
 
 def plan_rows(lengths, offsets, out_offsets) -> dict:
     """``pe_stress_plan`` (host only): the row plan and its constants."""
-    lib = _lib.load()
-    n = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    xo = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-    yo = np.ascontiguousarray(out_offsets, dtype=np.int64).reshape(-1)
-    if xo.size != n.size or yo.size != n.size:
-        raise ValueError("stress plan: one offset and one output offset per row")
-    R = int(n.size)
-    meta = np.zeros((max(R, 1), lib.pe_stress_plan_fields()), np.int64)
+    mismatch = "stress plan: one offset and one output offset per row"
+    R, n, xo, meta = plan_arrays("pe_stress_plan_fields", lengths, offsets, mismatch)
+    yo = i64(out_offsets)
+    if yo.size != R:
+        raise ValueError(mismatch)
     consts, totals = np.zeros(4, np.int64), np.zeros(2, np.int64)
-    _lib.check(lib.pe_stress_plan(R, *_p(n, xo, yo, consts, meta, totals)), "pe_stress_plan")
+    _lib.check(_lib.load().pe_stress_plan(R, *host_ptrs(n, xo, yo, consts, meta, totals)), "pe_stress_plan")
     return dict(rows=R, lengths=n, meta=meta, block_step=int(consts[0]), table_floats=int(consts[1]),
                 piece=int(consts[2]), clip_chunk=int(consts[3]), n_samples=int(totals[0]), n_blocks=int(totals[1]))
 
@@ -143,26 +140,13 @@ def _tables(device):
     return _lib.device_table("stress_fft", device, host_tables)
 
 
-def _check_waves(x, what):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2) or \
-            (x.numel() > 0 and x.stride(-1) != 1):
-        raise RuntimeError(f"{what} (HIP) needs contiguous-row float32 device audio; no CPU fallback exists")
-
-
 def _batch(x, lengths, what):
     """The plan of ``x`` in one of the three layouts, its device copy, and the zeroed dense output of ``x``'s shape."""
-    _check_waves(x, what)
-    lengths, offsets = row_layout(x, lengths, whole_by_default=True)
-    width = int(x.shape[1]) if x.dim() == 2 else 0
-    out_offsets = [r * width for r in range(len(lengths))] if x.dim() == 2 else offsets
-    pl = plan_rows(lengths, offsets, out_offsets)
-    pl["meta_d"] = torch.from_numpy(pl["meta"]).to(x.device)
-    y = torch.zeros(tuple(x.shape), dtype=torch.float32, device=x.device)
-    return pl, y
-
-
-def _workspace(n_bytes, device):
-    return torch.empty((max(int(n_bytes), 1),), dtype=torch.uint8, device=device)
+    def plan(lengths, offsets):                 # a padded row goes to its own row of the output, a packed one in place
+        width = int(x.shape[1]) if x.dim() == 2 else 0
+        return plan_rows(lengths, offsets, [r * width for r in range(len(lengths))] if x.dim() == 2 else offsets)
+    pl = device_plan(x, lengths, plan, what)
+    return pl, torch.zeros(tuple(x.shape), dtype=torch.float32, device=x.device)
 
 
 # ------------------------------------------------------------------------------------------------------------ conditions
@@ -220,7 +204,7 @@ def apply_rir(x: torch.Tensor, rirs: RirSet, rir_index=0, lengths=None) -> torch
     index_d = torch.from_numpy(host_index).to(x.device)
     tables = _tables(x.device)
     ws_bytes = lib.pe_stress_rir_workspace_bytes(pl["n_blocks"])
-    ws = _workspace(ws_bytes, x.device)
+    ws = workspace(ws_bytes, x.device)
     with torch.cuda.device(x.device):
         ops._call("pe_stress_rir", x.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, R, spectra.data_ptr(),
                   rir_meta_d.data_ptr(), rirs.plan["meta"].ctypes.data, len(rirs), index_d.data_ptr(),
@@ -278,7 +262,7 @@ def apply_agc_pumping(x: torch.Tensor, level_db: float, sr: int, target_rms: flo
         return copy_rows(x, lengths)
     prm = agc_parameters(level_db, sr, target_rms)
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
-        _check_waves(x, "apply_agc_pumping")
+        check_waves(x, "apply_agc_pumping")
     row_lengths, _ = row_layout(x, lengths, whole_by_default=True)
     if prm["smoothing"] > 1 and any(n < prm["smoothing"] for n in row_lengths):
         raise ValueError(f"apply_agc_pumping: a row is shorter than the smoothing length {prm['smoothing']}")
@@ -288,7 +272,7 @@ def apply_agc_pumping(x: torch.Tensor, level_db: float, sr: int, target_rms: flo
     lib = _lib.load()
     params = np.array([prm["attack_coeff"], prm["release_coeff"], prm["target_rms"], prm["max_gain"]], np.float64)
     ws_bytes = lib.pe_stress_agc_workspace_bytes(pl["n_samples"])
-    ws = _workspace(ws_bytes, x.device)
+    ws = workspace(ws_bytes, x.device)
     with torch.cuda.device(x.device):
         ops._call("pe_stress_agc", x.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, pl["rows"],
                   params.ctypes.data, prm["smoothing"], y.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr())
@@ -303,7 +287,7 @@ def apply_resample_condition(x: torch.Tensor, sr: int, target_rate: int, lengths
     ``(y (B, width) padded, lengths)``: the round trip changes a row's length as the reference's does.
     ``target_rate == sr`` is a copy."""
     sr, target_rate = int(sr), int(target_rate)
-    _check_waves(x, "apply_resample_condition")
+    check_waves(x, "apply_resample_condition")
     row_lengths, _ = row_layout(x, lengths, whole_by_default=True)
     B = len(row_lengths)
     if target_rate == sr:

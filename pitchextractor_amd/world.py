@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ragged import fft_roots, host_ptrs, i64, plan_meta
 
 FFT_SIZES = (512, 1024, 2048)
 WORKSPACE_BYTES = 256 << 20                                 # responses of one launch; more rows go to further launches
@@ -109,7 +110,7 @@ def noise_seed(curve) -> int:
 
 # --------------------------------------------------------------------------- batch layout
 def _i64(a, n=None):
-    a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    a = i64(a)
     if n is not None and a.size != n:
         raise ValueError("WORLD plan: per-row arrays differ in length")
     return a
@@ -124,6 +125,7 @@ class Plan:
                  fft_size, f0s=None):
         self.n_frames = _i64(n_frames)
         R = self.n_rows = self.n_frames.size
+        self.meta = plan_meta("pe_world_plan_fields", R)
         self.fs, self.frame_period_ms, self.fft_size = fs, float(frame_period_ms), int(fft_size)
         if len(tables) != R:
             raise ValueError("WORLD plan: one pulse table per row")
@@ -150,20 +152,16 @@ class Plan:
                                       if R else np.zeros(0))
             if f0.size != int(self.n_frames.sum()):
                 raise ValueError("WORLD plan: f0 curves do not match the frame counts")
-        lib = _lib.load()
-        K = lib.pe_world_plan_fields()
         P = max(int(self.index.size), 1)
-        self.meta = np.zeros((max(R, 1), K), np.int64)
         self.pulses = np.zeros((P, 6), np.int64)
         self.pulse_f = np.zeros((P, 2), np.float64)
         self.totals = np.zeros(2, np.int64)
-        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        _lib.check(lib.pe_world_plan(R, p(self.n_frames), p(f0), p(self.pulse_cnt), p(self.index), p(self.shift),
-                                     p(self.vuv), p(self.sp_offsets), p(self.sp_strides), p(self.ap_offsets),
-                                     p(self.ap_strides), p(self.noise_offsets), p(self.seeds), p(self.out_start),
-                                     p(self.out_len), p(self.out_rows), self.out_stride, float(fs),
-                                     self.frame_period_ms, self.fft_size, p(self.meta), p(self.pulses),
-                                     p(self.pulse_f), p(self.totals)), "pe_world_plan")
+        _lib.check(_lib.load().pe_world_plan(
+            R, *host_ptrs(self.n_frames, f0, self.pulse_cnt, self.index, self.shift, self.vuv, self.sp_offsets,
+                          self.sp_strides, self.ap_offsets, self.ap_strides, self.noise_offsets, self.seeds,
+                          self.out_start, self.out_len, self.out_rows),
+            self.out_stride, float(fs), self.frame_period_ms, self.fft_size,
+            *host_ptrs(self.meta, self.pulses, self.pulse_f, self.totals)), "pe_world_plan")
         self.n_pulses, self.n_out = (int(v) for v in self.totals)
         self.pulses, self.pulse_f = self.pulses[:max(self.n_pulses, 1)], self.pulse_f[:max(self.n_pulses, 1)]
 
@@ -173,11 +171,8 @@ class WorldSynth:
     stages for a ``Plan``."""
 
     def table(self, fft_size, device):
-        def build():
-            m = np.arange(fft_size)
-            ang = -2.0 * np.pi * m / fft_size
-            return np.concatenate([np.stack([np.cos(ang), np.sin(ang)], axis=1).reshape(-1), dc_remover(fft_size)])
-        return _lib.device_table(("world", int(fft_size)), device, build)
+        return _lib.device_table(("world", int(fft_size)), device,
+                                 lambda: np.concatenate([fft_roots(fft_size).reshape(-1), dc_remover(fft_size)]))
 
     def run(self, plan: Plan, sp, ap, gains, out, noise=None, out_noise=None, keep=False):
         """sp / ap / noise: flat float32 device tensors addressed by the plan's offsets (ap, noise optional); gains

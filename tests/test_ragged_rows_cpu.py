@@ -85,3 +85,13 @@ def test_refusals():
         row_layout(torch.zeros((2, 3, 4)), [1, 1])
     assert row_layout(packed, [10]) == ([10], [0])                            # the bounds themselves are allowed
     assert row_layout(padded, [8, 8, 8])[0] == [8, 8, 8]
+
+
+def test_host_audio_is_refused_in_the_callers_name():
+    from pitchextractor_amd.ragged import check_waves
+    from pitchextractor_amd.resample import RaggedResampler
+    for bad in (torch.zeros(8), np.zeros(8, np.float32), None):
+        with pytest.raises(RuntimeError, match=r"^RaggedResampler \(HIP\) needs contiguous-row float32 device audio; no CPU"):
+            RaggedResampler(24000)(bad, [16000], [8])
+        with pytest.raises(RuntimeError, match=r"^somebody \(HIP\) needs .* no CPU fallback exists$"):
+            check_waves(bad, "somebody")

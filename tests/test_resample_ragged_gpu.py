@@ -109,3 +109,13 @@ def test_host_checks_refuse_before_launch(hip_device):
         rs(x, [44100, 16000], [100, 100], y_width=100)     # 16 kHz row: 150 outputs do not fit
     with pytest.raises(ValueError):
         rs(x, [44100, 16000], [101, 100])
+
+
+def test_rows_without_samples_need_no_launch(hip_device):
+    """An empty input goes through whatever its stride is (``torch.from_numpy`` of an empty array has stride 0), as it
+    does for the trackers and the stress conditions: no row has an output, nothing is launched."""
+    rs = RaggedResampler(24000)
+    for x, lengths in ((torch.from_numpy(np.zeros(0, np.float32)).to(hip_device), [0, 0]),
+                       (torch.zeros((2, 0), device=hip_device), None)):
+        y, out_lengths = rs(x, [16000, 24000], lengths)
+        assert tuple(y.shape) == (2, 0) and out_lengths.cpu().tolist() == [0, 0]
