@@ -9,7 +9,8 @@ reference nor installed in this image, so this is a restatement of
 torchaudio's *published* MelSpectrogram semantics with its defaults:
 ``f_min=0, f_max=sr//2, power=2, normalized=False, center=True,
 pad_mode="reflect", window=hann(periodic), onesided=True, norm=None,
-mel_scale="htk"``.  PARITY UNPINNED by the reference (it holds no vectors for
+mel_scale="htk"``.  ``f_min`` / ``f_max`` are honoured as keywords (``f_max=None`` is that
+default), so band-limited ``mel_params`` have an oracle too.  PARITY UNPINNED by the reference (it holds no vectors for
 this stage); pinned by agreement of two independent restatements:
 
 * :func:`mel_spectrogram` -- float64, direct O(N^2) DFT or ``numpy.fft.rfft``;
@@ -87,11 +88,17 @@ def stft_power(x: np.ndarray, n_fft: int = 1024, hop: int = 300,
     return (spec.real ** 2 + spec.imag ** 2).T
 
 
+def _f_max(f_max, sample_rate: int) -> float:
+    return float(sample_rate // 2) if f_max is None else float(f_max)
+
+
 def mel_spectrogram(x: np.ndarray, sample_rate: int = 24000, n_fft: int = 1024,
                     hop_length: int = 300, n_mels: int = 80,
-                    direct_dft: bool = False, **_unused) -> np.ndarray:
-    """(n_mels, 1 + N//hop) mel power spectrogram, float64."""
-    fb = mel_filterbank(n_fft // 2 + 1, 0.0, float(sample_rate // 2), n_mels, sample_rate)
+                    direct_dft: bool = False, f_min: float = 0.0, f_max=None,
+                    **_unused) -> np.ndarray:
+    """(n_mels, 1 + N//hop) mel power spectrogram, float64.  ``f_max=None`` is torchaudio's
+    default, ``float(sample_rate // 2)``."""
+    fb = mel_filterbank(n_fft // 2 + 1, float(f_min), _f_max(f_max, sample_rate), n_mels, sample_rate)
     return fb.T @ stft_power(x, n_fft, hop_length, direct_dft)
 
 
@@ -105,7 +112,8 @@ def log_mel(x: np.ndarray, **kw) -> np.ndarray:
 
 
 def mel_spectrogram_torch_stft(x, sample_rate: int = 24000, n_fft: int = 1024,
-                               hop_length: int = 300, n_mels: int = 80):
+                               hop_length: int = 300, n_mels: int = 80,
+                               f_min: float = 0.0, f_max=None, **_unused):
     """Second, independent restatement in float32 through ``torch.stft`` (CPU)."""
     import torch
     xt = torch.as_tensor(np.asarray(x), dtype=torch.float32)
@@ -113,6 +121,6 @@ def mel_spectrogram_torch_stft(x, sample_rate: int = 24000, n_fft: int = 1024,
                       center=True, pad_mode="reflect", normalized=False,
                       onesided=True, return_complex=True)
     power = spec.abs().pow(2)
-    fb = torch.as_tensor(mel_filterbank(n_fft // 2 + 1, 0.0, float(sample_rate // 2),
+    fb = torch.as_tensor(mel_filterbank(n_fft // 2 + 1, float(f_min), _f_max(f_max, sample_rate),
                                         n_mels, sample_rate), dtype=torch.float32)
     return (fb.T @ power).numpy()

@@ -123,6 +123,7 @@ __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int pa
     const int n_valid = n_samples > kHalf ? 1 + n_samples / hop : 0;
     const int f0 = f_out0 + (a.frame_start ? max(a.frame_start[b], 0) : 0);   // first source frame
     const float* wsrc = a.wave + (long)b * a.wave_stride;
+    const unsigned long wsrc_addr = reinterpret_cast<unsigned long>(wsrc);
     const long N = n_samples;
 
     if (f0 < n_valid) {
@@ -133,7 +134,9 @@ __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int pa
         if (valid) {
           // pass 1: radix-8 over a, lane = m = 8b+c, x[n = 64a + m]
           const long base = (long)(f0 + fi) * hop - kHalf;      // first sample of the frame (may be < 0)
-          if (base >= 0 && base + kNfft <= N && ((base | a.wave_stride) & 1) == 0) {
+          // float2 loads need the ADDRESS of the frame 8-byte aligned: the row pointer counts (an odd row
+          // stride or a view at an odd storage offset shifts it), not just the parity of base
+          if (base >= 0 && base + kNfft <= N && ((wsrc_addr + 4 * (unsigned long)base) & 7) == 0) {
             const float2* fr = reinterpret_cast<const float2*>(wsrc + base);
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
