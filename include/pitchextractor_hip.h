@@ -100,6 +100,37 @@ int pe_mel_forward_ragged(const pe_mel_plan* plan, const float* wave, int batch,
                           long wave_stride, const int* n_samples, const int* frame_start, float* out,
                           long out_sb, long out_sm, long out_st, int out_frames, int log_mode,
                           float log_eps, float mean, float std, float pad_value, void* stream);
+/* Chunked batch (inference.predict_f0_batch): item i of n_chunks is described by row i of `chunks` (n_chunks x
+ * pe_mel_chunk_fields() int64 on the device; host_chunks its host copy) = {sample offset of its row in wave, samples
+ * of that row, first source frame}: output frame t < chunk_size of item i shows frame chunks[i][2] + t of the row
+ * at wave + chunks[i][0], reflect-padded at the ROW's ends; frames at or past the row's 1 + n / hop are pad_value.
+ * Written at caller-given strides like pe_mel_forward (out_sm == 1 gives the model's (chunk, 1, frames, mels) input
+ * directly).  Checked on host_chunks before any device call: PE_E_ARG for a null pointer, a negative entry, a row of
+ * at most n_fft/2 samples or one that ends past wave_elems; PE_E_UNSUPPORTED for more than 65535 chunks or a row of
+ * 2^31 samples or more. */
+int pe_mel_chunk_fields(void);
+int pe_mel_forward_chunks(const pe_mel_plan* plan, const float* wave, long wave_elems, const long* chunks,
+                          const long* host_chunks, int n_chunks, int chunk_size, float* out, long out_sb,
+                          long out_sm, long out_st, int log_mode, float log_eps, float mean, float std,
+                          float pad_value, void* stream);
+
+/* ---- stitching chunk outputs into rows (inference.predict_f0_batch) --------------------------------------------------
+ * pe_stitch_chunks: x is (n_chunks, chunk_size, C) float32, frame (k, f) at x + (k * chunk_size + f) * ld_x, unit
+ * stride over the C columns, 1 <= C <= 1024, ld_x >= C; det (nullable) is (n_chunks, chunk_size) dense.  The
+ * destination is n_dst frames, frame d at out + d * ld_out (ld_out >= C), and det_out[d] (given exactly when det is).
+ * runs (n_runs x pe_stitch_run_fields() int64 on the device; host_runs its host copy) = per run {chunk a, frame in a,
+ * first destination frame, length, n_ov, j0, chunk b, frame in b}, sorted by destination and not overlapping.
+ * n_ov == 0: destination frame dst + i is a copy of frame (a, fa + i), no arithmetic.  n_ov > 0 (a seam): with
+ * float32 w = (j0 + i + 1) / (n_ov + 1) it is A + w * (B - A) in float32, A = frame (a, fa + i), B = frame (b, fb + i);
+ * j0 + length <= n_ov.  Destination frames that no run covers are written as 0 in every column.  Every destination
+ * element is written exactly once, by one launch, without atomics.  Checked on host_runs before any device call:
+ * PE_E_ARG for a null pointer, a negative size, a run that leaves its chunk, the chunk batch or the destination, runs
+ * out of order or overlapping, or det given without det_out (or the reverse); PE_E_UNSUPPORTED for C outside
+ * 1 .. 1024. */
+int pe_stitch_run_fields(void);
+int pe_stitch_chunks(const float* x, long ld_x, const float* det, const long* runs, const long* host_runs,
+                     int n_runs, int n_chunks, int chunk_size, int C, float* out, long ld_out, float* det_out,
+                     long n_dst, void* stream);
 
 
 /* ---- dense fp32 GEMMs on the MFMA engine -----------------------------------

@@ -48,6 +48,7 @@ struct MelArgs {
   int audio_len;               // (FB-1)*hop + 1024, padded to a multiple of 4
   const int* n_samples_arr;    // optional [batch]: per-utterance length (ragged batches)
   const int* frame_start;      // optional [batch]: output frame t shows source frame t + frame_start[b]
+  const long* chunk_tab;       // optional [batch][3]: {sample offset of the row in wave, its samples, first source frame}
 };
 
 __device__ __forceinline__ void fft4(const float2 u0, const float2 u1, const float2 u2, const float2 u3,
@@ -81,7 +82,11 @@ __device__ __forceinline__ void fft8(float2 (&v)[8]) {
 // by the host so that parts * batch fills the resident grid and the VALID frames divide evenly: 161 frames over 4
 // workgroups = 41 each, where a fixed 16-frame block grid would give one workgroup 48 and another 32); a workgroup
 // walks its range in chunks of FB frames.  Frames >= the utterance's frame count are written as padding.
-template <int FB>
+// CHUNKS: items are rows of the chunk table (a window of frames of a row found by its sample offset) instead of
+// wave rows.  It is an instance of its own so that the other entry points keep the code they had; it refetches the
+// twiddles of passes 1 and 2 per frame (fourteen cached loads of the same values) instead of holding them, which
+// keeps it free of scratch under the 128-VGPR cap of four workgroups per CU.
+template <int FB, bool CHUNKS>
 __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int parts, int span, int n_items) {
   static_assert(FB % 4 == 0, "FB frames are dealt to 4 waves");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -103,8 +108,8 @@ __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int pa
   for (int r = 0; r < 8; ++r) {
     const int n = 64 * r + lane;                        // complex sample index, stage 1
     win[r] = make_float2(a.win[2 * n], a.win[2 * n + 1]);
-    tw1[r] = a.tw512[(lane * r) & 511];                 // W512^(m*k0)
-    tw2[r] = a.tw512[(8 * c_ * r) & 511];               // W64^(c*k1)
+    if constexpr (!CHUNKS) tw1[r] = a.tw512[(lane * r) & 511];     // W512^(m*k0)
+    if constexpr (!CHUNKS) tw2[r] = a.tw512[(8 * c_ * r) & 511];   // W64^(c*k1)
   }
   const float2* twp = a.tw1024 + lane;                  // W1024^k of the real-FFT split: 4 cached loads per frame
   float2* X = s_X + wv * kXchg;
@@ -118,11 +123,13 @@ __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int pa
    const int r_lo = prt * span, r_hi = prt + 1 == parts ? a.out_frames : min(a.out_frames, r_lo + span);
    for (int f_out0 = r_lo; f_out0 < r_hi; f_out0 += FB) {      // first output frame of this chunk
     const int n_out = min(FB, r_hi - f_out0);
-    const int n_samples = a.n_samples_arr ? a.n_samples_arr[b] : a.n_samples;
+    // chunk table: item b is a window of frames of the row at wave + offset (the reflect padding is the row's)
+    const long* ct = CHUNKS ? a.chunk_tab + 3 * (long)b : nullptr;
+    const int n_samples = CHUNKS ? (int)ct[1] : a.n_samples_arr ? a.n_samples_arr[b] : a.n_samples;
     // reflect padding needs more than n_fft/2 samples; shorter items come out as padding only
     const int n_valid = n_samples > kHalf ? 1 + n_samples / hop : 0;
-    const int f0 = f_out0 + (a.frame_start ? max(a.frame_start[b], 0) : 0);   // first source frame
-    const float* wsrc = a.wave + (long)b * a.wave_stride;
+    const int f0 = f_out0 + (CHUNKS ? (int)ct[2] : a.frame_start ? max(a.frame_start[b], 0) : 0);   // first source frame
+    const float* wsrc = a.wave + (CHUNKS ? ct[0] : (long)b * a.wave_stride);
     const unsigned long wsrc_addr = reinterpret_cast<unsigned long>(wsrc);
     const long N = n_samples;
 
@@ -158,8 +165,11 @@ __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int pa
             }
           }
           fft8(v);
+          int tw1_at = lane;
+          if constexpr (CHUNKS) asm volatile("" : "+v"(tw1_at));   // loaded here, per frame: not hoisted and held
 #pragma unroll
-          for (int r = 0; r < 8; ++r) X[r * 72 + lane] = (r == 0) ? v[0] : cmul(v[r], tw1[r]);
+          for (int r = 0; r < 8; ++r)
+            X[r * 72 + lane] = (r == 0) ? v[0] : cmul(v[r], CHUNKS ? a.tw512[(tw1_at * r) & 511] : tw1[r]);
         }
         wave_lds_sync();
         if (valid) {
@@ -169,8 +179,11 @@ __global__ __launch_bounds__(256, 4) void mel_fwd_kernel(const MelArgs a, int pa
           for (int r = 0; r < 8; ++r) v[r] = X[k0 * 72 + 8 * r + c_];
           fft8(v);
           wave_lds_sync();
+          int tw2_at = 8 * c_;
+          if constexpr (CHUNKS) asm volatile("" : "+v"(tw2_at));   // loaded here, per frame: not hoisted and held
 #pragma unroll
-          for (int r = 0; r < 8; ++r) X[(k0 + 8 * r) * 9 + c_] = (r == 0) ? v[0] : cmul(v[r], tw2[r]);
+          for (int r = 0; r < 8; ++r)
+            X[(k0 + 8 * r) * 9 + c_] = (r == 0) ? v[0] : cmul(v[r], CHUNKS ? a.tw512[(tw2_at * r) & 511] : tw2[r]);
         }
         wave_lds_sync();
         if (valid) {
@@ -368,8 +381,11 @@ extern "C" int pe_mel_plan_create(pe_mel_plan** plan_out, int sample_rate, int n
   PE_CHECK_HIP(hipMalloc(&d, total));
   hipError_t e = hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(d); return (int)e; }
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_fwd_kernel<kFB>),
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_fwd_kernel<kFB, false>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_fwd_kernel<kFB, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) { (void)hipFree(d); return (int)e; }
 
   pe_mel_plan* p = new pe_mel_plan;
@@ -398,17 +414,18 @@ extern "C" int pe_mel_num_frames(const pe_mel_plan* plan, int n_samples) {
 }
 
 static int mel_launch(const pe_mel_plan* plan, const float* wave, int batch, int n_samples, long wave_stride,
-                      const int* n_samples_arr, const int* frame_start, float* out, long out_sb, long out_sm,
+                      const int* n_samples_arr, const int* frame_start, const long* chunk_tab, float* out,
+                      long out_sb, long out_sm,
                       long out_st, int out_frames, int log_mode, float log_eps, float mean, float std,
                       float pad_value, void* stream) {
   if (!plan || !wave || !out || batch < 0 || out_frames < 0) return PE_E_ARG;
   // reflect padding needs n_fft/2 < n_samples (torch.stft raises otherwise)
-  if ((!n_samples_arr && n_samples <= kHalf) || wave_stride < n_samples || std == 0.0f) return PE_E_ARG;
+  if ((!n_samples_arr && !chunk_tab && n_samples <= kHalf) || wave_stride < n_samples || std == 0.0f) return PE_E_ARG;
   if (batch == 0 || out_frames == 0) return PE_OK;
   if (batch > 65535) return PE_E_UNSUPPORTED;
 
   MelArgs a;
-  a.n_samples_arr = n_samples_arr; a.frame_start = frame_start;
+  a.n_samples_arr = n_samples_arr; a.frame_start = frame_start; a.chunk_tab = chunk_tab;
   a.wave = wave; a.wave_stride = wave_stride; a.n_samples = n_samples; a.hop = plan->hop;
   a.n_mels = plan->n_mels; a.n_valid = 1 + n_samples / plan->hop; a.out_frames = out_frames;
   a.out = out; a.out_sb = out_sb; a.out_sm = out_sm; a.out_st = out_st;
@@ -424,7 +441,7 @@ static int mel_launch(const pe_mel_plan* plan, const float* wave, int batch, int
   // not ragged) are divided evenly, in multiples of 4 frames (one per wave)
   const long resident = (long)mel_cus() * ((160 * 1024) / (long)lds < 4 ? (160 * 1024) / (long)lds : 4);
   int work_frames = out_frames;
-  if (!n_samples_arr && !frame_start && a.n_valid < work_frames) work_frames = a.n_valid;
+  if (!n_samples_arr && !frame_start && !chunk_tab && a.n_valid < work_frames) work_frames = a.n_valid;
   int parts = (int)((resident + batch - 1) / batch);
   const int max_parts = pe_cdiv(work_frames, 4);
   if (parts > max_parts) parts = max_parts;
@@ -433,8 +450,8 @@ static int mel_launch(const pe_mel_plan* plan, const float* wave, int batch, int
   parts = pe_cdiv(work_frames, span);
   const long n_items = (long)parts * batch;
   const int grid = (int)(n_items < resident ? n_items : resident);
-  hipLaunchKernelGGL(mel_fwd_kernel<kFB>, dim3(grid), dim3(256), lds, pe_stream(stream), a, parts, span,
-                     (int)n_items);
+  const auto kernel = chunk_tab ? mel_fwd_kernel<kFB, true> : mel_fwd_kernel<kFB, false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, pe_stream(stream), a, parts, span, (int)n_items);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
@@ -443,7 +460,7 @@ extern "C" int pe_mel_forward(const pe_mel_plan* plan, const float* wave, int ba
                               long wave_stride, float* out, long out_sb, long out_sm, long out_st,
                               int out_frames, int log_mode, float log_eps, float mean, float std,
                               float pad_value, void* stream) {
-  return mel_launch(plan, wave, batch, n_samples, wave_stride, nullptr, nullptr, out, out_sb, out_sm, out_st,
+  return mel_launch(plan, wave, batch, n_samples, wave_stride, nullptr, nullptr, nullptr, out, out_sb, out_sm, out_st,
                     out_frames, log_mode, log_eps, mean, std, pad_value, stream);
 }
 
@@ -452,6 +469,29 @@ extern "C" int pe_mel_forward_ragged(const pe_mel_plan* plan, const float* wave,
                                      long out_sb, long out_sm, long out_st, int out_frames, int log_mode,
                                      float log_eps, float mean, float std, float pad_value, void* stream) {
   if (!n_samples) return PE_E_ARG;
-  return mel_launch(plan, wave, batch, max_samples, wave_stride, n_samples, frame_start, out, out_sb, out_sm,
+  return mel_launch(plan, wave, batch, max_samples, wave_stride, n_samples, frame_start, nullptr, out, out_sb, out_sm,
                     out_st, out_frames, log_mode, log_eps, mean, std, pad_value, stream);
+}
+
+enum { C_OFF = 0, C_N, C_FRAME, C_K };
+
+extern "C" int pe_mel_chunk_fields(void) { return C_K; }
+
+extern "C" int pe_mel_forward_chunks(const pe_mel_plan* plan, const float* wave, long wave_elems, const long* chunks,
+                                     const long* host_chunks, int n_chunks, int chunk_size, float* out, long out_sb,
+                                     long out_sm, long out_st, int log_mode, float log_eps, float mean, float std,
+                                     float pad_value, void* stream) {
+  if (!plan || n_chunks < 0 || chunk_size < 0 || wave_elems < 0) return PE_E_ARG;
+  if (n_chunks > 0 && !host_chunks) return PE_E_ARG;
+  long longest = 0;
+  for (int i = 0; i < n_chunks; ++i) {
+    const long* c = host_chunks + (long)i * C_K;
+    if (c[C_OFF] < 0 || c[C_N] <= kHalf || c[C_FRAME] < 0 || c[C_OFF] > wave_elems - c[C_N]) return PE_E_ARG;
+    if (c[C_N] >= (1L << 31) || c[C_FRAME] >= (1L << 31) - chunk_size) return PE_E_UNSUPPORTED;
+    if (c[C_N] > longest) longest = c[C_N];
+  }
+  if (n_chunks > 65535) return PE_E_UNSUPPORTED;
+  if (!wave || !chunks || !out || std == 0.0f) return PE_E_ARG;
+  return mel_launch(plan, wave, n_chunks, (int)longest, longest, nullptr, nullptr, chunks, out, out_sb, out_sm, out_st,
+                    chunk_size, log_mode, log_eps, mean, std, pad_value, stream);
 }

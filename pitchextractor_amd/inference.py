@@ -15,7 +15,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, ragged
 from .mel import DEFAULT_MEL_PARAMS, LOG_EPS, MEL_MEAN, MEL_STD, MelSpectrogram
 from .model import JDCNet
 
@@ -65,8 +65,29 @@ def waveform_to_mel(audio, mel_transform: MelSpectrogram | None = None, device="
     """(N,) float audio at the model rate -> (n_mels, L) normalised log-mel on the device."""
     tf = mel_transform or MelSpectrogram(**DEFAULT_MEL_PARAMS)
     wave = torch.as_tensor(np.asarray(audio, dtype=np.float32)).to(device)
-    mel = tf(wave)
+    return _normalised_log(tf(wave))
+
+
+def _normalised_log(mel: torch.Tensor) -> torch.Tensor:
+    """meldataset.py:650 as the notebooks apply it to a mel power tensor."""
     return (torch.log(mel + LOG_EPS) - MEL_MEAN) / MEL_STD
+
+
+def _silence_cut(p) -> float:
+    """logit(p), the detector logit above which ``sigmoid(z) > p``."""
+    p = float(p)
+    return -np.inf if p <= 0.0 else (np.inf if p >= 1.0 else float(np.log(p) - np.log1p(-p)))
+
+
+def _check_decoding(model, decoder, silence_threshold, return_confidence):
+    if decoder is not None and decoder not in ops.F0_DECODERS:
+        raise ValueError(f"decoder must be one of {ops.F0_DECODERS}, got {decoder!r}")
+    if decoder is not None and model.num_class == 1:
+        raise ValueError("decoder: the model is a regression model (num_class == 1), there are no bins to decode")
+    if return_confidence and decoder is None:
+        raise ValueError("return_confidence needs a decoder")
+    if silence_threshold is not None and decoder is None and model.num_class != 1:
+        raise ValueError("silence_threshold on a classifier needs a decoder")
 
 
 @torch.no_grad()
@@ -82,14 +103,7 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
     are decoded in one call and concatenated as the Hz of a regression model are.  ``silence_threshold=p`` returns
     0 Hz where ``sigmoid(detector logit) > p`` (the detector head predicts ``is_silence``).
     ``return_confidence=True`` returns ``(f0, confidence)``, confidence = softmax(frame)[decoded bin]."""
-    if decoder is not None and decoder not in ops.F0_DECODERS:
-        raise ValueError(f"decoder must be one of {ops.F0_DECODERS}, got {decoder!r}")
-    if decoder is not None and model.num_class == 1:
-        raise ValueError("decoder: the model is a regression model (num_class == 1), there are no bins to decode")
-    if return_confidence and decoder is None:
-        raise ValueError("return_confidence needs a decoder")
-    if silence_threshold is not None and decoder is None and model.num_class != 1:
-        raise ValueError("silence_threshold on a classifier needs a decoder")
+    _check_decoding(model, decoder, silence_threshold, return_confidence)
     device = model.flat_parameters.device
     mel = waveform_to_mel(audio, mel_transform, device)
     total = mel.shape[-1]
@@ -120,9 +134,7 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
             hz = f0[..., 0]
         if silence_threshold is not None:
             # sigmoid(z) > p  <=>  z > logit(p); the comparison is exact, the zeros are written on the device
-            p = float(silence_threshold)
-            cut = -np.inf if p <= 0.0 else (np.inf if p >= 1.0 else float(np.log(p) - np.log1p(-p)))
-            hz = torch.where(sil.reshape(hz.shape) > cut, torch.zeros_like(hz), hz)
+            hz = torch.where(sil.reshape(hz.shape) > _silence_cut(silence_threshold), torch.zeros_like(hz), hz)
         hz = hz.cpu().numpy()
         out = np.concatenate([hz[i][:e] for i, e in enumerate(ends)])
         if not return_confidence:
@@ -131,6 +143,277 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
         return out, np.concatenate([conf[i][:e] for i, e in enumerate(ends)])
     f0 = f0[..., 0].cpu().numpy() if f0.shape[-1] == 1 else f0.cpu().numpy()
     return np.concatenate([f0[i][:min(s + chunk_size, total) - s] for i, s in enumerate(starts)])
+
+# ---------------------------------------------------------------------------------------- batched ragged inference
+STITCH_MODES = ("concat", "center", "crossfade")
+# columns of a stitch run (include/pitchextractor_hip.h, pe_stitch_chunks)
+RUN_A, RUN_FA, RUN_DST, RUN_LEN, RUN_NOV, RUN_J0, RUN_B, RUN_FB = range(8)
+
+
+def _row_runs(starts, ends, n_frames, chunk_size, stitch):
+    """``(kept, runs)`` of one row: the chunks (indices into ``starts``) that own an output frame, and its stitch runs
+    as 8-column rows whose chunk columns count in ``kept`` and whose destination counts from the row's first frame."""
+    K = len(starts)
+    runs = []
+    if K == 0:
+        return [], runs
+    if stitch == "concat":
+        at = 0
+        for k in range(K):
+            runs.append((k, 0, at, ends[k] - starts[k], 0, 0, 0, 0))
+            at += ends[k] - starts[k]
+        return list(range(K)), runs
+    if stitch == "center":
+        owner = np.zeros(n_frames, np.int64)
+        best = np.full(n_frames, np.iinfo(np.int64).max, np.int64)
+        for k in range(K):                              # ascending k and a strict "<": ties go to the smaller k
+            t = np.arange(starts[k], ends[k], dtype=np.int64)
+            cost = np.abs(2 * (t - starts[k]) - (chunk_size - 1))
+            win = cost < best[starts[k]:ends[k]]
+            owner[starts[k]:ends[k]][win] = k
+            best[starts[k]:ends[k]][win] = cost[win]
+        cuts = [0] + (np.flatnonzero(np.diff(owner)) + 1).tolist() + [n_frames]
+        kept = sorted(set(owner.tolist()))
+        index = {k: i for i, k in enumerate(kept)}
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            k = int(owner[lo])
+            runs.append((index[k], lo - starts[k], lo, hi - lo, 0, 0, 0, 0))
+        return kept, runs
+    for k in range(K):                                  # crossfade: a chunk's own frames, then its seam with the next
+        lo = max(starts[k], ends[k - 1]) if k else starts[k]
+        hi = min(ends[k], starts[k + 1]) if k + 1 < K else ends[k]
+        if hi > lo:
+            runs.append((k, lo - starts[k], lo, hi - lo, 0, 0, 0, 0))
+        if k + 1 < K and ends[k] > starts[k + 1]:
+            n_ov = ends[k] - starts[k + 1]
+            runs.append((k, starts[k + 1] - starts[k], starts[k + 1], n_ov, n_ov, 0, k + 1, 0))
+    return list(range(K)), runs
+
+
+def chunk_plan(n_frames, chunk_size: int = 192, overlap: int = 48, stitch: str = "concat", *, sample_offsets=None,
+               sample_counts=None) -> dict:
+    """Host plan of chunked inference over rows of ``n_frames`` mel frames (an int, or one per row).
+
+    Chunks start every ``max(chunk_size - overlap, 1)`` frames from 0 (the notebook's rule) and chunk k is valid over
+    ``[s_k, e_k)``, ``e_k = min(s_k + chunk_size, n_frames)``.  ``stitch`` makes a row's output of them:
+    "concat", the valid frames of every chunk back to back (``sum(e_k - s_k)`` values, ``overlap`` frames repeated at
+    every seam); "center", ``n_frames`` values, frame t copied from the covering chunk that minimises
+    ``|2 (t - s_k) - (chunk_size - 1)|`` (ties: the smaller k), chunks that own no frame left out; "crossfade"
+    (``2 * overlap <= chunk_size``), ``n_frames`` values, the ``n_ov = e_k - s_{k+1}`` frames two chunks share
+    blended as ``a + w (b - a)``, ``w = (j + 1) / (n_ov + 1)`` for the j-th of them, the others copied.
+
+    Returns ``rows`` (per row: ``starts``, ``valid``, ``kept``, ``out_len``, ``out_offset``, ``chunks`` and ``runs``
+    as (first, end) positions in the two tables) and, for the batch in row-major order, ``meta`` (n_chunks, 3) int64
+    {sample offset, sample count (``sample_offsets`` / ``sample_counts`` per row; 0 without), first frame},
+    ``chunk_valid`` (n_chunks,), ``runs`` (n_runs, 8) int64 {chunk, frame in it, destination, length, n_ov, first j,
+    second chunk, frame in it} with rows packed back to back in the destination, and ``n_out``."""
+    chunk_size, overlap = int(chunk_size), int(overlap)
+    if stitch not in STITCH_MODES:
+        raise ValueError(f"stitch must be one of {STITCH_MODES}, got {stitch!r}")
+    if chunk_size < 1 or not 0 <= overlap < chunk_size:
+        raise ValueError("chunk_plan: need chunk_size >= 1 and 0 <= overlap < chunk_size")
+    if stitch == "crossfade" and 2 * overlap > chunk_size:
+        raise ValueError("chunk_plan: crossfade needs 2 * overlap <= chunk_size (at most two chunks per frame)")
+    frames = [int(n_frames)] if np.ndim(n_frames) == 0 else [int(n) for n in n_frames]
+    if any(n < 0 for n in frames):
+        raise ValueError("chunk_plan: a frame count is negative")
+    R = len(frames)
+    offs = np.zeros(R, np.int64) if sample_offsets is None else ragged.i64(sample_offsets)
+    counts = np.zeros(R, np.int64) if sample_counts is None else ragged.i64(sample_counts)
+    if offs.size != R or counts.size != R:
+        raise ValueError("chunk_plan: one sample offset and one sample count per row")
+    step = max(chunk_size - overlap, 1)
+    rows, meta, valid, runs = [], [], [], []
+    n_out = 0
+    for r, L in enumerate(frames):
+        starts = list(range(0, L, step))
+        ends = [min(s + chunk_size, L) for s in starts]
+        kept, row_runs = _row_runs(starts, ends, L, chunk_size, stitch)
+        out_len = sum(run[RUN_LEN] for run in row_runs)
+        base = len(meta)
+        rows.append(dict(starts=starts, valid=[e - s for s, e in zip(starts, ends)], kept=kept, out_len=out_len,
+                         out_offset=n_out, chunks=(base, base + len(kept)), runs=(len(runs), len(runs) + len(row_runs))))
+        meta += [(offs[r], counts[r], starts[k]) for k in kept]
+        valid += [ends[k] - starts[k] for k in kept]
+        runs += [(a + base, fa, dst + n_out, n, n_ov, j0, b + base if n_ov else 0, fb)
+                 for a, fa, dst, n, n_ov, j0, b, fb in row_runs]
+        n_out += out_len
+    return dict(rows=rows, n_out=n_out, chunk_size=chunk_size, overlap=overlap, stitch=stitch,
+                meta=np.array(meta, np.int64).reshape(-1, 3), chunk_valid=np.array(valid, np.int64),
+                runs=np.array(runs, np.int64).reshape(-1, 8))
+
+
+def _moved_runs(plan: dict, order, dst_starts) -> np.ndarray:
+    """The stitch runs of rows ``order`` with row ``order[i]`` written from destination frame ``dst_starts[i]``
+    (ascending) instead of its packed place."""
+    parts = []
+    for r, at in zip(order, dst_starts):
+        row = plan["rows"][r]
+        part = plan["runs"][row["runs"][0]:row["runs"][1]].copy()
+        part[:, RUN_DST] += at - row["out_offset"]
+        parts.append(part)
+    return np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 8), np.int64)
+
+
+def _length_groups(lengths, row_bytes: int, budget: int):
+    """Rows in order of length cut into groups whose padded size ``rows * longest * row_bytes`` stays within ``budget``
+    (a row that is over it alone is a group of its own)."""
+    order = sorted(range(len(lengths)), key=lambda r: (lengths[r], r))
+    groups, cur = [], []
+    for r in order:
+        if cur and (len(cur) + 1) * lengths[r] * row_bytes > budget:
+            groups.append(cur)
+            cur = []
+        cur.append(r)
+    return groups + ([cur] if cur else [])
+
+
+_DEFAULT_MEL = None
+
+
+def _default_mel() -> MelSpectrogram:
+    global _DEFAULT_MEL
+    if _DEFAULT_MEL is None:
+        _DEFAULT_MEL = MelSpectrogram(**DEFAULT_MEL_PARAMS)
+    return _DEFAULT_MEL
+
+
+def mel_chunks(waves, plan: dict, mel_transform: MelSpectrogram | None = None) -> torch.Tensor:
+    """The model input ``(n_chunks, 1, chunk_size, n_mels)`` of a ``chunk_plan`` with its device copy (``meta_d``): one
+    launch writes the mel power of every chunk of every row in that layout (``ops.mel_forward_chunks``), zero past a
+    row's frames; log and normalisation are then ``waveform_to_mel``'s own expression, in place of the kernel's fused
+    form, whose logarithm rounds differently -- so a chunk is, bit for bit, a slice of ``waveform_to_mel`` of its row
+    alone, which is what makes the batched path comparable with the notebook's on the same chunks."""
+    tf = mel_transform or _default_mel()
+    x = ops.mel_forward_chunks(tf, waves, plan["meta"], plan["meta_d"], plan["chunk_size"], log=False)
+    valid = torch.from_numpy(plan["chunk_valid"]).to(x.device)
+    frame = torch.arange(plan["chunk_size"], device=x.device)
+    return _normalised_log(x).masked_fill_((frame[None, :] >= valid[:, None])[:, None, :, None], 0.0)
+
+
+def _stitch(x, runs, n_dst, det=None):
+    """``ops.stitch_chunks`` into a fresh destination of ``n_dst`` frames: ``(out, det_out)``."""
+    out = torch.empty((n_dst,) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    det_out = None if det is None else torch.empty((n_dst,), dtype=torch.float32, device=x.device)
+    ops.stitch_chunks(x, runs, torch.from_numpy(runs).to(x.device), out, det, det_out)
+    return out, det_out
+
+
+@torch.no_grad()
+def predict_f0_batch(model: JDCNet, waves, lengths=None, *, chunk_size: int = 192, overlap: int = 48,
+                     stitch: str = "center", max_chunks: int = 256, mel_transform: MelSpectrogram | None = None,
+                     decoder: str | None = None, silence_threshold: float | None = None,
+                     return_confidence: bool = False, group_bytes: int = 1 << 30):
+    """``predict_f0`` for a whole ragged batch without leaving the device, and with a choice of how chunks become a
+    row (``chunk_plan``): the default "center" returns one value per mel frame.
+
+    ``waves`` is float32 device audio at the model rate in the layouts of ``ragged.device_plan`` (one 1-D wave, packed
+    rows with ``lengths``, padded 2-D rows) or a list of numpy arrays, uploaded once.  One launch takes the mel of
+    every chunk of every row into the model's input layout (``mel_chunks``), the model runs in eval mode over
+    consecutive sub-batches of at most ``max_chunks`` chunks (row-major), one launch stitches.  Returns one device
+    tensor per row, views of one buffer: Hz for a regression model, the stitched ``(L, num_class)`` logits for a
+    classifier without a ``decoder``.
+    With a ``decoder`` and "concat" every chunk is decoded on its own as in ``predict_f0``; with "center" or
+    "crossfade" a row's stitched logits are ONE sequence for ``ops.decode_f0_bins``, so a Viterbi path crosses seams
+    (rows go through it in padded groups by length of at most ``group_bytes``).  ``silence_threshold`` and
+    ``return_confidence`` as in ``predict_f0``, on the stitched detector logit.  A chunk's output depends at rounding
+    level on the chunks that share its forward (the h2 products scale by tensor maxima), so the result is not
+    bit-equal to a ``predict_f0`` loop in any mode."""
+    _check_decoding(model, decoder, silence_threshold, return_confidence)
+    device = model.flat_parameters.device
+    if isinstance(waves, (list, tuple)):
+        host = [np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1)) for w in waves]
+        if not host:
+            return ([], []) if return_confidence else []
+        lengths = [int(w.size) for w in host]
+        waves = torch.from_numpy(np.concatenate(host)).to(device)
+    tf = mel_transform or _default_mel()
+    frames = []
+
+    def plan(row_lengths, offsets):
+        if any(n <= tf.n_fft // 2 for n in row_lengths):
+            raise ValueError(f"predict_f0_batch: a row has at most n_fft / 2 = {tf.n_fft // 2} samples; the mel front "
+                             "end cannot reflect-pad it")
+        frames[:] = [tf.num_frames(n) for n in row_lengths]
+        return chunk_plan(frames, chunk_size, overlap, stitch, sample_offsets=offsets, sample_counts=row_lengths)
+
+    pl = ragged.device_plan(waves, lengths, plan, "predict_f0_batch")
+    rows, n_chunks, C = pl["rows"], int(pl["meta"].shape[0]), model.num_class
+    if not rows:
+        return ([], []) if return_confidence else []
+    mel = mel_chunks(waves, pl, tf)
+
+    was_training = model.training
+    model.eval()
+    max_chunks = max(int(max_chunks), 1)
+    logits = det = None
+    if n_chunks > max_chunks:
+        logits = torch.empty((n_chunks, chunk_size, C), dtype=torch.float32, device=device)
+        det = torch.empty((n_chunks, chunk_size), dtype=torch.float32, device=device)
+    for lo in range(0, n_chunks, max_chunks):
+        x = mel[lo:lo + max_chunks]
+        f0, sil = model(x)
+        if ops.persistent_lstm_error(device):          # a timed-out group barrier voids the outputs: redo
+            ops.clear_persistent_lstm_error(device)
+            ops.USE_PERSISTENT_LSTM = False
+            f0, sil = model(x)
+        if logits is None:
+            logits, det = f0.detach().reshape(n_chunks, chunk_size, C), sil.detach().reshape(n_chunks, chunk_size)
+        else:
+            logits[lo:lo + max_chunks] = f0.reshape(-1, chunk_size, C)
+            det[lo:lo + max_chunks] = sil.reshape(-1, chunk_size)
+    if was_training:
+        model.train()
+    logits, det = logits.contiguous(), det.contiguous()
+
+    gate = None if silence_threshold is None else _silence_cut(silence_threshold)
+    want_det = det if gate is not None else None
+    conf = None
+    if decoder is None:
+        out, sil = _stitch(logits, pl["runs"], pl["n_out"], want_det)
+        hz = out[:, 0] if C == 1 else out
+        offsets = [row["out_offset"] for row in rows]
+    elif stitch == "concat":
+        valid = torch.from_numpy(pl["chunk_valid"].astype(np.int32)).to(device)
+        hz, conf, _ = ops.decode_f0_bins(logits, valid, decoder)
+        hz, sil = _stitch(hz, pl["runs"], pl["n_out"], want_det)
+        if return_confidence:
+            conf, _ = _stitch(conf, pl["runs"], pl["n_out"])
+        offsets = [row["out_offset"] for row in rows]
+    else:
+        # one sequence per row: padded groups by length for the decoder, gathered into one packed buffer group by group
+        n_out = pl["n_out"]
+        hz = torch.empty((n_out,), dtype=torch.float32, device=device)
+        conf = torch.empty((n_out,), dtype=torch.float32, device=device) if return_confidence else None
+        sil = None
+        offsets = [0] * len(rows)
+        at = 0
+        for group in _length_groups(frames, 4 * C, int(group_bytes)):
+            G, width = len(group), max(frames[r] for r in group)
+            runs = _moved_runs(pl, group, [i * width for i in range(G)])
+            padded, sil_g = _stitch(logits, runs, G * width, want_det)
+            row_frames = torch.tensor([frames[r] for r in group], dtype=torch.int32, device=device)
+            hz_g, conf_g, _ = ops.decode_f0_bins(padded.view(G, width, C), row_frames, decoder)
+            if gate is not None:
+                hz_g = torch.where(sil_g.view(G, width) > gate, torch.zeros_like(hz_g), hz_g)
+            gather = np.zeros((G, 8), np.int64)
+            total = 0
+            for i, r in enumerate(group):
+                gather[i, [RUN_A, RUN_DST, RUN_LEN]] = (i, total, frames[r])
+                offsets[r] = at + total
+                total += frames[r]
+            gather_d = torch.from_numpy(gather).to(device)
+            ops.stitch_chunks(hz_g, gather, gather_d, hz[at:at + total])
+            if return_confidence:
+                ops.stitch_chunks(conf_g, gather, gather_d, conf[at:at + total])
+            at += total
+        gate = None                                    # applied per group above
+    if gate is not None:
+        hz = torch.where(sil > gate, torch.zeros_like(hz), hz)
+    out_rows = [hz[o:o + row["out_len"]] for o, row in zip(offsets, rows)]
+    if not return_confidence:
+        return out_rows
+    return out_rows, [conf[o:o + row["out_len"]] for o, row in zip(offsets, rows)]
 
 
 _TRACKERS = {}
@@ -199,13 +482,15 @@ def melody_metrics(pred, ref, baseline=None, voicing_threshold_hz: float = 10.0,
 
 @torch.no_grad()
 def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voicing_threshold_hz: float = 10.0,
-                 **predict_kwargs) -> dict:
+                 batched: bool = False, **predict_kwargs) -> dict:
     """The notebooks' sweep: ``items`` (a list of ``{"audio", "reference_f0"}`` at the model rate ``sr``, default the
     mel front end's) are scored clean, then every ``stress.Condition`` degrades the whole set as one ragged batch on
     the device and each degraded row goes through ``predict_f0`` (``predict_kwargs``: its keyword arguments; a
     classifier needs a ``decoder``).  Returns ``{"baseline": [...], "conditions": [...]}``: one record per item, and
     one per (condition, item) in order, each ``{"condition", "kind", "item"}`` plus ``melody_metrics``; a condition's
-    ``VUV_flips`` is measured against the item's clean prediction, the baseline's own is 0."""
+    ``VUV_flips`` is measured against the item's clean prediction, the baseline's own is 0.  ``batched=True``: the
+    clean set and every degraded set go through ``predict_f0_batch(..., stitch="concat")`` without leaving the device;
+    the records keep their shape, the predictions differ from the per-row ones at rounding level."""
     from . import stress
     device = model.flat_parameters.device
     sr = int(sr or DEFAULT_MEL_PARAMS["sample_rate"])
@@ -217,6 +502,8 @@ def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voi
         batch[r, :w.size] = torch.from_numpy(w).to(device)
 
     def run(rows, row_lengths):
+        if batched:
+            return predict_f0_batch(model, rows, row_lengths, **{"stitch": "concat", **predict_kwargs})
         return [np.asarray(predict_f0(model, rows[r, :n].cpu().numpy(), **predict_kwargs), dtype=np.float32)
                 for r, n in enumerate(row_lengths)]
 

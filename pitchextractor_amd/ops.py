@@ -951,6 +951,87 @@ def decode_f0_bins(logits, lengths=None, method="argmax"):
     return (f0[0], conf[0], bins[0]) if squeeze else (f0, conf, bins)
 
 
+def _host_table(t, fields_fn: str, name: str):
+    """(rows, host array) of an int64 host table of ``fields_fn()`` columns."""
+    import numpy as np
+    _chk(isinstance(t, np.ndarray) and t.dtype == np.int64 and t.ndim == 2 and t.flags.c_contiguous
+         and t.shape[1] == getattr(_lib.load(), fields_fn)(), f"{name}: expected a C-contiguous int64 host table")
+    return int(t.shape[0]), t
+
+
+def _device_table(t, host, name: str):
+    _chk(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+         and tuple(t.shape) == host.shape, f"{name}: expected the device copy of the host table")
+    return t
+
+
+def mel_forward_chunks(mel, wave, chunks, chunks_d, chunk_size, out=None, log=True):
+    """Mel of chunk table entries in the model's input layout (``pe_mel_forward_chunks``): ``mel`` a
+    ``MelSpectrogram``, ``wave`` float32 device audio (1-D packed or 2-D padded rows), ``chunks`` the (n, 3) int64 host
+    table {sample offset of the row from ``wave``'s first element, samples of the row, first frame} and ``chunks_d``
+    its device copy.  Returns ``out`` (n, 1, chunk_size, n_mels), frames past a row's end 0: the normalised log-mel
+    with the kernel's own logarithm (what ``log_mel_ragged`` writes), or with ``log=False`` the mel power (what the
+    transform itself returns)."""
+    from .mel import LOG_EPS, MEL_MEAN, MEL_STD
+    _f32c(wave, "wave")
+    _chk(wave.dim() in (1, 2) and (wave.numel() == 0 or wave.stride(-1) == 1),
+         "wave: expected 1-D or 2-D rows of unit stride")
+    n, chunks = _host_table(chunks, "pe_mel_chunk_fields", "chunks")
+    _device_table(chunks_d, chunks, "chunks_d")
+    chunk_size = int(chunk_size)
+    _chk(chunk_size >= 1, "chunk_size must be positive")
+    if wave.dim() == 1 or wave.shape[0] == 0:
+        elems = wave.numel()
+    else:
+        elems = (wave.shape[0] - 1) * wave.stride(0) + wave.shape[1]
+    if out is None:
+        out = torch.empty((n, 1, chunk_size, mel.n_mels), dtype=torch.float32, device=wave.device)
+    _chk(_dense(out, "out").shape == (n, 1, chunk_size, mel.n_mels), "mel_forward_chunks: out shape")
+    if n == 0:
+        return out
+    with torch.cuda.device(wave.device):
+        _call("pe_mel_forward_chunks", mel._get_plan(wave.device), wave.data_ptr(), elems, chunks_d.data_ptr(),
+              chunks.ctypes.data, n, chunk_size, out.data_ptr(), out.stride(0), out.stride(3), out.stride(2),
+              int(bool(log)), LOG_EPS, MEL_MEAN, MEL_STD, 0.0, _s(), work=float(n * chunk_size * 4 * (mel.hop_length + mel.n_mels)))
+    return out
+
+
+def stitch_chunks(x, runs, runs_d, out, det=None, det_out=None):
+    """Chunk outputs to stitched rows by a run table (``pe_stitch_chunks``, ``inference.chunk_plan``): ``x``
+    (n_chunks, chunk_size, C) or (n_chunks, chunk_size) float32 with unit stride over C and evenly spaced frames,
+    ``out`` (n_dst, C) or (n_dst,) with unit stride over C, ``runs`` the (n_runs, 8) int64 host table and ``runs_d``
+    its device copy; ``det`` (n_chunks, chunk_size) and ``det_out`` (n_dst,), both dense, go together.  Every element
+    of ``out`` is written: a copy, a blend, or 0 where no run lands.  One launch."""
+    _f32c(x, "x")
+    _f32c(out, "out")
+    _chk(x.dim() in (2, 3) and out.dim() == x.dim() - 1,
+         "stitch_chunks: x (n, T, C) with out (n_dst, C), or (n, T) with (n_dst,)")
+    if x.dim() == 2:
+        x, out = x.unsqueeze(-1), out.unsqueeze(-1)
+    n_chunks, T, C = x.shape
+    n_dst = out.shape[0]
+    _chk(out.shape[1] == C, "stitch_chunks: x and out differ in columns")
+    _chk(1 <= C <= 1024, "stitch_chunks: need 1 <= C <= 1024")
+    _chk(C == 1 or (x.stride(2) == 1 and out.stride(1) == 1), "stitch_chunks: expected unit stride over the columns")
+    ld_x = x.stride(1) if T > 1 else max(C, x.stride(1))
+    ld_out = out.stride(0) if n_dst > 1 else max(C, out.stride(0))
+    _chk(ld_x >= C and ld_out >= C and (n_chunks <= 1 or x.stride(0) == T * ld_x),
+         "stitch_chunks: frames overlap in memory or chunks are not evenly spaced")
+    n_runs, runs = _host_table(runs, "pe_stitch_run_fields", "runs")
+    _device_table(runs_d, runs, "runs_d")
+    _chk((det is None) == (det_out is None), "stitch_chunks: det and det_out go together")
+    if det is not None:
+        _chk(_dense(det, "det").shape == (n_chunks, T), "det: expected (n_chunks, chunk_size)")
+        _chk(_dense(det_out, "det_out").shape == (n_dst,), "det_out: expected (n_dst,)")
+    if n_dst == 0:
+        return out
+    with torch.cuda.device(x.device):
+        _call("pe_stitch_chunks", x.data_ptr(), ld_x, _lib.ptr(det), runs_d.data_ptr(), runs.ctypes.data, n_runs,
+              n_chunks, T, C, out.data_ptr(), ld_out, _lib.ptr(det_out), n_dst, _s(),
+              work=float(2 * 4 * n_dst * (C + (det is not None))))
+    return out
+
+
 def pitch_metrics(f0_pred, f0_ref, threshold_cents=50.0):
     """float64 device tensor [rms_cents, rpa, rca, vuv_error, n_voiced, n_frames] of a predicted F0 track against a
     reference, both (n,) float32 device tensors of one length (see ``inference.pitch_metrics``)."""
