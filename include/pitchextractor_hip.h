@@ -666,6 +666,65 @@ int pe_melody_metrics_fields(void);
 int pe_melody_metrics(const float* f0_pred, const float* f0_ref, const float* f0_base, const long* tracks,
                       const long* host_tracks, int n_rows, double voicing_threshold_hz, double* out7, void* stream);
 
+/* ---- Synthesized evaluation stimuli (reference Utils/dynamic_pitch_tools.py, dynamic_pitch_behavior.ipynb,
+ * pitch_range_and_timbre_coverage.ipynb) and the dynamic metrics, ragged batches -------------------------------------
+ * pe_stim_plan (host only): row r has n[r] >= 1 samples written at y + y_off[r]; kind[r] = 0 a given F0 curve
+ * (curve_len[r] float32 values at curves + curve_off[r]; curve_len 1 is a constant tone, else n[r]), 1 a linear
+ * glide, 2 a vibrato, 3 a harmonic tone.  raw6[r] = {amplitude, a, b, c, duration in seconds, snr_db}: glide a =
+ * start Hz, b = end Hz; vibrato a = base Hz, b = depth in cents, c = rate Hz; tone a = frequency.  partials[r] = 16 x
+ * {harmonic, amplitude} of which the first n_partials[r] (1 .. 16, tones only) are summed in order; noise_off[r] = the
+ * row's offset in the noise tensor, -1 for none.  n is given by the caller (int(duration * sr)); fade =
+ * (long)max(0.02 * sr, 0).  consts4 = {piece S = 2048, fade, 16, doubles per row of `stats`}; meta (n_rows x
+ * pe_stim_plan_fields() int64, to be copied to the device) = per row {offset, samples, kind, sample prefix, pieces =
+ * ceil(n / S), piece prefix, curve offset, curve length, partials, fade, noise offset}; params (n_rows x
+ * pe_stim_param_fields() doubles, to be copied to the device) = every derived parameter, evaluated once in the
+ * reference's order: {amplitude, a' , b', c', snr_db, sr, duration / n, 0, then per partial {amplitude, (2 pi f) h}},
+ * glide: start, (end - start) / (n - 1), end; vibrato: base, depth / 1200, (2 pi) rate; totals2 = {samples, pieces}.
+ * PE_E_ARG: n < 1, 0 < fade and n < fade, a non-finite or non-positive frequency, duration or sr, a non-finite
+ * amplitude, more than 16 partials or none, a curve length other than 1 or n.
+ *
+ * Every entry point below checks its arguments and host_meta (the host copy of meta) before any device call, allocates
+ * nothing, and launches the same number of kernels whatever the rows; pieces are counted from a row's own first sample
+ * and reduced in a fixed order, so a row's output is bit-identical alone, packed at any offset or padded.  workspace:
+ * pe_stim_workspace_bytes(totals2[1]) (PE_E_WORKSPACE when missing or too small).
+ * pe_stim_phase: phase[sample prefix + i] = sum over j <= i of ((2 pi) curve[j]) / sr in double, for rows of kinds
+ * 0 .. 2 (three launches: piece sums, per-row carries, the scan).  pe_stim_synth: y = float32(amplitude sin(phase)).
+ * pe_stim_tone: rows of kind 3, y[i] = float32(sum_h a_h sin(((2 pi f) h) t[i])), t[i] = i (duration / n).
+ * pe_stim_finish, in place on y: the raised-cosine fade float32(float64(y) window) (ramp[j] = 0.5 - 0.5 cos(j (pi /
+ * (fade - 1))) over the head and mirrored over the tail, the tail overwriting an overlap); for rows with noise,
+ * scale = float32((rms_s / 10^(snr_db / 20)) / rms_n) with both rms in double over the float32 samples, y = y +
+ * float32(noise scale) in float32, skipped when either rms is 0; then with peak = max |y|, y = y / float32(peak + 1e-6)
+ * if peak > 0.99.  stats[r] = {peak, rms_s, rms_n (0 without noise), scale (0: no mix)}.  Four launches.
+ * pe_stim_reference: the reference's sample_reference_f0 without a per-sample curve: frame_table (n_rows x 2 int64,
+ * host copy host_frame_table) = per row {frame prefix, frames}; frame_times (device doubles, made by the caller);
+ * ref[f] = float32(np.interp(tau, float32(t), float32(curve))), a tone's curve being float32(frequency).
+ *
+ * pe_dynamic_metrics: tracks (n_rows x pe_dynamic_metrics_fields() int64; host_tracks its host copy) = per row
+ * {offset in f0_pred, frames L, offset in f0_ref}.  out4[r] = {rms cents error (pe_pitch_metrics' expression), lag in
+ * frames = argmax_k sum_n pred_c[n + k - (L - 1)] ref_c[n] - (L - 1) on the mean-centred tracks (first maximum;
+ * positive when the prediction is late; NaN when every |centred| of either track is <= 1e-8), overshoot 1200
+ * log2(max(pred) / ref[L - 1]) (NaN when either is <= 0), final error 1200 log2(max(pred[L - 1], 1e-5) /
+ * max(ref[L - 1], 1e-5)) (NaN when ref[L - 1] <= 0)}; all NaN for L = 0.  One workgroup per row, O(L^2) for the lag. */
+int pe_stim_plan_fields(void);
+int pe_stim_param_fields(void);
+int pe_stim_plan(int n_rows, const long* n, const long* y_off, const int* kind, const double* raw6,
+                 const double* partials, const int* n_partials, const long* curve_off, const long* curve_len,
+                 const long* noise_off, double sr, long* consts4, long* meta, double* params, long* totals2);
+size_t pe_stim_workspace_bytes(long pieces);
+int pe_stim_phase(const long* meta, const long* host_meta, const double* params, const float* curves, int n_rows,
+                  double* phase, void* workspace, size_t workspace_bytes, void* stream);
+int pe_stim_synth(const long* meta, const long* host_meta, const double* params, const double* phase, int n_rows,
+                  float* y, void* stream);
+int pe_stim_tone(const long* meta, const long* host_meta, const double* params, int n_rows, float* y, void* stream);
+int pe_stim_finish(const long* meta, const long* host_meta, const double* params, const float* noise, int n_rows,
+                   float* y, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int pe_stim_reference(const long* meta, const long* host_meta, const double* params, const float* curves,
+                      const long* frame_table, const long* host_frame_table, const double* frame_times, int n_rows,
+                      float* ref, void* stream);
+int pe_dynamic_metrics_fields(void);
+int pe_dynamic_metrics(const float* f0_pred, const float* f0_ref, const long* tracks, const long* host_tracks,
+                       int n_rows, double* out4, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

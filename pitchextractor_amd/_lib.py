@@ -161,6 +161,17 @@ PROTOTYPES = {
     "pe_stress_agc": (_i, [_p, _p, _p, _i, _p, _i, _p, _p, _z, _p]),
     "pe_melody_metrics_fields": (_i, []),
     "pe_melody_metrics": (_i, [_p, _p, _p, _p, _p, _i, _d, _p, _p]),
+    "pe_stim_plan_fields": (_i, []),
+    "pe_stim_param_fields": (_i, []),
+    "pe_stim_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _p, _p, _p, _p]),
+    "pe_stim_workspace_bytes": (_z, [_l]),
+    "pe_stim_phase": (_i, [_p, _p, _p, _p, _i, _p, _p, _z, _p]),
+    "pe_stim_synth": (_i, [_p, _p, _p, _p, _i, _p, _p]),
+    "pe_stim_tone": (_i, [_p, _p, _p, _i, _p, _p]),
+    "pe_stim_finish": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _z, _p]),
+    "pe_stim_reference": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "pe_dynamic_metrics_fields": (_i, []),
+    "pe_dynamic_metrics": (_i, [_p, _p, _p, _p, _i, _p, _p]),
 }
 
 

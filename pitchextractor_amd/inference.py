@@ -483,10 +483,10 @@ def melody_metrics(pred, ref, baseline=None, voicing_threshold_hz: float = 10.0,
 @torch.no_grad()
 def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voicing_threshold_hz: float = 10.0,
                  batched: bool = False, **predict_kwargs) -> dict:
-    """The notebooks' sweep: ``items`` (a list of ``{"audio", "reference_f0"}`` at the model rate ``sr``, default the
-    mel front end's) are scored clean, then every ``stress.Condition`` degrades the whole set as one ragged batch on
-    the device and each degraded row goes through ``predict_f0`` (``predict_kwargs``: its keyword arguments; a
-    classifier needs a ``decoder``).  Returns ``{"baseline": [...], "conditions": [...]}``: one record per item, and
+    """The notebooks' sweep: ``items`` (``{"audio", "reference_f0"}`` each, arrays or device tensors, at the model rate
+    ``sr``, default the mel front end's) are scored clean, then every ``stress.Condition`` degrades the whole set as one
+    ragged batch on the device and each degraded row goes through ``predict_f0`` (``predict_kwargs``: its keyword
+    arguments; a classifier needs a ``decoder``).  Returns ``{"baseline": [...], "conditions": [...]}``: one record per item, and
     one per (condition, item) in order, each ``{"condition", "kind", "item"}`` plus ``melody_metrics``; a condition's
     ``VUV_flips`` is measured against the item's clean prediction, the baseline's own is 0.  ``batched=True``: the
     clean set and every degraded set go through ``predict_f0_batch(..., stitch="concat")`` without leaving the device;
@@ -494,12 +494,19 @@ def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voi
     from . import stress
     device = model.flat_parameters.device
     sr = int(sr or DEFAULT_MEL_PARAMS["sample_rate"])
-    waves = [np.ascontiguousarray(np.asarray(it["audio"], dtype=np.float32).reshape(-1)) for it in items]
-    refs = [np.asarray(it["reference_f0"], dtype=np.float32).reshape(-1) for it in items]
-    lengths = [int(w.size) for w in waves]
+
+    def track(x):                                       # device tensors (``stimuli.StimulusSet.items``) stay there
+        if isinstance(x, torch.Tensor):
+            return x.detach().reshape(-1).to(device, torch.float32)
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1)))
+
+    items = list(items)
+    waves = [track(it["audio"]) for it in items]
+    refs = [track(it["reference_f0"]) for it in items]
+    lengths = [int(w.numel()) for w in waves]
     batch = torch.zeros((len(waves), max(lengths, default=0)), dtype=torch.float32, device=device)
     for r, w in enumerate(waves):
-        batch[r, :w.size] = torch.from_numpy(w).to(device)
+        batch[r, :w.numel()] = w.to(device)
 
     def run(rows, row_lengths):
         if batched:
@@ -518,3 +525,98 @@ def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voi
         degraded, row_lengths = stress.apply_condition(cond, batch, sr, lengths)
         out["conditions"] += records(cond, run(degraded, row_lengths))
     return out
+
+
+# ------------------------------------------------------------------------------------------- synthesized-stimulus sweeps
+def _score_set(model, st, stitch, voicing_threshold_hz, predict_kwargs):
+    """One ``predict_f0_batch`` call over a ``stimuli.StimulusSet`` and its scores: ``(melody metrics, dynamic
+    metrics)``, the reference sampled at each prediction's own length as the notebooks do."""
+    from . import stimuli, stress
+    if model.num_class != 1 and predict_kwargs.get("decoder") is None:
+        raise ValueError("a classifier needs a decoder (predict_kwargs) to be scored in Hz")
+    device = model.flat_parameters.device
+    preds = predict_f0_batch(model, st.audio, st.lengths, **{"stitch": stitch, **predict_kwargs})
+    refs = st.reference_f0([int(p.numel()) for p in preds])
+    melody = stress.melody_metrics_rows(preds, refs, None, voicing_threshold_hz, device)
+    return melody, stimuli.dynamic_metrics_rows(preds, refs, device)
+
+
+def _frame_period_ms(predict_kwargs, sr) -> float:
+    tf = predict_kwargs.get("mel_transform") or _default_mel()
+    return tf.hop_length * 1000.0 / sr
+
+
+_MELODY_COLUMNS = ("RPA", "RCA", "VUV", "OctaveError")
+
+
+@torch.no_grad()
+def dynamic_pitch_sweep(model: JDCNet, *, sr: int | None = None, vibrato: dict | None = None, glide: dict | None = None,
+                        stitch: str = "concat", voicing_threshold_hz: float = 10.0, **predict_kwargs) -> dict:
+    """Utils/dynamic_pitch_behavior.ipynb without the host touching a sample: the vibrato grid and the glides are
+    synthesized on the device (``stimuli.vibratos``, ``stimuli.glides``; ``vibrato`` / ``glide``: the notebook's CONFIG
+    sections, default ``stimuli.VIBRATO_GRID`` / ``stimuli.GLIDE_GRID``), each set is one ``predict_f0_batch`` call
+    (``stitch="concat"`` is the notebooks' ``predict_f0``; ``predict_kwargs``: its other keyword arguments, a classifier
+    needs a ``decoder``) and the reference is sampled at the prediction's own length.  Returns ``{"vibrato": [...],
+    "glide": [...]}`` with the notebook's columns: ``rate_hz, depth_cents, RPA, RCA, VUV, OctaveError, RMSE_cents`` and
+    ``duration_s, RPA, RCA, VUV, OctaveError, RMSE_cents, Lag_ms, Overshoot_cents, Final_error_cents``."""
+    from . import stimuli
+    device = model.flat_parameters.device
+    sr = int(sr or DEFAULT_MEL_PARAMS["sample_rate"])
+    v, g = {**stimuli.VIBRATO_GRID, **(vibrato or {})}, {**stimuli.GLIDE_GRID, **(glide or {})}
+    period = _frame_period_ms(predict_kwargs, sr)
+    out = {"vibrato": [], "glide": []}
+    st = stimuli.vibratos([float(r) for r in v["rates_hz"]], [float(d) for d in v["depth_cents"]],
+                          float(v["base_frequency_hz"]), float(v["duration_seconds"]), sr, device=device)
+    melody, dynamic = _score_set(model, st, stitch, voicing_threshold_hz, predict_kwargs)
+    for label, m, d in zip(st.labels, melody, dynamic):
+        out["vibrato"].append(dict(rate_hz=label["rate_hz"], depth_cents=label["depth_cents"],
+                                   **{k: m[k] for k in _MELODY_COLUMNS}, RMSE_cents=d["RMSE_cents"]))
+    st = stimuli.glides([float(d) for d in g["durations_seconds"]], float(g["start_hz"]), float(g["end_hz"]), sr,
+                        device=device)
+    melody, dynamic = _score_set(model, st, stitch, voicing_threshold_hz, predict_kwargs)
+    for label, m, d in zip(st.labels, melody, dynamic):
+        out["glide"].append(dict(duration_s=label["duration_s"], **{k: m[k] for k in _MELODY_COLUMNS},
+                                 RMSE_cents=d["RMSE_cents"], Lag_ms=d["Lag_frames"] * period,
+                                 Overshoot_cents=d["Overshoot_cents"], Final_error_cents=d["Final_error_cents"]))
+    return out
+
+
+@torch.no_grad()
+def timbre_coverage_sweep(model: JDCNet, *, sr: int | None = None, ranges=None, profiles: dict | None = None,
+                          duration: float | None = None, frequencies_per_range: int | None = None,
+                          edge_band_fraction: float | None = None, seed: int | None = None, noise: str = "numpy",
+                          stitch: str = "concat", voicing_threshold_hz: float = 10.0, **predict_kwargs) -> dict:
+    """Utils/pitch_range_and_timbre_coverage.ipynb on the device: every range x frequency x timbre profile is one row of
+    one ``stimuli.timbre_tones`` set (the notebook's order, so the noisy profile draws the notebook's noise), scored by
+    one ``predict_f0_batch`` call.  Defaults: ``stimuli.VOCAL_RANGES``, ``stimuli.TIMBRE_PROFILES``,
+    ``stimuli.TIMBRE_STIMULUS``.  Returns ``{"records": [...], "per_range": {...}}``: records with the notebook's columns
+    ``range, frequency_hz, timbre, edge_region, RPA, RCA, VUV, OctaveError``, and per range the means
+    ``RPA_mean, RCA_mean, VUV_mean, OctaveError_mean`` (NaN records left out, as a data frame's mean leaves them)."""
+    from . import stimuli
+    device = model.flat_parameters.device
+    sr = int(sr or DEFAULT_MEL_PARAMS["sample_rate"])
+    cfg = stimuli.TIMBRE_STIMULUS
+    ranges = stimuli.VOCAL_RANGES if ranges is None else ranges
+    count = int(cfg["frequencies_per_range"] if frequencies_per_range is None else frequencies_per_range)
+    fraction = float(cfg["edge_band_fraction"] if edge_band_fraction is None else edge_band_fraction)
+    freqs, labels = [], []
+    for rng in ranges:
+        lo, hi = float(rng["min_hz"]), float(rng["max_hz"])
+        for f in stimuli.frequency_grid(lo, hi, count):
+            freqs.append(float(f))
+            labels.append({"range": rng["name"], "edge_region": stimuli.edge_region(float(f), lo, hi, fraction)})
+    st = stimuli.timbre_tones(freqs, profiles, float(cfg["duration_seconds"] if duration is None else duration), sr,
+                              int(cfg["random_seed"] if seed is None else seed), noise, device=device, labels=labels)
+    melody, _ = _score_set(model, st, stitch, voicing_threshold_hz, predict_kwargs)
+    records = [dict(range=label["range"], frequency_hz=label["frequency_hz"], timbre=label["timbre"],
+                    edge_region=label["edge_region"], **{k: m[k] for k in _MELODY_COLUMNS})
+               for label, m in zip(st.labels, melody)]
+    per_range = {}
+    for rng in ranges:
+        rows = [r for r in records if r["range"] == rng["name"]]
+        means = {}
+        for k in _MELODY_COLUMNS:
+            vals = [r[k] for r in rows if not np.isnan(r[k])]
+            means[k + "_mean"] = float(np.mean(vals)) if vals else float("nan")
+        per_range[rng["name"]] = means
+    return {"records": records, "per_range": per_range}
