@@ -725,6 +725,54 @@ int pe_dynamic_metrics_fields(void);
 int pe_dynamic_metrics(const float* f0_pred, const float* f0_ref, const long* tracks, const long* host_tracks,
                        int n_rows, double* out4, void* stream);
 
+/* ---- Additive noise at an SNR (what the reference's Utils/noise_robustness_evaluation.ipynb is meant to add), ragged
+ * batches ------------------------------------------------------------------------------------------------------------
+ * pe_noise_plan (host only): row r has n[r] >= 0 samples written at y + y_off[r], generated after warmup[r] >= 0
+ * samples that are run and not written, from seeds[r]; white_off[r] = the offset of the row's warmup + n given white
+ * samples in `white`, -1 for samples drawn in the kernel.  coeffs = {d0, d1, then (a, b) per section}, n_sections <= 8:
+ * the colour y[j] = d0 w[j] + d1 w[j - 1] + sum_k s_k[j], s_k[j] = a_k s_k[j - 1] + b_k w[j], w[-1] = s_k[-1] = 0.
+ * consts4 = {piece S = 2048, 8, doubles per row of `stats`, int64 per row of `beds`}; meta (n_rows x
+ * pe_noise_plan_fields() int64, to be copied to the device) = per row {offset, samples, warm-up, generated = warm-up +
+ * samples, pieces = ceil(generated / S) (0 for a row without samples), piece prefix, seed, white offset}; params
+ * (pe_noise_param_fields() doubles, to be copied to the device) = {d0, d1, sections, 0, then per section {a, b,
+ * a^(8 2^m) for m < 8, a^2048, 0}}, the powers by repeated multiplication and squaring in double; totals2 = {samples,
+ * pieces}.  PE_E_ARG: more than 8 sections, a non-finite coefficient, |a| >= 1, a negative length, warm-up or offset.
+ *
+ * Every entry point below checks its arguments and host_meta (the host copy of meta) before any device call, allocates
+ * nothing, and launches the same number of kernels whatever the rows; pieces are counted from a row's own first
+ * generated sample and combined in a fixed order, so a row's output is bit-identical alone, packed at any offset or
+ * padded.  Rows of length 0 are valid.  workspace: pe_noise_workspace_bytes(totals2[1]) (PE_E_WORKSPACE when missing
+ * or too small).
+ * pe_noise_white: y[i] = z(seed, warm-up + i), z(seed, j) the standard normal of pe_world_responses' drawn noise:
+ * Philox4x32-10 with key {seed lo, seed hi} and counter {j lo, j hi, 0, 0}, u1 = ((w0 >> 8) + 0.5) 2^-24, u2 =
+ * (w1 >> 8) 2^-24, sqrt(-2 ln u1) cos(2 pi u2) in float32.  One launch.
+ * pe_noise_colour: the colour of `params` (host_params its host copy; PE_E_ARG unless it is pe_noise_plan's) over
+ * w[j] = z(seed, j) or the given white[white offset + j] (n_white = floats in `white`), j < generated, in double,
+ * rounded once to float32; y[i] = sample warm-up + i.  A parallel scan: piece end states from a zero state, per-row
+ * carries in piece order, the pieces again from their carries.  Three launches.
+ * pe_noise_bed: y[i] = bed[offset + (start + i) mod L] with beds (n_rows x 3 int64; host_beds its host copy) = per row
+ * {offset in `bed`, L >= 1, 0 <= start < L}; n_bed = floats in `bed`.  PE_E_ARG for a bed outside it.  One launch.
+ * pe_noise_mix: x, noise and y share the plan's offsets.  rms_s, rms_n in double over the float32 samples of the row,
+ * scale = float32((rms_s / 10^(snr_db / 20)) / rms_n), y = x + float32(noise scale) in float32; y = x and scale = 0
+ * when either rms is 0.  With peak = max |y|: y = y / float32(peak + 1e-6) if peak_normalize and peak > 0.99.
+ * stats[r] = {peak, rms_s, rms_n, scale}, all 0 for a row of length 0.  snr_db: one double per row on the device,
+ * host_snr_db its host copy, PE_E_ARG unless every one is finite.  Five launches (four without peak_normalize). */
+int pe_noise_plan_fields(void);
+int pe_noise_param_fields(void);
+int pe_noise_plan(int n_rows, const long* n, const long* y_off, const long* warmup, const long* seeds,
+                  const long* white_off, const double* coeffs, int n_sections, long* consts4, long* meta,
+                  double* params, long* totals2);
+size_t pe_noise_workspace_bytes(long pieces);
+int pe_noise_white(const long* meta, const long* host_meta, int n_rows, float* y, void* stream);
+int pe_noise_colour(const long* meta, const long* host_meta, const double* params, const double* host_params,
+                    const float* white, long n_white, int n_rows, float* y, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int pe_noise_bed(const long* meta, const long* host_meta, const float* bed, long n_bed, const long* beds,
+                 const long* host_beds, int n_rows, float* y, void* stream);
+int pe_noise_mix(const float* x, const float* noise, const long* meta, const long* host_meta, const double* snr_db,
+                 const double* host_snr_db, int peak_normalize, int n_rows, float* y, double* stats, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,14 @@ PROTOTYPES = {
     "pe_stim_reference": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
     "pe_dynamic_metrics_fields": (_i, []),
     "pe_dynamic_metrics": (_i, [_p, _p, _p, _p, _i, _p, _p]),
+    "pe_noise_plan_fields": (_i, []),
+    "pe_noise_param_fields": (_i, []),
+    "pe_noise_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "pe_noise_workspace_bytes": (_z, [_l]),
+    "pe_noise_white": (_i, [_p, _p, _i, _p, _p]),
+    "pe_noise_colour": (_i, [_p, _p, _p, _p, _p, _l, _i, _p, _p, _z, _p]),
+    "pe_noise_bed": (_i, [_p, _p, _p, _l, _p, _p, _i, _p, _p]),
+    "pe_noise_mix": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _z, _p]),
 }
 
 

@@ -1,10 +1,11 @@
-// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip, stress.hip) share.
+// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip, stress.hip,
+// stimuli.hip, noise.hip) share.
 // Host: the row bound and the launch-grid clamps of the ragged entry points, the header every row plan opens with, the
 // gate every entry point that takes a host plan passes before its own checks (open_rows, kNothing, PE_OPEN), the size
 // of the transform roots every table opens with, and with_log2 (transform size -> kernel instance).  Device: float2
 // complex arithmetic, the wave-private LDS fence, the in-place radix-4 Stockham FFT in LDS, a packed half-length
 // transform's bins as the real one's and back (real_fft_split, real_fft_bin, real_fft_pack), the 256-thread workgroup
-// reductions in a fixed order, and the row search of ragged plans.
+// reductions in a fixed order, the seeded standard normal (world_randn), and the row search of ragged plans.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -198,6 +199,16 @@ __device__ __forceinline__ float block_max(float v, float* s_red, int tid) {
   if ((tid & 63) == 0) s_red[tid >> 6] = v;
   __syncthreads();
   return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+}
+
+// Standard normal for sample i of a row (world_synth.hip's pulse noise, noise.hip): Philox4x32-10 keyed by (seed, i),
+// words 0 and 1, Box-Muller in float32.  A row's draws depend on its seed and the sample index alone.
+__device__ __forceinline__ float world_randn(uint64_t seed, uint64_t i) {
+  uint32_t w[4];
+  philox4(seed, i, w);
+  const float u1 = ((float)(w[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);       // (0, 1)
+  const float u2 = (float)(w[1] >> 8) * (1.0f / 16777216.0f);                // [0, 1)
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
 
 // Largest row whose prefix offset meta[row][field] <= g, in a plan of `fields` int64 per row (rows with no work share

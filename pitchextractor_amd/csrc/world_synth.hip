@@ -37,15 +37,6 @@ enum {
 enum { P_INDEX, P_LO, P_HI, P_NS, P_VOICED, P_ROW, P_K };
 enum { F_FRAC, F_SHIFT, F_K };
 
-// standard normal for sample i of a row: Philox4x32-10 keyed by (seed, i), Box-Muller in float32
-__device__ __forceinline__ float world_randn(uint64_t seed, uint64_t i) {
-  uint32_t w[4];
-  philox4(seed, i, w);
-  const float u1 = ((float)(w[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);       // (0, 1)
-  const float u2 = (float)(w[1] >> 8) * (1.0f / 16777216.0f);                // [0, 1)
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
-
 __device__ __forceinline__ float2 cexp2(float2 z) {           // exp(z), full-accuracy exp / sin / cos
   float s, c;
   sincosf(z.y, &s, &c);

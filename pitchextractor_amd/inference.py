@@ -527,6 +527,73 @@ def stress_sweep(model: JDCNet, items, conditions, *, sr: int | None = None, voi
     return out
 
 
+SUMMARY_METRICS = ("RPA", "RCA", "VUV", "OctaveError")
+_LOWER_IS_BETTER = ("OctaveError",)
+
+
+def summarize_with_drop(records, baseline_records, group_keys, metrics=SUMMARY_METRICS) -> list:
+    """The summary table the evaluation notebooks print under every sweep (Utils/codec_and_bandwidth_torture.ipynb's
+    ``_summarize_with_drop``), on the host: the records (of ``stress_sweep`` or any list of dicts) grouped by
+    ``group_keys``, one row per group in order of first appearance with the group's keys and per metric
+    ``<metric>_mean`` (NaN left out), ``<metric>_std`` (NaN left out, ddof 1, NaN below two values) and
+    ``<metric>_drop`` against the NaN-skipping mean over ``baseline_records``: baseline - mean where higher is better,
+    mean - baseline for ``OctaveError``."""
+    group_keys = [group_keys] if isinstance(group_keys, str) else list(group_keys)
+
+    def column(rows, metric):
+        vals = np.asarray([float(r[metric]) for r in rows], dtype=np.float64)
+        return vals[~np.isnan(vals)]
+
+    baseline = {}
+    for metric in metrics:
+        vals = column(baseline_records, metric)
+        baseline[metric] = float(np.mean(vals)) if vals.size else float("nan")
+    groups = {}
+    for rec in records:
+        groups.setdefault(tuple(rec[k] for k in group_keys), []).append(rec)
+    table = []
+    for key, rows in groups.items():
+        line = dict(zip(group_keys, key))
+        for metric in metrics:
+            vals = column(rows, metric)
+            line[metric + "_mean"] = float(np.mean(vals)) if vals.size else float("nan")
+            line[metric + "_std"] = float(np.std(vals, ddof=1)) if vals.size >= 2 else float("nan")
+        for metric in metrics:
+            mean = line[metric + "_mean"]
+            line[metric + "_drop"] = mean - baseline[metric] if metric in _LOWER_IS_BETTER else baseline[metric] - mean
+        table.append(line)
+    return table
+
+
+def noise_sweep(model: JDCNet, items, snrs_db=(30, 20, 10, 5, 0, -5), sources=("white", "pink", "brown"), seed=0,
+                batched: bool = True, **predict_kwargs) -> dict:
+    """The noise-robustness curve (what the reference's Utils/noise_robustness_evaluation.ipynb is meant to draw): one
+    ``stress.Condition("additive_noise", ...)`` per (source, SNR), sources outermost, run by ``stress_sweep`` (its
+    ``items``, ``batched`` and other keyword arguments).  ``sources``: colour names or custom colours of
+    ``noise.colour_sections``, ``noise.NoiseSet`` beds, or ``(name, source)`` pairs; item r of every condition draws its
+    noise from ``seed + r``.  Returns ``stress_sweep``'s dict, whose condition records also carry ``source`` and
+    ``snr_db``, plus ``"summary"``: ``summarize_with_drop`` of them by ``("source", "snr_db")``."""
+    from . import stress
+    conditions, labels = [], {}
+    for k, source in enumerate(sources):
+        if isinstance(source, tuple) and len(source) == 2 and isinstance(source[0], str):
+            name, source = source
+        else:
+            name = source if isinstance(source, str) else f"source {k}"
+        for snr in snrs_db:
+            cond = stress.Condition("additive_noise", f"{name} {float(snr):g} dB", snr_db=float(snr), source=source,
+                                    seed=seed)
+            conditions.append(cond)
+            labels[cond.label] = (name, float(snr))
+    if len(labels) != len(conditions):
+        raise ValueError("noise_sweep: two conditions share a source name and an SNR")
+    out = stress_sweep(model, items, conditions, batched=batched, **predict_kwargs)
+    for rec in out["conditions"]:
+        rec["source"], rec["snr_db"] = labels[rec["condition"]]
+    out["summary"] = summarize_with_drop(out["conditions"], out["baseline"], ("source", "snr_db"))
+    return out
+
+
 # ------------------------------------------------------------------------------------------- synthesized-stimulus sweeps
 def _score_set(model, st, stitch, voicing_threshold_hz, predict_kwargs):
     """One ``predict_f0_batch`` call over a ``stimuli.StimulusSet`` and its scores: ``(melody metrics, dynamic

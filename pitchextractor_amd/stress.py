@@ -1,7 +1,8 @@
 """Robustness stress conditions of the reference's evaluation notebooks on the device (``csrc/stress.hip``): room
 impulse responses and microphone colouration (Utils/room_and_microphone_stress.ipynb), sample clipping and AGC pumping
-(Utils/amplitude_pathologies.ipynb) and the down/up resample (Utils/codec_and_bandwidth_torture.ipynb).  There is no CPU
-path.  ``tests/stress_ref.py`` is the float64 restatement that pins every one of them.
+(Utils/amplitude_pathologies.ipynb), the down/up resample (Utils/codec_and_bandwidth_torture.ipynb) and additive noise
+at an SNR (``noise.py``).  There is no CPU path.  ``tests/stress_ref.py`` (the noise: ``tests/noise_ref.py``) is the
+float64 restatement that pins every one of them.
 
 Every condition takes a ragged batch the way the F0 trackers do (``ragged.device_plan``): a 1-D wave of rows packed back
 to back with ``lengths``, or a padded 2-D batch.  The result has the input's shape (dense; zero outside the rows) and a
@@ -31,7 +32,7 @@ MICROPHONE_PROFILES = {
     "studio_ldc": ({"freq": 80.0, "gain_db": 2.0, "Q": 0.9}, {"freq": 4500.0, "gain_db": -1.5, "Q": 1.3},
                    {"freq": 12000.0, "gain_db": 1.5, "Q": 0.9}),
 }
-CONDITION_KINDS = ("rir", "microphone", "clipping", "agc", "resample")
+CONDITION_KINDS = ("rir", "microphone", "clipping", "agc", "resample", "additive_noise")
 POLE_RADIUS_LIMIT = 1.0 - 1e-9
 
 
@@ -39,11 +40,16 @@ class Condition:
     """One stress condition of a sweep: ``Condition(kind, label, **params)``, ``kind`` one of ``CONDITION_KINDS``.
     params -- rir: ``rirs`` (a ``RirSet``), ``rir_index`` (an int, or one per item); microphone: ``curve`` (a name in
     ``MICROPHONE_PROFILES`` or a list of stages); clipping: ``percent``; agc: ``level_db`` [, ``target_rms``];
-    resample: ``target_rate``."""
+    resample: ``target_rate``; additive_noise: ``snr_db`` [, ``source`` (a colour of ``noise.colour_sections`` or a
+    ``noise.NoiseSet``; default white), ``seed``, ``bed_index``, ``bed_start``, ``warmup``, ``peak_normalize``].  An
+    additive_noise condition is checked here: ``ValueError`` for a missing or non-finite ``snr_db`` or an unknown
+    ``source``."""
 
     def __init__(self, kind: str, label: str, **params):
         if kind not in CONDITION_KINDS:
             raise ValueError(f"Condition: kind {kind!r} is not one of {CONDITION_KINDS}")
+        if kind == "additive_noise":
+            _check_noise_condition(params)
         self.kind, self.label, self.params = kind, str(label), dict(params)
 
     def __repr__(self):
@@ -51,6 +57,17 @@ class Condition:
 
 
 # ------------------------------------------------------------------------------------------------------------ host side
+def _check_noise_condition(params: dict) -> None:
+    from . import noise
+    if "snr_db" not in params:
+        raise ValueError("Condition: an additive_noise condition needs snr_db")
+    if not np.all(np.isfinite(np.asarray(params["snr_db"], dtype=np.float64))):
+        raise ValueError(f"Condition: snr_db must be finite, got {params['snr_db']!r}")
+    source = params.get("source", "white")
+    if not isinstance(source, noise.NoiseSet):
+        noise.colour_sections(source, 24000)               # ValueError for what is not a colour
+
+
 def prepare_rir(audio) -> np.ndarray:
     """The notebook's load-time normalisation of an impulse response, ``audio / (max|audio| + 1e-6)`` in float32."""
     a = np.asarray(audio, dtype=np.float32).reshape(-1)
@@ -312,6 +329,28 @@ def apply_resample_condition(x: torch.Tensor, sr: int, target_rate: int, lengths
     return up, [_RESAMPLERS[sr].out_len(target_rate, n) for n in down_lengths]
 
 
+def apply_additive_noise(x: torch.Tensor, sr, snr_db, source="white", seed=0, bed_index=0, bed_start=0,
+                         warmup: int = 4096, lengths=None, peak_normalize: bool = True, return_stats: bool = False):
+    """Noise added to every row at ``snr_db`` (a number, or one per row) over the whole row (``noise.mix_at_snr``): the
+    condition the reference's Utils/noise_robustness_evaluation.ipynb is meant to apply.  ``source``: a colour name
+    (``noise.NOISE_COLOURS``) or a custom colour, drawn on the device with row r seeded ``seed + r`` (or ``seed[r]``)
+    after ``warmup`` settling samples; or a ``noise.NoiseSet``, row r looping recording ``bed_index`` from its sample
+    ``bed_start`` (numbers, or one per row).  ``peak_normalize``: the notebooks' ``max|y| > 0.99`` rule.
+    ``return_stats``: also the ``(rows, 4)`` float64 ``noise.STAT_KEYS``.  Six to eight launches."""
+    from . import noise
+    check_waves(x, "apply_additive_noise")
+    x = x.contiguous()
+    row_lengths, offsets = row_layout(x, lengths, whole_by_default=True)
+    flat = torch.zeros((max(x.numel(), 1),), dtype=torch.float32, device=x.device)
+    if isinstance(source, noise.NoiseSet):
+        noise.bed(source, row_lengths, bed_index, bed_start, offsets=offsets, out=flat)
+    elif source == "white":
+        noise.white(row_lengths, seed, offsets=offsets, out=flat)
+    else:
+        noise.coloured(row_lengths, source, sr, seeds=seed, warmup=warmup, offsets=offsets, out=flat)
+    return noise.mix_at_snr(x, flat[:x.numel()].view(x.shape), snr_db, lengths, peak_normalize, return_stats)
+
+
 def apply_condition(cond: Condition, x: torch.Tensor, sr: int, lengths=None):
     """``(y, lengths)`` of one ``Condition`` on a ragged batch."""
     row_lengths, _ = row_layout(x, lengths, whole_by_default=True)
@@ -324,6 +363,10 @@ def apply_condition(cond: Condition, x: torch.Tensor, sr: int, lengths=None):
         return apply_sample_clipping(x, p["percent"], lengths), row_lengths
     if cond.kind == "agc":
         return apply_agc_pumping(x, p["level_db"], sr, p.get("target_rms", 0.15), lengths), row_lengths
+    if cond.kind == "additive_noise":
+        return apply_additive_noise(x, sr, p["snr_db"], p.get("source", "white"), p.get("seed", 0),
+                                    p.get("bed_index", 0), p.get("bed_start", 0), p.get("warmup", 4096), lengths,
+                                    p.get("peak_normalize", True)), row_lengths
     return apply_resample_condition(x, sr, p["target_rate"], lengths)
 
 
