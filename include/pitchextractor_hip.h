@@ -259,6 +259,22 @@ int pe_maxpool_fwd(int act16, const void* x, void* y, long rows, int Fin, int C,
                    unsigned char* argmax_out, void* stream);
 int pe_maxpool_bwd_add(int act16, const void* x, const unsigned char* argmax, const void* dy, void* dx, long rows,
                        int Fin, int C, int pool, long lddy, int coff, unsigned* amax_out, void* stream);
+/* A detector tap folded into the BN passes of the block that reads the same tensor: one read of x leaves y / amax_out as
+ * pe_bn_act_pool_fwd does AND the plain max-pool of x over tap_pool (at tap_y[(row*(Fin/tap_pool) + w)*tap_ldy +
+ * tap_coff + c]) with its positions (tap_arg, optional) as pe_maxpool_fwd does; the backward writes dx with the tap
+ * gradient already added and amax_out as pe_bn_act_pool_bwd followed by pe_maxpool_bwd_add(argmax = tap_arg) leave
+ * them.  Bit for bit the two passes they replace.  Served (pe_bn_act_pool_tap_supported = 1, else PE_E_UNSUPPORTED):
+ * pool in {1, 2, 4}, tap_pool % pool == 0, Fin % tap_pool == 0, tap_pool <= 255 when positions are wanted, rows * Fin
+ * below 2^31, and the alignment of the plain passes. */
+int pe_bn_act_pool_tap_supported(long rows, int Fin, int C, int pool, int tap_pool, int with_arg);
+int pe_bn_act_pool_tap_fwd(int act16, const void* x, const float* scale, const float* shift, float slope, void* y,
+                           long rows, int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out, void* tap_y,
+                           long tap_ldy, int tap_coff, int tap_pool, unsigned char* tap_arg, void* stream);
+int pe_bn_act_pool_tap_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
+                           const float* mean, const float* invstd, float slope, void* dx, float* dgamma, float* dbeta,
+                           long rows, int Fin, int C, int pool, long lddy, int coff, void* workspace,
+                           size_t workspace_bytes, unsigned* amax_out, const void* tap_dy, long tap_lddy, int tap_coff,
+                           int tap_pool, const unsigned char* tap_arg, void* stream);
 /* nn.Dropout (model.py:40,56; LSTM inter-layer): Philox4x32-10 keyed by (seed, offset + quad index);
  * mask bytes (1 = kept) can be exported (mask_out) or replayed (mask_in). */
 int pe_dropout_fwd(int act16, const void* x, long ldx, void* y, long ldy, const unsigned char* mask_in,

@@ -168,6 +168,94 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const TA* __restri
   amax_commit(am, amax);
 }
 
+// The same pass with a detector tap folded in: the plain MaxPool(1, tap_pool) of the raw x it reads anyway, written at
+// tap_y[tw*tap_ldy + tap_coff + c] (tw = row*Fo_tap + w), and the window position of each maximum at tap_arg[tw*C + c],
+// exactly as maxpool_fwd_kernel leaves them (strict > scanning upwards: the first maximum wins, value = the x bits).
+// Fin % tap_pool == 0 and tap_pool % POOL == 0, so tap window tw is the x pixels [tw*tap_pool, (tw+1)*tap_pool) and the
+// BN windows [tw*nbw, (tw+1)*nbw): no division anywhere.  A tap window is cut into S segments of segw = nbw / S BN
+// windows; pixel lane g of a trip owns segment g % S of tap window trip*TW + g / S (TW = G / S windows per trip; the
+// host picks S so that TW*S fills the lanes).  Every lane scans its segment upwards, the (value, position) pairs meet
+// in LDS and the lane of segment 0 folds them in segment order with the same strict >, which keeps the first-maximum
+// rule (a later segment starts from -inf, so a NaN inside a window is skipped and one at position 0 sticks, as in the
+// serial scan).  The LDS buffers alternate by trip: one barrier per trip.
+template <int POOL, class TA>
+__global__ __launch_bounds__(256) void bn_act_pool_tap_fwd_kernel(const TA* __restrict__ x,
+                                                                  const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, float slope,
+                                                                  TA* __restrict__ y, long n_tap, int C, int nbw, int S,
+                                                                  long ldy, int coff, unsigned* __restrict__ amax,
+                                                                  TA* __restrict__ tap_y, long tap_ldy, int tap_coff,
+                                                                  unsigned char* __restrict__ tap_arg) {
+  __shared__ float4 tap_val[2][256];
+  __shared__ uchar4 tap_pos[2][256];
+  const int quads = C >> 2;
+  const int G = 256 / quads, q = threadIdx.x % quads, g = threadIdx.x / quads;
+  const int TW = G / S, segw = nbw / S;
+  const int wl = g / S, seg = g - wl * S;
+  const bool lane_on = g < TW * S;
+  const float4 sc = *reinterpret_cast<const float4*>(scale + q * 4), sh = *reinterpret_cast<const float4*>(shift + q * 4);
+  const long n_trips = (n_tap + TW - 1) / TW;
+  float am = 0.f;
+  int buf = 0;
+  for (long trip = blockIdx.x; trip < n_trips; trip += gridDim.x, buf ^= 1) {
+    const long tw = trip * TW + wl;
+    const bool on = lane_on && tw < n_tap;
+    const float ninf = -__builtin_inff();
+    float4 tm = make_float4(ninf, ninf, ninf, ninf);
+    int a0 = seg * segw * POOL, a1 = a0, a2 = a0, a3 = a0;
+    if (on) {
+      const long op0 = tw * nbw + (long)seg * segw;
+      const TA* xp = x + (op0 * POOL * C + q * 4);
+      TA* yp = y + (op0 * ldy + coff + q * 4);
+      int pos = seg * segw * POOL;
+      bool first = seg == 0;                                       // the scan of a window starts AT its first element
+      for (int i = 0; i < segw; ++i, xp += (long)POOL * C, yp += ldy) {
+        float4 v[POOL];
+#pragma unroll
+        for (int j = 0; j < POOL; ++j) v[j] = ld4(xp + (long)j * C);
+        float4 m;
+#pragma unroll
+        for (int j = 0; j < POOL; ++j, ++pos) {
+          float4 a;
+          a.x = lrelu(fmaf(v[j].x, sc.x, sh.x), slope);
+          a.y = lrelu(fmaf(v[j].y, sc.y, sh.y), slope);
+          a.z = lrelu(fmaf(v[j].z, sc.z, sh.z), slope);
+          a.w = lrelu(fmaf(v[j].w, sc.w, sh.w), slope);
+          if (j == 0) m = a;
+          else { m.x = fmaxf(m.x, a.x); m.y = fmaxf(m.y, a.y); m.z = fmaxf(m.z, a.z); m.w = fmaxf(m.w, a.w); }
+          if (first || v[j].x > tm.x) { tm.x = v[j].x; a0 = pos; }
+          if (first || v[j].y > tm.y) { tm.y = v[j].y; a1 = pos; }
+          if (first || v[j].z > tm.z) { tm.z = v[j].z; a2 = pos; }
+          if (first || v[j].w > tm.w) { tm.w = v[j].w; a3 = pos; }
+          first = false;
+        }
+        st4(yp, m);
+        am = amax4(am, m);
+      }
+      if (S > 1) {
+        tap_val[buf][threadIdx.x] = tm;
+        tap_pos[buf][threadIdx.x] = make_uchar4((unsigned char)a0, (unsigned char)a1, (unsigned char)a2, (unsigned char)a3);
+      }
+    }
+    if (S > 1) __syncthreads();
+    if (on && seg == 0) {
+      for (int k = 1; k < S; ++k) {                                // segments in window order: a tie stays with the lower one
+        const float4 o = tap_val[buf][threadIdx.x + k * quads];
+        const uchar4 p = tap_pos[buf][threadIdx.x + k * quads];
+        if (o.x > tm.x) { tm.x = o.x; a0 = p.x; }
+        if (o.y > tm.y) { tm.y = o.y; a1 = p.y; }
+        if (o.z > tm.z) { tm.z = o.z; a2 = p.z; }
+        if (o.w > tm.w) { tm.w = o.w; a3 = p.w; }
+      }
+      st4(tap_y + tw * tap_ldy + tap_coff + q * 4, tm);
+      if (tap_arg != nullptr)
+        *reinterpret_cast<uchar4*>(tap_arg + tw * C + q * 4) = make_uchar4((unsigned char)a0, (unsigned char)a1,
+                                                                           (unsigned char)a2, (unsigned char)a3);
+    }
+  }
+  amax_commit(am, amax);
+}
+
 // dz for the input pixel (row, f) of a BN->LReLU->MaxPool block, recomputed from x and dy.
 // The max-pool routes dy to the FIRST maximum of each window (torch max_pool2d backward).
 __device__ __forceinline__ float dz_one(const float* __restrict__ xwin, long cstride, int j, int pool, float sc,
@@ -348,6 +436,28 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_win_kernel(const BnBwdArgs
       n_items, a.C, partial);
 }
 
+// The gradient of a detector tap (the plain MaxPool(1, tap_pool) of x, see bn_act_pool_tap_fwd_kernel) for the apply pass
+// to add to the dx it writes: dy of tap window tw at dy[tw*lddy + coff + c], the position of its maximum at arg[tw*C + c].
+template <class TA>
+struct BnTapGrad {
+  const TA* dy;
+  const unsigned char* arg;
+  long lddy;
+  int coff;
+  unsigned nbw;         // BN windows per tap window (tap_pool / POOL)
+};
+
+// stored element + tap gradient as the separate pass adds them: the element rounded to its storage type first, and an
+// add of its own (fused into the multiply that produced dx it would round once instead of twice)
+__device__ __forceinline__ float round_act(const float*, float v) { return v; }
+__device__ __forceinline__ float round_act(const act16_t*, float v) {          // what st4 stores, widened again
+  return __uint_as_float(pack_bf16_rne(v, 0.f) << 16);
+}
+__device__ __forceinline__ float add_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 template <int POOL, class TA>
 __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BnBwdArgsT<TA> a, long n_items, int nwin,
                                                                const float* __restrict__ c1,
@@ -372,6 +482,49 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BnBwdArgsT<
       o.w = sc.w * (w.dz[j].w - k1.w - (w.v[j].w - mu.w) * is.w * k2.w);
       st4(dx + (w.p0 + j) * a.C + c, o);
       am = amax4(am, o);
+    }
+  }
+  amax_commit(am, amax);
+}
+
+// The same apply pass with the tap's gradient added to the element it belongs to.  Fin % tap_pool == 0 and
+// n_items < 2^31 (the host checks both), so BN window `item` of the whole tensor lies in tap window item / nbw, at
+// positions pos0 .. pos0 + POOL - 1 of it.
+template <int POOL, class TA>
+__global__ __launch_bounds__(256) void bn_bwd_apply_win_tap_kernel(const BnBwdArgsT<TA> a, long n_items, int nwin,
+                                                                   const float* __restrict__ c1,
+                                                                   const float* __restrict__ c2, TA* __restrict__ dx,
+                                                                   unsigned* __restrict__ amax, const BnTapGrad<TA> t) {
+  const int quads = a.C >> 2;
+  float am = 0.f;
+  const int G = 256 / quads, c = (threadIdx.x % quads) * 4, g = threadIdx.x / quads;     // see bn_act_pool_fwd_kernel
+  const float4 mu = *reinterpret_cast<const float4*>(a.mean + c), is = *reinterpret_cast<const float4*>(a.invstd + c);
+  const float4 sc = *reinterpret_cast<const float4*>(a.scale + c), sh = *reinterpret_cast<const float4*>(a.shift + c);
+  const float4 k1 = *reinterpret_cast<const float4*>(c1 + c), k2 = *reinterpret_cast<const float4*>(c2 + c);
+  for (long item = (long)blockIdx.x * G + g; g < G && item < n_items; item += (long)gridDim.x * G) {
+    BnWindow<POOL> w;
+    bn_window<POOL, TA>(a, item, nwin, c, w, sc, sh);
+    const unsigned tw = (unsigned)item / t.nbw;
+    const int pos0 = (int)((unsigned)item - tw * t.nbw) * POOL;
+    const uchar4 ar = *reinterpret_cast<const uchar4*>(t.arg + (long)tw * a.C + c);
+    const float4 tg = ld4(t.dy + (long)tw * t.lddy + t.coff + c);
+#pragma unroll
+    for (int j = 0; j < POOL; ++j) {
+      if (j >= w.n) break;
+      float4 o;
+      o.x = sc.x * (w.dz[j].x - k1.x - (w.v[j].x - mu.x) * is.x * k2.x);
+      o.y = sc.y * (w.dz[j].y - k1.y - (w.v[j].y - mu.y) * is.y * k2.y);
+      o.z = sc.z * (w.dz[j].z - k1.z - (w.v[j].z - mu.z) * is.z * k2.z);
+      o.w = sc.w * (w.dz[j].w - k1.w - (w.v[j].w - mu.w) * is.w * k2.w);
+      // the two steps this replaces, value for value: dx is stored (rounded to TA) and its word takes |dx|; then the
+      // tap pass reads the stored element back, adds its gradient, stores again and merges |dx + g| into the word
+      am = amax4(am, o);
+      const int pj = pos0 + j;
+      if (ar.x == pj) { o.x = add_unfused(round_act(dx, o.x), tg.x); am = fmaxf(am, fabsf(o.x)); }
+      if (ar.y == pj) { o.y = add_unfused(round_act(dx, o.y), tg.y); am = fmaxf(am, fabsf(o.y)); }
+      if (ar.z == pj) { o.z = add_unfused(round_act(dx, o.z), tg.z); am = fmaxf(am, fabsf(o.z)); }
+      if (ar.w == pj) { o.w = add_unfused(round_act(dx, o.w), tg.w); am = fmaxf(am, fabsf(o.w)); }
+      st4(dx + (w.p0 + j) * a.C + c, o);
     }
   }
   amax_commit(am, amax);
@@ -723,7 +876,7 @@ template <class TA>
 static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, const float* shift, const float* mean,
                                 const float* invstd, float slope, TA* dx, float* dgamma, float* dbeta, long rows,
                                 int Fin, int C, int pool, long lddy, int coff, void* workspace, size_t workspace_bytes,
-                                unsigned* amax_out, void* stream) {
+                                unsigned* amax_out, void* stream, const BnTapGrad<TA>* tap = nullptr) {
   if (!x || !dy || !scale || !shift || !mean || !invstd || !dx || !dgamma || !dbeta || rows <= 0) return PE_E_ARG;
   if (!bn_channels_ok(C) || (lddy & 3) || (coff & 3) || pool <= 0) return PE_E_UNSUPPORTED;
   const size_t need = pe_bn_workspace_bytes(C) + 2 * (size_t)C * sizeof(float);
@@ -754,7 +907,17 @@ static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, c
                      dgamma, dbeta, c1, c2);
   PE_LAUNCH_CHECK();
   const int agrid = win ? ew_grid(pe_cdiv(n_items, 256 / (C / 4)) * 256L) : ew_grid(a.n_in_pix * (C / 4));
-  if (pool == 1)
+  if (tap != nullptr) {                  // (the caller checked tap_geometry_ok: pool is 1, 2 or 4)
+    if (pool == 1)
+      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<1, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2,
+                         dx, amax_out, *tap);
+    else if (pool == 2)
+      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<2, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2,
+                         dx, amax_out, *tap);
+    else
+      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<4, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2,
+                         dx, amax_out, *tap);
+  } else if (pool == 1)
     hipLaunchKernelGGL((bn_bwd_apply_win_kernel<1, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2, dx,
                        amax_out);
   else if (pool == 2)
@@ -778,6 +941,83 @@ extern "C" int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, cons
     return bn_act_pool_bwd_impl(static_cast<const TA*>(x), static_cast<const TA*>(dy), scale, shift, mean, invstd, slope,
                                 static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, workspace,
                                 workspace_bytes, amax_out, stream);
+  });
+}
+
+// ---- detector tap folded into the BN passes (pe_bn_act_pool_tap_*)
+// What the two tap kernels serve: whole tap windows made of whole BN windows, positions that fit a byte, and a tensor
+// whose BN-window count fits the 32-bit division of the apply pass.
+static bool tap_geometry_ok(long rows, int Fin, int C, int pool, int tap_pool, bool with_arg) {
+  if (!bn_channels_ok(C) || rows <= 0 || Fin <= 0) return false;
+  if (pool != 1 && pool != 2 && pool != 4) return false;
+  if (tap_pool <= 0 || tap_pool % pool != 0 || Fin % tap_pool != 0) return false;
+  if (with_arg && tap_pool > 255) return false;
+  return rows * (long)Fin < (1L << 31);
+}
+
+extern "C" int pe_bn_act_pool_tap_supported(long rows, int Fin, int C, int pool, int tap_pool, int with_arg) {
+  return tap_geometry_ok(rows, Fin, C, pool, tap_pool, with_arg != 0) ? 1 : 0;
+}
+
+template <class TA>
+static int bn_act_pool_tap_fwd_impl(const TA* x, const float* scale, const float* shift, float slope, TA* y, long rows,
+                                    int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out, TA* tap_y,
+                                    long tap_ldy, int tap_coff, int tap_pool, unsigned char* tap_arg, void* stream) {
+  if (!x || !scale || !shift || !y || !tap_y || rows <= 0 || Fin <= 0 || pool <= 0) return PE_E_ARG;
+  if ((ldy & 3) || (coff & 3) || (tap_ldy & 3) || (tap_coff & 3) ||
+      !tap_geometry_ok(rows, Fin, C, pool, tap_pool, tap_arg != nullptr))
+    return PE_E_UNSUPPORTED;
+  const int G = 256 / (C / 4), nbw = tap_pool / pool;
+  // segments per tap window: fill the pixel lanes (TW * S of G), then prefer the shorter segments
+  int S = 1, used = 0;
+  for (int s = 1; s <= G && s <= nbw; ++s) {
+    if (nbw % s) continue;
+    const int u = (G / s) * s;
+    if (u >= used) { used = u; S = s; }
+  }
+  const long n_tap = rows * (Fin / tap_pool), n_trips = pe_cdiv(n_tap, (long)(G / S));
+  const dim3 grid(ew_grid(n_trips * 256L));
+  hipStream_t st = pe_stream(stream);
+  if (pool == 1)
+    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<1, TA>), grid, dim3(256), 0, st, x, scale, shift, slope, y, n_tap, C,
+                       nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
+  else if (pool == 2)
+    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<2, TA>), grid, dim3(256), 0, st, x, scale, shift, slope, y, n_tap, C,
+                       nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
+  else
+    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<4, TA>), grid, dim3(256), 0, st, x, scale, shift, slope, y, n_tap, C,
+                       nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
+  PE_LAUNCH_CHECK();
+  return PE_OK;
+}
+
+extern "C" int pe_bn_act_pool_tap_fwd(int act16, const void* x, const float* scale, const float* shift, float slope,
+                                      void* y, long rows, int Fin, int C, int pool, long ldy, int coff,
+                                      unsigned* amax_out, void* tap_y, long tap_ldy, int tap_coff, int tap_pool,
+                                      unsigned char* tap_arg, void* stream) {
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return bn_act_pool_tap_fwd_impl(static_cast<const TA*>(x), scale, shift, slope, static_cast<TA*>(y), rows, Fin, C,
+                                    pool, ldy, coff, amax_out, static_cast<TA*>(tap_y), tap_ldy, tap_coff, tap_pool,
+                                    tap_arg, stream);
+  });
+}
+
+extern "C" int pe_bn_act_pool_tap_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
+                                      const float* mean, const float* invstd, float slope, void* dx, float* dgamma,
+                                      float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
+                                      void* workspace, size_t workspace_bytes, unsigned* amax_out, const void* tap_dy,
+                                      long tap_lddy, int tap_coff, int tap_pool, const unsigned char* tap_arg,
+                                      void* stream) {
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    if (!tap_dy || !tap_arg) return (int)PE_E_ARG;
+    if ((tap_lddy & 3) || (tap_coff & 3) || !tap_geometry_ok(rows, Fin, C, pool, tap_pool, true))
+      return (int)PE_E_UNSUPPORTED;
+    const BnTapGrad<TA> tap{static_cast<const TA*>(tap_dy), tap_arg, tap_lddy, tap_coff, (unsigned)(tap_pool / pool)};
+    return bn_act_pool_bwd_impl(static_cast<const TA*>(x), static_cast<const TA*>(dy), scale, shift, mean, invstd, slope,
+                                static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, workspace,
+                                workspace_bytes, amax_out, stream, &tap);
   });
 }
 

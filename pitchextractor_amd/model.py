@@ -206,13 +206,14 @@ def _no_amax(_param):
     return None
 
 
-def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None, wa=_no_amax):
-    """x [B,T,F,Cin] -> [B,T,F/pool,Cout]; returns (out, saved, BatchNorm partials of out or None)."""
+def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None, wa=_no_amax, tap=None):
+    """x [B,T,F,Cin] -> [B,T,F/pool,Cout]; returns (out, saved, BatchNorm partials of out or None).  ``tap``
+    (ops.Tap): the detector tap of x, taken by the pass that reads x here."""
     s = _Ctx()
     s.x = x
     s.bn_pre = _bn(blk.pre_conv[0], x, train, x_stats)
     s.am_p = ops.amax_word()            # "h2" products: one absmax word per operand tensor, left by its producer
-    s.p = ops.bn_act_pool_fwd(x, s.bn_pre, pool=pool, slope=slope, amax_out=s.am_p)
+    s.p = ops.bn_act_pool_fwd(x, s.bn_pre, pool=pool, slope=slope, amax_out=s.am_p, tap=tap)
     out = ops.gemm_nt(_flat2(s.p), blk.conv1by1.weight.view(blk.cout, blk.cin), amax_a=s.am_p,
                       amax_b=wa(blk.conv1by1.weight))
     out = out.view(*s.p.shape[:3], blk.cout)
@@ -227,9 +228,10 @@ def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None,
     return out, s, out_stats
 
 
-def _res_backward(blk: _ResBlock, s, d_out, pool, slope, grads, side, am_do=None, wa=_no_amax):
+def _res_backward(blk: _ResBlock, s, d_out, pool, slope, grads, side, am_do=None, wa=_no_amax, tap=None):
     """d_out: grad of the block output (am_do: its absmax word if the producer left one).  Returns (grad wrt the block
-    input (dense, overwritten), its absmax word).  The three weight gradients go through `side` (_SideWork)."""
+    input (dense, overwritten), its absmax word).  The three weight gradients go through `side` (_SideWork).  ``tap``
+    (ops.Tap with its gradient): the detector tap of the block input, whose gradient joins the returned one."""
     if am_do is None:
         am_do = ops.amax_for(d_out)
     side.run(lambda: (ops.conv3x3_wgrad(s.a, d_out, grads[blk.conv[3].weight], amax_x=s.am_a, amax_dy=am_do),
@@ -249,7 +251,7 @@ def _res_backward(blk: _ResBlock, s, d_out, pool, slope, grads, side, am_do=None
     ops.gemm_nt(_flat2(d_out), w1t, out=_flat2(d_p), accumulate=True, amax_a=am_do, amax_b=wa(blk.conv1by1.weight))
     am_dx = ops.amax_word()
     return ops.bn_act_pool_bwd(s.x, d_p, s.bn_pre, grads[blk.pre_conv[0].weight], grads[blk.pre_conv[0].bias],
-                               pool=pool, slope=slope, amax_out=am_dx), am_dx
+                               pool=pool, slope=slope, amax_out=am_dx, tap=tap), am_dx
 
 
 class _DropoutCfg:
@@ -385,6 +387,9 @@ OVERLAP_TF_WGRAD = os.environ.get("PE_OVERLAP_TF_WGRAD", "1") != "0"
 # the LSTM weight gradients are joined right after the LSTM backward: letting them float under the conv backward
 # ("late") only delays the conv weight gradients queued behind them on the same side stream (+1.1 ms, measured)
 LSTM_WGRAD_JOIN_EARLY = os.environ.get("PE_LSTM_WGRAD_JOIN", "early") == "early"
+# the three detector-tap max-pools ride on the BN passes of the res blocks that read the same tensors ("0": passes of
+# their own after the pool block, as before; same bits either way -- for A/B runs)
+FOLD_TAPS = os.environ.get("PE_FOLD_TAPS", "1") != "0"
 
 
 def _lstm_backward(models, saved, dys, grads, side, wa=_no_amax):
@@ -823,9 +828,16 @@ class JDCNet(nn.Module):
         wf, s.wd_cb = ops.conv3x3_repack(cbk[3].weight, True, need_grad, amax=self.weight_amax(cbk[3].weight))
         s.cb, st_cb = ops.conv3x3_fwd(s.a0, wf, bn_stats=train, amax=s.am_a0)        # convblock_out
         wa = self.weight_amax
-        s.rb1, s.r1, st1 = _res_forward(self.res_block1, s.cb, 2, train, need_grad, slope, st_cb, wa)
-        s.rb2, s.r2, st2 = _res_forward(self.res_block2, s.rb1, 2, train, need_grad, slope, st1, wa)
-        s.rb3, s.r3, st3 = _res_forward(self.res_block3, s.rb2, 2, train, need_grad, slope, st2, wa)
+        # detector taps (model.py:45-49): max-pools of cb / rb1 / rb2 into channels [0, 384) of the concat.  Folded, each
+        # is a by-product of the BN pass of the res block that reads the same tensor (no second read of 1 GB).
+        s.taps = None
+        if FOLD_TAPS:
+            s.concat = torch.empty((B, T, 2, 640), dtype=s.cb.dtype, device=x.device)  # (bf16 under ops.ACT_BF16)
+            s.taps = [ops.Tap(s.concat, tp, coff, want_argmax=need_grad) for tp, coff in ((40, 0), (20, 64), (10, 192))]
+        t_cb, t_rb1, t_rb2 = s.taps or (None, None, None)
+        s.rb1, s.r1, st1 = _res_forward(self.res_block1, s.cb, 2, train, need_grad, slope, st_cb, wa, t_cb)
+        s.rb2, s.r2, st2 = _res_forward(self.res_block2, s.rb1, 2, train, need_grad, slope, st1, wa, t_rb1)
+        s.rb3, s.r3, st3 = _res_forward(self.res_block3, s.rb2, 2, train, need_grad, slope, st2, wa, t_rb2)
 
         # pool_block -> channels [384, 640) of the detector concat (model.py:36-41,90,108)
         Fp = s.rb3.shape[2] // 4
@@ -833,16 +845,18 @@ class JDCNet(nn.Module):
             raise ValueError("JDCNet geometry expects 80 mel bins (F/40 == 2)")
         s.bnp = _bn(self.pool_block[0], s.rb3, train, st3)
         pooled = ops.bn_act_pool_fwd(s.rb3, s.bnp, pool=4, slope=slope)            # [B,T,2,256]
-        s.concat = torch.empty((B, T, 2, 640), dtype=s.rb3.dtype, device=x.device)     # (bf16 under ops.ACT_BF16)
+        if s.taps is None:
+            s.concat = torch.empty((B, T, 2, 640), dtype=s.rb3.dtype, device=x.device)     # (bf16 under ops.ACT_BF16)
         p_blk = self.block_dropout if train else 0.0
         cslice = s.concat.view(-1, 640)[:, 384:640]
         _, s.mask_pool = _dropout(self.dropout_cfg, _flat2(pooled), p_blk, out2d=cslice)
         seq_c = ops.nhwc_to_seq(s.concat, 256, coff=384)
 
         # (the positions of the maxima are kept: 25 MB of bytes save the backward pass three 1 GB reads)
-        _, s.arg_cb = ops.maxpool_fwd(s.cb, 40, out=s.concat, coff=0, want_argmax=True)
-        _, s.arg_rb1 = ops.maxpool_fwd(s.rb1, 20, out=s.concat, coff=64, want_argmax=True)
-        _, s.arg_rb2 = ops.maxpool_fwd(s.rb2, 10, out=s.concat, coff=192, want_argmax=True)
+        if s.taps is None:
+            _, s.arg_cb = ops.maxpool_fwd(s.cb, 40, out=s.concat, coff=0, want_argmax=True)
+            _, s.arg_rb1 = ops.maxpool_fwd(s.rb1, 20, out=s.concat, coff=64, want_argmax=True)
+            _, s.arg_rb2 = ops.maxpool_fwd(s.rb2, 10, out=s.concat, coff=192, want_argmax=True)
         wdet = self.detector_conv[0].weight.view(256, 640)
         s.dconv = ops.gemm_nt(s.concat.view(-1, 640), wdet, amax_b=self.weight_amax(self.detector_conv[0].weight))
         s.dconv = s.dconv.view(B, T, 2, 256)
@@ -933,18 +947,24 @@ class JDCNet(nn.Module):
             if cuts is not None:
                 self._dp.reduce_range(cuts[k], cuts[k + 1], after=side.pending_stream())
 
-        # each block-input gradient leaves its absmax word behind; the detector tap's max-pool gradient, added in place
-        # afterwards, merges the values it rewrote into the same word
+        # each block-input gradient leaves its absmax word behind; the detector tap's max-pool gradient is added by the
+        # same pass (folded taps) or in place afterwards, and the values it rewrote are merged into the same word
         wa = self.weight_amax
-        d_rb2, am2 = _res_backward(self.res_block3, s.r3, d_rb3, 2, slope, g, side, am3, wa)
+        t_cb, t_rb1, t_rb2 = s.taps or (None, None, None)
+        for t in s.taps or ():
+            t.grad = d_concat
+        d_rb2, am2 = _res_backward(self.res_block3, s.r3, d_rb3, 2, slope, g, side, am3, wa, t_rb2)
         block_done(3)                       # res_block3 + pool_block + detector_conv
-        ops.maxpool_bwd_add(s.rb2, d_concat, d_rb2, 10, coff=192, amax_out=am2, argmax=s.arg_rb2)
-        d_rb1, am1 = _res_backward(self.res_block2, s.r2, d_rb2, 2, slope, g, side, am2, wa)
+        if s.taps is None:
+            ops.maxpool_bwd_add(s.rb2, d_concat, d_rb2, 10, coff=192, amax_out=am2, argmax=s.arg_rb2)
+        d_rb1, am1 = _res_backward(self.res_block2, s.r2, d_rb2, 2, slope, g, side, am2, wa, t_rb1)
         block_done(2)
-        ops.maxpool_bwd_add(s.rb1, d_concat, d_rb1, 20, coff=64, amax_out=am1, argmax=s.arg_rb1)
-        d_cb, am_dcb = _res_backward(self.res_block1, s.r1, d_rb1, 2, slope, g, side, am1, wa)
+        if s.taps is None:
+            ops.maxpool_bwd_add(s.rb1, d_concat, d_rb1, 20, coff=64, amax_out=am1, argmax=s.arg_rb1)
+        d_cb, am_dcb = _res_backward(self.res_block1, s.r1, d_rb1, 2, slope, g, side, am1, wa, t_cb)
         block_done(1)
-        ops.maxpool_bwd_add(s.cb, d_concat, d_cb, 40, coff=0, amax_out=am_dcb, argmax=s.arg_cb)
+        if s.taps is None:
+            ops.maxpool_bwd_add(s.cb, d_concat, d_cb, 40, coff=0, amax_out=am_dcb, argmax=s.arg_cb)
 
         cbk = self.conv_block
         side.run(lambda: ops.conv3x3_wgrad(s.a0, d_cb, g[cbk[3].weight], amax_x=s.am_a0, amax_dy=am_dcb), d_cb, am_dcb,

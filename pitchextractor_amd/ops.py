@@ -580,20 +580,55 @@ def _slice_target(out, B, T, Fo, Cc, coff):
     return ld
 
 
-def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_out=None):
-    """``amax_out``: a zeroed word from ``amax_word()``; the pass leaves the absmax of its output there."""
+class Tap:
+    """A detector tap of the tensor a BN pass reads: MaxPool2d((1, pool)) of the raw input into channels
+    [coff, coff + C) of ``out`` ([B, T, F // pool, Ctot]).  ``bn_act_pool_fwd(tap=...)`` writes the slice and, with
+    ``want_argmax``, leaves the positions of the maxima in ``argmax``; ``bn_act_pool_bwd(tap=...)`` reads ``grad`` (the
+    gradient of ``out``, same layout) and ``argmax`` and adds the tap's gradient to the dx it writes."""
+
+    def __init__(self, out, pool, coff, want_argmax=False):
+        self.out, self.pool, self.coff, self.want_argmax = out, int(pool), int(coff), bool(want_argmax)
+        self.argmax = None
+        self.grad = None
+
+
+def _tap_folded(x, pool, tap: Tap, with_arg) -> bool:
+    """True if the library's fused pass serves this tap; otherwise the BN pass and the tap pass run one after the other."""
+    B, T, F, Cc = x.shape
+    return bool(_lib.load().pe_bn_act_pool_tap_supported(B * T, F, Cc, pool, tap.pool, int(with_arg)))
+
+
+def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_out=None, tap: Tap | None = None):
+    """``amax_out``: a zeroed word from ``amax_word()``; the pass leaves the absmax of its output there.
+    ``tap``: also max-pool the raw x into ``tap.out`` (see ``Tap``), in the same pass where the library serves it."""
     x = _actd(x, "x")
     B, T, F, Cc = x.shape
     Fo = F // pool
     if out is None:
         out = torch.empty((B, T, Fo, Cc), dtype=x.dtype, device=x.device)
     ld = _slice_target(out, B, T, Fo, Cc, coff)
+    if tap is not None and _tap_folded(x, pool, tap, tap.want_argmax):
+        Ft = F // tap.pool
+        tld = _slice_target(tap.out, B, T, Ft, Cc, tap.coff)
+        tap.argmax = torch.empty((B, T, Ft, Cc), dtype=torch.uint8, device=x.device) if tap.want_argmax else None
+        _call("pe_bn_act_pool_tap_fwd", x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), slope, out.data_ptr(),
+              B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), tap.out.data_ptr(), tld, tap.coff, tap.pool,
+              _lib.ptr(tap.argmax), _s(), act16=_act16(x, out, tap.out))
+        return out
     _call("pe_bn_act_pool_fwd", x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), slope, out.data_ptr(),
           B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s(), act16=_act16(x, out))
+    if tap is not None:
+        if tap.want_argmax:
+            _, tap.argmax = maxpool_fwd(x, tap.pool, out=tap.out, coff=tap.coff, want_argmax=True)
+        else:
+            maxpool_fwd(x, tap.pool, out=tap.out, coff=tap.coff)
     return out
 
 
-def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=0, dx=None, amax_out=None):
+def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=0, dx=None, amax_out=None,
+                    tap: Tap | None = None):
+    """``tap`` (with ``grad`` and ``argmax`` set): dx also takes the gradient of the tap, and ``amax_out`` what
+    ``maxpool_bwd_add`` would have merged into it."""
     x = _actd(x, "x")
     B, T, F, Cc = x.shape
     ld = _slice_target(dy, B, T, F // pool, Cc, coff)
@@ -603,9 +638,21 @@ def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=
     _chk(_dense(dgamma, "dgamma").numel() == Cc and _dense(dbeta, "dbeta").numel() == Cc, "dgamma/dbeta size")
     lib = _lib.load()
     ws = workspace(lib.pe_bn_workspace_bytes(Cc) + 8 * Cc, x.device)
+    if tap is not None and tap.argmax is not None and _tap_folded(x, pool, tap, True):
+        Ft = F // tap.pool
+        _chk(tap.argmax.is_cuda and tap.argmax.dtype == torch.uint8 and tap.argmax.is_contiguous()
+             and tap.argmax.shape == (B, T, Ft, Cc), "bn_act_pool_bwd: tap argmax shape")
+        tld = _slice_target(tap.grad, B, T, Ft, Cc, tap.coff)
+        _call("pe_bn_act_pool_tap_bwd", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
+              st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+              B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _lib.ptr(amax_out), tap.grad.data_ptr(), tld,
+              tap.coff, tap.pool, tap.argmax.data_ptr(), _s(), act16=_act16(x, dy, dx, tap.grad))
+        return dx
     _call("pe_bn_act_pool_bwd", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
           st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
           B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _lib.ptr(amax_out), _s(), act16=_act16(x, dy, dx))
+    if tap is not None:
+        maxpool_bwd_add(x, tap.grad, dx, tap.pool, coff=tap.coff, amax_out=amax_out, argmax=tap.argmax)
     return dx
 
 
