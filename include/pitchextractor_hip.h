@@ -789,6 +789,44 @@ int pe_noise_mix(const float* x, const float* noise, const long* meta, const lon
                  const double* host_snr_db, int peak_normalize, int n_rows, float* y, double* stats, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- Room impulse responses by the image-source method and their decay time (the impulse-response files that the
+ * reference's Utils/room_and_microphone_stress.ipynb reads and nobody ships), ragged batches --------------------------
+ * One row is one response of a shoebox room.  params (n_rows x 19 doubles, made by the caller) = per row {Lx, Ly, Lz,
+ * source x y z, microphone x y z, beta x0 x1 y0 y1 z0 z1 (wall at coordinate 0, wall at L), fs, c, N, max_order (-1:
+ * none)}.  With R_a = (1 - 2 p_a) s_a + 2 n_a L_a - r_a over n in Z^3, p in {0, 1}^3, d = |R|, tau = d fs / c and
+ * A = prod_a beta_a0^|n_a - p_a| beta_a1^|n_a| / (4 pi d) (0^0 = 1), an image with A != 0, tau < N + 41 and
+ * sum_a |n_a - p_a| + |n_a| <= max_order adds v = A sinc(x) (1 + cos(pi x / 41)) / 2 at every 0 <= k < N with
+ * x = k - tau, |x| < 41, and h[k] = float32(2^-44 sum rint(2^44 v)) with the sum in 64-bit integers: the result
+ * depends on no order of addition.  d, tau, A and the taps are double.
+ * pe_rir_plan (host only): consts4 = {tile length T = 256, 19, int64 per tile, doubles per row of pe_rir_decay's out};
+ * meta (n_rows x pe_rir_plan_fields() int64, to be copied to the device) = per row {offset y_off[r], N, tiles =
+ * ceil(N / T), tile prefix}; tiles (may be null: totals only; else tile_capacity >= totals2[1] entries of 2 int64, to
+ * be copied to the device) = {row, first sample} of every tile, those with the most images first; totals2 = {samples,
+ * tiles}.  PE_E_ARG: a non-finite value, a dimension, fs or c <= 0, a source or microphone not strictly inside the
+ * room or less than 1 cm apart, a beta outside [0, 1], N < 1 or not an integer, max_order < -1 or not an integer, a
+ * negative offset.  PE_E_UNSUPPORTED: N > 2^24; more than 2^20 tiles; a lattice index that could pass 2^30, (d_max + D)
+ * / L_a + 8 >= 2^30 with D the room's diagonal and d_max = (N + 42) c / fs; or too little fixed-point headroom: the
+ * bound 288 pi D^3 / V + (d_max + D)^2 / V on the sum of all image amplitudes must stay below 2^18 (the integer sum
+ * holds |h| < 2^19).
+ * pe_rir_synth: host_meta, host_params and host_tiles are the host copies; PE_E_ARG unless they are what pe_rir_plan
+ * makes of host_params and the offsets, or if a row leaves the n_y floats of y.  One launch, one workgroup per tile,
+ * whatever the rows; every sample of every row is written, nothing else is.  A row's samples are bit-identical alone,
+ * in a batch in any order, at any offset or padded.
+ * pe_rir_decay: Schroeder's backward integration of the rows of h (n_h floats) that meta describes (any row plan:
+ * meta_fields int64 per row, opening with offset and length; host_meta its host copy).  E[k] = sum_{m >= k} h[m]^2 in
+ * double, db[k] = 10 log10(E[k] / E[0]); k_lo, k_hi = the first k with db[k] < lo_db, hi_db (N when there is none);
+ * the least-squares line of db over k / fs on k_lo <= k < k_hi.  out6 (n_rows x 6 doubles) = {T60 = -60 / slope,
+ * slope in dB / s, intercept in dB, k_lo, k_hi, db[N - 1]}; T60, slope and intercept are NaN when hi_db is never
+ * reached or k_hi - k_lo < 2.  curve (may be null): db[k] as float32 at the rows' offsets.  PE_E_ARG: fs <= 0, lo_db >
+ * 0, hi_db >= lo_db, a row outside h.  One launch, one workgroup per row. */
+int pe_rir_plan_fields(void);
+int pe_rir_plan(int n_rows, const double* params, const long* y_off, long* consts4, long* meta, long* tiles,
+                long tile_capacity, long* totals2);
+int pe_rir_synth(const long* meta, const long* host_meta, const double* params, const double* host_params,
+                 const long* tiles, const long* host_tiles, int n_rows, float* y, long n_y, void* stream);
+int pe_rir_decay(const float* h, long n_h, const long* meta, const long* host_meta, int meta_fields, int n_rows,
+                 double fs, double lo_db, double hi_db, double* out6, float* curve, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,10 @@ PROTOTYPES = {
     "pe_noise_colour": (_i, [_p, _p, _p, _p, _p, _l, _i, _p, _p, _z, _p]),
     "pe_noise_bed": (_i, [_p, _p, _p, _l, _p, _p, _i, _p, _p]),
     "pe_noise_mix": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "pe_rir_plan_fields": (_i, []),
+    "pe_rir_plan": (_i, [_i, _p, _p, _p, _p, _p, _l, _p]),
+    "pe_rir_synth": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _l, _p]),
+    "pe_rir_decay": (_i, [_p, _l, _p, _p, _i, _i, _d, _d, _d, _p, _p, _p]),
 }
 
 
