@@ -204,6 +204,11 @@ int pe_conv3x3_c1_fwd(int act16, const float* x, long sb, long st, long sf, cons
                       int F, double* bn_partials, void* stream);
 int pe_conv3x3_c1_wgrad(int act16, const float* x, long sb, long st, long sf, const void* dy, float* dw_oihw, int B,
                         int T, int F, float* workspace, size_t workspace_bytes, void* stream);
+/* data gradient of the first convolution: dx[b][t][f] = sum_{co,i,j} w[co][0][i][j] * dy[b][t-i+1][f-j+1][co], dy
+ * channels-last [B][T][F][64] (zero outside the grid), dx dense [B][T][F] fp32.  One pass over dy, no atomics, the
+ * same bits however large B is.  act16: 0 = fp32 dy, 1 = bf16, 2 = fp16.  F % 4 != 0 or B*T*F near 2^31:
+ * PE_E_UNSUPPORTED. */
+int pe_conv3x3_c1_dgrad(int act16, const void* dy, const float* w_oihw, float* dx, int B, int T, int F, void* stream);
 
 /* ---- fused self-attention (model.py:231-239: nn.MultiheadAttention inside TransformerEncoderLayer) -------------
  * qkv [B*T][ld_qkv] packed projections (Q | K | V, head h at columns h*dh of each part); o [B*T][ld_o] merged
@@ -229,7 +234,11 @@ int pe_attn_bwd(int products, const float* qkv, long ld_qkv, const float* o, con
  * unbiased variance, plus the fused affine scale = gamma*invstd, shift = beta - mean*scale.
  * pe_bn_act_pool_fwd: y = maxpool_k(lrelu(x*scale + shift)) written at
  *   y[(row*Fout + fo)*ldy + coff + c] (model.py:36-41,148-153).
- * pe_bn_act_pool_bwd: gradient of that block w.r.t. x, gamma, beta (train-mode BN).
+ * pe_bn_act_pool_bwd: gradient of that block w.r.t. x, gamma, beta.  eval_mode = 0: train-mode BN (mean / invstd are
+ *   the batch statistics).  eval_mode = 1: the forward ran on running statistics (pe_bn_eval_affine filled scale, shift,
+ *   mean = running_mean, invstd = 1/sqrt(running_var + eps)): dx = scale * lrelu'(z) * unpool(dy) with no mean or
+ *   projection term, dgamma = sum dz * (x - mean) * invstd, dbeta = sum dz -- nn.BatchNorm2d.eval() under autograd.
+ *   With eval_mode = 1, dgamma and dbeta may both be NULL: no per-channel reduction runs and workspace may be NULL.
  * amax_out (optional, these two and pe_maxpool_bwd_add): a device word the caller zeroed; the pass max-merges the
  *   IEEE bits of the largest magnitude it stored into it (atomicMax), which is the scale source an "h2" product
  *   reading the output needs (PE_PROD_H2) -- no separate pe_absmax pass.  pe_maxpool_bwd_add merges the values it
@@ -245,12 +254,13 @@ int pe_bn_finalize_stats(const double* partials, int nparts, long n_pix, int C, 
                          float* invstd, float* scale, float* shift, void* workspace, size_t workspace_bytes,
                          void* stream);   /* workspace: pe_bn_workspace_bytes(C) */
 int pe_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
-                      const float* running_var, float eps, int C, float* scale, float* shift, void* stream);
+                      const float* running_var, float eps, int C, float* scale, float* shift, float* mean,
+                      float* invstd, void* stream);
 int pe_bn_act_pool_fwd(int act16, const void* x, const float* scale, const float* shift, float slope, void* y, long rows,
                        int Fin, int C, int pool, long ldy, int coff, unsigned* amax_out, void* stream);
 int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
                        const float* mean, const float* invstd, float slope, void* dx, float* dgamma, float* dbeta,
-                       long rows, int Fin, int C, int pool, long lddy, int coff, void* workspace,
+                       long rows, int Fin, int C, int pool, long lddy, int coff, int eval_mode, void* workspace,
                        size_t workspace_bytes, unsigned* amax_out, void* stream);
 /* detector-branch MaxPool2d((1,40|20|10)) (model.py:45-49,103-105) into a channel slice.  argmax_out (optional,
  * [rows * (Fin / pool)][C] bytes): the window position of each maximum (the first one, as torch's backward routes it);
@@ -272,7 +282,7 @@ int pe_bn_act_pool_tap_fwd(int act16, const void* x, const float* scale, const f
                            long tap_ldy, int tap_coff, int tap_pool, unsigned char* tap_arg, void* stream);
 int pe_bn_act_pool_tap_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
                            const float* mean, const float* invstd, float slope, void* dx, float* dgamma, float* dbeta,
-                           long rows, int Fin, int C, int pool, long lddy, int coff, void* workspace,
+                           long rows, int Fin, int C, int pool, long lddy, int coff, int eval_mode, void* workspace,
                            size_t workspace_bytes, unsigned* amax_out, const void* tap_dy, long tap_lddy, int tap_coff,
                            int tap_pool, const unsigned char* tap_arg, void* stream);
 /* nn.Dropout (model.py:40,56; LSTM inter-layer): Philox4x32-10 keyed by (seed, offset + quad index);
@@ -348,6 +358,7 @@ int pe_colsum(const float* x, long rows, int cols, long ld, float* out0, float* 
 int pe_head_fwd(const float* x, long ldx, const float* w, const float* bias, int n_out, float* y, long R,
                 int D, void* stream);
 size_t pe_head_bwd_workspace_bytes(int D);
+/* dw and db both NULL: dx only (x and the workspace are not read). */
 int pe_head_bwd(const float* x, long ldx, const float* w, const float* dy, int n_out, float* dx, long lddx,
                 float* dw, float* db, long R, int D, void* workspace, size_t workspace_bytes, void* stream);
 int pe_f0_sil_loss(const float* f0_pred, const float* f0, const float* sil_pred, const float* sil,
@@ -397,6 +408,8 @@ int pe_layernorm_fwd(const float* a, const float* b, const float* pe, int period
                      const float* beta, float eps, float* z_out, float* y, float* mean, float* rstd, long rows,
                      int D, void* stream);
 size_t pe_layernorm_bwd_workspace_bytes(int D);
+/* pe_layernorm_bwd / pe_layernorm_bwd_fused with dgamma and dbeta both NULL: dz only (the parameter sums are not
+ * reduced; the workspace is still needed). */
 int pe_layernorm_bwd(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
                      float* dz, float* dgamma, float* dbeta, long rows, int D, void* workspace,
                      size_t workspace_bytes, void* stream);

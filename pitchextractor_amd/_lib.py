@@ -66,18 +66,20 @@ PROTOTYPES = {
     "pe_conv3x3_c1_stat_parts": (_i, [_i, _i, _i]),
     "pe_conv3x3_c1_fwd": (_i, [_i, _p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p]),
     "pe_conv3x3_c1_wgrad": (_i, [_i, _p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _z, _p]),
+    "pe_conv3x3_c1_dgrad": (_i, [_i, _p, _p, _p, _i, _i, _i, _p]),
     "pe_bn_workspace_bytes": (_z, [_i]),
     "pe_bn_train_stats": (_i, [_i, _p, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "pe_conv3x3_wf_stat_parts": (_i, [_i, _i, _i]),
     "pe_bn_finalize_stats": (_i, [_p, _i, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "pe_bn_eval_affine": (_i, [_p, _p, _p, _p, _f, _i, _p, _p, _p]),
+    "pe_bn_eval_affine": (_i, [_p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p]),
     "pe_bn_act_pool_fwd": (_i, [_i, _p, _p, _p, _f, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
-    "pe_bn_act_pool_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _z, _p, _p]),
+    "pe_bn_act_pool_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _i, _p, _z, _p,
+                                _p]),
     "pe_maxpool_fwd": (_i, [_i, _p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
     "pe_maxpool_bwd_add": (_i, [_i, _p, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _p]),
     "pe_bn_act_pool_tap_supported": (_i, [_l, _i, _i, _i, _i, _i]),
     "pe_bn_act_pool_tap_fwd": (_i, [_i, _p, _p, _p, _f, _p, _l, _i, _i, _i, _l, _i, _p, _p, _l, _i, _i, _p, _p]),
-    "pe_bn_act_pool_tap_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _p, _z, _p,
+    "pe_bn_act_pool_tap_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _l, _i, _i, _i, _l, _i, _i, _p, _z, _p,
                                     _p, _l, _i, _i, _p, _p]),
     "pe_dropout_fwd": (_i, [_i, _p, _l, _p, _l, _p, _p, _l, _i, _f, _u64, _u64, _p]),
     "pe_nhwc_to_seq": (_i, [_i, _p, _l, _i, _p, _l, _i, _p]),

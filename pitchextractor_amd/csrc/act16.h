@@ -19,6 +19,11 @@ __device__ __forceinline__ float4 ld4(const act16_t* p) {            // 4 consec
   return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
                      __uint_as_float(u.y & 0xffff0000u));
 }
+__device__ __forceinline__ float4 ld4(const _Float16* p) {           // 4 consecutive fp16 (8-byte aligned)
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  const h4 v = *reinterpret_cast<const h4*>(p);
+  return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+}
 __device__ __forceinline__ unsigned pack_bf16_rne(float a, float b) {
   typedef __bf16 b2 __attribute__((ext_vector_type(2)));
   typedef float f2 __attribute__((ext_vector_type(2)));

@@ -919,6 +919,82 @@ __global__ void c1_wgrad_reduce_kernel(const float* __restrict__ partial, float*
   if (lane == 0) dw[i] = (float)s;
 }
 
+// dx[b][t][f] = sum_{co,i,j} w[co][i][j] * dy[b][t-i+1][f-j+1][co]  (dy zero outside the grid): the data gradient of the
+// first convolution.  One pass over dy (1 GB at B = 256 against 16 MB written).  A workgroup owns a kDgTT x kDgTF tile
+// of dx and reads that tile of dy with a one-pixel halo.  16 lanes take a pixel (one float4 / 4 x 16 bit of its 64
+// channels each, the 36 weights of those channels in registers) and reduce it against the nine taps; four pixels are in
+// flight per 16-lane group and folded together with DPP moves (no LDS traffic): inside each quad of lanes the odd and
+// even lanes trade pixel pairs, then single pixels, so that lane l of a quad holds one pixel's sum over the quad's 16
+// channels; two row rotations (by 8, then 4 lanes) add the four quads -- 45 moves for 4 x 9 sums instead of 144.
+// The nine partials of every halo pixel stay in LDS (stride 9 words: odd, so neighbouring pixels fall into different
+// banks) and each output gathers the nine that belong to it.  No atomics; the order of every sum is fixed by the tile
+// geometry alone.
+template <int CTRL>
+__device__ __forceinline__ float dpp_move(float v) {           // all lanes active: every lane reads the lane CTRL names
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+constexpr int kDppSwap1 = 0xB1, kDppSwap2 = 0x4E;              // quad_perm:[1,0,3,2] (lane ^ 1), [2,3,0,1] (lane ^ 2)
+constexpr int kDppRor8 = 0x128, kDppRor4 = 0x124;              // row_ror:8, row_ror:4 (rotation within 16 lanes)
+
+constexpr int kDgTT = 30, kDgTF = 16, kDgHF = kDgTF + 2, kDgHalo = (kDgTT + 2) * kDgHF;   // 576 halo pixels = 9 x 64
+static_assert(kDgHalo % 64 == 0, "whole passes of 16 groups x 4 pixels");
+
+template <class TA>
+__global__ __launch_bounds__(256) void conv3x3_c1_dgrad_kernel(const TA* __restrict__ dy, const float* __restrict__ w,
+                                                               float* __restrict__ dx, int T, int F, int tiles_t,
+                                                               int tiles_f) {
+  __shared__ float part[kDgHalo * 9];
+  const int lane = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  float wr[4][9];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wr[c][k] = w[(lane * 4 + c) * 9 + k];
+  const int tf = blockIdx.x % tiles_f, tt = (blockIdx.x / tiles_f) % tiles_t, b = blockIdx.x / (tiles_f * tiles_t);
+  const int t0 = tt * kDgTT, f0 = tf * kDgTF;
+  const TA* dyb = dy + (long)b * T * F * 64 + lane * 4;         // B*T*F < 2^31 (checked by the host)
+  const bool odd1 = lane & 1, odd2 = lane & 2;
+  for (int q = grp; q < kDgHalo / 4; q += 16) {
+    float4 g[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int h = q * 4 + u, hr = h / kDgHF, t = t0 - 1 + hr, f = f0 - 1 + (h - hr * kDgHF);
+      g[u] = (t >= 0 && t < T && f >= 0 && f < F) ? ld4(dyb + ((long)t * F + f) * 64) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      float a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        a[u] = fmaf(g[u].w, wr[3][k], fmaf(g[u].z, wr[2][k], fmaf(g[u].y, wr[1][k], g[u].x * wr[0][k])));
+      // even lanes keep pixels 0, 1 and odd lanes pixels 2, 3; then bit 1 of the lane picks one of the pair:
+      // lane l of every quad ends with pixel 2 * (l & 1) + ((l >> 1) & 1)
+      const float p0 = (odd1 ? a[2] : a[0]) + dpp_move<kDppSwap1>(odd1 ? a[0] : a[2]);
+      const float p1 = (odd1 ? a[3] : a[1]) + dpp_move<kDppSwap1>(odd1 ? a[1] : a[3]);
+      float v = (odd2 ? p1 : p0) + dpp_move<kDppSwap2>(odd2 ? p0 : p1);
+      v += dpp_move<kDppRor8>(v);                             // quads 0 + 2, 1 + 3 (a rotation keeps the place in the quad)
+      s[k] = v + dpp_move<kDppRor4>(v);                       // all four quads, in every lane
+    }
+    if (lane < 4) {
+      float* pp = part + (q * 4 + 2 * (lane & 1) + (lane >> 1)) * 9;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) pp[k] = s[k];
+    }
+  }
+  __syncthreads();
+  for (int o = threadIdx.x; o < kDgTT * kDgTF; o += 256) {
+    const int r = o / kDgTF, c = o - r * kDgTF, t = t0 + r, f = f0 + c;
+    if (t >= T || f >= F) continue;
+    float acc = 0.f;                                           // tile pixel (r, c) is halo pixel (r + 1, c + 1)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc += part[((r + 2 - i) * kDgHF + (c + 2 - j)) * 9 + i * 3 + j];
+    dx[((long)b * T + t) * F + f] = acc;
+  }
+}
+
 constexpr int kC1WgradBlocks = 2048;
 
 }  // namespace
@@ -1142,5 +1218,26 @@ extern "C" int pe_conv3x3_c1_wgrad(int act16, const float* x, long sb, long st, 
     using TA = typename decltype(a)::TA;
     return conv3x3_c1_wgrad_impl(x, sb, st, sf, static_cast<const TA*>(dy), dw_oihw, B, T, F, workspace, workspace_bytes,
                                  stream);
+  });
+}
+
+template <class TA>
+static int conv3x3_c1_dgrad_impl(const TA* dy, const float* w_oihw, float* dx, int B, int T, int F, void* stream) {
+  if (!dy || !w_oihw || !dx || B <= 0 || T <= 0 || F <= 0) return PE_E_ARG;
+  if ((F & 3) || (long)B * T * F >= (1L << 31) - 65536) return PE_E_UNSUPPORTED;   // as the forward; 32-bit pixel index
+  const int tiles_t = (T + kDgTT - 1) / kDgTT, tiles_f = (F + kDgTF - 1) / kDgTF;   // (tiles <= pixels < 2^31)
+  hipLaunchKernelGGL(conv3x3_c1_dgrad_kernel<TA>, dim3(B * tiles_t * tiles_f), dim3(256), 0, pe_stream(stream), dy,
+                     w_oihw, dx, T, F, tiles_t, tiles_f);
+  PE_LAUNCH_CHECK();
+  return PE_OK;
+}
+
+// act16: 0 = fp32 dy, 1 = bf16 (the conv stack's 16-bit storage type), 2 = fp16 (this entry point only)
+extern "C" int pe_conv3x3_c1_dgrad(int act16, const void* dy, const float* w_oihw, float* dx, int B, int T, int F,
+                                   void* stream) {
+  if (act16 == 2) return conv3x3_c1_dgrad_impl(static_cast<const _Float16*>(dy), w_oihw, dx, B, T, F, stream);
+  return with_act(act16, [&](auto a) {
+    using TA = typename decltype(a)::TA;
+    return conv3x3_c1_dgrad_impl(static_cast<const TA*>(dy), w_oihw, dx, B, T, F, stream);
   });
 }

@@ -99,13 +99,16 @@ __global__ void bn_stats_finalize_kernel(const double* __restrict__ partial, int
 
 __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                       const float* __restrict__ rm, const float* __restrict__ rv, float eps, int C,
-                                      float* __restrict__ scale, float* __restrict__ shift) {
+                                      float* __restrict__ scale, float* __restrict__ shift,
+                                      float* __restrict__ mean, float* __restrict__ invstd_out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float invstd = 1.0f / sqrtf(rv[c] + eps);
   const float sc = gamma[c] * invstd;
   scale[c] = sc;
   shift[c] = beta[c] - rm[c] * sc;
+  mean[c] = rm[c];                      // the statistics the layer normalised with: what its backward reads
+  invstd_out[c] = invstd;
 }
 
 // ---------------------------------------------------------------- "h2" scale source from the producing pass
@@ -337,11 +340,18 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ partial, int n
   if ((threadIdx.x & 63) != 0) return;
   dbeta[c] = (float)s1;
   dgamma[c] = (float)s2;
+  if (c1 == nullptr) return;            // running statistics: the input gradient has no mean / projection term
   c1[c] = (float)(s1 / (double)n_pix);
   c2[c] = (float)(s2 / (double)n_pix);
 }
 
 // dx = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat));  scale == gamma*invstd
+// With running statistics (eval mode) the layer is the affine map z = scale * x + shift and dx = scale * dz: the apply
+// passes run with c1 == c2 == nullptr, which stands for two zero vectors (dz - 0 - xhat * 0 == dz exactly).
+__device__ __forceinline__ float4 bn_term(const float* __restrict__ k, int c) {
+  return k != nullptr ? *reinterpret_cast<const float4*>(k + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a, const float* __restrict__ c1,
                                                            const float* __restrict__ c2, float* __restrict__ dx,
                                                            unsigned* __restrict__ amax) {
@@ -356,8 +366,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a, co
     const float4 mu = *reinterpret_cast<const float4*>(a.mean + c);
     const float4 is = *reinterpret_cast<const float4*>(a.invstd + c);
     const float4 sc = *reinterpret_cast<const float4*>(a.scale + c);
-    const float4 k1 = *reinterpret_cast<const float4*>(c1 + c);
-    const float4 k2 = *reinterpret_cast<const float4*>(c2 + c);
+    const float4 k1 = bn_term(c1, c), k2 = bn_term(c2, c);
     float4 o;
     o.x = sc.x * (dz.x - k1.x - (v.x - mu.x) * is.x * k2.x);
     o.y = sc.y * (dz.y - k1.y - (v.y - mu.y) * is.y * k2.y);
@@ -468,7 +477,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BnBwdArgsT<
   const int G = 256 / quads, c = (threadIdx.x % quads) * 4, g = threadIdx.x / quads;     // see bn_act_pool_fwd_kernel
   const float4 mu = *reinterpret_cast<const float4*>(a.mean + c), is = *reinterpret_cast<const float4*>(a.invstd + c);
   const float4 sc = *reinterpret_cast<const float4*>(a.scale + c), sh = *reinterpret_cast<const float4*>(a.shift + c);
-  const float4 k1 = *reinterpret_cast<const float4*>(c1 + c), k2 = *reinterpret_cast<const float4*>(c2 + c);
+  const float4 k1 = bn_term(c1, c), k2 = bn_term(c2, c);
   for (long item = (long)blockIdx.x * G + g; g < G && item < n_items; item += (long)gridDim.x * G) {
     BnWindow<POOL> w;
     bn_window<POOL, TA>(a, item, nwin, c, w, sc, sh);
@@ -500,7 +509,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_tap_kernel(const BnBwdAr
   const int G = 256 / quads, c = (threadIdx.x % quads) * 4, g = threadIdx.x / quads;     // see bn_act_pool_fwd_kernel
   const float4 mu = *reinterpret_cast<const float4*>(a.mean + c), is = *reinterpret_cast<const float4*>(a.invstd + c);
   const float4 sc = *reinterpret_cast<const float4*>(a.scale + c), sh = *reinterpret_cast<const float4*>(a.shift + c);
-  const float4 k1 = *reinterpret_cast<const float4*>(c1 + c), k2 = *reinterpret_cast<const float4*>(c2 + c);
+  const float4 k1 = bn_term(c1, c), k2 = bn_term(c2, c);
   for (long item = (long)blockIdx.x * G + g; g < G && item < n_items; item += (long)gridDim.x * G) {
     BnWindow<POOL> w;
     bn_window<POOL, TA>(a, item, nwin, c, w, sc, sh);
@@ -842,10 +851,11 @@ extern "C" int pe_bn_finalize_stats(const double* partials, int nparts, long n_p
 
 extern "C" int pe_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
                                  const float* running_var, float eps, int C, float* scale, float* shift,
-                                 void* stream) {
-  if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || C <= 0) return PE_E_ARG;
+                                 float* mean, float* invstd, void* stream) {
+  if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || !mean || !invstd || C <= 0)
+    return PE_E_ARG;
   hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(pe_cdiv(C, 64)), dim3(64), 0, pe_stream(stream), gamma, beta,
-                     running_mean, running_var, eps, C, scale, shift);
+                     running_mean, running_var, eps, C, scale, shift, mean, invstd);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }
@@ -875,17 +885,23 @@ extern "C" int pe_bn_act_pool_fwd(int act16, const void* x, const float* scale, 
 template <class TA>
 static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, const float* shift, const float* mean,
                                 const float* invstd, float slope, TA* dx, float* dgamma, float* dbeta, long rows,
-                                int Fin, int C, int pool, long lddy, int coff, void* workspace, size_t workspace_bytes,
-                                unsigned* amax_out, void* stream, const BnTapGrad<TA>* tap = nullptr) {
-  if (!x || !dy || !scale || !shift || !mean || !invstd || !dx || !dgamma || !dbeta || rows <= 0) return PE_E_ARG;
+                                int Fin, int C, int pool, long lddy, int coff, int eval_mode, void* workspace,
+                                size_t workspace_bytes, unsigned* amax_out, void* stream,
+                                const BnTapGrad<TA>* tap = nullptr) {
+  // eval_mode: mean / invstd are the running statistics the forward normalised with (pe_bn_eval_affine); dgamma and
+  // dbeta may then be null together, and the per-channel reduction is not launched at all
+  const bool sums = !(eval_mode && !dgamma && !dbeta);
+  if (!x || !dy || !scale || !shift || !mean || !invstd || !dx || rows <= 0) return PE_E_ARG;
+  if (sums && (!dgamma || !dbeta)) return PE_E_ARG;
   if (!bn_channels_ok(C) || (lddy & 3) || (coff & 3) || pool <= 0) return PE_E_UNSUPPORTED;
   const size_t need = pe_bn_workspace_bytes(C) + 2 * (size_t)C * sizeof(float);
-  if (!workspace || workspace_bytes < need) return PE_E_WORKSPACE;
+  if (sums && (!workspace || workspace_bytes < need)) return PE_E_WORKSPACE;
   hipStream_t st = pe_stream(stream);
   BnBwdArgsT<TA> a{x, dy, scale, shift, mean, invstd, slope, rows * Fin, Fin, C, pool, lddy, coff};
   double* partial = reinterpret_cast<double*>(workspace);
-  float* c1 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pe_bn_workspace_bytes(C));
-  float* c2 = c1 + C;
+  float* c1 = eval_mode ? nullptr
+                        : reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pe_bn_workspace_bytes(C));
+  float* c2 = eval_mode ? nullptr : c1 + C;
   const int nwin = Fin / pool + (Fin % pool ? 1 : 0);
   const long n_items = rows * nwin;
   const bool win = pool == 1 || pool == 2 || pool == 4;
@@ -894,18 +910,20 @@ static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, c
   // (partial<1>: 348 -> 257 us; the pooled forms and fp32 tensors, at HBM speed with 1024, lose 5-10 % with more)
   const int grid = reduce_grid(win ? n_items : a.n_in_pix, C,
                                (!std::is_same<TA, float>::value && pool == 1) ? kMaxPartials : 1024);
-  if (pool == 1)
-    hipLaunchKernelGGL((bn_bwd_partial_win_kernel<1, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
-  else if (pool == 2)
-    hipLaunchKernelGGL((bn_bwd_partial_win_kernel<2, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
-  else if (pool == 4)
-    hipLaunchKernelGGL((bn_bwd_partial_win_kernel<4, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
-  else if constexpr (std::is_same<TA, float>::value)
-    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(grid), dim3(256), reduce_lds(C), st, a, partial);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(pe_cdiv(C, 4)), dim3(256), 0, st, partial, grid, a.n_in_pix, C,
-                     dgamma, dbeta, c1, c2);
-  PE_LAUNCH_CHECK();
+  if (sums) {
+    if (pool == 1)
+      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<1, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
+    else if (pool == 2)
+      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<2, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
+    else if (pool == 4)
+      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<4, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
+    else if constexpr (std::is_same<TA, float>::value)
+      hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(grid), dim3(256), reduce_lds(C), st, a, partial);
+    PE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(pe_cdiv(C, 4)), dim3(256), 0, st, partial, grid, a.n_in_pix, C,
+                       dgamma, dbeta, c1, c2);
+    PE_LAUNCH_CHECK();
+  }
   const int agrid = win ? ew_grid(pe_cdiv(n_items, 256 / (C / 4)) * 256L) : ew_grid(a.n_in_pix * (C / 4));
   if (tap != nullptr) {                  // (the caller checked tap_geometry_ok: pool is 1, 2 or 4)
     if (pool == 1)
@@ -934,13 +952,13 @@ static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, c
 
 extern "C" int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
                                   const float* mean, const float* invstd, float slope, void* dx, float* dgamma,
-                                  float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
+                                  float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff, int eval_mode,
                                   void* workspace, size_t workspace_bytes, unsigned* amax_out, void* stream) {
   return with_act(act16, [&](auto a) {
     using TA = typename decltype(a)::TA;
     return bn_act_pool_bwd_impl(static_cast<const TA*>(x), static_cast<const TA*>(dy), scale, shift, mean, invstd, slope,
-                                static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, workspace,
-                                workspace_bytes, amax_out, stream);
+                                static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, eval_mode,
+                                workspace, workspace_bytes, amax_out, stream);
   });
 }
 
@@ -1006,7 +1024,8 @@ extern "C" int pe_bn_act_pool_tap_fwd(int act16, const void* x, const float* sca
 extern "C" int pe_bn_act_pool_tap_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
                                       const float* mean, const float* invstd, float slope, void* dx, float* dgamma,
                                       float* dbeta, long rows, int Fin, int C, int pool, long lddy, int coff,
-                                      void* workspace, size_t workspace_bytes, unsigned* amax_out, const void* tap_dy,
+                                      int eval_mode, void* workspace, size_t workspace_bytes, unsigned* amax_out,
+                                      const void* tap_dy,
                                       long tap_lddy, int tap_coff, int tap_pool, const unsigned char* tap_arg,
                                       void* stream) {
   return with_act(act16, [&](auto a) {
@@ -1016,8 +1035,8 @@ extern "C" int pe_bn_act_pool_tap_bwd(int act16, const void* x, const void* dy, 
       return (int)PE_E_UNSUPPORTED;
     const BnTapGrad<TA> tap{static_cast<const TA*>(tap_dy), tap_arg, tap_lddy, tap_coff, (unsigned)(tap_pool / pool)};
     return bn_act_pool_bwd_impl(static_cast<const TA*>(x), static_cast<const TA*>(dy), scale, shift, mean, invstd, slope,
-                                static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, workspace,
-                                workspace_bytes, amax_out, stream, &tap);
+                                static_cast<TA*>(dx), dgamma, dbeta, rows, Fin, C, pool, lddy, coff, eval_mode,
+                                workspace, workspace_bytes, amax_out, stream, &tap);
   });
 }
 

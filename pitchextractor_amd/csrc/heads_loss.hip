@@ -306,14 +306,17 @@ extern "C" size_t pe_head_bwd_workspace_bytes(int D) { return (size_t)kHeadParts
 extern "C" int pe_head_bwd(const float* x, long ldx, const float* w, const float* dy, int n_out, float* dx,
                            long lddx, float* dw, float* db, long R, int D, void* workspace, size_t workspace_bytes,
                            void* stream) {
-  if (!x || !w || !dy || !dx || !dw || !db || R <= 0 || D <= 0 || n_out < 1 || n_out > 8) return PE_E_ARG;
+  const bool sums = dw || db;             // both null: data gradient only (x and the workspace are not read)
+  if (!w || !dy || !dx || R <= 0 || D <= 0 || n_out < 1 || n_out > 8) return PE_E_ARG;
+  if (sums && (!x || !dw || !db)) return PE_E_ARG;
   if ((D & 3) || (ldx & 3) || (lddx & 3)) return PE_E_UNSUPPORTED;
-  if (!workspace || workspace_bytes < pe_head_bwd_workspace_bytes(D)) return PE_E_WORKSPACE;
+  if (sums && (!workspace || workspace_bytes < pe_head_bwd_workspace_bytes(D))) return PE_E_WORKSPACE;
   hipStream_t st = pe_stream(stream);
   long g = (R * (D / 4) + 255) / 256;
   if (g > 16384) g = 16384;
   hipLaunchKernelGGL(head_bwd_dx_kernel, dim3((int)g), dim3(256), 0, st, w, n_out, dy, dx, lddx, R, D);
   PE_LAUNCH_CHECK();
+  if (!sums) return PE_OK;
   double* partial = reinterpret_cast<double*>(workspace);
   const int parts = R < kHeadParts ? (int)R : kHeadParts;
   hipLaunchKernelGGL(head_bwd_dw_partial_kernel, dim3(pe_cdiv(D + 1, 256), parts), dim3(256), 0, st, x, ldx, dy, R, D,

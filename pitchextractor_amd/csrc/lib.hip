@@ -1,7 +1,7 @@
 // Library-level entry points of the C ABI.
 #include "common.h"
 
-extern "C" int pe_abi_version(void) { return 6; }     // bumped with every round that changes a signature
+extern "C" int pe_abi_version(void) { return 7; }     // bumped with every round that changes a signature
 
 extern "C" int pe_device_count(void) {
   int n = 0;

@@ -464,6 +464,7 @@ int launch_layernorm_bwd(const float* dy, const float* dy2, const float* z, cons
   else if (D == 1024) hipLaunchKernelGGL((layernorm_bwd_kernel<4, FUSED>), grid, dim3(256), 0, st, dy, dy2, z, mean, rstd, gamma, dz, mask, scale, dz_drop, partial, rows);
   else return PE_E_UNSUPPORTED;
   PE_LAUNCH_CHECK();
+  if (!dgamma) return PE_OK;             // data gradient only: the per-wave partials stay in the workspace, unreduced
   hipLaunchKernelGGL(layernorm_bwd_final_kernel, dim3(pe_cdiv(2 * D, 4)), dim3(256), 0, st, partial, kLnBwdBlocks * 4, D,
                      dgamma, dbeta);
   PE_LAUNCH_CHECK();
@@ -497,7 +498,7 @@ extern "C" size_t pe_layernorm_bwd_workspace_bytes(int D) { return (size_t)kLnBw
 extern "C" int pe_layernorm_bwd(const float* dy, const float* z, const float* mean, const float* rstd,
                                 const float* gamma, float* dz, float* dgamma, float* dbeta, long rows, int D,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (!dy || !z || !mean || !rstd || !gamma || !dz || !dgamma || !dbeta || rows <= 0) return PE_E_ARG;
+  if (!dy || !z || !mean || !rstd || !gamma || !dz || (!dgamma != !dbeta) || rows <= 0) return PE_E_ARG;
   if (!workspace || workspace_bytes < pe_layernorm_bwd_workspace_bytes(D)) return PE_E_WORKSPACE;
   return launch_layernorm_bwd<false>(dy, nullptr, z, mean, rstd, gamma, dz, nullptr, 1.f, nullptr, dgamma, dbeta, rows,
                                      D, reinterpret_cast<float*>(workspace), pe_stream(stream));
@@ -508,7 +509,7 @@ extern "C" int pe_layernorm_bwd_fused(const float* dy, const float* dy2, const f
                                       const unsigned char* drop_mask, float p, float* dz_drop, float* dgamma,
                                       float* dbeta, long rows, int D, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  if (!dy || !z || !mean || !rstd || !gamma || !dz || !dgamma || !dbeta || rows <= 0) return PE_E_ARG;
+  if (!dy || !z || !mean || !rstd || !gamma || !dz || (!dgamma != !dbeta) || rows <= 0) return PE_E_ARG;
   if ((drop_mask != nullptr) != (dz_drop != nullptr)) return PE_E_ARG;
   if (drop_mask && (p <= 0.f || p >= 1.f)) return PE_E_ARG;
   if (!workspace || workspace_bytes < pe_layernorm_bwd_workspace_bytes(D)) return PE_E_WORKSPACE;

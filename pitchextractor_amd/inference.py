@@ -42,9 +42,11 @@ def infer_model_config(model_state: dict) -> tuple[int, dict]:
     return num_class, cfg
 
 
-def load_model(checkpoint_path, device="cuda", sequence_model_config: dict | None = None) -> JDCNet:
+def load_model(checkpoint_path, device="cuda", sequence_model_config: dict | None = None, frozen=False) -> JDCNet:
     """Build a ``JDCNet`` for a reference-format checkpoint ({"model": state_dict, ...} or a bare state dict),
-    load it non-strictly and put it in eval mode on ``device``."""
+    load it non-strictly and put it in eval mode on ``device``.  ``frozen``: also ``requires_grad_(False)``, the
+    form a loss network takes (StyleTTS / StarGANv2-VC): a backward through it then computes the gradient with respect to
+    its input and nothing else (``JDCNet.is_frozen``)."""
     path = Path(checkpoint_path)
     if not path.is_file():
         raise FileNotFoundError(f"Checkpoint not found: {path}")
@@ -58,7 +60,8 @@ def load_model(checkpoint_path, device="cuda", sequence_model_config: dict | Non
     cfg.update(sequence_model_config or {})
     model = JDCNet(num_class=num_class, sequence_model_config=cfg)
     model.load_state_dict(state, strict=False)
-    return model.to(device).eval()
+    model = model.to(device).eval()
+    return model.requires_grad_(False) if frozen else model
 
 
 def waveform_to_mel(audio, mel_transform: MelSpectrogram | None = None, device="cuda") -> torch.Tensor:

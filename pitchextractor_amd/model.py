@@ -24,6 +24,7 @@ import os
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -202,13 +203,31 @@ def _flat2(t):
     return t.view(-1, t.shape[-1])
 
 
+class _NoGrads:
+    """Stands in for the gradient views of a frozen network (no parameter requires grad): every slot is None, which
+    the fused passes read as "data gradient only"."""
+
+    def __getitem__(self, _param):
+        return None
+
+
+def _bn_slots(grads, mod: _BatchNorm, st):
+    """(dgamma, dbeta) targets of a BatchNorm backward.  A frozen network has none; on batch statistics the input
+    gradient still needs the two sums, which then land in scratch."""
+    dg, db = grads[mod.weight], grads[mod.bias]
+    if dg is None and not st.eval:
+        dg, db = torch.empty((2, mod.weight.numel()), dtype=torch.float32, device=mod.weight.device)
+    return dg, db
+
+
 def _no_amax(_param):
     return None
 
 
-def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None, wa=_no_amax, tap=None):
+def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None, wa=_no_amax, tap=None, frozen=False):
     """x [B,T,F,Cin] -> [B,T,F/pool,Cout]; returns (out, saved, BatchNorm partials of out or None).  ``tap``
-    (ops.Tap): the detector tap of x, taken by the pass that reads x here."""
+    (ops.Tap): the detector tap of x, taken by the pass that reads x here.  ``frozen``: no weight gradient will be
+    asked for, so the two tensors only those read are not kept."""
     s = _Ctx()
     s.x = x
     s.bn_pre = _bn(blk.pre_conv[0], x, train, x_stats)
@@ -225,32 +244,37 @@ def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None,
     wf3, s.wd3 = ops.conv3x3_repack(blk.conv[3].weight, True, need_grad, amax=wa(blk.conv[3].weight))
     _, out_stats = ops.conv3x3_fwd(s.a, wf3, out=out, accumulate=True, bn_stats=train,   # conv(x) + conv1by1(x), model.py:171-172
                                    amax=s.am_a)
+    if frozen:
+        s.p = s.a = None
     return out, s, out_stats
 
 
 def _res_backward(blk: _ResBlock, s, d_out, pool, slope, grads, side, am_do=None, wa=_no_amax, tap=None):
     """d_out: grad of the block output (am_do: its absmax word if the producer left one).  Returns (grad wrt the block
-    input (dense, overwritten), its absmax word).  The three weight gradients go through `side` (_SideWork).  ``tap``
-    (ops.Tap with its gradient): the detector tap of the block input, whose gradient joins the returned one."""
+    input (dense, overwritten), its absmax word).  The three weight gradients go through `side` (_SideWork; None for a
+    frozen network: there are none).  ``tap`` (ops.Tap with its gradient): the detector tap of the block input, whose
+    gradient joins the returned one."""
     if am_do is None:
         am_do = ops.amax_for(d_out)
-    side.run(lambda: (ops.conv3x3_wgrad(s.a, d_out, grads[blk.conv[3].weight], amax_x=s.am_a, amax_dy=am_do),
-                      ops.gemm_tn(_flat2(d_out), _flat2(s.p), out=grads[blk.conv1by1.weight].view(blk.cout, blk.cin),
-                                  amax_a=am_do, amax_b=s.am_p)),
-             d_out, am_do, on=OVERLAP_CONV_WGRAD)
+    if side is not None:
+        side.run(lambda: (ops.conv3x3_wgrad(s.a, d_out, grads[blk.conv[3].weight], amax_x=s.am_a, amax_dy=am_do),
+                          ops.gemm_tn(_flat2(d_out), _flat2(s.p), out=grads[blk.conv1by1.weight].view(blk.cout, blk.cin),
+                                      amax_a=am_do, amax_b=s.am_p)),
+                 d_out, am_do, on=OVERLAP_CONV_WGRAD)
     with ops.timer_tag("dgrad"):
         d_a = ops.conv3x3_fwd(d_out, s.wd3, amax=am_do)
     am_dc = ops.amax_word()
-    d_c = ops.bn_act_pool_bwd(s.c, d_a, s.bn_mid, grads[blk.conv[1].weight], grads[blk.conv[1].bias], pool=1,
+    d_c = ops.bn_act_pool_bwd(s.c, d_a, s.bn_mid, *_bn_slots(grads, blk.conv[1], s.bn_mid), pool=1,
                               slope=slope, dx=d_a, amax_out=am_dc)
-    side.run(lambda: ops.conv3x3_wgrad(s.p, d_c, grads[blk.conv[0].weight], amax_x=s.am_p, amax_dy=am_dc), d_c, am_dc,
-             on=OVERLAP_CONV_WGRAD)
+    if side is not None:
+        side.run(lambda: ops.conv3x3_wgrad(s.p, d_c, grads[blk.conv[0].weight], amax_x=s.am_p, amax_dy=am_dc), d_c,
+                 am_dc, on=OVERLAP_CONV_WGRAD)
     with ops.timer_tag("dgrad"):
         d_p = ops.conv3x3_fwd(d_c, s.wd0, amax=am_dc)
     w1t = ops.transpose2d(blk.conv1by1.weight.view(blk.cout, blk.cin))
     ops.gemm_nt(_flat2(d_out), w1t, out=_flat2(d_p), accumulate=True, amax_a=am_do, amax_b=wa(blk.conv1by1.weight))
     am_dx = ops.amax_word()
-    return ops.bn_act_pool_bwd(s.x, d_p, s.bn_pre, grads[blk.pre_conv[0].weight], grads[blk.pre_conv[0].bias],
+    return ops.bn_act_pool_bwd(s.x, d_p, s.bn_pre, *_bn_slots(grads, blk.pre_conv[0], s.bn_pre),
                                pool=pool, slope=slope, amax_out=am_dx, tap=tap), am_dx
 
 
@@ -288,9 +312,10 @@ def _dropout_bwd(dy2d, p, mask, out2d=None):
     return out
 
 
-def _lstm_forward(models, xs, train, need_grad, drop: _DropoutCfg, wa=_no_amax):
+def _lstm_forward(models, xs, train, need_grad, drop: _DropoutCfg, wa=_no_amax, frozen=False):
     """models: list of SequenceModel (identical shapes); xs: list of [B,T,in].  One launch per time step
-    advances every (model, direction) cell of a layer together."""
+    advances every (model, direction) cell of a layer together.  ``frozen``: the layer inputs and outputs, which only
+    the weight gradients read, are not kept."""
     m0 = models[0].model
     H, L, ND = m0.hidden_size, m0.num_layers, m0.num_dirs
     B, T = xs[0].shape[:2]
@@ -324,6 +349,8 @@ def _lstm_forward(models, xs, train, need_grad, drop: _DropoutCfg, wa=_no_amax):
             lay.mask.append((p, mask))
             nxt.append(yd.view(B, T, ND * H))
         cur = nxt
+        if frozen:
+            lay.x = lay.y = None
         saved.append(lay if need_grad else None)
     return cur, saved
 
@@ -394,7 +421,7 @@ FOLD_TAPS = os.environ.get("PE_FOLD_TAPS", "1") != "0"
 
 def _lstm_backward(models, saved, dys, grads, side, wa=_no_amax):
     """dys: list of [B,T,ND*H] grads of the top layer outputs.  Returns grads of the inputs.  Weight / bias gradients
-    go through `side` (_SideWork) and are NOT joined here."""
+    go through `side` (_SideWork; None for a frozen network: there are none) and are NOT joined here."""
     m0 = models[0].model
     H, L, ND = m0.hidden_size, m0.num_layers, m0.num_dirs
     B, T = dys[0].shape[:2]
@@ -423,7 +450,7 @@ def _lstm_backward(models, saved, dys, grads, side, wa=_no_amax):
         # the data gradients first (the next layer's recurrence waits for them) ...
         dxs = []
         for mi, sm in enumerate(models):
-            dx = torch.empty_like(lay.x[mi])
+            dx = torch.empty((B, T, sm.model.cell(layer, 0)[0].shape[1]), dtype=torch.float32, device=dev)
             for d in range(ND):
                 w_ih = sm.model.cell(layer, d)[0]
                 ops.gemm_nt(_flat2(lay.gates[mi * ND + d]), ops.transpose2d(w_ih), out=_flat2(dx), accumulate=(d > 0),
@@ -444,7 +471,8 @@ def _lstm_backward(models, saved, dys, grads, side, wa=_no_amax):
                                       amax_dg=am_dg[mi * ND + d])
                     ops.colsum(brows[mi * ND + d] if have_db else dg2, grads[b_ih], grads[b_hh])
 
-        side.run(weight_grads, brows, am_dg, on=OVERLAP_LSTM_WGRAD)   # (kept alive until the side stream has read them)
+        if side is not None:
+            side.run(weight_grads, brows, am_dg, on=OVERLAP_LSTM_WGRAD)   # (kept alive until the side stream has read them)
         dys = dxs
     return dys
 
@@ -485,8 +513,9 @@ def _residual_norm_bwd(dy, dy_add, st, norm, g, p, mask):
     return dsum, _dropout_bwd(dsum, p, mask)
 
 
-def _tf_forward(sm, x, train, need_grad, drop: _DropoutCfg):
-    """SequenceModel(transformer).forward (model.py:253-255) for one branch.  x [B,T,D] -> [B,T,D]."""
+def _tf_forward(sm, x, train, need_grad, drop: _DropoutCfg, frozen=False):
+    """SequenceModel(transformer).forward (model.py:253-255) for one branch.  x [B,T,D] -> [B,T,D].  ``frozen``: the
+    operands only the weight gradients read are not kept."""
     B, T, D = x.shape
     H = sm.nhead
     dh = D // H
@@ -529,13 +558,16 @@ def _tf_forward(sm, x, train, need_grad, drop: _DropoutCfg):
             c.a, c.mask_f = _dropout(drop, ops.gelu_fwd(c.h), p)
         ff = ops.gemm_nt(c.a, lyr.linear2.weight, bias0=lyr.linear2.bias)
         y, c.ln2, c.mask2 = _residual_norm(drop, x1, ff, lyr.norm2, p)
+        if frozen:
+            c.x = c.x1 = c.a = None
         saved.layers.append(c)
     saved.p, saved.shape = p, (B, T, D)
     return y.view(B, T, D), (saved if need_grad else None)
 
 
 def _tf_backward(sm, saved, dy, g, side):
-    """Backward of one Transformer branch; the weight / bias gradients go through `side` (_SideWork)."""
+    """Backward of one Transformer branch; the weight / bias gradients go through `side` (_SideWork; None for a frozen
+    network: there are none)."""
     B, T, D = saved.shape
     H = sm.nhead
     dh = D // H
@@ -550,21 +582,24 @@ def _tf_backward(sm, saved, dy, g, side):
         att = lyr.self_attn
         # y = LN2(x1 + dropout2(ff))
         dsum, dff = _residual_norm_bwd(dy, dres, c.ln2, lyr.norm2, g, p, c.mask2)
-        side.run(lambda: (ops.gemm_tn(dff, c.a, out=g[lyr.linear2.weight]), ops.colsum(dff, g[lyr.linear2.bias])),
-                 dff, on=OVERLAP_TF_WGRAD)
+        if side is not None:
+            side.run(lambda: (ops.gemm_tn(dff, c.a, out=g[lyr.linear2.weight]), ops.colsum(dff, g[lyr.linear2.bias])),
+                     dff, on=OVERLAP_TF_WGRAD)
         da = ops.gemm_nt(dff, ops.transpose2d(lyr.linear2.weight))
         if c.mask_f is not None and TF_FUSE_DROPOUT:
             dh_ = ops.gelu_dropout_bwd(c.h, da, c.mask_f, p, out=da)
         else:
             da = _dropout_bwd(da, p, c.mask_f)
             dh_ = ops.gelu_bwd(c.h, da, out=da)
-        side.run(lambda: (ops.gemm_tn(dh_, c.x1, out=g[lyr.linear1.weight]), ops.colsum(dh_, g[lyr.linear1.bias])),
-                 dh_, on=OVERLAP_TF_WGRAD)
+        if side is not None:
+            side.run(lambda: (ops.gemm_tn(dh_, c.x1, out=g[lyr.linear1.weight]), ops.colsum(dh_, g[lyr.linear1.bias])),
+                     dh_, on=OVERLAP_TF_WGRAD)
         dx1 = ops.gemm_nt(dh_, ops.transpose2d(lyr.linear1.weight))
         # x1 = LN1(x + dropout1(sa)); dsum is the residual branch's share of d(x1)
         dsum1, dsa = _residual_norm_bwd(dx1, dsum, c.ln1, lyr.norm1, g, p, c.mask1)
-        side.run(lambda: (ops.gemm_tn(dsa, c.o, out=g[att.out_proj.weight]), ops.colsum(dsa, g[att.out_proj.bias])),
-                 dsa, on=OVERLAP_TF_WGRAD)
+        if side is not None:
+            side.run(lambda: (ops.gemm_tn(dsa, c.o, out=g[att.out_proj.weight]), ops.colsum(dsa, g[att.out_proj.bias])),
+                     dsa, on=OVERLAP_TF_WGRAD)
         do = ops.gemm_nt(dsa, ops.transpose2d(att.out_proj.weight))                        # [R, D] merged heads
         if c.fused:
             dqkv = ops.attn_bwd(c.qkv, c.o, do, c.lse, c.mask_p, B, T, H, scale, p if c.mask_p is not None else 0.0)
@@ -580,8 +615,9 @@ def _tf_backward(sm, saved, dy, g, side):
             ops.softmax_bwd_(c.P, dP, scale)                                               # dP <- dS (incl. 1/sqrt(dh))
             ops.bgemm(1, dP, pview, kv, hview, dq, hview, H, B * H, T, dh, T)              # dQ = dS K
             ops.bgemm(2, dP, pview, qv, hview, dk, hview, H, B * H, T, dh, T)              # dK = dS^T Q
-        side.run(lambda: (ops.gemm_tn(dqkv, c.x, out=g[att.in_proj_weight]), ops.colsum(dqkv, g[att.in_proj_bias])),
-                 dqkv, on=OVERLAP_TF_WGRAD)
+        if side is not None:
+            side.run(lambda: (ops.gemm_tn(dqkv, c.x, out=g[att.in_proj_weight]), ops.colsum(dqkv, g[att.in_proj_bias])),
+                     dqkv, on=OVERLAP_TF_WGRAD)
         dy = ops.gemm_nt(dqkv, ops.transpose2d(att.in_proj_weight))
         dres = dsum1
     if TF_FUSE_DROPOUT:
@@ -598,6 +634,8 @@ class _JDCFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, x, _anchor, need_grad):
         ctx.net, ctx.recompute = net, None
+        ctx.frozen = frozen = net.is_frozen()   # no parameter takes a gradient: the backward is the data chain alone
+        ctx.x_meta = (x.shape, x.dtype)
         if need_grad and net.checkpoint_forward:
             # Whole-model gradient checkpointing, the reference's granularity (trainer.py:226-233 wraps the
             # entire model in ONE checkpoint segment): this pass keeps nothing but the input and the dropout
@@ -609,13 +647,14 @@ class _JDCFunction(torch.autograd.Function):
             out_cls, out_det, _ = net._forward_impl(x, False)
             ctx.saved = None
             return out_cls, out_det
-        out_cls, out_det, saved = net._forward_impl(x, need_grad)
+        out_cls, out_det, saved = net._forward_impl(x, need_grad, frozen)
         ctx.saved = saved
         if net.keep_last_context:
             net.last_context = saved
         return out_cls, out_det
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, d_cls, d_det):
         net = ctx.net
         if ctx.recompute is not None:
@@ -627,16 +666,19 @@ class _JDCFunction(torch.autograd.Function):
             try:
                 # like torch.utils.checkpoint under the reference, the second forward runs in train mode again:
                 # BatchNorm running statistics take a second momentum update with the same batch statistics
-                _, _, ctx.saved = net._forward_impl(x, True)
+                _, _, ctx.saved = net._forward_impl(x, True, ctx.frozen)
             finally:
                 drop.seed, drop.offset = now[0], max(now[1], drop.offset)
                 net.train(now[2])
             ctx.recompute = None
         if ctx.saved is None:
             raise RuntimeError("JDCNet backward called on a forward that ran without gradient bookkeeping")
-        net._backward_impl(ctx.saved, d_cls, d_det)
+        dx = net._backward_impl(ctx.saved, d_cls, d_det, want_dx=ctx.needs_input_grad[1])
         ctx.saved = None
-        return None, None, None, None
+        if dx is not None:                      # d loss / d x in x's shape (B,1,T,F) and dtype
+            shape, dtype = ctx.x_meta
+            dx = dx.view(shape).to(dtype)
+        return None, dx, None, None
 
 
 class JDCNet(nn.Module):
@@ -669,6 +711,7 @@ class JDCNet(nn.Module):
         self.keep_last_context = False      # tests: expose the saved tensors (dropout masks) of the last forward
         self.checkpoint_forward = False     # Trainer(gradient_checkpointing=True): recompute the forward in backward
         self.last_context = None
+        self.backward_status = None         # frozen network: the persistent-LSTM fault word of the last backward
         self._init_weights()
         self._flat = None
         self._grad_flat = None
@@ -785,8 +828,21 @@ class JDCNet(nn.Module):
         fused AdamW skips its update on the device when it is set; the trainer reads it with the loss scalars."""
         return self.flat_gradients()[self._status_off:self._status_off + 1]
 
-    def _write_status(self, dev):
-        slot, word = self.status_slot(), ops.persistent_lstm_error_word(dev)
+    def is_frozen(self) -> bool:
+        """True if no parameter requires grad (``net.requires_grad_(False)``): the network is a fixed differentiable
+        function of its input.  A backward then computes the input gradient alone -- no weight- or bias-gradient
+        kernel, no side stream, no gradient buffer, no data-parallel reduction -- and leaves its status in
+        ``backward_status``.  Partly frozen parameter sets are treated as trainable."""
+        return not any(p.requires_grad for p in self._param_list)
+
+    def _write_status(self, dev, frozen=False):
+        word = ops.persistent_lstm_error_word(dev)
+        if frozen:                          # there is no gradient buffer to carry the word
+            if self.backward_status is None or self.backward_status.device != torch.device(dev):
+                self.backward_status = torch.zeros(1, dtype=torch.float32, device=dev)
+            slot = self.backward_status
+        else:
+            slot = self.status_slot()
         if word is None:
             slot.zero_()
         else:
@@ -809,10 +865,11 @@ class JDCNet(nn.Module):
             raise RuntimeError("JDCNet (HIP) needs device tensors; there is no CPU fallback")
         if x.dim() != 4 or x.shape[1] != 1:
             raise ValueError("expected input of shape (B, 1, T, n_mels)")
-        need_grad = torch.is_grad_enabled() and self.training_graph_wanted
-        return _JDCFunction.apply(self, x, self._flat, need_grad)
+        frozen = self.is_frozen()
+        need_grad = torch.is_grad_enabled() and self.training_graph_wanted and (x.requires_grad or not frozen)
+        return _JDCFunction.apply(self, x, None if frozen else self._flat, need_grad)
 
-    def _forward_impl(self, x, need_grad):
+    def _forward_impl(self, x, need_grad, frozen=False):
         train = self.training
         slope = self.leaky_relu_slope
         self._refresh_weight_amax()
@@ -835,9 +892,9 @@ class JDCNet(nn.Module):
             s.concat = torch.empty((B, T, 2, 640), dtype=s.cb.dtype, device=x.device)  # (bf16 under ops.ACT_BF16)
             s.taps = [ops.Tap(s.concat, tp, coff, want_argmax=need_grad) for tp, coff in ((40, 0), (20, 64), (10, 192))]
         t_cb, t_rb1, t_rb2 = s.taps or (None, None, None)
-        s.rb1, s.r1, st1 = _res_forward(self.res_block1, s.cb, 2, train, need_grad, slope, st_cb, wa, t_cb)
-        s.rb2, s.r2, st2 = _res_forward(self.res_block2, s.rb1, 2, train, need_grad, slope, st1, wa, t_rb1)
-        s.rb3, s.r3, st3 = _res_forward(self.res_block3, s.rb2, 2, train, need_grad, slope, st2, wa, t_rb2)
+        s.rb1, s.r1, st1 = _res_forward(self.res_block1, s.cb, 2, train, need_grad, slope, st_cb, wa, t_cb, frozen)
+        s.rb2, s.r2, st2 = _res_forward(self.res_block2, s.rb1, 2, train, need_grad, slope, st1, wa, t_rb1, frozen)
+        s.rb3, s.r3, st3 = _res_forward(self.res_block3, s.rb2, 2, train, need_grad, slope, st2, wa, t_rb2, frozen)
 
         # pool_block -> channels [384, 640) of the detector concat (model.py:36-41,90,108)
         Fp = s.rb3.shape[2] // 4
@@ -867,10 +924,10 @@ class JDCNet(nn.Module):
 
         models = [self.sequence_classifier, self.sequence_detector]
         if models[0].model_type == "bilstm":
-            (yc, yd), s.lstm = _lstm_forward(models, [seq_c, seq_d], train, need_grad, self.dropout_cfg, wa)
+            (yc, yd), s.lstm = _lstm_forward(models, [seq_c, seq_d], train, need_grad, self.dropout_cfg, wa, frozen)
         else:
-            yc, s.tf_c = _tf_forward(models[0], seq_c, train, need_grad, self.dropout_cfg)
-            yd, s.tf_d = _tf_forward(models[1], seq_d, train, need_grad, self.dropout_cfg)
+            yc, s.tf_c = _tf_forward(models[0], seq_c, train, need_grad, self.dropout_cfg, frozen)
+            yd, s.tf_d = _tf_forward(models[1], seq_d, train, need_grad, self.dropout_cfg, frozen)
         s.yc, s.yd = yc, yd
         D = yc.shape[-1]
         if self.num_class == 1:
@@ -880,10 +937,19 @@ class JDCNet(nn.Module):
             out_cls = out_cls.view(B, T, self.num_class)
         out_det = ops.head_fwd(yd.view(-1, D), self.detector.weight, self.detector.bias).view(B, T)
         s.shape = (B, T, F)
+        s.frozen, s.act_dtype = frozen, s.concat.dtype
+        if frozen:                          # operands of weight gradients only: the first conv's input, the second
+            s.x_btf = s.a0 = s.concat = None    # conv's input and the detector conv's input (the taps wrote it)
+            for t in s.taps or ():
+                t.out = None
         return out_cls, out_det, (s if need_grad else None)
 
-    def _backward_impl(self, s, d_cls, d_det):
-        g = self._grad_views()
+    def _backward_impl(self, s, d_cls, d_det, want_dx=False):
+        """Gradients of every parameter into the flat gradient buffer; returns d loss / d x [B,T,F] float32 if
+        ``want_dx``, else None.  For a forward of a frozen network (``is_frozen``) only the data-gradient chain runs."""
+        frozen = s.frozen
+        g = _NoGrads() if frozen else self._grad_views()
+        dp = None if frozen else self._dp
         slope = self.leaky_relu_slope
         B, T, F = s.shape
         D = s.yc.shape[-1]
@@ -899,53 +965,56 @@ class JDCNet(nn.Module):
             dyc = ops.head_bwd(s.yc.view(-1, D), cls.weight, d_cls.view(-1), g[cls.weight], g[cls.bias])
         else:
             d2 = d_cls.view(-1, self.num_class)
-            ops.gemm_tn(d2, s.yc.view(-1, D), out=g[cls.weight])
-            ops.colsum(d2, g[cls.bias])
+            if not frozen:
+                ops.gemm_tn(d2, s.yc.view(-1, D), out=g[cls.weight])
+                ops.colsum(d2, g[cls.bias])
             dyc = ops.gemm_nt(d2, ops.transpose2d(cls.weight))
         dyd = ops.head_bwd(s.yd.view(-1, D), det.weight, d_det.view(-1), g[det.weight], g[det.bias])
 
         models = [self.sequence_classifier, self.sequence_detector]
-        side = _SideWork(dev)               # weight-gradient kernels of the whole backward; joined once, at the end
+        # weight-gradient kernels of the whole backward; joined once, at the end (a frozen network has none)
+        side = None if frozen else _SideWork(dev)
         if models[0].model_type == "bilstm":
             dseq_c, dseq_d = _lstm_backward(models, s.lstm, [dyc.view(B, T, D), dyd.view(B, T, D)], g, side,
                                             self.weight_amax)
-            if LSTM_WGRAD_JOIN_EARLY:
+            if LSTM_WGRAD_JOIN_EARLY and side is not None:
                 side.join()
         else:
             dseq_d = _tf_backward(models[1], s.tf_d, dyd.view(B, T, D), g, side)
             dseq_c = _tf_backward(models[0], s.tf_c, dyc.view(B, T, D), g, side)
 
-        self._write_status(dev)             # every recurrence of this step has been queued: its fault word is final
-        if self._dp is not None:            # temporal heads + output heads are final once the side stream has
+        self._write_status(dev, frozen)     # every recurrence of this step has been queued: its fault word is final
+        if dp is not None:                  # temporal heads + output heads are final once the side stream has
             # finished what is queued on it so far: the collectives are issued from that stream, the main stream does not wait
-            self._dp.reduce_range(self._seq_offset(), self._grad_flat.numel(), after=side.pending_stream())
+            dp.reduce_range(self._seq_offset(), self._grad_flat.numel(), after=side.pending_stream())
 
         # detector branch (model.py:103-112)
         p_blk = self.block_dropout
-        d_ddrop = torch.empty((B, T, 2, 256), dtype=s.concat.dtype, device=dev)
+        d_ddrop = torch.empty((B, T, 2, 256), dtype=s.act_dtype, device=dev)
         ops.seq_to_nhwc(dseq_d, d_ddrop, 256)
         d_dact = _dropout_bwd(_flat2(d_ddrop), p_blk, s.mask_det).view(B, T, 2, 256)
         bn1 = self.detector_conv[1]
-        d_dconv = ops.bn_act_pool_bwd(s.dconv, d_dact, s.bnd, g[bn1.weight], g[bn1.bias], pool=1, slope=slope)
+        d_dconv = ops.bn_act_pool_bwd(s.dconv, d_dact, s.bnd, *_bn_slots(g, bn1, s.bnd), pool=1, slope=slope)
         wdet = self.detector_conv[0].weight
-        side.run(lambda: ops.gemm_tn(_flat2(d_dconv), s.concat.view(-1, 640), out=g[wdet].view(256, 640)), d_dconv,
-                 on=OVERLAP_CONV_WGRAD)
+        if side is not None:
+            side.run(lambda: ops.gemm_tn(_flat2(d_dconv), s.concat.view(-1, 640), out=g[wdet].view(256, 640)), d_dconv,
+                     on=OVERLAP_CONV_WGRAD)
         d_concat = ops.gemm_nt(_flat2(d_dconv), ops.transpose2d(wdet.view(256, 640)), amax_b=self.weight_amax(wdet))
         d_concat = d_concat.view(B, T, 2, 640)
         # classifier branch joins at the pool_block output (channels 384..639 of the concat)
         ops.seq_to_nhwc(dseq_c, d_concat, 256, coff=384, accumulate=True)
-        d_pool = torch.empty((B, T, 2, 256), dtype=s.concat.dtype, device=dev)
+        d_pool = torch.empty((B, T, 2, 256), dtype=s.act_dtype, device=dev)
         _dropout_bwd(d_concat.view(-1, 640)[:, 384:640], p_blk if s.mask_pool is not None else 0.0, s.mask_pool,
                      out2d=_flat2(d_pool))
         bnp = self.pool_block[0]
         am3 = ops.amax_word()
-        d_rb3 = ops.bn_act_pool_bwd(s.rb3, d_pool, s.bnp, g[bnp.weight], g[bnp.bias], pool=4, slope=slope, amax_out=am3)
+        d_rb3 = ops.bn_act_pool_bwd(s.rb3, d_pool, s.bnp, *_bn_slots(g, bnp, s.bnp), pool=4, slope=slope, amax_out=am3)
 
-        cuts = self._dp_cuts if self._dp is not None else None
+        cuts = self._dp_cuts if dp is not None else None
 
         def block_done(k):                  # gradients of flat range [cuts[k], cuts[k+1]) are queued: reduce them
             if cuts is not None:
-                self._dp.reduce_range(cuts[k], cuts[k + 1], after=side.pending_stream())
+                dp.reduce_range(cuts[k], cuts[k + 1], after=side.pending_stream())
 
         # each block-input gradient leaves its absmax word behind; the detector tap's max-pool gradient is added by the
         # same pass (folded taps) or in place afterwards, and the values it rewrote are merged into the same word
@@ -967,12 +1036,17 @@ class JDCNet(nn.Module):
             ops.maxpool_bwd_add(s.cb, d_concat, d_cb, 40, coff=0, amax_out=am_dcb, argmax=s.arg_cb)
 
         cbk = self.conv_block
-        side.run(lambda: ops.conv3x3_wgrad(s.a0, d_cb, g[cbk[3].weight], amax_x=s.am_a0, amax_dy=am_dcb), d_cb, am_dcb,
-                 on=OVERLAP_CONV_WGRAD)
+        if side is not None:
+            side.run(lambda: ops.conv3x3_wgrad(s.a0, d_cb, g[cbk[3].weight], amax_x=s.am_a0, amax_dy=am_dcb), d_cb,
+                     am_dcb, on=OVERLAP_CONV_WGRAD)
         with ops.timer_tag("dgrad"):
             d_a0 = ops.conv3x3_fwd(d_cb, s.wd_cb, amax=am_dcb)
-        d_y0 = ops.bn_act_pool_bwd(s.y0, d_a0, s.bn0, g[cbk[1].weight], g[cbk[1].bias], pool=1, slope=slope, dx=d_a0)
-        ops.conv3x3_c1_wgrad(s.x_btf, d_y0, g[cbk[0].weight])
-        side.join()                             # every weight gradient is final from here on
-        if self._dp is not None:
-            self._dp.reduce_range(0, cuts[1] if cuts is not None else self._seq_offset())
+        d_y0 = ops.bn_act_pool_bwd(s.y0, d_a0, s.bn0, *_bn_slots(g, cbk[1], s.bn0), pool=1, slope=slope, dx=d_a0)
+        if not frozen:
+            ops.conv3x3_c1_wgrad(s.x_btf, d_y0, g[cbk[0].weight])
+        dx = ops.conv3x3_c1_dgrad(d_y0, cbk[0].weight) if want_dx else None
+        if side is not None:
+            side.join()                         # every weight gradient is final from here on
+        if dp is not None:
+            dp.reduce_range(0, cuts[1] if cuts is not None else self._seq_offset())
+        return dx

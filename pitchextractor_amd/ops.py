@@ -527,13 +527,34 @@ def conv3x3_c1_wgrad(x_btf, dy, dw):
     return dw
 
 
+def conv3x3_c1_dgrad(dy, w, out=None):
+    """Data gradient of the first convolution: dy [B,T,F,64] (float32, bfloat16 or float16) -> dx [B,T,F] float32."""
+    _chk(dy.is_cuda and dy.is_contiguous() and dy.dim() == 4 and dy.shape[3] == 64 and dy.dtype in _DGRAD_ACT,
+         "conv3x3_c1_dgrad: dy must be a dense [B,T,F,64] float32 / bfloat16 / float16 device tensor")
+    w = _dense(w, "w")
+    _chk(w.shape == (64, 1, 3, 3) and w.device == dy.device, "first conv is 1 -> 64")
+    B, T, F = dy.shape[:3]
+    if out is None:
+        out = torch.empty((B, T, F), dtype=torch.float32, device=dy.device)
+    _chk(_dense(out, "out").shape == (B, T, F) and out.device == dy.device, "conv3x3_c1_dgrad: out shape")
+    a16 = _DGRAD_ACT[dy.dtype]
+    _call("pe_conv3x3_c1_dgrad", a16, dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, T, F, _s(),
+          work=2.0 * B * T * F * 576, key="pe_conv3x3_c1_dgrad" + ("_a16" if a16 else ""))
+    return out
+
+
+_DGRAD_ACT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # the entry point's act16 values
+
+
 # ------------------------------------------------------------------ BN / pooling / dropout
 class BnState:
-    """Per-call BN tensors: mean, invstd, scale, shift (all [C])."""
+    """Per-call BN tensors: mean, invstd, scale, shift (all [C]).  ``eval``: they are the running statistics and their
+    affine map (bn_eval_affine), so the backward pass has no batch-statistics terms."""
 
-    def __init__(self, C_, device):
+    def __init__(self, C_, device, eval=False):
         buf = torch.empty((4, C_), dtype=torch.float32, device=device)
         self.mean, self.invstd, self.scale, self.shift = buf[0], buf[1], buf[2], buf[3]
+        self.eval = bool(eval)
 
 
 def bn_train_stats(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, partials=None):
@@ -563,11 +584,11 @@ def bn_train_stats(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum
 
 def bn_eval_affine(gamma, beta, running_mean, running_var, eps=1e-5):
     Cc = gamma.numel()
-    st = BnState(Cc, gamma.device)
+    st = BnState(Cc, gamma.device, eval=True)
     for t in (gamma, beta, running_mean, running_var):
         _chk(_dense(t, "bn tensor").numel() == Cc, "bn tensor size")
     _call("pe_bn_eval_affine", gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
-          eps, Cc, st.scale.data_ptr(), st.shift.data_ptr(), _s())
+          eps, Cc, st.scale.data_ptr(), st.shift.data_ptr(), st.mean.data_ptr(), st.invstd.data_ptr(), _s())
     return st
 
 
@@ -628,29 +649,35 @@ def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_o
 def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=0, dx=None, amax_out=None,
                     tap: Tap | None = None):
     """``tap`` (with ``grad`` and ``argmax`` set): dx also takes the gradient of the tap, and ``amax_out`` what
-    ``maxpool_bwd_add`` would have merged into it."""
+    ``maxpool_bwd_add`` would have merged into it.  The mode follows ``st.eval``; with an eval-mode state ``dgamma`` and
+    ``dbeta`` may both be None (input gradient only: no per-channel reduction, no workspace)."""
     x = _actd(x, "x")
     B, T, F, Cc = x.shape
     ld = _slice_target(dy, B, T, F // pool, Cc, coff)
     if dx is None:
         dx = torch.empty_like(x)
     _chk(_actd(dx, "dx").shape == x.shape, "dx shape")
-    _chk(_dense(dgamma, "dgamma").numel() == Cc and _dense(dbeta, "dbeta").numel() == Cc, "dgamma/dbeta size")
-    lib = _lib.load()
-    ws = workspace(lib.pe_bn_workspace_bytes(Cc) + 8 * Cc, x.device)
+    ev = int(st.eval)
+    if dgamma is None and dbeta is None:
+        _chk(st.eval, "bn_act_pool_bwd: only an eval-mode BatchNorm has an input gradient without dgamma / dbeta")
+        ws_ptr, ws_len = None, 0
+    else:
+        _chk(_dense(dgamma, "dgamma").numel() == Cc and _dense(dbeta, "dbeta").numel() == Cc, "dgamma/dbeta size")
+        ws = workspace(_lib.load().pe_bn_workspace_bytes(Cc) + 8 * Cc, x.device)
+        ws_ptr, ws_len = ws.data_ptr(), ws.numel()
     if tap is not None and tap.argmax is not None and _tap_folded(x, pool, tap, True):
         Ft = F // tap.pool
         _chk(tap.argmax.is_cuda and tap.argmax.dtype == torch.uint8 and tap.argmax.is_contiguous()
              and tap.argmax.shape == (B, T, Ft, Cc), "bn_act_pool_bwd: tap argmax shape")
         tld = _slice_target(tap.grad, B, T, Ft, Cc, tap.coff)
         _call("pe_bn_act_pool_tap_bwd", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-              st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-              B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _lib.ptr(amax_out), tap.grad.data_ptr(), tld,
+              st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), _lib.ptr(dgamma), _lib.ptr(dbeta),
+              B * T, F, Cc, pool, ld, coff, ev, ws_ptr, ws_len, _lib.ptr(amax_out), tap.grad.data_ptr(), tld,
               tap.coff, tap.pool, tap.argmax.data_ptr(), _s(), act16=_act16(x, dy, dx, tap.grad))
         return dx
     _call("pe_bn_act_pool_bwd", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
-          st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-          B * T, F, Cc, pool, ld, coff, ws.data_ptr(), ws.numel(), _lib.ptr(amax_out), _s(), act16=_act16(x, dy, dx))
+          st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), _lib.ptr(dgamma), _lib.ptr(dbeta),
+          B * T, F, Cc, pool, ld, coff, ev, ws_ptr, ws_len, _lib.ptr(amax_out), _s(), act16=_act16(x, dy, dx))
     if tap is not None:
         maxpool_bwd_add(x, tap.grad, dx, tap.pool, coff=tap.coff, amax_out=amax_out, argmax=tap.argmax)
     return dx
@@ -912,7 +939,8 @@ def head_bwd(x2d, w, dy, dw, db, dx=None):
     R, D, ldx = _rows2d(x2d, "x")
     n_out = w.shape[0]
     _chk(_dense(dy, "dy").numel() == R, "head_bwd: dy size")
-    _chk(_dense(dw, "dw").shape == (n_out, D) and _dense(db, "db").numel() == n_out, "head_bwd: grads shape")
+    if dw is not None or db is not None:       # (both None: data gradient only)
+        _chk(_dense(dw, "dw").shape == (n_out, D) and _dense(db, "db").numel() == n_out, "head_bwd: grads shape")
     if dx is None:
         dx = torch.empty((R, D), dtype=torch.float32, device=x2d.device)
     R2, D2, lddx = _rows2d(dx, "dx")
@@ -920,7 +948,7 @@ def head_bwd(x2d, w, dy, dw, db, dx=None):
     lib = _lib.load()
     ws = workspace(lib.pe_head_bwd_workspace_bytes(D), x2d.device)
     _call("pe_head_bwd", x2d.data_ptr(), ldx, w.data_ptr(), dy.data_ptr(), n_out, dx.data_ptr(), lddx,
-          dw.data_ptr(), db.data_ptr(), R, D, ws.data_ptr(), ws.numel(), _s())
+          _lib.ptr(dw), _lib.ptr(db), R, D, ws.data_ptr(), ws.numel(), _s())
     return dx
 
 
@@ -1234,12 +1262,13 @@ def layernorm_bwd(dy2d, st: LnState, gamma, dgamma, dbeta, dz=None, dy_add=None,
     if dz is None:
         dz = torch.empty_like(dy2d)
     _chk(_dense(dz, "dz").shape == (R, D), "layernorm_bwd: dz shape")
-    _chk(_dense(dgamma, "dgamma").numel() == D and _dense(dbeta, "dbeta").numel() == D, "layernorm_bwd: grads")
+    if dgamma is not None or dbeta is not None:    # (both None: data gradient only, the sums are not reduced)
+        _chk(_dense(dgamma, "dgamma").numel() == D and _dense(dbeta, "dbeta").numel() == D, "layernorm_bwd: grads")
     lib = _lib.load()
     ws = workspace(lib.pe_layernorm_bwd_workspace_bytes(D), dy2d.device)
     if dy_add is None and drop_mask is None:
         _call("pe_layernorm_bwd", dy2d.data_ptr(), st.z.data_ptr(), st.mean.data_ptr(), st.rstd.data_ptr(),
-              gamma.data_ptr(), dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), R, D, ws.data_ptr(), ws.numel(),
+              gamma.data_ptr(), dz.data_ptr(), _lib.ptr(dgamma), _lib.ptr(dbeta), R, D, ws.data_ptr(), ws.numel(),
               _s())
         return dz
     if dy_add is not None:
@@ -1251,7 +1280,7 @@ def layernorm_bwd(dy2d, st: LnState, gamma, dgamma, dbeta, dz=None, dy_add=None,
         dz_drop = torch.empty_like(dy2d)
     _call("pe_layernorm_bwd_fused", dy2d.data_ptr(), _lib.ptr(dy_add), st.z.data_ptr(), st.mean.data_ptr(),
           st.rstd.data_ptr(), gamma.data_ptr(), dz.data_ptr(), _lib.ptr(drop_mask), float(p), _lib.ptr(dz_drop),
-          dgamma.data_ptr(), dbeta.data_ptr(), R, D, ws.data_ptr(), ws.numel(), _s())
+          _lib.ptr(dgamma), _lib.ptr(dbeta), R, D, ws.data_ptr(), ws.numel(), _s())
     return dz if drop_mask is None else (dz, dz_drop)
 
 
