@@ -723,7 +723,8 @@ int pe_melody_metrics(const float* f0_pred, const float* f0_ref, const float* f0
  * (fade - 1))) over the head and mirrored over the tail, the tail overwriting an overlap); for rows with noise,
  * scale = float32((rms_s / 10^(snr_db / 20)) / rms_n) with both rms in double over the float32 samples, y = y +
  * float32(noise scale) in float32, skipped when either rms is 0; then with peak = max |y|, y = y / float32(peak + 1e-6)
- * if peak > 0.99.  stats[r] = {peak, rms_s, rms_n (0 without noise), scale (0: no mix)}.  Four launches.
+ * if peak > 0.99.  stats[r] = {peak, rms_s, rms_n (0 without noise), scale (0: no mix)}.  Four launches: the mix of
+ * pe_noise_mix below (one implementation, csrc/snr_mix.h), in place and under the fade.
  * pe_stim_reference: the reference's sample_reference_f0 without a per-sample curve: frame_table (n_rows x 2 int64,
  * host copy host_frame_table) = per row {frame prefix, frames}; frame_times (device doubles, made by the caller);
  * ref[f] = float32(np.interp(tau, float32(t), float32(curve))), a tone's curve being float32(frequency).
@@ -785,7 +786,8 @@ int pe_dynamic_metrics(const float* f0_pred, const float* f0_ref, const long* tr
  * scale = float32((rms_s / 10^(snr_db / 20)) / rms_n), y = x + float32(noise scale) in float32; y = x and scale = 0
  * when either rms is 0.  With peak = max |y|: y = y / float32(peak + 1e-6) if peak_normalize and peak > 0.99.
  * stats[r] = {peak, rms_s, rms_n, scale}, all 0 for a row of length 0.  snr_db: one double per row on the device,
- * host_snr_db its host copy, PE_E_ARG unless every one is finite.  Five launches (four without peak_normalize). */
+ * host_snr_db its host copy, PE_E_ARG unless every one is finite.  Five launches (four without peak_normalize): the
+ * mix that pe_stim_finish runs in place (one implementation, csrc/snr_mix.h), the row peaks in a launch of their own. */
 int pe_noise_plan_fields(void);
 int pe_noise_param_fields(void);
 int pe_noise_plan(int n_rows, const long* n, const long* y_off, const long* warmup, const long* seeds,

@@ -16,21 +16,19 @@
 //           piece scan again with thread 0 started from the carry, each thread running its samples from the state
 //           before it.  Three, and no workgroup waits on another.
 //   bed:    y[i] = bed[(start + i) mod L].  One.
-//   mix:    piece sums of squares, row rms and scale, y = x + float32(noise scale) and piece peaks, row peak,
-//           normalisation.  Five.
+//   mix:    the mix at an SNR of snr_mix.h (piece sums of squares, row rms and scale, y = x + float32(noise scale)
+//           and piece peaks, row peak, normalisation), which pe_stim_finish runs too.  Five, four without the peak
+//           rule: a row here may have thousands of pieces, so the row peaks take a launch of their own.
 // Sums and recurrences are double with contraction off; nothing a row computes depends on where the row lies or on
 // its neighbours: a row's result is the same alone, packed at an odd offset or padded.
 #include <math.h>
 #include "common.h"
-#include "dsp.h"
+#include "snr_mix.h"
 
 using namespace pe;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRun = 8;                          // consecutive samples of one thread
-constexpr int kPiece = kRun * kThreads;          // scan / reduction piece S = 2048 generated samples
 constexpr int kSteps = 8;                        // scan steps over the threads: 2^kSteps == kThreads
 constexpr int kMaxSections = 8;
 constexpr long kMaxSamples = (1L << 31) - 8;
@@ -43,7 +41,13 @@ enum { C_D0, C_D1, C_NSEC, C_SPARE, C_SECTIONS };
 enum { Q_A, Q_B, Q_POW, Q_PIECE = Q_POW + kSteps, Q_SPARE, Q_K };
 constexpr int C_K = C_SECTIONS + kMaxSections * Q_K;
 enum { B_OFF, B_LEN, B_START, B_K };             // a row's bed: offset in the bed audio, length, first sample
-enum { ST_PEAK, ST_RMS_S, ST_RMS_N, ST_SCALE, ST_K };
+
+// The plan as snr_mix.h reads it: x -> y without a fade, the noise where the row lies, one snr_db per row in an array;
+// a row may have thousands of pieces.  (The plan's pieces count the generated samples, the mix's the row's n.)
+struct NoiseMixRows {
+  static constexpr int kFields = N_K, kPieceOffset = N_POFF, kFade = -1, kNoiseOffset = -1, kSnrStride = 1;
+  static constexpr bool kInPlace = false, kPeakLaunch = true;
+};
 
 long pieces_of(long n, long gen) { return n > 0 ? (gen + kPiece - 1) / kPiece : 0; }
 
@@ -98,20 +102,6 @@ bool colour_ok(const double* hp) {
   }
   if (!fill_colour(coeffs, n_sections, again)) return false;
   return memcmp(again, hp, sizeof(again)) == 0;
-}
-
-// Sum of one double per thread over the workgroup (a fixed tree); every thread gets it.
-__device__ __forceinline__ double block_sum_d(double v, double* s_sum, int tid) {
-#pragma clang fp contract(off)
-  s_sum[tid] = v;
-  __syncthreads();
-  for (int st = kThreads / 2; st > 0; st >>= 1) {
-    if (tid < st) s_sum[tid] += s_sum[tid + st];
-    __syncthreads();
-  }
-  const double out = s_sum[0];
-  __syncthreads();
-  return out;
 }
 
 // ---- white ---------------------------------------------------------------------------------------------------------
@@ -261,136 +251,6 @@ __global__ __launch_bounds__(kThreads) void noise_bed_kernel(const long* __restr
   }
 }
 
-// ---- mix -----------------------------------------------------------------------------------------------------------
-// part[g] = {sum of x^2, sum of noise^2, -} of the piece: a thread adds its kRun samples in order, the threads a tree
-__global__ __launch_bounds__(kThreads) void noise_sums_kernel(const long* __restrict__ meta,
-                                                              const float* __restrict__ x,
-                                                              const float* __restrict__ noise, int n_rows, long pieces,
-                                                              double* __restrict__ part) {
-#pragma clang fp contract(off)
-  __shared__ double s_sum[kThreads];
-  const int tid = threadIdx.x;
-  for (long g = blockIdx.x; g < pieces; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, N_K, N_POFF, g);
-    const long* m = meta + (long)row * N_K;
-    const long n = m[N_N], i0 = (g - m[N_POFF]) * kPiece + (long)tid * kRun;
-    const float* xr = x + m[N_OFF];
-    const float* nr = noise + m[N_OFF];
-    double ss = 0.0, sn = 0.0;
-#pragma unroll
-    for (int u = 0; u < kRun; ++u)
-      if (i0 + u < n) {
-        const double v = (double)xr[i0 + u], q = (double)nr[i0 + u];
-        ss += v * v;
-        sn += q * q;
-      }
-    const double tss = block_sum_d(ss, s_sum, tid), tsn = block_sum_d(sn, s_sum, tid);
-    if (tid == 0) { part[3 * g] = tss; part[3 * g + 1] = tsn; part[3 * g + 2] = 0.0; }
-  }
-}
-
-// stats[row] = {0, rms of the signal, rms of the noise, scale}.  One workgroup per row: kThreads piece sums at a time
-// come into LDS, thread 0 adds them in piece order; scale = float32((rms_s / 10^(snr_db / 20)) / rms_n), 0 (a copy)
-// when either rms is 0
-__global__ __launch_bounds__(kThreads) void noise_rms_kernel(const long* __restrict__ meta,
-                                                             const double* __restrict__ snr_db,
-                                                             const double* __restrict__ part,
-                                                             double* __restrict__ stats) {
-#pragma clang fp contract(off)
-  __shared__ double s_s[kThreads], s_n[kThreads];
-  const int tid = threadIdx.x, row = blockIdx.x;
-  const long* m = meta + (long)row * N_K;
-  const long n = m[N_N];
-  const long pieces = (n + kPiece - 1) / kPiece;        // of the row's n samples; the plan's count those generated
-  const double* pr = part + 3 * m[N_POFF];
-  double ss = 0.0, sn = 0.0;
-  for (long p0 = 0; p0 < pieces; p0 += kThreads) {
-    const int count = (int)(pieces - p0 < kThreads ? pieces - p0 : kThreads);
-    if (tid < count) { s_s[tid] = pr[3 * (p0 + tid)]; s_n[tid] = pr[3 * (p0 + tid) + 1]; }
-    __syncthreads();
-    if (tid == 0)
-      for (int p = 0; p < count; ++p) { ss += s_s[p]; sn += s_n[p]; }
-    __syncthreads();
-  }
-  if (tid != 0) return;
-  const double rs = n > 0 ? sqrt(ss / (double)n) : 0.0, rn = n > 0 ? sqrt(sn / (double)n) : 0.0;
-  double scale = 0.0;
-  if (rs > 0.0 && rn > 0.0) {
-    const double target = rs / pow(10.0, snr_db[row] / 20.0);
-    scale = (double)(float)(target / rn);
-  }
-  double* st = stats + (long)row * ST_K;
-  st[ST_PEAK] = 0.0; st[ST_RMS_S] = rs; st[ST_RMS_N] = rn; st[ST_SCALE] = scale;
-}
-
-// y = x + float32(noise scale), both in float32 (y = x for a scale of 0); part[3 g + 2] = max |y| of the piece
-__global__ __launch_bounds__(kThreads) void noise_mix_kernel(const long* __restrict__ meta,
-                                                             const float* __restrict__ x,
-                                                             const float* __restrict__ noise,
-                                                             const double* __restrict__ stats, int n_rows, long pieces,
-                                                             float* __restrict__ y, double* __restrict__ part) {
-#pragma clang fp contract(off)
-  __shared__ float s_red[kThreads / 64];
-  const int tid = threadIdx.x;
-  for (long g = blockIdx.x; g < pieces; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, N_K, N_POFF, g);
-    const long* m = meta + (long)row * N_K;
-    const double sc = stats[(long)row * ST_K + ST_SCALE];
-    const bool mixed = sc != 0.0;
-    const float scale = (float)sc;
-    const long n = m[N_N], base = (g - m[N_POFF]) * kPiece;
-    const float* xr = x + m[N_OFF];
-    const float* nr = noise + m[N_OFF];
-    float* yr = y + m[N_OFF];
-    float pk = 0.f;
-    for (int j = tid; j < kPiece && base + j < n; j += kThreads) {
-      float v = xr[base + j];
-      if (mixed) {
-        const float q = nr[base + j] * scale;
-        v = v + q;
-      }
-      yr[base + j] = v;
-      pk = fmaxf(pk, fabsf(v));
-    }
-    pk = block_max(pk, s_red, tid);
-    if (tid == 0) part[3 * g + 2] = (double)pk;
-    __syncthreads();
-  }
-}
-
-// stats[row].peak = max of the row's piece peaks, each a float32 (one workgroup per row; the order is immaterial)
-__global__ __launch_bounds__(kThreads) void noise_peak_kernel(const long* __restrict__ meta,
-                                                              const double* __restrict__ part,
-                                                              double* __restrict__ stats) {
-  __shared__ float s_red[kThreads / 64];
-  const int tid = threadIdx.x, row = blockIdx.x;
-  const long* m = meta + (long)row * N_K;
-  const long pieces = (m[N_N] + kPiece - 1) / kPiece;
-  const double* pr = part + 3 * m[N_POFF] + 2;
-  float pk = 0.f;
-  for (long p = tid; p < pieces; p += kThreads) pk = fmaxf(pk, (float)pr[3 * p]);
-  pk = block_max(pk, s_red, tid);
-  if (tid == 0) stats[(long)row * ST_K + ST_PEAK] = (double)pk;
-}
-
-// peak > 0.99: y = y / float32(peak + 1e-6)
-__global__ __launch_bounds__(kThreads) void noise_normalize_kernel(const long* __restrict__ meta, int n_rows,
-                                                                   long pieces, const double* __restrict__ stats,
-                                                                   float* __restrict__ y) {
-#pragma clang fp contract(off)
-  const int tid = threadIdx.x;
-  for (long g = blockIdx.x; g < pieces; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, N_K, N_POFF, g);
-    const long* m = meta + (long)row * N_K;
-    const double peak = stats[(long)row * ST_K + ST_PEAK];
-    if (!(peak > 0.99)) continue;
-    const float d = (float)(peak + 1e-6);
-    const long n = m[N_N], base = (g - m[N_POFF]) * kPiece;
-    float* yr = y + m[N_OFF];
-    for (int j = tid; j < kPiece && base + j < n; j += kThreads) yr[base + j] = yr[base + j] / d;
-  }
-}
-
 }  // namespace
 
 extern "C" int pe_noise_plan_fields(void) { return N_K; }
@@ -485,20 +345,6 @@ extern "C" int pe_noise_mix(const float* x, const float* noise, const long* meta
     if (!isfinite(host_snr_db[r])) return PE_E_ARG;
   if (!x || !noise || !meta || !snr_db || !y || !stats) return PE_E_ARG;
   if (!workspace || workspace_bytes < pe_noise_workspace_bytes(tot[TOT_PIECES])) return PE_E_WORKSPACE;
-  double* part = static_cast<double*>(workspace);
-  const long pieces = tot[TOT_PIECES];
-  const dim3 grid(grid_of(pieces)), rows(n_rows), wg(kThreads);
-  hipLaunchKernelGGL(noise_sums_kernel, grid, wg, 0, pe_stream(stream), meta, x, noise, n_rows, pieces, part);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(noise_rms_kernel, rows, wg, 0, pe_stream(stream), meta, snr_db, part, stats);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(noise_mix_kernel, grid, wg, 0, pe_stream(stream), meta, x, noise, stats, n_rows, pieces, y, part);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(noise_peak_kernel, rows, wg, 0, pe_stream(stream), meta, part, stats);
-  PE_LAUNCH_CHECK();
-  if (peak_normalize) {
-    hipLaunchKernelGGL(noise_normalize_kernel, grid, wg, 0, pe_stream(stream), meta, n_rows, pieces, stats, y);
-    PE_LAUNCH_CHECK();
-  }
-  return PE_OK;
+  return launch_snr_mix<NoiseMixRows>(meta, n_rows, snr_db, tot[TOT_PIECES], x, noise, y, peak_normalize != 0, stats,
+                                      static_cast<double*>(workspace), pe_stream(stream));
 }

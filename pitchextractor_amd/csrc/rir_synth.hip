@@ -34,13 +34,13 @@
 #include <algorithm>
 #include <vector>
 #include "common.h"
-#include "dsp.h"
+#include "pieces.h"
 
 using namespace pe;
 
 namespace {
 
-constexpr int kThreads = 256;                    // of a decay workgroup
+// a decay workgroup is the kThreads of pieces.h, whose block_sum_d it takes
 constexpr int kSynthThreads = 1024;              // of a tile's workgroup: four waves per SIMD under the long double chains
 constexpr int kTile = 256;                       // samples of one tile: 2 KiB of LDS accumulators
 constexpr int kHalf = 41;                        // half-width of the windowed sinc, in samples
@@ -223,20 +223,6 @@ __device__ __forceinline__ void suffix_runs(double v, double* s_run, int tid) {
     for (int t = kThreads - 1; t >= 0; --t) { acc += s_run[t]; s_run[t] = acc; }
   }
   __syncthreads();
-}
-
-__device__ __forceinline__ double block_sum_d(double v, double* s_sum, int tid) {
-#pragma clang fp contract(off)
-  __syncthreads();
-  s_sum[tid] = v;
-  __syncthreads();
-  for (int st = kThreads / 2; st > 0; st >>= 1) {
-    if (tid < st) s_sum[tid] += s_sum[tid + st];
-    __syncthreads();
-  }
-  const double out = s_sum[0];
-  __syncthreads();
-  return out;
 }
 
 __global__ __launch_bounds__(kThreads) void rir_decay_kernel(const float* __restrict__ h,

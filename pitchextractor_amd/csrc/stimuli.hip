@@ -13,26 +13,23 @@
 //              carry).  Three launches, and no workgroup waits on another.
 //   synth:     float32(amplitude sin(phase)).
 //   tone:      the sum of up to 16 partials in the profile's order.
-//   finish:    fade and piece sums of squares, row rms and scale, noise mix and piece peaks, normalisation.  Four.
+//   finish:    the mix at an SNR of snr_mix.h in place, under the fade (fade and piece sums of squares, row rms and
+//              scale, noise mix and piece peaks, row peak with the normalisation), which pe_noise_mix runs too.  Four.
 //   reference: one thread per frame: the bracketing samples of the float32 time axis, np.interp's expression.
 //   metrics:   one workgroup per row; every lag of the full cross-correlation is summed by one thread in index order.
 // Everything is double with contraction off; nothing a row computes depends on where the row lies or on its
 // neighbours: a row's result is the same alone, packed at an odd offset or padded.
 #include <math.h>
 #include "common.h"
-#include "dsp.h"
+#include "snr_mix.h"
 
 using namespace pe;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRun = 8;                          // consecutive samples of one thread
-constexpr int kPiece = kRun * kThreads;          // scan / reduction piece S = 2048, counted from the row's start
 constexpr int kMaxPartials = 16;
 constexpr long kMaxSamples = (1L << 31) - 8;
 constexpr double kTwoPi = 2.0 * 3.141592653589793;
-constexpr double kPi = 3.141592653589793;
 constexpr double kFadeTime = 0.02;
 
 enum { K_CURVE, K_GLIDE, K_VIBRATO, K_TONE, K_KINDS };
@@ -45,7 +42,13 @@ enum { P_AMP, P_A, P_B, P_C, P_SNR, P_SR, P_TSTEP, P_SPARE, P_PARTIALS, P_K = P_
 enum { F_FOFF, F_NF, F_K };                      // frame table of pe_stim_reference: frame prefix, frames
 enum { M_POFF, M_N, M_ROFF, M_K };               // tracks of pe_dynamic_metrics: pred offset, frames, ref offset
 static_assert(F_FOFF == kRowOffset && F_NF == kRowLength && M_POFF == kRowOffset && M_N == kRowLength, "row header");
-enum { ST_PEAK, ST_RMS_S, ST_RMS_N, ST_SCALE, ST_K };
+
+// The plan as snr_mix.h reads it: in place under the fade, packed noise that a row may lack, snr_db in the row's
+// parameters; rows of a few dozen pieces, so the division finds the row peaks itself.
+struct StimMixRows {
+  static constexpr int kFields = S_K, kPieceOffset = S_POFF, kFade = S_FADE, kNoiseOffset = S_NOFF, kSnrStride = P_K;
+  static constexpr bool kInPlace = true, kPeakLaunch = false;
+};
 
 long fade_samples(double sr) { return (long)fmax(kFadeTime * sr, 0.0); }
 
@@ -80,38 +83,6 @@ __device__ __forceinline__ double curve_at(const long* m, const double* p, const
   }
   if (kind == K_CURVE) return (double)curves[m[S_COFF] + (m[S_CLEN] == 1 ? 0 : i)];
   return (double)(float)p[P_A];
-}
-
-// Scan of one double per thread over the workgroup (Hillis-Steele in LDS, a fixed order): returns the sum of the
-// threads before `tid`, and the sum of all in `total`.
-__device__ __forceinline__ double block_scan(double v, double* s_sum, int tid, double& total) {
-#pragma clang fp contract(off)
-  s_sum[tid] = v;
-  __syncthreads();
-  for (int st = 1; st < kThreads; st <<= 1) {
-    const double add = tid >= st ? s_sum[tid - st] : 0.0;
-    __syncthreads();
-    s_sum[tid] += add;
-    __syncthreads();
-  }
-  const double before = tid > 0 ? s_sum[tid - 1] : 0.0;
-  total = s_sum[kThreads - 1];
-  __syncthreads();
-  return before;
-}
-
-// Sum of one double per thread over the workgroup (a fixed tree); every thread gets it.
-__device__ __forceinline__ double block_sum_d(double v, double* s_sum, int tid) {
-#pragma clang fp contract(off)
-  s_sum[tid] = v;
-  __syncthreads();
-  for (int st = kThreads / 2; st > 0; st >>= 1) {
-    if (tid < st) s_sum[tid] += s_sum[tid + st];
-    __syncthreads();
-  }
-  const double out = s_sum[0];
-  __syncthreads();
-  return out;
 }
 
 // ---- phase ---------------------------------------------------------------------------------------------------------
@@ -210,133 +181,6 @@ __global__ __launch_bounds__(kThreads) void stim_tone_kernel(const long* __restr
   }
 }
 
-// ---- finish --------------------------------------------------------------------------------------------------------
-// window[i] of a row of n samples with a fade of F: ramp[i] over the head, ramp[n - 1 - i] over the tail (the tail
-// overwrites the head where they overlap), ramp[j] = 0.5 - 0.5 cos(j (pi / (F - 1))) with the last angle pi itself.
-__device__ __forceinline__ double fade_window(long i, long n, long F) {
-#pragma clang fp contract(off)
-  if (F <= 0) return 1.0;
-  long j = -1;
-  if (i < F) j = i;
-  if (i >= n - F) j = n - 1 - i;
-  if (j < 0) return 1.0;
-  const double ang = j == 0 ? 0.0 : (j == F - 1 ? kPi : (double)j * (kPi / (double)(F - 1)));
-  return 0.5 - 0.5 * cos(ang);
-}
-
-// y = float32(float64(y) window); part[g] = {sum of y^2, sum of noise^2, max |y|} of the piece
-__global__ __launch_bounds__(kThreads) void stim_fade_kernel(const long* __restrict__ meta,
-                                                             const float* __restrict__ noise, int n_rows, long pieces,
-                                                             float* __restrict__ y, double* __restrict__ part) {
-#pragma clang fp contract(off)
-  __shared__ double s_sum[kThreads];
-  const int tid = threadIdx.x;
-  for (long g = blockIdx.x; g < pieces; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, S_K, S_POFF, g);
-    const long* m = meta + (long)row * S_K;
-    const long n = m[S_N], F = m[S_FADE], i0 = (g - m[S_POFF]) * kPiece + (long)tid * kRun;
-    float* yr = y + m[S_OFF];
-    const float* nr = noise && m[S_NOFF] >= 0 ? noise + m[S_NOFF] : nullptr;
-    double ss = 0.0, sn = 0.0, pk = 0.0;
-#pragma unroll
-    for (int u = 0; u < kRun; ++u)
-      if (i0 + u < n) {
-        const float v = (float)((double)yr[i0 + u] * fade_window(i0 + u, n, F));
-        yr[i0 + u] = v;
-        ss += (double)v * (double)v;
-        pk = fmax(pk, fabs((double)v));
-        if (nr) { const double q = (double)nr[i0 + u]; sn += q * q; }
-      }
-    const double tss = block_sum_d(ss, s_sum, tid), tsn = block_sum_d(sn, s_sum, tid);
-    s_sum[tid] = pk;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-      if (tid < st) s_sum[tid] = fmax(s_sum[tid], s_sum[tid + st]);
-      __syncthreads();
-    }
-    if (tid == 0) { part[3 * g] = tss; part[3 * g + 1] = tsn; part[3 * g + 2] = s_sum[0]; }
-    __syncthreads();
-  }
-}
-
-// stats[row] = {-, rms of the signal, rms of the noise, scale}: piece sums added in order by one thread per row;
-// scale = float32((rms_s / 10^(snr_db / 20)) / rms_n), 0 (no mix) for a row without noise or with an rms of 0
-__global__ __launch_bounds__(kThreads) void stim_rms_kernel(const long* __restrict__ meta,
-                                                            const double* __restrict__ prm, int n_rows,
-                                                            const double* __restrict__ part,
-                                                            double* __restrict__ stats) {
-#pragma clang fp contract(off)
-  const int row = blockIdx.x * kThreads + threadIdx.x;
-  if (row >= n_rows) return;
-  const long* m = meta + (long)row * S_K;
-  double ss = 0.0, sn = 0.0;
-  for (long k = 0; k < m[S_PIECES]; ++k) { ss += part[3 * (m[S_POFF] + k)]; sn += part[3 * (m[S_POFF] + k) + 1]; }
-  const double rs = sqrt(ss / (double)m[S_N]);
-  const double rn = m[S_NOFF] >= 0 ? sqrt(sn / (double)m[S_N]) : 0.0;
-  double scale = 0.0;
-  if (m[S_NOFF] >= 0 && rs > 0.0 && rn > 0.0) {
-    const double target = rs / pow(10.0, prm[(long)row * P_K + P_SNR] / 20.0);
-    scale = (double)(float)(target / rn);
-  }
-  double* st = stats + (long)row * ST_K;
-  st[ST_RMS_S] = rs; st[ST_RMS_N] = rn; st[ST_SCALE] = scale;
-}
-
-// noise rows with a scale: y = y + float32(noise scale), both in float32; part[3 g + 2] = max |y| of the piece
-__global__ __launch_bounds__(kThreads) void stim_mix_kernel(const long* __restrict__ meta,
-                                                            const float* __restrict__ noise,
-                                                            const double* __restrict__ stats, int n_rows, long pieces,
-                                                            float* __restrict__ y, double* __restrict__ part) {
-#pragma clang fp contract(off)
-  __shared__ float s_red[kThreads / 64];
-  const int tid = threadIdx.x;
-  for (long g = blockIdx.x; g < pieces; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, S_K, S_POFF, g);
-    const long* m = meta + (long)row * S_K;
-    const double sc = stats[(long)row * ST_K + ST_SCALE];
-    if (!noise || m[S_NOFF] < 0 || !(sc != 0.0)) continue;        // the piece peak of the fade stands
-    const float scale = (float)sc;
-    const long n = m[S_N], base = (g - m[S_POFF]) * kPiece;
-    float* yr = y + m[S_OFF];
-    const float* nr = noise + m[S_NOFF];
-    float pk = 0.f;
-    for (int j = tid; j < kPiece && base + j < n; j += kThreads) {
-      const float q = nr[base + j] * scale;
-      const float v = yr[base + j] + q;
-      yr[base + j] = v;
-      pk = fmaxf(pk, fabsf(v));
-    }
-    pk = block_max(pk, s_red, tid);
-    if (tid == 0) part[3 * g + 2] = (double)pk;
-    __syncthreads();
-  }
-}
-
-// peak = max of the row's piece peaks (whatever the order); peak > 0.99: y = y / float32(peak + 1e-6)
-__global__ __launch_bounds__(kThreads) void stim_normalize_kernel(const long* __restrict__ meta, int n_rows,
-                                                                  long pieces, const double* __restrict__ part,
-                                                                  float* __restrict__ y, double* __restrict__ stats) {
-#pragma clang fp contract(off)
-  __shared__ float s_red[kThreads / 64];
-  const int tid = threadIdx.x;
-  for (long g = blockIdx.x; g < pieces; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, S_K, S_POFF, g);
-    const long* m = meta + (long)row * S_K;
-    float pk = 0.f;
-    for (long k = tid; k < m[S_PIECES]; k += kThreads) pk = fmaxf(pk, (float)part[3 * (m[S_POFF] + k) + 2]);
-    const float peakf = block_max(pk, s_red, tid);
-    const double peak = (double)peakf;
-    const long n = m[S_N], base = (g - m[S_POFF]) * kPiece;
-    if (base == 0 && tid == 0) stats[(long)row * ST_K + ST_PEAK] = peak;
-    if (peak > 0.99) {
-      const float d = (float)(peak + 1e-6);
-      float* yr = y + m[S_OFF];
-      for (int j = tid; j < kPiece && base + j < n; j += kThreads) yr[base + j] = yr[base + j] / d;
-    }
-    __syncthreads();
-  }
-}
-
 // ---- reference at frame rate ---------------------------------------------------------------------------------------
 // ref[f] = float32(np.interp(tau[f], float32(t), float32(curve))) with t[i] = i tstep: j with t32[j] <= tau < t32[j + 1]
 // from floor(tau / tstep) corrected against the rounded times; the last sample at or beyond t32[n - 1].
@@ -409,36 +253,14 @@ __global__ __launch_bounds__(kThreads) void stim_metrics_kernel(const float* __r
   }
   sq = block_sum_d(sq, s_sum, tid); nv = block_sum_d(nv, s_sum, tid);
   const double mp = block_sum_d(sp, s_sum, tid) / (double)L, mr = block_sum_d(sr, s_sum, tid) / (double)L;
-  s_sum[tid] = mx;
-  __syncthreads();
-  for (int st = kThreads / 2; st > 0; st >>= 1) {
-    if (tid < st) s_sum[tid] = fmax(s_sum[tid], s_sum[tid + st]);
-    __syncthreads();
-  }
-  const double peak = s_sum[0];
-  __syncthreads();
+  const double peak = block_max_d(mx, s_sum, tid);
   // np.allclose(centred, 0): every |centred| <= 1e-8
   double fp = 0.0, fr = 0.0;
   for (long i = tid; i < L; i += kThreads) {
     fp = fmax(fp, fabs((double)p[i] - mp));
     fr = fmax(fr, fabs((double)f[i] - mr));
   }
-  s_sum[tid] = fp;
-  __syncthreads();
-  for (int st = kThreads / 2; st > 0; st >>= 1) {
-    if (tid < st) s_sum[tid] = fmax(s_sum[tid], s_sum[tid + st]);
-    __syncthreads();
-  }
-  fp = s_sum[0];
-  __syncthreads();
-  s_sum[tid] = fr;
-  __syncthreads();
-  for (int st = kThreads / 2; st > 0; st >>= 1) {
-    if (tid < st) s_sum[tid] = fmax(s_sum[tid], s_sum[tid + st]);
-    __syncthreads();
-  }
-  fr = s_sum[0];
-  __syncthreads();
+  fp = block_max_d(fp, s_sum, tid); fr = block_max_d(fr, s_sum, tid);
   double lag = nan;
   if (fp > 1e-8 && fr > 1e-8) {
     // c[k] = sum over n of pred_c[n + k - (L - 1)] ref_c[n], k < 2 L - 1; the first maximum
@@ -601,18 +423,8 @@ extern "C" int pe_stim_finish(const long* meta, const long* host_meta, const dou
   PE_OPEN(open_batch(n_rows, host_meta, tot));
   if (!meta || !params || !y || !stats || (has_noise_rows(host_meta, n_rows) && !noise)) return PE_E_ARG;
   if (!workspace || workspace_bytes < pe_stim_workspace_bytes(tot[TOT_PIECES])) return PE_E_WORKSPACE;
-  double* part = static_cast<double*>(workspace);
-  const long pieces = tot[TOT_PIECES];
-  const dim3 grid(grid_of(pieces)), rows((n_rows + kThreads - 1) / kThreads), wg(kThreads);
-  hipLaunchKernelGGL(stim_fade_kernel, grid, wg, 0, pe_stream(stream), meta, noise, n_rows, pieces, y, part);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stim_rms_kernel, rows, wg, 0, pe_stream(stream), meta, params, n_rows, part, stats);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stim_mix_kernel, grid, wg, 0, pe_stream(stream), meta, noise, stats, n_rows, pieces, y, part);
-  PE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stim_normalize_kernel, grid, wg, 0, pe_stream(stream), meta, n_rows, pieces, part, y, stats);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  return launch_snr_mix<StimMixRows>(meta, n_rows, params + P_SNR, tot[TOT_PIECES], y, noise, y, true, stats,
+                                     static_cast<double*>(workspace), pe_stream(stream));
 }
 
 extern "C" int pe_stim_reference(const long* meta, const long* host_meta, const double* params, const float* curves,

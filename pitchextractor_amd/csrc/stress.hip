@@ -172,7 +172,8 @@ __global__ __launch_bounds__(kThreads) void stress_rir_convolve_kernel(const flo
   }
 }
 
-// p = max |y| of the row (the max of its block peaks, whatever the order); p > 0.99: y /= p + 1e-6, in float32
+// p = max |y| of the row (the max of its block peaks, whatever the order); p > 0.99: y /= p + 1e-6, in float32: not
+// the rounding of float32(double(p) + 1e-6) in the mix of snr_mix.h, so the two stay apart
 __global__ __launch_bounds__(kThreads) void stress_rir_normalize_kernel(const long* __restrict__ meta,
                                                                         const float* __restrict__ peak, int n_rows,
                                                                         long blocks, float* __restrict__ y) {

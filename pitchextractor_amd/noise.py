@@ -15,18 +15,18 @@ samples that are not written, so sample ``i`` is generated sample ``warmup + i``
 silence included."""
 from __future__ import annotations
 
-import hashlib
 import math
 
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .ragged import check_waves, host_ptrs, i64, plan_arrays, row_layout, workspace
+from .ragged import (PackedRecordings, check_device_tensor, check_waves, gpu_device, host_ptrs, i64, per_row,
+                     plan_arrays, plan_extent, plan_output, row_layout, to_device, workspace)
 
 MAX_SECTIONS = 8
 NOISE_COLOURS = ("white", "pink", "brown")
-STAT_KEYS = ("peak", "rms_signal", "rms_noise", "scale")
+STAT_KEYS = ("peak", "rms_signal", "rms_noise", "scale")           # of the mix at an SNR; stimuli.finish's too
 BROWN_CORNER_HZ = 20.0
 # d0, d1 and the (pole, gain) sections of the pink filter: a pole-zero fit of 1 / sqrt(f) whose poles are fixed in z, so
 # the response follows -3 dB / octave from sr / 2000 to sr / 2.2 within 0.059 dB peak to peak at any rate
@@ -86,10 +86,8 @@ def plan_rows(lengths, offsets=None, warmup=0, seeds=0, white_offsets=None, colo
     R, n, off, meta = plan_arrays("pe_noise_plan_fields", lengths, offsets, "noise plan: one offset per row")
     if np.any(n < 0):
         raise ValueError("noise plan: a row length is negative")
-    warm = np.full(R, int(warmup), np.int64) if np.ndim(warmup) == 0 else i64(warmup)
-    woff = np.full(R, -1, np.int64) if white_offsets is None else i64(white_offsets)
-    if warm.size != R or woff.size != R:
-        raise ValueError("noise plan: one warm-up and one white offset per row")
+    one_each = "noise plan: one warm-up and one white offset per row"
+    warm, woff = per_row(warmup, R, one_each), per_row(-1 if white_offsets is None else white_offsets, R, one_each)
     if np.any(warm < 0):
         raise ValueError("noise plan: a warm-up is negative")
     seed = row_seeds(seeds, R)
@@ -106,40 +104,6 @@ def plan_rows(lengths, offsets=None, warmup=0, seeds=0, white_offsets=None, colo
                 n_pieces=int(totals[1]), sections=len(sections))
 
 
-def to_device(pl: dict, device) -> dict:
-    """The plan with the device copies of its two tables (``meta_d``, ``params_d``)."""
-    device = torch.device(device)
-    if "meta_d" not in pl or pl["meta_d"].device != device:
-        pl["meta_d"] = torch.from_numpy(pl["meta"]).to(device)
-        pl["params_d"] = torch.from_numpy(pl["params"]).to(device)
-    return pl
-
-
-def _device(device) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"noise (HIP) needs a GPU device, got {device}; no CPU fallback exists")
-    return device
-
-
-def _check_device(t, who: str) -> None:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-        raise RuntimeError(f"{who} (HIP) needs a contiguous float32 device tensor; no CPU fallback exists")
-
-
-def _extent(pl) -> int:
-    return int(np.max(pl["offsets"] + pl["lengths"])) if pl["rows"] else 0
-
-
-def _output(pl, out, device, who):
-    if out is None:
-        return torch.zeros((max(_extent(pl), 1),), dtype=torch.float32, device=device)
-    _check_device(out, who)
-    if out.numel() < _extent(pl):
-        raise ValueError(f"{who}: the output is shorter than the plan's rows")
-    return out
-
-
 def _ws(pl, device):
     n_bytes = _lib.load().pe_noise_workspace_bytes(pl["n_pieces"])
     return workspace(n_bytes, device), n_bytes
@@ -150,13 +114,13 @@ def white(lengths, seeds=0, device="cuda", offsets=None, warmup=0, out=None) -> 
     """``pe_noise_white``: standard normals, row r from its own seed (``seeds``: an int, row r takes ``seeds + r``, or
     one per row).  Rows packed back to back, or at ``offsets`` of ``out``.  ``warmup``: the first sample's index in the
     row's stream.  One launch."""
-    device = _device(out.device if isinstance(out, torch.Tensor) else device)
+    device = gpu_device(out.device if isinstance(out, torch.Tensor) else device, "noise")
     pl = to_device(plan_rows(lengths, offsets, warmup, seeds), device)
-    y = _output(pl, out, device, "noise.white")
+    y = plan_output(pl, out, device, "noise.white")
     with torch.cuda.device(device):
         ops._call("pe_noise_white", pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, pl["rows"], y.data_ptr(),
                   _lib.stream_ptr())
-    return y if out is not None else y[:_extent(pl)]
+    return y if out is not None else y[:plan_extent(pl)]
 
 
 def coloured(lengths, colour, sr, seeds=None, white=None, warmup=4096, offsets=None, device="cuda", out=None):
@@ -169,44 +133,35 @@ def coloured(lengths, colour, sr, seeds=None, white=None, warmup=4096, offsets=N
     n = i64(lengths)
     woff = None
     if white is not None:
-        _check_device(white, "noise.coloured")
+        check_device_tensor(white, "noise.coloured")
         device = white.device
-        warm = np.full(n.size, int(warmup), np.int64) if np.ndim(warmup) == 0 else i64(warmup)
-        gen = n + warm
+        gen = n + per_row(warmup, n.size, "noise plan: one warm-up and one white offset per row")
         woff = np.cumsum(gen) - gen
         if int(np.sum(gen)) > white.numel():
             raise ValueError("noise.coloured: the white input needs warmup + n samples per row")
-    device = _device(out.device if isinstance(out, torch.Tensor) else device)
+    device = gpu_device(out.device if isinstance(out, torch.Tensor) else device, "noise")
     pl = to_device(plan_rows(n, offsets, warmup, 0 if seeds is None else seeds, woff, colour, sr), device)
-    y = _output(pl, out, device, "noise.coloured")
+    y = plan_output(pl, out, device, "noise.coloured")
     ws, n_bytes = _ws(pl, device)
     with torch.cuda.device(device):
         ops._call("pe_noise_colour", pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, pl["params_d"].data_ptr(),
                   pl["params"].ctypes.data, _lib.ptr(white), 0 if white is None else white.numel(), pl["rows"],
                   y.data_ptr(), ws.data_ptr(), n_bytes, _lib.stream_ptr())
-    return y if out is not None else y[:_extent(pl)]
+    return y if out is not None else y[:plan_extent(pl)]
 
 
-class NoiseSet:
-    """K recorded noise beds (1-D float arrays of any length >= 1, taken as they are) as one ragged batch, kept on the
-    device once per set and device."""
+class NoiseSet(PackedRecordings):
+    """K recorded noise beds (1-D float arrays of any length >= 1, taken as they are) as one ragged batch
+    (``recordings``, ``lengths``, ``offsets``, ``packed``, ``key``), kept on the device once per set and device."""
 
     def __init__(self, recordings, device="cuda"):
-        self.recordings = [np.ascontiguousarray(np.asarray(h, dtype=np.float32).reshape(-1)) for h in recordings]
-        if not self.recordings or any(h.size < 1 for h in self.recordings):
-            raise ValueError("NoiseSet: at least one recording, each of at least one sample")
-        self.lengths = [int(h.size) for h in self.recordings]
-        self.offsets = (np.cumsum(self.lengths) - np.asarray(self.lengths)).tolist()
-        self.packed = np.concatenate(self.recordings)
-        self.key = hashlib.sha1(np.asarray(self.lengths, np.int64).tobytes() + self.packed.tobytes()).hexdigest()
+        super().__init__(recordings, "NoiseSet: at least one recording, each of at least one sample")
+        self.recordings = self._items
         self.device = torch.device(device)
-
-    def __len__(self):
-        return len(self.recordings)
 
     def audio(self, device=None) -> torch.Tensor:
         """The recordings back to back on the device."""
-        device = _device(self.device if device is None else device)
+        device = gpu_device(self.device if device is None else device, "noise")
         return _lib.device_table(("noise_bed", self.key), device, lambda: self.packed)
 
 
@@ -216,13 +171,12 @@ def bed(noise_set: NoiseSet, lengths, index=0, start=0, offsets=None, device=Non
     recording.  One launch."""
     if not isinstance(noise_set, NoiseSet):
         raise ValueError("noise.bed: a NoiseSet is expected")
-    device = _device(out.device if isinstance(out, torch.Tensor) else (noise_set.device if device is None else device))
+    device = gpu_device(out.device if isinstance(out, torch.Tensor) else
+                        (noise_set.device if device is None else device), "noise")
     pl = plan_rows(lengths, offsets)
     R = pl["rows"]
-    index = [int(index)] * R if np.ndim(index) == 0 else [int(k) for k in index]
-    start = [int(start)] * R if np.ndim(start) == 0 else [int(k) for k in start]
-    if len(index) != R or len(start) != R:
-        raise ValueError("noise.bed: one index and one start per row")
+    one_each = "noise.bed: one index and one start per row"
+    index, start = per_row(index, R, one_each).tolist(), per_row(start, R, one_each).tolist()
     if any(k < 0 or k >= len(noise_set) for k in index):
         raise ValueError("noise.bed: an index lies outside the set")
     if any(s < 0 or s >= noise_set.lengths[k] for k, s in zip(index, start)):
@@ -231,13 +185,13 @@ def bed(noise_set: NoiseSet, lengths, index=0, start=0, offsets=None, device=Non
     for r, (k, s) in enumerate(zip(index, start)):
         beds[r] = (noise_set.offsets[k], noise_set.lengths[k], s)
     to_device(pl, device)
-    y = _output(pl, out, device, "noise.bed")
+    y = plan_output(pl, out, device, "noise.bed")
     audio = noise_set.audio(device)
     beds_d = torch.from_numpy(beds).to(device)
     with torch.cuda.device(device):
         ops._call("pe_noise_bed", pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, audio.data_ptr(), audio.numel(),
                   beds_d.data_ptr(), beds.ctypes.data, R, y.data_ptr(), _lib.stream_ptr())
-    return y if out is not None else y[:_extent(pl)]
+    return y if out is not None else y[:plan_extent(pl)]
 
 
 def mix_at_snr(x, noise, snr_db, lengths=None, peak_normalize: bool = True, return_stats: bool = False):
@@ -246,7 +200,8 @@ def mix_at_snr(x, noise, snr_db, lengths=None, peak_normalize: bool = True, retu
     is silent is a copy with ``scale = 0``.  ``peak_normalize``: then ``y / float32(peak + 1e-6)`` where ``peak = max|y|
     > 0.99`` (the notebooks' ``_normalize``).  ``x`` and ``noise`` share one layout (packed with ``lengths``, or padded);
     ``snr_db``: a number or one per row.  The result is dense of ``x``'s shape, zero outside the rows.
-    ``return_stats``: also the ``(rows, 4)`` float64 ``STAT_KEYS`` on the device.  Five launches."""
+    ``return_stats``: also the ``(rows, 4)`` float64 ``STAT_KEYS`` on the device.  Five launches, four without the peak
+    rule: the mix of ``csrc/snr_mix.h``, which ``stimuli.finish`` runs in place under its fade."""
     check_waves(x, "mix_at_snr")
     check_waves(noise, "mix_at_snr")
     if tuple(noise.shape) != tuple(x.shape) or noise.device != x.device:
@@ -255,10 +210,7 @@ def mix_at_snr(x, noise, snr_db, lengths=None, peak_normalize: bool = True, retu
     row_lengths, offsets = row_layout(x, lengths, whole_by_default=True)
     pl = to_device(plan_rows(row_lengths, offsets), x.device)
     R = pl["rows"]
-    snr = np.full(R, float(snr_db), np.float64) if np.ndim(snr_db) == 0 else \
-        np.ascontiguousarray(snr_db, dtype=np.float64).reshape(-1)
-    if snr.size != R:
-        raise ValueError("mix_at_snr: one snr_db per row")
+    snr = per_row(snr_db, R, "mix_at_snr: one snr_db per row", np.float64)
     if not np.all(np.isfinite(snr)):
         raise ValueError("mix_at_snr: snr_db must be finite")
     y = torch.zeros(tuple(x.shape), dtype=torch.float32, device=x.device)

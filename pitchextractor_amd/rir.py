@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops, stress
-from .ragged import check_waves, host_ptrs, i64, packed_offsets, plan_meta, row_layout
+from .ragged import (check_device_tensor, check_waves, gpu_device, host_ptrs, i64, packed_offsets, plan_extent,
+                     plan_meta, plan_output, row_layout)
 
 DECAY_KEYS = ("t60", "slope", "intercept", "k_lo", "k_hi", "db_last")
 # Build-defined: the notebook only names its rooms.  Dimensions, an off-centre source and a microphone, in metres.
@@ -31,13 +32,6 @@ ROOMS = {
 LIBRARY_T60S = {"small_room": (0.30, 0.60, 0.90), "office": (0.45, 0.80, 1.20), "hall": (0.80, 1.10, 1.50)}
 T60_SWEEP = tuple(round(float(x), 2) for x in np.linspace(0.2, 1.5, 14))
 BETA_RANGE = (0.0, 0.9999)
-
-
-def _device(device) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"rir (HIP) needs a GPU device, got {device}; no CPU fallback exists")
-    return device
 
 
 def _consts() -> dict:
@@ -107,20 +101,12 @@ def synthesize(rooms, fs, c=343.0, max_order=None, device="cuda", out=None, offs
     that arrive before the response ends).  One launch."""
     rooms = list(rooms)
     if out is not None:
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or \
-                not out.is_contiguous():
-            raise RuntimeError("rir.synthesize (HIP) needs a contiguous float32 device tensor; no CPU fallback exists")
-    device = _device(out.device if out is not None else device)
+        check_device_tensor(out, "rir.synthesize")
+    device = gpu_device(out.device if out is not None else device, "rir")
     pl = plan_rooms(rooms, fs, c, max_order, offsets)
     R = pl["rows"]
     lengths = [int(n) for n in pl["lengths"]]
-    extent = int(np.max(pl["offsets"] + pl["lengths"])) if R else 0
-    if out is None:
-        y = torch.zeros((max(extent, 1),), dtype=torch.float32, device=device)
-    else:
-        y = out
-        if y.numel() < extent:
-            raise ValueError("rir.synthesize: the output is shorter than the rooms' responses")
+    y = plan_output(pl, out, device, "rir.synthesize", "the output is shorter than the rooms' responses")
     if R:
         meta_d = torch.from_numpy(pl["meta"]).to(device)
         params_d = torch.from_numpy(pl["params"]).to(device)
@@ -129,7 +115,7 @@ def synthesize(rooms, fs, c=343.0, max_order=None, device="cuda", out=None, offs
             ops._call("pe_rir_synth", meta_d.data_ptr(), pl["meta"].ctypes.data, params_d.data_ptr(),
                       pl["params"].ctypes.data, tiles_d.data_ptr(), pl["tiles"].ctypes.data, R, y.data_ptr(),
                       y.numel(), _lib.stream_ptr())
-    return (y if out is not None else y[:extent]), lengths
+    return (y if out is not None else y[:plan_extent(pl)]), lengths
 
 
 def measure_t60(h, lengths=None, fs=24000, lo_db=-5.0, hi_db=-25.0, return_curve: bool = False):
@@ -255,7 +241,7 @@ def room_library(fs, rooms=None, t60s=None, rtol=0.02, max_iter=20, tail=1.5, c=
     0.45 / 0.80 / 1.20 and 0.80 / 1.10 / 1.50 s), then all of them measured again as one batch."""
     rooms = ROOMS if rooms is None else rooms
     t60s = LIBRARY_T60S if t60s is None else t60s
-    device = _device(device)
+    device = gpu_device(device, "rir")
     entries, parts = [], []
     for name, room in rooms.items():
         for target in t60s[name]:

@@ -20,7 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .ragged import check_waves, host_ptrs, plan_arrays, row_layout, workspace
+from .noise import STAT_KEYS  # noqa: F401  (the mix at an SNR is one implementation; finish returns its stats)
+from .ragged import (check_device_tensor, check_waves, host_ptrs, pack_tracks, per_row, plan_arrays, plan_output,
+                     row_layout, to_device, workspace)
 
 KINDS = ("curve", "glide", "vibrato", "tone")
 K_CURVE, K_GLIDE, K_VIBRATO, K_TONE = range(4)
@@ -45,7 +47,6 @@ TIMBRE_STIMULUS = {"duration_seconds": 2.5, "frequencies_per_range": 15, "edge_b
 VIBRATO_GRID = {"base_frequency_hz": 220.0, "duration_seconds": 3.0, "rates_hz": (4.0, 6.0, 8.0),
                 "depth_cents": (20.0, 60.0, 120.0, 200.0)}
 GLIDE_GRID = {"start_hz": 60.0, "end_hz": 500.0, "durations_seconds": (0.4, 0.8, 1.6, 3.2)}
-STAT_KEYS = ("peak", "rms_signal", "rms_noise", "scale")
 DYNAMIC_KEYS = ("RMSE_cents", "Lag_frames", "Overshoot_cents", "Final_error_cents")
 
 
@@ -161,31 +162,14 @@ def plan_rows(rows, sr, offsets=None) -> dict:
                 has_phases=bool(np.any(kind != K_TONE)))
 
 
-def to_device(pl: dict, device) -> dict:
-    """The plan with the device copies of its two tables (``meta_d``, ``params_d``)."""
-    if "meta_d" not in pl or pl["meta_d"].device != torch.device(device):
-        pl["meta_d"] = torch.from_numpy(pl["meta"]).to(device)
-        pl["params_d"] = torch.from_numpy(pl["params"]).to(device)
-    return pl
-
-
-def _check_device(t, who: str, dtype=torch.float32) -> None:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError(f"{who} (HIP) needs a contiguous {dtype} device tensor; no CPU fallback exists")
-
-
 def _curves_ptr(pl, curves, who):
     if not pl["has_curves"]:
         return 0
-    _check_device(curves, who)
+    check_device_tensor(curves, who)
     need = max(int(row["curve"][0]) + int(row["curve"][1]) for row in pl["specs"] if row["kind"] == K_CURVE)
     if curves.numel() < need:
         raise ValueError(f"{who}: the curve tensor is shorter than the rows' curves")
     return curves.data_ptr()
-
-
-def _extent(pl) -> int:
-    return int(np.max(pl["offsets"] + pl["lengths"])) if pl["rows"] else 0
 
 
 def _ws(pl, device):
@@ -209,16 +193,14 @@ def phase(pl: dict, curves=None, device="cuda") -> torch.Tensor:
 
 
 def _check_out(pl, y, who):
-    _check_device(y, who)
-    if y.numel() < _extent(pl):
-        raise ValueError(f"{who}: the output is shorter than the plan's rows")
-    to_device(pl, y.device)
+    check_device_tensor(y, who)
+    to_device(pl, plan_output(pl, y, y.device, who).device)
 
 
 def synth(pl: dict, phases: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """``pe_stim_synth``: ``float32(amplitude * sin(phase))`` into the rows of ``y``.  One launch."""
     _check_out(pl, y, "stimuli.synth")
-    _check_device(phases, "stimuli.synth", torch.float64)
+    check_device_tensor(phases, "stimuli.synth", torch.float64)
     if phases.numel() < pl["n_samples"]:
         raise ValueError("stimuli.synth: one phase per sample")
     with torch.cuda.device(y.device):
@@ -238,10 +220,11 @@ def tone(pl: dict, y: torch.Tensor) -> torch.Tensor:
 
 def finish(pl: dict, y: torch.Tensor, noise=None, return_stats: bool = False):
     """``pe_stim_finish`` in place on ``y``: fade, noise mix (``noise``: the packed noise of the rows that have one) and
-    peak normalisation.  Four launches.  ``return_stats``: also the ``(rows, 4)`` float64 ``STAT_KEYS``."""
+    peak normalisation: the mix of ``csrc/snr_mix.h``, which ``noise.mix_at_snr`` runs without a fade.  Four launches.
+    ``return_stats``: also the ``(rows, 4)`` float64 ``STAT_KEYS``."""
     _check_out(pl, y, "stimuli.finish")
     if pl["n_noise"]:
-        _check_device(noise, "stimuli.finish")
+        check_device_tensor(noise, "stimuli.finish")
         if noise.numel() < pl["n_noise"]:
             raise ValueError("stimuli.finish: the noise tensor is shorter than the rows that mix it")
     stats = torch.zeros((max(pl["rows"], 1), pl["stat_fields"]), dtype=torch.float64, device=y.device)
@@ -269,9 +252,10 @@ def reference(pl: dict, num_frames, curves=None, device="cuda"):
     device = curves.device if isinstance(curves, torch.Tensor) and curves.is_cuda else torch.device(device)
     to_device(pl, device)
     R = pl["rows"]
-    nf = [int(num_frames)] * R if np.ndim(num_frames) == 0 else [int(v) for v in num_frames]
-    if len(nf) != R or any(v < 0 for v in nf):
-        raise ValueError("stimuli.reference: one non-negative frame count per row")
+    one_each = "stimuli.reference: one non-negative frame count per row"
+    nf = per_row(num_frames, R, one_each).tolist()
+    if any(v < 0 for v in nf):
+        raise ValueError(one_each)
     table = np.zeros((max(R, 1), 2), np.int64)
     table[:R, 1] = nf
     table[:R, 0] = np.cumsum([0] + nf[:-1]) if R else 0
@@ -290,26 +274,16 @@ def reference(pl: dict, num_frames, curves=None, device="cuda"):
 def dynamic_metrics_rows(preds, refs, device="cuda"):
     """``pe_dynamic_metrics`` for R rows in one launch: ``preds[r]`` against ``refs[r]`` (tensors or arrays of Hz) over
     their first ``min(len)`` frames.  One dict of ``DYNAMIC_KEYS`` per row; the lag is in frames."""
-    def track(t):
-        if isinstance(t, torch.Tensor):
-            return t.detach().reshape(-1).to(device, torch.float32)
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(-1))).to(device)
-
     R = len(preds)
     if len(refs) != R:
         raise ValueError("dynamic_metrics: one reference per prediction")
     if R == 0:
         return []
-    lib = _lib.load()
-    P, F = [track(t) for t in preds], [track(t) for t in refs]
-    tracks = np.zeros((R, lib.pe_dynamic_metrics_fields()), np.int64)
-    po = ro = 0
+    (pred, po, pn), (ref, ro, rn) = pack_tracks(preds, device), pack_tracks(refs, device)
+    tracks = np.zeros((R, _lib.load().pe_dynamic_metrics_fields()), np.int64)
     for r in range(R):
-        tracks[r] = (po, min(P[r].numel(), F[r].numel()), ro)
-        po, ro = po + P[r].numel(), ro + F[r].numel()
-    dev = P[0].device
-    cat = lambda ts: torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=dev)])  # noqa: E731  (never empty)
-    pred, ref = cat(P), cat(F)
+        tracks[r] = (po[r], min(pn[r], rn[r]), ro[r])
+    dev = pred.device
     out = torch.empty((R, 4), dtype=torch.float64, device=dev)
     tracks_d = torch.from_numpy(tracks).to(dev)
     with torch.cuda.device(dev):
@@ -340,7 +314,7 @@ class StimulusSet:
         """One float32 device tensor per row: the analytic F0 at ``num_frames`` (an int, or one per row) frames, as the
         reference's ``sample_reference_f0`` samples it."""
         ref, offsets = reference(self.plan, num_frames, self.curves, self.audio.device)
-        nf = [int(num_frames)] * len(self) if np.ndim(num_frames) == 0 else [int(v) for v in num_frames]
+        nf = per_row(num_frames, len(self), "stimuli.reference: one non-negative frame count per row").tolist()
         return [ref[o:o + n] for o, n in zip(offsets, nf)]
 
     def items(self, hop_length: int = 300):
@@ -355,7 +329,7 @@ def build(rows, sr, curves=None, noise=None, device="cuda") -> StimulusSet:
     """The row specs as one packed batch: phase and synthesis for the curve rows, the partial sums for the tone rows,
     then ``finish``."""
     if curves is not None:
-        _check_device(curves, "stimuli.build")
+        check_device_tensor(curves, "stimuli.build")
         device = curves.device
     pl = to_device(plan_rows(rows, sr), device)
     y = torch.zeros((max(pl["n_samples"], 1),), dtype=torch.float32, device=device)

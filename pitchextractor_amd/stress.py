@@ -11,15 +11,14 @@ not depend on the rows.  ``inference.stress_sweep`` runs a model over a list of 
 """
 from __future__ import annotations
 
-import hashlib
 import math
 
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .ragged import (check_waves, device_plan, fft_roots, host_ptrs, i64, plan_arrays, real_split_roots, row_layout,
-                     workspace)
+from .ragged import (PackedRecordings, check_waves, device_plan, fft_roots, host_ptrs, i64, pack_tracks, per_row,
+                     plan_arrays, real_split_roots, row_layout, workspace)
 from .resample import RaggedResampler
 
 MAX_STAGES = 8
@@ -170,22 +169,15 @@ def _batch(x, lengths, what):
 _RIR_SPECTRA = {}
 
 
-class RirSet:
+class RirSet(PackedRecordings):
     """K impulse responses (1-D float arrays of any length >= 1, taken as they are: see ``prepare_rir``) as one ragged
-    batch.  Their partition spectra are made on the device once per set and device and kept."""
+    batch (``rirs``, ``lengths``, ``offsets``, ``packed``, ``key``, ``plan``).  Their partition spectra are made on the
+    device once per set and device and kept."""
 
     def __init__(self, rirs):
-        self.rirs = [np.ascontiguousarray(np.asarray(h, dtype=np.float32).reshape(-1)) for h in rirs]
-        if not self.rirs or any(h.size < 1 for h in self.rirs):
-            raise ValueError("RirSet: at least one impulse response, each of at least one sample")
-        self.lengths = [int(h.size) for h in self.rirs]
-        self.packed = np.concatenate(self.rirs)
-        self.key = hashlib.sha1(np.asarray(self.lengths, np.int64).tobytes() + self.packed.tobytes()).hexdigest()
-        offsets = np.cumsum([0] + self.lengths[:-1])
-        self.plan = plan_rows(self.lengths, offsets, offsets)
-
-    def __len__(self):
-        return len(self.rirs)
+        super().__init__(rirs, "RirSet: at least one impulse response, each of at least one sample")
+        self.rirs = self._items
+        self.plan = plan_rows(self.lengths, self.offsets, self.offsets)
 
     def device_spectra(self, device):
         """``(plan on the device, partition spectra)`` of the set."""
@@ -208,9 +200,7 @@ def apply_rir(x: torch.Tensor, rirs: RirSet, rir_index=0, lengths=None) -> torch
     divided by ``max|y| + 1e-6`` if ``max|y| > 0.99``: the notebook's ``apply_rir``.  Three launches."""
     pl, y = _batch(x, lengths, "apply_rir")
     R = pl["rows"]
-    index = [int(rir_index)] * R if np.ndim(rir_index) == 0 else [int(k) for k in rir_index]
-    if len(index) != R:
-        raise ValueError("apply_rir: one rir_index per row")
+    index = per_row(rir_index, R, "apply_rir: one rir_index per row").tolist()
     if any(k < 0 or k >= len(rirs) for k in index):
         raise ValueError("apply_rir: a rir_index lies outside the set")
     if R == 0 or pl["n_samples"] == 0:
@@ -336,7 +326,8 @@ def apply_additive_noise(x: torch.Tensor, sr, snr_db, source="white", seed=0, be
     (``noise.NOISE_COLOURS``) or a custom colour, drawn on the device with row r seeded ``seed + r`` (or ``seed[r]``)
     after ``warmup`` settling samples; or a ``noise.NoiseSet``, row r looping recording ``bed_index`` from its sample
     ``bed_start`` (numbers, or one per row).  ``peak_normalize``: the notebooks' ``max|y| > 0.99`` rule.
-    ``return_stats``: also the ``(rows, 4)`` float64 ``noise.STAT_KEYS``.  Six to eight launches."""
+    ``return_stats``: also the ``(rows, 4)`` float64 ``noise.STAT_KEYS``.  Six to eight launches: the noise (one for
+    white or a bed, three for a colour) and the mix's five (one fewer without the peak rule)."""
     from . import noise
     check_waves(x, "apply_additive_noise")
     x = x.contiguous()
@@ -378,29 +369,17 @@ def melody_metrics_rows(preds, refs, baselines=None, voicing_threshold_hz: float
     """The notebooks' ``compute_metrics`` for R rows in one launch (``pe_melody_metrics``): ``preds[r]`` against
     ``refs[r]`` over their first ``min(len)`` frames, and ``VUV_flips`` against ``baselines[r]`` (``None``: NaN) over the
     first ``min(len)`` frames of the two.  Tracks are arrays or tensors of Hz.  Returns one dict per row."""
-    def track(t):
-        if isinstance(t, torch.Tensor):
-            return t.detach().reshape(-1).to(device, torch.float32)
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(-1))).to(device)
-
     R = len(preds)
     if len(refs) != R or (baselines is not None and len(baselines) != R):
         raise ValueError("melody_metrics: one reference (and one baseline) per prediction")
     if R == 0:
         return []
-    lib = _lib.load()
-    P, F = [track(t) for t in preds], [track(t) for t in refs]
-    B = None if baselines is None else [track(t) for t in baselines]
-    tracks = np.zeros((R, lib.pe_melody_metrics_fields()), np.int64)
-    po = ro = bo = 0
+    (pred, po, pn), (ref, ro, rn) = pack_tracks(preds, device), pack_tracks(refs, device)
+    base, bo, bn = (None, [0] * R, [0] * R) if baselines is None else pack_tracks(baselines, device)
+    tracks = np.zeros((R, _lib.load().pe_melody_metrics_fields()), np.int64)
     for r in range(R):
-        tracks[r] = (po, min(P[r].numel(), F[r].numel()), ro, bo, 0 if B is None else min(P[r].numel(), B[r].numel()))
-        po, ro = po + P[r].numel(), ro + F[r].numel()
-        bo += 0 if B is None else B[r].numel()
-    dev = P[0].device
-    cat = lambda ts: torch.cat(ts + [torch.zeros(1, dtype=torch.float32, device=dev)])  # noqa: E731  (never empty)
-    pred, ref = cat(P), cat(F)
-    base = None if B is None else cat(B)
+        tracks[r] = (po[r], min(pn[r], rn[r]), ro[r], bo[r], 0 if base is None else min(pn[r], bn[r]))
+    dev = pred.device
     out = torch.empty((R, 7), dtype=torch.float64, device=dev)
     tracks_d = torch.from_numpy(tracks).to(dev)
     with torch.cuda.device(dev):
