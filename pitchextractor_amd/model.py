@@ -220,62 +220,57 @@ def _bn_slots(grads, mod: _BatchNorm, st):
     return dg, db
 
 
-def _no_amax(_param):
-    return None
+def _w(param):
+    """The parameter as ops.Scaled, with its word of the last ``JDCNet._refresh_weight_amax`` (no word outside "h2"
+    mode).  Only the call sites below that hand a weight to a product read the word: nothing inside ``ops`` does."""
+    # (the network's [word block or None], this parameter's index in it); a parameter no network has bound: no word
+    words, i = getattr(param, "h2_slot", ([None], 0))
+    return ops.Scaled(param, None if words[0] is None else words[0][i:i + 1])
 
 
-def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None, wa=_no_amax, tap=None, frozen=False):
+def _res_forward(blk: _ResBlock, x, pool, train, need_grad, slope, x_stats=None, tap=None, frozen=False):
     """x [B,T,F,Cin] -> [B,T,F/pool,Cout]; returns (out, saved, BatchNorm partials of out or None).  ``tap``
     (ops.Tap): the detector tap of x, taken by the pass that reads x here.  ``frozen``: no weight gradient will be
     asked for, so the two tensors only those read are not kept."""
     s = _Ctx()
     s.x = x
     s.bn_pre = _bn(blk.pre_conv[0], x, train, x_stats)
-    s.am_p = ops.amax_word()            # "h2" products: one absmax word per operand tensor, left by its producer
-    s.p = ops.bn_act_pool_fwd(x, s.bn_pre, pool=pool, slope=slope, amax_out=s.am_p, tap=tap)
-    out = ops.gemm_nt(_flat2(s.p), blk.conv1by1.weight.view(blk.cout, blk.cin), amax_a=s.am_p,
-                      amax_b=wa(blk.conv1by1.weight))
+    # "h2" products: one absmax word per operand tensor, left by its producer and carried with it (ops.Scaled)
+    s.p = ops.bn_act_pool_fwd(x, s.bn_pre, pool=pool, slope=slope, amax_out=True, tap=tap)
+    out = ops.gemm_nt(_flat2(s.p), _w(blk.conv1by1.weight).view(blk.cout, blk.cin))
     out = out.view(*s.p.shape[:3], blk.cout)
-    wf0, s.wd0 = ops.conv3x3_repack(blk.conv[0].weight, True, need_grad, amax=wa(blk.conv[0].weight))
-    s.c, c_stats = ops.conv3x3_fwd(s.p, wf0, bn_stats=train, amax=s.am_p)
+    wf0, s.wd0 = ops.conv3x3_repack(_w(blk.conv[0].weight), True, need_grad)
+    s.c, c_stats = ops.conv3x3_fwd(s.p, wf0, bn_stats=train)
     s.bn_mid = _bn(blk.conv[1], s.c, train, c_stats)
-    s.am_a = ops.amax_word()
-    s.a = ops.bn_act_pool_fwd(s.c, s.bn_mid, pool=1, slope=slope, amax_out=s.am_a)
-    wf3, s.wd3 = ops.conv3x3_repack(blk.conv[3].weight, True, need_grad, amax=wa(blk.conv[3].weight))
-    _, out_stats = ops.conv3x3_fwd(s.a, wf3, out=out, accumulate=True, bn_stats=train,   # conv(x) + conv1by1(x), model.py:171-172
-                                   amax=s.am_a)
+    s.a = ops.bn_act_pool_fwd(s.c, s.bn_mid, pool=1, slope=slope, amax_out=True)
+    wf3, s.wd3 = ops.conv3x3_repack(_w(blk.conv[3].weight), True, need_grad)
+    _, out_stats = ops.conv3x3_fwd(s.a, wf3, out=out, accumulate=True, bn_stats=train)   # conv(x) + conv1by1(x), model.py:171-172
     if frozen:
         s.p = s.a = None
     return out, s, out_stats
 
 
-def _res_backward(blk: _ResBlock, s, d_out, pool, slope, grads, side, am_do=None, wa=_no_amax, tap=None):
-    """d_out: grad of the block output (am_do: its absmax word if the producer left one).  Returns (grad wrt the block
-    input (dense, overwritten), its absmax word).  The three weight gradients go through `side` (_SideWork; None for a
-    frozen network: there are none).  ``tap`` (ops.Tap with its gradient): the detector tap of the block input, whose
-    gradient joins the returned one."""
-    if am_do is None:
-        am_do = ops.amax_for(d_out)
+def _res_backward(blk: _ResBlock, s, d_out, pool, slope, grads, side, tap=None):
+    """d_out: grad of the block output (ops.Scaled, as its producer left it).  Returns the grad wrt the block input
+    (ops.Scaled; dense, overwritten).  The three weight gradients go through `side` (_SideWork; None for a frozen
+    network: there are none).  ``tap`` (ops.Tap with its gradient): the detector tap of the block input, whose gradient
+    joins the returned one."""
     if side is not None:
-        side.run(lambda: (ops.conv3x3_wgrad(s.a, d_out, grads[blk.conv[3].weight], amax_x=s.am_a, amax_dy=am_do),
-                          ops.gemm_tn(_flat2(d_out), _flat2(s.p), out=grads[blk.conv1by1.weight].view(blk.cout, blk.cin),
-                                      amax_a=am_do, amax_b=s.am_p)),
-                 d_out, am_do, on=OVERLAP_CONV_WGRAD)
+        side.run(lambda: (ops.conv3x3_wgrad(s.a, d_out, grads[blk.conv[3].weight]),
+                          ops.gemm_tn(_flat2(d_out), _flat2(s.p), out=grads[blk.conv1by1.weight].view(blk.cout, blk.cin))),
+                 d_out, on=OVERLAP_CONV_WGRAD)
     with ops.timer_tag("dgrad"):
-        d_a = ops.conv3x3_fwd(d_out, s.wd3, amax=am_do)
-    am_dc = ops.amax_word()
+        d_a = ops.conv3x3_fwd(d_out, s.wd3)
     d_c = ops.bn_act_pool_bwd(s.c, d_a, s.bn_mid, *_bn_slots(grads, blk.conv[1], s.bn_mid), pool=1,
-                              slope=slope, dx=d_a, amax_out=am_dc)
+                              slope=slope, dx=d_a, amax_out=True)
     if side is not None:
-        side.run(lambda: ops.conv3x3_wgrad(s.p, d_c, grads[blk.conv[0].weight], amax_x=s.am_p, amax_dy=am_dc), d_c,
-                 am_dc, on=OVERLAP_CONV_WGRAD)
+        side.run(lambda: ops.conv3x3_wgrad(s.p, d_c, grads[blk.conv[0].weight]), d_c, on=OVERLAP_CONV_WGRAD)
     with ops.timer_tag("dgrad"):
-        d_p = ops.conv3x3_fwd(d_c, s.wd0, amax=am_dc)
-    w1t = ops.transpose2d(blk.conv1by1.weight.view(blk.cout, blk.cin))
-    ops.gemm_nt(_flat2(d_out), w1t, out=_flat2(d_p), accumulate=True, amax_a=am_do, amax_b=wa(blk.conv1by1.weight))
-    am_dx = ops.amax_word()
+        d_p = ops.conv3x3_fwd(d_c, s.wd0)
+    w1t = ops.transpose2d(_w(blk.conv1by1.weight).view(blk.cout, blk.cin))
+    ops.gemm_nt(_flat2(d_out), w1t, out=_flat2(d_p), accumulate=True)
     return ops.bn_act_pool_bwd(s.x, d_p, s.bn_pre, *_bn_slots(grads, blk.pre_conv[0], s.bn_pre),
-                               pool=pool, slope=slope, amax_out=am_dx, tap=tap), am_dx
+                               pool=pool, slope=slope, amax_out=True, tap=tap)
 
 
 class _DropoutCfg:
@@ -312,7 +307,7 @@ def _dropout_bwd(dy2d, p, mask, out2d=None):
     return out
 
 
-def _lstm_forward(models, xs, train, need_grad, drop: _DropoutCfg, wa=_no_amax, frozen=False):
+def _lstm_forward(models, xs, train, need_grad, drop: _DropoutCfg, frozen=False):
     """models: list of SequenceModel (identical shapes); xs: list of [B,T,in].  One launch per time step
     advances every (model, direction) cell of a layer together.  ``frozen``: the layer inputs and outputs, which only
     the weight gradients read, are not kept."""
@@ -323,20 +318,17 @@ def _lstm_forward(models, xs, train, need_grad, drop: _DropoutCfg, wa=_no_amax, 
     cur = list(xs)
     for layer in range(L):
         lay = _Ctx()
-        lay.x = cur
         lay.gates, lay.cbuf, lay.y, lay.mask = [], [], [], []
-        ys = [torch.empty((B, T, ND * H), dtype=torch.float32, device=cur[0].device) for _ in models]
-        whh, gts, ysl, cbs, rev = [], [], [], [], []
         # "h2" products: layer 0 reads the conv stack's features (one absmax pass each); deeper layers read LSTM
         # outputs, |h| < 1, scaled by the inter-layer dropout's 1 / (1 - p): a bound serves as the scale source
-        lay.am_x = [ops.amax_for(cur[mi]) if layer == 0 else
-                    ops.amax_bound(1.0 / (1.0 - (sm.dropout if train else 0.0)), cur[mi].device)
-                    for mi, sm in enumerate(models)]
+        lay.x = cur = [ops.Scaled.measured(x) if layer == 0 else
+                       ops.Scaled.bounded(x, 1.0 / (1.0 - (sm.dropout if train else 0.0))) for x, sm in zip(cur, models)]
+        ys = [torch.empty((B, T, ND * H), dtype=torch.float32, device=xs[0].device) for _ in models]
+        whh, gts, ysl, cbs, rev = [], [], [], [], []
         for mi, sm in enumerate(models):
             for d in range(ND):
                 w_ih, w_hh, b_ih, b_hh = sm.model.cell(layer, d)
-                g = ops.gemm_nt(_flat2(cur[mi]), w_ih, bias0=b_ih, bias1=b_hh, amax_a=lay.am_x[mi],
-                                amax_b=wa(w_ih)).view(B, T, 4 * H)
+                g = ops.gemm_nt(_flat2(cur[mi]), _w(w_ih), bias0=b_ih, bias1=b_hh).view(B, T, 4 * H)
                 cb = torch.empty((B, T, H), dtype=torch.float32, device=g.device)
                 whh.append(w_hh); gts.append(g); cbs.append(cb); rev.append(d)
                 ysl.append(ys[mi][:, :, d * H:(d + 1) * H])
@@ -419,7 +411,7 @@ LSTM_WGRAD_JOIN_EARLY = os.environ.get("PE_LSTM_WGRAD_JOIN", "early") == "early"
 FOLD_TAPS = os.environ.get("PE_FOLD_TAPS", "1") != "0"
 
 
-def _lstm_backward(models, saved, dys, grads, side, wa=_no_amax):
+def _lstm_backward(models, saved, dys, grads, side):
     """dys: list of [B,T,ND*H] grads of the top layer outputs.  Returns grads of the inputs.  Weight / bias gradients
     go through `side` (_SideWork; None for a frozen network: there are none) and are NOT joined here."""
     m0 = models[0].model
@@ -442,37 +434,34 @@ def _lstm_backward(models, saved, dys, grads, side, wa=_no_amax):
         nrows = ops.lstm_bwd_dbias_rows(len(whh_t), B, T, H, dsl[0].stride(1), dev)
         brows = [torch.empty((nrows, 4 * H), dtype=torch.float32, device=dev) for _ in whh_t] if nrows else None
         # "h2": the scale source of each cell's gate gradients comes out of the recurrence kernel where it can emit it
-        am_dg = [ops.amax_word() for _ in whh_t] if (nrows and ops.h2_active()) else None
-        have_db = ops.lstm_bwd(whh_t, lay.gates, lay.cbuf, dsl, dcs, rev, B, T, H,     # gates now hold d(pre-activations)
-                               dbias_rows=brows, amax_out=am_dg)
-        if am_dg is None:                                               # (else one pass per tensor; None outside "h2")
-            am_dg = [ops.amax_for(gt) for gt in lay.gates]
+        # (else one pass per tensor; none outside "h2")
+        have_db, dgs = ops.lstm_bwd(whh_t, lay.gates, lay.cbuf, dsl, dcs, rev, B, T, H,    # gates now hold d(pre-activations)
+                                    dbias_rows=brows, amax_out=True)
+        dgs = [ops.Scaled.measured(dg) for dg in dgs]
         # the data gradients first (the next layer's recurrence waits for them) ...
         dxs = []
         for mi, sm in enumerate(models):
             dx = torch.empty((B, T, sm.model.cell(layer, 0)[0].shape[1]), dtype=torch.float32, device=dev)
             for d in range(ND):
                 w_ih = sm.model.cell(layer, d)[0]
-                ops.gemm_nt(_flat2(lay.gates[mi * ND + d]), ops.transpose2d(w_ih), out=_flat2(dx), accumulate=(d > 0),
-                            amax_a=am_dg[mi * ND + d], amax_b=wa(w_ih))
+                ops.gemm_nt(_flat2(dgs[mi * ND + d]), ops.transpose2d(_w(w_ih)), out=_flat2(dx), accumulate=(d > 0))
             dxs.append(dx)
 
         # ... the weight / bias gradients need nothing downstream: on the (low-priority) side stream they fill the
         # CUs the next layer's persistent recurrence leaves idle (192 of 256) and then the gaps of the conv backward
-        def weight_grads(layer=layer, lay=lay, brows=brows, have_db=have_db, am_dg=am_dg):
+        def weight_grads(layer=layer, lay=lay, brows=brows, have_db=have_db, dgs=dgs):
             for mi, sm in enumerate(models):
                 x2 = _flat2(lay.x[mi])
                 for d in range(ND):
                     w_ih, w_hh, b_ih, b_hh = sm.model.cell(layer, d)
-                    dg = lay.gates[mi * ND + d]
+                    dg = dgs[mi * ND + d]
                     dg2 = _flat2(dg)
-                    ops.gemm_tn(dg2, x2, out=grads[w_ih], amax_a=am_dg[mi * ND + d], amax_b=lay.am_x[mi])
-                    ops.lstm_whh_grad(dg, lay.y[mi][:, :, d * H:(d + 1) * H], grads[w_hh], d, B, T, H,
-                                      amax_dg=am_dg[mi * ND + d])
-                    ops.colsum(brows[mi * ND + d] if have_db else dg2, grads[b_ih], grads[b_hh])
+                    ops.gemm_tn(dg2, x2, out=grads[w_ih])
+                    ops.lstm_whh_grad(dg, lay.y[mi][:, :, d * H:(d + 1) * H], grads[w_hh], d, B, T, H)
+                    ops.colsum(brows[mi * ND + d] if have_db else dg2.t, grads[b_ih], grads[b_hh])
 
         if side is not None:
-            side.run(weight_grads, brows, am_dg, on=OVERLAP_LSTM_WGRAD)   # (kept alive until the side stream has read them)
+            side.run(weight_grads, brows, dgs, on=OVERLAP_LSTM_WGRAD)   # (kept alive until the side stream has read them)
         dys = dxs
     return dys
 
@@ -516,6 +505,8 @@ def _residual_norm_bwd(dy, dy_add, st, norm, g, p, mask):
 def _tf_forward(sm, x, train, need_grad, drop: _DropoutCfg, frozen=False):
     """SequenceModel(transformer).forward (model.py:253-255) for one branch.  x [B,T,D] -> [B,T,D].  ``frozen``: the
     operands only the weight gradients read are not kept."""
+    # The products here and in _tf_backward take plain tensors, so in "h2" mode each runs its own absmax passes.
+    # Handing them `_w(weight)` is one line per site: a later change, to be measured on its own.
     B, T, D = x.shape
     H = sm.nhead
     dh = D // H
@@ -758,7 +749,9 @@ class JDCNet(nn.Module):
         self._grad_flat = None
         self._param_offsets = {id(p): off for p, off in zip(params, offsets)}
         self._param_list = params
-        self._wseg = self._wamax = None
+        self._wseg, self._wwords = None, [None]
+        for i, p in enumerate(params):      # where `_w` finds the parameter's word: bound once, filled per forward
+            p.h2_slot = (self._wwords, i)
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
@@ -804,23 +797,17 @@ class JDCNet(nn.Module):
         return self._grad_flat
 
     def _refresh_weight_amax(self):
-        """"h2" products: the absmax word of every parameter, one launch per forward over the flat buffer."""
-        if not ops.h2_active() or self._flat is None or not self._flat.is_cuda:
-            self._wamax = None
-            return
-        if getattr(self, "_wseg", None) is None or self._wseg[0].device != self._flat.device:
-            offs = torch.tensor([self._param_offsets[id(p)] for p in self._param_list], dtype=torch.int64)
-            lens = torch.tensor([p.numel() for p in self._param_list], dtype=torch.int64)
-            self._wseg = (offs.to(self._flat.device), lens.to(self._flat.device))
-            self._windex = {id(p): i for i, p in enumerate(self._param_list)}
-        self._wamax = ops.absmax_segments(self._flat.detach(), self._wseg[0], self._wseg[1])
+        """"h2" products: the absmax word of every parameter, one launch per forward over the flat buffer, into the
+        block every parameter's ``h2_slot`` points at (None outside "h2" mode) for ``scaled`` to hand out."""
+        self._wwords[0] = None
+        if ops.h2_active() and self._flat is not None and self._flat.is_cuda:
+            if getattr(self, "_wseg", None) is None or self._wseg[0].device != self._flat.device:
+                offs = torch.tensor([self._param_offsets[id(p)] for p in self._param_list], dtype=torch.int64)
+                lens = torch.tensor([p.numel() for p in self._param_list], dtype=torch.int64)
+                self._wseg = (offs.to(self._flat.device), lens.to(self._flat.device))
+            self._wwords[0] = ops.absmax_segments(self._flat.detach(), self._wseg[0], self._wseg[1])
 
-    def weight_amax(self, param):
-        """1-element view of the absmax word of ``param`` (None outside "h2" mode)."""
-        if getattr(self, "_wamax", None) is None:
-            return None
-        i = self._windex[id(param)]
-        return self._wamax[i:i + 1]
+    scaled = staticmethod(_w)       # a parameter of this network as ops.Scaled, with the word of the last refresh
 
     def status_slot(self) -> torch.Tensor:
         """1-element view of the flat gradient buffer behind the last parameter: 0 after a clean backward, non-zero
@@ -880,11 +867,9 @@ class JDCNet(nn.Module):
         cbk = self.conv_block
         s.y0, y0_stats = ops.conv3x3_c1_fwd(x_btf, cbk[0].weight, bn_stats=train)
         s.bn0 = _bn(cbk[1], s.y0, train, y0_stats)
-        s.am_a0 = ops.amax_word()
-        s.a0 = ops.bn_act_pool_fwd(s.y0, s.bn0, pool=1, slope=slope, amax_out=s.am_a0)
-        wf, s.wd_cb = ops.conv3x3_repack(cbk[3].weight, True, need_grad, amax=self.weight_amax(cbk[3].weight))
-        s.cb, st_cb = ops.conv3x3_fwd(s.a0, wf, bn_stats=train, amax=s.am_a0)        # convblock_out
-        wa = self.weight_amax
+        s.a0 = ops.bn_act_pool_fwd(s.y0, s.bn0, pool=1, slope=slope, amax_out=True)
+        wf, s.wd_cb = ops.conv3x3_repack(_w(cbk[3].weight), True, need_grad)
+        s.cb, st_cb = ops.conv3x3_fwd(s.a0, wf, bn_stats=train)                     # convblock_out
         # detector taps (model.py:45-49): max-pools of cb / rb1 / rb2 into channels [0, 384) of the concat.  Folded, each
         # is a by-product of the BN pass of the res block that reads the same tensor (no second read of 1 GB).
         s.taps = None
@@ -892,9 +877,9 @@ class JDCNet(nn.Module):
             s.concat = torch.empty((B, T, 2, 640), dtype=s.cb.dtype, device=x.device)  # (bf16 under ops.ACT_BF16)
             s.taps = [ops.Tap(s.concat, tp, coff, want_argmax=need_grad) for tp, coff in ((40, 0), (20, 64), (10, 192))]
         t_cb, t_rb1, t_rb2 = s.taps or (None, None, None)
-        s.rb1, s.r1, st1 = _res_forward(self.res_block1, s.cb, 2, train, need_grad, slope, st_cb, wa, t_cb, frozen)
-        s.rb2, s.r2, st2 = _res_forward(self.res_block2, s.rb1, 2, train, need_grad, slope, st1, wa, t_rb1, frozen)
-        s.rb3, s.r3, st3 = _res_forward(self.res_block3, s.rb2, 2, train, need_grad, slope, st2, wa, t_rb2, frozen)
+        s.rb1, s.r1, st1 = _res_forward(self.res_block1, s.cb, 2, train, need_grad, slope, st_cb, t_cb, frozen)
+        s.rb2, s.r2, st2 = _res_forward(self.res_block2, s.rb1, 2, train, need_grad, slope, st1, t_rb1, frozen)
+        s.rb3, s.r3, st3 = _res_forward(self.res_block3, s.rb2, 2, train, need_grad, slope, st2, t_rb2, frozen)
 
         # pool_block -> channels [384, 640) of the detector concat (model.py:36-41,90,108)
         Fp = s.rb3.shape[2] // 4
@@ -914,8 +899,7 @@ class JDCNet(nn.Module):
             _, s.arg_cb = ops.maxpool_fwd(s.cb, 40, out=s.concat, coff=0, want_argmax=True)
             _, s.arg_rb1 = ops.maxpool_fwd(s.rb1, 20, out=s.concat, coff=64, want_argmax=True)
             _, s.arg_rb2 = ops.maxpool_fwd(s.rb2, 10, out=s.concat, coff=192, want_argmax=True)
-        wdet = self.detector_conv[0].weight.view(256, 640)
-        s.dconv = ops.gemm_nt(s.concat.view(-1, 640), wdet, amax_b=self.weight_amax(self.detector_conv[0].weight))
+        s.dconv = ops.gemm_nt(s.concat.view(-1, 640), _w(self.detector_conv[0].weight).view(256, 640))
         s.dconv = s.dconv.view(B, T, 2, 256)
         s.bnd = _bn(self.detector_conv[1], s.dconv, train)
         dact = ops.bn_act_pool_fwd(s.dconv, s.bnd, pool=1, slope=slope)
@@ -924,7 +908,7 @@ class JDCNet(nn.Module):
 
         models = [self.sequence_classifier, self.sequence_detector]
         if models[0].model_type == "bilstm":
-            (yc, yd), s.lstm = _lstm_forward(models, [seq_c, seq_d], train, need_grad, self.dropout_cfg, wa, frozen)
+            (yc, yd), s.lstm = _lstm_forward(models, [seq_c, seq_d], train, need_grad, self.dropout_cfg, frozen)
         else:
             yc, s.tf_c = _tf_forward(models[0], seq_c, train, need_grad, self.dropout_cfg, frozen)
             yd, s.tf_d = _tf_forward(models[1], seq_d, train, need_grad, self.dropout_cfg, frozen)
@@ -975,8 +959,7 @@ class JDCNet(nn.Module):
         # weight-gradient kernels of the whole backward; joined once, at the end (a frozen network has none)
         side = None if frozen else _SideWork(dev)
         if models[0].model_type == "bilstm":
-            dseq_c, dseq_d = _lstm_backward(models, s.lstm, [dyc.view(B, T, D), dyd.view(B, T, D)], g, side,
-                                            self.weight_amax)
+            dseq_c, dseq_d = _lstm_backward(models, s.lstm, [dyc.view(B, T, D), dyd.view(B, T, D)], g, side)
             if LSTM_WGRAD_JOIN_EARLY and side is not None:
                 side.join()
         else:
@@ -999,7 +982,7 @@ class JDCNet(nn.Module):
         if side is not None:
             side.run(lambda: ops.gemm_tn(_flat2(d_dconv), s.concat.view(-1, 640), out=g[wdet].view(256, 640)), d_dconv,
                      on=OVERLAP_CONV_WGRAD)
-        d_concat = ops.gemm_nt(_flat2(d_dconv), ops.transpose2d(wdet.view(256, 640)), amax_b=self.weight_amax(wdet))
+        d_concat = ops.gemm_nt(_flat2(d_dconv), ops.transpose2d(_w(wdet).view(256, 640)))
         d_concat = d_concat.view(B, T, 2, 640)
         # classifier branch joins at the pool_block output (channels 384..639 of the concat)
         ops.seq_to_nhwc(dseq_c, d_concat, 256, coff=384, accumulate=True)
@@ -1007,8 +990,7 @@ class JDCNet(nn.Module):
         _dropout_bwd(d_concat.view(-1, 640)[:, 384:640], p_blk if s.mask_pool is not None else 0.0, s.mask_pool,
                      out2d=_flat2(d_pool))
         bnp = self.pool_block[0]
-        am3 = ops.amax_word()
-        d_rb3 = ops.bn_act_pool_bwd(s.rb3, d_pool, s.bnp, *_bn_slots(g, bnp, s.bnp), pool=4, slope=slope, amax_out=am3)
+        d_rb3 = ops.bn_act_pool_bwd(s.rb3, d_pool, s.bnp, *_bn_slots(g, bnp, s.bnp), pool=4, slope=slope, amax_out=True)
 
         cuts = self._dp_cuts if dp is not None else None
 
@@ -1016,31 +998,29 @@ class JDCNet(nn.Module):
             if cuts is not None:
                 dp.reduce_range(cuts[k], cuts[k + 1], after=side.pending_stream())
 
-        # each block-input gradient leaves its absmax word behind; the detector tap's max-pool gradient is added by the
-        # same pass (folded taps) or in place afterwards, and the values it rewrote are merged into the same word
-        wa = self.weight_amax
+        # each block-input gradient carries its absmax word (ops.Scaled); the detector tap's max-pool gradient is added
+        # by the same pass (folded taps) or in place afterwards, and the values it rewrote are merged into the same word
         t_cb, t_rb1, t_rb2 = s.taps or (None, None, None)
         for t in s.taps or ():
             t.grad = d_concat
-        d_rb2, am2 = _res_backward(self.res_block3, s.r3, d_rb3, 2, slope, g, side, am3, wa, t_rb2)
+        d_rb2 = _res_backward(self.res_block3, s.r3, d_rb3, 2, slope, g, side, t_rb2)
         block_done(3)                       # res_block3 + pool_block + detector_conv
         if s.taps is None:
-            ops.maxpool_bwd_add(s.rb2, d_concat, d_rb2, 10, coff=192, amax_out=am2, argmax=s.arg_rb2)
-        d_rb1, am1 = _res_backward(self.res_block2, s.r2, d_rb2, 2, slope, g, side, am2, wa, t_rb1)
+            d_rb2 = ops.maxpool_bwd_add(s.rb2, d_concat, d_rb2, 10, coff=192, argmax=s.arg_rb2)
+        d_rb1 = _res_backward(self.res_block2, s.r2, d_rb2, 2, slope, g, side, t_rb1)
         block_done(2)
         if s.taps is None:
-            ops.maxpool_bwd_add(s.rb1, d_concat, d_rb1, 20, coff=64, amax_out=am1, argmax=s.arg_rb1)
-        d_cb, am_dcb = _res_backward(self.res_block1, s.r1, d_rb1, 2, slope, g, side, am1, wa, t_cb)
+            d_rb1 = ops.maxpool_bwd_add(s.rb1, d_concat, d_rb1, 20, coff=64, argmax=s.arg_rb1)
+        d_cb = _res_backward(self.res_block1, s.r1, d_rb1, 2, slope, g, side, t_cb)
         block_done(1)
         if s.taps is None:
-            ops.maxpool_bwd_add(s.cb, d_concat, d_cb, 40, coff=0, amax_out=am_dcb, argmax=s.arg_cb)
+            d_cb = ops.maxpool_bwd_add(s.cb, d_concat, d_cb, 40, coff=0, argmax=s.arg_cb)
 
         cbk = self.conv_block
         if side is not None:
-            side.run(lambda: ops.conv3x3_wgrad(s.a0, d_cb, g[cbk[3].weight], amax_x=s.am_a0, amax_dy=am_dcb), d_cb,
-                     am_dcb, on=OVERLAP_CONV_WGRAD)
+            side.run(lambda: ops.conv3x3_wgrad(s.a0, d_cb, g[cbk[3].weight]), d_cb, on=OVERLAP_CONV_WGRAD)
         with ops.timer_tag("dgrad"):
-            d_a0 = ops.conv3x3_fwd(d_cb, s.wd_cb, amax=am_dcb)
+            d_a0 = ops.conv3x3_fwd(d_cb, s.wd_cb)
         d_y0 = ops.bn_act_pool_bwd(s.y0, d_a0, s.bn0, *_bn_slots(g, cbk[1], s.bn0), pool=1, slope=slope, dx=d_a0)
         if not frozen:
             ops.conv3x3_c1_wgrad(s.x_btf, d_y0, g[cbk[0].weight])

@@ -210,11 +210,6 @@ def h2_active() -> bool:
     return (not MATMUL_BF16) and FP32_MATMUL == "h2"
 
 
-def amax_for(t):
-    """absmax(t) in "h2" mode, else None: what model code hands on to the products that read ``t``."""
-    return absmax(t) if h2_active() else None
-
-
 _AMAX_POOL: dict = {}
 
 
@@ -235,18 +230,6 @@ def amax_word():
 _BOUND_AMAX: dict = {}
 
 
-def amax_bound(bound: float, device):
-    """absmax word for a tensor known to satisfy |x| <= bound (no pass over the data); None outside "h2" mode."""
-    if not h2_active():
-        return None
-    key = (torch.device(device), float(bound))
-    if key not in _BOUND_AMAX:
-        import struct
-        bits = struct.unpack("<i", struct.pack("<f", float(bound)))[0]
-        _BOUND_AMAX[key] = torch.full((1,), bits, dtype=torch.int32, device=key[0])
-    return _BOUND_AMAX[key]
-
-
 def absmax(t, out=None):
     """uint32 device word = IEEE bits of max |t| (t: float32, 1-D / 2-D row-strided / dense N-D): the scale source of
     an "h2" operand."""
@@ -262,6 +245,58 @@ def absmax(t, out=None):
     _chk(out.is_cuda and out.dtype == torch.int32 and out.numel() == 1, "absmax: out is an int32 device word")
     _call("pe_absmax", t.data_ptr(), rows, cols, ld, out.data_ptr(), _s())
     return out
+
+
+class Scaled:
+    """A tensor with its "h2" scale word: ``t``, and ``amax`` = the 1-element int32 device tensor with the IEEE bits of
+    max |t| (or of a bound on it), None for "not known".  Every product takes a plain tensor or a ``Scaled`` for an
+    operand and returns a plain tensor.  A plain tensor and a ``Scaled`` without a word are alike: an "h2" product then
+    takes the maximum in a pass of its own; the other forms read no word.  The pairing speaks of the buffer's contents
+    when it was made (a pass that overwrites ``t`` hands back a new one) and holds the reference that keeps the word's
+    memory from becoming the next ``absmax()``'s output before the product that reads it is launched.  Reshaping views
+    keep the word; an index or slice gives a plain tensor, whose maximum nobody knows.  Made by ``measured``, ``bounded``
+    or a producing pass (``bn_act_pool_fwd`` / ``_bwd``, ``lstm_bwd``) asked with ``amax_out=True``: the pass takes a
+    zeroed word of ``amax_word()`` and returns the pairing.  (A caller that passes its own zeroed word as ``amax_out``
+    holds the word already and gets the plain output.)"""
+
+    __slots__ = ("t", "amax")
+
+    def __init__(self, t, amax=None):
+        self.t, self.amax = t, amax
+
+    @classmethod
+    def measured(cls, t):
+        """``t`` (plain, or a ``Scaled``: a word it has is kept) with the word of a stand-alone ``absmax`` pass in "h2"
+        mode, without one otherwise."""
+        t, amax = _tw(t)
+        return cls(t, absmax(t) if (amax is None and h2_active()) else amax)
+
+    @classmethod
+    def bounded(cls, t, bound: float):
+        """``t`` known to satisfy |t| <= bound, with the constant word of the bound ("h2" mode; no pass over the data)."""
+        if not h2_active():
+            return cls(t)
+        key = (t.device, float(bound))
+        if key not in _BOUND_AMAX:
+            import struct
+            bits = struct.unpack("<i", struct.pack("<f", float(bound)))[0]
+            _BOUND_AMAX[key] = torch.full((1,), bits, dtype=torch.int32, device=key[0])
+        return cls(t, _BOUND_AMAX[key])
+
+    @property
+    def shape(self):
+        return self.t.shape
+
+    def view(self, *shape):
+        return Scaled(self.t.view(*shape), self.amax)
+
+    def __getitem__(self, index):
+        return self.t[index]
+
+
+def _tw(x):
+    """(tensor, scale word or None) of an operand: a plain tensor or a ``Scaled``."""
+    return (x.t, x.amax) if isinstance(x, Scaled) else (x, None)
 
 
 # which persistent LSTM recurrences use the three-term split when FP32_MATMUL == "x3" (tools/bench_lstm.py)
@@ -314,9 +349,10 @@ class matmul_bf16:
 
 
 # ------------------------------------------------------------------ GEMM
-def gemm_nt(A, B, bias0=None, bias1=None, out=None, accumulate=False, amax_a=None, amax_b=None):
-    """out[M,N] = A[M,K] @ B[N,K]^T + bias0 + bias1 (+ out).  ``amax_*``: the operands' absmax words when the caller
-    already has them ("h2" mode; computed here otherwise)."""
+def gemm_nt(A, B, bias0=None, bias1=None, out=None, accumulate=False):
+    """out[M,N] = A[M,K] @ B[N,K]^T + bias0 + bias1 (+ out).  A, B: plain tensors or ``Scaled`` (the operands' absmax
+    words when the caller already has them: "h2" mode; computed here otherwise)."""
+    (A, amax_a), (B, amax_b) = _tw(A), _tw(B)
     M, K, lda = _rows2d(A, "A", act=True)
     N, K2, ldb = _rows2d(B, "B")
     _chk(K == K2, "gemm_nt: K mismatch")
@@ -339,8 +375,9 @@ def gemm_nt(A, B, bias0=None, bias1=None, out=None, accumulate=False, amax_a=Non
     return out
 
 
-def gemm_tn(A, B, out=None, accumulate=False, amax_a=None, amax_b=None):
-    """out[M,N] = A[K,M]^T @ B[K,N] (+ out); deterministic split-K."""
+def gemm_tn(A, B, out=None, accumulate=False):
+    """out[M,N] = A[K,M]^T @ B[K,N] (+ out); deterministic split-K.  A, B: plain tensors or ``Scaled``."""
+    (A, amax_a), (B, amax_b) = _tw(A), _tw(B)
     K, M, lda = _rows2d(A, "A", act=True)
     K2, N, ldb = _rows2d(B, "B", act=True)
     _chk(K == K2, "gemm_tn: K mismatch")
@@ -362,6 +399,9 @@ def gemm_tn(A, B, out=None, accumulate=False, amax_a=None, amax_b=None):
 
 
 def transpose2d(x, out=None):
+    """x^T; of a ``Scaled`` a ``Scaled`` with the same word (the same values)."""
+    if isinstance(x, Scaled):
+        return Scaled(transpose2d(x.t, out), x.amax)
     x = _dense(x, "x")
     _chk(x.dim() == 2, "transpose2d: 2-D")
     if out is None:
@@ -380,19 +420,21 @@ CONV_WFRAG = os.environ.get("PE_CONV_WFRAG", "1") == "1"
 class PackedWeight:
     """One packed 3x3 weight: ``fp32`` [N, 9*C] (native MFMA path, fallback shapes) and, in the x3 / h2 / bf16 / f16
     modes, ``frag`` = the same matrix as 16-bit MFMA fragments packed for the pe_products value ``products`` (h2:
-    scaled by ``amax``, the weight's absmax word)."""
+    scaled by ``amax``, the weight's absmax word).  Built from the matrix as a plain tensor or a ``Scaled``, whose word
+    it keeps."""
 
-    def __init__(self, fp32, frag=None, products=None, amax=None):
-        self.fp32, self.frag, self.products, self.amax = fp32, frag, products, amax
+    def __init__(self, w, frag=None, products=None):
+        (self.fp32, self.amax), self.frag, self.products = _tw(w), frag, products
 
     @property
     def shape(self):
         return self.fp32.shape
 
 
-def wfrag_pack(w2d, products, amax=None):
+def wfrag_pack(w2d, products):
     """[N, K] float32 (K % 16 == 0) -> fragment-ordered 16-bit terms of the form ``products`` (uint8 buffer); h2 needs
-    the weight's absmax word."""
+    the weight's absmax word (a ``Scaled`` with one)."""
+    w2d, amax = _tw(w2d)
     N, K, ld = _rows2d(w2d, "w")
     nbytes = _lib.load().pe_wfrag_bytes(products, N, K)
     _chk(nbytes > 0, "wfrag_pack: K must be a multiple of 16 and the form x3, h2, bf16 or f16")
@@ -404,9 +446,10 @@ def wfrag_pack(w2d, products, amax=None):
     return out
 
 
-def conv3x3_repack(w, want_fwd=True, want_dgrad=True, amax=None):
-    """OIHW (Cout,Cin,3,3) -> (w_fwd [Cout, 9*Cin], w_dgrad [Cin, 9*Cout]) as ``PackedWeight``s.  ``amax``: the
-    weight's absmax word when the caller has it ("h2" mode)."""
+def conv3x3_repack(w, want_fwd=True, want_dgrad=True):
+    """OIHW (Cout,Cin,3,3), plain or ``Scaled`` -> (w_fwd [Cout, 9*Cin], w_dgrad [Cin, 9*Cout]) as ``PackedWeight``s
+    with the weight's absmax word ("h2" mode: the one handed over, else computed here)."""
+    w, amax = _tw(w)
     w = _dense(w, "w")
     _chk(w.dim() == 4 and w.shape[2:] == (3, 3), "conv3x3_repack: OIHW 3x3")
     co, ci = w.shape[0], w.shape[1]
@@ -423,18 +466,18 @@ def conv3x3_repack(w, want_fwd=True, want_dgrad=True, amax=None):
         if t is None:
             out.append(None)
         elif CONV_WFRAG and p != _lib.PE_PROD_NATIVE and t.shape[1] % 16 == 0:
-            out.append(PackedWeight(t, wfrag_pack(t, p, amax), p, amax))
+            out.append(PackedWeight(Scaled(t, amax), wfrag_pack(Scaled(t, amax), p), p))
         else:
-            out.append(PackedWeight(t, amax=amax))
+            out.append(PackedWeight(Scaled(t, amax)))
     return out[0], out[1]
 
 
-def conv3x3_fwd(x, w_packed, out=None, accumulate=False, bn_stats=None, amax=None):
-    """x [B,T,F,C], w_packed [N, 9*C] (tensor or PackedWeight) -> y [B,T,F,N] (+= when accumulate).
-    ``amax``: x's absmax word when the caller has it ("h2" mode; computed here otherwise).
+def conv3x3_fwd(x, w_packed, out=None, accumulate=False, bn_stats=None):
+    """x [B,T,F,C] (plain or ``Scaled``), w_packed [N, 9*C] (tensor or PackedWeight) -> y [B,T,F,N] (+= when accumulate).
     ``bn_stats`` True / False (not None) returns (y, partials): with True the fragment-fed kernel leaves the BatchNorm
     column sums of its final outputs behind ([tiles, 2, N] float64, for ``bn_train_stats(..., partials=)``);
     partials is None when not asked for or when another kernel ran."""
+    x, amax = _tw(x)
     x = _actd(x, "x")
     pw = w_packed if isinstance(w_packed, PackedWeight) else PackedWeight(w_packed)
     w32 = _dense(pw.fp32, "w_packed")
@@ -451,7 +494,7 @@ def conv3x3_fwd(x, w_packed, out=None, accumulate=False, bn_stats=None, amax=Non
     amax_w = None
     if p == _lib.PE_PROD_H2:
         amax_w = pw.amax if pw.amax is not None else absmax(w32)
-        amax = absmax(x) if amax is None else amax                      # (held: see conv3x3_wgrad)
+        amax = absmax(x) if amax is None else amax
     h2 = (_lib.ptr(amax), _lib.ptr(amax_w))
     work = 2.0 * B * T * F * N * 9 * Cc
     if pw.frag is not None and pw.products == p and CONV_WFRAG and _lib.load().pe_conv3x3_wf_supported(F, Cc, N):
@@ -467,8 +510,9 @@ def conv3x3_fwd(x, w_packed, out=None, accumulate=False, bn_stats=None, amax=Non
     return (out, None) if bn_stats is not None else out
 
 
-def conv3x3_wgrad(x, dy, dw, amax_x=None, amax_dy=None):
-    """dw (OIHW view, contiguous) = grad of conv3x3 wrt weights."""
+def conv3x3_wgrad(x, dy, dw):
+    """dw (OIHW view, contiguous) = grad of conv3x3 wrt weights.  x, dy: plain tensors or ``Scaled``."""
+    (x, amax_x), (dy, amax_dy) = _tw(x), _tw(dy)
     x = _actd(x, "x")
     dy = _actd(dy, "dy")
     dw = _dense(dw, "dw")
@@ -480,8 +524,7 @@ def conv3x3_wgrad(x, dy, dw, amax_x=None, amax_dy=None):
     _chk(not a16 or p == _lib.PE_PROD_BF16, "bfloat16 activations need the bf16 mixed-precision mode")
     ws = workspace(_lib.load().pe_conv3x3_wgrad_workspace_bytes(B, T, F, Ci, Co), x.device)
     if p == _lib.PE_PROD_H2:
-        # both words stay referenced until the launch: a temporary dropped after .data_ptr() returns its memory to
-        # the caching allocator, the second absmax() can reuse it, and x is then scaled by dy's word (Inf / NaN)
+        # (both words stay referenced until the launch: see ``Scaled``)
         amax_x = absmax(x) if amax_x is None else amax_x
         amax_dy = absmax(dy) if amax_dy is None else amax_dy
     _call("pe_conv3x3_wgrad", x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, T, F, Ci, Co, ws.data_ptr(), ws.numel(),
@@ -620,9 +663,10 @@ def _tap_folded(x, pool, tap: Tap, with_arg) -> bool:
 
 
 def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_out=None, tap: Tap | None = None):
-    """``amax_out``: a zeroed word from ``amax_word()``; the pass leaves the absmax of its output there.
+    """``amax_out``: a zeroed word, where the pass leaves the absmax of its output, or True (see ``Scaled``).
     ``tap``: also max-pool the raw x into ``tap.out`` (see ``Tap``), in the same pass where the library serves it."""
     x = _actd(x, "x")
+    paired, amax_out = amax_out is True, (amax_word() if amax_out is True else amax_out)
     B, T, F, Cc = x.shape
     Fo = F // pool
     if out is None:
@@ -635,7 +679,7 @@ def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_o
         _call("pe_bn_act_pool_tap_fwd", x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), slope, out.data_ptr(),
               B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), tap.out.data_ptr(), tld, tap.coff, tap.pool,
               _lib.ptr(tap.argmax), _s(), act16=_act16(x, out, tap.out))
-        return out
+        return Scaled(out, amax_out) if paired else out
     _call("pe_bn_act_pool_fwd", x.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), slope, out.data_ptr(),
           B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s(), act16=_act16(x, out))
     if tap is not None:
@@ -643,15 +687,17 @@ def bn_act_pool_fwd(x, st: BnState, pool=1, slope=0.01, out=None, coff=0, amax_o
             _, tap.argmax = maxpool_fwd(x, tap.pool, out=tap.out, coff=tap.coff, want_argmax=True)
         else:
             maxpool_fwd(x, tap.pool, out=tap.out, coff=tap.coff)
-    return out
+    return Scaled(out, amax_out) if paired else out
 
 
 def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=0, dx=None, amax_out=None,
                     tap: Tap | None = None):
-    """``tap`` (with ``grad`` and ``argmax`` set): dx also takes the gradient of the tap, and ``amax_out`` what
-    ``maxpool_bwd_add`` would have merged into it.  The mode follows ``st.eval``; with an eval-mode state ``dgamma`` and
-    ``dbeta`` may both be None (input gradient only: no per-channel reduction, no workspace)."""
+    """``amax_out``: as in ``bn_act_pool_fwd``, for dx.  ``tap`` (with ``grad`` and ``argmax`` set): dx also takes the
+    gradient of the tap, and ``amax_out`` what ``maxpool_bwd_add`` would have merged into it.  The mode follows
+    ``st.eval``; with an eval-mode state ``dgamma`` and ``dbeta`` may both be None (input gradient only: no per-channel
+    reduction, no workspace)."""
     x = _actd(x, "x")
+    paired, amax_out = amax_out is True, (amax_word() if amax_out is True else amax_out)
     B, T, F, Cc = x.shape
     ld = _slice_target(dy, B, T, F // pool, Cc, coff)
     if dx is None:
@@ -674,13 +720,13 @@ def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=
               st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), _lib.ptr(dgamma), _lib.ptr(dbeta),
               B * T, F, Cc, pool, ld, coff, ev, ws_ptr, ws_len, _lib.ptr(amax_out), tap.grad.data_ptr(), tld,
               tap.coff, tap.pool, tap.argmax.data_ptr(), _s(), act16=_act16(x, dy, dx, tap.grad))
-        return dx
+        return Scaled(dx, amax_out) if paired else dx
     _call("pe_bn_act_pool_bwd", x.data_ptr(), dy.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
           st.mean.data_ptr(), st.invstd.data_ptr(), slope, dx.data_ptr(), _lib.ptr(dgamma), _lib.ptr(dbeta),
           B * T, F, Cc, pool, ld, coff, ev, ws_ptr, ws_len, _lib.ptr(amax_out), _s(), act16=_act16(x, dy, dx))
     if tap is not None:
         maxpool_bwd_add(x, tap.grad, dx, tap.pool, coff=tap.coff, amax_out=amax_out, argmax=tap.argmax)
-    return dx
+    return Scaled(dx, amax_out) if paired else dx
 
 
 def maxpool_fwd(x, pool, out=None, coff=0, want_argmax=False):
@@ -699,8 +745,14 @@ def maxpool_fwd(x, pool, out=None, coff=0, want_argmax=False):
 
 
 def maxpool_bwd_add(x, dy, dx, pool, coff=0, amax_out=None, argmax=None):
-    """dx[first maximum of each window] += dy.  With ``argmax`` (from ``maxpool_fwd``) x is only used for its shape."""
+    """dx[first maximum of each window] += dy; the values written are max-merged into the word of a ``Scaled`` dx,
+    which comes back as a new pairing (or into the caller's own ``amax_out`` for a plain dx).  With ``argmax`` (from
+    ``maxpool_fwd``) x is only used for its shape."""
     B, T, F, Cc = x.shape
+    paired = isinstance(dx, Scaled)
+    if paired:
+        _chk(amax_out is None, "maxpool_bwd_add: a Scaled dx brings its word")
+        dx, amax_out = dx.t, dx.amax
     if argmax is None:
         x = _actd(x, "x")
     else:
@@ -710,7 +762,7 @@ def maxpool_bwd_add(x, dy, dx, pool, coff=0, amax_out=None, argmax=None):
     _chk(_actd(dx, "dx").shape == x.shape, "dx shape")
     _call("pe_maxpool_bwd_add", x.data_ptr() if argmax is None else 0, _lib.ptr(argmax), dy.data_ptr(), dx.data_ptr(),
           B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s(), act16=_act16(dy, dx, x if argmax is None else None))
-    return dx
+    return Scaled(dx, amax_out) if paired else dx
 
 
 def dropout(x2d, p, out2d=None, mask_in=None, want_mask=True, seed=0, offset=0):
@@ -851,8 +903,9 @@ def lstm_bwd(whh_t, gates, cbuf, dy_slices, dcarry, reverse, B, T, H, dbias_rows
     """Backward recurrences of len(whh_t) cells; gates become d(pre-activation gates) in place.  dbias_rows: optional
     list of [lstm_bwd_dbias_rows(...)][4H] buffers, one per cell, that receive the per-batch-tile column sums of the
     gate gradients (only pass it when that query is non-zero); returns True if they were written.  amax_out: optional
-    list of zeroed words (``amax_word()``), one per cell, filled with the gate gradients' absmax under the same
-    condition (else untouched: take ``absmax`` of the tensors)."""
+    list of zeroed words, one per cell, filled with the gate gradients' absmax under the same condition (else
+    untouched); or True (see ``Scaled``): then returns (bias rows written, the gate gradients as ``Scaled``: with the
+    words the kernel filled, else without one)."""
     n = len(whh_t)
     _chk(1 <= n <= 4 and len(gates) == len(dy_slices) == len(cbuf) == len(reverse) == len(dcarry) == n,
          "lstm_bwd: cell lists")
@@ -873,14 +926,17 @@ def lstm_bwd(whh_t, gates, cbuf, dy_slices, dcarry, reverse, B, T, H, dbias_rows
         if rows:
             _chk(len(dbias_rows) == n and all(_dense(d, "dbias_rows").shape == (rows, 4 * H) for d in dbias_rows),
                  "lstm_bwd: dbias_rows shape")
+        words = [None] * n
+        if rows and amax_out is not None:
+            words = [amax_word() for _ in gates] if amax_out is True else list(amax_out)
         _call("pe_lstm_bwd_persistent", n, _ptr_array(whh_t), _ptr_array(gates), _ptr_array(cbuf),
               _ptr_array(dy_slices), _int_array(reverse), ld, B, T, H, _ptr_array(dbias_rows) if rows else None,
-              _ptr_array(amax_out) if (rows and amax_out is not None) else None,
+              _ptr_array(words) if words[0] is not None else None,
               sync.data_ptr(), _s(), products=products_for("lstm_bwd"), work=2.0 * n * B * (T - 1) * 4 * H * H)
-        return bool(rows)
+        return (bool(rows), [Scaled(g, w) for g, w in zip(gates, words)]) if amax_out is True else bool(rows)
     _call("pe_lstm_bwd", n, _ptr_array(whh_t), _ptr_array(gates), _ptr_array(cbuf), _ptr_array(dy_slices),
           _ptr_array(dcarry), _int_array(reverse), ld, B, T, H, _s(), work=2.0 * n * B * (T - 1) * 4 * H * H)
-    return False
+    return (False, [Scaled(g) for g in gates]) if amax_out is True else False
 
 
 def lstm_bwd_dbias_rows(n, B, T, H, ld, device) -> int:
@@ -891,7 +947,9 @@ def lstm_bwd_dbias_rows(n, B, T, H, ld, device) -> int:
     return int(_lib.load().pe_lstm_bwd_persistent_dbias_rows(n, B, T, H, ld))
 
 
-def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H, amax_dg=None, amax_y=None):
+def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H):
+    """dgates, y_slice: plain tensors or ``Scaled``."""
+    (dgates, amax_dg), (y_slice, amax_y) = _tw(dgates), _tw(y_slice)
     _chk(_dense(dgates, "dgates").shape == (B, T, 4 * H), "dgates shape")
     ys = _f32c(y_slice, "y")
     _chk(ys.shape == (B, T, H) and ys.stride(2) == 1 and ys.stride(0) == T * ys.stride(1), "y slice layout")
@@ -902,7 +960,7 @@ def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H, amax_dg=None, amax_y=
     if p == _lib.PE_PROD_H2:
         if amax_y is None:                 # |h| < 1 by construction (o * tanh(c)): a constant bound is a valid amax
             amax_y = _unit_amax(dgates.device)
-        amax_dg = absmax(dgates) if amax_dg is None else amax_dg      # (held: see conv3x3_wgrad)
+        amax_dg = absmax(dgates) if amax_dg is None else amax_dg
     _call("pe_lstm_whh_grad", dgates.data_ptr(), ys.data_ptr(), ys.stride(1), dwhh.data_ptr(), B, T, H,
           int(bool(reverse)), ws.data_ptr(), ws.numel(), _lib.ptr(amax_dg), _lib.ptr(amax_y), _s(), products=p,
           work=2.0 * B * T * 4 * H * H)

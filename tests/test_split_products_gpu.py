@@ -278,7 +278,7 @@ def test_wfrag_pack_h2_and_x3_products_are_the_split_in_fragment_layout(hip_devi
     w[1, :3] = torch.tensor([2.0 ** -130, -(2.0 ** -120), 1 + 2.0 ** -11])
     amax = ops.absmax(w.to(hip_device))
     assert amax.item() == S.absmax_bits(w)
-    raw = ops.wfrag_pack(w.to(hip_device), _lib.PE_PROD_H2, amax).cpu()
+    raw = ops.wfrag_pack(ops.Scaled(w.to(hip_device), amax), _lib.PE_PROD_H2).cpu()
     frag = raw.view(torch.int16).view(K // 16, (N + 31) // 32, 2, 64, 8)
     hi, lo, _ = S.split_h2(w)
     for i, t in enumerate((hi, lo)):
@@ -311,7 +311,7 @@ def test_h2_amax_word_edges(hip_device, monkeypatch):
     amax = A.abs().max().item()
     cases = [16 * amax, amax / 2]
     for v in cases:
-        got = ops.gemm_nt(A.to(dev), Bd, amax_a=_word(v).to(dev))
+        got = ops.gemm_nt(ops.Scaled(A.to(dev), _word(v).to(dev)), Bd)
         m = h2m(S.op_nt, A, B, amax_a=S.f32_bits(v))
         check(got, m, tol, [("own word", S.h2_product(S.op_nt, A, B))])
         assert torch.isfinite(got).all()
@@ -320,7 +320,7 @@ def test_h2_amax_word_edges(hip_device, monkeypatch):
     rows = [5, 77]
     for r in rows:
         A2[r, 3] = -(1 - 2.0 ** -24)
-    got = ops.gemm_nt(A2.to(dev), Bd, amax_a=_word(amax / 4).to(dev)).cpu()
+    got = ops.gemm_nt(ops.Scaled(A2.to(dev), _word(amax / 4).to(dev)), Bd).cpu()
     m = h2m(S.op_nt, A2, B, amax_a=S.f32_bits(amax / 4))
     check(got, m, tol)
     bad = ~torch.isfinite(got)
@@ -329,7 +329,7 @@ def test_h2_amax_word_edges(hip_device, monkeypatch):
     At = S.heavy((M, K), 0, seed=13, scale=2.0 ** -118)
     ref = h2m(S.op_nt, At, B)
     for bits in (0, 1, S.absmax_bits(At)):
-        got = ops.gemm_nt(At.to(dev), Bd, amax_a=torch.tensor([bits], dtype=torch.int32, device=dev))
+        got = ops.gemm_nt(ops.Scaled(At.to(dev), torch.tensor([bits], dtype=torch.int32, device=dev)), Bd)
         check(got, h2m(S.op_nt, At, B, amax_a=bits), tol)
         check(got, ref, tol)
         assert (got != 0).any()
@@ -413,7 +413,7 @@ def test_f16_mfma_subnormal_factor_probe(hip_device, monkeypatch):
         k = k or 16
         a, b = Ak.float().to(dev), B[:, :k].float().to(dev)
         monkeypatch.setattr(ops, "FP32_MATMUL", "h2")
-        h2 = ops.gemm_nt(a, b, amax_a=word, amax_b=word).cpu().double()
+        h2 = ops.gemm_nt(ops.Scaled(a, word), ops.Scaled(b, word)).cpu().double()
         with ops.matmul_bf16(True, "f16"):
             f16 = ops.gemm_nt(a, b).cpu().double()
         assert torch.equal(h2, f16), k
@@ -532,10 +532,10 @@ BOUND_FACTOR = 2.0 ** 6       # a constant-bound word may overstate its operand 
 
 @pytest.mark.parametrize("nc,H", [(1, 384), (360, 64)])
 def test_h2_amax_words_in_a_training_step(hip_device, nc, H, monkeypatch):
-    """One JDCNet train forward and backward in h2 mode: every absmax word a product receives from model code is
-    checked against the operand it is used with, after a device synchronize.  Words from absmax, absmax_segments
+    """One JDCNet train forward and backward in h2 mode: every absmax word a product receives from model code, with its
+    operand as an ops.Scaled, is checked against that operand, after a device synchronize.  Words from absmax, absmax_segments
     and the producer epilogues (BN / pool passes, maxpool_bwd_add, the persistent backward's dgates_amax) must equal
-    max|operand| exactly; the constant words of amax_bound(1 / (1 - p)) and _unit_amax must bound it, within
+    max|operand| exactly; the constant words of Scaled.bounded(1 / (1 - p)) and _unit_amax must bound it, within
     BOUND_FACTOR.  The number of checks per op is asserted, so a refactor cannot skip them silently."""
     from oracle import model_ref
     from tests.test_model_gpu import build
@@ -567,32 +567,36 @@ def test_h2_amax_words_in_a_training_step(hip_device, nc, H, monkeypatch):
 
     orig = {k: getattr(ops, k) for k in EXACT_WORD_OPS}
 
-    def gemm_nt(A, B, *a, amax_a=None, amax_b=None, **k):
-        chk("gemm_nt", amax_a, A); chk("gemm_nt", amax_b, B)
-        return orig["gemm_nt"](A, B, *a, amax_a=amax_a, amax_b=amax_b, **k)
+    def chk_op(name, operand, default=None):         # an operand as the product gets it: plain or ops.Scaled
+        t, word = ops._tw(operand)
+        chk(name, default if word is None else word, t)
 
-    def gemm_tn(A, B, *a, amax_a=None, amax_b=None, **k):
-        chk("gemm_tn", amax_a, A); chk("gemm_tn", amax_b, B)
-        return orig["gemm_tn"](A, B, *a, amax_a=amax_a, amax_b=amax_b, **k)
+    def gemm_nt(A, B, *a, **k):
+        chk_op("gemm_nt", A); chk_op("gemm_nt", B)
+        return orig["gemm_nt"](A, B, *a, **k)
 
-    def conv3x3_fwd(x, w_packed, *a, amax=None, **k):
-        chk("conv3x3_fwd", amax, x)
+    def gemm_tn(A, B, *a, **k):
+        chk_op("gemm_tn", A); chk_op("gemm_tn", B)
+        return orig["gemm_tn"](A, B, *a, **k)
+
+    def conv3x3_fwd(x, w_packed, *a, **k):
+        chk_op("conv3x3_fwd", x)
         if isinstance(w_packed, ops.PackedWeight):
             chk("conv3x3_fwd", w_packed.amax, w_packed.fp32)
-        return orig["conv3x3_fwd"](x, w_packed, *a, amax=amax, **k)
+        return orig["conv3x3_fwd"](x, w_packed, *a, **k)
 
-    def conv3x3_repack(w, *a, amax=None, **k):
-        chk("conv3x3_repack", amax, w)
-        return orig["conv3x3_repack"](w, *a, amax=amax, **k)
+    def conv3x3_repack(w, *a, **k):
+        chk_op("conv3x3_repack", w)
+        return orig["conv3x3_repack"](w, *a, **k)
 
-    def conv3x3_wgrad(x, dy, dw, amax_x=None, amax_dy=None):
-        chk("conv3x3_wgrad", amax_x, x); chk("conv3x3_wgrad", amax_dy, dy)
-        return orig["conv3x3_wgrad"](x, dy, dw, amax_x=amax_x, amax_dy=amax_dy)
+    def conv3x3_wgrad(x, dy, dw):
+        chk_op("conv3x3_wgrad", x); chk_op("conv3x3_wgrad", dy)
+        return orig["conv3x3_wgrad"](x, dy, dw)
 
-    def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H_, amax_dg=None, amax_y=None):
-        chk("lstm_whh_grad", amax_dg, dgates)
-        chk("lstm_whh_grad", ops._unit_amax(dgates.device) if amax_y is None else amax_y, y_slice)
-        return orig["lstm_whh_grad"](dgates, y_slice, dwhh, reverse, B, T, H_, amax_dg=amax_dg, amax_y=amax_y)
+    def lstm_whh_grad(dgates, y_slice, dwhh, reverse, B, T, H_):
+        chk_op("lstm_whh_grad", dgates)
+        chk_op("lstm_whh_grad", y_slice, default=ops._unit_amax(ops._tw(dgates)[0].device))
+        return orig["lstm_whh_grad"](dgates, y_slice, dwhh, reverse, B, T, H_)
 
     for k, f in (("gemm_nt", gemm_nt), ("gemm_tn", gemm_tn), ("conv3x3_fwd", conv3x3_fwd),
                  ("conv3x3_repack", conv3x3_repack), ("conv3x3_wgrad", conv3x3_wgrad),

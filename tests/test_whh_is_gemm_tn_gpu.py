@@ -50,7 +50,8 @@ def test_lstm_whh_grad_equals_gemm_tn_of_shifted_y(hip_device, operands, form, r
     # h2: the same two scale words on both sides (the LSTM side's default for y is the word of 1.0, not absmax(y))
     amax = (amax_dg, ops._unit_amax(hip_device)) if form == "h2" else (None, None)
     with ctx:
-        dw = ops.lstm_whh_grad(dg, y, torch.full((4 * H, H), float("nan"), device=hip_device), reverse, B, T, H, *amax)
-        ref = ops.gemm_tn(dg.view(B * T, 4 * H), ysh.view(B * T, H), amax_a=amax[0], amax_b=amax[1])
+        dw = ops.lstm_whh_grad(ops.Scaled(dg, amax[0]), ops.Scaled(y, amax[1]),
+                               torch.full((4 * H, H), float("nan"), device=hip_device), reverse, B, T, H)
+        ref = ops.gemm_tn(ops.Scaled(dg.view(B * T, 4 * H), amax[0]), ops.Scaled(ysh.view(B * T, H), amax[1]))
     assert torch.equal(dw.view(torch.int32), ref.view(torch.int32))
     assert dw.abs().max() > 0

@@ -44,12 +44,12 @@ def bench_conv(B, F, C, args, dev):
     x = torch.randn(B, T, F, C, device=dev)
     w = torch.randn(C, C, 3, 3, device=dev) * 0.05
     out = torch.randn(B, T, F, C, device=dev)
-    am = ops.amax_for(x)
+    sx = ops.Scaled.measured(x)
     wf, _ = ops.conv3x3_repack(w, True, False)
     res = {}
     for name, acc, stats in (("off", False, True), ("on", True, True), ("off_nostats", False, False),
                              ("on_nostats", True, False)):
-        res[name] = median_ms(lambda: ops.conv3x3_fwd(x, wf, out=out, accumulate=acc, bn_stats=stats, amax=am),
+        res[name] = median_ms(lambda: ops.conv3x3_fwd(sx, wf, out=out, accumulate=acc, bn_stats=stats),
                               args.iters, args.warmup)
     return res
 
@@ -58,9 +58,9 @@ def bench_gemm(M, N, K, args, dev):
     a = torch.randn(M, K, device=dev)
     b = torch.randn(N, K, device=dev) * 0.05
     out = torch.randn(M, N, device=dev)
-    ama, amb = ops.amax_for(a), ops.amax_for(b)
-    return {name: median_ms(lambda: ops.gemm_nt(a, b, out=out, accumulate=acc, amax_a=ama, amax_b=amb), args.iters,
-                            args.warmup) for name, acc in (("off", False), ("on", True))}
+    sa, sb = ops.Scaled.measured(a), ops.Scaled.measured(b)
+    return {name: median_ms(lambda: ops.gemm_nt(sa, sb, out=out, accumulate=acc), args.iters, args.warmup)
+            for name, acc in (("off", False), ("on", True))}
 
 
 def main():

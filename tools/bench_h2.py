@@ -56,8 +56,8 @@ def fam_nt(modes):
         A = wide((M, K), 12) * 1e-3
         B = wide((N, K), 6) * 0.05
         outs = {m: torch.empty(M, N, device=dev) for m in modes}
-        am = (ops.absmax(A), ops.absmax(B))
-        fns = {m: (lambda m=m: ops.gemm_nt(A, B, out=outs[m], amax_a=am[0], amax_b=am[1])) for m in modes}
+        sa, sb = ops.Scaled(A, ops.absmax(A)), ops.Scaled(B, ops.absmax(B))
+        fns = {m: (lambda m=m: ops.gemm_nt(sa, sb, out=outs[m])) for m in modes}
         t = timed(fns)
         line = f"nt M={M:8d} N={N:4d} K={K:4d} "
         for m in modes:
@@ -76,8 +76,8 @@ def fam_tn(modes):
         A = wide((K, M), 12) * 1e-4
         B = wide((K, N), 4)
         outs = {m: torch.empty(M, N, device=dev) for m in modes}
-        am = (ops.absmax(A), ops.absmax(B))
-        fns = {m: (lambda m=m: ops.gemm_tn(A, B, out=outs[m], amax_a=am[0], amax_b=am[1])) for m in modes}
+        sa, sb = ops.Scaled(A, ops.absmax(A)), ops.Scaled(B, ops.absmax(B))
+        fns = {m: (lambda m=m: ops.gemm_tn(sa, sb, out=outs[m])) for m in modes}
         t = timed(fns)
         cols = torch.arange(0, M, max(M // 16, 1), device=dev)
         ref = A[:, cols].double().t() @ B.double()
@@ -106,8 +106,8 @@ def fam_conv(modes):
             ops.FP32_MATMUL = m
             pw, _ = ops.conv3x3_repack(w, want_dgrad=False)
             outs[m] = torch.empty(256, 192, F, Co, device=dev)
-            ax = ops.absmax(x)
-            fns[m] = (lambda m=m, pw=pw, ax=ax: ops.conv3x3_fwd(x, pw, out=outs[m], amax=ax))
+            sx = ops.Scaled(x, ops.absmax(x))
+            fns[m] = (lambda m=m, pw=pw, sx=sx: ops.conv3x3_fwd(sx, pw, out=outs[m]))
         t = timed(fns)
         xs = x[:2].permute(0, 3, 1, 2).double()
         ref = Fn.conv2d(xs, w.double(), padding=1).permute(0, 2, 3, 1)
@@ -130,8 +130,8 @@ def fam_wgrad(modes):
         x = wide((256, 192, F, Ci), 8)
         dy = wide((256, 192, F, Co), 12) * 1e-4
         outs = {m: torch.empty(Co, Ci, 3, 3, device=dev) for m in modes}
-        am = (ops.absmax(x), ops.absmax(dy))
-        fns = {m: (lambda m=m: ops.conv3x3_wgrad(x, dy, outs[m], amax_x=am[0], amax_dy=am[1])) for m in modes}
+        sx, sdy = ops.Scaled(x, ops.absmax(x)), ops.Scaled(dy, ops.absmax(dy))
+        fns = {m: (lambda m=m: ops.conv3x3_wgrad(sx, sdy, outs[m])) for m in modes}
         t = timed(fns)
         # float64 reference on a few output channels (all pixels)
         co = [0, Co // 2, Co - 1]
@@ -162,9 +162,8 @@ def fam_whh(modes):
     dg = wide((B, T, 4 * H), 12) * 1e-4
     y = torch.tanh(torch.randn(B, T, 2 * H, device=dev))
     outs = {m: torch.empty(4 * H, H, device=dev) for m in modes}
-    am = (ops.absmax(dg), ops.absmax(y.view(B * T, 2 * H)[:, :H]))
-    fns = {m: (lambda m=m: ops.lstm_whh_grad(dg, y[:, :, :H], outs[m], False, B, T, H, amax_dg=am[0], amax_y=am[1]))
-           for m in modes}
+    sdg, sy = ops.Scaled(dg, ops.absmax(dg)), ops.Scaled(y[:, :, :H], ops.absmax(y.view(B * T, 2 * H)[:, :H]))
+    fns = {m: (lambda m=m: ops.lstm_whh_grad(sdg, sy, outs[m], False, B, T, H)) for m in modes}
     t = timed(fns)
     hp = torch.zeros(B, T, H, dtype=torch.float64, device=dev)
     hp[:, 1:] = y[:, :-1, :H].double()

@@ -26,12 +26,11 @@ for (F, Ci, Co) in [(80, 64, 64), (40, 64, 128), (40, 128, 128), (20, 128, 192),
     dy = torch.randn(256, 192, F, Co, device=dev)
     dw = torch.empty(Co, Ci, 3, 3, device=dev)
     fl = 2.0 * 256 * 192 * F * Co * 9 * Ci
-    am = {"amax_x": ops.absmax(x), "amax_dy": ops.absmax(dy)}   # h2: the maxima held, as the model's backward holds them
+    sx, sdy = ops.Scaled(x, ops.absmax(x)), ops.Scaled(dy, ops.absmax(dy))   # h2: the maxima held, as in the model's backward
     row = []
     for mode, bf in (("native", False), ("x3", False), ("h2", False), ("native", True)):
         ops.FP32_MATMUL = mode
         with ops.matmul_bf16(bf):
-            kw = am if mode == "h2" else {}
-            ms = timed(lambda: ops.conv3x3_wgrad(x, dy, dw, **kw))
+            ms = timed(lambda: ops.conv3x3_wgrad(sx, sdy, dw))      # (the words are read in h2 mode only)
         row.append(f"{'bf16' if bf else mode}: {ms:.3f} ms ({fl / ms / 1e9:.0f} TF)")
     print(f"wgrad F={F} Cin={Ci} Cout={Co}: " + "  ".join(row), flush=True)

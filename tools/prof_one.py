@@ -15,9 +15,9 @@ ops.FP32_MATMUL = sys.argv[5] if len(sys.argv) > 5 else "h2"
 if kind == "nt":
     A, B = torch.randn(a, c, device=dev), torch.randn(b, c, device=dev) * 0.05
     out = torch.empty(a, b, device=dev)
-    am = (ops.absmax(A), ops.absmax(B)) if ops.h2_active() else (None, None)
+    sa, sb = ops.Scaled.measured(A), ops.Scaled.measured(B)
     for _ in range(4):
-        ops.gemm_nt(A, B, out=out, amax_a=am[0], amax_b=am[1])
+        ops.gemm_nt(sa, sb, out=out)
 elif kind == "tn":
     A, B = torch.randn(c, a, device=dev), torch.randn(c, b, device=dev)
     out = torch.empty(a, b, device=dev)
@@ -28,9 +28,9 @@ elif kind == "conv":
     w = torch.randn(c, b, 3, 3, device=dev) * 0.05
     out = torch.empty(256, 192, a, c, device=dev)
     wf = ops.conv3x3_repack(w, True, False)[0]
-    ax = ops.amax_for(x)
+    sx = ops.Scaled.measured(x)
     for _ in range(4):
-        ops.conv3x3_fwd(x, wf, out=out, amax=ax)
+        ops.conv3x3_fwd(sx, wf, out=out)
 else:
     x = torch.randn(256, 192, a, b, device=dev)
     dy = torch.randn(256, 192, a, c, device=dev)
