@@ -113,6 +113,31 @@ int pe_mel_forward_chunks(const pe_mel_plan* plan, const float* wave, long wave_
                           const long* host_chunks, int n_chunks, int chunk_size, float* out, long out_sb,
                           long out_sm, long out_st, int log_mode, float log_eps, float mean, float std,
                           float pad_value, void* stream);
+/* Backward of pe_mel_forward / pe_mel_forward_ragged with respect to the wave (the chunk-table mode has none).
+ * grad_out: d loss / d out, element (b, m, t) at grad_out[b*g_sb + m*g_sm + t*g_st] for t < out_frames, read at the
+ *       strides the forward writes `out` at.  Positions the forward wrote as padding (source frame t + frame_start[b]
+ *       at or past 1 + n/hop) carry no gradient and are never read: a NaN there does not reach grad_wave.
+ * grad_wave: [batch] rows of n_samples (max_samples) float32, row stride grad_wave_stride; every element is written
+ *       exactly once (no atomics: the caller need not clear it), samples at or past a ragged row's length and rows
+ *       of at most n_fft/2 samples as 0.
+ * The spectrum and the mel of every frame are recomputed from `wave`; `mean` does not enter the gradient.  A row's
+ * gradient is the same bits alone, in a batch of any size and at any row stride.  Two launches.
+ * workspace: pe_mel_backward_workspace_bytes(plan, batch, n_samples or max_samples, out_frames) bytes, never read
+ * before written (0 for a null plan or a non-positive size).
+ * Checked on the host before any device call: PE_E_ARG for a null pointer, a non-positive size, std == 0, a row
+ * stride below the row length or a fixed-batch n_samples <= n_fft/2; PE_E_UNSUPPORTED for batch > 65535, rows of
+ * more than 2^30 samples, a hop whose block segment does not fit in LDS, or a filterbank with more than two filters
+ * on one bin; PE_E_WORKSPACE when workspace_bytes is too small. */
+size_t pe_mel_backward_workspace_bytes(const pe_mel_plan* plan, int batch, int max_samples, int out_frames);
+int pe_mel_backward(const pe_mel_plan* plan, const float* wave, int batch, int n_samples, long wave_stride,
+                    const float* grad_out, long g_sb, long g_sm, long g_st, int out_frames, int log_mode,
+                    float log_eps, float mean, float std, float* grad_wave, long grad_wave_stride,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int pe_mel_backward_ragged(const pe_mel_plan* plan, const float* wave, int batch, int max_samples,
+                           long wave_stride, const int* n_samples, const int* frame_start,
+                           const float* grad_out, long g_sb, long g_sm, long g_st, int out_frames,
+                           int log_mode, float log_eps, float mean, float std, float* grad_wave,
+                           long grad_wave_stride, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- stitching chunk outputs into rows (inference.predict_f0_batch) --------------------------------------------------
  * pe_stitch_chunks: x is (n_chunks, chunk_size, C) float32, frame (k, f) at x + (k * chunk_size + f) * ld_x, unit

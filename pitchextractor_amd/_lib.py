@@ -47,6 +47,10 @@ PROTOTYPES = {
     "pe_mel_forward_ragged": (_i, [_p, _p, _i, _i, _l, _p, _p, _p, _l, _l, _l, _i, _i, _f, _f, _f, _f, _p]),
     "pe_mel_chunk_fields": (_i, []),
     "pe_mel_forward_chunks": (_i, [_p, _p, _l, _p, _p, _i, _i, _p, _l, _l, _l, _i, _f, _f, _f, _f, _p]),
+    "pe_mel_backward_workspace_bytes": (_z, [_p, _i, _i, _i]),
+    "pe_mel_backward": (_i, [_p, _p, _i, _i, _l, _p, _l, _l, _l, _i, _i, _f, _f, _f, _p, _l, _p, _z, _p]),
+    "pe_mel_backward_ragged": (_i, [_p, _p, _i, _i, _l, _p, _p, _p, _l, _l, _l, _i, _i, _f, _f, _f, _p, _l, _p, _z,
+                                    _p]),
     "pe_stitch_run_fields": (_i, []),
     "pe_stitch_chunks": (_i, [_p, _l, _p, _p, _p, _i, _i, _i, _i, _p, _l, _p, _l, _p]),
     "pe_gemm_nt": (_i, [_i, _i, _p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p, _p, _p]),

@@ -17,6 +17,7 @@
 #include <vector>
 #include "common.h"
 #include "dsp.h"
+#include "mel_plan.h"
 
 using namespace pe;
 
@@ -293,16 +294,6 @@ size_t mel_lds_bytes(int n_mels, int n_pairs, int fb) {
 
 }  // namespace
 
-struct pe_mel_plan {
-  int sample_rate, n_fft, hop, n_mels, n_freq, n_pairs;
-  void* d_base;
-  float* d_win;
-  float2* d_tw512;
-  float2* d_tw1024;
-  int* d_fb_idx;
-  float* d_fb_w;
-};
-
 extern "C" int pe_mel_plan_create(pe_mel_plan** plan_out, int sample_rate, int n_fft, int win_length,
                                   int hop_length, int n_mels, float f_min, float f_max) {
   if (!plan_out || sample_rate <= 0 || hop_length <= 0 || n_mels <= 0) return PE_E_ARG;
@@ -321,6 +312,11 @@ extern "C" int pe_mel_plan_create(pe_mel_plan** plan_out, int sample_rate, int n
   // sparse filterbank as 8-tap chunks: pair p covers bins [k0[p], k0[p] + 8) of one filter
   std::vector<int> pair_k0, mel_first(n_mels), mel_cnt(n_mels);
   std::vector<float> w;
+  // the same weights by bin, for the backward (mel_plan.h): at most two filters per bin, or no table
+  std::vector<int2> tfb_m(n_freq, make_int2(0, 0));
+  std::vector<float2> tfb_w(n_freq, make_float2(0.0f, 0.0f));
+  std::vector<int> tfb_n(n_freq, 0);
+  bool tfb_ok = true;
   for (int m = 0; m < n_mels; ++m) {
     int first = -1, last = -1;
     std::vector<float> col(n_freq);
@@ -330,7 +326,14 @@ extern "C" int pe_mel_plan_create(pe_mel_plan** plan_out, int sample_rate, int n
       const double up = (f_pts[m + 2] - f) / (f_pts[m + 2] - f_pts[m + 1]);
       const double v = fmax(0.0, fmin(down, up));
       col[k] = (float)v;
-      if (col[k] != 0.0f) { if (first < 0) first = k; last = k; }
+      if (col[k] != 0.0f) {
+        if (first < 0) first = k;
+        last = k;
+        const int slot = tfb_n[k]++;
+        if (slot == 0) { tfb_m[k].x = m; tfb_w[k].x = col[k]; }
+        else if (slot == 1) { tfb_m[k].y = m; tfb_w[k].y = col[k]; }
+        else tfb_ok = false;
+      }
     }
     mel_first[m] = (int)pair_k0.size();
     const int len = first < 0 ? 0 : last - first + 1;
@@ -369,13 +372,17 @@ extern "C" int pe_mel_plan_create(pe_mel_plan** plan_out, int sample_rate, int n
   size_t o_t10 = o_t5 + up256(sizeof(float2) * 512);
   size_t o_ix = o_t10 + up256(sizeof(float2) * 257);
   size_t o_w = o_ix + up256(sizeof(int) * idx.size());
-  size_t total = o_w + up256(sizeof(float) * (w.empty() ? 1 : w.size()));
+  size_t o_tm = o_w + up256(sizeof(float) * (w.empty() ? 1 : w.size()));
+  size_t o_tw = o_tm + up256(sizeof(int2) * n_freq);
+  size_t total = o_tw + up256(sizeof(float2) * n_freq);
   std::vector<char> host(total, 0);
   memcpy(host.data() + o_win, win.data(), sizeof(float) * kNfft);
   memcpy(host.data() + o_t5, tw512.data(), sizeof(float2) * 512);
   memcpy(host.data() + o_t10, tw1024.data(), sizeof(float2) * 257);
   memcpy(host.data() + o_ix, idx.data(), sizeof(int) * idx.size());
   if (!w.empty()) memcpy(host.data() + o_w, w.data(), sizeof(float) * w.size());
+  memcpy(host.data() + o_tm, tfb_m.data(), sizeof(int2) * n_freq);
+  memcpy(host.data() + o_tw, tfb_w.data(), sizeof(float2) * n_freq);
 
   void* d = nullptr;
   PE_CHECK_HIP(hipMalloc(&d, total));
@@ -397,6 +404,8 @@ extern "C" int pe_mel_plan_create(pe_mel_plan** plan_out, int sample_rate, int n
   p->d_tw1024 = reinterpret_cast<float2*>(c + o_t10);
   p->d_fb_idx = reinterpret_cast<int*>(c + o_ix);
   p->d_fb_w = reinterpret_cast<float*>(c + o_w);
+  p->d_tfb_m = tfb_ok ? reinterpret_cast<int2*>(c + o_tm) : nullptr;
+  p->d_tfb_w = tfb_ok ? reinterpret_cast<float2*>(c + o_tw) : nullptr;
   *plan_out = p;
   return PE_OK;
 }

@@ -71,6 +71,23 @@ def waveform_to_mel(audio, mel_transform: MelSpectrogram | None = None, device="
     return _normalised_log(tf(wave))
 
 
+def f0_from_wave(model: JDCNet, waves: torch.Tensor, lengths: torch.Tensor | None = None,
+                 mel_transform: MelSpectrogram | None = None, *, max_frames: int | None = None,
+                 frame_start: torch.Tensor | None = None):
+    """The model's outputs for (B, N) float32 device audio with the autograd graph intact: ``log_mel_batch`` (or
+    ``log_mel_ragged`` with int32 device ``lengths``), the transpose to the model's (B, 1, T, n_mels) input, the
+    model.  With a frozen ``model`` (``load_model(..., frozen=True)``) and ``waves`` that require grad, a loss on the
+    result back-propagates to the waveform through native kernels only (the F0 loss of something that emits audio).
+    ``max_frames``: frames per row, padded or truncated (default: the frames of N samples)."""
+    tf = mel_transform or _default_mel()
+    T = int(max_frames) if max_frames is not None else tf.num_frames(waves.shape[1])
+    if lengths is None:
+        mel = tf.log_mel_batch(waves, max_frames=T)
+    else:
+        mel = tf.log_mel_ragged(waves, lengths, frame_start, max_frames=T)
+    return model(mel.transpose(-1, -2))
+
+
 def _normalised_log(mel: torch.Tensor) -> torch.Tensor:
     """meldataset.py:650 as the notebooks apply it to a mel power tensor."""
     return (torch.log(mel + LOG_EPS) - MEL_MEAN) / MEL_STD

@@ -23,6 +23,38 @@ MEL_MEAN, MEL_STD = -4.0, 4.0
 MAX_MEL_LENGTH = 192
 
 
+def _tracked(waves: torch.Tensor) -> bool:
+    """True when the result has to join the autograd graph of ``waves``."""
+    return torch.is_grad_enabled() and waves.requires_grad
+
+
+class _MelOfWave(torch.autograd.Function):
+    """The forward launch as it is, with ``ops.mel_backward`` (csrc/mel_grad.hip) behind it: the backward recomputes
+    the spectrum from the saved wave, so nothing of the forward is kept.  ``run(waves)`` is the untracked call."""
+
+    @staticmethod
+    def forward(ctx, waves, mel, run, lengths, frame_start, log):
+        if waves.dim() == 2 and waves.shape[1] > 1 and waves.stride(1) != 1:
+            waves = waves.contiguous()
+        ctx.save_for_backward(waves, lengths, frame_start)
+        ctx.mel, ctx.log = mel, log
+        return run(waves)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import ops
+        waves, lengths, frame_start = ctx.saved_tensors
+        grad = ops.mel_backward(ctx.mel, waves, grad_out, lengths=lengths, frame_start=frame_start, log=ctx.log)
+        return grad, None, None, None, None, None
+
+
+def _no_out(out):
+    if out is not None:
+        raise ValueError("out= cannot be combined with a wave that requires grad: a caller-owned output does not "
+                         "join the autograd graph")
+
+
 class MelSpectrogram:
     """``transform(wave)``: (N,) -> (n_mels, 1 + N // hop) mel power, or (B, N) -> (B, n_mels, L).
 
@@ -30,6 +62,10 @@ class MelSpectrogram:
     from ``mel_params``; everything not listed keeps torchaudio's defaults
     (centre reflect padding, periodic Hann, power 2, HTK scale, norm None).
     Inputs must live on a HIP device: there is no CPU path.
+
+    Differentiable with respect to the wave: when grad is enabled and the wave requires grad, ``__call__``,
+    ``log_mel_batch`` and ``log_mel_ragged`` return the same values from the same launch with a ``grad_fn``
+    (``ops.mel_backward``, once differentiable; ``out=`` is refused).  Otherwise nothing is recorded.
     """
 
     def __init__(self, sample_rate=24000, n_fft=1024, win_length=None, hop_length=None,
@@ -102,12 +138,17 @@ class MelSpectrogram:
         waves = wave.unsqueeze(0) if single else wave
         if waves.dim() != 2:
             raise ValueError("expected (N,) or (B, N)")
-        L = self.num_frames(waves.shape[1])
-        out = torch.empty((waves.shape[0], self.n_mels, L), dtype=torch.float32, device=waves.device)
-        self._run(waves, out, (out.stride(0), out.stride(1), out.stride(2)), L, 0, 0.0)
+        out = (_MelOfWave.apply(waves, self, self._mel_power, None, None, False) if _tracked(waves)
+               else self._mel_power(waves))
         return out[0] if single else out
 
     forward = __call__
+
+    def _mel_power(self, waves: torch.Tensor) -> torch.Tensor:
+        L = self.num_frames(waves.shape[1])
+        out = torch.empty((waves.shape[0], self.n_mels, L), dtype=torch.float32, device=waves.device)
+        self._run(waves, out, (out.stride(0), out.stride(1), out.stride(2)), L, 0, 0.0)
+        return out
 
     def log_mel_batch(self, waves: torch.Tensor, max_frames: int = MAX_MEL_LENGTH,
                       out: torch.Tensor | None = None) -> torch.Tensor:
@@ -118,6 +159,9 @@ class MelSpectrogram:
         Utterances longer than ``max_frames`` frames are truncated on the right (the random
         crop of meldataset.py:668-672 is applied to the audio before this call).
         """
+        if _tracked(waves):
+            _no_out(out)
+            return _MelOfWave.apply(waves, self, lambda w: self.log_mel_batch(w, max_frames), None, None, True)
         B = waves.shape[0]
         if out is None:
             out = torch.empty((B, 1, self.n_mels, max_frames), dtype=torch.float32, device=waves.device)
@@ -130,6 +174,10 @@ class MelSpectrogram:
         ``frame_start`` (B,) int32 first frame kept per item (meldataset.py:668-672 random crop).
         Returns (B, 1, n_mels, max_frames) normalised log-mel; frames past an item's end are 0."""
         from . import ops
+        if _tracked(waves):
+            _no_out(out)
+            return _MelOfWave.apply(waves, self, lambda w: self.log_mel_ragged(w, lengths, frame_start, max_frames),
+                                    lengths, frame_start, True)
         if not (waves.is_cuda and lengths.is_cuda and waves.dtype == torch.float32 and waves.dim() == 2):
             raise RuntimeError("log_mel_ragged needs float32 (B, N) device audio and device lengths")
         if lengths.dtype != torch.int32 or lengths.numel() != waves.shape[0] or not lengths.is_contiguous():

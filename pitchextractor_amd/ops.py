@@ -1129,6 +1129,54 @@ def mel_forward_chunks(mel, wave, chunks, chunks_d, chunk_size, out=None, log=Tr
     return out
 
 
+def mel_backward(mel, wave, grad_out, *, lengths=None, frame_start=None, log=True, frames_last=True):
+    """Gradient of the mel front end with respect to the waveform (``pe_mel_backward`` / ``pe_mel_backward_ragged``):
+    ``mel`` a ``MelSpectrogram``, ``wave`` the (B, N) float32 device audio the forward saw, ``grad_out`` d loss / d out
+    of ``mel(wave)`` (``log=False``: (B, n_mels, T)) or of ``log_mel_batch`` / ``log_mel_ragged`` (``log=True``:
+    (B, 1, n_mels, T)); with ``frames_last=False`` the last two axes are (T, n_mels), the model's input layout.  It is
+    read at its own strides, so a transposed view costs no copy.  ``lengths`` / ``frame_start``: the int32 device
+    tensors of ``log_mel_ragged``.  Positions the forward padded are never read.  Returns (B, N) float32, every element
+    written by the kernels; the spectrum is recomputed from ``wave``, nothing of the forward is needed."""
+    from .mel import LOG_EPS, MEL_MEAN, MEL_STD
+    _f32c(wave, "wave")
+    _f32c(grad_out, "grad_out")
+    _chk(wave.dim() == 2 and (wave.shape[1] <= 1 or wave.stride(1) == 1), "wave: expected (B, N) rows of unit stride")
+    B, N = wave.shape
+    g = grad_out
+    if g.dim() == 4:
+        _chk(g.shape[1] == 1, "grad_out: expected (B, 1, n_mels, T) or (B, 1, T, n_mels)")
+        g = g[:, 0]
+    _chk(g.dim() == 3 and g.shape[0] == B and g.shape[1 if frames_last else 2] == mel.n_mels
+         and g.device == wave.device, "grad_out: expected one (n_mels, T) or (T, n_mels) map per wave row")
+    T = g.shape[2 if frames_last else 1]
+    g_sm, g_st = (g.stride(1), g.stride(2)) if frames_last else (g.stride(2), g.stride(1))
+    ragged = lengths is not None
+    _chk(ragged or frame_start is None, "frame_start needs lengths")
+    for t, nme in ((lengths, "lengths"), (frame_start, "frame_start")):
+        _chk(t is None or (t.is_cuda and t.dtype == torch.int32 and t.numel() == B and t.is_contiguous()),
+             f"{nme}: expected a contiguous int32 device tensor of size B")
+    _chk(ragged or N > mel.n_fft // 2, "wave: reflect padding needs more than n_fft / 2 samples")
+    grad_wave = torch.empty((B, N), dtype=torch.float32, device=wave.device)
+    if B == 0 or N == 0 or T == 0:
+        return grad_wave.zero_()
+    ld = wave.stride(0) if B > 1 else max(N, wave.stride(0))
+    plan = mel._get_plan(wave.device)
+    need = _lib.load().pe_mel_backward_workspace_bytes(plan, B, N, T)
+    ws = workspace(need, wave.device)
+    frames = B * T if ragged else B * min(mel.num_frames(N), T)
+    # algorithmic bytes per valid frame: hop samples read, hop written, n_mels floats of grad_out read
+    work = float(frames * 4 * (2 * mel.hop_length + mel.n_mels))
+    tail = (g.data_ptr(), g.stride(0), g_sm, g_st, T, int(bool(log)), LOG_EPS, MEL_MEAN, MEL_STD, grad_wave.data_ptr(),
+            grad_wave.stride(0), ws.data_ptr(), ws.numel(), _s())
+    with torch.cuda.device(wave.device):
+        if ragged:
+            _call("pe_mel_backward_ragged", plan, wave.data_ptr(), B, N, ld, lengths.data_ptr(), _lib.ptr(frame_start),
+                  *tail, work=work)
+        else:
+            _call("pe_mel_backward", plan, wave.data_ptr(), B, N, ld, *tail, work=work)
+    return grad_wave
+
+
 def stitch_chunks(x, runs, runs_d, out, det=None, det_out=None):
     """Chunk outputs to stitched rows by a run table (``pe_stitch_chunks``, ``inference.chunk_plan``): ``x``
     (n_chunks, chunk_size, C) or (n_chunks, chunk_size) float32 with unit stride over C and evenly spaced frames,
