@@ -544,6 +544,29 @@ int pe_world_responses(const float* sp, const float* ap, const float* noise, con
 int pe_world_overlap_add(const float* responses, const long* meta, const long* pulses, const float* gains,
                          const float* out_noise, int n_rows, long n_out, int fft_size, float* out, void* stream);
 
+/* ---- WORLD CheapTrick: the spectral envelope of a recording (pyworld.cheaptrick, WORLD's cheaptrick.cpp) ----------
+ * One frame per F0 value, frame f at f * frame_period_ms with f0 = F0[f] (500 Hz where F0[f] <= 3 fs / (fft_size - 3),
+ * or is not a number): F0-adaptive window, power spectrum, DC correction, linear smoothing of width 2 f0 / 3, + 2^-52,
+ * smoothing with recovery (lifter parameter q1).  float32 per frame; the two randn safeguards are dropped; the linear
+ * smoothing sums the covered bins and the two partial edge bins.  F0 belongs below fs / 2 (it is clamped there).
+ * fft_size 512 / 1024 / 2048, and 3 fs / (fft_size - 3) <= f0_floor: otherwise PE_E_UNSUPPORTED; PE_E_ARG for a
+ * non-positive or non-finite fs, frame_period_ms or f0_floor, a null pointer, n_rows outside 0 .. 65535.
+ * pe_cheaptrick_plan (host only, no device call) lays out a ragged batch: row r is the x_len[r] >= 0 samples at
+ * x + x_off[r] (at least one where frames are asked for), its F0 the f0_len[r] floats at f0 + f0_off[r]; frames
+ * [first_frame[r], first_frame[r] + n_frames[r]) of it (within f0_len[r]) are analysed, frame first_frame[r] + q going
+ * to the fft_size / 2 + 1 floats at sp + out_off[r] + q * out_stride[r] (out_stride[r] >= fft_size / 2 + 1).  It fills
+ * meta (n_rows x pe_cheaptrick_plan_fields() int64) and totals {frames}.
+ * pe_cheaptrick: one launch, one workgroup per (row, frame); host_meta: the host copy of meta (PE_E_ARG unless it is
+ * the plan's); table: exp(-2 pi i m / fft_size) for m < fft_size (re, im), what pe_world_responses' table opens with.
+ * A row's frames are bit-identical alone, at any offset, padded, anywhere in a batch and in any frame sub-range. */
+int pe_cheaptrick_plan_fields(void);
+int pe_cheaptrick_plan(int n_rows, const long* x_off, const long* x_len, const long* f0_off, const long* f0_len,
+                       const long* first_frame, const long* n_frames, const long* out_off, const long* out_stride,
+                       double fs, double frame_period_ms, double f0_floor, int fft_size, long* meta, long* totals);
+int pe_cheaptrick(const float* x, const float* f0, const long* meta, const long* host_meta, const float* table,
+                  int n_rows, double fs, double frame_period_ms, double q1, double f0_floor, int fft_size, float* sp,
+                  void* stream);
+
 /* ---- F0 bin decoding (build-defined; the inverse of pe_f0_bins_ce_loss) and pitch metrics --------------------
  * logits: N sequences of T frames of C bins, frame (n, t) at logits + n * ld_n + t * ld_t (2 <= C <= 1024, more is
  * PE_E_UNSUPPORTED).  Bin b stands for cents(b) = 20 b + 1997.3794084376191, f(b) = 10 * 2^(cents(b) / 1200) Hz.

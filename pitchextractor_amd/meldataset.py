@@ -18,7 +18,12 @@ GPU when its block carries ``backend: hip`` (``pitchextractor_amd.world``): a wo
 reference's order, computes the pulse positions of the drawn F0 curve (a sequential float64 recurrence) and the labels,
 and ships a ``WorldRequest`` instead of audio; the device synthesizes only the samples the cropped 192 mel frames read
 into the batch row.  With ``enabled: true`` alone the generator is logged as disabled, as the reference does without
-pyworld.  The pitch-shift augmentation (``synthetic_data.pitch_shift``,
+pyworld.  The analysis / resynthesis augmentation (``synthetic_data.world_resynthesis``, not a key of the reference;
+``enabled: true`` and ``backend: hip``) resynthesizes a listed file on a shifted F0 curve: a worker makes the draws
+(file, semitone, gain, vibrato, noise, crop), builds the new curve and its labels and ships a ``ResynthesisRequest``
+with the file's audio; the device estimates the file's spectral envelope (WORLD CheapTrick) over the frames the cropped
+window reads and synthesizes the window on the new curve, so the labels are exact.
+The pitch-shift augmentation (``synthetic_data.pitch_shift``,
 meldataset.py:324-517) runs on the GPU (``pitchextractor_amd.pitch_shift``): workers draw everything the reference
 draws, in its order, and ship the whole base file; the device shifts it and writes only the samples the cropped
 192 mel frames read into the batch row.  F0 labels come from the reference's cache files under the reference's own
@@ -68,7 +73,8 @@ from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS,
 from . import f0_tracker
 from .pitch_shift import check_res_type, pitch_shift_ragged
 from .resample import RaggedResampler, Resampler
-from .world import WorldGenerator, noise_seed, output_length, world_synthesize_ragged
+from .world import (CHEAPTRICK_Q1, WorldGenerator, check_fft_size, cheaptrick_fft_size, label_curve, noise_seed,
+                    output_length, resynthesize_ragged, time_base, world_synthesize_ragged)
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.DEBUG)
@@ -332,7 +338,50 @@ class WorldBatch(NamedTuple):
     seeds: tuple                               # K ints
 
 
-_SYNTHETIC_REQUESTS = (PitchShiftRequest, WorldRequest)
+class ResynthesisRequest(NamedTuple):
+    """What a worker hands the device for one analysis / resynthesis item (last element of the item tuple; the item's
+    first element is the base file's audio, as for a pitch-shifted one).  The device estimates the file's CheapTrick
+    envelope under ``base_curve`` and synthesizes samples [out_start, out_start + out_len) of it on ``curve``; the
+    item's labels are ``curve``, exact by construction.  ``n``: samples of the base file at the model rate."""
+    path: str
+    gain: float
+    n: int
+    crop: int
+    out_start: int
+    out_len: int
+    frame_start: int
+    base_curve: np.ndarray                     # float64 (frames,) the file's F0 labels, one per hop
+    curve: np.ndarray                          # float64 (frames,) the new curve = the labels (world.label_curve)
+    index: np.ndarray                          # the new curve's pulse table (world.time_base)
+    shift: np.ndarray
+    vuv: np.ndarray
+    seed: int                                  # of the aperiodic noise, drawn on the device
+    noise: np.ndarray | None                   # float32 (out_len,) slice of the full-length additive draw
+
+
+class ResynthesisBatch(NamedTuple):
+    """Collated resynthesis rows: their base files packed back to back (no padding) and their F0 labels likewise; the
+    new curves and their pulse tables feed the host-side plan and stay numpy arrays."""
+    rows: torch.Tensor                         # int64 (K,) batch rows
+    src: torch.Tensor                          # float32 flat source audio at the files' own rate
+    src_len: torch.Tensor                      # int64 (K,)
+    n: torch.Tensor                            # int64 (K,) lengths at the model rate
+    base: torch.Tensor                         # float32 flat, the base curves back to back
+    gains: torch.Tensor                        # float32 (K,)
+    out_len: torch.Tensor                      # int64 (K,)
+    noise: torch.Tensor | None                 # float32 flat, the windows back to back
+    src_sr: torch.Tensor                       # int32 (K,) the base files' rates
+    out_start: np.ndarray                      # int64 (K,)
+    curves: tuple                              # K float64 curves
+    tables: tuple                              # K (index, shift, vuv)
+    seeds: tuple                               # K ints
+
+
+_SYNTHETIC_REQUESTS = (PitchShiftRequest, WorldRequest, ResynthesisRequest)
+_SYNTHETIC_BATCHES = (PitchShiftBatch, WorldBatch, ResynthesisBatch)
+_RESYNTHESIS_KEYS = ("enabled", "backend", "semitones", "gain_db_range", "noise_db", "min_voiced_fraction",
+                     "max_attempts", "modulation", "aperiodicity", "q1")
+_RESYNTHESIS_MODULATION_KEYS = ("vibrato_probability", "vibrato_semitones", "vibrato_rate_range")
 
 
 def synthetic_window(n: int, crop: int, hop: int, n_fft: int, max_frames: int = MAX_MEL_LENGTH):
@@ -451,6 +500,17 @@ class MelDataset(torch.utils.data.Dataset):
             else:
                 logger.warning("[MelDataset] WORLD vocoder synthetic generation disabled: pyworld unavailable")
 
+        self.synthetic_resynthesis_config = None
+        resyn_cfg = config.get("world_resynthesis", {}) or {}
+        if resyn_cfg.get("enabled", False):
+            if str(resyn_cfg.get("backend", "")).lower() != "hip":
+                logger.warning("[MelDataset] WORLD analysis / resynthesis disabled: it exists with `backend: hip` only")
+            elif not self.data_list:
+                logger.warning("[MelDataset] WORLD analysis / resynthesis disabled: no base samples available")
+            else:
+                self.synthetic_resynthesis_config = self._check_resynthesis_config(resyn_cfg)
+                self._synthetic_generators.append("world_resynthesis")
+
         if not self._synthetic_generators or self._synthetic_count <= 0:
             self.synthetic_enabled = False
             self._synthetic_generators = []
@@ -475,9 +535,121 @@ class MelDataset(torch.utils.data.Dataset):
                 if result is not None:
                     return result
                 raise RuntimeError("Unable to produce synthetic pitch-shift sample")
+        if generator_name == "world_resynthesis":
+            result = self._generate_resynthesis_sample()
+            if result is not None:
+                return result
+            if "world_vocoder" not in self._synthetic_generators:
+                raise RuntimeError("Unable to produce synthetic resynthesis sample")
+            generator_name = "world_vocoder"                  # the one generator that needs no file; no draw for it
         if generator_name == "world_vocoder" and self._world_generator is not None:
             return self._generate_world_sample()
         raise RuntimeError(f"Unknown synthetic generator '{generator_name}'")
+
+    def _check_resynthesis_config(self, cfg):
+        """The ``world_resynthesis`` block with its defaults filled in; a key it does not read gets a warning, a value
+        it cannot use a ``ValueError``."""
+        for k in cfg:
+            if k not in _RESYNTHESIS_KEYS:
+                logger.warning("world_resynthesis: option %r is not read", k)
+        mod = dict(cfg.get("modulation", {}) or {})
+        for k in mod:
+            if k not in _RESYNTHESIS_MODULATION_KEYS:
+                logger.warning("world_resynthesis.modulation: option %r is not read", k)
+        gain = cfg.get("gain_db_range", [-6.0, 3.0])
+        if isinstance(gain, (int, float)):
+            gain = (float(gain), float(gain))
+        elif gain is not None:
+            gain = tuple(float(v) for v in gain)
+            if len(gain) != 2:
+                raise ValueError("world_resynthesis: gain_db_range must provide two values")
+        aperiodicity = float(cfg.get("aperiodicity", 0.0))
+        if not 0.0 <= aperiodicity < 1.0:
+            raise ValueError("world_resynthesis: aperiodicity must lie in [0, 1)")
+        rate = tuple(float(v) for v in mod.get("vibrato_rate_range", (4.0, 7.0)))
+        if len(rate) != 2:
+            raise ValueError("world_resynthesis: vibrato_rate_range must provide two values")
+        hop = int(self.mel_params["hop_length"])
+        noise_db = cfg.get("noise_db", None)
+        return {"semitones": list(cfg.get("semitones") or [-4, -2, -1, 1, 2, 4]), "gain_db_range": gain,
+                "noise_db": None if noise_db is None else float(noise_db),
+                "min_voiced_fraction": float(cfg.get("min_voiced_fraction", 0.05)),
+                "max_attempts": max(1, int(cfg.get("max_attempts", 5))),
+                "vibrato_probability": float(mod.get("vibrato_probability", 0.6)),
+                "vibrato_semitones": float(mod.get("vibrato_semitones", 0.35)), "vibrato_rate_range": rate,
+                "aperiodicity": aperiodicity, "q1": float(cfg.get("q1", CHEAPTRICK_Q1)),
+                "fft_size": check_fft_size(cheaptrick_fft_size(self.sr)), "frame_period": 1000.0 * hop / self.sr}
+
+    def _generate_resynthesis_sample(self):
+        """A listed file resynthesized on a new F0 curve (``world.resynthesize_ragged`` in the loader stage), after
+        ``_generate_pitch_shift_sample``.  Draws, in this order, per attempt: the file (``random.choice``); the
+        semitone (``random.choice``; 0 is allowed: a resynthesis at the file's own pitch); the gain
+        (``random.uniform``, unless ``gain_db_range`` is null); the vibrato (``random.random`` against its
+        probability and, when it applies with a positive depth, ``random.uniform`` for its rate); the additive noise
+        (``np.random.normal`` of the file's length, unless ``noise_db`` is null); the crop (``np.random.randint``, for a
+        file longer than 192 frames).  An unreadable, unlabelled or too sparsely voiced file ends the attempt after
+        the file draw.  Returns None when every attempt failed."""
+        cfg = self.synthetic_resynthesis_config
+        hop = int(self.mel_params["hop_length"])
+        fft_size, frame_period = cfg["fft_size"], cfg["frame_period"]
+        for _ in range(cfg["max_attempts"]):
+            available_paths = [p for p in self.data_list if p not in self._invalid_paths]
+            if not available_paths:
+                return None
+            base_path = random.choice(available_paths)
+            try:
+                wave, wave_sr = read_wav(base_path)
+            except (RuntimeError, OSError, ValueError, struct.error) as exc:
+                self._invalid_paths.add(base_path)
+                logger.warning("[MelDataset] Skipping unreadable audio file: %s (%s)", base_path, exc)
+                continue
+            if wave.ndim > 1:
+                wave = np.mean(wave, axis=-1)
+            wave = wave.astype(np.float32)
+            n = Resampler(wave_sr, self.sr).out_len(len(wave)) if wave_sr != self.sr else len(wave)
+            try:
+                base_f0 = self._f0_for(base_path, wave, 0, None)
+            except RuntimeError as exc:
+                logger.warning("[MelDataset] %s", exc)
+                base_f0 = np.zeros((0,), dtype=np.float32)
+            mel_len = 1 + n // hop
+            if base_f0.size == 0 or mel_len < 2:
+                continue
+            if float(np.count_nonzero(base_f0 > 0)) / max(1, base_f0.size) < cfg["min_voiced_fraction"]:
+                continue
+            # one analysis frame per mel frame: frame f of both sits on sample f * hop
+            base = align_length(np.asarray(base_f0, dtype=np.float32), mel_len).astype(np.float64)
+            base = np.where(np.isfinite(base) & (base > 0), base, 0.0)
+            semitone = random.choice(cfg["semitones"])
+            gain = 1.0
+            if cfg["gain_db_range"] is not None:
+                low, high = sorted(cfg["gain_db_range"])
+                gain = 10.0 ** (random.uniform(low, high) / 20.0)
+            new = base * float(2 ** (semitone / 12.0))
+            if random.random() < cfg["vibrato_probability"]:
+                depth = max(cfg["vibrato_semitones"], 0.0)
+                if depth > 0:
+                    rate = random.uniform(*cfg["vibrato_rate_range"])
+                    t = np.arange(mel_len, dtype=np.float64) * (frame_period / 1000.0)
+                    new = new * 2.0 ** (np.sin(2.0 * math.pi * rate * t) * (depth / 12.0))
+            curve = label_curve(new, self.sr, fft_size)
+            noise = None
+            if cfg["noise_db"] is not None:
+                noise = np.random.normal(scale=10.0 ** (cfg["noise_db"] / 20.0), size=(n,)).astype(np.float32)
+            f0 = align_length(curve.astype(np.float32), mel_len)
+            sil = (f0 == 0).astype(np.float32)
+            crop = 0
+            if mel_len > self.max_mel_length:
+                crop = int(np.random.randint(0, mel_len - self.max_mel_length))
+                f0 = f0[crop:crop + self.max_mel_length]
+                sil = sil[crop:crop + self.max_mel_length]
+            start, count, first = synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
+            table = time_base(curve, self.sr, frame_period, fft_size)
+            req = ResynthesisRequest(base_path, float(gain), int(n), crop, start, count, first, base, curve,
+                                     table.index, table.shift, table.vuv, noise_seed(curve),
+                                     None if noise is None else np.ascontiguousarray(noise[start:start + count]))
+            return torch.from_numpy(wave), torch.from_numpy(f0), torch.from_numpy(sil), first, int(wave_sr), req
+        return None
 
     def _generate_world_sample(self):
         """Utils/synthetic.py:194-220 + _build_training_example (meldataset.py:629-677) with the synthesis left to the
@@ -913,8 +1085,9 @@ class Collater(object):
     rates, an int32 ``(B,)`` tensor of per-row rates (0 for an item without one),
     followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram and by a
     ``PitchShiftBatch`` when any item is a pitch-shifted one, then by a ``WorldBatch`` when any item is a WORLD-vocoder
-    one.  A synthetic row's waveform is left zero (the device writes its window there) and its length is that
-    window's; a pitch-shifted row's base file is packed, not padded."""
+    one, then by a ``ResynthesisBatch`` when any item is a resynthesized one.
+    A synthetic row's waveform is left zero (the device writes its window there) and its length is that
+    window's; a pitch-shifted or resynthesized row's base file is packed, not padded."""
 
     def __init__(self, return_wave=False):
         self.return_wave = return_wave
@@ -937,6 +1110,7 @@ class Collater(object):
             return mels.unsqueeze(1), f0s, sils
         syn = [i for i, item in enumerate(batch) if isinstance(item[-1], PitchShiftRequest)]
         wld = [i for i, item in enumerate(batch) if isinstance(item[-1], WorldRequest)]
+        rsy = [i for i, item in enumerate(batch) if isinstance(item[-1], ResynthesisRequest)]
         n_max = max(int(item[-1].out_len) if isinstance(item[-1], _SYNTHETIC_REQUESTS) else int(item[0].shape[0])
                     for item in batch)
         waves = torch.zeros((B, n_max), dtype=torch.float32)
@@ -989,6 +1163,21 @@ class Collater(object):
                                np.array([r.out_start for r in reqs], dtype=np.int64),
                                tuple(r.curve for r in reqs), tuple((r.index, r.shift, r.vuv) for r in reqs),
                                tuple(r.seed for r in reqs)),)
+        if rsy:
+            reqs = [batch[i][-1] for i in rsy]
+            noise = None
+            if reqs[0].noise is not None:
+                noise = torch.from_numpy(np.concatenate([r.noise for r in reqs]).astype(np.float32))
+            i64 = lambda v: torch.tensor(v, dtype=torch.int64)  # noqa: E731
+            out += (ResynthesisBatch(i64(rsy), torch.cat([batch[i][0].reshape(-1) for i in rsy]),
+                                     i64([int(batch[i][0].shape[0]) for i in rsy]), i64([r.n for r in reqs]),
+                                     torch.from_numpy(np.concatenate([r.base_curve for r in reqs]).astype(np.float32)),
+                                     torch.tensor([r.gain for r in reqs], dtype=torch.float32),
+                                     i64([r.out_len for r in reqs]), noise,
+                                     torch.tensor([row_rates[i] for i in rsy], dtype=torch.int32),
+                                     np.array([r.out_start for r in reqs], dtype=np.int64),
+                                     tuple(r.curve for r in reqs), tuple((r.index, r.shift, r.vuv) for r in reqs),
+                                     tuple(r.seed for r in reqs)),)
         return out
 
 
@@ -1006,7 +1195,7 @@ class H2DPrefetcher:
 
     def submit(self, host_items):
         def to_dev(t):
-            if isinstance(t, (PitchShiftBatch, WorldBatch)):
+            if isinstance(t, _SYNTHETIC_BATCHES):
                 return type(t)(*(to_dev(x) for x in t))
             return t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t
         with torch.cuda.stream(self.stream):
@@ -1020,7 +1209,7 @@ class H2DPrefetcher:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ready)
         for t in dev:
-            for x in (t if isinstance(t, (PitchShiftBatch, WorldBatch)) else (t,)):
+            for x in (t if isinstance(t, _SYNTHETIC_BATCHES) else (t,)):
                 if torch.is_tensor(x) and x.is_cuda:
                     x.record_stream(cur)          # allocated on the side stream, consumed on the compute stream
         return dev
@@ -1084,11 +1273,36 @@ class DeviceMelLoader:
         lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
         return waves, lengths
 
+    def _resynthesis(self, waves, lengths, pack, host):
+        """Resynthesized rows: bring their packed base files to the model rate (if needed), estimate the envelope of
+        the frames each row's window reads and synthesize the window on the row's new curve."""
+        sr = self.mel.sample_rate
+        cfg = self.dataset.synthetic_resynthesis_config
+        src, n = pack.src, host.n.tolist()
+        rates = host.src_sr.tolist()
+        if any(r and r != sr for r in rates):                 # base files at their own rates: one ragged launch
+            src, _ = self._ragged(src, [r or sr for r in rates], host.src_len.tolist())
+        need = int(host.out_len.max())
+        if waves.shape[1] < need:
+            waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
+        waves = waves.contiguous()
+        bins = cfg["fft_size"] // 2 + 1
+        ap = None
+        if cfg["aperiodicity"] > 0:
+            ap = torch.full((bins,), cfg["aperiodicity"], dtype=torch.float32, device=waves.device)
+        resynthesize_ragged(src, n, pack.base.split([len(c) for c in host.curves]), host.curves, sr,
+                            cfg["frame_period"], ap=ap, seeds=host.seeds, gains=pack.gains, out=waves,
+                            out_rows=host.rows.numpy(), out_start=host.out_start, out_len=host.out_len.numpy(),
+                            out_noise=pack.noise, tables=host.tables, q1=cfg["q1"], fft_size=cfg["fft_size"])
+        lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
+        return waves, lengths
+
     def _finish(self, ticket):
         waves, lengths, crops, f0s, sils, src_sr, *cached = self._h2d.acquire(ticket)
+        resyn = cached.pop() if cached and isinstance(cached[-1], ResynthesisBatch) else None
         world = cached.pop() if cached and isinstance(cached[-1], WorldBatch) else None
         pack = cached.pop() if cached and isinstance(cached[-1], PitchShiftBatch) else None
-        host_pack, host_world = self._host_packs.pop(0)
+        host_pack, host_world, host_resyn = self._host_packs.pop(0)
         host_lengths, host_rates = self._host_lengths.pop(0), self._host_rates.pop(0)
         sr = self.mel.sample_rate
         rates = host_rates if host_rates is not None else [src_sr] * len(host_lengths)
@@ -1096,14 +1310,17 @@ class DeviceMelLoader:
             # one ragged launch, each row at its own rate and bit-identical to that item resampled alone; synthetic
             # rows are left zero (length 0) for the pitch shift, which resamples their base files itself
             syn = set(host_pack.rows.tolist()) if host_pack is not None else set()
-            if host_world is not None:
-                syn |= set(host_world.rows.tolist())
+            for other in (host_world, host_resyn):
+                if other is not None:
+                    syn |= set(other.rows.tolist())
             waves, lengths = self._ragged(waves, [r or sr for r in rates],
                                           [0 if i in syn else int(n) for i, n in enumerate(host_lengths)])
         if pack is not None:                                  # after the resampler, before the one mel launch
             waves, lengths = self._pitch_shift(waves, lengths, src_sr, pack, host_pack)
         if world is not None:
             waves, lengths = self._world(waves, lengths, world, host_world)
+        if resyn is not None:
+            waves, lengths = self._resynthesis(waves, lengths, resyn, host_resyn)
         mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
         if cached:                                            # rows whose spectrogram came from <wav>_mel.npy
             rows, cached_mels = cached
@@ -1125,9 +1342,9 @@ class DeviceMelLoader:
         for host in self.loader:
             self._host_lengths.append(host[1].tolist())
             self._host_rates.append(host[5].tolist() if torch.is_tensor(host[5]) else None)
-            packs = [t for t in host[6:] if isinstance(t, (PitchShiftBatch, WorldBatch))]
-            self._host_packs.append((next((t for t in packs if isinstance(t, PitchShiftBatch)), None),
-                                     next((t for t in packs if isinstance(t, WorldBatch)), None)))
+            packs = [t for t in host[6:] if isinstance(t, _SYNTHETIC_BATCHES)]
+            self._host_packs.append(tuple(next((t for t in packs if isinstance(t, kind)), None)
+                                          for kind in _SYNTHETIC_BATCHES))
             ticket = self._h2d.submit(host)
             if pending is not None:
                 yield self._finish(pending)

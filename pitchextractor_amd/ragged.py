@@ -1,9 +1,9 @@
-"""Host side of every ragged audio entry point: the F0 trackers, the stress conditions, WORLD synthesis, pitch shift,
-``RaggedResampler``, the noise, the stimuli and the room responses.  A ragged batch is rows packed back to back in a 1-D
-tensor or padded in a 2-D one; here it becomes lengths and offsets (``row_layout``), the int64 arrays and the zeroed
-plan a C row plan fills (``plan_arrays``, ``plan_meta``; every such plan opens with offset and length), and that plan
-with its device copy (``device_plan``; ``to_device`` for a plan that also has a ``params`` table).  Also what those
-callers share around it: the refusal of anything but a GPU device (``gpu_device``), but float32 device audio
+"""Host side of every ragged audio entry point: the F0 trackers, the stress conditions, WORLD synthesis and CheapTrick,
+pitch shift, ``RaggedResampler``, the noise, the stimuli and the room responses.  A ragged batch is rows packed back to
+back in a 1-D tensor or padded in a 2-D one; here it becomes lengths and offsets (``row_layout``), the int64 arrays and
+the zeroed plan a C row plan fills (``plan_arrays``, ``plan_meta``; every such plan opens with offset and length), and
+that plan with its device copy (``device_plan``; ``to_device`` for a plan that also has a ``params`` table).  Also what
+those callers share around it: the refusal of anything but a GPU device (``gpu_device``), but float32 device audio
 (``check_waves``) or but a contiguous device tensor of a dtype (``check_device_tensor``), one value per row from a
 number or a sequence (``per_row``), where a plan's rows end (``plan_extent``) and the output made or checked for them
 (``plan_output``), recordings or tracks as one packed batch (``PackedRecordings``, ``pack_tracks``), host pointers for

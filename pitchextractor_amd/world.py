@@ -10,6 +10,14 @@ noise_size[p]]`` of a caller-given array of standard normals, or drawn in the ke
 sample)`` (WORLD draws from a process-global xorshift stream), and the per-pulse arithmetic is float32.  pyworld is not
 available here: parity with its binary is unpinned, the yardstick is a float64 restatement of the published algorithm
 (``tests/world_ref.py``), see DESIGN.md.
+
+Also WORLD's CheapTrick (``pyworld.cheaptrick``), the spectral envelope of a recording (``cheaptrick``,
+``cheaptrick_ragged``, ``csrc/cheaptrick.hip``), and analysis / resynthesis on top of both (``resynthesize``,
+``resynthesize_ragged``): the envelope of a recording through ``Synthesis`` on a chosen F0 curve, returned with the
+curve it was synthesized from (``label_curve``), which is exact by construction.  Stated deviations of CheapTrick:
+float32 per-frame arithmetic, the two ``randn`` safeguards dropped or replaced by their scale, and the linear smoothing
+as a sum over the covered bins instead of a cumulative-sum difference.  Parity with pyworld's binary is unpinned here
+too; the yardstick is ``tests/cheaptrick_ref.py``.
 """
 from __future__ import annotations
 
@@ -23,7 +31,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .ragged import fft_roots, host_ptrs, i64, plan_meta
+from .ragged import (check_device_tensor, check_waves, fft_roots, host_ptrs, i64, pack_tracks, plan_meta,
+                     row_layout)
 
 FFT_SIZES = (512, 1024, 2048)
 WORKSPACE_BYTES = 256 << 20                                 # responses of one launch; more rows go to further launches
@@ -319,6 +328,167 @@ def world_synthesize(f0, sp: torch.Tensor, ap: torch.Tensor | None = None, fs=24
                             noise=None if noise is None else noise.reshape(-1),
                             noise_offsets=None if noise is None else [0], seeds=[seed])
     return out[0, :n]
+
+
+# --------------------------------------------------------------------------- CheapTrick: the envelope of a recording
+CHEAPTRICK_Q1 = -0.15
+CHEAPTRICK_F0_FLOOR = 71.0
+
+
+def cheaptrick_fft_size(fs, f0_floor: float = CHEAPTRICK_F0_FLOOR) -> int:
+    """WORLD's GetFFTSizeForCheapTrick: 2^(1 + floor(log2(3 fs / f0_floor + 1)))."""
+    return 2 ** (1 + int(math.log(3.0 * fs / f0_floor + 1.0) / math.log(2.0)))
+
+
+def cheaptrick_floor(fs, fft_size: int) -> float:
+    """The lowest F0 a transform of ``fft_size`` analyses as itself; frames at or below it are analysed at 500 Hz."""
+    return 3.0 * fs / (fft_size - 3.0)
+
+
+class Envelopes(NamedTuple):
+    """What ``cheaptrick_ragged`` returns: frame ``first[r] + q`` of row r is the ``bins`` floats of the flat float32
+    device tensor ``sp`` at ``offsets[r] + q * strides[r]``, for ``q < counts[r]``."""
+    sp: torch.Tensor
+    offsets: np.ndarray
+    strides: np.ndarray
+    first: np.ndarray
+    counts: np.ndarray
+    fft_size: int
+
+    def row(self, r: int) -> torch.Tensor:
+        bins = self.fft_size // 2 + 1
+        return self.sp.as_strided((int(self.counts[r]), bins), (int(self.strides[r]), 1), int(self.offsets[r]))
+
+    def frame0_offsets(self) -> np.ndarray:
+        """Where frame 0 of each row lies (or would lie), for ``world_synthesize_ragged``'s ``sp_offsets``."""
+        return self.offsets - self.first * self.strides
+
+
+def cheaptrick_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5.0, *, q1: float = CHEAPTRICK_Q1,
+                      f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None, frames=None,
+                      out: torch.Tensor | None = None, out_offsets=None, out_strides=None) -> Envelopes:
+    """WORLD's CheapTrick for a ragged batch, one launch.  ``x``: float32 device audio, rows packed back to back (1-D,
+    with ``lengths``) or padded (2-D; ``lengths`` defaults to the width).  ``f0s``: one F0 curve per row at
+    ``frame_period`` (ms) spacing, 0 = unvoiced (tensors or arrays; brought to the device as float32).  ``frames``: per
+    row ``(first_frame, n_frames)`` to analyse only those (default: every frame of the curve).  ``out``: a flat float32
+    device tensor to write into, at ``out_offsets[r] + q * out_strides[r]`` (default: the rows' frames back to back in a
+    new tensor).  There is no CPU path."""
+    check_waves(x, "CheapTrick")
+    lengths, offsets = row_layout(x, lengths, whole_by_default=True)
+    R = len(lengths)
+    fft_size = check_fft_size(cheaptrick_fft_size(fs, f0_floor) if fft_size is None else fft_size)
+    bins = fft_size // 2 + 1
+    f0s = list(f0s)
+    if len(f0s) != R:
+        raise ValueError("CheapTrick: one F0 curve per row")
+    f0_d, f0_off, f0_len = pack_tracks(f0s, x.device)
+    first = np.zeros(R, np.int64) if frames is None else _i64([fr[0] for fr in frames], R)
+    counts = _i64(f0_len, R) - first if frames is None else _i64([fr[1] for fr in frames], R)
+    strides = np.full(R, bins, np.int64) if out_strides is None else _i64(out_strides, R)
+    if out_offsets is None:
+        out_offsets = np.cumsum(counts * strides) - counts * strides
+    out_offsets = _i64(out_offsets, R)
+    meta = plan_meta("pe_cheaptrick_plan_fields", R)
+    totals = np.zeros(1, np.int64)
+    _lib.check(_lib.load().pe_cheaptrick_plan(
+        R, *host_ptrs(i64(offsets), i64(lengths), i64(f0_off), i64(f0_len), first, counts, out_offsets, strides),
+        float(fs), float(frame_period), float(f0_floor), fft_size, *host_ptrs(meta, totals)), "pe_cheaptrick_plan")
+    need = int((out_offsets + np.maximum(counts - 1, 0) * strides + bins)[counts > 0].max(initial=0))
+    if out is None:
+        out = torch.empty((max(need, 1),), dtype=torch.float32, device=x.device)
+    else:
+        check_device_tensor(out, "CheapTrick")
+        if out.numel() < need:
+            raise ValueError("CheapTrick: the output is smaller than the plan addresses")
+    if R and int(totals[0]):
+        meta_d = torch.from_numpy(meta).to(x.device)
+        with torch.cuda.device(x.device):
+            ops._call("pe_cheaptrick", x.data_ptr(), f0_d.data_ptr(), meta_d.data_ptr(), meta.ctypes.data,
+                      _SYNTH.table(fft_size, x.device).data_ptr(), R, float(fs), float(frame_period), float(q1),
+                      float(f0_floor), fft_size, out.data_ptr(), _lib.stream_ptr(),
+                      work=float(int(totals[0]) * (bins * 4 + 3 * fft_size * 4)))
+    return Envelopes(out, out_offsets, strides, first, counts, fft_size)
+
+
+def cheaptrick(x: torch.Tensor, f0, fs, frame_period: float = 5.0, *, q1: float = CHEAPTRICK_Q1,
+               f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None) -> torch.Tensor:
+    """pyworld's ``cheaptrick(x, f0, t, fs)`` on the device for ``t = arange(len(f0)) * frame_period`` ms: ``x`` a 1-D
+    float32 device wave, ``f0`` its curve (0 = unvoiced).  Returns the ``(len(f0), fft_size / 2 + 1)`` float32 power
+    envelope; ``fft_size`` defaults to WORLD's for ``f0_floor``."""
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise RuntimeError("CheapTrick (HIP) needs a 1-D float32 device wave; no CPU fallback exists")
+    env = cheaptrick_ragged(x, None, [f0], fs, frame_period, q1=q1, f0_floor=f0_floor, fft_size=fft_size)
+    return env.row(0)
+
+
+def label_curve(new_f0, fs, fft_size: int) -> np.ndarray:
+    """The curve a resynthesized item is labelled with: ``new_f0`` (float64) with every frame the synthesizer does not
+    voice (``new_f0 <= lowest_f0(fs, fft_size)``) set to 0.  The synthesizer is driven with this curve."""
+    f0 = _host_f0(new_f0).copy()
+    f0[~(f0 > lowest_f0(fs, fft_size))] = 0.0
+    return f0
+
+
+def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period: float, *, ap=None, seeds=None,
+                        noise=None, noise_offsets=None, gains=None, out: torch.Tensor | None = None, out_rows=None,
+                        out_start=None, out_len=None, out_noise=None, tables=None, q1: float = CHEAPTRICK_Q1,
+                        f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None):
+    """Analysis / resynthesis of a ragged batch: the envelope of row r of ``x`` under ``f0s[r]``
+    (``cheaptrick_ragged``), then ``world_synthesize_ragged`` driven by ``label_curve(new_f0s[r])`` reading that
+    envelope in place.  ``ap``: ``None`` or one ``(bins,)`` float32 device template for every row and frame.  With
+    windows (``out_start`` / ``out_len``) only the frames their pulses read are analysed: the samples of the window -+
+    ``fft_size / 2``, and one frame either side for the synthesizer's frame interpolation.  The other arguments are
+    ``world_synthesize_ragged``'s. Returns ``(out, labels)``, ``labels[r]`` the float64 label curve of row r."""
+    check_waves(x, "WORLD resynthesis")
+    R = len(row_layout(x, lengths, whole_by_default=True)[0])
+    fft_size = check_fft_size(cheaptrick_fft_size(fs, f0_floor) if fft_size is None else fft_size)
+    bins = fft_size // 2 + 1
+    labels = [label_curve(f, fs, fft_size) for f in new_f0s]
+    f0s = list(f0s)
+    if len(f0s) != R or len(labels) != R or any(len(a) != b.size for a, b in zip(f0s, labels)):
+        raise ValueError("WORLD resynthesis: one F0 curve and one new curve of the same length per row")
+    if ap is not None and tuple(ap.shape) != (bins,):
+        raise ValueError(f"WORLD resynthesis: ap must be one ({bins},) template")
+    n_frames = np.array([b.size for b in labels], np.int64)
+    y_len = np.array([output_length(n, fs, frame_period) for n in n_frames], np.int64)
+    out_start = np.zeros(R, np.int64) if out_start is None else _i64(out_start, R)
+    out_len = y_len - out_start if out_len is None else _i64(out_len, R)
+    if out is None:
+        out = torch.zeros((max(R, 1), max(int(out_len.max(initial=0)), 1)), dtype=torch.float32, device=x.device)
+    # frames the planned pulses read: pulse samples in [start - N/2, start + len - 2 + N/2], frames floor / ceil of each
+    per_frame = frame_period * fs / 1000.0
+    lo = np.clip(np.floor((out_start - fft_size // 2) / per_frame).astype(np.int64) - 1, 0, n_frames)
+    hi = np.clip(np.ceil((out_start + out_len + fft_size // 2) / per_frame).astype(np.int64) + 2, 0, n_frames)
+    hi = np.where(out_len > 0, hi, lo)
+    base = np.cumsum(n_frames * bins) - n_frames * bins          # each row's frame 0, whole rows laid out
+    sp = torch.empty((max(int((n_frames * bins).sum()), 1),), dtype=torch.float32, device=x.device)
+    env = cheaptrick_ragged(x, lengths, f0s, fs, frame_period, q1=q1, f0_floor=f0_floor, fft_size=fft_size,
+                            frames=list(zip(lo, hi - lo)), out=sp, out_offsets=base + lo * bins)
+    world_synthesize_ragged(labels, env.sp, env.frame0_offsets(), env.strides,
+                            torch.ones(R) if gains is None else gains, out, out_rows, out_start, out_len, fs=fs,
+                            frame_period=frame_period, fft_size=fft_size, ap=ap,
+                            ap_offsets=None if ap is None else [0] * R, ap_strides=None if ap is None else [0] * R,
+                            tables=tables, noise=noise, noise_offsets=noise_offsets, seeds=seeds, out_noise=out_noise)
+    return out, labels
+
+
+def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, ap: torch.Tensor | None = None,
+                 seed: int = 0, noise: torch.Tensor | None = None, q1: float = CHEAPTRICK_Q1,
+                 f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None):
+    """The recording ``x`` (1-D float32 device wave with the curve ``f0``) resynthesized on ``new_f0``: its CheapTrick
+    envelope through WORLD's ``Synthesis``.  Returns ``(audio, label)``: the 1-D float32 device wave of
+    ``int(len(f0) * frame_period * fs / 1000)`` samples and the float64 host curve it was synthesized from
+    (``label_curve``), exact by construction."""
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise RuntimeError("WORLD resynthesis (HIP) needs a 1-D float32 device wave; no CPU fallback exists")
+    n = output_length(len(_host_f0(new_f0)), fs, frame_period)
+    if noise is not None and noise.numel() != n:
+        raise ValueError("resynthesize: noise must hold one value per output sample")
+    out, labels = resynthesize_ragged(x, None, [f0], [new_f0], fs, frame_period, ap=ap, seeds=[seed],
+                                      noise=None if noise is None else noise.reshape(-1),
+                                      noise_offsets=None if noise is None else [0], q1=q1, f0_floor=f0_floor,
+                                      fft_size=fft_size)
+    return out[0, :n], labels[0]
 
 
 # --------------------------------------------------------------------------- the reference's vowel generator

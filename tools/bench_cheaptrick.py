@@ -1,0 +1,199 @@
+"""Device cost of WORLD CheapTrick and of the analysis / resynthesis rows (synthetic_data.world_resynthesis) per batch.
+
+64 rows of 4 s at 24 kHz, 12.5 ms frames (hop 300), N = 1024 -- the share a ``ratio: 0.25`` batch of 256 carries --
+harmonic voices on gliding F0 curves from fixed seeds.  Reports (1) the envelope launch alone, from a run of its own
+under ``rocprofv3 --kernel-trace --stats`` (no counters) started here as a child process; (2) ``resynthesize_ragged``
+of the whole rows with its host work (label curves, time bases, plans; wall clock around a synchronize); (3) the loader
+stage (``DeviceMelLoader._resynthesis``) for a B = 256 batch with 64 resynthesis rows, each cropped to the 192-frame
+window; each next to the fp32 training step of the flagship batch in the same session (bench.py as a child process).
+Writes profiles/bench_cheaptrick.json and profiles/bench_cheaptrick_kernel_stats.csv and prints the JSON line.  Needs a
+GPU.
+
+    python tools/bench_cheaptrick.py               # time, trace, training step
+    python tools/bench_cheaptrick.py --trace-run   # what the traced child runs
+
+Not a gate.  The kernel does three 1024-point complex transforms in LDS per frame plus 513 x (log, exp, sinpi, cospi)
+and the interval sums: its bytes are reported against the 6.29 TB/s copy rate and its transforms per second against
+what ``world_responses_kernel`` reaches (profiles/bench_world_synth.json: four transforms per pulse).
+"""
+import argparse
+import csv
+import json
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from pitchextractor_amd import meldataset as md  # noqa: E402
+from pitchextractor_amd import world  # noqa: E402
+
+SR, HOP, N, ROWS, SECONDS, BATCH = 24000, 300, 1024, 64, 4.0, 256
+FP = 1000.0 * HOP / SR
+HBM_COPY_TBS = 6.29                       # measured copy rate of the MI355X microarchitecture guide
+KERNEL = "cheaptrick_kernel"
+
+
+def make_rows():
+    """(waves, base curves, new curves): float32 host arrays, one per row."""
+    rng = np.random.default_rng(0)
+    n = int(SECONDS * SR)
+    L = 1 + n // HOP
+    t = np.arange(n) / SR
+    waves, f0s, new = [], [], []
+    for r in range(ROWS):
+        a, b = rng.uniform(110.0, 320.0, 2)
+        curve = np.linspace(a, b, L)
+        phase = 2 * np.pi * np.cumsum(np.interp(t, np.arange(L) * HOP / SR, curve)) / SR
+        x = sum(np.sin(h * phase) / h for h in range(1, 9))
+        waves.append((0.3 * x / np.abs(x).max() + 1e-3 * rng.standard_normal(n)).astype(np.float32))
+        f0s.append(curve.astype(np.float32))
+        new.append(curve * 2.0 ** (rng.choice([-4, -2, -1, 1, 2, 4]) / 12.0))
+    return waves, f0s, new
+
+
+def trace_run(dev):
+    waves, f0s, _ = make_rows()
+    x = torch.from_numpy(np.concatenate(waves)).to(dev)
+    for _ in range(10):
+        world.cheaptrick_ragged(x, [len(w) for w in waves], f0s, SR, FP, fft_size=N)
+    torch.cuda.synchronize()
+
+
+def kernel_row(out_csv: Path):
+    prof = shutil.which("rocprofv3")
+    if prof is None:
+        raise SystemExit("bench_cheaptrick: rocprofv3 not found; kernel times are not optional")
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "cheaptrick", "--",
+               sys.executable, str(Path(__file__).resolve()), "--trace-run"]
+        subprocess.run(cmd, check=True, timeout=600, stdout=subprocess.DEVNULL)
+        stats = sorted(Path(tmp).rglob("*kernel_stats.csv"))
+        trace = sorted(Path(tmp).rglob("*kernel_trace.csv"))
+        if not stats or not trace:
+            raise SystemExit("bench_cheaptrick: the profiler wrote no kernel_stats.csv / kernel_trace.csv")
+        rows = list(csv.DictReader(open(stats[0])))
+        events = list(csv.DictReader(open(trace[0])))
+    keep = [r for r in rows if KERNEL in r.get("Name", "")]
+    if not keep:
+        raise SystemExit("bench_cheaptrick: the CheapTrick kernel does not appear in the trace")
+    with open(out_csv, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=list(keep[0].keys()))
+        w.writeheader()
+        w.writerows(keep)
+    d = [int(e["End_Timestamp"]) - int(e["Start_Timestamp"]) for e in events if KERNEL in e.get("Kernel_Name", "")]
+    d = d[2:] if len(d) > 4 else d                                      # the first calls carry the code load
+    return {"calls": len(d), "avg_us": sum(d) / len(d) / 1e3, "min_us": min(d) / 1e3, "max_us": max(d) / 1e3}
+
+
+def wall_ms(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), float(np.min(ts))
+
+
+def loader_stage(dev, waves, f0s, new, reps):
+    """The stage as the loader runs it: a collated B = 256 batch whose 64 resynthesis rows are cropped windows."""
+    class _Dataset:
+        synthetic_resynthesis_config = {"fft_size": N, "frame_period": FP, "aperiodicity": 0.0,
+                                        "q1": world.CHEAPTRICK_Q1}
+
+    class _Host:
+        dataset = _Dataset()
+
+    loader = md.DeviceMelLoader(_Host(), md.MelSpectrogram(**md.DEFAULT_MEL_PARAMS), dev)
+    rng = np.random.default_rng(1)
+    items = []
+    for r in range(ROWS):
+        n = len(waves[r])
+        curve = world.label_curve(new[r], SR, N)
+        crop = int(rng.integers(0, 1 + n // HOP - 192))
+        start, count, first = md.synthetic_window(n, crop, HOP, 1024)
+        table = world.time_base(curve, SR, FP, N)
+        req = md.ResynthesisRequest("", 1.0, n, crop, start, count, first, f0s[r].astype(np.float64), curve,
+                                    table.index, table.shift, table.vuv, world.noise_seed(curve), None)
+        label = torch.from_numpy(curve[crop:crop + 192].astype(np.float32))
+        items.append((torch.from_numpy(waves[r]), label, (label == 0).float(), first, SR, req))
+    plain = (torch.zeros(192 * HOP), torch.zeros(192), torch.zeros(192), 0, SR)
+    batch = [items[i // 4] if i % 4 == 0 else plain for i in range(BATCH)]
+    host = md.Collater()(batch)
+    pack_host = host[-1]
+    dev_items = md.H2DPrefetcher(dev).submit(host)[0]
+    torch.cuda.synchronize()
+    waves_d, lengths_d, pack = dev_items[0], dev_items[1], dev_items[-1]
+    return wall_ms(lambda: loader._resynthesis(waves_d, lengths_d, pack, pack_host), reps)
+
+
+def training_step_ms():
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--no-cpu-baseline",
+           "--no-native-ref"]
+    res = subprocess.run(cmd, check=True, timeout=900, capture_output=True, text=True, cwd=str(ROOT))
+    line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
+    return float(json.loads(line)["ms_per_step"])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--trace-run", action="store_true")
+    ap.add_argument("--no-train-step", action="store_true")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "bench_cheaptrick.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_cheaptrick: no GPU visible; this benchmark does not run without one")
+    dev = torch.device("cuda:0")
+    if a.trace_run:
+        trace_run(dev)
+        return
+    waves, f0s, new = make_rows()
+    lengths = [len(w) for w in waves]
+    x = torch.from_numpy(np.concatenate(waves)).to(dev)
+    frames = sum(len(f) for f in f0s)
+    bins = N // 2 + 1
+    env_ms = wall_ms(lambda: world.cheaptrick_ragged(x, lengths, f0s, SR, FP, fft_size=N), a.reps)
+    resyn_ms = wall_ms(lambda: world.resynthesize_ragged(x, lengths, f0s, new, SR, FP, fft_size=N,
+                                                         seeds=list(range(ROWS))), a.reps)
+    stage_ms = loader_stage(dev, waves, f0s, new, a.reps)
+    out = Path(a.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    kern = kernel_row(out.with_name(out.stem + "_kernel_stats.csv"))
+    window = float(np.mean([2 * round(1.5 * SR / f) + 1 for c in f0s for f in c]))
+    moved = frames * (bins * 4 + window * 4)                      # envelope written, the window's samples read
+    kern.update(bytes=float(moved), share_of_copy_rate=moved / (kern["avg_us"] * 1e-6) / 1e12 / HBM_COPY_TBS,
+                transforms_per_s=3 * frames / (kern["avg_us"] * 1e-6),
+                bound="LDS passes and barriers of three transforms per frame, then transcendentals; not memory")
+    sib = json.loads((ROOT / "profiles" / "bench_world_synth.json").read_text())
+    sib_rate = 4 * sib["pulses"] / (sib["kernels"]["world_responses_kernel"]["avg_us"] * 1e-6)
+    kern.update(world_responses_transforms_per_s=sib_rate,
+                share_of_world_responses_rate=kern["transforms_per_s"] / sib_rate)
+    res = {"rows": ROWS, "seconds_per_row": SECONDS, "fft_size": N, "frame_period_ms": FP, "frames": frames,
+           "envelope_bytes": frames * bins * 4, "kernel": kern,
+           "cheaptrick_ragged_ms_median": env_ms[0], "cheaptrick_ragged_ms_min": env_ms[1],
+           "resynthesize_ragged_ms_median": resyn_ms[0], "resynthesize_ragged_ms_min": resyn_ms[1],
+           "loader_stage_ms_median": stage_ms[0], "loader_stage_ms_min": stage_ms[1], "loader_batch": BATCH,
+           "loader_resynthesis_rows": ROWS}
+    if not a.no_train_step:
+        step = training_step_ms()
+        res["training_step_ms_fp32_batch256"] = step
+        res["kernel_to_training_step_ratio"] = kern["avg_us"] / 1e3 / step
+        res["resynthesize_to_training_step_ratio"] = resyn_ms[0] / step
+        res["stage_to_training_step_ratio"] = stage_ms[0] / step
+    out.write_text(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
