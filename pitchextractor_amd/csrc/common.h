@@ -40,6 +40,23 @@ static inline int pe_epilogue_buffer(long out_bytes) {
   return !forced_pointer && out_bytes < (1L << 31);
 }
 
+// Tile override of pe_gemm_tn / pe_lstm_whh_grad for the shapes they plan on 128 x 128 tiles: PE_TN_TILE in the
+// environment (read once) = 128 keeps them on that tiling, 192 / 128x192 / 192x128 puts every such shape on that
+// tile where the product form has it (tests and A/B runs); unset, each entry point picks per shape.  The results
+// have the same bits either way (splitk.h, launch_tn).  Returns BM * 1000 + BN, 0 without an override.
+static inline int pe_tn_tile_override() {
+  static const int tile = [] {
+    const char* e = getenv("PE_TN_TILE");
+    if (!e) return 0;
+    if (strcmp(e, "128") == 0) return 128128;
+    if (strcmp(e, "192") == 0 || strcmp(e, "192x192") == 0) return 192192;
+    if (strcmp(e, "128x192") == 0) return 128192;
+    if (strcmp(e, "192x128") == 0) return 192128;
+    return 0;
+  }();
+  return tile;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -258,15 +258,29 @@ static int gemm_tn_impl(const TA* A, long lda, const TA* B, long ldb, float* C, 
   hipStream_t st = pe_stream(stream);
   auto launch = [&](auto bm, auto bn) {
     constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
-    return launch_tn<BM, BN, F>(KRowLoader<BM, TA>{A, lda, M, 0}, KRowLoader<BN, TA>{B, ldb, N, 0}, C, ldc, M, N, K,
-                                accumulate, workspace, workspace_bytes, st, amax_a, amax_b);
+    // (the plan is that of pe_gemm_tn_workspace_bytes: a 192-wide tile runs the k-splits of the 128-wide tiling)
+    return launch_tn<BM, BN, F, (BM < 128 ? BM : 128), (BN < 128 ? BN : 128)>(
+        KRowLoader<BM, TA>{A, lda, M, 0}, KRowLoader<BN, TA>{B, ldb, N, 0}, C, ldc, M, N, K, accumulate, workspace,
+        workspace_bytes, st, amax_a, amax_b);
   };
   std::integral_constant<int, 64> t64;
   std::integral_constant<int, 128> t128;
+  std::integral_constant<int, 192> t192;
   if (M <= 64 && N <= 64) return launch(t64, t64);
   if (M <= 64) return launch(t64, t128);
   if (N <= 64) return launch(t128, t64);
-  return launch(t128, t128);
+  // Shapes planned on 128 x 128: the first 192-wide tile that pads M x N no further, in the order measured on the
+  // step's shapes (profiles/ab_tn_tile.txt: 1536 x 768 on 192 x 192, 1536 x 512 and 192 x 128 on 192 x 128, 256 x 192
+  // on 128 x 192 are 4-21 % faster in h2; 256 x 640, which every wide tile pads further, is 15-35 % slower on them)
+  const int tile = tn_tile_for(M, N, {192192, 192128, 128192});
+  int rc = kTnNarrowTile;                                          // (what a wide tile answers that cannot serve the launch)
+  if constexpr (tn_tile_fits<MODE, 192, 192>())
+    if (tile == 192192) rc = launch(t192, t192);
+  if constexpr (tn_tile_fits<MODE, 192, 128>())
+    if (tile == 192128) rc = launch(t192, t128);
+  if constexpr (tn_tile_fits<MODE, 128, 192>())
+    if (tile == 128192) rc = launch(t128, t192);
+  return rc != kTnNarrowTile ? rc : launch(t128, t128);
 }
 
 extern "C" int pe_gemm_tn(int products, int act16, const void* A, long lda, const void* B, long ldb, float* C, long ldc,

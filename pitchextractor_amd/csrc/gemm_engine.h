@@ -577,14 +577,23 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TL::TM][TL::TN]) {
 // ------------------------------------------------------------------ operand loaders (TN)
 // A TN loader hands out float4 = 4 consecutive columns of one k-row of a [32][COLS] k-tile.
 // COLS/4 threads cover a row, 1024/COLS rows per pass, COLS/32 passes ("slots") per k-tile.
+// 192 columns (48 quads per k-row do not divide 256 threads) go as three 64-column chunks side by side, each with the
+// 64-wide geometry: 16 threads per k-row, 16 k-rows per pass, slot s = chunk s % 3 of row pass s / 3 (6 slots).  A
+// 16-lane group then reads 256 contiguous bytes of one fp32 k-row and writes 128 contiguous bytes of one LDS row,
+// which is the unit ds_write_b64 is served in.
 template <int COLS>
 struct TnGeom {
-  static constexpr int TPR = COLS / 4;           // threads per k-row
+  static constexpr int CHUNKS = COLS == 192 ? 3 : 1;
+  static constexpr int CW = COLS / CHUNKS;       // columns per chunk
+  static constexpr int TPR = CW / 4;             // threads per k-row (of a chunk)
   static constexpr int ROWS = 256 / TPR;         // k-rows per pass
-  static constexpr int SLOTS = kBK / ROWS;
-  static_assert(COLS == 64 || COLS == 128 || COLS == 256, "TN tile widths");
-  __device__ static __forceinline__ int col4() { return (threadIdx.x % TPR) * 4; }
-  __device__ static __forceinline__ int krow(int slot) { return threadIdx.x / TPR + ROWS * slot; }
+  static constexpr int SLOTS = CHUNKS * kBK / ROWS;
+  static_assert(COLS == 64 || COLS == 128 || COLS == 192 || COLS == 256, "TN tile widths");
+  __device__ static __forceinline__ int col4() { return (threadIdx.x % TPR) * 4; }               // within the chunk
+  static constexpr int chunk_col(int slot) { return (slot % CHUNKS) * CW; }
+  __device__ static __forceinline__ int krow(int slot) { return threadIdx.x / TPR + ROWS * (slot / CHUNKS); }
+  // where slot `slot` of a thread goes in an LDS image of `stride` elements per k-row, from its slot-0 position
+  static constexpr int lds_off(int slot, int stride) { return (slot / CHUNKS) * ROWS * stride + chunk_col(slot); }
 };
 
 template <int COLS, class TA = float>
@@ -593,11 +602,15 @@ struct KRowLoader {           // plain [K][cols] matrix; buffer loads based at t
   long ld;
   int cols;
   int col0;
-  unsigned vo_ = 0, rowstep_ = 0;
+  unsigned vo_[TnGeom<COLS>::CHUNKS] = {}, rowstep_ = 0;
   typedef typename RawQuad<TA>::type Raw;
   __device__ __forceinline__ void init(int first_col, int /*k_begin*/) {
     col0 = first_col + TnGeom<COLS>::col4();
-    vo_ = (unsigned)(((long)(threadIdx.x / TnGeom<COLS>::TPR) * ld + col0) * (long)sizeof(TA)) | (col0 < cols ? 0u : 0x80000000u);
+#pragma unroll
+    for (int c = 0; c < TnGeom<COLS>::CHUNKS; ++c) {
+      const int col = col0 + TnGeom<COLS>::chunk_col(c);
+      vo_[c] = (unsigned)(((long)(threadIdx.x / TnGeom<COLS>::TPR) * ld + col) * (long)sizeof(TA)) | (col < cols ? 0u : 0x80000000u);
+    }
     rowstep_ = (unsigned)(TnGeom<COLS>::ROWS * ld * (long)sizeof(TA));
   }
   __device__ __forceinline__ Raw load(int slot, int k0, int k_end) const {
@@ -605,7 +618,7 @@ struct KRowLoader {           // plain [K][cols] matrix; buffer loads based at t
     long bytes = left > 0 ? ((left - 1) * ld + cols) * (long)sizeof(TA) : 0;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<TA*>(p + (long)k0 * ld), 0, (unsigned)(bytes < 0x7fffffffL ? bytes : 0x7fffffffL), 0x00020000);
-    return ldraw_buffer<TA>(rs, vo_ + (unsigned)slot * rowstep_, 0u);
+    return ldraw_buffer<TA>(rs, vo_[slot % TnGeom<COLS>::CHUNKS] + (unsigned)(slot / TnGeom<COLS>::CHUNKS) * rowstep_, 0u);
   }
 };
 
@@ -646,21 +659,27 @@ struct ShiftedTimeLoader {    // [B][T][ld] sequence read at time t + dt (zero o
   long ld;
   int T, dt, cols;
   int col0;
-  int t_[TnGeom<COLS>::SLOTS];
+  int t_[TnGeom<COLS>::SLOTS / TnGeom<COLS>::CHUNKS];                 // one per row pass: the chunks of a pass share it
   __device__ __forceinline__ void init(int first_col, int k_begin) {
     col0 = first_col + TnGeom<COLS>::col4();
 #pragma unroll
-    for (int i = 0; i < TnGeom<COLS>::SLOTS; ++i) t_[i] = (k_begin + TnGeom<COLS>::krow(i)) % T;
+    for (int i = 0; i < TnGeom<COLS>::SLOTS / TnGeom<COLS>::CHUNKS; ++i)
+      t_[i] = (k_begin + TnGeom<COLS>::krow(i * TnGeom<COLS>::CHUNKS)) % T;
   }
+  // must be called once per slot per k-tile, slots and k-tiles in increasing order starting at k_begin
   __device__ __forceinline__ float4 load(int slot, int k0, int k_end) {
+    constexpr int CH = TnGeom<COLS>::CHUNKS;
     const int k = k0 + TnGeom<COLS>::krow(slot);
-    const int t = t_[slot] + dt;
+    const int col = col0 + TnGeom<COLS>::chunk_col(slot);
+    const int t = t_[slot / CH] + dt;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < k_end && col0 < cols && t >= 0 && t < T)
-      v = *reinterpret_cast<const float4*>(p + ((long)k + dt) * ld + col0);
-    int tn = t_[slot] + kBK;
-    while (tn >= T) tn -= T;
-    t_[slot] = tn;
+    if (k < k_end && col < cols && t >= 0 && t < T)
+      v = *reinterpret_cast<const float4*>(p + ((long)k + dt) * ld + col);
+    if (slot % CH == CH - 1) {                                        // the pass's last chunk moves its clock on
+      int tn = t_[slot / CH] + kBK;
+      while (tn >= T) tn -= T;
+      t_[slot / CH] = tn;
+    }
     return v;
   }
 };
@@ -688,9 +707,9 @@ __device__ __forceinline__ void tn_mainloop(AL& al, BL& bl, int k_begin, int k_e
   for (int k0 = k_begin; k0 < k_end; k0 += kBK) {
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < SA; ++i) *reinterpret_cast<float4*>(As + sta + i * TnGeom<BM>::ROWS * BM) = ra[i];
+    for (int i = 0; i < SA; ++i) *reinterpret_cast<float4*>(As + sta + TnGeom<BM>::lds_off(i, BM)) = ra[i];
 #pragma unroll
-    for (int i = 0; i < SB; ++i) *reinterpret_cast<float4*>(Bs + stb + i * TnGeom<BN>::ROWS * BN) = rb[i];
+    for (int i = 0; i < SB; ++i) *reinterpret_cast<float4*>(Bs + stb + TnGeom<BN>::lds_off(i, BN)) = rb[i];
     __syncthreads();
     if (k0 + kBK < k_end) {
 #pragma unroll
@@ -718,7 +737,10 @@ __device__ __forceinline__ void tn_mainloop(AL& al, BL& bl, int k_begin, int k_e
 // [k][cols (+32 pad)] bf16 and the MFMA fragments (8 consecutive k of one column) come from the gfx950
 // transposed read ds_read_b64_tr_b16: per 16-lane group, lane 4q+p supplies the address of row q,
 // columns 4p..4p+3 of a 4 x 16 block and lane i receives column i of the 4 rows.  With a row stride of
-// cols/2 + 16 dwords the four rows of a half-wave's two blocks fall on disjoint banks.
+// cols/2 + 16 dwords the four rows of a half-wave's two blocks fall on disjoint banks: the read is served 32 lanes at
+// a time over 64 banks, a half-wave reads 16 dwords of each of 4 consecutive k-rows, and cols/2 + 16 is 48 (64 and 192
+// columns: rows at banks 0, 48, 32, 16) or 16 (128 columns: 0, 16, 32, 48) modulo 64.  192 columns therefore keep the
+// same pad, 224 elements = 112 dwords per k-row.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <int COLS> constexpr int tn_split_stride() { return COLS + 32; }                 // bf16 elements per k-row
 template <int COLS, int NT = 3> constexpr int tn_split_floats() { return NT * kBK * tn_split_stride<COLS>() / 2; }
@@ -763,7 +785,9 @@ __device__ __forceinline__ void tn_split_store(H* img, int off, const uint2& raw
   else tn_split_store<COLS, NT>(img, off, widen(raw), scale);
 }
 
-template <int BM, int BN, int NT, int PF = 1, class TH = __bf16, class AL, class BL>
+// SW: the two operands swap roles in the MFMAs (same products, same order: mfma_terms<NT, true>), so a 32 x 32
+// accumulator block comes out transposed -- a lane owns four column quads of ONE output row (tn_for_each_quad)
+template <int BM, int BN, int NT, int PF = 1, class TH = __bf16, bool SW = false, class AL, class BL>
 __device__ __forceinline__ void tn_mainloop_split(AL& al, BL& bl, int k_begin, int k_end, float* As_f, float* Bs_f,
                                                   f32x16 (&acc)[BM / 64][BN / 64], float sa = 1.0f, float sb = 1.0f) {
   constexpr int TM = BM / 64, TN = BN / 64;
@@ -794,9 +818,9 @@ __device__ __forceinline__ void tn_mainloop_split(AL& al, BL& bl, int k_begin, i
     constexpr int u = decltype(uc)::value;
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < SA; ++i) tn_split_store<BM, NT>(As, sta + i * TnGeom<BM>::ROWS * STA, ra[u][i], sa);
+    for (int i = 0; i < SA; ++i) tn_split_store<BM, NT>(As, sta + TnGeom<BM>::lds_off(i, STA), ra[u][i], sa);
 #pragma unroll
-    for (int i = 0; i < SB; ++i) tn_split_store<BN, NT>(Bs, stb + i * TnGeom<BN>::ROWS * STB, rb[u][i], sb);
+    for (int i = 0; i < SB; ++i) tn_split_store<BN, NT>(Bs, stb + TnGeom<BN>::lds_off(i, STB), rb[u][i], sb);
     __syncthreads();
     if (PF == 2 || k0 + kBK < k_end) {
 #pragma unroll
@@ -819,7 +843,10 @@ __device__ __forceinline__ void tn_mainloop_split(AL& al, BL& bl, int k_begin, i
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_terms<NT>(fa[i], fb[j], acc[i][j]);
+        for (int j = 0; j < TN; ++j) {
+          if constexpr (SW) acc[i][j] = mfma_terms<NT, true>(fb[j], fa[i], acc[i][j]);
+          else acc[i][j] = mfma_terms<NT>(fa[i], fb[j], acc[i][j]);
+        }
     }
     if constexpr (PF == 2) __builtin_amdgcn_sched_barrier(0);
   };
@@ -838,12 +865,14 @@ template <int MODE, int COLS> constexpr int tn_lds_floats() {
        : MODE == kBf16 ? tn_split_floats<COLS, 1>() : kBK * COLS;
 }
 
-template <int MODE, int BM, int BN, int PF = 1, class TH = __bf16, class AL, class BL>
+// SW (16-bit-term modes only; the native loop has no swapped form): see tn_mainloop_split
+template <int MODE, int BM, int BN, int PF = 1, class TH = __bf16, bool SW = false, class AL, class BL>
 __device__ __forceinline__ void tn_mainloop_mode(AL& al, BL& bl, int k_begin, int k_end, float* As, float* Bs,
                                                  f32x16 (&acc)[BM / 64][BN / 64], float sa = 1.0f, float sb = 1.0f) {
-  if constexpr (MODE == kSplit) tn_mainloop_split<BM, BN, 3, PF>(al, bl, k_begin, k_end, As, Bs, acc);
-  else if constexpr (MODE == kSplit2) tn_mainloop_split<BM, BN, 2, PF>(al, bl, k_begin, k_end, As, Bs, acc, sa, sb);
-  else if constexpr (MODE == kBf16) tn_mainloop_split<BM, BN, 1, PF, TH>(al, bl, k_begin, k_end, As, Bs, acc);
+  static_assert(!SW || MODE != kNative, "the native fp32 TN loop is not swapped");
+  if constexpr (MODE == kSplit) tn_mainloop_split<BM, BN, 3, PF, __bf16, SW>(al, bl, k_begin, k_end, As, Bs, acc);
+  else if constexpr (MODE == kSplit2) tn_mainloop_split<BM, BN, 2, PF, __bf16, SW>(al, bl, k_begin, k_end, As, Bs, acc, sa, sb);
+  else if constexpr (MODE == kBf16) tn_mainloop_split<BM, BN, 1, PF, TH, SW>(al, bl, k_begin, k_end, As, Bs, acc);
   else tn_mainloop<BM, BN>(al, bl, k_begin, k_end, As, Bs, acc);
 }
 
@@ -909,6 +938,23 @@ __device__ __forceinline__ void tn_for_each_acc(const f32x16 (&acc)[BM / 64][BN 
 #pragma unroll
       for (int g = 0; g < 16; ++g)
         fn(wm * (BM / 2) + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * h, wn * (BN / 2) + j * 32 + r, acc[i][j][g]);
+}
+
+// The same for the accumulators of a swapped main loop (SW), whose blocks are transposed: fn(row_in_tile, col_in_tile,
+// quad) with the quad = columns col .. col + 3 of that one row.
+template <int BM, int BN, class FN>
+__device__ __forceinline__ void tn_for_each_quad(const f32x16 (&acc)[BM / 64][BN / 64], FN&& fn) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wm = wv >> 1, wn = wv & 1;
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int i = 0; i < BM / 64; ++i)
+#pragma unroll
+    for (int j = 0; j < BN / 64; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        fn(wm * (BM / 2) + i * 32 + r, wn * (BN / 2) + j * 32 + 8 * q + 4 * h,
+           make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]));
 }
 
 }  // namespace pe

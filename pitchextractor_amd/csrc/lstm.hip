@@ -283,7 +283,7 @@ extern "C" int pe_lstm_bwd(int ncells, const float* const* whh_t, float* const* 
 }
 
 // dW_hh[4H][H] = sum_{b,t} dgates[b][t][:]^T . y[b][t -/+ 1][:]   (y = this direction's output slice): the TN split-K
-// product (splitk.h) with y behind a time-shifted loader, on the 128 x 128 tile at every H.
+// product (splitk.h) with y behind a time-shifted loader, planned on the 128 x 128 tile at every H.
 extern "C" size_t pe_lstm_whh_grad_workspace_bytes(int B, int T, int H) {
   // (a whole slab also where every form plans one split and stores to dW_hh directly)
   return (size_t)tn_max_splits(pe_cdiv(4 * H, 128) * pe_cdiv(H, 128), B * T) * 4 * H * H * sizeof(float);
@@ -297,11 +297,25 @@ static int whh_grad_impl(const float* dgates, const float* y, long ldy, float* d
   if (F::MODE == kSplit2 && (!amax_dg || !amax_y)) return PE_E_ARG;
   if ((H & 3) || (ldy & 3)) return PE_E_UNSUPPORTED;
   const int M = 4 * H, N = H;
-  KRowLoader<128> al{dgates, (long)M, M, 0};
-  ShiftedTimeLoader<128> bl;
-  bl.p = y; bl.ld = ldy; bl.T = T; bl.dt = reverse ? 1 : -1; bl.cols = N; bl.col0 = 0;
-  return launch_tn<128, 128, F>(al, bl, dwhh, (long)N, M, N, B * T, 0, workspace, workspace_bytes, pe_stream(stream),
-                                amax_dg, amax_y);
+  auto launch = [&](auto bm, auto bn) {                    // (always the plan of the 128 x 128 tiling)
+    constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+    KRowLoader<BM> al{dgates, (long)M, M, 0};
+    ShiftedTimeLoader<BN> bl;
+    bl.p = y; bl.ld = ldy; bl.T = T; bl.dt = reverse ? 1 : -1; bl.cols = N; bl.col0 = 0;
+    return launch_tn<BM, BN, F, 128, 128>(al, bl, dwhh, (long)N, M, N, B * T, 0, workspace, workspace_bytes,
+                                          pe_stream(stream), amax_dg, amax_y);
+  };
+  std::integral_constant<int, 128> t128;
+  std::integral_constant<int, 192> t192;
+  // 192 x 192 where it pads 4H x H no further (H = 384: 1 120 workgroups for 2 520, h2 0.299 ms for 0.313, bf16 0.169
+  // for 0.197; profiles/ab_tn_tile.txt)
+  const int tile = tn_tile_for(M, N, {192192});
+  int rc = kTnNarrowTile;
+  if constexpr (tn_tile_fits<F::MODE, 192, 192>())
+    if (tile == 192192) rc = launch(t192, t192);
+  if constexpr (tn_tile_fits<F::MODE, 128, 192>())
+    if (tile == 128192) rc = launch(t128, t192);
+  return rc != kTnNarrowTile ? rc : launch(t128, t128);
 }
 
 extern "C" int pe_lstm_whh_grad(int products, const float* dgates, const float* y, long ldy, float* dwhh, int B, int T,
