@@ -13,20 +13,14 @@ to HBM once and ONE launch of the fused mel kernel does framing + FFT + mel + lo
 alignment (f0_backends.py:788-806), crop offsets -- is reproduced exactly and runs on the host.
 
 Out of scope here: the pyworld harvest / CREPE / SwiftF0 tracker backends (packages or weights that
-are not available; pyworld's ``algorithm: dio`` is native, ``f0_tracker.WorldDioTracker``).  The WORLD-vocoder augmentation (``synthetic_data.world_vocoder``, Utils/synthetic.py) runs on the
-GPU when its block carries ``backend: hip`` (``pitchextractor_amd.world``): a worker makes the generator's draws in the
-reference's order, computes the pulse positions of the drawn F0 curve (a sequential float64 recurrence) and the labels,
-and ships a ``WorldRequest`` instead of audio; the device synthesizes only the samples the cropped 192 mel frames read
-into the batch row.  With ``enabled: true`` alone the generator is logged as disabled, as the reference does without
-pyworld.  The analysis / resynthesis augmentation (``synthetic_data.world_resynthesis``, not a key of the reference;
-``enabled: true`` and ``backend: hip``) resynthesizes a listed file on a shifted F0 curve: a worker makes the draws
-(file, semitone, gain, vibrato, noise, crop), builds the new curve and its labels and ships a ``ResynthesisRequest``
-with the file's audio; the device estimates the file's spectral envelope (WORLD CheapTrick) over the frames the cropped
-window reads and synthesizes the window on the new curve, so the labels are exact.
-The pitch-shift augmentation (``synthetic_data.pitch_shift``,
-meldataset.py:324-517) runs on the GPU (``pitchextractor_amd.pitch_shift``): workers draw everything the reference
-draws, in its order, and ship the whole base file; the device shifts it and writes only the samples the cropped
-192 mel frames read into the batch row.  F0 labels come from the reference's cache files under the reference's own
+are not available; pyworld's ``algorithm: dio`` is native, ``f0_tracker.WorldDioTracker``).
+The synthetic augmentations run on the GPU, one kind each behind one protocol in ``pitchextractor_amd.synthetic_items``:
+``synthetic_data.pitch_shift`` (meldataset.py:324-517), ``world_vocoder`` (Utils/synthetic.py; with ``backend: hip``,
+else logged as disabled, as the reference does without pyworld) and ``world_resynthesis`` (not a key of the reference;
+``backend: hip``).  A worker makes the kind's draws in the reference's order, builds the labels and ships a ``Request``;
+the device writes only the samples the cropped 192 mel frames read into the batch row.  Only ``MelDataset``'s gating and
+its fallback ladder (``_generate_synthetic_sample``, the reference's) name a kind; the rest asks the registry.
+F0 labels come from the reference's cache files under the reference's own
 contract (meldataset.py:519-604): ``<wav>_f0<cache_identifier>.npy`` validated by its sibling ``.json``
 (cache_identifier, sample_rate, hop_length), then the legacy ``<wav>_f0.npy``; or from an ``f0_provider`` callable.
 When the enabled backend chain of ``f0_params`` holds a ``praat`` / ``parselmouth`` entry (method ``ac``), the caches
@@ -67,14 +61,16 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from typing import NamedTuple
-
 from .mel import DEFAULT_MEL_PARAMS, MAX_MEL_LENGTH, MEL_MEAN, MEL_STD, LOG_EPS, MelSpectrogram
-from . import f0_tracker
-from .pitch_shift import check_res_type, pitch_shift_ragged
+from . import f0_tracker, synthetic_items
+from .pitch_shift import check_res_type
 from .resample import RaggedResampler, Resampler
-from .world import (CHEAPTRICK_Q1, WorldGenerator, check_fft_size, cheaptrick_fft_size, label_curve, noise_seed,
-                    output_length, resynthesize_ragged, time_base, world_synthesize_ragged)
+from .synthetic_items import (PITCH_SHIFT, WORLD_RESYNTHESIS, WORLD_VOCODER, PitchShiftBatch,  # noqa: F401
+                              PitchShiftRequest, ResynthesisBatch, ResynthesisRequest, WorldBatch, WorldRequest,
+                              synthetic_window)
+from .world import WorldGenerator
+
+_SYNTHETIC_BATCHES = tuple(kind.Batch for kind in synthetic_items.KINDS)     # of the built-in kinds
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.DEBUG)
@@ -275,127 +271,6 @@ def f0_cache_identifier(f0_params: dict | None) -> str:
     return ("-" + "_".join(keys)) if keys else ""
 
 
-# --------------------------------------------------------------------------- synthetic pitch-shift items
-class PitchShiftRequest(NamedTuple):
-    """What a worker hands the device for one pitch-shifted item (last element of the item tuple).  ``n``: samples
-    of the base file at the model rate; the device writes shifted samples [out_start, out_start + out_len) to the
-    batch row, whose mel frame ``frame_start`` is then the item's first kept frame (``crop`` of the whole file)."""
-    path: str
-    n_steps: float
-    gain: float
-    n: int
-    crop: int
-    out_start: int
-    out_len: int
-    frame_start: int
-    noise: np.ndarray | None                   # float32 (out_len,) slice of the reference's full-length draw
-
-
-class PitchShiftBatch(NamedTuple):
-    """Collated synthetic rows: their base files packed back to back (no padding), plus per-row parameters."""
-    rows: torch.Tensor                         # int64 (K,) batch rows
-    src: torch.Tensor                          # float32 flat source audio at the files' own rate
-    src_len: torch.Tensor                      # int64 (K,)
-    n: torch.Tensor                            # int64 (K,) lengths at the model rate
-    n_steps: torch.Tensor                      # float32 (K,)
-    gains: torch.Tensor                        # float32 (K,)
-    out_start: torch.Tensor                    # int64 (K,)
-    out_len: torch.Tensor                      # int64 (K,)
-    noise: torch.Tensor | None                 # float32 flat, the windows back to back
-    src_sr: torch.Tensor | None = None         # int32 (K,) the base files' rates when the batch mixes rates
-
-
-class WorldRequest(NamedTuple):
-    """What a worker hands the device for one WORLD-vocoder item (last element of the item tuple): the drawn curve's
-    pulse table instead of audio.  ``n``: samples of the whole utterance; the device writes synthesized samples
-    [out_start, out_start + out_len) to the batch row, as for a ``PitchShiftRequest``."""
-    template: int
-    gain: float
-    n: int
-    crop: int
-    out_start: int
-    out_len: int
-    frame_start: int
-    curve: np.ndarray                          # float64 (frames,) the drawn F0 curve
-    index: np.ndarray                          # the pulse table (world.time_base)
-    shift: np.ndarray
-    vuv: np.ndarray
-    seed: int                                  # of the aperiodic noise, drawn on the device
-    noise: np.ndarray | None                   # float32 (out_len,) slice of the reference's full-length draw
-
-
-class WorldBatch(NamedTuple):
-    """Collated WORLD-vocoder rows.  Only what the kernels read travels to the device as tensors; the curves and
-    their pulse tables feed the host-side plan and stay numpy arrays."""
-    rows: torch.Tensor                         # int64 (K,) batch rows
-    gains: torch.Tensor                        # float32 (K,)
-    out_len: torch.Tensor                      # int64 (K,)
-    noise: torch.Tensor | None                 # float32 flat, the windows back to back
-    templates: np.ndarray                      # int64 (K,)
-    out_start: np.ndarray                      # int64 (K,)
-    curves: tuple                              # K float64 curves
-    tables: tuple                              # K (index, shift, vuv)
-    seeds: tuple                               # K ints
-
-
-class ResynthesisRequest(NamedTuple):
-    """What a worker hands the device for one analysis / resynthesis item (last element of the item tuple; the item's
-    first element is the base file's audio, as for a pitch-shifted one).  The device estimates the file's CheapTrick
-    envelope under ``base_curve`` and synthesizes samples [out_start, out_start + out_len) of it on ``curve``; the
-    item's labels are ``curve``, exact by construction.  ``n``: samples of the base file at the model rate."""
-    path: str
-    gain: float
-    n: int
-    crop: int
-    out_start: int
-    out_len: int
-    frame_start: int
-    base_curve: np.ndarray                     # float64 (frames,) the file's F0 labels, one per hop
-    curve: np.ndarray                          # float64 (frames,) the new curve = the labels (world.label_curve)
-    index: np.ndarray                          # the new curve's pulse table (world.time_base)
-    shift: np.ndarray
-    vuv: np.ndarray
-    seed: int                                  # of the aperiodic noise, drawn on the device
-    noise: np.ndarray | None                   # float32 (out_len,) slice of the full-length additive draw
-
-
-class ResynthesisBatch(NamedTuple):
-    """Collated resynthesis rows: their base files packed back to back (no padding) and their F0 labels likewise; the
-    new curves and their pulse tables feed the host-side plan and stay numpy arrays."""
-    rows: torch.Tensor                         # int64 (K,) batch rows
-    src: torch.Tensor                          # float32 flat source audio at the files' own rate
-    src_len: torch.Tensor                      # int64 (K,)
-    n: torch.Tensor                            # int64 (K,) lengths at the model rate
-    base: torch.Tensor                         # float32 flat, the base curves back to back
-    gains: torch.Tensor                        # float32 (K,)
-    out_len: torch.Tensor                      # int64 (K,)
-    noise: torch.Tensor | None                 # float32 flat, the windows back to back
-    src_sr: torch.Tensor                       # int32 (K,) the base files' rates
-    out_start: np.ndarray                      # int64 (K,)
-    curves: tuple                              # K float64 curves
-    tables: tuple                              # K (index, shift, vuv)
-    seeds: tuple                               # K ints
-
-
-_SYNTHETIC_REQUESTS = (PitchShiftRequest, WorldRequest, ResynthesisRequest)
-_SYNTHETIC_BATCHES = (PitchShiftBatch, WorldBatch, ResynthesisBatch)
-_RESYNTHESIS_KEYS = ("enabled", "backend", "semitones", "gain_db_range", "noise_db", "min_voiced_fraction",
-                     "max_attempts", "modulation", "aperiodicity", "q1")
-_RESYNTHESIS_MODULATION_KEYS = ("vibrato_probability", "vibrato_semitones", "vibrato_rate_range")
-
-
-def synthetic_window(n: int, crop: int, hop: int, n_fft: int, max_frames: int = MAX_MEL_LENGTH):
-    """(out_start, out_len, frame_start): the shifted samples that mel frames crop .. crop + max_frames - 1 of an
-    n-sample wave read (centre padding n_fft // 2), laid out so that the batch row's frame ``frame_start`` is frame
-    ``crop`` of the whole wave and the row's reflect padding happens only where the whole wave's does."""
-    frames = 1 + n // hop
-    if frames <= max_frames:
-        return 0, n, 0
-    margin = -(-(n_fft // 2) // hop)
-    start, first = (hop * (crop - margin), margin) if crop >= margin else (0, crop)
-    return start, min(n - start, hop * (first + max_frames - 1) + n_fft // 2), first
-
-
 # --------------------------------------------------------------------------- dataset
 class MelDataset(torch.utils.data.Dataset):
     def __init__(self, data_list, sr=DEFAULT_MEL_PARAMS["sample_rate"], mel_params=None, f0_params=None,
@@ -508,7 +383,7 @@ class MelDataset(torch.utils.data.Dataset):
             elif not self.data_list:
                 logger.warning("[MelDataset] WORLD analysis / resynthesis disabled: no base samples available")
             else:
-                self.synthetic_resynthesis_config = self._check_resynthesis_config(resyn_cfg)
+                self.synthetic_resynthesis_config = WORLD_RESYNTHESIS.check_config(self, resyn_cfg)
                 self._synthetic_generators.append("world_resynthesis")
 
         if not self._synthetic_generators or self._synthetic_count <= 0:
@@ -519,237 +394,74 @@ class MelDataset(torch.utils.data.Dataset):
                 print("[MelDataset] Synthetic data disabled: no valid generators or count is zero.")
 
     def _generate_synthetic_sample(self):
-        """meldataset.py:382-418, draw for draw."""
+        """meldataset.py:382-418, draw for draw: which kind makes the item, and which one steps in when it cannot."""
         if not self._synthetic_generators:
             raise RuntimeError("Synthetic generation requested but no generators are available")
         generator_name = random.choice(self._synthetic_generators)
         if generator_name == "pitch_shift":
-            result = self._generate_pitch_shift_sample()
+            result = PITCH_SHIFT.generate(self)
             if result is not None:
                 return result
             remaining = [g for g in self._synthetic_generators if g != "pitch_shift"]
             if remaining:
                 generator_name = random.choice(remaining)
             else:
-                result = self._generate_pitch_shift_sample(force=True)
+                result = PITCH_SHIFT.generate(self, force=True)
                 if result is not None:
                     return result
                 raise RuntimeError("Unable to produce synthetic pitch-shift sample")
         if generator_name == "world_resynthesis":
-            result = self._generate_resynthesis_sample()
+            result = WORLD_RESYNTHESIS.generate(self)
             if result is not None:
                 return result
             if "world_vocoder" not in self._synthetic_generators:
                 raise RuntimeError("Unable to produce synthetic resynthesis sample")
             generator_name = "world_vocoder"                  # the one generator that needs no file; no draw for it
         if generator_name == "world_vocoder" and self._world_generator is not None:
-            return self._generate_world_sample()
+            return WORLD_VOCODER.generate(self)
         raise RuntimeError(f"Unknown synthetic generator '{generator_name}'")
 
-    def _check_resynthesis_config(self, cfg):
-        """The ``world_resynthesis`` block with its defaults filled in; a key it does not read gets a warning, a value
-        it cannot use a ``ValueError``."""
-        for k in cfg:
-            if k not in _RESYNTHESIS_KEYS:
-                logger.warning("world_resynthesis: option %r is not read", k)
-        mod = dict(cfg.get("modulation", {}) or {})
-        for k in mod:
-            if k not in _RESYNTHESIS_MODULATION_KEYS:
-                logger.warning("world_resynthesis.modulation: option %r is not read", k)
-        gain = cfg.get("gain_db_range", [-6.0, 3.0])
-        if isinstance(gain, (int, float)):
-            gain = (float(gain), float(gain))
-        elif gain is not None:
-            gain = tuple(float(v) for v in gain)
-            if len(gain) != 2:
-                raise ValueError("world_resynthesis: gain_db_range must provide two values")
-        aperiodicity = float(cfg.get("aperiodicity", 0.0))
-        if not 0.0 <= aperiodicity < 1.0:
-            raise ValueError("world_resynthesis: aperiodicity must lie in [0, 1)")
-        rate = tuple(float(v) for v in mod.get("vibrato_rate_range", (4.0, 7.0)))
-        if len(rate) != 2:
-            raise ValueError("world_resynthesis: vibrato_rate_range must provide two values")
-        hop = int(self.mel_params["hop_length"])
-        noise_db = cfg.get("noise_db", None)
-        return {"semitones": list(cfg.get("semitones") or [-4, -2, -1, 1, 2, 4]), "gain_db_range": gain,
-                "noise_db": None if noise_db is None else float(noise_db),
-                "min_voiced_fraction": float(cfg.get("min_voiced_fraction", 0.05)),
-                "max_attempts": max(1, int(cfg.get("max_attempts", 5))),
-                "vibrato_probability": float(mod.get("vibrato_probability", 0.6)),
-                "vibrato_semitones": float(mod.get("vibrato_semitones", 0.35)), "vibrato_rate_range": rate,
-                "aperiodicity": aperiodicity, "q1": float(cfg.get("q1", CHEAPTRICK_Q1)),
-                "fft_size": check_fft_size(cheaptrick_fft_size(self.sr)), "frame_period": 1000.0 * hop / self.sr}
+    align_length = staticmethod(align_length)
 
-    def _generate_resynthesis_sample(self):
-        """A listed file resynthesized on a new F0 curve (``world.resynthesize_ragged`` in the loader stage), after
-        ``_generate_pitch_shift_sample``.  Draws, in this order, per attempt: the file (``random.choice``); the
-        semitone (``random.choice``; 0 is allowed: a resynthesis at the file's own pitch); the gain
-        (``random.uniform``, unless ``gain_db_range`` is null); the vibrato (``random.random`` against its
-        probability and, when it applies with a positive depth, ``random.uniform`` for its rate); the additive noise
-        (``np.random.normal`` of the file's length, unless ``noise_db`` is null); the crop (``np.random.randint``, for a
-        file longer than 192 frames).  An unreadable, unlabelled or too sparsely voiced file ends the attempt after
-        the file draw.  Returns None when every attempt failed."""
-        cfg = self.synthetic_resynthesis_config
-        hop = int(self.mel_params["hop_length"])
-        fft_size, frame_period = cfg["fft_size"], cfg["frame_period"]
-        for _ in range(cfg["max_attempts"]):
-            available_paths = [p for p in self.data_list if p not in self._invalid_paths]
-            if not available_paths:
-                return None
-            base_path = random.choice(available_paths)
-            try:
-                wave, wave_sr = read_wav(base_path)
-            except (RuntimeError, OSError, ValueError, struct.error) as exc:
-                self._invalid_paths.add(base_path)
-                logger.warning("[MelDataset] Skipping unreadable audio file: %s (%s)", base_path, exc)
-                continue
-            if wave.ndim > 1:
-                wave = np.mean(wave, axis=-1)
-            wave = wave.astype(np.float32)
-            n = Resampler(wave_sr, self.sr).out_len(len(wave)) if wave_sr != self.sr else len(wave)
-            try:
-                base_f0 = self._f0_for(base_path, wave, 0, None)
-            except RuntimeError as exc:
-                logger.warning("[MelDataset] %s", exc)
-                base_f0 = np.zeros((0,), dtype=np.float32)
-            mel_len = 1 + n // hop
-            if base_f0.size == 0 or mel_len < 2:
-                continue
-            if float(np.count_nonzero(base_f0 > 0)) / max(1, base_f0.size) < cfg["min_voiced_fraction"]:
-                continue
-            # one analysis frame per mel frame: frame f of both sits on sample f * hop
-            base = align_length(np.asarray(base_f0, dtype=np.float32), mel_len).astype(np.float64)
-            base = np.where(np.isfinite(base) & (base > 0), base, 0.0)
-            semitone = random.choice(cfg["semitones"])
-            gain = 1.0
-            if cfg["gain_db_range"] is not None:
-                low, high = sorted(cfg["gain_db_range"])
-                gain = 10.0 ** (random.uniform(low, high) / 20.0)
-            new = base * float(2 ** (semitone / 12.0))
-            if random.random() < cfg["vibrato_probability"]:
-                depth = max(cfg["vibrato_semitones"], 0.0)
-                if depth > 0:
-                    rate = random.uniform(*cfg["vibrato_rate_range"])
-                    t = np.arange(mel_len, dtype=np.float64) * (frame_period / 1000.0)
-                    new = new * 2.0 ** (np.sin(2.0 * math.pi * rate * t) * (depth / 12.0))
-            curve = label_curve(new, self.sr, fft_size)
-            noise = None
-            if cfg["noise_db"] is not None:
-                noise = np.random.normal(scale=10.0 ** (cfg["noise_db"] / 20.0), size=(n,)).astype(np.float32)
-            f0 = align_length(curve.astype(np.float32), mel_len)
-            sil = (f0 == 0).astype(np.float32)
-            crop = 0
-            if mel_len > self.max_mel_length:
-                crop = int(np.random.randint(0, mel_len - self.max_mel_length))
-                f0 = f0[crop:crop + self.max_mel_length]
-                sil = sil[crop:crop + self.max_mel_length]
-            start, count, first = synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
-            table = time_base(curve, self.sr, frame_period, fft_size)
-            req = ResynthesisRequest(base_path, float(gain), int(n), crop, start, count, first, base, curve,
-                                     table.index, table.shift, table.vuv, noise_seed(curve),
-                                     None if noise is None else np.ascontiguousarray(noise[start:start + count]))
-            return torch.from_numpy(wave), torch.from_numpy(f0), torch.from_numpy(sil), first, int(wave_sr), req
-        return None
+    def _base_file_attempt(self, available_paths, min_voiced_fraction):
+        """One attempt of a kind that starts from a listed file (meldataset.py:437-466): draws the file
+        (``random.choice``), reads it as mono float32 and fetches its F0 track -> (path, wave, wave_sr, n = its length
+        at the model rate, base_f0), or None for "next attempt": unreadable (and from now on invalid), unlabelled or
+        voiced in less than ``min_voiced_fraction`` of its frames."""
+        base_path = random.choice(available_paths)
+        try:
+            wave, wave_sr = read_wav(base_path)
+        except (RuntimeError, OSError, ValueError, struct.error) as exc:
+            self._invalid_paths.add(base_path)
+            logger.warning("[MelDataset] Skipping unreadable audio file: %s (%s)", base_path, exc)
+            return None
+        if wave.ndim > 1:
+            wave = np.mean(wave, axis=-1)
+        wave = wave.astype(np.float32)
+        n = Resampler(wave_sr, self.sr).out_len(len(wave)) if wave_sr != self.sr else len(wave)
+        try:
+            base_f0 = self._f0_for(base_path, wave, 0, None)
+        except RuntimeError as exc:          # the reference falls back to an empty track when F0 fails
+            logger.warning("[MelDataset] %s", exc)
+            base_f0 = np.zeros((0,), dtype=np.float32)
+        if base_f0.size == 0 or float(np.count_nonzero(base_f0 > 0)) / base_f0.size < min_voiced_fraction:
+            return None
+        return base_path, wave, wave_sr, n, base_f0
 
-    def _generate_world_sample(self):
-        """Utils/synthetic.py:194-220 + _build_training_example (meldataset.py:629-677) with the synthesis left to the
-        device: the generator's draws in its order, then the crop draw; labels built here from the drawn curve."""
-        draw = self._world_generator.draw()
+    def _labels_and_window(self, curve, n):
+        """_build_training_example (meldataset.py:629-677) with caches off, for a synthetic item of ``n`` samples whose
+        F0 track is ``curve`` (float32): labels per mel frame, the crop draw (``np.random.randint``, beyond 192 frames),
+        the samples the kept frames read -> (f0, is_silence, crop, out_start, out_len, frame_start), NaNs left in."""
         hop = int(self.mel_params["hop_length"])
-        n = output_length(draw.curve.shape[0], self.sr, self._world_generator.frame_period)
         mel_len = 1 + n // hop
-        f0 = align_length(draw.curve.astype(np.float32), mel_len)
+        f0 = align_length(curve, mel_len)
         sil = (f0 == 0).astype(np.float32)
         crop = 0
         if mel_len > self.max_mel_length:
             crop = int(np.random.randint(0, mel_len - self.max_mel_length))
             f0 = f0[crop:crop + self.max_mel_length]
             sil = sil[crop:crop + self.max_mel_length]
-        f0 = np.where(np.isnan(f0), np.float32(self.zero_value), f0).astype(np.float32)
-        start, count, first = synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
-        noise = None if draw.noise is None else np.ascontiguousarray(draw.noise[start:start + count], dtype=np.float32)
-        req = WorldRequest(int(draw.template), float(draw.gain), n, crop, start, count, first, draw.curve,
-                           draw.table.index, draw.table.shift, draw.table.vuv, noise_seed(draw.curve), noise)
-        return (torch.zeros(0, dtype=torch.float32), torch.from_numpy(f0), torch.from_numpy(sil), first, int(self.sr),
-                req)
-
-    def _generate_pitch_shift_sample(self, force=False):
-        """meldataset.py:423-517 with the signal work left to the device: the same draws in the same order, the
-        labels built here, the shift itself requested through a ``PitchShiftRequest``."""
-        cfg = self.synthetic_pitch_shift_config or {}
-        semitone_choices = cfg.get("semitones") or [-4, -2, -1, 1, 2, 4]
-        max_attempts = max(1, int(cfg.get("max_attempts", 5)))
-        min_voiced_fraction = float(cfg.get("min_voiced_fraction", 0.05))
-        gain_db_range = cfg.get("gain_db_range", [-6.0, 3.0])
-        if isinstance(gain_db_range, (int, float)):
-            gain_db_range = (float(gain_db_range), float(gain_db_range))
-        elif gain_db_range is not None:
-            gain_db_range = tuple(float(v) for v in gain_db_range)
-        noise_db = cfg.get("noise_db", None)
-        noise_db = float(noise_db) if noise_db is not None else None
-        keep_original_when_zero = bool(cfg.get("keep_zero_pitch", True))
-        hop = int(self.mel_params["hop_length"])
-
-        for attempt in range(max_attempts):
-            available_paths = [p for p in self.data_list if p not in self._invalid_paths]
-            if not available_paths:
-                if force and attempt == max_attempts - 1:
-                    raise RuntimeError("No valid audio files available for pitch shifting")
-                return None
-            base_path = random.choice(available_paths)
-            try:
-                wave, wave_sr = read_wav(base_path)
-            except (RuntimeError, OSError, ValueError, struct.error) as exc:
-                self._invalid_paths.add(base_path)
-                logger.warning("[MelDataset] Skipping unreadable audio file: %s (%s)", base_path, exc)
-                continue
-            if wave.ndim > 1:
-                wave = np.mean(wave, axis=-1)
-            wave = wave.astype(np.float32)
-            n = Resampler(wave_sr, self.sr).out_len(len(wave)) if wave_sr != self.sr else len(wave)
-            try:
-                base_f0 = self._f0_for(base_path, wave, 0, None)
-            except RuntimeError as exc:          # the reference falls back to an empty track when F0 fails
-                logger.warning("[MelDataset] %s", exc)
-                base_f0 = np.zeros((0,), dtype=np.float32)
-            if base_f0.size == 0:
-                continue
-            voiced_fraction = float(np.count_nonzero(base_f0 > 0)) / max(1, base_f0.size)
-            if voiced_fraction < min_voiced_fraction:
-                continue
-            semitone = random.choice(semitone_choices)
-            if semitone == 0 and not force:
-                continue
-
-            ratio = float(2 ** (semitone / 12.0))
-            shifted_f0 = base_f0.astype(np.float32) * ratio
-            if keep_original_when_zero:
-                shifted_f0[base_f0 == 0] = 0.0
-            gain = 1.0
-            if gain_db_range is not None:
-                low, high = gain_db_range
-                if low > high:
-                    low, high = high, low
-                gain = 10.0 ** (random.uniform(low, high) / 20.0)
-            noise = None
-            if noise_db is not None:
-                noise = np.random.normal(scale=10.0 ** (noise_db / 20.0), size=(n,)).astype(np.float32)
-
-            # _build_training_example (meldataset.py:629-677) with caches off
-            mel_len = 1 + n // hop
-            f0 = align_length(shifted_f0, mel_len)
-            sil = (f0 == 0).astype(np.float32)
-            crop = 0
-            if mel_len > self.max_mel_length:
-                crop = int(np.random.randint(0, mel_len - self.max_mel_length))
-                f0 = f0[crop:crop + self.max_mel_length]
-                sil = sil[crop:crop + self.max_mel_length]
-            f0 = np.where(np.isnan(f0), np.float32(self.zero_value), f0).astype(np.float32)
-            start, count, first = synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
-            req = PitchShiftRequest(base_path, float(semitone), float(gain), int(n), crop, start, count, first,
-                                    None if noise is None else np.ascontiguousarray(noise[start:start + count]))
-            return torch.from_numpy(wave), torch.from_numpy(f0), torch.from_numpy(sil), first, int(wave_sr), req
-        return None
+        return (f0, sil, crop) + synthetic_window(n, crop, hop, int(self.mel_params["n_fft"]), self.max_mel_length)
 
     # ---- labels ---------------------------------------------------------------------------
     def _f0_cache_paths(self, path):
@@ -1083,11 +795,10 @@ class Collater(object):
     host tensors ``(waves (B,Nmax), lengths, crop_starts, f0s, is_silences, source_sr)`` for the device mel stage,
     where ``source_sr`` is the batch's one source rate (``int``, 0 if unknown) or, when its items carry different
     rates, an int32 ``(B,)`` tensor of per-row rates (0 for an item without one),
-    followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram and by a
-    ``PitchShiftBatch`` when any item is a pitch-shifted one, then by a ``WorldBatch`` when any item is a WORLD-vocoder
-    one, then by a ``ResynthesisBatch`` when any item is a resynthesized one.
-    A synthetic row's waveform is left zero (the device writes its window there) and its length is that
-    window's; a pitch-shifted or resynthesized row's base file is packed, not padded."""
+    followed by ``(cached_rows (K,), cached_mels (K,80,192))`` when any item carries a cached spectrogram, then by one
+    ``Batch`` per synthetic kind with items in the batch (their last element is the kind's ``Request``), in the order of
+    ``synthetic_items.KINDS``: pitch shift, WORLD vocoder, WORLD resynthesis.  A synthetic row's waveform is left zero
+    (the device writes its window there) and its length is that window's; the rest travels in the kind's ``Batch``."""
 
     def __init__(self, return_wave=False):
         self.return_wave = return_wave
@@ -1108,11 +819,13 @@ class Collater(object):
                 f0s[i, :n] = f0
                 sils[i, :n] = sil
             return mels.unsqueeze(1), f0s, sils
-        syn = [i for i, item in enumerate(batch) if isinstance(item[-1], PitchShiftRequest)]
-        wld = [i for i, item in enumerate(batch) if isinstance(item[-1], WorldRequest)]
-        rsy = [i for i, item in enumerate(batch) if isinstance(item[-1], ResynthesisRequest)]
-        n_max = max(int(item[-1].out_len) if isinstance(item[-1], _SYNTHETIC_REQUESTS) else int(item[0].shape[0])
-                    for item in batch)
+        rows_of = {}                                   # type of an item's last element -> rows, in one pass
+        for i, item in enumerate(batch):
+            rows_of.setdefault(type(item[-1]), []).append(i)
+        kinds = [kind for kind in synthetic_items.KINDS if kind.Request in rows_of]
+        synthetic = {i for kind in kinds for i in rows_of[kind.Request]}
+        n_max = max(int(item[-1].out_len) if i in synthetic else int(item[0].shape[0])
+                    for i, item in enumerate(batch))
         waves = torch.zeros((B, n_max), dtype=torch.float32)
         lengths = torch.zeros((B,), dtype=torch.int32)
         crops = torch.zeros((B,), dtype=torch.int32)
@@ -1121,7 +834,7 @@ class Collater(object):
         mixed = len(rates) > 1
         for i, item in enumerate(batch):
             wave, f0, sil, crop = item[:4]
-            if isinstance(item[-1], _SYNTHETIC_REQUESTS):
+            if i in synthetic:
                 n = item[-1].out_len
             else:
                 n = wave.shape[0]
@@ -1139,46 +852,7 @@ class Collater(object):
                 m = batch[i][5]
                 cached[k, :, :m.shape[1]] = m
             out += (torch.tensor(rows, dtype=torch.int64), cached)
-        if syn:
-            reqs = [batch[i][-1] for i in syn]
-            noise = None
-            if reqs[0].noise is not None:
-                noise = torch.from_numpy(np.concatenate([r.noise for r in reqs]).astype(np.float32))
-            i64 = lambda v: torch.tensor(v, dtype=torch.int64)  # noqa: E731
-            out += (PitchShiftBatch(i64(syn), torch.cat([batch[i][0].reshape(-1) for i in syn]),
-                                    i64([int(batch[i][0].shape[0]) for i in syn]), i64([r.n for r in reqs]),
-                                    torch.tensor([r.n_steps for r in reqs], dtype=torch.float32),
-                                    torch.tensor([r.gain for r in reqs], dtype=torch.float32),
-                                    i64([r.out_start for r in reqs]), i64([r.out_len for r in reqs]), noise,
-                                    torch.tensor([row_rates[i] for i in syn], dtype=torch.int32) if mixed else None),)
-        if wld:
-            reqs = [batch[i][-1] for i in wld]
-            noise = None
-            if reqs[0].noise is not None:
-                noise = torch.from_numpy(np.concatenate([r.noise for r in reqs]).astype(np.float32))
-            out += (WorldBatch(torch.tensor(wld, dtype=torch.int64),
-                               torch.tensor([r.gain for r in reqs], dtype=torch.float32),
-                               torch.tensor([r.out_len for r in reqs], dtype=torch.int64), noise,
-                               np.array([r.template for r in reqs], dtype=np.int64),
-                               np.array([r.out_start for r in reqs], dtype=np.int64),
-                               tuple(r.curve for r in reqs), tuple((r.index, r.shift, r.vuv) for r in reqs),
-                               tuple(r.seed for r in reqs)),)
-        if rsy:
-            reqs = [batch[i][-1] for i in rsy]
-            noise = None
-            if reqs[0].noise is not None:
-                noise = torch.from_numpy(np.concatenate([r.noise for r in reqs]).astype(np.float32))
-            i64 = lambda v: torch.tensor(v, dtype=torch.int64)  # noqa: E731
-            out += (ResynthesisBatch(i64(rsy), torch.cat([batch[i][0].reshape(-1) for i in rsy]),
-                                     i64([int(batch[i][0].shape[0]) for i in rsy]), i64([r.n for r in reqs]),
-                                     torch.from_numpy(np.concatenate([r.base_curve for r in reqs]).astype(np.float32)),
-                                     torch.tensor([r.gain for r in reqs], dtype=torch.float32),
-                                     i64([r.out_len for r in reqs]), noise,
-                                     torch.tensor([row_rates[i] for i in rsy], dtype=torch.int32),
-                                     np.array([r.out_start for r in reqs], dtype=np.int64),
-                                     tuple(r.curve for r in reqs), tuple((r.index, r.shift, r.vuv) for r in reqs),
-                                     tuple(r.seed for r in reqs)),)
-        return out
+        return out + tuple(kind.collate(batch, rows_of[kind.Request], row_rates, mixed) for kind in kinds)
 
 
 class H2DPrefetcher:
@@ -1195,11 +869,10 @@ class H2DPrefetcher:
 
     def submit(self, host_items):
         def to_dev(t):
-            if isinstance(t, _SYNTHETIC_BATCHES):
-                return type(t)(*(to_dev(x) for x in t))
             return t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t
         with torch.cuda.stream(self.stream):
-            dev = tuple(to_dev(t) for t in host_items)
+            # a tuple among the items is a synthetic kind's Batch: rebuilt field by field, as pin_memory does
+            dev = tuple(type(t)(*map(to_dev, t)) if isinstance(t, tuple) else to_dev(t) for t in host_items)
             ready = torch.cuda.Event()
             ready.record(self.stream)
         return dev, ready
@@ -1209,7 +882,7 @@ class H2DPrefetcher:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ready)
         for t in dev:
-            for x in (t if isinstance(t, _SYNTHETIC_BATCHES) else (t,)):
+            for x in (t if isinstance(t, tuple) else (t,)):
                 if torch.is_tensor(x) and x.is_cuda:
                     x.record_stream(cur)          # allocated on the side stream, consumed on the compute stream
         return dev
@@ -1223,7 +896,7 @@ class DeviceMelLoader:
         self.loader, self.mel, self.device = loader, mel, torch.device(device)
         self.dataset = loader.dataset
         self._ragged = RaggedResampler(mel.sample_rate)
-        self._h2d = None
+        self._h2d, self._host = None, []
 
     def __len__(self):
         return len(self.loader)
@@ -1234,101 +907,18 @@ class DeviceMelLoader:
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)
 
-    def _pitch_shift(self, waves, lengths, src_sr, pack, host):
-        """Synthetic rows: resample their packed base files (if needed), shift them and write each row's window."""
-        sr = self.mel.sample_rate
-        src = pack.src
-        n = host.n.numpy()
-        offsets = np.concatenate([[0], np.cumsum(n)[:-1]])
-        rates = host.src_sr.tolist() if host.src_sr is not None else [src_sr] * len(n)
-        if any(r and r != sr for r in rates):                 # base files at their own rates: one ragged launch
-            src, _ = self._ragged(src, [r or sr for r in rates], host.src_len.tolist())
-            offsets = np.arange(len(n), dtype=np.int64) * src.stride(0)
-            src = src.reshape(-1)
-        need = int(host.out_len.max())
+    def _run_stage(self, kind, waves, lengths, dev_batch, host_batch, src_sr):
+        """One synthetic kind's device stage: ``waves`` widened to the kind's largest window, the kind's ``run``, then
+        its rows' lengths set to their windows'."""
+        need = int(host_batch.out_len.max())
         if waves.shape[1] < need:
             waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
-        waves = waves.contiguous()
-        res_type = (getattr(self.dataset, "synthetic_pitch_shift_config", None) or {}).get("resample_type",
-                                                                                            "kaiser_best")
-        pitch_shift_ragged(src, offsets, n, host.n_steps.numpy(), pack.gains, waves,
-                           host.rows.numpy(), host.out_start.numpy(), host.out_len.numpy(), sr=sr, res_type=res_type,
-                           noise=pack.noise)
-        lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
-        return waves, lengths
+        waves, lengths = kind.run(self, waves.contiguous(), lengths, dev_batch, host_batch, src_sr)
+        return waves, lengths.index_copy(0, dev_batch.rows, dev_batch.out_len.to(torch.int32))
 
-    def _world(self, waves, lengths, pack, host):
-        """WORLD-vocoder rows: synthesize each row's window from its pulse table and vowel template."""
-        gen = self.dataset._world_generator
-        need = int(host.out_len.max())
-        if waves.shape[1] < need:
-            waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
-        waves = waves.contiguous()
-        bins = gen.fft_size // 2 + 1
-        world_synthesize_ragged(pack.curves, gen.device_templates(self.device).reshape(-1), pack.templates * bins,
-                                np.zeros(len(pack.curves), np.int64), pack.gains, waves, host.rows.numpy(),
-                                pack.out_start, host.out_len.numpy(), fs=gen.sample_rate,
-                                frame_period=gen.frame_period, fft_size=gen.fft_size, tables=pack.tables,
-                                seeds=pack.seeds, out_noise=pack.noise)
-        lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
-        return waves, lengths
-
-    def _resynthesis(self, waves, lengths, pack, host):
-        """Resynthesized rows: bring their packed base files to the model rate (if needed), estimate the envelope of
-        the frames each row's window reads and synthesize the window on the row's new curve."""
-        sr = self.mel.sample_rate
-        cfg = self.dataset.synthetic_resynthesis_config
-        src, n = pack.src, host.n.tolist()
-        rates = host.src_sr.tolist()
-        if any(r and r != sr for r in rates):                 # base files at their own rates: one ragged launch
-            src, _ = self._ragged(src, [r or sr for r in rates], host.src_len.tolist())
-        need = int(host.out_len.max())
-        if waves.shape[1] < need:
-            waves = torch.nn.functional.pad(waves, (0, need - waves.shape[1]))
-        waves = waves.contiguous()
-        bins = cfg["fft_size"] // 2 + 1
-        ap = None
-        if cfg["aperiodicity"] > 0:
-            ap = torch.full((bins,), cfg["aperiodicity"], dtype=torch.float32, device=waves.device)
-        resynthesize_ragged(src, n, pack.base.split([len(c) for c in host.curves]), host.curves, sr,
-                            cfg["frame_period"], ap=ap, seeds=host.seeds, gains=pack.gains, out=waves,
-                            out_rows=host.rows.numpy(), out_start=host.out_start, out_len=host.out_len.numpy(),
-                            out_noise=pack.noise, tables=host.tables, q1=cfg["q1"], fft_size=cfg["fft_size"])
-        lengths = lengths.index_copy(0, pack.rows, pack.out_len.to(torch.int32))
-        return waves, lengths
-
-    def _finish(self, ticket):
-        waves, lengths, crops, f0s, sils, src_sr, *cached = self._h2d.acquire(ticket)
-        resyn = cached.pop() if cached and isinstance(cached[-1], ResynthesisBatch) else None
-        world = cached.pop() if cached and isinstance(cached[-1], WorldBatch) else None
-        pack = cached.pop() if cached and isinstance(cached[-1], PitchShiftBatch) else None
-        host_pack, host_world, host_resyn = self._host_packs.pop(0)
-        host_lengths, host_rates = self._host_lengths.pop(0), self._host_rates.pop(0)
-        sr = self.mel.sample_rate
-        rates = host_rates if host_rates is not None else [src_sr] * len(host_lengths)
-        if any(r and r != sr for r in rates):
-            # one ragged launch, each row at its own rate and bit-identical to that item resampled alone; synthetic
-            # rows are left zero (length 0) for the pitch shift, which resamples their base files itself
-            syn = set(host_pack.rows.tolist()) if host_pack is not None else set()
-            for other in (host_world, host_resyn):
-                if other is not None:
-                    syn |= set(other.rows.tolist())
-            waves, lengths = self._ragged(waves, [r or sr for r in rates],
-                                          [0 if i in syn else int(n) for i, n in enumerate(host_lengths)])
-        if pack is not None:                                  # after the resampler, before the one mel launch
-            waves, lengths = self._pitch_shift(waves, lengths, src_sr, pack, host_pack)
-        if world is not None:
-            waves, lengths = self._world(waves, lengths, world, host_world)
-        if resyn is not None:
-            waves, lengths = self._resynthesis(waves, lengths, resyn, host_resyn)
-        mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
-        if cached:                                            # rows whose spectrogram came from <wav>_mel.npy
-            rows, cached_mels = cached
-            mels[:, 0].index_copy_(0, rows, cached_mels)
-        return mels, f0s, sils
-
-    def __iter__(self):
-        """Double-buffered: batch k+1's H2D is in flight on the side stream while batch k is being consumed."""
+    def _submit(self, host):
+        """Start a collated batch's copies on the side stream -> ticket for ``_finish``.  What ``_finish`` reads on the
+        host waits in a FIFO: (lengths, per-row rates or None, {Batch type: host batch})."""
         if self._h2d is None:
             from . import distributed as pdist
             shared = None
@@ -1337,15 +927,38 @@ class DeviceMelLoader:
                 from .model import _side_stream
                 shared = _side_stream(self.device)
             self._h2d = H2DPrefetcher(self.device, stream=shared)
-        self._host_lengths, self._host_rates, self._host_packs = [], [], []
+        self._host.append((host[1].tolist(), host[5].tolist() if torch.is_tensor(host[5]) else None,
+                           {type(t): t for t in host[6:] if isinstance(t, tuple)}))
+        return self._h2d.submit(host)
+
+    def _finish(self, ticket):
+        waves, lengths, crops, f0s, sils, src_sr, *rest = self._h2d.acquire(ticket)
+        host_lengths, host_rates, host_batches = self._host.pop(0)
+        batches = {type(t): (t, host_batches[type(t)]) for t in rest if type(t) in host_batches}
+        cached = [t for t in rest if type(t) not in host_batches]
+        sr = self.mel.sample_rate
+        rates = host_rates if host_rates is not None else [src_sr] * len(host_lengths)
+        if any(r and r != sr for r in rates):
+            # one ragged launch, each row at its own rate and bit-identical to that item resampled alone; synthetic
+            # rows are left zero (length 0): their stages write them, and resample their base files themselves
+            synthetic = {i for t in host_batches.values() for i in t.rows.tolist()}
+            waves, lengths = self._ragged(waves, [r or sr for r in rates],
+                                          [0 if i in synthetic else int(n) for i, n in enumerate(host_lengths)])
+        for kind in synthetic_items.KINDS:                    # after the resampler, before the one mel launch
+            if kind.Batch in batches:
+                waves, lengths = self._run_stage(kind, waves, lengths, *batches[kind.Batch], src_sr)
+        mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
+        if cached:                                            # rows whose spectrogram came from <wav>_mel.npy
+            rows, cached_mels = cached
+            mels[:, 0].index_copy_(0, rows, cached_mels)
+        return mels, f0s, sils
+
+    def __iter__(self):
+        """Double-buffered: batch k+1's H2D is in flight on the side stream while batch k is being consumed."""
+        self._host.clear()
         pending = None
         for host in self.loader:
-            self._host_lengths.append(host[1].tolist())
-            self._host_rates.append(host[5].tolist() if torch.is_tensor(host[5]) else None)
-            packs = [t for t in host[6:] if isinstance(t, _SYNTHETIC_BATCHES)]
-            self._host_packs.append(tuple(next((t for t in packs if isinstance(t, kind)), None)
-                                          for kind in _SYNTHETIC_BATCHES))
-            ticket = self._h2d.submit(host)
+            ticket = self._submit(host)
             if pending is not None:
                 yield self._finish(pending)
             pending = ticket

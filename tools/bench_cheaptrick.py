@@ -4,8 +4,8 @@
 harmonic voices on gliding F0 curves from fixed seeds.  Reports (1) the envelope launch alone, from a run of its own
 under ``rocprofv3 --kernel-trace --stats`` (no counters) started here as a child process; (2) ``resynthesize_ragged``
 of the whole rows with its host work (label curves, time bases, plans; wall clock around a synchronize); (3) the loader
-stage (``DeviceMelLoader._resynthesis``) for a B = 256 batch with 64 resynthesis rows, each cropped to the 192-frame
-window; each next to the fp32 training step of the flagship batch in the same session (bench.py as a child process).
+stage (``DeviceMelLoader._run_stage`` of the ``world_resynthesis`` kind) for a B = 256 batch with 64 resynthesis rows,
+each cropped to the 192-frame window; each next to the fp32 training step of the flagship batch in the same session (bench.py as a child process).
 Writes profiles/bench_cheaptrick.json and profiles/bench_cheaptrick_kernel_stats.csv and prints the JSON line.  Needs a
 GPU.
 
@@ -134,7 +134,7 @@ def loader_stage(dev, waves, f0s, new, reps):
     dev_items = md.H2DPrefetcher(dev).submit(host)[0]
     torch.cuda.synchronize()
     waves_d, lengths_d, pack = dev_items[0], dev_items[1], dev_items[-1]
-    return wall_ms(lambda: loader._resynthesis(waves_d, lengths_d, pack, pack_host), reps)
+    return wall_ms(lambda: loader._run_stage(md.WORLD_RESYNTHESIS, waves_d, lengths_d, pack, pack_host, SR), reps)
 
 
 def training_step_ms():
