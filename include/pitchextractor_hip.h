@@ -269,7 +269,8 @@ int pe_attn_bwd(int products, const float* qkv, long ld_qkv, const float* o, con
  *   reading the output needs (PE_PROD_H2) -- no separate pe_absmax pass.  pe_maxpool_bwd_add merges the values it
  *   rewrote into dx's word: the result bounds max |dx| from above.
  * act16 (every pass of this section but pe_bn_finalize_stats / pe_bn_eval_affine): 0 = fp32 activation tensors, 1 =
- *   bf16 (see "bf16 ACTIVATION STORAGE").  pe_bn_act_pool_bwd with act16 = 1 takes pool in {1, 2, 4}. */
+ *   bf16 (see "bf16 ACTIVATION STORAGE").  pe_bn_act_pool_bwd takes pool in {1, 2, 4} (the widths the model pools by),
+ *   for both storage types; any other width is PE_E_UNSUPPORTED.  The forward pass takes any pool > 0. */
 size_t pe_bn_workspace_bytes(int C);
 int pe_bn_train_stats(int act16, const void* x, long n_pix, int C, const float* gamma, const float* beta, float eps,
                       float momentum, float* running_mean, float* running_var, float* mean, float* invstd,

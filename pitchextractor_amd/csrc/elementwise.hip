@@ -45,6 +45,69 @@ __device__ __forceinline__ void column_reduce2(F&& f, long n_pix, int C, double*
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// ---------------------------------------------------------------- the per-quad rules every pass below shares
+// BatchNorm (as the affine map scale * x + shift) and LeakyReLU of one channel quad
+__device__ __forceinline__ float4 bn_lrelu4(const float4& v, const float4& sc, const float4& sh, float slope) {
+  return make_float4(lrelu(fmaf(v.x, sc.x, sh.x), slope), lrelu(fmaf(v.y, sc.y, sh.y), slope),
+                     lrelu(fmaf(v.z, sc.z, sh.z), slope), lrelu(fmaf(v.w, sc.w, sh.w), slope));
+}
+
+__device__ __forceinline__ float4 fmax4(const float4& a, const float4& b) {
+  return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+}
+
+// dx = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat)) of one quad: sc == gamma*invstd, k1 / k2 the two means
+__device__ __forceinline__ float4 bn_dx4(const float4& dz, const float4& v, const float4& mu, const float4& is,
+                                         const float4& sc, const float4& k1, const float4& k2) {
+  return make_float4(sc.x * (dz.x - k1.x - (v.x - mu.x) * is.x * k2.x), sc.y * (dz.y - k1.y - (v.y - mu.y) * is.y * k2.y),
+                     sc.z * (dz.z - k1.z - (v.z - mu.z) * is.z * k2.z), sc.w * (dz.w - k1.w - (v.w - mu.w) * is.w * k2.w));
+}
+
+// The first maximum of a window and its position, per channel of a quad: a strict > scanning upwards, so a tie stays
+// with the lower position (where torch's max_pool2d backward routes the gradient), a NaN inside the window is skipped
+// and one at the window's start sticks.  `force`: x is the window's first element and is taken whatever m holds.
+// Every max-pool of this file, forward and backward, finds its maxima through this rule; the one place that spells
+// it out again is the LDS fold of bn_act_pool_tap_fwd_kernel (see there).
+__device__ __forceinline__ void first_max(float& m, int& at, float x, int pos, bool force = false) {
+  if (force || x > m) { m = x; at = pos; }
+}
+
+// the running maxima of a channel quad and their positions
+struct FirstMax4 {
+  float4 v;
+  int p0, p1, p2, p3;
+
+  __device__ __forceinline__ static FirstMax4 at(const float4& x, int pos) { return FirstMax4{x, pos, pos, pos, pos}; }
+
+  // one step: the quad x, found at position pos
+  __device__ __forceinline__ void take(const float4& x, int pos, bool force = false) {
+    first_max(v.x, p0, x.x, pos, force);
+    first_max(v.y, p1, x.y, pos, force);
+    first_max(v.z, p2, x.z, pos, force);
+    first_max(v.w, p3, x.w, pos, force);
+  }
+
+  // rows 0 .. n-1 of a window that starts at xp, `stride` elements apart; four rows in flight
+  template <class TA>
+  __device__ __forceinline__ static FirstMax4 scan(const TA* xp, long stride, int n) {
+    FirstMax4 m = at(ld4(xp), 0);
+    int j = 1;
+    for (; j + 4 <= n; j += 4) {
+      float4 x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) x[u] = ld4(xp + (long)(j + u) * stride);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) m.take(x[u], j + u);
+    }
+    for (; j < n; ++j) m.take(ld4(xp + (long)j * stride), j);
+    return m;
+  }
+
+  __device__ __forceinline__ uchar4 bytes() const {
+    return make_uchar4((unsigned char)p0, (unsigned char)p1, (unsigned char)p2, (unsigned char)p3);
+  }
+};
+
 // ---------------------------------------------------------------- BN statistics
 template <class TA>
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const TA* __restrict__ x, long n_pix, int C,
@@ -156,14 +219,8 @@ __global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const TA* __restri
     const TA* xp = x + ((row * Fin + (long)fo * pool) * C + q * 4);
     float4 m;
     for (int j = 0; j < pool; ++j) {
-      const float4 v = ld4(xp + (long)j * C);
-      float4 a;
-      a.x = lrelu(fmaf(v.x, sc.x, sh.x), slope);
-      a.y = lrelu(fmaf(v.y, sc.y, sh.y), slope);
-      a.z = lrelu(fmaf(v.z, sc.z, sh.z), slope);
-      a.w = lrelu(fmaf(v.w, sc.w, sh.w), slope);
-      if (j == 0) m = a;
-      else { m.x = fmaxf(m.x, a.x); m.y = fmaxf(m.y, a.y); m.z = fmaxf(m.z, a.z); m.w = fmaxf(m.w, a.w); }
+      const float4 a = bn_lrelu4(ld4(xp + (long)j * C), sc, sh, slope);
+      m = j == 0 ? a : fmax4(m, a);
     }
     st4(y + op * ldy + coff + q * 4, m);
     am = amax4(am, m);
@@ -204,8 +261,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_tap_fwd_kernel(const TA* __re
     const long tw = trip * TW + wl;
     const bool on = lane_on && tw < n_tap;
     const float ninf = -__builtin_inff();
-    float4 tm = make_float4(ninf, ninf, ninf, ninf);
-    int a0 = seg * segw * POOL, a1 = a0, a2 = a0, a3 = a0;
+    FirstMax4 tm = FirstMax4::at(make_float4(ninf, ninf, ninf, ninf), seg * segw * POOL);
     if (on) {
       const long op0 = tw * nbw + (long)seg * segw;
       const TA* xp = x + (op0 * POOL * C + q * 4);
@@ -219,25 +275,17 @@ __global__ __launch_bounds__(256) void bn_act_pool_tap_fwd_kernel(const TA* __re
         float4 m;
 #pragma unroll
         for (int j = 0; j < POOL; ++j, ++pos) {
-          float4 a;
-          a.x = lrelu(fmaf(v[j].x, sc.x, sh.x), slope);
-          a.y = lrelu(fmaf(v[j].y, sc.y, sh.y), slope);
-          a.z = lrelu(fmaf(v[j].z, sc.z, sh.z), slope);
-          a.w = lrelu(fmaf(v[j].w, sc.w, sh.w), slope);
-          if (j == 0) m = a;
-          else { m.x = fmaxf(m.x, a.x); m.y = fmaxf(m.y, a.y); m.z = fmaxf(m.z, a.z); m.w = fmaxf(m.w, a.w); }
-          if (first || v[j].x > tm.x) { tm.x = v[j].x; a0 = pos; }
-          if (first || v[j].y > tm.y) { tm.y = v[j].y; a1 = pos; }
-          if (first || v[j].z > tm.z) { tm.z = v[j].z; a2 = pos; }
-          if (first || v[j].w > tm.w) { tm.w = v[j].w; a3 = pos; }
+          const float4 a = bn_lrelu4(v[j], sc, sh, slope);
+          m = j == 0 ? a : fmax4(m, a);
+          tm.take(v[j], pos, first);
           first = false;
         }
         st4(yp, m);
         am = amax4(am, m);
       }
       if (S > 1) {
-        tap_val[buf][threadIdx.x] = tm;
-        tap_pos[buf][threadIdx.x] = make_uchar4((unsigned char)a0, (unsigned char)a1, (unsigned char)a2, (unsigned char)a3);
+        tap_val[buf][threadIdx.x] = tm.v;
+        tap_pos[buf][threadIdx.x] = tm.bytes();
       }
     }
     if (S > 1) __syncthreads();
@@ -245,36 +293,22 @@ __global__ __launch_bounds__(256) void bn_act_pool_tap_fwd_kernel(const TA* __re
       for (int k = 1; k < S; ++k) {                                // segments in window order: a tie stays with the lower one
         const float4 o = tap_val[buf][threadIdx.x + k * quads];
         const uchar4 p = tap_pos[buf][threadIdx.x + k * quads];
-        if (o.x > tm.x) { tm.x = o.x; a0 = p.x; }
-        if (o.y > tm.y) { tm.y = o.y; a1 = p.y; }
-        if (o.z > tm.z) { tm.z = o.z; a2 = p.z; }
-        if (o.w > tm.w) { tm.w = o.w; a3 = p.w; }
+        // first_max written out: the positions are converted inside the branches, so the compiler reads them from LDS
+        // byte by byte and only where taken; handed to first_max as ints they become one word read per segment and
+        // another kernel (71 -> 56..60 VGPRs at POOL = 1, other occupancies), which has not been timed
+        if (o.x > tm.v.x) { tm.v.x = o.x; tm.p0 = p.x; }
+        if (o.y > tm.v.y) { tm.v.y = o.y; tm.p1 = p.y; }
+        if (o.z > tm.v.z) { tm.v.z = o.z; tm.p2 = p.z; }
+        if (o.w > tm.v.w) { tm.v.w = o.w; tm.p3 = p.w; }
       }
-      st4(tap_y + tw * tap_ldy + tap_coff + q * 4, tm);
-      if (tap_arg != nullptr)
-        *reinterpret_cast<uchar4*>(tap_arg + tw * C + q * 4) = make_uchar4((unsigned char)a0, (unsigned char)a1,
-                                                                           (unsigned char)a2, (unsigned char)a3);
+      st4(tap_y + tw * tap_ldy + tap_coff + q * 4, tm.v);
+      if (tap_arg != nullptr) *reinterpret_cast<uchar4*>(tap_arg + tw * C + q * 4) = tm.bytes();
     }
   }
   amax_commit(am, amax);
 }
 
-// dz for the input pixel (row, f) of a BN->LReLU->MaxPool block, recomputed from x and dy.
-// The max-pool routes dy to the FIRST maximum of each window (torch max_pool2d backward).
-__device__ __forceinline__ float dz_one(const float* __restrict__ xwin, long cstride, int j, int pool, float sc,
-                                        float sh, float slope, float dyv) {
-  // xwin points at window element 0 of this channel
-  float best = lrelu(fmaf(xwin[0], sc, sh), slope);
-  int arg = 0;
-  for (int k = 1; k < pool; ++k) {
-    const float a = lrelu(fmaf(xwin[(long)k * cstride], sc, sh), slope);
-    if (a > best) { best = a; arg = k; }
-  }
-  if (arg != j) return 0.f;
-  const float z = fmaf(xwin[(long)j * cstride], sc, sh);
-  return z > 0.f ? dyv : dyv * slope;
-}
-
+// ---------------------------------------------------------------- BN -> LReLU -> MaxPool(1,k) backward, k in {1, 2, 4}
 template <class TA>
 struct BnBwdArgsT {
   const TA* x;          // [rows][Fin][C]
@@ -285,50 +319,10 @@ struct BnBwdArgsT {
   const float* invstd;
   float slope;
   long n_in_pix;        // rows * Fin
-  int Fin, C, pool;
+  int Fin, C;
   long lddy;
   int coff;
 };
-typedef BnBwdArgsT<float> BnBwdArgs;
-
-__device__ __forceinline__ float4 dz_quad(const BnBwdArgs& a, long p, int c) {
-  const int Fout = a.Fin / a.pool;
-  const long row = p / a.Fin;
-  const int f = (int)(p % a.Fin);
-  const int fo = f / a.pool, j = f - fo * a.pool;
-  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (fo >= Fout) return out;                                   // floor-mode remainder gets no gradient
-  const float4 dyv = *reinterpret_cast<const float4*>(a.dy + (row * Fout + fo) * a.lddy + a.coff + c);
-  const float* xw = a.x + (row * a.Fin + (long)fo * a.pool) * a.C + c;
-  const float4 sc = *reinterpret_cast<const float4*>(a.scale + c);
-  const float4 sh = *reinterpret_cast<const float4*>(a.shift + c);
-  if (a.pool == 1) {
-    const float4 v = *reinterpret_cast<const float4*>(xw);
-    out.x = fmaf(v.x, sc.x, sh.x) > 0.f ? dyv.x : dyv.x * a.slope;
-    out.y = fmaf(v.y, sc.y, sh.y) > 0.f ? dyv.y : dyv.y * a.slope;
-    out.z = fmaf(v.z, sc.z, sh.z) > 0.f ? dyv.z : dyv.z * a.slope;
-    out.w = fmaf(v.w, sc.w, sh.w) > 0.f ? dyv.w : dyv.w * a.slope;
-    return out;
-  }
-  out.x = dz_one(xw + 0, a.C, j, a.pool, sc.x, sh.x, a.slope, dyv.x);
-  out.y = dz_one(xw + 1, a.C, j, a.pool, sc.y, sh.y, a.slope, dyv.y);
-  out.z = dz_one(xw + 2, a.C, j, a.pool, sc.z, sh.z, a.slope, dyv.z);
-  out.w = dz_one(xw + 3, a.C, j, a.pool, sc.w, sh.w, a.slope, dyv.w);
-  return out;
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const BnBwdArgs a, double* __restrict__ partial) {
-  column_reduce2(
-      [&](long p, int c, float4& s, float4& t) {
-        s = dz_quad(a, p, c);
-        const float4 v = *reinterpret_cast<const float4*>(a.x + p * a.C + c);
-        const float4 mu = *reinterpret_cast<const float4*>(a.mean + c);
-        const float4 is = *reinterpret_cast<const float4*>(a.invstd + c);
-        t = make_float4(s.x * ((v.x - mu.x) * is.x), s.y * ((v.y - mu.y) * is.y), s.z * ((v.z - mu.z) * is.z),
-                        s.w * ((v.w - mu.w) * is.w));
-      },
-      a.n_in_pix, a.C, partial);
-}
 
 __global__ void bn_bwd_finalize_kernel(const double* __restrict__ partial, int nparts, long n_pix, int C,
                                        float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -345,40 +339,14 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ partial, int n
   c2[c] = (float)(s2 / (double)n_pix);
 }
 
-// dx = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat));  scale == gamma*invstd
-// With running statistics (eval mode) the layer is the affine map z = scale * x + shift and dx = scale * dz: the apply
-// passes run with c1 == c2 == nullptr, which stands for two zero vectors (dz - 0 - xhat * 0 == dz exactly).
+// The means of bn_dx4.  With running statistics (eval mode) the layer is the affine map z = scale * x + shift and
+// dx = scale * dz: the apply pass runs with c1 == c2 == nullptr, which stands for two zero vectors
+// (dz - 0 - xhat * 0 == dz exactly).
 __device__ __forceinline__ float4 bn_term(const float* __restrict__ k, int c) {
   return k != nullptr ? *reinterpret_cast<const float4*>(k + c) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a, const float* __restrict__ c1,
-                                                           const float* __restrict__ c2, float* __restrict__ dx,
-                                                           unsigned* __restrict__ amax) {
-  const int quads = a.C >> 2;
-  const long total = a.n_in_pix * quads;
-  float am = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % quads) * 4;
-    const long p = i / quads;
-    const float4 dz = dz_quad(a, p, c);
-    const float4 v = *reinterpret_cast<const float4*>(a.x + p * a.C + c);
-    const float4 mu = *reinterpret_cast<const float4*>(a.mean + c);
-    const float4 is = *reinterpret_cast<const float4*>(a.invstd + c);
-    const float4 sc = *reinterpret_cast<const float4*>(a.scale + c);
-    const float4 k1 = bn_term(c1, c), k2 = bn_term(c2, c);
-    float4 o;
-    o.x = sc.x * (dz.x - k1.x - (v.x - mu.x) * is.x * k2.x);
-    o.y = sc.y * (dz.y - k1.y - (v.y - mu.y) * is.y * k2.y);
-    o.z = sc.z * (dz.z - k1.z - (v.z - mu.z) * is.z * k2.z);
-    o.w = sc.w * (dz.w - k1.w - (v.w - mu.w) * is.w * k2.w);
-    *reinterpret_cast<float4*>(dx + p * a.C + c) = o;
-    am = amax4(am, o);
-  }
-  amax_commit(am, amax);
-}
-
-// Window form of the two backward passes for POOL in {1, 2, 4}: one thread owns a whole pool window of a
+// The two backward passes (per-channel sums, then dx) in window form: one thread owns a whole pool window of a
 // channel quad, so x is read exactly once per pass (float4, coalesced along C), the arg-max is found once
 // and only one 64-bit division is paid per window.  Item w of a row is window w for w < Fout, plus one
 // trailing item for the floor-mode remainder pixels (dz = 0, but they count in the means and get a dx).
@@ -406,6 +374,8 @@ __device__ __forceinline__ void bn_window(const BnBwdArgsT<TA>& a, long item, in
   }
   if (!real) return;
   const float4 dyv = ld4(a.dy + (row * Fout + wi) * a.lddy + a.coff + c);
+  // bn_lrelu4 of the window's quads, channel by channel: computed as whole quads up front the six pooled instances
+  // come out with other registers (apply_win<4>: 80 -> 88..90 VGPRs, occupancy 6 -> 5), so the scalar form stays
   const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
   const float dys[4] = {dyv.x, dyv.y, dyv.z, dyv.w};
 #pragma unroll
@@ -413,10 +383,8 @@ __device__ __forceinline__ void bn_window(const BnBwdArgsT<TA>& a, long item, in
     float best = lrelu(fmaf(reinterpret_cast<const float*>(&w.v[0])[ch], scv[ch], shv[ch]), a.slope);
     int arg = 0;
 #pragma unroll
-    for (int j = 1; j < POOL; ++j) {
-      const float act = lrelu(fmaf(reinterpret_cast<const float*>(&w.v[j])[ch], scv[ch], shv[ch]), a.slope);
-      if (act > best) { best = act; arg = j; }               // first maximum wins (torch max_pool2d backward)
-    }
+    for (int j = 1; j < POOL; ++j)
+      first_max(best, arg, lrelu(fmaf(reinterpret_cast<const float*>(&w.v[j])[ch], scv[ch], shv[ch]), a.slope), j);
     const float g = best > 0.f ? dys[ch] : dys[ch] * a.slope;  // sign(lrelu(z)) == sign(z)
 #pragma unroll
     for (int j = 0; j < POOL; ++j) reinterpret_cast<float*>(&w.dz[j])[ch] = j == arg ? g : 0.f;
@@ -467,11 +435,16 @@ __device__ __forceinline__ float add_unfused(float a, float b) {
   return a + b;
 }
 
-template <int POOL, class TA>
-__global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BnBwdArgsT<TA> a, long n_items, int nwin,
-                                                               const float* __restrict__ c1,
-                                                               const float* __restrict__ c2, TA* __restrict__ dx,
-                                                               unsigned* __restrict__ amax) {
+// The apply pass: dx of every window, and with a tap (Tap = BnTapGrad<TA>; NoTap: none) the tap's gradient added to the
+// element it belongs to.  Fin % tap_pool == 0 and n_items < 2^31 (the host checks both), so BN window `item` of the
+// whole tensor lies in tap window item / nbw, at positions pos0 .. pos0 + POOL - 1 of it.
+struct NoTap {};
+
+template <int POOL, class TA, class Tap>
+__device__ __forceinline__ void bn_bwd_apply_win(const BnBwdArgsT<TA>& a, long n_items, int nwin,
+                                                 const float* __restrict__ c1, const float* __restrict__ c2,
+                                                 TA* __restrict__ dx, unsigned* __restrict__ amax, const Tap& t) {
+  constexpr bool TAP = !std::is_same<Tap, NoTap>::value;
   const int quads = a.C >> 2;
   float am = 0.f;
   const int G = 256 / quads, c = (threadIdx.x % quads) * 4, g = threadIdx.x / quads;     // see bn_act_pool_fwd_kernel
@@ -481,62 +454,49 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BnBwdArgsT<
   for (long item = (long)blockIdx.x * G + g; g < G && item < n_items; item += (long)gridDim.x * G) {
     BnWindow<POOL> w;
     bn_window<POOL, TA>(a, item, nwin, c, w, sc, sh);
+    [[maybe_unused]] int pos0 = 0;
+    [[maybe_unused]] uchar4 ar;
+    [[maybe_unused]] float4 tg;
+    if constexpr (TAP) {
+      const unsigned tw = (unsigned)item / t.nbw;
+      pos0 = (int)((unsigned)item - tw * t.nbw) * POOL;
+      ar = *reinterpret_cast<const uchar4*>(t.arg + (long)tw * a.C + c);
+      tg = ld4(t.dy + (long)tw * t.lddy + t.coff + c);
+    }
 #pragma unroll
     for (int j = 0; j < POOL; ++j) {
       if (j >= w.n) break;
-      float4 o;
-      o.x = sc.x * (w.dz[j].x - k1.x - (w.v[j].x - mu.x) * is.x * k2.x);
-      o.y = sc.y * (w.dz[j].y - k1.y - (w.v[j].y - mu.y) * is.y * k2.y);
-      o.z = sc.z * (w.dz[j].z - k1.z - (w.v[j].z - mu.z) * is.z * k2.z);
-      o.w = sc.w * (w.dz[j].w - k1.w - (w.v[j].w - mu.w) * is.w * k2.w);
-      st4(dx + (w.p0 + j) * a.C + c, o);
+      float4 o = bn_dx4(w.dz[j], w.v[j], mu, is, sc, k1, k2);
       am = amax4(am, o);
+      if constexpr (TAP) {
+        // the two steps this replaces, value for value: dx is stored (rounded to TA) and its word takes |dx|; then the
+        // tap pass reads the stored element back, adds its gradient, stores again and merges |dx + g| into the word
+        const int pj = pos0 + j;
+        if (ar.x == pj) { o.x = add_unfused(round_act(dx, o.x), tg.x); am = fmaxf(am, fabsf(o.x)); }
+        if (ar.y == pj) { o.y = add_unfused(round_act(dx, o.y), tg.y); am = fmaxf(am, fabsf(o.y)); }
+        if (ar.z == pj) { o.z = add_unfused(round_act(dx, o.z), tg.z); am = fmaxf(am, fabsf(o.z)); }
+        if (ar.w == pj) { o.w = add_unfused(round_act(dx, o.w), tg.w); am = fmaxf(am, fabsf(o.w)); }
+      }
+      st4(dx + (w.p0 + j) * a.C + c, o);
     }
   }
   amax_commit(am, amax);
 }
 
-// The same apply pass with the tap's gradient added to the element it belongs to.  Fin % tap_pool == 0 and
-// n_items < 2^31 (the host checks both), so BN window `item` of the whole tensor lies in tap window item / nbw, at
-// positions pos0 .. pos0 + POOL - 1 of it.
+template <int POOL, class TA>
+__global__ __launch_bounds__(256) void bn_bwd_apply_win_kernel(const BnBwdArgsT<TA> a, long n_items, int nwin,
+                                                               const float* __restrict__ c1,
+                                                               const float* __restrict__ c2, TA* __restrict__ dx,
+                                                               unsigned* __restrict__ amax) {
+  bn_bwd_apply_win<POOL, TA>(a, n_items, nwin, c1, c2, dx, amax, NoTap{});
+}
+
 template <int POOL, class TA>
 __global__ __launch_bounds__(256) void bn_bwd_apply_win_tap_kernel(const BnBwdArgsT<TA> a, long n_items, int nwin,
                                                                    const float* __restrict__ c1,
                                                                    const float* __restrict__ c2, TA* __restrict__ dx,
                                                                    unsigned* __restrict__ amax, const BnTapGrad<TA> t) {
-  const int quads = a.C >> 2;
-  float am = 0.f;
-  const int G = 256 / quads, c = (threadIdx.x % quads) * 4, g = threadIdx.x / quads;     // see bn_act_pool_fwd_kernel
-  const float4 mu = *reinterpret_cast<const float4*>(a.mean + c), is = *reinterpret_cast<const float4*>(a.invstd + c);
-  const float4 sc = *reinterpret_cast<const float4*>(a.scale + c), sh = *reinterpret_cast<const float4*>(a.shift + c);
-  const float4 k1 = bn_term(c1, c), k2 = bn_term(c2, c);
-  for (long item = (long)blockIdx.x * G + g; g < G && item < n_items; item += (long)gridDim.x * G) {
-    BnWindow<POOL> w;
-    bn_window<POOL, TA>(a, item, nwin, c, w, sc, sh);
-    const unsigned tw = (unsigned)item / t.nbw;
-    const int pos0 = (int)((unsigned)item - tw * t.nbw) * POOL;
-    const uchar4 ar = *reinterpret_cast<const uchar4*>(t.arg + (long)tw * a.C + c);
-    const float4 tg = ld4(t.dy + (long)tw * t.lddy + t.coff + c);
-#pragma unroll
-    for (int j = 0; j < POOL; ++j) {
-      if (j >= w.n) break;
-      float4 o;
-      o.x = sc.x * (w.dz[j].x - k1.x - (w.v[j].x - mu.x) * is.x * k2.x);
-      o.y = sc.y * (w.dz[j].y - k1.y - (w.v[j].y - mu.y) * is.y * k2.y);
-      o.z = sc.z * (w.dz[j].z - k1.z - (w.v[j].z - mu.z) * is.z * k2.z);
-      o.w = sc.w * (w.dz[j].w - k1.w - (w.v[j].w - mu.w) * is.w * k2.w);
-      // the two steps this replaces, value for value: dx is stored (rounded to TA) and its word takes |dx|; then the
-      // tap pass reads the stored element back, adds its gradient, stores again and merges |dx + g| into the word
-      am = amax4(am, o);
-      const int pj = pos0 + j;
-      if (ar.x == pj) { o.x = add_unfused(round_act(dx, o.x), tg.x); am = fmaxf(am, fabsf(o.x)); }
-      if (ar.y == pj) { o.y = add_unfused(round_act(dx, o.y), tg.y); am = fmaxf(am, fabsf(o.y)); }
-      if (ar.z == pj) { o.z = add_unfused(round_act(dx, o.z), tg.z); am = fmaxf(am, fabsf(o.z)); }
-      if (ar.w == pj) { o.w = add_unfused(round_act(dx, o.w), tg.w); am = fmaxf(am, fabsf(o.w)); }
-      st4(dx + (w.p0 + j) * a.C + c, o);
-    }
-  }
-  amax_commit(am, amax);
+  bn_bwd_apply_win<POOL, TA>(a, n_items, nwin, c1, c2, dx, amax, t);
 }
 
 // ---------------------------------------------------------------- plain MaxPool(1,k) (detector taps)
@@ -553,28 +513,25 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const TA* __restrict__
     const long op = i / quads, row = op / Fout;
     const int fo = (int)(op % Fout);
     const TA* xp = x + ((row * Fin + (long)fo * pool) * C + q * 4);
+    // FirstMax4::scan on variables of the kernel's own: with the maxima and positions in one struct the bf16 instance
+    // comes out another kernel (42 -> 54 VGPRs, 604 -> 637 instructions), which has not been timed
     float4 m = ld4(xp);
     int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    const auto take = [&](const float4& v, int pos) {
+      first_max(m.x, a0, v.x, pos);
+      first_max(m.y, a1, v.y, pos);
+      first_max(m.z, a2, v.z, pos);
+      first_max(m.w, a3, v.w, pos);
+    };
     int j = 1;
     for (; j + 4 <= pool; j += 4) {                               // four window rows in flight
       float4 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = ld4(xp + (long)(j + u) * C);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (v[u].x > m.x) { m.x = v[u].x; a0 = j + u; }
-        if (v[u].y > m.y) { m.y = v[u].y; a1 = j + u; }
-        if (v[u].z > m.z) { m.z = v[u].z; a2 = j + u; }
-        if (v[u].w > m.w) { m.w = v[u].w; a3 = j + u; }
-      }
+      for (int u = 0; u < 4; ++u) take(v[u], j + u);
     }
-    for (; j < pool; ++j) {
-      const float4 v = ld4(xp + (long)j * C);
-      if (v.x > m.x) { m.x = v.x; a0 = j; }
-      if (v.y > m.y) { m.y = v.y; a1 = j; }
-      if (v.z > m.z) { m.z = v.z; a2 = j; }
-      if (v.w > m.w) { m.w = v.w; a3 = j; }
-    }
+    for (; j < pool; ++j) take(ld4(xp + (long)j * C), j);
     st4(y + op * ldy + coff + q * 4, m);
     if (arg != nullptr)
       *reinterpret_cast<uchar4*>(arg + op * C + q * 4) = make_uchar4((unsigned char)a0, (unsigned char)a1,
@@ -599,33 +556,13 @@ __global__ __launch_bounds__(256) void maxpool_bwd_add_kernel(const TA* __restri
     const int c = (int)(i - op * quads) * 4;
     const long row = op / Fout;
     const int fo = (int)(op - row * Fout);
-    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    int a0, a1, a2, a3;
     if (arg != nullptr) {
       const uchar4 a = *reinterpret_cast<const uchar4*>(arg + op * C + c);
       a0 = a.x; a1 = a.y; a2 = a.z; a3 = a.w;
     } else {
-    const TA* xp = x + (row * Fin + (long)fo * pool) * C + c;
-    float4 best = ld4(xp);
-    int jn = 1;
-    for (; jn + 4 <= pool; jn += 4) {
-      float4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = ld4(xp + (long)(jn + u) * C);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (v[u].x > best.x) { best.x = v[u].x; a0 = jn + u; }
-        if (v[u].y > best.y) { best.y = v[u].y; a1 = jn + u; }
-        if (v[u].z > best.z) { best.z = v[u].z; a2 = jn + u; }
-        if (v[u].w > best.w) { best.w = v[u].w; a3 = jn + u; }
-      }
-    }
-    for (; jn < pool; ++jn) {
-      const float4 v = ld4(xp + (long)jn * C);
-      if (v.x > best.x) { best.x = v.x; a0 = jn; }
-      if (v.y > best.y) { best.y = v.y; a1 = jn; }
-      if (v.z > best.z) { best.z = v.z; a2 = jn; }
-      if (v.w > best.w) { best.w = v.w; a3 = jn; }
-    }
+      const FirstMax4 m = FirstMax4::scan(x + (row * Fin + (long)fo * pool) * C + c, C, pool);
+      a0 = m.p0; a1 = m.p1; a2 = m.p2; a3 = m.p3;
     }
     const float4 g = ld4(dy + op * lddy + coff + c);
     TA* dp = dx + (row * Fin + (long)fo * pool) * C + c;
@@ -739,6 +676,16 @@ int reduce_grid(long n_pix, int C, int cap = 1024) {
 size_t reduce_lds(int C) { return (size_t)(256 / (C / 4)) * 2 * C * sizeof(double); }
 
 bool bn_channels_ok(int C) { return C >= 4 && (C % 4) == 0 && C <= 1024; }
+
+// Calls fn(std::integral_constant<int, POOL>{}) for the pool widths the window-form kernels are built for (the ones
+// JDCNet pools by) and returns its status; PE_E_UNSUPPORTED for any other (what with_act of forms.h is for `act16`).
+template <class Fn>
+int with_pool(int pool, Fn&& fn) {
+  if (pool == 1) return fn(std::integral_constant<int, 1>{});
+  if (pool == 2) return fn(std::integral_constant<int, 2>{});
+  if (pool == 4) return fn(std::integral_constant<int, 4>{});
+  return PE_E_UNSUPPORTED;
+}
 
 // ---------------------------------------------------------------- largest magnitude of a tensor (h2 operand scale)
 // out[0] = max(out[0], IEEE bits of max |x|) over a row-strided [rows][cols] matrix (cols % 4 == 0).  The bit
@@ -893,61 +840,40 @@ static int bn_act_pool_bwd_impl(const TA* x, const TA* dy, const float* scale, c
   const bool sums = !(eval_mode && !dgamma && !dbeta);
   if (!x || !dy || !scale || !shift || !mean || !invstd || !dx || rows <= 0) return PE_E_ARG;
   if (sums && (!dgamma || !dbeta)) return PE_E_ARG;
-  if (!bn_channels_ok(C) || (lddy & 3) || (coff & 3) || pool <= 0) return PE_E_UNSUPPORTED;
+  if (!bn_channels_ok(C) || (lddy & 3) || (coff & 3)) return PE_E_UNSUPPORTED;
   const size_t need = pe_bn_workspace_bytes(C) + 2 * (size_t)C * sizeof(float);
   if (sums && (!workspace || workspace_bytes < need)) return PE_E_WORKSPACE;
   hipStream_t st = pe_stream(stream);
-  BnBwdArgsT<TA> a{x, dy, scale, shift, mean, invstd, slope, rows * Fin, Fin, C, pool, lddy, coff};
+  const BnBwdArgsT<TA> a{x, dy, scale, shift, mean, invstd, slope, rows * Fin, Fin, C, lddy, coff};
   double* partial = reinterpret_cast<double*>(workspace);
   float* c1 = eval_mode ? nullptr
                         : reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pe_bn_workspace_bytes(C));
   float* c2 = eval_mode ? nullptr : c1 + C;
-  const int nwin = Fin / pool + (Fin % pool ? 1 : 0);
-  const long n_items = rows * nwin;
-  const bool win = pool == 1 || pool == 2 || pool == 4;
-  if (!win && !std::is_same<TA, float>::value) return PE_E_UNSUPPORTED;      // other pool widths: fp32 tensors only
-  // bf16 tensors without pooling: 8-byte requests, so four times the workgroups keep the same bytes in flight
-  // (partial<1>: 348 -> 257 us; the pooled forms and fp32 tensors, at HBM speed with 1024, lose 5-10 % with more)
-  const int grid = reduce_grid(win ? n_items : a.n_in_pix, C,
-                               (!std::is_same<TA, float>::value && pool == 1) ? kMaxPartials : 1024);
-  if (sums) {
-    if (pool == 1)
-      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<1, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
-    else if (pool == 2)
-      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<2, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
-    else if (pool == 4)
-      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<4, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items, nwin, partial);
-    else if constexpr (std::is_same<TA, float>::value)
-      hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(grid), dim3(256), reduce_lds(C), st, a, partial);
-    PE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(pe_cdiv(C, 4)), dim3(256), 0, st, partial, grid, a.n_in_pix, C,
-                       dgamma, dbeta, c1, c2);
-    PE_LAUNCH_CHECK();
-  }
-  const int agrid = win ? ew_grid(pe_cdiv(n_items, 256 / (C / 4)) * 256L) : ew_grid(a.n_in_pix * (C / 4));
-  if (tap != nullptr) {                  // (the caller checked tap_geometry_ok: pool is 1, 2 or 4)
-    if (pool == 1)
-      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<1, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2,
-                         dx, amax_out, *tap);
-    else if (pool == 2)
-      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<2, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2,
-                         dx, amax_out, *tap);
+  return with_pool(pool, [&](auto p) {
+    constexpr int POOL = decltype(p)::value;
+    const int nwin = Fin / POOL + (Fin % POOL ? 1 : 0);
+    const long n_items = rows * nwin;
+    if (sums) {
+      // bf16 tensors without pooling: 8-byte requests, so four times the workgroups keep the same bytes in flight
+      // (partial<1>: 348 -> 257 us; the pooled forms and fp32 tensors, at HBM speed with 1024, lose 5-10 % with more)
+      const int grid = reduce_grid(n_items, C, (!std::is_same<TA, float>::value && POOL == 1) ? kMaxPartials : 1024);
+      hipLaunchKernelGGL((bn_bwd_partial_win_kernel<POOL, TA>), dim3(grid), dim3(256), reduce_lds(C), st, a, n_items,
+                         nwin, partial);
+      PE_LAUNCH_CHECK();
+      hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(pe_cdiv(C, 4)), dim3(256), 0, st, partial, grid, a.n_in_pix, C,
+                         dgamma, dbeta, c1, c2);
+      PE_LAUNCH_CHECK();
+    }
+    const dim3 agrid(ew_grid(pe_cdiv(n_items, 256 / (C / 4)) * 256L));
+    if (tap != nullptr)
+      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<POOL, TA>), agrid, dim3(256), 0, st, a, n_items, nwin, c1, c2, dx,
+                         amax_out, *tap);
     else
-      hipLaunchKernelGGL((bn_bwd_apply_win_tap_kernel<4, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2,
-                         dx, amax_out, *tap);
-  } else if (pool == 1)
-    hipLaunchKernelGGL((bn_bwd_apply_win_kernel<1, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2, dx,
-                       amax_out);
-  else if (pool == 2)
-    hipLaunchKernelGGL((bn_bwd_apply_win_kernel<2, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2, dx,
-                       amax_out);
-  else if (pool == 4)
-    hipLaunchKernelGGL((bn_bwd_apply_win_kernel<4, TA>), dim3(agrid), dim3(256), 0, st, a, n_items, nwin, c1, c2, dx,
-                       amax_out);
-  else if constexpr (std::is_same<TA, float>::value)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(agrid), dim3(256), 0, st, a, c1, c2, dx, amax_out);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+      hipLaunchKernelGGL((bn_bwd_apply_win_kernel<POOL, TA>), agrid, dim3(256), 0, st, a, n_items, nwin, c1, c2, dx,
+                         amax_out);
+    PE_LAUNCH_CHECK();
+    return (int)PE_OK;
+  });
 }
 
 extern "C" int pe_bn_act_pool_bwd(int act16, const void* x, const void* dy, const float* scale, const float* shift,
@@ -996,17 +922,12 @@ static int bn_act_pool_tap_fwd_impl(const TA* x, const float* scale, const float
   const long n_tap = rows * (Fin / tap_pool), n_trips = pe_cdiv(n_tap, (long)(G / S));
   const dim3 grid(ew_grid(n_trips * 256L));
   hipStream_t st = pe_stream(stream);
-  if (pool == 1)
-    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<1, TA>), grid, dim3(256), 0, st, x, scale, shift, slope, y, n_tap, C,
-                       nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
-  else if (pool == 2)
-    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<2, TA>), grid, dim3(256), 0, st, x, scale, shift, slope, y, n_tap, C,
-                       nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
-  else
-    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<4, TA>), grid, dim3(256), 0, st, x, scale, shift, slope, y, n_tap, C,
-                       nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
-  PE_LAUNCH_CHECK();
-  return PE_OK;
+  return with_pool(pool, [&](auto p) {
+    hipLaunchKernelGGL((bn_act_pool_tap_fwd_kernel<decltype(p)::value, TA>), grid, dim3(256), 0, st, x, scale, shift,
+                       slope, y, n_tap, C, nbw, S, ldy, coff, amax_out, tap_y, tap_ldy, tap_coff, tap_arg);
+    PE_LAUNCH_CHECK();
+    return (int)PE_OK;
+  });
 }
 
 extern "C" int pe_bn_act_pool_tap_fwd(int act16, const void* x, const float* scale, const float* shift, float slope,

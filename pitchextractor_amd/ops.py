@@ -695,8 +695,9 @@ def bn_act_pool_bwd(x, dy, st: BnState, dgamma, dbeta, pool=1, slope=0.01, coff=
     """``amax_out``: as in ``bn_act_pool_fwd``, for dx.  ``tap`` (with ``grad`` and ``argmax`` set): dx also takes the
     gradient of the tap, and ``amax_out`` what ``maxpool_bwd_add`` would have merged into it.  The mode follows
     ``st.eval``; with an eval-mode state ``dgamma`` and ``dbeta`` may both be None (input gradient only: no per-channel
-    reduction, no workspace)."""
+    reduction, no workspace).  ``pool`` is 1, 2 or 4: the widths the backward kernels are built for."""
     x = _actd(x, "x")
+    _chk(pool in (1, 2, 4), "bn_act_pool_bwd: pool is 1, 2 or 4")
     paired, amax_out = amax_out is True, (amax_word() if amax_out is True else amax_out)
     B, T, F, Cc = x.shape
     ld = _slice_target(dy, B, T, F // pool, Cc, coff)
