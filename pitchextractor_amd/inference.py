@@ -122,7 +122,10 @@ def predict_f0(model: JDCNet, audio, chunk_size: int = 192, overlap: int = 48,
     the un-blended concatenation repeats ``overlap`` frames at each seam, so no path runs across seams), all chunks
     are decoded in one call and concatenated as the Hz of a regression model are.  ``silence_threshold=p`` returns
     0 Hz where ``sigmoid(detector logit) > p`` (the detector head predicts ``is_silence``).
-    ``return_confidence=True`` returns ``(f0, confidence)``, confidence = softmax(frame)[decoded bin]."""
+    ``return_confidence=True`` returns ``(f0, confidence)``, confidence = softmax(frame)[decoded bin].
+
+    A Transformer model needs ``chunk_size % 4 == 0`` and ``chunk_size <= max_len`` (its positional table); the
+    model raises otherwise."""
     _check_decoding(model, decoder, silence_threshold, return_confidence)
     device = model.flat_parameters.device
     mel = waveform_to_mel(audio, mel_transform, device)
@@ -338,7 +341,8 @@ def predict_f0_batch(model: JDCNet, waves, lengths=None, *, chunk_size: int = 19
     (rows go through it in padded groups by length of at most ``group_bytes``).  ``silence_threshold`` and
     ``return_confidence`` as in ``predict_f0``, on the stitched detector logit.  A chunk's output depends at rounding
     level on the chunks that share its forward (the h2 products scale by tensor maxima), so the result is not
-    bit-equal to a ``predict_f0`` loop in any mode."""
+    bit-equal to a ``predict_f0`` loop in any mode.  A Transformer model needs ``chunk_size % 4 == 0`` and
+    ``chunk_size <= max_len`` (its positional table); the model raises otherwise."""
     _check_decoding(model, decoder, silence_threshold, return_confidence)
     device = model.flat_parameters.device
     if isinstance(waves, (list, tuple)):

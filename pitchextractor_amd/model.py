@@ -511,6 +511,13 @@ def _tf_forward(sm, x, train, need_grad, drop: _DropoutCfg, frozen=False):
     H = sm.nhead
     dh = D // H
     R = B * T
+    # refused before the first launch: a shorter table would make the LayerNorm kernel's `row % period` wrap the
+    # positions (the reference fails to broadcast here), and the batched products read rows of T floats as float4
+    max_len = sm.pos_encoding.pe.shape[1]
+    if T > max_len:
+        raise ValueError(f"transformer head: T = {T} frames exceed the positional table's max_len = {max_len}")
+    if T % 4:
+        raise NotImplementedError(f"transformer head: T = {T} frames must be a multiple of 4")
     p = sm.dropout if train else 0.0
     scale = 1.0 / math.sqrt(dh)
     saved = _Ctx()
