@@ -380,7 +380,8 @@ int pe_colsum(const float* x, long rows, int cols, long ld, float* out0, float* 
  *   trainer.py:237-239) and the gradients w.r.t. both prediction vectors (times grad_scale).
  * pe_adamw_step: torch.optim.AdamW (optimizers.py:55-62) on a flat buffer; the caller passes the
  *   current lr / beta1 (OneCycleLR rewrites both every step) and the bias corrections
- *   1 - beta^step computed in double. Gradients are multiplied by grad_scale first. */
+ *   1 - beta^step computed in double (step >= 1: a correction outside (0, 1] is PE_E_ARG -- step 0 would make
+ *   the step size infinite). Gradients are multiplied by grad_scale first. */
 int pe_head_fwd(const float* x, long ldx, const float* w, const float* bias, int n_out, float* y, long R,
                 int D, void* stream);
 size_t pe_head_bwd_workspace_bytes(int D);

@@ -371,6 +371,9 @@ extern "C" int pe_adamw_step(float* param, const float* grad, float* exp_avg, fl
                              float beta1, float beta2, float eps, float weight_decay, double bias_correction1,
                              double bias_correction2, float grad_scale, const float* skip_if_nonzero, void* stream) {
   if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return PE_E_ARG;
+  // 1 - beta^step of a step >= 1 lies in (0, 1]; 0 (step 0) would make the step size infinite and every parameter NaN
+  if (!(bias_correction1 > 0.0 && bias_correction1 <= 1.0) || !(bias_correction2 > 0.0 && bias_correction2 <= 1.0))
+    return PE_E_ARG;
   if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return PE_E_UNSUPPORTED;
   AdamArgs a;
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;

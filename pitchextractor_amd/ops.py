@@ -740,6 +740,9 @@ def maxpool_fwd(x, pool, out=None, coff=0, want_argmax=False):
         out = torch.empty((B, T, Fo, Cc), dtype=x.dtype, device=x.device)
     ld = _slice_target(out, B, T, Fo, Cc, coff)
     arg = torch.empty((B, T, Fo, Cc), dtype=torch.uint8, device=x.device) if want_argmax else None
+    if Fo == 0:                                 # F < pool: no window, nothing to write (and no pointer to pass)
+        _act16(x, out)
+        return (out, arg) if want_argmax else out
     _call("pe_maxpool_fwd", x.data_ptr(), out.data_ptr(), B * T, F, Cc, pool, ld, coff, _lib.ptr(arg), _s(),
           act16=_act16(x, out))
     return (out, arg) if want_argmax else out
@@ -761,6 +764,9 @@ def maxpool_bwd_add(x, dy, dx, pool, coff=0, amax_out=None, argmax=None):
              and argmax.shape == (B, T, F // pool, Cc), "maxpool_bwd_add: argmax shape")
     ld = _slice_target(dy, B, T, F // pool, Cc, coff)
     _chk(_actd(dx, "dx").shape == x.shape, "dx shape")
+    if F // pool == 0:                          # F < pool: no window, dx stays as it is
+        _act16(dy, dx, x if argmax is None else None)
+        return Scaled(dx, amax_out) if paired else dx
     _call("pe_maxpool_bwd_add", x.data_ptr() if argmax is None else 0, _lib.ptr(argmax), dy.data_ptr(), dx.data_ptr(),
           B * T, F, Cc, pool, ld, coff, _lib.ptr(amax_out), _s(), act16=_act16(dy, dx, x if argmax is None else None))
     return Scaled(dx, amax_out) if paired else dx
@@ -1231,6 +1237,8 @@ def nonfinite_flag(x, flag=None):
     if flag is None:
         flag = torch.empty((1,), dtype=torch.int32, device=x.device)
     _chk(flag.is_cuda and flag.dtype == torch.int32 and flag.numel() == 1, "flag: int32 device scalar")
+    if x.numel() == 0:                          # nothing to test (and no pointer to pass): the word is cleared
+        return flag.zero_()
     _call("pe_nonfinite_flag", x.data_ptr(), x.numel(), flag.data_ptr(), _s())
     return flag
 
@@ -1241,6 +1249,7 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_d
     n = param.numel()
     for t, nme in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _chk(_dense(t, nme).numel() == n, f"{nme}: size")
+    _chk(int(step) >= 1, "adamw_step: steps count from 1 (step 0 has no bias correction: the step size is infinite)")
     bc1 = 1.0 - float(beta1) ** int(step)
     bc2 = 1.0 - float(beta2) ** int(step)
     _call("pe_adamw_step", param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,

@@ -17,13 +17,14 @@ PINK = (0.5362, 0.115926, ((0.99886, 0.0555179), (0.99332, 0.0750759), (0.96900,
                            (0.55000, 0.5329522), (-0.7616, -0.0168980)))
 
 
-def philox4x32(seed: int, counters) -> np.ndarray:
-    """The four 32-bit words of Philox4x32-10 for every counter: ``(len(counters), 4)`` uint32."""
+def philox4x32(seed: int, counters, rounds: int = 10) -> np.ndarray:
+    """The four 32-bit words of Philox4x32-10 for every counter: ``(len(counters), 4)`` uint32.  (``rounds``: another
+    round count, for controls that must miss.)"""
     ctr = np.asarray(counters, dtype=np.uint64).reshape(-1)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     c = [ctr & MASK, ctr >> np.uint64(32), np.zeros_like(ctr), np.zeros_like(ctr)]
     k0, k1 = seed & 0xFFFFFFFF, seed >> 32
-    for _ in range(10):
+    for _ in range(rounds):
         p0, p1 = M0 * c[0], M1 * c[2]                       # 32 x 32 -> 64 bits, exact in uint64
         c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & MASK, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1),
              p0 & MASK]

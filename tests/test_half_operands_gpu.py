@@ -260,7 +260,7 @@ def _init_cells(n, B, T, seed):
 @pytest.mark.parametrize("B,reverse", [(1, (0,)), (1, (1,)), (65, (0,)), (65, (1,)), (130, (0,)), (130, (1,)),
                                        (256, (0, 1, 0, 1))])
 @pytest.mark.parametrize("half", HALVES)
-def test_persistent_lstm_half_step_by_step(hip_device, B, reverse, half):
+def test_persistent_lstm_half_step_by_step(hip_device, B, reverse, half, T=None):
     """pe_lstm_fwd_persistent_{bf16,f16} and pe_lstm_bwd_persistent_{bf16,f16}, one float64 step at a time from the
     kernel's own stored state.
 
@@ -276,9 +276,12 @@ def test_persistent_lstm_half_step_by_step(hip_device, B, reverse, half):
     float64.  A partial within fp32 accumulation noise of a bf16 rounding midpoint may round either way: its bf16 ulp
     is allowed (propagated to the gate gradients), and such partials must be rare.
     Also: the per-batch-tile bias-gradient rows (the ragged last tile at B = 65, 130), the gate-gradient absmax word,
-    and controls -- unrounded operands and the other half type miss the GPU result."""
+    and controls -- unrounded operands and the other half type miss the GPU result (from T = 2 on: a single step has
+    no recurrent product, so nothing is rounded and every model agrees).  ``T``: another sequence length
+    (test_persistent_lstm_half_one_cell_edges)."""
     dev = hip_device
-    n, T = len(reverse), (6 if B < 256 else 4)
+    n = len(reverse)
+    T = T if T is not None else (6 if B < 256 else 4)
     whh, xg, dyb = _init_cells(n, B, T, seed=B + n)
     ybuf = [torch.zeros(B, T, 2 * H_P, device=dev) for _ in range((n + 1) // 2)]
     col = lambda i: slice((i % 2) * H_P, (i % 2 + 1) * H_P) if n > 1 else \
@@ -307,7 +310,7 @@ def test_persistent_lstm_half_step_by_step(hip_device, B, reverse, half):
         G, C, Y = R.lstm_fwd_teacher(xg[i], y, c, whh[i], reverse[i], half)
         for got, ref in ((y, Y), (c, C), (acts[i], G)):
             close(got, ref)
-        for wrong in (None, OTHER[half]):
+        for wrong in (None, OTHER[half]) if T > 1 else ():
             assert misses(y, R.lstm_fwd_teacher(xg[i], y, c, whh[i], reverse[i], wrong)[2])
         # backward
         dy = dsl[i].cpu()
@@ -320,7 +323,7 @@ def test_persistent_lstm_half_step_by_step(hip_device, B, reverse, half):
         assert n_amb <= 0.02 * parts, (n_amb, parts)
         print(f"cell {i}: dgates err {err.max().item():.2e} of {scale:.2e}; {n_amb} of {parts} partials at a "
               f"rounding boundary")
-        for wrong, xh in ((None, None), (OTHER[half], R.XCHG_HALF)):
+        for wrong, xh in ((None, None), (OTHER[half], R.XCHG_HALF)) if T > 1 else ():
             Dw, _, _ = R.lstm_bwd_teacher(dy, acts[i], c, whh[i], reverse[i], wrong, dgates_src=dgt, xhalf=xh)
             assert not ((dgt.double() - Dw).abs() <= tol).all(), wrong
         # bias-gradient rows: column sums of this cell's gate gradients over each 64-sample batch tile
@@ -331,6 +334,16 @@ def test_persistent_lstm_half_step_by_step(hip_device, B, reverse, half):
             ref_row, mag = blk.sum((0, 1)), blk.abs().sum((0, 1))
             assert ((got_rows[bt] - ref_row).abs() <= 1e-5 * mag + 1e-30).all(), bt
         assert amx[i].item() == dgt.abs().max().view(torch.int32).item()
+
+
+@pytest.mark.parametrize("B,T", [(65, 1), (65, 2), (32, 3), (33, 3), (64, 3)])
+@pytest.mark.parametrize("reverse", [0, 1])
+@pytest.mark.parametrize("half", HALVES)
+def test_persistent_lstm_half_one_cell_edges(hip_device, B, T, reverse, half):
+    """test_persistent_lstm_half_step_by_step (its models and its bounds) on one cell at the edges of the recurrence:
+    T = 1 is the peeled step 0 alone and T = 2 adds the trailing cell update with no step between them; B = 32, 33
+    and 64 leave the second half of the 64-sample batch tile empty, with one row and full."""
+    test_persistent_lstm_half_step_by_step(hip_device, B, (reverse,), half, T=T)
 
 
 @pytest.mark.parametrize("H", [64, 384])

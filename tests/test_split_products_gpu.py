@@ -466,7 +466,7 @@ def test_h2_words_computed_inside_the_op_belong_to_their_operand(hip_device, op_
 
 # ------------------------------------------------------------------ x3 persistent LSTM (H = 384), teacher forcing
 @pytest.mark.parametrize("B,reverse", [(1, (0,)), (65, (1,)), (130, (0, 1))])
-def test_persistent_lstm_x3_step_by_step(hip_device, B, reverse, monkeypatch):
+def test_persistent_lstm_x3_step_by_step(hip_device, B, reverse, monkeypatch, T=6):
     """pe_lstm_fwd_persistent / pe_lstm_bwd_persistent (x3) one float64 step at a time from the kernel's own stored
     state (tests/half_ref.py, half=None: the x3 split rebuilds every operand and the kept products miss at most
     2^-23 of sum|w h|; the backward exchanges its partial sums as fp32).
@@ -474,10 +474,12 @@ def test_persistent_lstm_x3_step_by_step(hip_device, B, reverse, monkeypatch):
     Forward, per element: the pre-activation is off by at most d = 2^-20 (|xg| + |h_prev| |W_hh|^T) (accumulation and
     the dropped x3 products); sigmoid' <= 1/4 and tanh' <= 1, so a gate is off by <= d + 2^-21 (fp32 transcendentals),
     c by <= 3 max_gate(d) |.| + 2^-21 (1 + |c|) and h by <= 4 max_gate(d) + 2^-20.  Backward: per element within 1e-5
-    of the step's largest gate gradient (as the 16-bit test).  Control: the one-term bf16 model misses both."""
+    of the step's largest gate gradient (as the 16-bit test).  Control: the one-term bf16 model misses both (from
+    T = 2 on: a single step has no recurrent product).  ``T``: another sequence length
+    (test_persistent_lstm_x3_one_cell_edges)."""
     from tests import half_ref as R
     monkeypatch.setattr(ops, "FP32_MATMUL", "x3")
-    dev, H, T = hip_device, 384, 6
+    dev, H = hip_device, 384
     n = len(reverse)
     g = torch.Generator().manual_seed(B + n)
     whh = [(torch.rand(4 * H, H, generator=g) * 2 - 1) * H ** -0.5 for _ in range(n)]
@@ -513,7 +515,7 @@ def test_persistent_lstm_x3_step_by_step(hip_device, B, reverse, monkeypatch):
                 ((c.double() - C).abs() <= 3 * dmax + 2.0 ** -21 * (1 + C.abs())).all() and \
                 ((y.double() - Y).abs() <= 4 * dmax + 2.0 ** -20).all()
         assert fwd_ok(None), i
-        assert not fwd_ok("bf16"), i
+        assert T == 1 or not fwd_ok("bf16"), i
         dy = dsl[i].cpu()
 
         def bwd_err(half, xhalf):
@@ -522,7 +524,16 @@ def test_persistent_lstm_x3_step_by_step(hip_device, B, reverse, monkeypatch):
         err, tol = bwd_err(None, None)
         assert (err <= tol).all(), (err.max().item(), tol.max().item())
         err_w, _ = bwd_err("bf16", "bf16")
-        assert not (err_w <= tol).all()
+        assert T == 1 or not (err_w <= tol).all()
+
+
+@pytest.mark.parametrize("B,T", [(65, 1), (65, 2), (32, 3), (33, 3), (64, 3)])
+@pytest.mark.parametrize("reverse", [0, 1])
+def test_persistent_lstm_x3_one_cell_edges(hip_device, B, T, reverse, monkeypatch):
+    """test_persistent_lstm_x3_step_by_step (its models and its bounds) on one cell at the edges of the recurrence:
+    T = 1 is the peeled step 0 alone and T = 2 adds the trailing cell update with no step between them; B = 32, 33
+    and 64 leave the second half of the 64-sample batch tile empty, with one row and full."""
+    test_persistent_lstm_x3_step_by_step(hip_device, B, (reverse,), monkeypatch, T=T)
 
 
 # ------------------------------------------------------------------ amax words in a training step
