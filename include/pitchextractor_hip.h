@@ -569,6 +569,36 @@ int pe_cheaptrick(const float* x, const float* f0, const long* meta, const long*
                   int n_rows, double fs, double frame_period_ms, double q1, double f0_floor, int fft_size, float* sp,
                   void* stream);
 
+/* ---- WORLD D4C: the band aperiodicity of a recording (pyworld.d4c, WORLD's d4c.cpp) --------------------------------
+ * One frame per F0 value, frame f at f * frame_period_ms.  LoveTrain (Blackman window of 3 periods of max(F0, 40),
+ * N_l = 2^(1 + floor(log2(3 fs / 40 + 1))) points): a0 = power in [100, 4000] Hz / power in [100, 7900] Hz, 0 where
+ * F0[f] <= 0 or is not a number, or the denominator is 0.  F0[f] <= 0 or a0 <= threshold is the unvoiced verdict; so is
+ * a smoothed power spectrum that is not positive in every bin.  Otherwise, with f0 = max(47, F0[f]) and N_d = 2^(1 +
+ * floor(log2(4 fs / 47 + 1))) points: static centroid, smoothed power, static group delay, and per 3 kHz band i <
+ * bands = int(min(15000, fs / 2 - 3000) / 3000) the coarse aperiodicity in dB, min(0, . + (F0[f] - 100) / 50).
+ * float32 per frame; the window's randn is dropped; the linear smoothing is CheapTrick's interval sum.  F0 belongs
+ * below fs / 2 (it is clamped there).  PE_E_UNSUPPORTED: fs / 2 <= 7900, N_d or N_l above 4096, bands above 5,
+ * fft_size not 512 / 1024 / 2048; PE_E_ARG: a non-positive or non-finite fs or frame_period_ms, a non-finite
+ * threshold, a null pointer, n_rows outside 0 .. 65535.
+ * pe_d4c_plan (host only, no device call): pe_cheaptrick_plan's arguments and layout (frame first_frame[r] + q of row
+ * r goes to the fft_size / 2 + 1 floats at ap + out_off[r] + q * out_stride[r]); fills meta (n_rows x
+ * pe_d4c_plan_fields() int64) and totals {frames, N_d, N_l, bands, L} (L: points of the Nuttall window).
+ * pe_d4c_bands: one launch, one workgroup per (row, frame); host_meta: the host copy of meta (PE_E_ARG unless it is the
+ * plan's); table: exp(-2 pi i m / N_d) for m < N_d (re, im), then the same for N_l.  band: frames x (1 + bands)
+ * floats in plan order, {a0, coarse[0 .. bands)}; coarse is NaN in a frame with the unvoiced verdict.
+ * pe_d4c_expand: one launch; a frame's band values to its bins: the knots (0, -60), (3000 (i + 1), coarse[i]), (fs / 2,
+ * -1e-12) in dB interpolated at k fs / fft_size, ap = 10^(dB / 20); 1 - 1e-12 in every bin of an unvoiced frame.
+ * A row's frames are bit-identical alone, at any offset, padded, anywhere in a batch and in any frame sub-range. */
+int pe_d4c_plan_fields(void);
+int pe_d4c_plan(int n_rows, const long* x_off, const long* x_len, const long* f0_off, const long* f0_len,
+                const long* first_frame, const long* n_frames, const long* out_off, const long* out_stride, double fs,
+                double frame_period_ms, int fft_size, long* meta, long* totals);
+int pe_d4c_bands(const float* x, const float* f0, const long* meta, const long* host_meta, const float* table,
+                 int n_rows, double fs, double frame_period_ms, double threshold, int fft_size, float* band,
+                 void* stream);
+int pe_d4c_expand(const float* band, const long* meta, const long* host_meta, int n_rows, double fs, int fft_size,
+                  float* ap, void* stream);
+
 /* ---- F0 bin decoding (build-defined; the inverse of pe_f0_bins_ce_loss) and pitch metrics --------------------
  * logits: N sequences of T frames of C bins, frame (n, t) at logits + n * ld_n + t * ld_t (2 <= C <= 1024, more is
  * PE_E_UNSUPPORTED).  Bin b stands for cents(b) = 20 b + 1997.3794084376191, f(b) = 10 * 2^(cents(b) / 1200) Hz.

@@ -289,7 +289,7 @@ class WorldResynthesis:
     file draw; ``generate`` returns None when every attempt failed."""
     name, Request, Batch = "world_resynthesis", ResynthesisRequest, ResynthesisBatch
     KEYS = ("enabled", "backend", "semitones", "gain_db_range", "noise_db", "min_voiced_fraction", "max_attempts",
-            "modulation", "aperiodicity", "q1")
+            "modulation", "aperiodicity", "d4c_threshold", "q1")
     MODULATION_KEYS = ("vibrato_probability", "vibrato_semitones", "vibrato_rate_range")
 
     def check_config(self, ds, cfg):
@@ -303,9 +303,21 @@ class WorldResynthesis:
         gain = _gain_range(cfg.get("gain_db_range", [-6.0, 3.0]))
         if gain is not None and len(gain) != 2:
             raise ValueError("world_resynthesis: gain_db_range must provide two values")
-        aperiodicity = float(cfg.get("aperiodicity", 0.0))
-        if not 0.0 <= aperiodicity < 1.0:
-            raise ValueError("world_resynthesis: aperiodicity must lie in [0, 1)")
+        aperiodicity = cfg.get("aperiodicity", 0.0)
+        if isinstance(aperiodicity, str):
+            if aperiodicity != "d4c":
+                raise ValueError(f"world_resynthesis: aperiodicity {aperiodicity!r} is neither a number nor 'd4c'")
+            if not 15800 < ds.sr <= 48000:
+                raise ValueError("world_resynthesis: aperiodicity 'd4c' needs a sample rate above 15.8 kHz (its "
+                                 "voicing test reads up to 7.9 kHz) and of 48 kHz at the most")
+        else:
+            aperiodicity = float(aperiodicity)
+            if not 0.0 <= aperiodicity < 1.0:
+                raise ValueError("world_resynthesis: aperiodicity must lie in [0, 1)")
+        # 0, not pyworld's 0.85: a frame the label calls voiced keeps a periodic part
+        d4c_threshold = float(cfg.get("d4c_threshold", 0.0))
+        if not 0.0 <= d4c_threshold < 1.0:
+            raise ValueError("world_resynthesis: d4c_threshold must lie in [0, 1)")
         rate = tuple(float(v) for v in mod.get("vibrato_rate_range", (4.0, 7.0)))
         if len(rate) != 2:
             raise ValueError("world_resynthesis: vibrato_rate_range must provide two values")
@@ -317,7 +329,7 @@ class WorldResynthesis:
                 "max_attempts": max(1, int(cfg.get("max_attempts", 5))),
                 "vibrato_probability": float(mod.get("vibrato_probability", 0.6)),
                 "vibrato_semitones": float(mod.get("vibrato_semitones", 0.35)), "vibrato_rate_range": rate,
-                "aperiodicity": aperiodicity, "q1": float(cfg.get("q1", CHEAPTRICK_Q1)),
+                "aperiodicity": aperiodicity, "d4c_threshold": d4c_threshold, "q1": float(cfg.get("q1", CHEAPTRICK_Q1)),
                 "fft_size": check_fft_size(cheaptrick_fft_size(ds.sr)), "frame_period": 1000.0 * hop / ds.sr}
 
     def generate(self, ds):
@@ -372,12 +384,15 @@ class WorldResynthesis:
         cfg = loader.dataset.synthetic_resynthesis_config
         src = _base_files_at_model_rate(loader, pack.src, host.src_sr.tolist(), host.src_len.tolist())
         ap = None
-        if cfg["aperiodicity"] > 0:
+        if cfg["aperiodicity"] == "d4c":
+            ap = "d4c"                                           # the window's frames, analysed after CheapTrick
+        elif cfg["aperiodicity"] > 0:
             ap = torch.full((cfg["fft_size"] // 2 + 1,), cfg["aperiodicity"], dtype=torch.float32, device=waves.device)
         resynthesize_ragged(src, host.n.tolist(), pack.base.split([len(c) for c in host.curves]), host.curves,
                             loader.mel.sample_rate, cfg["frame_period"], ap=ap, seeds=host.seeds, gains=pack.gains,
                             out=waves, out_rows=host.rows.numpy(), out_start=host.out_start, out_noise=pack.noise,
-                            out_len=host.out_len.numpy(), tables=host.tables, q1=cfg["q1"], fft_size=cfg["fft_size"])
+                            out_len=host.out_len.numpy(), tables=host.tables, q1=cfg["q1"], fft_size=cfg["fft_size"],
+                            d4c_threshold=cfg.get("d4c_threshold", 0.0))
         return waves, lengths
 
 

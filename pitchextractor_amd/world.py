@@ -18,6 +18,12 @@ curve it was synthesized from (``label_curve``), which is exact by construction.
 float32 per-frame arithmetic, the two ``randn`` safeguards dropped or replaced by their scale, and the linear smoothing
 as a sum over the covered bins instead of a cumulative-sum difference.  Parity with pyworld's binary is unpinned here
 too; the yardstick is ``tests/cheaptrick_ref.py``.
+
+And WORLD's D4C (``pyworld.d4c``), the band aperiodicity of a recording (``d4c``, ``d4c_ragged``, ``csrc/d4c.hip``),
+which ``resynthesize(..., ap="d4c")`` hands to the synthesizer in place of a constant template.  Stated deviations:
+float32 per-frame arithmetic with the smoothing sums accumulated in double, the window's ``randn`` dropped (a silent
+window is unvoiced), the linear smoothing as for CheapTrick.  Unpinned as well; the yardstick is ``tests/d4c_ref.py``
+(DESIGN.md section 24).
 """
 from __future__ import annotations
 
@@ -346,8 +352,9 @@ def cheaptrick_floor(fs, fft_size: int) -> float:
 
 
 class Envelopes(NamedTuple):
-    """What ``cheaptrick_ragged`` returns: frame ``first[r] + q`` of row r is the ``bins`` floats of the flat float32
-    device tensor ``sp`` at ``offsets[r] + q * strides[r]``, for ``q < counts[r]``."""
+    """What ``cheaptrick_ragged`` and ``d4c_ragged`` return: frame ``first[r] + q`` of row r is the ``bins`` floats of
+    the flat float32 device tensor ``sp`` (the envelopes, or D4C's aperiodicities) at ``offsets[r] + q * strides[r]``,
+    for ``q < counts[r]``."""
     sp: torch.Tensor
     offsets: np.ndarray
     strides: np.ndarray
@@ -364,6 +371,39 @@ class Envelopes(NamedTuple):
         return self.offsets - self.first * self.strides
 
 
+def _frame_plan(who, plan_fn, x, lengths, f0s, frames, out, out_offsets, out_strides, fft_size, config, n_totals=1):
+    """The host layout both frame analyses share: the rows of ``x``, their packed F0 curves, the frames asked for and
+    where they go, through the C plan ``plan_fn`` (``config``: its arguments between ``out_stride`` and ``meta``).
+    Returns ``(R, f0_d, meta, totals, out, Envelopes)`` with ``out`` made, or checked against what the plan addresses."""
+    check_waves(x, who)
+    lengths, offsets = row_layout(x, lengths, whole_by_default=True)
+    R = len(lengths)
+    bins = fft_size // 2 + 1
+    f0s = list(f0s)
+    if len(f0s) != R:
+        raise ValueError(f"{who}: one F0 curve per row")
+    f0_d, f0_off, f0_len = pack_tracks(f0s, x.device)
+    first = np.zeros(R, np.int64) if frames is None else _i64([fr[0] for fr in frames], R)
+    counts = _i64(f0_len, R) - first if frames is None else _i64([fr[1] for fr in frames], R)
+    strides = np.full(R, bins, np.int64) if out_strides is None else _i64(out_strides, R)
+    if out_offsets is None:
+        out_offsets = np.cumsum(counts * strides) - counts * strides
+    out_offsets = _i64(out_offsets, R)
+    meta = plan_meta(plan_fn + "_fields", R)
+    totals = np.zeros(n_totals, np.int64)
+    _lib.check(getattr(_lib.load(), plan_fn)(
+        R, *host_ptrs(i64(offsets), i64(lengths), i64(f0_off), i64(f0_len), first, counts, out_offsets, strides),
+        *config, *host_ptrs(meta, totals)), plan_fn)
+    need = int((out_offsets + np.maximum(counts - 1, 0) * strides + bins)[counts > 0].max(initial=0))
+    if out is None:
+        out = torch.empty((max(need, 1),), dtype=torch.float32, device=x.device)
+    else:
+        check_device_tensor(out, who)
+        if out.numel() < need:
+            raise ValueError(f"{who}: the output is smaller than the plan addresses")
+    return R, f0_d, meta, totals, out, Envelopes(out, out_offsets, strides, first, counts, fft_size)
+
+
 def cheaptrick_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5.0, *, q1: float = CHEAPTRICK_Q1,
                       f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None, frames=None,
                       out: torch.Tensor | None = None, out_offsets=None, out_strides=None) -> Envelopes:
@@ -374,32 +414,11 @@ def cheaptrick_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5
     device tensor to write into, at ``out_offsets[r] + q * out_strides[r]`` (default: the rows' frames back to back in a
     new tensor).  There is no CPU path."""
     check_waves(x, "CheapTrick")
-    lengths, offsets = row_layout(x, lengths, whole_by_default=True)
-    R = len(lengths)
     fft_size = check_fft_size(cheaptrick_fft_size(fs, f0_floor) if fft_size is None else fft_size)
     bins = fft_size // 2 + 1
-    f0s = list(f0s)
-    if len(f0s) != R:
-        raise ValueError("CheapTrick: one F0 curve per row")
-    f0_d, f0_off, f0_len = pack_tracks(f0s, x.device)
-    first = np.zeros(R, np.int64) if frames is None else _i64([fr[0] for fr in frames], R)
-    counts = _i64(f0_len, R) - first if frames is None else _i64([fr[1] for fr in frames], R)
-    strides = np.full(R, bins, np.int64) if out_strides is None else _i64(out_strides, R)
-    if out_offsets is None:
-        out_offsets = np.cumsum(counts * strides) - counts * strides
-    out_offsets = _i64(out_offsets, R)
-    meta = plan_meta("pe_cheaptrick_plan_fields", R)
-    totals = np.zeros(1, np.int64)
-    _lib.check(_lib.load().pe_cheaptrick_plan(
-        R, *host_ptrs(i64(offsets), i64(lengths), i64(f0_off), i64(f0_len), first, counts, out_offsets, strides),
-        float(fs), float(frame_period), float(f0_floor), fft_size, *host_ptrs(meta, totals)), "pe_cheaptrick_plan")
-    need = int((out_offsets + np.maximum(counts - 1, 0) * strides + bins)[counts > 0].max(initial=0))
-    if out is None:
-        out = torch.empty((max(need, 1),), dtype=torch.float32, device=x.device)
-    else:
-        check_device_tensor(out, "CheapTrick")
-        if out.numel() < need:
-            raise ValueError("CheapTrick: the output is smaller than the plan addresses")
+    R, f0_d, meta, totals, out, env = _frame_plan(
+        "CheapTrick", "pe_cheaptrick_plan", x, lengths, f0s, frames, out, out_offsets, out_strides, fft_size,
+        (float(fs), float(frame_period), float(f0_floor), fft_size))
     if R and int(totals[0]):
         meta_d = torch.from_numpy(meta).to(x.device)
         with torch.cuda.device(x.device):
@@ -407,7 +426,7 @@ def cheaptrick_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5
                       _SYNTH.table(fft_size, x.device).data_ptr(), R, float(fs), float(frame_period), float(q1),
                       float(f0_floor), fft_size, out.data_ptr(), _lib.stream_ptr(),
                       work=float(int(totals[0]) * (bins * 4 + 3 * fft_size * 4)))
-    return Envelopes(out, out_offsets, strides, first, counts, fft_size)
+    return env
 
 
 def cheaptrick(x: torch.Tensor, f0, fs, frame_period: float = 5.0, *, q1: float = CHEAPTRICK_Q1,
@@ -421,6 +440,56 @@ def cheaptrick(x: torch.Tensor, f0, fs, frame_period: float = 5.0, *, q1: float 
     return env.row(0)
 
 
+# --------------------------------------------------------------------------- D4C: the band aperiodicity of a recording
+D4C_THRESHOLD = 0.85
+
+
+def _d4c_table(n_d: int, n_l: int, device) -> torch.Tensor:
+    """The N_d-th roots of unity, then the N_l-th (LoveTrain's transform), as ``pe_d4c_bands`` reads them."""
+    return _lib.device_table(("d4c", n_d, n_l), device,
+                             lambda: np.concatenate([fft_roots(n_d).reshape(-1), fft_roots(n_l).reshape(-1)]))
+
+
+def d4c_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5.0, *, threshold: float = D4C_THRESHOLD,
+               fft_size: int | None = None, frames=None, out: torch.Tensor | None = None, out_offsets=None,
+               out_strides=None, return_bands: bool = False):
+    """WORLD's D4C for a ragged batch, two launches (the band analysis, then its expansion to bins).  The arguments are
+    ``cheaptrick_ragged``'s, and so is the layout returned: an ``Envelopes`` whose ``sp`` holds the aperiodicity, ``bins
+    = fft_size / 2 + 1`` floats in (0, 1] per frame (``fft_size`` defaults to CheapTrick's for ``fs``).  ``threshold``:
+    LoveTrain's; a frame with ``a0 <= threshold`` is all ``1 - 1e-12``.  With ``return_bands`` also the ``(frames, 1 +
+    bands)`` float32 device tensor of the analysed frames in row order: ``a0``, then the bands' coarse aperiodicity in
+    dB (NaN where the frame has the unvoiced verdict).  There is no CPU path."""
+    check_waves(x, "D4C")
+    fft_size = check_fft_size(cheaptrick_fft_size(fs) if fft_size is None else fft_size)
+    threshold = float(threshold)
+    if not math.isfinite(threshold):
+        raise ValueError("D4C: threshold must be finite")
+    R, f0_d, meta, totals, out, env = _frame_plan(
+        "D4C", "pe_d4c_plan", x, lengths, f0s, frames, out, out_offsets, out_strides, fft_size,
+        (float(fs), float(frame_period), fft_size), n_totals=5)
+    n_frames, n_d, n_l, n_bands, _ = (int(v) for v in totals)
+    bands = torch.empty((max(n_frames, 1), 1 + n_bands), dtype=torch.float32, device=x.device)
+    if R and n_frames:
+        meta_d = torch.from_numpy(meta).to(x.device)
+        with torch.cuda.device(x.device):
+            ops._call("pe_d4c_bands", x.data_ptr(), f0_d.data_ptr(), meta_d.data_ptr(), meta.ctypes.data,
+                      _d4c_table(n_d, n_l, x.device).data_ptr(), R, float(fs), float(frame_period), threshold,
+                      fft_size, bands.data_ptr(), _lib.stream_ptr(), work=float(n_frames * 8 * n_d * 4))
+            ops._call("pe_d4c_expand", bands.data_ptr(), meta_d.data_ptr(), meta.ctypes.data, R, float(fs), fft_size,
+                      out.data_ptr(), _lib.stream_ptr(), work=float(n_frames * (fft_size // 2 + 1) * 4))
+    return (env, bands[:n_frames]) if return_bands else env
+
+
+def d4c(x: torch.Tensor, f0, fs, frame_period: float = 5.0, *, threshold: float = D4C_THRESHOLD,
+        fft_size: int | None = None) -> torch.Tensor:
+    """pyworld's ``d4c(x, f0, t, fs)`` on the device for ``t = arange(len(f0)) * frame_period`` ms: ``x`` a 1-D float32
+    device wave, ``f0`` its curve (0 = unvoiced).  Returns the ``(len(f0), fft_size / 2 + 1)`` float32 aperiodicity;
+    ``fft_size`` defaults to CheapTrick's for ``fs``."""
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise RuntimeError("D4C (HIP) needs a 1-D float32 device wave; no CPU fallback exists")
+    return d4c_ragged(x, None, [f0], fs, frame_period, threshold=threshold, fft_size=fft_size).row(0)
+
+
 def label_curve(new_f0, fs, fft_size: int) -> np.ndarray:
     """The curve a resynthesized item is labelled with: ``new_f0`` (float64) with every frame the synthesizer does not
     voice (``new_f0 <= lowest_f0(fs, fft_size)``) set to 0.  The synthesizer is driven with this curve."""
@@ -432,10 +501,13 @@ def label_curve(new_f0, fs, fft_size: int) -> np.ndarray:
 def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period: float, *, ap=None, seeds=None,
                         noise=None, noise_offsets=None, gains=None, out: torch.Tensor | None = None, out_rows=None,
                         out_start=None, out_len=None, out_noise=None, tables=None, q1: float = CHEAPTRICK_Q1,
-                        f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None):
+                        f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None,
+                        d4c_threshold: float = D4C_THRESHOLD):
     """Analysis / resynthesis of a ragged batch: the envelope of row r of ``x`` under ``f0s[r]``
     (``cheaptrick_ragged``), then ``world_synthesize_ragged`` driven by ``label_curve(new_f0s[r])`` reading that
-    envelope in place.  ``ap``: ``None`` or one ``(bins,)`` float32 device template for every row and frame.  With
+    envelope in place.  ``ap``: ``None``, one ``(bins,)`` float32 device template for every row and frame, or the
+    string ``"d4c"``: the recording's own aperiodicity (``d4c_ragged`` with ``d4c_threshold`` on the frames CheapTrick
+    analyses, into a buffer of the same layout that the synthesizer reads in place).  With
     windows (``out_start`` / ``out_len``) only the frames their pulses read are analysed: the samples of the window -+
     ``fft_size / 2``, and one frame either side for the synthesizer's frame interpolation.  The other arguments are
     ``world_synthesize_ragged``'s. Returns ``(out, labels)``, ``labels[r]`` the float64 label curve of row r."""
@@ -447,7 +519,10 @@ def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period
     f0s = list(f0s)
     if len(f0s) != R or len(labels) != R or any(len(a) != b.size for a, b in zip(f0s, labels)):
         raise ValueError("WORLD resynthesis: one F0 curve and one new curve of the same length per row")
-    if ap is not None and tuple(ap.shape) != (bins,):
+    estimate = isinstance(ap, str)
+    if estimate and ap != "d4c":
+        raise ValueError(f"WORLD resynthesis: ap {ap!r} is not a mode; the one estimator is 'd4c'")
+    if ap is not None and not estimate and tuple(ap.shape) != (bins,):
         raise ValueError(f"WORLD resynthesis: ap must be one ({bins},) template")
     n_frames = np.array([b.size for b in labels], np.int64)
     y_len = np.array([output_length(n, fs, frame_period) for n in n_frames], np.int64)
@@ -464,19 +539,25 @@ def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period
     sp = torch.empty((max(int((n_frames * bins).sum()), 1),), dtype=torch.float32, device=x.device)
     env = cheaptrick_ragged(x, lengths, f0s, fs, frame_period, q1=q1, f0_floor=f0_floor, fft_size=fft_size,
                             frames=list(zip(lo, hi - lo)), out=sp, out_offsets=base + lo * bins)
+    ap_offsets = ap_strides = None if ap is None else [0] * R
+    if estimate:
+        ap = d4c_ragged(x, lengths, f0s, fs, frame_period, threshold=d4c_threshold, fft_size=fft_size,
+                        frames=list(zip(lo, hi - lo)), out=torch.empty_like(sp), out_offsets=base + lo * bins).sp
+        ap_offsets, ap_strides = env.frame0_offsets(), env.strides
     world_synthesize_ragged(labels, env.sp, env.frame0_offsets(), env.strides,
                             torch.ones(R) if gains is None else gains, out, out_rows, out_start, out_len, fs=fs,
-                            frame_period=frame_period, fft_size=fft_size, ap=ap,
-                            ap_offsets=None if ap is None else [0] * R, ap_strides=None if ap is None else [0] * R,
+                            frame_period=frame_period, fft_size=fft_size, ap=ap, ap_offsets=ap_offsets,
+                            ap_strides=ap_strides,
                             tables=tables, noise=noise, noise_offsets=noise_offsets, seeds=seeds, out_noise=out_noise)
     return out, labels
 
 
-def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, ap: torch.Tensor | None = None,
-                 seed: int = 0, noise: torch.Tensor | None = None, q1: float = CHEAPTRICK_Q1,
-                 f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None):
+def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, ap=None, seed: int = 0,
+                 noise: torch.Tensor | None = None, q1: float = CHEAPTRICK_Q1, f0_floor: float = CHEAPTRICK_F0_FLOOR,
+                 fft_size: int | None = None, d4c_threshold: float = D4C_THRESHOLD):
     """The recording ``x`` (1-D float32 device wave with the curve ``f0``) resynthesized on ``new_f0``: its CheapTrick
-    envelope through WORLD's ``Synthesis``.  Returns ``(audio, label)``: the 1-D float32 device wave of
+    envelope through WORLD's ``Synthesis``, with no aperiodicity (``ap=None``), one ``(bins,)`` template, or the
+    recording's own as D4C estimates it (``ap="d4c"``, ``d4c_threshold``).  Returns ``(audio, label)``: the 1-D float32 device wave of
     ``int(len(f0) * frame_period * fs / 1000)`` samples and the float64 host curve it was synthesized from
     (``label_curve``), exact by construction."""
     if not torch.is_tensor(x) or x.dim() != 1:
@@ -487,7 +568,7 @@ def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, 
     out, labels = resynthesize_ragged(x, None, [f0], [new_f0], fs, frame_period, ap=ap, seeds=[seed],
                                       noise=None if noise is None else noise.reshape(-1),
                                       noise_offsets=None if noise is None else [0], q1=q1, f0_floor=f0_floor,
-                                      fft_size=fft_size)
+                                      fft_size=fft_size, d4c_threshold=d4c_threshold)
     return out[0, :n], labels[0]
 
 
