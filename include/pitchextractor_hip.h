@@ -768,6 +768,9 @@ int pe_stress_biquad(const float* x, const long* meta, const long* host_meta, in
                      int n_stages, float* y, void* stream);
 int pe_stress_clip(const float* x, const long* meta, const long* host_meta, int n_rows, double q, int copy, float* y,
                    float* thresholds, void* stream);
+int pe_stress_clip_rows(const float* x, const long* meta, const long* host_meta, int n_rows, const double* q,
+                        const double* host_q, const int* copy, const int* host_copy, float* y, float* thresholds,
+                        void* stream);
 size_t pe_stress_agc_workspace_bytes(long samples);
 int pe_stress_agc(const float* x, const long* meta, const long* host_meta, int n_rows, const double* params4,
                   int smoothing, float* y, void* workspace, size_t workspace_bytes, void* stream);
@@ -921,6 +924,29 @@ int pe_rir_synth(const long* meta, const long* host_meta, const double* params, 
                  const long* tiles, const long* host_tiles, int n_rows, float* y, long n_y, void* stream);
 int pe_rir_decay(const float* h, long n_h, const long* meta, const long* host_meta, int meta_fields, int n_rows,
                  double fs, double lo_db, double hi_db, double* out6, float* curve, void* stream);
+
+/* ---- Training-time augmentation: per-row biquad cascades as a parallel scan, ragged batches -------------------------
+ * pe_augment_biquad: row r (any row plan: meta_fields int64 per row, opening with offset and length; host_meta its host
+ * copy) of x runs through its own cascade of n_stages[r] in 0 .. 8 biquads and is written to y at the same offset;
+ * y == x (in place) is allowed.  sos (device, n_rows x 8 x 5 doubles; host_sos its host copy) = per row and stage
+ * {b0, b1, b2, a1, a2} with a0 = 1; the stages past n_stages[r] are not read by the checks and not used.  The float32
+ * input is widened to double, the stages are chained in double in transposed direct form II (y = b0 x + z1; z1 = b1 x
+ * - a1 y + z2; z2 = b2 x - a2 y) from a zero state without a clamp or a rounding between them, and the result is
+ * rounded once to float32: scipy.signal.sosfilt in float64 and a cast.  No stages is a copy.  One launch, one workgroup
+ * per row, a parallel scan over pieces of the row (csrc/augment.hip); a row's output is bit-identical alone, packed at
+ * any offset, padded, in place, and beside any other rows.  Checked before any device call, PE_E_ARG: a null pointer,
+ * meta_fields < 2, a negative offset or length, n_stages outside 0 .. 8, a non-finite coefficient of a used stage, a
+ * used stage whose poles lie outside the stability triangle (|a2| < 1, |a1| < 1 + a2) or whose pole radius exceeds
+ * 1 - 2^-12 (what the error bound 2^-24 |y| + 2^-26 max |y| of the row stands on).  No workspace.
+ * pe_augment_biquad_consts (host only): consts3 = {samples of a lane's piece, samples of a workgroup's block, 8}.
+ * pe_augment_gain: y = float32(x gains[r]) over row r (gain and polarity in one multiply; y == x is allowed; gains on the
+ * device, host_gains its host copy, PE_E_ARG unless every one is finite).  One launch. */
+int pe_augment_biquad_consts(long* consts3);
+int pe_augment_gain(const float* x, const long* meta, const long* host_meta, int meta_fields, int n_rows,
+                    const float* gains, const float* host_gains, float* y, void* stream);
+int pe_augment_biquad(const float* x, const long* meta, const long* host_meta, int meta_fields, int n_rows,
+                      const double* sos, const double* host_sos, const int* n_stages, const int* host_n_stages,
+                      float* y, void* stream);
 
 #ifdef __cplusplus
 }

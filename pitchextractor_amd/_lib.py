@@ -174,6 +174,7 @@ PROTOTYPES = {
     "pe_stress_rir": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _l, _p, _p, _z, _p]),
     "pe_stress_biquad": (_i, [_p, _p, _p, _i, _p, _i, _p, _p]),
     "pe_stress_clip": (_i, [_p, _p, _p, _i, _d, _i, _p, _p, _p]),
+    "pe_stress_clip_rows": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "pe_stress_agc_workspace_bytes": (_z, [_l]),
     "pe_stress_agc": (_i, [_p, _p, _p, _i, _p, _i, _p, _p, _z, _p]),
     "pe_melody_metrics_fields": (_i, []),
@@ -201,6 +202,9 @@ PROTOTYPES = {
     "pe_rir_plan": (_i, [_i, _p, _p, _p, _p, _p, _l, _p]),
     "pe_rir_synth": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _l, _p]),
     "pe_rir_decay": (_i, [_p, _l, _p, _p, _i, _i, _d, _d, _d, _p, _p, _p]),
+    "pe_augment_biquad_consts": (_i, [_p]),
+    "pe_augment_biquad": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "pe_augment_gain": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
 }
 
 

@@ -248,15 +248,19 @@ __global__ __launch_bounds__(64) void stress_biquad_kernel(const float* __restri
 // ---- clip ----------------------------------------------------------------------------------------------------------
 // copy != 0: y = x.  Else thr = numpy's linear quantile of |x| at q, in the arithmetic numpy 2 uses for a float32
 // array and a Python float q: everything in float32 (q itself, the virtual index (n - 1) q, the weight, the
-// interpolation).  thr <= 0: y = x, else y = clip(x, -thr, thr).  thr_out[row] = thr (NaN for a copy).
+// interpolation).  thr <= 0: y = x, else y = clip(x, -thr, thr).  thr_out[row] = thr (NaN for a copy).  q_rows and
+// copy_rows (pe_stress_clip_rows; null: q and copy serve every row) hold one q and one copy per row.
 __global__ __launch_bounds__(kThreads) void stress_clip_kernel(const float* __restrict__ x,
                                                                const long* __restrict__ meta, float q, int copy,
+                                                               const double* __restrict__ q_rows,
+                                                               const int* __restrict__ copy_rows,
                                                                float* __restrict__ y, float* __restrict__ thr_out) {
 #pragma clang fp contract(off)
   __shared__ unsigned s_hist[256];
   __shared__ unsigned s_sel[3];             // digit, rank inside the digit, count of the digit
   __shared__ unsigned s_min;
   const int tid = threadIdx.x;
+  if (q_rows) { q = (float)q_rows[blockIdx.x]; copy = copy_rows[blockIdx.x]; }
   const long* m = meta + (long)blockIdx.x * S_K;
   const long n = m[S_N];
   const float* xr = x + m[S_XOFF];
@@ -587,7 +591,22 @@ extern "C" int pe_stress_clip(const float* x, const long* meta, const long* host
   PE_OPEN(open_batch(n_rows, host_meta, tot));
   if (!x || !meta || !y) return PE_E_ARG;
   hipLaunchKernelGGL(stress_clip_kernel, dim3(n_rows), dim3(kThreads), 0, pe_stream(stream), x, meta, (float)q,
-                     copy ? 1 : 0, y, thresholds);
+                     copy ? 1 : 0, nullptr, nullptr, y, thresholds);
+  PE_LAUNCH_CHECK();
+  return PE_OK;
+}
+
+extern "C" int pe_stress_clip_rows(const float* x, const long* meta, const long* host_meta, int n_rows, const double* q,
+                                   const double* host_q, const int* copy, const int* host_copy, float* y,
+                                   float* thresholds, void* stream) {
+  long tot[2];
+  PE_OPEN(open_batch(n_rows, host_meta, tot));
+  if (!host_q || !host_copy) return PE_E_ARG;
+  for (int r = 0; r < n_rows; ++r)
+    if (!host_copy[r] && !(host_q[r] >= 0.0 && host_q[r] <= 1.0)) return PE_E_ARG;
+  if (!x || !meta || !q || !copy || !y) return PE_E_ARG;
+  hipLaunchKernelGGL(stress_clip_kernel, dim3(n_rows), dim3(kThreads), 0, pe_stream(stream), x, meta, 0.f, 0, q, copy, y,
+                     thresholds);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }

@@ -46,6 +46,10 @@ deleted (the reference clears every cache of the dataset on the first mismatch, 
 (meldataset.py:621-627 -> ``pitchextractor_amd.resample``) right before the mel launch; a batch may mix source
 rates: it is then resampled by one ragged launch at each row's own rate (``RaggedResampler``), every row bit-identical
 to resampling that item alone.
+``dataset_config["augmentation"]`` (not a key of the reference) is taken out by ``build_dataloader`` before the dataset
+is built and becomes the loader's ``augment.Augmenter``: reverb, noise, a per-row biquad cascade, clipping, gain and
+polarity on the device after the stages above and before the mel launch, drawn from a generator of its own; without
+the key, or with ``enabled: false``, every batch is what it was.  Rows with a cached spectrogram are not augmented.
 """
 from __future__ import annotations
 
@@ -892,9 +896,10 @@ class DeviceMelLoader:
     """Iterates a host DataLoader of raw-audio batches and yields the reference's batch tuple
     ``(mels (B,1,80,192), f0s, is_silences)`` with the mel computed on the GPU in one launch."""
 
-    def __init__(self, loader: DataLoader, mel: MelSpectrogram, device):
+    def __init__(self, loader: DataLoader, mel: MelSpectrogram, device, augmenter=None):
         self.loader, self.mel, self.device = loader, mel, torch.device(device)
         self.dataset = loader.dataset
+        self.augmenter = augmenter                 # augment.Augmenter or None: the stage ahead of the mel launch
         self._ragged = RaggedResampler(mel.sample_rate)
         self._h2d, self._host = None, []
 
@@ -942,11 +947,22 @@ class DeviceMelLoader:
             # one ragged launch, each row at its own rate and bit-identical to that item resampled alone; synthetic
             # rows are left zero (length 0): their stages write them, and resample their base files themselves
             synthetic = {i for t in host_batches.values() for i in t.rows.tolist()}
-            waves, lengths = self._ragged(waves, [r or sr for r in rates],
-                                          [0 if i in synthetic else int(n) for i, n in enumerate(host_lengths)])
+            host_lengths = [0 if i in synthetic else int(n) for i, n in enumerate(host_lengths)]
+            waves, lengths = self._ragged(waves, [r or sr for r in rates], host_lengths)
+            host_lengths = [self._ragged.out_len(r or sr, n) for r, n in zip(rates, host_lengths)]
         for kind in synthetic_items.KINDS:                    # after the resampler, before the one mel launch
             if kind.Batch in batches:
                 waves, lengths = self._run_stage(kind, waves, lengths, *batches[kind.Batch], src_sr)
+        if self.augmenter is not None and self.augmenter.active:
+            # the whole rows at their lengths after the stages above; labels, crops and cached mels are not touched
+            synthetic = [i for t in host_batches.values() for i in t.rows.tolist()]
+            for t in host_batches.values():
+                for i, n in zip(t.rows.tolist(), t.out_len.tolist()):
+                    host_lengths[i] = int(n)
+            plan = self.augmenter.draw(len(host_lengths))
+            if synthetic and not self.augmenter.config["apply_to_synthetic"]:
+                plan = plan.without(synthetic)
+            waves = self.augmenter.apply(waves, host_lengths, plan)
         mels = self.mel.log_mel_ragged(waves, lengths, crops, max_frames=MAX_MEL_LENGTH)
         if cached:                                            # rows whose spectrogram came from <wav>_mel.npy
             rows, cached_mels = cached
@@ -973,6 +989,7 @@ def build_dataloader(path_list, validation=False, batch_size=4, num_workers=1, d
     of a per-epoch permutation) instead of the single-process shuffle."""
     dataset_config = dict(dataset_config or {})
     dataloader_options = dataset_config.pop("dataloader", {}) or {}
+    augmentation = dataset_config.pop("augmentation", None)      # the device stage's block: the dataset never sees it
     if torch.device(device).type != "cuda":
         raise RuntimeError("build_dataloader (HIP path): device must be a HIP ('cuda') device; the mel stage has "
                            "no CPU fallback")
@@ -1001,4 +1018,13 @@ def build_dataloader(path_list, validation=False, batch_size=4, num_workers=1, d
         kwargs["persistent_workers"] = bool(dataloader_options["persistent_workers"])
     if dataloader_options.get("prefetch_factor") is not None and num_workers > 0:
         kwargs["prefetch_factor"] = int(dataloader_options["prefetch_factor"])
-    return DeviceMelLoader(DataLoader(dataset, **kwargs), dataset.to_melspec, device)
+    augmenter = None
+    if augmentation is not None:
+        from .augment import Augmenter
+        augmenter = Augmenter(augmentation, dataset.sr, seed=int((augmentation or {}).get("seed", 0)),
+                              rank=int(shard[0]) if shard is not None else 0)
+        if not augmenter.active or (validation and not augmenter.config["apply_to_validation"]):
+            augmenter = None
+        else:
+            augmenter.prepare(device)
+    return DeviceMelLoader(DataLoader(dataset, **kwargs), dataset.to_melspec, device, augmenter)

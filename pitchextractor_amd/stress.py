@@ -260,6 +260,26 @@ def apply_sample_clipping(x: torch.Tensor, percent: float, lengths=None, return_
     return _clip(x, lengths, q, percent <= 0, "apply_sample_clipping", return_threshold)
 
 
+def apply_sample_clipping_rows(x: torch.Tensor, percents, lengths=None, return_threshold: bool = False):
+    """``apply_sample_clipping`` with one ``percent`` per row in one launch (``pe_stress_clip_rows``, the same kernel):
+    row r is bit for bit ``apply_sample_clipping(row, percents[r])``, a copy for ``percents[r] <= 0``."""
+    pl, y = _batch(x, lengths, "apply_sample_clipping_rows")
+    R = pl["rows"]
+    percent = per_row(percents, R, "apply_sample_clipping_rows: one percent per row", np.float64)
+    if not np.all(np.isfinite(percent)):
+        raise ValueError("apply_sample_clipping_rows: percent must be finite")
+    q = np.maximum(0.0, 1.0 - percent / 100.0)
+    copy = (percent <= 0).astype(np.int32)
+    thr = torch.full((max(R, 1),), float("nan"), dtype=torch.float32, device=x.device)
+    if R and pl["n_samples"]:
+        q_d, copy_d = torch.from_numpy(q).to(x.device), torch.from_numpy(copy).to(x.device)
+        with torch.cuda.device(x.device):
+            ops._call("pe_stress_clip_rows", x.data_ptr(), pl["meta_d"].data_ptr(), pl["meta"].ctypes.data, R,
+                      q_d.data_ptr(), q.ctypes.data, copy_d.data_ptr(), copy.ctypes.data, y.data_ptr(), thr.data_ptr(),
+                      _lib.stream_ptr())
+    return (y, thr[:R]) if return_threshold else y
+
+
 def apply_agc_pumping(x: torch.Tensor, level_db: float, sr: int, target_rms: float = 0.15, lengths=None) -> torch.Tensor:
     """The notebook's ``apply_agc_pumping``: envelope follower, gain towards ``target_rms`` within +- depth, moving
     average of the gains, product, clip.  A copy for ``level_db <= 0``.  ``ValueError`` for a row shorter than the
