@@ -576,13 +576,16 @@ int pe_cheaptrick(const float* x, const float* f0, const long* meta, const long*
  * a smoothed power spectrum that is not positive in every bin.  Otherwise, with f0 = max(47, F0[f]) and N_d = 2^(1 +
  * floor(log2(4 fs / 47 + 1))) points: static centroid, smoothed power, static group delay, and per 3 kHz band i <
  * bands = int(min(15000, fs / 2 - 3000) / 3000) the coarse aperiodicity in dB, min(0, . + (F0[f] - 100) / 50).
- * float32 per frame; the window's randn is dropped; the linear smoothing is CheapTrick's interval sum.  F0 belongs
+ * float32 per frame; the window's randn is dropped; the linear smoothing is CheapTrick's interval mean.  F0 belongs
  * below fs / 2 (it is clamped there).  PE_E_UNSUPPORTED: fs / 2 <= 7900, N_d or N_l above 4096, bands above 5,
  * fft_size not 512 / 1024 / 2048; PE_E_ARG: a non-positive or non-finite fs or frame_period_ms, a non-finite
  * threshold, a null pointer, n_rows outside 0 .. 65535.
  * pe_d4c_plan (host only, no device call): pe_cheaptrick_plan's arguments and layout (frame first_frame[r] + q of row
  * r goes to the fft_size / 2 + 1 floats at ap + out_off[r] + q * out_stride[r]); fills meta (n_rows x
- * pe_d4c_plan_fields() int64) and totals {frames, N_d, N_l, bands, L} (L: points of the Nuttall window).
+ * pe_d4c_plan_fields() int64) and totals {frames, N_d, N_l, bands, L} (L: points of the Nuttall window).  The layout
+ * is guaranteed to be one: both plans fill meta through the same code and the three launch entry points check it with
+ * the same walk, so a meta from either plan (same rows, frames and fft_size) is accepted by pe_cheaptrick, pe_d4c_bands
+ * and pe_d4c_expand alike, and pe_d4c_plan_fields() == pe_cheaptrick_plan_fields().
  * pe_d4c_bands: one launch, one workgroup per (row, frame); host_meta: the host copy of meta (PE_E_ARG unless it is the
  * plan's); table: exp(-2 pi i m / N_d) for m < N_d (re, im), then the same for N_l.  band: frames x (1 + bands)
  * floats in plan order, {a0, coarse[0 .. bands)}; coarse is NaN in a frame with the unvoiced verdict.

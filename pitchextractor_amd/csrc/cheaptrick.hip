@@ -1,7 +1,9 @@
 // WORLD CheapTrick on the GPU (Morise, Speech Communication 2015; WORLD's cheaptrick.cpp, pyworld's `cheaptrick`): the
 // spectral envelope of a recording, one frame per F0 value, for a ragged batch of rows in one launch -- one workgroup
 // per (row, frame), everything in LDS with the shared N-point FFT (fft_lds, dsp.h), N = fft_size in {512, 1024, 2048}.
-// pe_cheaptrick_plan (host only) lays the batch out; rows are addressed through its int64 table and find_row.
+// pe_cheaptrick_plan (host only) lays the batch out in the frame plan of world_frames.h; rows are addressed through its
+// int64 table and find_row.  The DC correction and the interval mean behind the linear smoothing are world_frames.h's,
+// which d4c.hip uses too; the window, the lifter and the F0 floor are this file's.
 //
 // Per frame, in WORLD's order: the F0-adaptive window (3 periods, sum w^2 = 1, zero DC) around the frame's sample; the
 // power spectrum; the DC correction (P[k] += P interpolated at f0 - k delta for k delta <= f0); the linear smoothing of
@@ -18,20 +20,14 @@
 // h = f0 N / (3 fs), so the two partial weights are the same for every bin of a frame.
 #include <math.h>
 #include "common.h"
-#include "dsp.h"
+#include "world_frames.h"
 
 using namespace pe;
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kFrameThreads;
 constexpr double kDefaultF0 = 500.0;                          // WORLD's F0 for frames at or below the floor
-
-// per-row plan fields (int64); see pe_cheaptrick_plan
-enum { C_XOFF, C_N, C_F0OFF, C_FIRST, C_FRAMES, C_FOFF, C_OOFF, C_OSTRIDE, C_K };
-static_assert(C_XOFF == kRowOffset && C_N == kRowLength, "a row plan opens with offset and length");
-
-bool fft_size_ok(int n) { return n == 512 || n == 1024 || n == 2048; }
 
 template <int LOG2N>
 __global__ __launch_bounds__(kThreads) void cheaptrick_kernel(const float* __restrict__ x, const float* __restrict__ f0,
@@ -50,16 +46,16 @@ __global__ __launch_bounds__(kThreads) void cheaptrick_kernel(const float* __res
   __syncthreads();
   const double floor_f0 = 3.0 * fs / ((double)N - 3.0);
   for (long g = blockIdx.x; g < n_frames; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, C_K, C_FOFF, g);
-    const long* m = meta + (long)row * C_K;
-    const long q = g - m[C_FOFF], f = m[C_FIRST] + q, n = m[C_N];
-    const float* xr = x + m[C_XOFF];
-    float* out = sp + m[C_OOFF] + q * m[C_OSTRIDE];
-    double f0d = (double)f0[m[C_F0OFF] + f];
+    const int row = find_row(meta, n_rows, FR_K, FR_FOFF, g);
+    const long* m = meta + (long)row * FR_K;
+    const long q = g - m[FR_FOFF], f = m[FR_FIRST] + q, n = m[FR_N];
+    const float* xr = x + m[FR_XOFF];
+    float* out = sp + m[FR_OOFF] + q * m[FR_OSTRIDE];
+    double f0d = (double)f0[m[FR_F0OFF] + f];
     if (!(f0d > floor_f0)) f0d = kDefaultF0;
     f0d = fmin(f0d, fs * (0.5 - 1.0 / N));                      // memory safety only: F0 belongs below Nyquist
     const int half = (int)(1.5 * fs / f0d + 0.5);               // 2 half + 1 <= N - 2 above the floor
-    const long origin = (long)(((double)f * frame_period_s) * fs + 0.001 + 0.5);
+    const long origin = sample_origin((double)f * frame_period_s, fs);
     const float wstep = (float)(f0d / (1.5 * fs));
     // the window scaled to sum w^2 = 1, then the windowed wave with zero DC
     float wv[NQ], xv[NQ];
@@ -97,64 +93,13 @@ __global__ __launch_bounds__(kThreads) void cheaptrick_kernel(const float* __res
       s_p[k] = v.x * v.x + v.y * v.y;
     }
     __syncthreads();
-    // DC correction: the replica from the uncorrected values, then the sum
-    {
-      int K = (int)(f0d / (fs / (double)N));
-      K = K < H - 1 ? K : H - 1;
-      const float r = (float)(f0d * (double)N / fs);
-      float rep[NK];
-#pragma unroll
-      for (int c = 0; c < NK; ++c) {
-        const int k = tid + kThreads * c;
-        rep[c] = 0.f;
-        if (k <= K) {
-          const float pos = r - (float)k;
-          int base = (int)floorf(pos);
-          const float frac = pos - (float)base;
-          base = base < 0 ? 0 : (base > H - 1 ? H - 1 : base);
-          const float p0 = s_p[base], p1 = s_p[base + 1];
-          rep[c] = p0 + (p1 - p0) * frac;
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < NK; ++c) {
-        const int k = tid + kThreads * c;
-        if (k <= K) s_p[k] += rep[c];
-      }
-      __syncthreads();
-    }
+    dc_correct<N>(s_p, f0d, fs, tid);
     // linear smoothing over [k + 1/2 - h, k + 1/2 + h) in cells, + 2^-52, log, mirrored to N points
-    {
-      const float h = (float)(f0d * (double)N / (3.0 * fs));
-      const int hi = (int)floorf(h);
-      const float hf = h - (float)hi;
-      const bool lo_down = hf > 0.5f, up = hf >= 0.5f;
-      const int ka_off = -hi - (lo_down ? 1 : 0), kb_off = hi + (up ? 1 : 0);
-      const float wa = 1.f - (lo_down ? 1.5f - hf : 0.5f - hf);
-      const float wb = up ? hf - 0.5f : 0.5f + hf;
-      auto cell = [&](int j) {
-        j = j < 0 ? -j : j;
-        j = j > H ? N - j : j;
-        return s_p[j < 0 ? 0 : j];
-      };
-      for (int k = tid; k <= H; k += kThreads) {
-        const int ka = k + ka_off, kb = k + kb_off;
-        float s;
-        if (ka == kb) {
-          s = 2.f * h * cell(ka);
-        } else {
-          s = wa * cell(ka);
-          float mid = 0.f;
-          for (int j = ka + 1; j < kb; ++j) mid += cell(j);
-          if (kb - ka > 1) s += mid;
-          s += wb * cell(kb);
-        }
-        const float lq = logf(s / (2.f * h) + 0x1p-52f);
-        s_buf[k] = make_float2(lq, 0.f);
-        if (k > 0 && k < H) s_buf[N - k] = make_float2(lq, 0.f);
-      }
-    }
+    interval_mean<N, float, false>(s_p, [&](int k, float mean) {
+      const float lq = logf(mean + 0x1p-52f);
+      s_buf[k] = make_float2(lq, 0.f);
+      if (k > 0 && k < H) s_buf[N - k] = make_float2(lq, 0.f);
+    }, (float)(f0d * (double)N / (3.0 * fs)), tid);
     __syncthreads();
     fft_lds<LOG2N, false, kThreads>(s_buf, s_tw, tid);          // N x the real, even cepstrum
     {
@@ -190,32 +135,18 @@ __global__ __launch_bounds__(kThreads) void cheaptrick_kernel(const float* __res
   }
 }
 
-// the plan's own walk over its host copy: what the kernel's addressing relies on; fills {frames}
-bool plan_consistent(const long* hm, int n_rows, int fft_size, long* frames) {
-  long tot = 0;
-  for (int r = 0; r < n_rows; ++r) {
-    const long* m = hm + (long)r * C_K;
-    if (m[C_XOFF] < 0 || m[C_N] < 0 || m[C_F0OFF] < 0 || m[C_FIRST] < 0 || m[C_FRAMES] < 0 || m[C_FOFF] != tot ||
-        m[C_OOFF] < 0 || m[C_OSTRIDE] < fft_size / 2 + 1 || (m[C_FRAMES] > 0 && m[C_N] < 1))
-      return false;
-    tot += m[C_FRAMES];
-  }
-  *frames = tot;
-  return true;
-}
-
 int config_status(double fs, double frame_period_ms, double f0_floor, int fft_size) {
   if (fft_size <= 0 || !(fs > 0.0) || !(frame_period_ms > 0.0) || !(f0_floor > 0.0) || !isfinite(fs) ||
       !isfinite(frame_period_ms) || !isfinite(f0_floor))
     return PE_E_ARG;
-  if (!fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
+  if (!world_fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
   if (3.0 * fs / ((double)fft_size - 3.0) > f0_floor) return PE_E_UNSUPPORTED;   // the transform is too short for it
   return PE_OK;
 }
 
 }  // namespace
 
-extern "C" int pe_cheaptrick_plan_fields(void) { return C_K; }
+extern "C" int pe_cheaptrick_plan_fields(void) { return FR_K; }
 
 /* Host-only batch layout; see include/pitchextractor_hip.h. */
 extern "C" int pe_cheaptrick_plan(int n_rows, const long* x_off, const long* x_len, const long* f0_off,
@@ -225,23 +156,8 @@ extern "C" int pe_cheaptrick_plan(int n_rows, const long* x_off, const long* x_l
   if (n_rows < 0 || n_rows > kMaxRows || !totals) return PE_E_ARG;
   const int st = config_status(fs, frame_period_ms, f0_floor, fft_size);
   if (st != PE_OK) return st;
-  if (n_rows > 0 && (!x_off || !x_len || !f0_off || !f0_len || !first_frame || !n_frames || !out_off || !out_stride ||
-                     !meta))
-    return PE_E_ARG;
-  const long bins = fft_size / 2 + 1;
-  long tot = 0;
-  for (int r = 0; r < n_rows; ++r) {
-    if (x_off[r] < 0 || x_len[r] < 0 || x_len[r] > (1L << 31) || f0_off[r] < 0 || f0_len[r] < 0 ||
-        f0_len[r] > (1L << 31) || first_frame[r] < 0 || n_frames[r] < 0 || first_frame[r] + n_frames[r] > f0_len[r] ||
-        out_off[r] < 0 || out_stride[r] < bins || (n_frames[r] > 0 && x_len[r] < 1))
-      return PE_E_ARG;
-    long* m = meta + (long)r * C_K;
-    m[C_XOFF] = x_off[r]; m[C_N] = x_len[r]; m[C_F0OFF] = f0_off[r]; m[C_FIRST] = first_frame[r];
-    m[C_FRAMES] = n_frames[r]; m[C_FOFF] = tot; m[C_OOFF] = out_off[r]; m[C_OSTRIDE] = out_stride[r];
-    tot += n_frames[r];
-  }
-  totals[0] = tot;
-  return PE_OK;
+  return frame_plan_fill(n_rows, x_off, x_len, f0_off, f0_len, first_frame, n_frames, out_off, out_stride, fft_size,
+                         meta, totals);
 }
 
 extern "C" int pe_cheaptrick(const float* x, const float* f0, const long* meta, const long* host_meta,
@@ -249,7 +165,7 @@ extern "C" int pe_cheaptrick(const float* x, const float* f0, const long* meta, 
                              double f0_floor, int fft_size, float* sp, void* stream) {
   long frames = 0;
   PE_OPEN(open_rows(n_rows, config_status(fs, frame_period_ms, f0_floor, fft_size), host_meta,
-                    [&] { return plan_consistent(host_meta, n_rows, fft_size, &frames); }, &frames));
+                    [&] { return frame_plan_consistent(host_meta, n_rows, fft_size, &frames); }, &frames));
   if (!x || !f0 || !meta || !table || !sp || !isfinite(q1)) return PE_E_ARG;
   const dim3 grid(grid_for(frames, 1, 16384)), block(kThreads);
   return with_log2<9, 11>(__builtin_ctz(fft_size), [&](auto L) {

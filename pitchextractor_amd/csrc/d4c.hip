@@ -1,8 +1,9 @@
 // WORLD D4C on the GPU (Morise, Speech Communication 84, 2016; WORLD's d4c.cpp, pyworld's `d4c`): the band aperiodicity
-// of a recording, one frame per F0 value, for a ragged batch of rows.  pe_d4c_plan (host only) lays the batch out like
-// pe_cheaptrick_plan; pe_d4c_bands is one launch with one workgroup per (row, frame), everything in LDS with the shared
-// FFT (fft_lds, dsp.h) at N_d = 2^(1 + floor(log2(4 fs / 47 + 1))) in {2048, 4096}; pe_d4c_expand is one launch that
-// interpolates a frame's band values to the fft_size / 2 + 1 bins the synthesizer reads.
+// of a recording, one frame per F0 value, for a ragged batch of rows.  pe_d4c_plan (host only) lays the batch out in
+// the frame plan of world_frames.h, as pe_cheaptrick_plan does; pe_d4c_bands is one launch with one workgroup per
+// (row, frame), everything in LDS with the shared FFT (fft_lds, dsp.h) at N_d = 2^(1 + floor(log2(4 fs / 47 + 1))) in
+// {2048, 4096}; pe_d4c_expand is one launch that interpolates a frame's band values to the fft_size / 2 + 1 bins the
+// synthesizer reads.
 //
 // Per frame, in WORLD's order.  LoveTrain: the Blackman window of 3 periods at max(F0, 40) around the frame's sample,
 // zero-padded to N_l = 2^(1 + floor(log2(3 fs / 40 + 1))) (N_d or N_d / 2), |X|^2, a0 = sum over [100 Hz, 4000 Hz] /
@@ -24,26 +25,22 @@
 // Stated deviations from WORLD: float32 per-frame arithmetic (sample origins, window lengths and per-frame constants
 // are formed in double); the randn * 1e-12 of the window is dropped, and a frame whose LoveTrain denominator is 0 has
 // a0 = 0, one whose smoothed power is not positive in every bin takes the unvoiced verdict; the linear smoothing is
-// CheapTrick's interval sum (cheaptrick.hip) at a general width, which serves the signed centroid unchanged, its sum
-// accumulated in double.  A band
-// whose group delay is all zero reads 0 dB, and coarse is floored at -200 dB so that no -inf reaches the interpolation.
+// the interval mean CheapTrick uses (world_frames.h, where the DC correction is too) at a general width, which serves
+// the signed centroid unchanged, its sum accumulated in double.  A band whose group delay is all zero reads 0 dB, and
+// coarse is floored at -200 dB so that no -inf reaches the interpolation.
 #include <math.h>
 #include "common.h"
-#include "dsp.h"
+#include "world_frames.h"
 
 using namespace pe;
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kFrameThreads;
 constexpr double kFloorF0 = 47.0, kLowestF0 = 40.0;           // band analysis / LoveTrain
 constexpr double kInterval = 3000.0, kUpperLimit = 15000.0;
 constexpr float kSafe = 1e-12f;
 constexpr int kMaxBands = 5, kMaxN = 4096;
-
-// per-row plan fields (int64); see pe_d4c_plan
-enum { D_XOFF, D_N, D_F0OFF, D_FIRST, D_FRAMES, D_FOFF, D_OOFF, D_OSTRIDE, D_K };
-static_assert(D_XOFF == kRowOffset && D_N == kRowLength, "a row plan opens with offset and length");
 
 struct Derived {
   int n_d, n_l, bands, L;
@@ -55,12 +52,10 @@ int pow2_above(double v) {                                     // 2^(1 + floor(l
   return n;
 }
 
-bool fft_size_ok(int n) { return n == 512 || n == 1024 || n == 2048; }
-
 int config_status(double fs, double frame_period_ms, int fft_size, Derived* d) {
   if (fft_size <= 0 || !(fs > 0.0) || !(frame_period_ms > 0.0) || !isfinite(fs) || !isfinite(frame_period_ms))
     return PE_E_ARG;
-  if (!fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
+  if (!world_fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
   if (fs / 2.0 <= 7900.0 || fs > 1e6) return PE_E_UNSUPPORTED;    // the LoveTrain band would leave the spectrum
   Derived v;
   v.n_d = pow2_above(4.0 * fs / kFloorF0 + 1.0);
@@ -72,8 +67,6 @@ int config_status(double fs, double frame_period_ms, int fft_size, Derived* d) {
   return PE_OK;
 }
 
-__device__ __forceinline__ long matlab_round(double v) { return v > 0.0 ? (long)(v + 0.5) : (long)(v - 0.5); }
-
 // WORLD's GetWindowedWaveform without its randn: samples j = tid + 256 c < len of the window of `ratio` periods of f0
 // around `pos` seconds (Blackman, or Hanning), times the wave, minus the window times sum(x w) / sum(w).
 template <int NQ>
@@ -82,7 +75,7 @@ __device__ __forceinline__ void windowed_wave(const float* __restrict__ xr, long
                                               float (&wave)[NQ], int& len) {
   const int half = (int)matlab_round(ratio * fs / f0d / 2.0);
   len = 2 * half + 1 < max_len ? 2 * half + 1 : max_len;
-  const long origin = matlab_round(pos * fs + 0.001);
+  const long origin = sample_origin(pos, fs);
   const float wstep = (float)(2.0 * f0d / (ratio * fs));
   float wv[NQ];
   float t_w = 0.f, t_xw = 0.f;
@@ -141,67 +134,13 @@ __device__ __forceinline__ float love_train(const float* __restrict__ xr, long n
   return den > 0.f ? num / den : 0.f;
 }
 
-// CheapTrick's DC correction in place: p[k] += p interpolated at r - k for k <= K (r = f0 N / fs in bins)
-template <int N>
-__device__ __forceinline__ void dc_correct(float* s_p, double f0d, double fs, int tid) {
-  constexpr int H = N / 2, NK = H / kThreads + 1;
-  int K = (int)(f0d / (fs / (double)N));
-  K = K < H - 1 ? K : H - 1;
-  const float r = (float)(f0d * (double)N / fs);
-  float rep[NK];
-#pragma unroll
-  for (int c = 0; c < NK; ++c) {
-    const int k = tid + kThreads * c;
-    rep[c] = 0.f;
-    if (k <= K) {
-      const float pos = r - (float)k;
-      int base = (int)floorf(pos);
-      const float frac = pos - (float)base;
-      base = base < 0 ? 0 : (base > H - 1 ? H - 1 : base);
-      const float p0 = s_p[base], p1 = s_p[base + 1];
-      rep[c] = p0 + (p1 - p0) * frac;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < NK; ++c) {
-    const int k = tid + kThreads * c;
-    if (k <= K) s_p[k] += rep[c];
-  }
-  __syncthreads();
-}
-
-// CheapTrick's linear smoothing at half width h bins: dst[k] = mean of src over [k + 1/2 - h, k + 1/2 + h) in cells
-// (cell j holds src[mirror(j)] on [j, j + 1)).  dst is not src; the caller meets after it.  The sum is accumulated in
-// double and rounded once: at F0 = 1000 Hz it has 85 terms, the group delay's second smoothing is subtracted from the
-// first, and a float32 running sum costs the band values four times what every other stage together does (DESIGN.md
-// section 24, tools/d4c_noise_study.py).
+// The linear smoothing at half width h bins: dst <- interval_mean of src (dst is not src; the caller meets after it),
+// accumulated in double and rounded once: at F0 = 1000 Hz the sum has 85 terms, the group delay's second smoothing is
+// subtracted from the first, and a float32 running sum costs the band values four times what every other stage together
+// does (tools/d4c_noise_study.py).
 template <int N>
 __device__ __forceinline__ void smooth(const float* src, float* dst, float h, int tid) {
-  constexpr int H = N / 2;
-  const int hi = (int)floorf(h);
-  const float hf = h - (float)hi;
-  const bool lo_down = hf > 0.5f, up = hf >= 0.5f;
-  const int ka_off = -hi - (lo_down ? 1 : 0), kb_off = hi + (up ? 1 : 0);
-  const float wa = 1.f - (lo_down ? 1.5f - hf : 0.5f - hf);
-  const float wb = up ? hf - 0.5f : 0.5f + hf;
-  auto cell = [&](int j) {
-    j = j < 0 ? -j : j;
-    j = j > H ? N - j : j;
-    return src[j < 0 ? 0 : j];
-  };
-  for (int k = tid; k <= H; k += kThreads) {
-    const int ka = k + ka_off, kb = k + kb_off;
-    double s;
-    if (ka == kb) {
-      s = 2.0 * (double)h * (double)cell(ka);
-    } else {
-      s = (double)wa * (double)cell(ka);
-      for (int j = ka + 1; j < kb; ++j) s += (double)cell(j);
-      s += (double)wb * (double)cell(kb);
-    }
-    dst[k] = (float)(s / (2.0 * (double)h));
-  }
+  interval_mean<N, double, true>(src, [&](int k, float mean) { dst[k] = mean; }, h, tid);
 }
 
 template <int LOG2N>
@@ -224,12 +163,12 @@ __global__ __launch_bounds__(kThreads) void d4c_bands_kernel(const float* __rest
   if (same) load_roots(s_tw, table, N, tid);
   __syncthreads();
   for (long g = blockIdx.x; g < n_frames; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, D_K, D_FOFF, g);
-    const long* m = meta + (long)row * D_K;
-    const long f = m[D_FIRST] + (g - m[D_FOFF]), n = m[D_N];
-    const float* xr = x + m[D_XOFF];
+    const int row = find_row(meta, n_rows, FR_K, FR_FOFF, g);
+    const long* m = meta + (long)row * FR_K;
+    const long f = m[FR_FIRST] + (g - m[FR_FOFF]), n = m[FR_N];
+    const float* xr = x + m[FR_XOFF];
     float* o = out + g * (1 + bands);
-    const float f0f = f0[m[D_F0OFF] + f];
+    const float f0f = f0[m[FR_F0OFF] + f];
     const double t = (double)f * frame_period_s;
     const bool f0_ok = f0f > 0.f;
     // ---- LoveTrain
@@ -416,9 +355,9 @@ __global__ __launch_bounds__(kThreads) void d4c_expand_kernel(const float* __res
                                                               int bands, float* __restrict__ ap) {
   const int bins = fft_size / 2 + 1;
   for (long g = blockIdx.x; g < n_frames; g += gridDim.x) {
-    const int row = find_row(meta, n_rows, D_K, D_FOFF, g);
-    const long* m = meta + (long)row * D_K;
-    float* out = ap + m[D_OOFF] + (g - m[D_FOFF]) * m[D_OSTRIDE];
+    const int row = find_row(meta, n_rows, FR_K, FR_FOFF, g);
+    const long* m = meta + (long)row * FR_K;
+    float* out = ap + m[FR_OOFF] + (g - m[FR_FOFF]) * m[FR_OSTRIDE];
     const float* c = band + g * (1 + bands) + 1;
     const bool unvoiced = !(c[0] == c[0]);
     for (int k = threadIdx.x; k < bins; k += kThreads) {
@@ -437,23 +376,9 @@ __global__ __launch_bounds__(kThreads) void d4c_expand_kernel(const float* __res
   }
 }
 
-// the plan's own walk over its host copy: what the kernels' addressing relies on; fills {frames}
-bool plan_consistent(const long* hm, int n_rows, int fft_size, long* frames) {
-  long tot = 0;
-  for (int r = 0; r < n_rows; ++r) {
-    const long* m = hm + (long)r * D_K;
-    if (m[D_XOFF] < 0 || m[D_N] < 0 || m[D_F0OFF] < 0 || m[D_FIRST] < 0 || m[D_FRAMES] < 0 || m[D_FOFF] != tot ||
-        m[D_OOFF] < 0 || m[D_OSTRIDE] < fft_size / 2 + 1 || (m[D_FRAMES] > 0 && m[D_N] < 1))
-      return false;
-    tot += m[D_FRAMES];
-  }
-  *frames = tot;
-  return true;
-}
-
 }  // namespace
 
-extern "C" int pe_d4c_plan_fields(void) { return D_K; }
+extern "C" int pe_d4c_plan_fields(void) { return FR_K; }
 
 /* Host-only batch layout; see include/pitchextractor_hip.h. */
 extern "C" int pe_d4c_plan(int n_rows, const long* x_off, const long* x_len, const long* f0_off, const long* f0_len,
@@ -461,24 +386,12 @@ extern "C" int pe_d4c_plan(int n_rows, const long* x_off, const long* x_len, con
                            double fs, double frame_period_ms, int fft_size, long* meta, long* totals) {
   if (n_rows < 0 || n_rows > kMaxRows || !totals) return PE_E_ARG;
   Derived d;
-  const int st = config_status(fs, frame_period_ms, fft_size, &d);
+  int st = config_status(fs, frame_period_ms, fft_size, &d);
   if (st != PE_OK) return st;
-  if (n_rows > 0 && (!x_off || !x_len || !f0_off || !f0_len || !first_frame || !n_frames || !out_off || !out_stride ||
-                     !meta))
-    return PE_E_ARG;
-  const long bins = fft_size / 2 + 1;
-  long tot = 0;
-  for (int r = 0; r < n_rows; ++r) {
-    if (x_off[r] < 0 || x_len[r] < 0 || x_len[r] > (1L << 31) || f0_off[r] < 0 || f0_len[r] < 0 ||
-        f0_len[r] > (1L << 31) || first_frame[r] < 0 || n_frames[r] < 0 || first_frame[r] + n_frames[r] > f0_len[r] ||
-        out_off[r] < 0 || out_stride[r] < bins || (n_frames[r] > 0 && x_len[r] < 1))
-      return PE_E_ARG;
-    long* m = meta + (long)r * D_K;
-    m[D_XOFF] = x_off[r]; m[D_N] = x_len[r]; m[D_F0OFF] = f0_off[r]; m[D_FIRST] = first_frame[r];
-    m[D_FRAMES] = n_frames[r]; m[D_FOFF] = tot; m[D_OOFF] = out_off[r]; m[D_OSTRIDE] = out_stride[r];
-    tot += n_frames[r];
-  }
-  totals[0] = tot; totals[1] = d.n_d; totals[2] = d.n_l; totals[3] = d.bands; totals[4] = d.L;
+  if ((st = frame_plan_fill(n_rows, x_off, x_len, f0_off, f0_len, first_frame, n_frames, out_off, out_stride, fft_size,
+                            meta, totals)) != PE_OK)
+    return st;
+  totals[1] = d.n_d; totals[2] = d.n_l; totals[3] = d.bands; totals[4] = d.L;
   return PE_OK;
 }
 
@@ -489,7 +402,7 @@ extern "C" int pe_d4c_bands(const float* x, const float* f0, const long* meta, c
   Derived d = {};
   if (!isfinite(threshold)) return PE_E_ARG;
   PE_OPEN(open_rows(n_rows, config_status(fs, frame_period_ms, fft_size, &d), host_meta,
-                    [&] { return plan_consistent(host_meta, n_rows, fft_size, &frames); }, &frames));
+                    [&] { return frame_plan_consistent(host_meta, n_rows, fft_size, &frames); }, &frames));
   if (!x || !f0 || !meta || !table || !band) return PE_E_ARG;
   const dim3 grid(grid_for(frames, 1, 16384)), block(kThreads);
   return with_log2<11, 12>(__builtin_ctz(d.n_d), [&](auto L2) {
@@ -505,7 +418,7 @@ extern "C" int pe_d4c_expand(const float* band, const long* meta, const long* ho
   long frames = 0;
   Derived d = {};
   PE_OPEN(open_rows(n_rows, config_status(fs, 1.0, fft_size, &d), host_meta,
-                    [&] { return plan_consistent(host_meta, n_rows, fft_size, &frames); }, &frames));
+                    [&] { return frame_plan_consistent(host_meta, n_rows, fft_size, &frames); }, &frames));
   if (!band || !meta || !ap) return PE_E_ARG;
   hipLaunchKernelGGL(d4c_expand_kernel, dim3(grid_for(frames, 1, 65536)), dim3(kThreads), 0, pe_stream(stream), band,
                      meta, n_rows, frames, fs, fft_size, d.bands, ap);

@@ -1,9 +1,11 @@
-// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip, cheaptrick.hip,
-// stress.hip, rir_synth.hip, stimuli.hip, noise.hip) share; on top of this, pieces.h holds what the last three share
-// among themselves (the piece geometry, the double reductions and scan) and snr_mix.h the mix at an SNR of the last
-// two. Host: the row bound and the launch-grid clamps of the ragged entry points, the header every row plan opens with,
-// the gate every entry point that takes a host plan passes before its own checks (open_rows, kNothing, PE_OPEN), the
-// size of the transform roots every table opens with, and with_log2 (transform size -> kernel instance).  Device:
+// What the audio kernels (mel.hip, pitch_shift.hip, f0_track.hip, f0_dio.hip, world_synth.hip, cheaptrick.hip, d4c.hip,
+// stress.hip, augment.hip, rir_synth.hip, stimuli.hip, noise.hip) share; on top of this, pieces.h holds what the last
+// three share among themselves (the piece geometry, the double reductions and scan), snr_mix.h the mix at an SNR of the
+// last two, and world_frames.h what the WORLD analyses cheaptrick.hip and d4c.hip share (the frame plan, the DC
+// correction, the interval mean). Host: the row bound and the launch-grid clamps of the ragged entry points, the header
+// every row plan opens with, the gate every entry point that takes a host plan passes before its own checks (open_rows,
+// kNothing, PE_OPEN), the size of the transform roots every table opens with, and with_log2 (transform size -> kernel
+// instance).  Device:
 // float2 complex arithmetic, the wave-private LDS fence, the in-place radix-4 Stockham FFT in LDS, a packed half-length
 // transform's bins as the real one's and back (real_fft_split, real_fft_bin, real_fft_pack), the 256-thread workgroup
 // float reductions in a fixed order, the seeded standard normal (world_randn), and the row search of ragged plans.

@@ -20,7 +20,7 @@
 //      are the epilogue.
 #include <math.h>
 #include "common.h"
-#include "dsp.h"
+#include "world_frames.h"
 
 using namespace pe;
 
@@ -210,8 +210,6 @@ __global__ __launch_bounds__(kThreads) void world_ola_kernel(const float* __rest
   }
 }
 
-bool fft_size_ok(int n) { return n == 512 || n == 1024 || n == 2048; }
-
 }  // namespace
 
 extern "C" int pe_world_plan_fields(void) { return W_K; }
@@ -224,7 +222,7 @@ extern "C" int pe_world_plan(int n_rows, const long* n_frames, const double* f0,
                              long out_stride, double fs, double frame_period_ms, int fft_size, long* meta,
                              long* pulses, double* pulse_f, long* totals) {
   if (fft_size <= 0 || (fft_size & (fft_size - 1))) return PE_E_ARG;
-  if (!fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
+  if (!world_fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
   if (n_rows < 0 || n_rows > kMaxRows || !totals || !(fs > 0.0) || !(frame_period_ms > 0.0) || !isfinite(fs) ||
       !isfinite(frame_period_ms))
     return PE_E_ARG;
@@ -289,7 +287,7 @@ extern "C" int pe_world_responses(const float* sp, const float* ap, const float*
                                   const long* pulses, const double* pulse_f, const float* table, int n_rows,
                                   long n_pulses, int fft_size, float* responses, void* stream) {
   if (n_rows < 0 || n_rows > kMaxRows || n_pulses < 0 || fft_size <= 0) return PE_E_ARG;
-  if (!fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
+  if (!world_fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
   if (n_pulses == 0 || n_rows == 0) return PE_OK;
   if (!sp || !meta || !pulses || !pulse_f || !table || !responses) return PE_E_ARG;
   const dim3 grid(grid_for(n_pulses, 1, 8192)), block(kThreads);
@@ -305,7 +303,7 @@ extern "C" int pe_world_overlap_add(const float* responses, const long* meta, co
                                     const float* out_noise, int n_rows, long n_out, int fft_size, float* out,
                                     void* stream) {
   if (n_rows < 0 || n_rows > kMaxRows || n_out < 0 || fft_size <= 0) return PE_E_ARG;
-  if (!fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
+  if (!world_fft_size_ok(fft_size)) return PE_E_UNSUPPORTED;
   if (n_out == 0 || n_rows == 0) return PE_OK;
   if (!meta || !gains || !out) return PE_E_ARG;               // responses / pulses may be empty: a window no pulse meets
   const dim3 grid(grid_for(n_out, kThreads, 8192)), block(kThreads);

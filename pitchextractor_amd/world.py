@@ -371,20 +371,41 @@ class Envelopes(NamedTuple):
         return self.offsets - self.first * self.strides
 
 
-def _frame_plan(who, plan_fn, x, lengths, f0s, frames, out, out_offsets, out_strides, fft_size, config, n_totals=1):
-    """The host layout both frame analyses share: the rows of ``x``, their packed F0 curves, the frames asked for and
-    where they go, through the C plan ``plan_fn`` (``config``: its arguments between ``out_stride`` and ``meta``).
-    Returns ``(R, f0_d, meta, totals, out, Envelopes)`` with ``out`` made, or checked against what the plan addresses."""
+class _FrameRows(NamedTuple):
+    """What a frame analysis takes from the rows alone, whichever analysis it is: where the rows lie in ``x``, their F0
+    curves packed on the device (``f0``) with each row's offset and length in it, and the frames asked for."""
+    n: int
+    offsets: np.ndarray
+    lengths: np.ndarray
+    f0: torch.Tensor
+    f0_off: np.ndarray
+    f0_len: np.ndarray
+    first: np.ndarray
+    counts: np.ndarray
+
+
+def _frame_rows(who, x, lengths, f0s, frames) -> _FrameRows:
+    """``cheaptrick_ragged`` and ``d4c_ragged`` build this from their arguments, or take the one that
+    ``resynthesize_ragged`` built for both (``_rows``, which then stands for ``lengths``, ``f0s`` and ``frames``): the
+    envelope and the aperiodicity of a resynthesis are of the same frames by construction, with one upload of the F0."""
     check_waves(x, who)
     lengths, offsets = row_layout(x, lengths, whole_by_default=True)
     R = len(lengths)
-    bins = fft_size // 2 + 1
     f0s = list(f0s)
     if len(f0s) != R:
         raise ValueError(f"{who}: one F0 curve per row")
     f0_d, f0_off, f0_len = pack_tracks(f0s, x.device)
     first = np.zeros(R, np.int64) if frames is None else _i64([fr[0] for fr in frames], R)
     counts = _i64(f0_len, R) - first if frames is None else _i64([fr[1] for fr in frames], R)
+    return _FrameRows(R, i64(offsets), i64(lengths), f0_d, i64(f0_off), i64(f0_len), first, counts)
+
+
+def _frame_plan(who, plan_fn, rows: _FrameRows, device, out, out_offsets, out_strides, fft_size, config, n_totals=1):
+    """``rows`` and where their frames go, through the C plan ``plan_fn`` (``config``: its arguments between
+    ``out_stride`` and ``meta``).  Returns ``(meta, totals, out, Envelopes)`` with ``out`` made on ``device``, or
+    checked against what the plan addresses."""
+    R, first, counts = rows.n, rows.first, rows.counts
+    bins = fft_size // 2 + 1
     strides = np.full(R, bins, np.int64) if out_strides is None else _i64(out_strides, R)
     if out_offsets is None:
         out_offsets = np.cumsum(counts * strides) - counts * strides
@@ -392,21 +413,22 @@ def _frame_plan(who, plan_fn, x, lengths, f0s, frames, out, out_offsets, out_str
     meta = plan_meta(plan_fn + "_fields", R)
     totals = np.zeros(n_totals, np.int64)
     _lib.check(getattr(_lib.load(), plan_fn)(
-        R, *host_ptrs(i64(offsets), i64(lengths), i64(f0_off), i64(f0_len), first, counts, out_offsets, strides),
+        R, *host_ptrs(rows.offsets, rows.lengths, rows.f0_off, rows.f0_len, first, counts, out_offsets, strides),
         *config, *host_ptrs(meta, totals)), plan_fn)
     need = int((out_offsets + np.maximum(counts - 1, 0) * strides + bins)[counts > 0].max(initial=0))
     if out is None:
-        out = torch.empty((max(need, 1),), dtype=torch.float32, device=x.device)
+        out = torch.empty((max(need, 1),), dtype=torch.float32, device=device)
     else:
         check_device_tensor(out, who)
         if out.numel() < need:
             raise ValueError(f"{who}: the output is smaller than the plan addresses")
-    return R, f0_d, meta, totals, out, Envelopes(out, out_offsets, strides, first, counts, fft_size)
+    return meta, totals, out, Envelopes(out, out_offsets, strides, first, counts, fft_size)
 
 
 def cheaptrick_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5.0, *, q1: float = CHEAPTRICK_Q1,
                       f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None, frames=None,
-                      out: torch.Tensor | None = None, out_offsets=None, out_strides=None) -> Envelopes:
+                      out: torch.Tensor | None = None, out_offsets=None, out_strides=None,
+                      _rows: _FrameRows | None = None) -> Envelopes:
     """WORLD's CheapTrick for a ragged batch, one launch.  ``x``: float32 device audio, rows packed back to back (1-D,
     with ``lengths``) or padded (2-D; ``lengths`` defaults to the width).  ``f0s``: one F0 curve per row at
     ``frame_period`` (ms) spacing, 0 = unvoiced (tensors or arrays; brought to the device as float32).  ``frames``: per
@@ -416,8 +438,10 @@ def cheaptrick_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5
     check_waves(x, "CheapTrick")
     fft_size = check_fft_size(cheaptrick_fft_size(fs, f0_floor) if fft_size is None else fft_size)
     bins = fft_size // 2 + 1
-    R, f0_d, meta, totals, out, env = _frame_plan(
-        "CheapTrick", "pe_cheaptrick_plan", x, lengths, f0s, frames, out, out_offsets, out_strides, fft_size,
+    rows = _frame_rows("CheapTrick", x, lengths, f0s, frames) if _rows is None else _rows
+    R, f0_d = rows.n, rows.f0
+    meta, totals, out, env = _frame_plan(
+        "CheapTrick", "pe_cheaptrick_plan", rows, x.device, out, out_offsets, out_strides, fft_size,
         (float(fs), float(frame_period), float(f0_floor), fft_size))
     if R and int(totals[0]):
         meta_d = torch.from_numpy(meta).to(x.device)
@@ -452,7 +476,7 @@ def _d4c_table(n_d: int, n_l: int, device) -> torch.Tensor:
 
 def d4c_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5.0, *, threshold: float = D4C_THRESHOLD,
                fft_size: int | None = None, frames=None, out: torch.Tensor | None = None, out_offsets=None,
-               out_strides=None, return_bands: bool = False):
+               out_strides=None, return_bands: bool = False, _rows: _FrameRows | None = None):
     """WORLD's D4C for a ragged batch, two launches (the band analysis, then its expansion to bins).  The arguments are
     ``cheaptrick_ragged``'s, and so is the layout returned: an ``Envelopes`` whose ``sp`` holds the aperiodicity, ``bins
     = fft_size / 2 + 1`` floats in (0, 1] per frame (``fft_size`` defaults to CheapTrick's for ``fs``).  ``threshold``:
@@ -464,9 +488,10 @@ def d4c_ragged(x: torch.Tensor, lengths, f0s, fs, frame_period: float = 5.0, *, 
     threshold = float(threshold)
     if not math.isfinite(threshold):
         raise ValueError("D4C: threshold must be finite")
-    R, f0_d, meta, totals, out, env = _frame_plan(
-        "D4C", "pe_d4c_plan", x, lengths, f0s, frames, out, out_offsets, out_strides, fft_size,
-        (float(fs), float(frame_period), fft_size), n_totals=5)
+    rows = _frame_rows("D4C", x, lengths, f0s, frames) if _rows is None else _rows
+    R, f0_d = rows.n, rows.f0
+    meta, totals, out, env = _frame_plan("D4C", "pe_d4c_plan", rows, x.device, out, out_offsets, out_strides, fft_size,
+                                         (float(fs), float(frame_period), fft_size), n_totals=5)
     n_frames, n_d, n_l, n_bands, _ = (int(v) for v in totals)
     bands = torch.empty((max(n_frames, 1), 1 + n_bands), dtype=torch.float32, device=x.device)
     if R and n_frames:
@@ -537,12 +562,13 @@ def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period
     hi = np.where(out_len > 0, hi, lo)
     base = np.cumsum(n_frames * bins) - n_frames * bins          # each row's frame 0, whole rows laid out
     sp = torch.empty((max(int((n_frames * bins).sum()), 1),), dtype=torch.float32, device=x.device)
-    env = cheaptrick_ragged(x, lengths, f0s, fs, frame_period, q1=q1, f0_floor=f0_floor, fft_size=fft_size,
-                            frames=list(zip(lo, hi - lo)), out=sp, out_offsets=base + lo * bins)
+    rows = _frame_rows("CheapTrick", x, lengths, f0s, list(zip(lo, hi - lo)))    # once, for both analyses
+    env = cheaptrick_ragged(x, lengths, f0s, fs, frame_period, q1=q1, f0_floor=f0_floor, fft_size=fft_size, out=sp,
+                            out_offsets=base + lo * bins, _rows=rows)
     ap_offsets = ap_strides = None if ap is None else [0] * R
     if estimate:
         ap = d4c_ragged(x, lengths, f0s, fs, frame_period, threshold=d4c_threshold, fft_size=fft_size,
-                        frames=list(zip(lo, hi - lo)), out=torch.empty_like(sp), out_offsets=base + lo * bins).sp
+                        out=torch.empty_like(sp), out_offsets=base + lo * bins, _rows=rows).sp
         ap_offsets, ap_strides = env.frame0_offsets(), env.strides
     world_synthesize_ragged(labels, env.sp, env.frame0_offsets(), env.strides,
                             torch.ones(R) if gains is None else gains, out, out_rows, out_start, out_len, fs=fs,
