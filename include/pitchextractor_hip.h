@@ -602,6 +602,39 @@ int pe_d4c_bands(const float* x, const float* f0, const long* meta, const long* 
 int pe_d4c_expand(const float* band, const long* meta, const long* host_meta, int n_rows, double fs, int fft_size,
                   float* ap, void* stream);
 
+/* ---- Voice transforms of WORLD frames: formant warp, tempo, tilt, breath (csrc/world_warp.hip) -----------------------
+ * Row r has src_frames[r] source frames of fft_size / 2 + 1 floats, frame f at sp_in + in_off[r] + f * in_stride[r]
+ * (in_stride >= 0; 0: one frame for every f) and, where ap_off is given and ap_off[r] >= 0, at ap_in + ap_off[r] +
+ * f * ap_stride[r].  Its out_frames[r] output frames go to sp_out (and ap_out, for a row with an ap) + out_off[r] +
+ * q * out_stride[r], out_stride[r] >= fft_size / 2 + 1.  Output frame q of the batch (rows back to back) reads the
+ * source position pos_frame[q] + pos_frac[q], 0 <= pos_frac < 1 (formed in float64 by the caller; pe_f0_dio_events'
+ * convention), within [0, src_frames[r] - 1].  params: n_rows x {alpha, f_hi, tilt_db_per_octave, breath_db} floats.
+ * Output bin k at f = k fs / fft_size: the frequency map w(f) = alpha f for f <= f_hi min(alpha, 1) / alpha and the
+ * straight line from there to (fs / 2, fs / 2) (Jaitly & Hinton 2013); sp_out(f) = exp of the bilinear interpolation
+ * of ln sp_in over the two source frames and the two source bins around w^-1(f), plus tilt_db_per_octave *
+ * log2(max(f, 125) / 1000) dB (sp is a power: 10 log10); ap_out(f) = the same read of ap_in, linear, times
+ * 10^(breath_db / 20), clamped to [0, 1].  sp_in must be positive.  With alpha == 1, no tilt and pos_frac == 0 the
+ * frame's sp is copied bit for bit, and its ap when breath_db == 0 as well.  float32; the buffers must not overlap.
+ * pe_world_warp_plan (host only, no device call): fills meta (n_rows x pe_world_warp_plan_fields() int64: the frame
+ * plan's fields, then in_stride, ap_off or -1, ap_stride) and totals {output frames}.  PE_E_ARG: a null pointer
+ * (ap_off may be null: no row has an ap; pos_frame / pos_frac may be null when there is no output frame), n_rows
+ * outside 0 .. 65535, a non-finite or non-positive fs, a negative count, offset or stride, an output stride below
+ * fft_size / 2 + 1, output frames of a row without source frames, alpha outside [0.5, 2] or any non-finite parameter,
+ * f_hi outside (0, fs / 2) (the map would not rise strictly on [0, fs / 2]), a position outside [0, src_frames[r] - 1]
+ * or a fraction outside [0, 1).  PE_E_UNSUPPORTED: fft_size not 512 / 1024 / 2048.
+ * pe_world_warp: one launch, one workgroup per (row, output frame); host_meta: the host copy of meta (PE_E_ARG unless
+ * it is the plan's); meta, pos_frame, pos_frac, params: device copies of what the plan took.  ap_in / ap_out may be
+ * null when no row has an ap.  No rows or no output frames: PE_OK without a launch.  A row's frames are bit-identical
+ * alone, at any offset, padded, anywhere in a batch and into a wider stride. */
+int pe_world_warp_plan_fields(void);
+int pe_world_warp_plan(int n_rows, const long* src_frames, const long* in_off, const long* in_stride,
+                       const long* ap_off, const long* ap_stride, const long* out_frames, const long* out_off,
+                       const long* out_stride, const int* pos_frame, const float* pos_frac, const float* params,
+                       double fs, int fft_size, long* meta, long* totals);
+int pe_world_warp(const float* sp_in, const float* ap_in, const long* meta, const long* host_meta,
+                  const int* pos_frame, const float* pos_frac, const float* params, int n_rows, double fs,
+                  int fft_size, float* sp_out, float* ap_out, void* stream);
+
 /* ---- F0 bin decoding (build-defined; the inverse of pe_f0_bins_ce_loss) and pitch metrics --------------------
  * logits: N sequences of T frames of C bins, frame (n, t) at logits + n * ld_n + t * ld_t (2 <= C <= 1024, more is
  * PE_E_UNSUPPORTED).  Bin b stands for cents(b) = 20 b + 1997.3794084376191, f(b) = 10 * 2^(cents(b) / 1200) Hz.

@@ -146,6 +146,9 @@ PROTOTYPES = {
     "pe_d4c_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _i, _p, _p]),
     "pe_d4c_bands": (_i, [_p, _p, _p, _p, _p, _i, _d, _d, _d, _i, _p, _p]),
     "pe_d4c_expand": (_i, [_p, _p, _p, _i, _d, _i, _p, _p]),
+    "pe_world_warp_plan_fields": (_i, []),
+    "pe_world_warp_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _i, _p, _p]),
+    "pe_world_warp": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _p, _p, _p]),
     "pe_f0_bins_ce_workspace_bytes": (_z, [_l]),
     "pe_f0_bins_ce_loss": (_i, [_p, _l, _i, _p, _p, _p, _f, _l, _f, _p, _p, _l, _p, _p, _z, _p]),
     "pe_nonfinite_flag": (_i, [_p, _l, _p, _p]),

@@ -19,10 +19,11 @@ enum { FR_XOFF, FR_N, FR_F0OFF, FR_FIRST, FR_FRAMES, FR_FOFF, FR_OOFF, FR_OSTRID
 static_assert(FR_XOFF == kRowOffset && FR_N == kRowLength, "a row plan opens with offset and length");
 
 // The body of a pe_*_plan after its own range and config checks: null arrays or a row out of range is PE_E_ARG; else
-// meta is filled and *frames is the batch's frame total.
+// meta is filled and *frames is the batch's frame total.  fields: int64 per row of meta, for a plan that appends fields
+// of its own to these (world_warp.hip).
 inline int frame_plan_fill(int n_rows, const long* x_off, const long* x_len, const long* f0_off, const long* f0_len,
                            const long* first_frame, const long* n_frames, const long* out_off,
-                           const long* out_stride, int fft_size, long* meta, long* frames) {
+                           const long* out_stride, int fft_size, long* meta, long* frames, int fields = FR_K) {
   if (n_rows > 0 && (!x_off || !x_len || !f0_off || !f0_len || !first_frame || !n_frames || !out_off || !out_stride ||
                      !meta))
     return PE_E_ARG;
@@ -33,7 +34,7 @@ inline int frame_plan_fill(int n_rows, const long* x_off, const long* x_len, con
         f0_len[r] > (1L << 31) || first_frame[r] < 0 || n_frames[r] < 0 || first_frame[r] + n_frames[r] > f0_len[r] ||
         out_off[r] < 0 || out_stride[r] < bins || (n_frames[r] > 0 && x_len[r] < 1))
       return PE_E_ARG;
-    long* m = meta + (long)r * FR_K;
+    long* m = meta + (long)r * fields;
     m[FR_XOFF] = x_off[r]; m[FR_N] = x_len[r]; m[FR_F0OFF] = f0_off[r]; m[FR_FIRST] = first_frame[r];
     m[FR_FRAMES] = n_frames[r]; m[FR_FOFF] = tot; m[FR_OOFF] = out_off[r]; m[FR_OSTRIDE] = out_stride[r];
     tot += n_frames[r];
@@ -43,10 +44,10 @@ inline int frame_plan_fill(int n_rows, const long* x_off, const long* x_len, con
 }
 
 // the plan's own walk over its host copy: what the kernels' addressing relies on; fills {frames}
-inline bool frame_plan_consistent(const long* hm, int n_rows, int fft_size, long* frames) {
+inline bool frame_plan_consistent(const long* hm, int n_rows, int fft_size, long* frames, int fields = FR_K) {
   long tot = 0;
   for (int r = 0; r < n_rows; ++r) {
-    const long* m = hm + (long)r * FR_K;
+    const long* m = hm + (long)r * fields;
     if (m[FR_XOFF] < 0 || m[FR_N] < 0 || m[FR_F0OFF] < 0 || m[FR_FIRST] < 0 || m[FR_FRAMES] < 0 ||
         m[FR_FOFF] != tot || m[FR_OOFF] < 0 || m[FR_OSTRIDE] < fft_size / 2 + 1 || (m[FR_FRAMES] > 0 && m[FR_N] < 1))
       return false;

@@ -24,8 +24,9 @@ import torch
 
 from .mel import MAX_MEL_LENGTH
 from .pitch_shift import pitch_shift_ragged
-from .world import (CHEAPTRICK_Q1, check_fft_size, cheaptrick_fft_size, label_curve, noise_seed, output_length,
-                    resynthesize_ragged, time_base, world_synthesize_ragged)
+from .world import (CHEAPTRICK_Q1, VoiceTransform, check_fft_size, cheaptrick_fft_size, label_curve, noise_seed,
+                    output_length, resynthesize_ragged, source_positions, time_base, time_warp_curve, warped_frames,
+                    warped_length, world_synthesize_ragged)
 
 logger = logging.getLogger(__name__)
 
@@ -94,7 +95,9 @@ class WorldBatch(NamedTuple):
 class ResynthesisRequest(NamedTuple):
     """One analysis / resynthesis item (its first element is the base file's audio, as for a pitch-shifted one).  The
     device estimates the file's CheapTrick envelope under ``base_curve`` and synthesizes samples [out_start, out_start +
-    out_len) of it on ``curve``, which is the item's labels.  ``n``: samples of the base file at the model rate."""
+    out_len) of it on ``curve``, which is the item's labels.  ``n``: samples of the base file at the model rate.  With a
+    ``transform`` (the ``world.VoiceTransform`` drawn for the item) ``curve``, the window and the noise are on the
+    output time axis, whose frame g reads the source frame ``positions[g]``."""
     path: str
     gain: float
     n: int
@@ -109,6 +112,8 @@ class ResynthesisRequest(NamedTuple):
     vuv: np.ndarray
     seed: int                                  # of the aperiodic noise, drawn on the device
     noise: np.ndarray | None                   # float32 (out_len,) slice of the full-length additive draw
+    transform: tuple | None = None             # (formant, rate, tilt, breath, f_hi), or None: the file's own voice
+    positions: np.ndarray | None = None        # float64 (frames of curve,) source frame of each output frame
 
 
 class ResynthesisBatch(NamedTuple):
@@ -127,6 +132,9 @@ class ResynthesisBatch(NamedTuple):
     curves: tuple                              # K float64 curves
     tables: tuple                              # K (index, shift, vuv)
     seeds: tuple                               # K ints
+    transforms: tuple | None = None            # K transforms (None: that row has none), or None: no row has one
+    positions: tuple | None = None             # K position arrays (None where the row has no transform)
+    base_len: tuple | None = None              # K lengths of the base curves (they differ from the curves' at a rate)
 
 
 def synthetic_window(n: int, crop: int, hop: int, n_fft: int, max_frames: int = MAX_MEL_LENGTH):
@@ -285,17 +293,49 @@ class WorldResynthesis:
     file's own pitch); the gain (``random.uniform``, unless ``gain_db_range`` is null); the vibrato (``random.random``
     against its probability and, when it applies with a positive depth, ``random.uniform`` for its rate); the additive
     noise (``np.random.normal`` of the file's length, unless ``noise_db`` is null); the crop (``np.random.randint``, for
-    a file longer than 192 frames).  An unreadable, unlabelled or too sparsely voiced file ends the attempt after the
+    a file longer than 192 frames).  With a ``transform`` block whose ``probability`` is positive, between the vibrato
+    and the noise: ``random.random`` against the probability and, when the transform applies, one ``random.uniform``
+    per range that is not a single value, in the order formant, rate, tilt, breath; the noise and the crop are then
+    drawn for the output length ``round(n / rate)``.  An unreadable, unlabelled or too sparsely voiced file ends the attempt after the
     file draw; ``generate`` returns None when every attempt failed."""
     name, Request, Batch = "world_resynthesis", ResynthesisRequest, ResynthesisBatch
     KEYS = ("enabled", "backend", "semitones", "gain_db_range", "noise_db", "min_voiced_fraction", "max_attempts",
-            "modulation", "aperiodicity", "d4c_threshold", "q1")
+            "modulation", "aperiodicity", "d4c_threshold", "q1", "transform")
     MODULATION_KEYS = ("vibrato_probability", "vibrato_semitones", "vibrato_rate_range")
+    TRANSFORM_KEYS = ("probability", "formant_ratio_range", "rate_range", "tilt_db_per_octave_range", "breath_db_range",
+                      "f_hi")
+    # a range's key, its identity, and the values it may take
+    TRANSFORM_RANGES = (("formant_ratio_range", 1.0, (0.5, 2.0)), ("rate_range", 1.0, (0.5, 2.0)),
+                        ("tilt_db_per_octave_range", 0.0, (-12.0, 12.0)), ("breath_db_range", 0.0, (-40.0, 40.0)))
+
+    def _check_transform(self, ds, block):
+        """The ``transform`` block as {probability, ranges (four sorted pairs), f_hi}, or None when it is absent or its
+        probability is 0: then no draw is added."""
+        if block is None:
+            return None
+        for k in block:
+            if k not in self.TRANSFORM_KEYS:
+                logger.warning("world_resynthesis.transform: option %r is not read", k)
+        probability = float(block.get("probability", 0.5))
+        if not 0.0 <= probability <= 1.0:
+            raise ValueError("world_resynthesis: transform.probability must lie in [0, 1]")
+        ranges = []
+        for key, identity, (low, high) in self.TRANSFORM_RANGES:
+            value = block.get(key, identity)
+            pair = (float(value),) * 2 if isinstance(value, (int, float)) else tuple(sorted(float(v) for v in value))
+            if len(pair) != 2 or not all(np.isfinite(pair)) or pair[0] < low or pair[1] > high:
+                raise ValueError(f"world_resynthesis: transform.{key} must be two values within [{low}, {high}]")
+            ranges.append(pair)
+        f_hi = float(block.get("f_hi", VoiceTransform().f_hi))
+        if not 0.0 < f_hi < ds.sr / 2.0:
+            raise ValueError("world_resynthesis: transform.f_hi must lie between 0 and half the sample rate")
+        return None if probability == 0.0 else {"probability": probability, "ranges": tuple(ranges), "f_hi": f_hi}
 
     def check_config(self, ds, cfg):
         """The ``world_resynthesis`` block with its defaults filled in; a key it does not read gets a warning, a value
         it cannot use a ``ValueError``."""
         mod = dict(cfg.get("modulation", {}) or {})
+        transform = self._check_transform(ds, cfg.get("transform"))
         for where, block, keys in (("", cfg, self.KEYS), (".modulation", mod, self.MODULATION_KEYS)):
             for k in block:
                 if k not in keys:
@@ -330,7 +370,16 @@ class WorldResynthesis:
                 "vibrato_probability": float(mod.get("vibrato_probability", 0.6)),
                 "vibrato_semitones": float(mod.get("vibrato_semitones", 0.35)), "vibrato_rate_range": rate,
                 "aperiodicity": aperiodicity, "d4c_threshold": d4c_threshold, "q1": float(cfg.get("q1", CHEAPTRICK_Q1)),
-                "fft_size": check_fft_size(cheaptrick_fft_size(ds.sr)), "frame_period": 1000.0 * hop / ds.sr}
+                "fft_size": check_fft_size(cheaptrick_fft_size(ds.sr)), "frame_period": 1000.0 * hop / ds.sr,
+                "transform": transform}
+
+    @staticmethod
+    def _draw_transform(tcfg):
+        """The item's ``VoiceTransform``, or None when the block is off or the draw says the file keeps its voice."""
+        if tcfg is None or not random.random() < tcfg["probability"]:
+            return None
+        return VoiceTransform(*(low if low == high else random.uniform(low, high) for low, high in tcfg["ranges"]),
+                              tcfg["f_hi"])
 
     def generate(self, ds):
         cfg = ds.synthetic_resynthesis_config
@@ -351,20 +400,32 @@ class WorldResynthesis:
             base = np.where(np.isfinite(base) & (base > 0), base, 0.0)
             semitone = random.choice(cfg["semitones"])
             gain = _draw_gain(cfg["gain_db_range"])
-            new = base * float(2 ** (semitone / 12.0))
+            vibrato, depth = None, 0.0
             if random.random() < cfg["vibrato_probability"]:
                 depth = max(cfg["vibrato_semitones"], 0.0)
                 if depth > 0:
-                    rate = random.uniform(*cfg["vibrato_rate_range"])
-                    t = np.arange(mel_len, dtype=np.float64) * (frame_period / 1000.0)
-                    new = new * 2.0 ** (np.sin(2.0 * np.pi * rate * t) * (depth / 12.0))
+                    vibrato = random.uniform(*cfg["vibrato_rate_range"])
+            transform = self._draw_transform(cfg.get("transform"))
+            positions, frames, n_out = None, mel_len, n
+            if transform is not None:                            # the output time axis: frame g sits on sample g * hop
+                hop = int(ds.mel_params["hop_length"])
+                n_out = warped_length(n, transform.rate)
+                frames = warped_frames(n, hop, transform.rate)
+                if frames < 2:
+                    continue
+                positions = source_positions(frames, transform.rate, mel_len)
+            new = (base if positions is None else time_warp_curve(base, positions)) * float(2 ** (semitone / 12.0))
+            if vibrato is not None:
+                t = np.arange(frames, dtype=np.float64) * (frame_period / 1000.0)
+                new = new * 2.0 ** (np.sin(2.0 * np.pi * vibrato * t) * (depth / 12.0))
             curve = label_curve(new, ds.sr, fft_size)
-            noise = _draw_noise(cfg["noise_db"], n)
-            f0, sil, crop, start, count, first = ds._labels_and_window(curve.astype(np.float32), n)
+            noise = _draw_noise(cfg["noise_db"], n_out)
+            f0, sil, crop, start, count, first = ds._labels_and_window(curve.astype(np.float32), n_out)
             table = time_base(curve, ds.sr, frame_period, fft_size)
             req = ResynthesisRequest(base_path, float(gain), int(n), crop, start, count, first, base, curve,
                                      table.index, table.shift, table.vuv, noise_seed(curve),
-                                     _noise_window(noise, start, count))
+                                     _noise_window(noise, start, count),
+                                     None if transform is None else tuple(transform), positions)
             return torch.from_numpy(wave), torch.from_numpy(f0), torch.from_numpy(sil), first, int(wave_sr), req
         return None
 
@@ -376,7 +437,10 @@ class WorldResynthesis:
                                 _f32([r.gain for r in reqs]), _i64([r.out_len for r in reqs]), _window_noise(reqs),
                                 torch.tensor([row_rates[i] for i in rows], dtype=torch.int32),
                                 np.array([r.out_start for r in reqs], dtype=np.int64), tuple(r.curve for r in reqs),
-                                tuple((r.index, r.shift, r.vuv) for r in reqs), tuple(r.seed for r in reqs))
+                                tuple((r.index, r.shift, r.vuv) for r in reqs), tuple(r.seed for r in reqs),
+                                *((tuple(r.transform for r in reqs), tuple(r.positions for r in reqs),
+                                   tuple(len(r.base_curve) for r in reqs))
+                                  if any(r.transform is not None for r in reqs) else ()))
 
     def run(self, loader, waves, lengths, pack, host, src_sr):
         """Bring the rows' packed base files to the model rate (if needed), estimate the envelope of the frames each
@@ -388,11 +452,15 @@ class WorldResynthesis:
             ap = "d4c"                                           # the window's frames, analysed after CheapTrick
         elif cfg["aperiodicity"] > 0:
             ap = torch.full((cfg["fft_size"] // 2 + 1,), cfg["aperiodicity"], dtype=torch.float32, device=waves.device)
-        resynthesize_ragged(src, host.n.tolist(), pack.base.split([len(c) for c in host.curves]), host.curves,
+        base_len = [len(c) for c in host.curves] if host.base_len is None else list(host.base_len)
+        resynthesize_ragged(src, host.n.tolist(), pack.base.split(base_len), host.curves,
                             loader.mel.sample_rate, cfg["frame_period"], ap=ap, seeds=host.seeds, gains=pack.gains,
                             out=waves, out_rows=host.rows.numpy(), out_start=host.out_start, out_noise=pack.noise,
                             out_len=host.out_len.numpy(), tables=host.tables, q1=cfg["q1"], fft_size=cfg["fft_size"],
-                            d4c_threshold=cfg.get("d4c_threshold", 0.0))
+                            d4c_threshold=cfg.get("d4c_threshold", 0.0), transforms=host.transforms,
+                            positions=None if host.transforms is None else
+                            [source_positions(len(c), 1.0, len(c)) if p is None else p
+                             for c, p in zip(host.curves, host.positions)])
         return waves, lengths
 
 

@@ -24,6 +24,12 @@ which ``resynthesize(..., ap="d4c")`` hands to the synthesizer in place of a con
 float32 per-frame arithmetic with the smoothing sums accumulated in double, the window's ``randn`` dropped (a silent
 window is unvoiced), the linear smoothing as for CheapTrick.  Unpinned as well; the yardstick is ``tests/d4c_ref.py``
 (DESIGN.md section 24).
+
+And voice transforms between analysis and synthesis (``VoiceTransform``, ``warp_envelopes``, ``resynthesize(...,
+transform=)``, ``csrc/world_warp.hip``): the envelope read along a warped frequency axis (formant ratio), the frames at
+another rate (tempo), a spectral tilt, and the aperiodicity scaled (breath).  The synthesizer is still driven by the
+curve the item is labelled with, so the label stays exact; ``time_warp_curve`` brings a curve to the output time axis.
+The yardstick is ``tests/world_warp_ref.py``.
 """
 from __future__ import annotations
 
@@ -523,11 +529,199 @@ def label_curve(new_f0, fs, fft_size: int) -> np.ndarray:
     return f0
 
 
+# --------------------------------------------------------------------------- voice transforms in the WORLD domain
+class VoiceTransform(NamedTuple):
+    """What a resynthesis changes about the speaker, none of which touches the label: ``formant`` scales the formant
+    frequencies (the VTLP factor alpha of Jaitly & Hinton 2013, within [0.5, 2]; the map is linear up to ``f_hi`` Hz or
+    ``f_hi / formant``, whichever is lower, and runs straight to Nyquist from there), ``rate`` the speed the frames are
+    read at (1.25: a quarter faster and shorter), ``tilt`` adds that many dB per octave to the envelope around 1 kHz,
+    ``breath`` that many dB to the aperiodicity.  The defaults are the identity."""
+    formant: float = 1.0
+    rate: float = 1.0
+    tilt: float = 0.0
+    breath: float = 0.0
+    f_hi: float = 4800.0
+
+
+def warped_length(n: int, rate: float) -> int:
+    """Samples of an ``n``-sample recording read at ``rate``."""
+    return int(round(int(n) / float(rate)))
+
+
+def warped_frames(n: int, hop: int, rate: float) -> int:
+    """Frames (one per ``hop``, the first at sample 0) of an ``n``-sample recording read at ``rate``."""
+    return 1 + warped_length(n, rate) // int(hop)
+
+
+def source_positions(n_frames: int, rate: float, src_frames: int) -> np.ndarray:
+    """Where output frame g reads the source, in source frames (float64): ``min(g * rate, src_frames - 1)``."""
+    return np.minimum(np.arange(int(n_frames), dtype=np.float64) * float(rate), float(max(int(src_frames) - 1, 0)))
+
+
+def time_warp_curve(base_f0, positions) -> np.ndarray:
+    """The curve ``base_f0`` (0 = unvoiced) at the source ``positions``, host float64: linear in Hz between two voiced
+    frames; where either neighbour is unvoiced, the value of the nearer one (the earlier on a tie), so that no value is
+    an average with 0."""
+    base = _host_f0(base_f0)
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1)
+    if base.size == 0 or pos.size == 0:
+        return np.zeros(pos.size)
+    i = np.clip(np.floor(pos).astype(np.int64), 0, base.size - 1)
+    j = np.minimum(i + 1, base.size - 1)
+    t = np.clip(pos - i, 0.0, 1.0)
+    a, b = base[i], base[j]
+    return np.where((a > 0) & (b > 0), a + t * (b - a), np.where(t <= 0.5, a, b))
+
+
+def warp_envelopes(env: Envelopes, ap, positions, transforms, fs, *, first=None, out: torch.Tensor | None = None,
+                   out_offsets=None, out_strides=None):
+    """The frames of ``env`` (``cheaptrick_ragged``'s result) read at ``positions`` under ``transforms``, one launch
+    (``csrc/world_warp.hip``).  ``positions[r]``: float64 source-frame positions of row r's output frames, on the axis
+    ``env.first`` counts on, each within the frames ``env`` holds; ``transforms[r]``: a ``VoiceTransform`` (``None``:
+    the identity; ``rate`` is not read here: it is in the positions).  ``ap``: ``None``, one ``(bins,)`` float32 device
+    template for every row and frame, or an ``Envelopes`` of the same frames (``d4c_ragged``'s).  ``first[r]``: the
+    output frame ``positions[r][0]`` stands for (default 0); ``out`` / ``out_offsets`` / ``out_strides`` as for
+    ``cheaptrick_ragged``.  Returns ``(Envelopes, ap_out)``: the warped envelopes, and the warped aperiodicity as a flat
+    tensor in the same layout (``None`` without ``ap``).  There is no CPU path."""
+    check_device_tensor(env.sp, "WORLD warp")
+    fft_size = check_fft_size(env.fft_size)
+    bins = fft_size // 2 + 1
+    src_counts = _i64(env.counts)
+    R = src_counts.size
+    positions = [np.asarray(p, dtype=np.float64).reshape(-1) for p in positions]
+    transforms = [VoiceTransform() if t is None else VoiceTransform(*t) for t in transforms]
+    if len(positions) != R or len(transforms) != R:
+        raise ValueError("WORLD warp: one position array and one transform per row")
+    counts = _i64([p.size for p in positions], R)
+    rel = np.concatenate([p - float(env.first[r]) for r, p in enumerate(positions)]) if R else np.zeros(0)
+    if not np.all(np.isfinite(rel)):
+        raise ValueError("WORLD warp: positions must be finite")
+    whole = np.floor(rel)
+    frac = (rel - whole).astype(np.float32)
+    whole[frac >= 1.0] += 1.0                                   # a fraction that float32 rounds up to 1
+    frac[frac >= 1.0] = 0.0
+    pos_frame = np.ascontiguousarray(np.clip(whole, -1.0, 2.0 ** 31 - 1), dtype=np.int32)
+    params = np.ascontiguousarray([[t.formant, t.f_hi, t.tilt, t.breath] for t in transforms],
+                                  dtype=np.float32).reshape(R, 4)
+    ap_t = ap_off = ap_str = None
+    if isinstance(ap, Envelopes):
+        if ap.fft_size != fft_size or not np.array_equal(ap.first, env.first) or \
+                not np.array_equal(ap.counts, env.counts):
+            raise ValueError("WORLD warp: ap must hold the frames env holds")
+        ap_t, ap_off, ap_str = ap.sp, _i64(ap.offsets, R), _i64(ap.strides, R)
+    elif ap is not None:
+        if not torch.is_tensor(ap) or tuple(ap.shape) != (bins,):
+            raise ValueError(f"WORLD warp: ap must be one ({bins},) template or an Envelopes")
+        ap_t, ap_off, ap_str = ap, np.zeros(R, np.int64), np.zeros(R, np.int64)
+    if ap_t is not None:
+        check_device_tensor(ap_t, "WORLD warp")
+    strides = np.full(R, bins, np.int64) if out_strides is None else _i64(out_strides, R)
+    out_offsets = _i64(np.cumsum(counts * strides) - counts * strides if out_offsets is None else out_offsets, R)
+    first = np.zeros(R, np.int64) if first is None else _i64(first, R)
+    meta = plan_meta("pe_world_warp_plan_fields", R)
+    totals = np.zeros(1, np.int64)
+    _lib.check(_lib.load().pe_world_warp_plan(
+        R, *host_ptrs(src_counts, _i64(env.offsets, R), _i64(env.strides, R), ap_off, ap_str, counts, out_offsets,
+                      strides, pos_frame, frac, params), float(fs), fft_size, *host_ptrs(meta, totals)),
+        "pe_world_warp_plan")
+    live = counts > 0
+    last = np.maximum(src_counts - 1, 0)
+    if env.sp.numel() < int((_i64(env.offsets) + last * _i64(env.strides) + bins)[live].max(initial=0)):
+        raise ValueError("WORLD warp: env.sp is smaller than its layout addresses")
+    if ap_t is not None and ap_t.numel() < int((ap_off + last * ap_str + bins)[live].max(initial=0)):
+        raise ValueError("WORLD warp: ap is smaller than its layout addresses")
+    need = int((out_offsets + np.maximum(counts - 1, 0) * strides + bins)[live].max(initial=0))
+    if out is None:
+        out = torch.empty((max(need, 1),), dtype=torch.float32, device=env.sp.device)
+    else:
+        check_device_tensor(out, "WORLD warp")
+        if out.numel() < need:
+            raise ValueError("WORLD warp: the output is smaller than the plan addresses")
+    ap_out = None if ap_t is None else torch.empty_like(out)
+    if R and int(totals[0]):
+        dev = env.sp.device
+        up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+        meta_d, pos_d, frac_d, params_d = up(meta), up(pos_frame), up(frac), up(params)
+        with torch.cuda.device(dev):
+            ops._call("pe_world_warp", env.sp.data_ptr(), _lib.ptr(ap_t), meta_d.data_ptr(), meta.ctypes.data,
+                      pos_d.data_ptr(), frac_d.data_ptr(), params_d.data_ptr(), R, float(fs), fft_size,
+                      out.data_ptr(), _lib.ptr(ap_out), _lib.stream_ptr(),
+                      work=float(int(totals[0]) * bins * 4 * (3 if ap_t is None else 6)))
+    return Envelopes(out, out_offsets, strides, first, counts, fft_size), ap_out
+
+
+def _resynthesize_warped(x, lengths, f0s, new_f0s, fs, frame_period, transforms, positions, *, ap, seeds, noise,
+                         noise_offsets, gains, out, out_rows, out_start, out_len, out_noise, tables, q1, f0_floor,
+                         fft_size, d4c_threshold):
+    """``resynthesize_ragged`` with ``transforms``: the analyses run on the source frames, ``warp_envelopes`` brings
+    them to the output frames, and the synthesizer reads those in place."""
+    check_waves(x, "WORLD resynthesis")
+    R = len(row_layout(x, lengths, whole_by_default=True)[0])
+    fft_size = check_fft_size(cheaptrick_fft_size(fs, f0_floor) if fft_size is None else fft_size)
+    bins = fft_size // 2 + 1
+    labels = [label_curve(f, fs, fft_size) for f in new_f0s]
+    f0s = list(f0s)
+    transforms = [VoiceTransform() if t is None else VoiceTransform(*t) for t in transforms]
+    if len(f0s) != R or len(labels) != R or len(transforms) != R:
+        raise ValueError("WORLD resynthesis: one F0 curve, one new curve and one transform per row")
+    for t in transforms:
+        if not (math.isfinite(t.rate) and 0.25 <= t.rate <= 4.0):
+            raise ValueError("WORLD resynthesis: a transform's rate must lie in [0.25, 4]")
+    src_frames = np.array([len(f) for f in f0s], np.int64)
+    n_frames = np.array([b.size for b in labels], np.int64)
+    if positions is None:
+        positions = [source_positions(n_frames[r], transforms[r].rate, src_frames[r]) for r in range(R)]
+    positions = [np.asarray(p, dtype=np.float64).reshape(-1) for p in positions]
+    if len(positions) != R or any(p.size != n for p, n in zip(positions, n_frames)):
+        raise ValueError("WORLD resynthesis: one source position per frame of the new curve")
+    if any(n > 0 and s < 1 for n, s in zip(n_frames, src_frames)):
+        raise ValueError("WORLD resynthesis: a row with output frames needs source frames")
+    estimate = isinstance(ap, str)
+    if estimate and ap != "d4c":
+        raise ValueError(f"WORLD resynthesis: ap {ap!r} is not a mode; the one estimator is 'd4c'")
+    if ap is not None and not estimate and tuple(ap.shape) != (bins,):
+        raise ValueError(f"WORLD resynthesis: ap must be one ({bins},) template")
+    y_len = np.array([output_length(n, fs, frame_period) for n in n_frames], np.int64)
+    out_start = np.zeros(R, np.int64) if out_start is None else _i64(out_start, R)
+    out_len = y_len - out_start if out_len is None else _i64(out_len, R)
+    if out is None:
+        out = torch.zeros((max(R, 1), max(int(out_len.max(initial=0)), 1)), dtype=torch.float32, device=x.device)
+    # the output frames the planned pulses read, as without transforms ...
+    per_frame = frame_period * fs / 1000.0
+    lo = np.clip(np.floor((out_start - fft_size // 2) / per_frame).astype(np.int64) - 1, 0, n_frames)
+    hi = np.clip(np.ceil((out_start + out_len + fft_size // 2) / per_frame).astype(np.int64) + 2, 0, n_frames)
+    hi = np.where(out_len > 0, hi, lo)
+    # ... and the source frames those read: floor / ceil of their positions, and one frame either side
+    s_lo, s_hi = np.zeros(R, np.int64), np.zeros(R, np.int64)
+    for r in range(R):
+        if hi[r] > lo[r]:
+            p = positions[r][lo[r]:hi[r]]
+            s_lo[r] = min(max(int(math.floor(p.min())) - 1, 0), src_frames[r])
+            s_hi[r] = min(max(int(math.ceil(p.max())) + 2, 0), src_frames[r])
+    rows = _frame_rows("CheapTrick", x, lengths, f0s, list(zip(s_lo, s_hi - s_lo)))
+    env = cheaptrick_ragged(x, lengths, f0s, fs, frame_period, q1=q1, f0_floor=f0_floor, fft_size=fft_size, _rows=rows)
+    if estimate:
+        ap = d4c_ragged(x, lengths, f0s, fs, frame_period, threshold=d4c_threshold, fft_size=fft_size, _rows=rows)
+    base = np.cumsum(n_frames * bins) - n_frames * bins          # each row's output frame 0, whole rows laid out
+    sp = torch.empty((max(int((n_frames * bins).sum()), 1),), dtype=torch.float32, device=x.device)
+    warped, ap = warp_envelopes(env, ap, [p[a:b] for p, a, b in zip(positions, lo, hi)], transforms, fs, first=lo,
+                                out=sp, out_offsets=base + lo * bins)
+    ap_offsets = ap_strides = None
+    if ap is not None:
+        ap_offsets, ap_strides = warped.frame0_offsets(), warped.strides
+    world_synthesize_ragged(labels, warped.sp, warped.frame0_offsets(), warped.strides,
+                            torch.ones(R) if gains is None else gains, out, out_rows, out_start, out_len, fs=fs,
+                            frame_period=frame_period, fft_size=fft_size, ap=ap, ap_offsets=ap_offsets,
+                            ap_strides=ap_strides, tables=tables, noise=noise, noise_offsets=noise_offsets,
+                            seeds=seeds, out_noise=out_noise)
+    return out, labels
+
+
 def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period: float, *, ap=None, seeds=None,
                         noise=None, noise_offsets=None, gains=None, out: torch.Tensor | None = None, out_rows=None,
                         out_start=None, out_len=None, out_noise=None, tables=None, q1: float = CHEAPTRICK_Q1,
                         f0_floor: float = CHEAPTRICK_F0_FLOOR, fft_size: int | None = None,
-                        d4c_threshold: float = D4C_THRESHOLD):
+                        d4c_threshold: float = D4C_THRESHOLD, transforms=None, positions=None):
     """Analysis / resynthesis of a ragged batch: the envelope of row r of ``x`` under ``f0s[r]``
     (``cheaptrick_ragged``), then ``world_synthesize_ragged`` driven by ``label_curve(new_f0s[r])`` reading that
     envelope in place.  ``ap``: ``None``, one ``(bins,)`` float32 device template for every row and frame, or the
@@ -535,7 +729,18 @@ def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period
     analyses, into a buffer of the same layout that the synthesizer reads in place).  With
     windows (``out_start`` / ``out_len``) only the frames their pulses read are analysed: the samples of the window -+
     ``fft_size / 2``, and one frame either side for the synthesizer's frame interpolation.  The other arguments are
-    ``world_synthesize_ragged``'s. Returns ``(out, labels)``, ``labels[r]`` the float64 label curve of row r."""
+    ``world_synthesize_ragged``'s. Returns ``(out, labels)``, ``labels[r]`` the float64 label curve of row r.
+
+    ``transforms``: one ``VoiceTransform`` (or ``None``: the identity) per row changes the speaker and leaves the label
+    exact (``warp_envelopes``).  ``new_f0s[r]`` is then on the output time axis, one value per output frame, and output
+    frame g reads the source at ``positions[r][g]`` frames (default ``min(g * rate, len(f0s[r]) - 1)``); only the
+    source frames the window's output frames read are analysed.  Without ``transforms`` nothing of this runs."""
+    if transforms is not None:
+        return _resynthesize_warped(x, lengths, f0s, new_f0s, fs, frame_period, transforms, positions, ap=ap,
+                                    seeds=seeds, noise=noise, noise_offsets=noise_offsets, gains=gains, out=out,
+                                    out_rows=out_rows, out_start=out_start, out_len=out_len, out_noise=out_noise,
+                                    tables=tables, q1=q1, f0_floor=f0_floor, fft_size=fft_size,
+                                    d4c_threshold=d4c_threshold)
     check_waves(x, "WORLD resynthesis")
     R = len(row_layout(x, lengths, whole_by_default=True)[0])
     fft_size = check_fft_size(cheaptrick_fft_size(fs, f0_floor) if fft_size is None else fft_size)
@@ -580,12 +785,15 @@ def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period
 
 def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, ap=None, seed: int = 0,
                  noise: torch.Tensor | None = None, q1: float = CHEAPTRICK_Q1, f0_floor: float = CHEAPTRICK_F0_FLOOR,
-                 fft_size: int | None = None, d4c_threshold: float = D4C_THRESHOLD):
+                 fft_size: int | None = None, d4c_threshold: float = D4C_THRESHOLD,
+                 transform: VoiceTransform | None = None):
     """The recording ``x`` (1-D float32 device wave with the curve ``f0``) resynthesized on ``new_f0``: its CheapTrick
     envelope through WORLD's ``Synthesis``, with no aperiodicity (``ap=None``), one ``(bins,)`` template, or the
     recording's own as D4C estimates it (``ap="d4c"``, ``d4c_threshold``).  Returns ``(audio, label)``: the 1-D float32 device wave of
     ``int(len(f0) * frame_period * fs / 1000)`` samples and the float64 host curve it was synthesized from
-    (``label_curve``), exact by construction."""
+    (``label_curve``), exact by construction.  With ``transform`` (a ``VoiceTransform``) the speaker changes as well:
+    ``new_f0`` then has one value per output frame (``time_warp_curve`` brings a curve there), and the wave has
+    ``int(len(new_f0) * frame_period * fs / 1000)`` samples."""
     if not torch.is_tensor(x) or x.dim() != 1:
         raise RuntimeError("WORLD resynthesis (HIP) needs a 1-D float32 device wave; no CPU fallback exists")
     n = output_length(len(_host_f0(new_f0)), fs, frame_period)
@@ -594,7 +802,8 @@ def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, 
     out, labels = resynthesize_ragged(x, None, [f0], [new_f0], fs, frame_period, ap=ap, seeds=[seed],
                                       noise=None if noise is None else noise.reshape(-1),
                                       noise_offsets=None if noise is None else [0], q1=q1, f0_floor=f0_floor,
-                                      fft_size=fft_size, d4c_threshold=d4c_threshold)
+                                      fft_size=fft_size, d4c_threshold=d4c_threshold,
+                                      transforms=None if transform is None else [transform])
     return out[0, :n], labels[0]
 
 
