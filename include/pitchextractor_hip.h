@@ -472,6 +472,12 @@ int pe_resample_plan_destroy(pe_resample_plan* plan);
 long pe_resample_out_len(const pe_resample_plan* plan, long n_in);
 int pe_resample_forward(const pe_resample_plan* plan, const float* x, int batch, int n_in, long x_stride, float* y,
                         long y_stride, int n_out, void* stream);
+/* The transpose of pe_resample_forward: dx (batch rows of n_in, every element written) from dy (batch rows of n_out
+ * <= pe_resample_out_len(n_in); dy past n_out is not read).  One thread per input sample gathers its terms with one
+ * fmaf chain in ascending output index over the plan's own taps, so a row's result depends on the row alone.
+ * PE_E_ARG as for the forward; PE_E_UNSUPPORTED: batch > 65535, or a ratio whose tile of dy passes 64 KB of LDS. */
+int pe_resample_backward(const pe_resample_plan* plan, const float* dy, int batch, int n_out, long dy_stride,
+                         float* dx, long dx_stride, int n_in, void* stream);
 
 /* Multi-rate ragged resampler: one plan for a list of up to 16 source rates (a rate equal to new_freq copies;
  * a plan of copies only allocates nothing on the device) and one target; same taps as pe_resample_plan_create.  pe_resample_ragged_forward resamples `batch` rows in one launch:
@@ -488,6 +494,15 @@ long pe_resample_ragged_out_len(const pe_resample_ragged_plan* plan, int rate_in
 int pe_resample_ragged_forward(const pe_resample_ragged_plan* plan, const float* x, const long* x_off, const int* n_in,
                                const int* rate_idx, const int* host_n_in, const int* host_rate_idx, int batch,
                                float* y, long y_stride, int y_width, void* stream);
+/* The transpose of pe_resample_ragged_forward in one launch: row r reads its pe_resample_ragged_out_len values at
+ * dy + r * dy_stride (nothing past them) and writes n_in[r] gradients at dx + x_off[r], the layout the forward read.
+ * dx_width > 0: padded rows, each also zeroed from n_in[r] to dx_width; dx_width == 0: packed rows, nothing else is
+ * written.  A row at the target rate is a copy of dy.  Each row is bit-identical to pe_resample_backward on that row
+ * alone.  PE_E_ARG: null pointer, rate index out of range, a row's output longer than dy_stride, a row longer than
+ * dx_width; PE_E_UNSUPPORTED as for pe_resample_backward.  Asynchronous on `stream`; no allocation. */
+int pe_resample_ragged_backward(const pe_resample_ragged_plan* plan, const float* dy, long dy_stride,
+                                const long* x_off, const int* n_in, const int* rate_idx, const int* host_n_in,
+                                const int* host_rate_idx, int batch, float* dx, int dx_width, void* stream);
 
 /* ---- pitch-shift augmentation (reference meldataset.py:324-517 -> librosa.effects.pitch_shift defaults) ----
  * STFT 2048 / hop 512 / periodic Hann / centre zero padding -> phase vocoder at rate 2^(-n_steps/12) -> iSTFT to

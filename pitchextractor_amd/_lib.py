@@ -124,6 +124,8 @@ PROTOTYPES = {
     "pe_resample_plan_destroy": (_i, [_p]),
     "pe_resample_out_len": (_l, [_p, _l]),
     "pe_resample_forward": (_i, [_p, _p, _i, _i, _l, _p, _l, _i, _p]),
+    "pe_resample_backward": (_i, [_p, _p, _i, _i, _l, _p, _l, _i, _p]),
+    "pe_resample_ragged_backward": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _i, _p, _i, _p]),
     "pe_resample_ragged_plan_create": (_i, [C.POINTER(_p), _ip, _i, _i, _i, _f]),
     "pe_resample_ragged_plan_destroy": (_i, [_p]),
     "pe_resample_ragged_out_len": (_l, [_p, _i, _l]),

@@ -33,6 +33,60 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   y[(long)blockIdx.y * y_stride + n] = acc;
 }
 
+// ---- backward: the exact transpose, in gather form ----------------------------------------------------------------
+// dx[q] = sum over (j, p), ascending n = j neu + p < n_out, of k[p][q + width - j orig] * dy[n], for the phase
+// periods j whose tap index i = q + width - j orig lies in [0, taps): j = jhi - m with jhi = (q + width) / orig and
+// m < M = ceil(taps / orig), so i = (q + width) % orig + m orig.  One thread owns one q and runs one fmaf chain, m
+// descending (j ascending) and p ascending: the result is a function of the row alone.  A workgroup takes RS_TILE
+// consecutive q.  It stages the dy span its periods cover in LDS: for a large orig the lanes of a wave share j and
+// the read is a broadcast, for a small orig (8 kHz -> 24 kHz: orig 1) every lane has its own j and reads dy at
+// stride neu, which LDS serves and a global load would not coalesce.  The taps come from the forward's own table:
+// for fixed (m, p) neighbouring q read neighbouring k[p][i], a coalesced load that L1/L2 serve.
+constexpr int RS_TILE = 256;
+constexpr int RS_MAX_SPAN = 16384;                      // 64 KB of LDS per workgroup
+
+// floats of dy one backward tile stages: the periods of RS_TILE consecutive q, plus the M - 1 before the first
+long backward_span(int orig, int neu, int taps) {
+  const long m = (taps + orig - 1) / orig;
+  return ((long)(RS_TILE + orig - 2) / orig + m) * neu;
+}
+
+__device__ __forceinline__ void resample_backward_tile(const float* __restrict__ dyb, int n_out,
+                                                       float* __restrict__ dxb, int n_in, int q0,
+                                                       const float* __restrict__ k, int orig, int neu, int width,
+                                                       int taps, float* ds) {
+  const int q_last = min(q0 + RS_TILE, n_in) - 1;
+  const int M = (taps + orig - 1) / orig;
+  const int j0 = max(0, (q0 + width) / orig - (M - 1));
+  const int n_lo = j0 * neu;
+  const int span = (int)min((long)((q_last + width) / orig + 1) * neu, (long)n_out) - n_lo;
+  for (int s = threadIdx.x; s < span; s += RS_TILE) ds[s] = dyb[n_lo + s];
+  __syncthreads();
+  const int q = q0 + threadIdx.x;
+  if (q >= n_in) return;
+  const int jhi = (q + width) / orig, r = q + width - jhi * orig;
+  float acc = 0.f;
+  for (int m = M - 1; m >= 0; --m) {
+    const int j = jhi - m, i = r + m * orig;
+    if (j < 0 || i >= taps) continue;
+    const long n0 = (long)j * neu;
+    const int pe = (int)min((long)neu, (long)n_out - n0);  // the n < n_out cut; <= 0 past the last period
+    const float* kp = k + i;
+    const float* dp = ds + (n0 - n_lo);
+    for (int p = 0; p < pe; ++p) acc = fmaf(kp[(long)p * taps], dp[p], acc);
+  }
+  dxb[q] = acc;
+}
+
+__global__ __launch_bounds__(RS_TILE) void resample_backward_kernel(const float* __restrict__ dy, long dy_stride,
+                                                                    int n_out, float* __restrict__ dx, long dx_stride,
+                                                                    int n_in, const float* __restrict__ k, int orig,
+                                                                    int neu, int width, int taps) {
+  extern __shared__ float ds[];
+  resample_backward_tile(dy + (long)blockIdx.y * dy_stride, n_out, dx + (long)blockIdx.y * dx_stride, n_in,
+                         blockIdx.x * RS_TILE, k, orig, neu, width, taps, ds);
+}
+
 int gcd_i(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
 
 // The [neu][taps] tap table of torchaudio's _get_sinc_resample_kernel for the reduced ratio orig -> neu, and its
@@ -102,6 +156,20 @@ extern "C" int pe_resample_forward(const pe_resample_plan* plan, const float* x,
   return PE_OK;
 }
 
+extern "C" int pe_resample_backward(const pe_resample_plan* plan, const float* dy, int batch, int n_out, long dy_stride,
+                                    float* dx, long dx_stride, int n_in, void* stream) {
+  if (!plan || !dy || !dx || batch < 0 || n_in < 0 || n_out < 0 || dy_stride < n_out || dx_stride < n_in) return PE_E_ARG;
+  if ((long)n_out > pe_resample_out_len(plan, n_in)) return PE_E_ARG;
+  if (batch == 0 || n_in == 0) return PE_OK;
+  const long span = backward_span(plan->orig, plan->neu, plan->taps);
+  if (batch > 65535 || span > RS_MAX_SPAN) return PE_E_UNSUPPORTED;
+  hipLaunchKernelGGL(resample_backward_kernel, dim3(pe_cdiv(n_in, RS_TILE), batch), dim3(RS_TILE),
+                     (size_t)span * sizeof(float), pe_stream(stream), dy, dy_stride, n_out, dx, dx_stride, n_in,
+                     plan->d_kernel, plan->orig, plan->neu, plan->width, plan->taps);
+  PE_LAUNCH_CHECK();
+  return PE_OK;
+}
+
 // ---- multi-rate ragged resampler --------------------------------------------------------------------------------
 // One launch resamples a batch whose rows come at different source rates.  Row r (input at x + x_off[r], n_in[r]
 // samples, source rate rates[rate_idx[r]]) writes its out_len outputs at y + r * y_stride and zeros from there to
@@ -118,9 +186,7 @@ struct pe_resample_rate {
 
 namespace {
 
-constexpr int RS_TILE = 256;
 constexpr int RS_MAX_RATES = 16;
-constexpr int RS_MAX_SPAN = 16384;                      // 64 KB of LDS per workgroup
 
 struct rs_rates { pe_resample_rate r[RS_MAX_RATES]; };  // kernel argument (byref kernarg: no scratch)
 
@@ -130,6 +196,7 @@ struct pe_resample_ragged_plan {
   int n_rates, span;              // span: largest LDS input span of one tile, floats
   rs_rates rates;
   float* d_table;                 // every non-copy rate's [neu][taps] table; null when all rates copy
+  long bspan;                     // largest LDS dy span of one backward tile, floats (may pass RS_MAX_SPAN)
 };
 
 namespace {
@@ -170,6 +237,34 @@ __global__ __launch_bounds__(RS_TILE) void resample_ragged_kernel(const float* _
   yb[n] = acc;
 }
 
+// Backward of the launch above.  Row r reads its own out_len values at dy + r * dy_stride and writes n_in[r]
+// gradients at dx + x_off[r], where the forward read its input; with dx_width > 0 (padded rows) it also writes zeros
+// from n_in[r] to dx_width, with dx_width == 0 (packed rows) nothing else.  A computing tile is
+// resample_backward_tile, as in resample_backward_kernel: the same bits as pe_resample_backward on the row alone.
+__global__ __launch_bounds__(RS_TILE) void resample_ragged_backward_kernel(const float* __restrict__ dy, long dy_stride,
+                                                                           const long* __restrict__ x_off,
+                                                                           const int* __restrict__ n_in,
+                                                                           const int* __restrict__ rate_idx,
+                                                                           float* __restrict__ dx, int dx_width,
+                                                                           const float* __restrict__ table,
+                                                                           rs_rates rates) {
+  extern __shared__ float ds[];
+  const int row = blockIdx.y;
+  const int q0 = blockIdx.x * RS_TILE, q = q0 + threadIdx.x;
+  const pe_resample_rate d = rates.r[rate_idx[row]];
+  const int nin = n_in[row];
+  const float* dyb = dy + (long)row * dy_stride;
+  float* dxb = dx + x_off[row];
+  if (q0 >= nin || d.neu == 0) {                        // padding tile, or a copied row
+    if (q < nin) dxb[q] = dyb[q];
+    else if (q < dx_width) dxb[q] = 0.f;
+    return;
+  }
+  const int n_out = (int)(((long)nin * d.neu + d.orig - 1) / d.orig);
+  resample_backward_tile(dyb, n_out, dxb, nin, q0, table + d.koff, d.orig, d.neu, d.width, d.taps, ds);
+  if (q >= nin && q < dx_width) dxb[q] = 0.f;
+}
+
 long ragged_out_len(const pe_resample_rate& d, long n_in) {
   return d.neu ? (n_in * d.neu + d.orig - 1) / d.orig : n_in;
 }
@@ -185,6 +280,7 @@ extern "C" int pe_resample_ragged_plan_create(pe_resample_ragged_plan** plan_out
   rs_rates rates = {};
   std::vector<float> all, k;
   int span = 0;
+  long bspan = 0;
   for (int r = 0; r < n_rates; ++r) {
     pe_resample_rate& d = rates.r[r];
     if (orig_freqs[r] == new_freq) { d = pe_resample_rate{1, 0, 0, 0, 0}; continue; }
@@ -195,6 +291,8 @@ extern "C" int pe_resample_ragged_plan_create(pe_resample_ragged_plan** plan_out
     const long s = (long)((d.neu + RS_TILE - 2) / d.neu) * d.orig + d.taps;
     if (s > RS_MAX_SPAN) return PE_E_UNSUPPORTED;
     if (s > span) span = (int)s;
+    const long b = backward_span(d.orig, d.neu, d.taps);
+    if (b > bspan) bspan = b;
   }
   float* d = nullptr;                                   // a plan of copies only touches no device
   if (!all.empty()) {
@@ -202,7 +300,7 @@ extern "C" int pe_resample_ragged_plan_create(pe_resample_ragged_plan** plan_out
     hipError_t e = hipMemcpy(d, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return (int)e; }
   }
-  *plan_out = new pe_resample_ragged_plan{n_rates, span, rates, d};
+  *plan_out = new pe_resample_ragged_plan{n_rates, span, rates, d, bspan};
   return PE_OK;
 }
 
@@ -235,6 +333,29 @@ extern "C" int pe_resample_ragged_forward(const pe_resample_ragged_plan* plan, c
   hipLaunchKernelGGL(resample_ragged_kernel, dim3(pe_cdiv(y_width, RS_TILE), batch), dim3(RS_TILE),
                      (size_t)plan->span * sizeof(float), pe_stream(stream), x, x_off, n_in, rate_idx, y, y_stride,
                      y_width, plan->d_table, plan->rates);
+  PE_LAUNCH_CHECK();
+  return PE_OK;
+}
+
+extern "C" int pe_resample_ragged_backward(const pe_resample_ragged_plan* plan, const float* dy, long dy_stride,
+                                           const long* x_off, const int* n_in, const int* rate_idx,
+                                           const int* host_n_in, const int* host_rate_idx, int batch, float* dx,
+                                           int dx_width, void* stream) {
+  if (!plan || !dy || !x_off || !n_in || !rate_idx || !host_n_in || !host_rate_idx || !dx || batch < 0 ||
+      dx_width < 0 || dy_stride < 0)
+    return PE_E_ARG;
+  int cover = dx_width;                                 // samples of a row the grid spans
+  for (int r = 0; r < batch; ++r) {
+    if (host_rate_idx[r] < 0 || host_rate_idx[r] >= plan->n_rates || host_n_in[r] < 0) return PE_E_ARG;
+    if (ragged_out_len(plan->rates.r[host_rate_idx[r]], host_n_in[r]) > dy_stride) return PE_E_ARG;
+    if (dx_width > 0 && host_n_in[r] > dx_width) return PE_E_ARG;
+    if (host_n_in[r] > cover) cover = host_n_in[r];
+  }
+  if (batch == 0 || cover == 0) return PE_OK;
+  if (batch > 65535 || plan->bspan > RS_MAX_SPAN) return PE_E_UNSUPPORTED;
+  hipLaunchKernelGGL(resample_ragged_backward_kernel, dim3(pe_cdiv(cover, RS_TILE), batch), dim3(RS_TILE),
+                     (size_t)plan->bspan * sizeof(float), pe_stream(stream), dy, dy_stride, x_off, n_in, rate_idx, dx,
+                     dx_width, plan->d_table, plan->rates);
   PE_LAUNCH_CHECK();
   return PE_OK;
 }

@@ -73,13 +73,29 @@ def waveform_to_mel(audio, mel_transform: MelSpectrogram | None = None, device="
 
 def f0_from_wave(model: JDCNet, waves: torch.Tensor, lengths: torch.Tensor | None = None,
                  mel_transform: MelSpectrogram | None = None, *, max_frames: int | None = None,
-                 frame_start: torch.Tensor | None = None):
+                 frame_start: torch.Tensor | None = None, sample_rate: int | None = None, rates=None):
     """The model's outputs for (B, N) float32 device audio with the autograd graph intact: ``log_mel_batch`` (or
     ``log_mel_ragged`` with int32 device ``lengths``), the transpose to the model's (B, 1, T, n_mels) input, the
     model.  With a frozen ``model`` (``load_model(..., frozen=True)``) and ``waves`` that require grad, a loss on the
     result back-propagates to the waveform through native kernels only (the F0 loss of something that emits audio).
-    ``max_frames``: frames per row, padded or truncated (default: the frames of N samples)."""
+    ``max_frames``: frames per row, padded or truncated (default: the frames of N samples).
+
+    Audio at another rate than the mel transform's: ``sample_rate=R`` for (B, N) rows all at rate ``R`` (``Resampler``
+    to the model rate, then ``log_mel_batch``), or ``rates=[...]`` with ``lengths`` as host sequences for a batch
+    that mixes rates, padded (B, N) or packed 1-D (``RaggedResampler``, then ``log_mel_ragged`` on the resampler's
+    ``out_lengths``).  Both resamplers are differentiable, so the gradient reaches the audio at its own rate.
+    ``max_frames`` then defaults to the frames of the longest resampled row."""
     tf = mel_transform or _default_mel()
+    if sample_rate is not None and rates is not None:
+        raise ValueError("f0_from_wave: give sample_rate (one rate) or rates (one per row), not both")
+    if sample_rate is not None:
+        if lengths is not None:
+            raise ValueError("f0_from_wave: sample_rate takes whole rows; pass rates= with lengths for ragged rows")
+        waves = _resampler(int(sample_rate), tf.sample_rate)(waves)
+    elif rates is not None:
+        if lengths is None or isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            raise ValueError("f0_from_wave: rates needs the rows' lengths as a host sequence")
+        waves, lengths = _ragged_resampler(tf.sample_rate)(waves, rates, [int(n) for n in lengths])
     T = int(max_frames) if max_frames is not None else tf.num_frames(waves.shape[1])
     if lengths is None:
         mel = tf.log_mel_batch(waves, max_frames=T)
@@ -299,6 +315,24 @@ def _default_mel() -> MelSpectrogram:
     if _DEFAULT_MEL is None:
         _DEFAULT_MEL = MelSpectrogram(**DEFAULT_MEL_PARAMS)
     return _DEFAULT_MEL
+
+
+_RESAMPLERS: dict = {}
+
+
+def _resampler(orig: int, target: int):
+    """The cached ``Resampler(orig, target)`` (its plan owns a device table)."""
+    from .resample import Resampler
+    if (orig, target) not in _RESAMPLERS:
+        _RESAMPLERS[orig, target] = Resampler(orig, target)
+    return _RESAMPLERS[orig, target]
+
+
+def _ragged_resampler(target: int):
+    from .resample import RaggedResampler
+    if target not in _RESAMPLERS:
+        _RESAMPLERS[target] = RaggedResampler(target)
+    return _RESAMPLERS[target]
 
 
 def mel_chunks(waves, plan: dict, mel_transform: MelSpectrogram | None = None) -> torch.Tensor:

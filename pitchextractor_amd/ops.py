@@ -1184,6 +1184,95 @@ def mel_backward(mel, wave, grad_out, *, lengths=None, frame_start=None, log=Tru
     return grad_wave
 
 
+def _grad_rows(grad_out, who: str) -> torch.Tensor:
+    """``grad_out`` as (B, W) float32 device rows of unit element stride that do not overlap (what autograd hands over
+    may be an expanded scalar); a host tensor is refused."""
+    if not isinstance(grad_out, torch.Tensor) or not grad_out.is_cuda or grad_out.dtype != torch.float32:
+        raise RuntimeError(f"{who} (HIP) needs a float32 device grad_out; no CPU fallback exists")
+    _chk(grad_out.dim() == 2, f"{who}: grad_out: expected (B, n_out) rows")
+    B, W = grad_out.shape
+    if (W > 1 and grad_out.stride(1) != 1) or (B > 1 and grad_out.stride(0) < W):
+        grad_out = grad_out.contiguous()
+    return grad_out
+
+
+def resample_backward(resampler, grad_out, n_in):
+    """Gradient of ``Resampler`` with respect to its input (``pe_resample_backward``): ``grad_out`` (B, n_out) float32
+    device rows, d loss / d y of ``resampler(x)`` for x of (B, n_in), read at its own row stride; ``n_out`` may stay
+    below ``resampler.out_len(n_in)`` (the missing outputs carry no gradient).  Returns (B, n_in) float32, every
+    element written by the kernel: the exact transpose of the forward over the same float32 taps, each sample one
+    ``fmaf`` chain in ascending output index.  Nothing of the forward is needed; the operator is linear."""
+    g = _grad_rows(grad_out, "resample_backward")
+    n_in = int(n_in)
+    B, n_out = g.shape
+    _chk(n_in >= 0 and n_out <= resampler.out_len(n_in), "resample_backward: grad_out is longer than the output of "
+         "n_in samples")
+    if resampler.orig_freq == resampler.new_freq:
+        return g
+    dx = torch.empty((B, n_in), dtype=torch.float32, device=g.device)
+    if B == 0 or n_in == 0:
+        return dx
+    ld = g.stride(0) if B > 1 else max(n_out, g.stride(0))
+    with torch.cuda.device(g.device):
+        # algorithmic bytes: grad_out read once, the gradient written once
+        _call("pe_resample_backward", resampler._get_plan(g.device), g.data_ptr(), B, n_out, ld, dx.data_ptr(),
+              dx.stride(0), n_in, _s(), work=float(4 * B * (n_out + n_in)))
+    return dx
+
+
+def resample_ragged_backward(resampler, grad_out, rates, lengths, *, packed: bool, width: int | None = None,
+                             out=None):
+    """Gradient of ``RaggedResampler`` with respect to its input in ONE launch (``pe_resample_ragged_backward``):
+    ``grad_out`` (B, W) float32 device rows, d loss / d y of ``resampler(x, rates, lengths)``; row r is read up to its
+    own output length and never past it.  ``rates``, ``lengths``: the host sequences of the forward.  Returns the
+    gradient in the layout the forward read: ``packed=True`` a flat tensor of the rows back to back (``width``: its
+    size, default ``sum(lengths)``; the slack is zero), ``packed=False`` (B, ``width``) padded rows (default
+    ``max(lengths)``), zero past each row's length; ``out``: a contiguous tensor of that layout to write instead (its
+    last dimension is the width; every element of it is written).  Row r equals ``resample_backward`` on that row alone bit for bit;
+    a row at the target rate is a copy."""
+    g = _grad_rows(grad_out, "resample_ragged_backward")
+    rates, lengths = [int(r) for r in rates], [int(n) for n in lengths]
+    B = g.shape[0]
+    _chk(len(rates) == B and len(lengths) == B, "resample_ragged_backward: one rate and one length per grad_out row")
+    _chk(all(n >= 0 for n in lengths), "resample_ragged_backward: a row length is negative")
+    _chk(all(resampler.out_len(r, n) <= g.shape[1] for r, n in zip(rates, lengths)),
+         "resample_ragged_backward: grad_out is narrower than a row's output")
+    total = sum(lengths) if packed else max(lengths, default=0)
+    if out is not None:
+        _chk(_dense(out, "out").device == g.device and (out.dim() == 1 if packed else out.dim() == 2 and
+                                                        out.shape[0] == B),
+             "resample_ragged_backward: out: expected a flat tensor for packed rows, (B, width) for padded rows")
+        width = out.shape[-1]
+    width = total if width is None else int(width)
+    _chk(width >= total, "resample_ragged_backward: width is below the rows' extent")
+    if packed:
+        dx = torch.empty((width,), dtype=torch.float32, device=g.device) if out is None else out
+        if width > total:
+            dx[total:].zero_()
+        offsets, acc = [], 0
+        for n in lengths:
+            offsets.append(acc)
+            acc += n
+    else:
+        dx = torch.empty((B, width), dtype=torch.float32, device=g.device) if out is None else out
+        offsets = [r * width for r in range(B)]
+    if total == 0:                                          # no row has a sample: nothing to launch
+        return dx.zero_()
+    distinct = tuple(sorted(set(rates)))
+    index = {r: k for k, r in enumerate(distinct)}
+    host32 = torch.tensor(lengths + [index[r] for r in rates], dtype=torch.int32).pin_memory()
+    host64 = torch.tensor(offsets, dtype=torch.int64).pin_memory()
+    dev32 = host32.to(g.device, non_blocking=True)
+    dev64 = host64.to(g.device, non_blocking=True)
+    ld = g.stride(0) if B > 1 else max(g.shape[1], g.stride(0))
+    with torch.cuda.device(g.device):
+        _call("pe_resample_ragged_backward", resampler._get_plan(distinct, g.device), g.data_ptr(), ld,
+              dev64.data_ptr(), dev32.data_ptr(), dev32[B:].data_ptr(), host32[:B].data_ptr(), host32[B:].data_ptr(), B,
+              dx.data_ptr(), 0 if packed else width, _s(),
+              work=float(4 * (sum(lengths) + sum(resampler.out_len(r, n) for r, n in zip(rates, lengths)))))
+    return dx
+
+
 def stitch_chunks(x, runs, runs_d, out, det=None, det_out=None):
     """Chunk outputs to stitched rows by a run table (``pe_stitch_chunks``, ``inference.chunk_plan``): ``x``
     (n_chunks, chunk_size, C) or (n_chunks, chunk_size) float32 with unit stride over C and evenly spaced frames,

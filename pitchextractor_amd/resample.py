@@ -9,10 +9,52 @@ import math
 import torch
 
 from . import _lib, ops
+from .mel import _tracked
 from .ragged import check_waves, row_layout
 
 
+class _ResampleOfWave(torch.autograd.Function):
+    """The forward launch as it is, with ``ops.resample_backward`` (csrc/resample.hip) behind it.  The operator is
+    linear: only the input's shape is kept.  ``run(wave)`` is the untracked call."""
+
+    @staticmethod
+    def forward(ctx, wave, resampler, run):
+        ctx.resampler, ctx.shape = resampler, tuple(wave.shape)
+        return run(wave)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        single = len(ctx.shape) == 1
+        grad = ops.resample_backward(ctx.resampler, grad_out.unsqueeze(0) if single else grad_out, ctx.shape[-1])
+        return (grad[0] if single else grad), None, None
+
+
+class _RaggedResampleOfWave(torch.autograd.Function):
+    """``RaggedResampler``'s launch with ``ops.resample_ragged_backward`` behind it; the gradient comes in the layout of
+    the input (packed or padded rows).  ``out_lengths`` carries no graph."""
+
+    @staticmethod
+    def forward(ctx, x, resampler, run, rates, lengths):
+        ctx.resampler, ctx.shape, ctx.rates, ctx.lengths = resampler, tuple(x.shape), rates, lengths
+        y, out_lengths = run(x)
+        ctx.mark_non_differentiable(out_lengths)
+        return y, out_lengths
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, _grad_lengths):
+        grad = ops.resample_ragged_backward(ctx.resampler, grad_y, ctx.rates, ctx.lengths,
+                                            packed=len(ctx.shape) == 1, width=ctx.shape[-1])
+        return grad, None, None, None, None
+
+
 class Resampler:
+    """``resampler(wave)``: (N,) or (B, N) float32 device audio at ``orig_freq`` -> ``out_len(N)`` samples at
+    ``new_freq``.  Differentiable with respect to the wave: when grad is enabled and the wave requires grad, the same
+    values come from the same launch with a ``grad_fn`` (``ops.resample_backward``, once differentiable); otherwise
+    nothing is recorded."""
+
     def __init__(self, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
         self.lowpass_filter_width, self.rolloff = int(lowpass_filter_width), float(rolloff)
@@ -43,6 +85,11 @@ class Resampler:
             raise RuntimeError("Resampler (HIP) needs float32 device audio; no CPU fallback exists")
         if self.orig_freq == self.new_freq:
             return wave
+        if _tracked(wave):
+            return _ResampleOfWave.apply(wave, self, self._resample)
+        return self._resample(wave)
+
+    def _resample(self, wave: torch.Tensor) -> torch.Tensor:
         single = wave.dim() == 1
         x = wave.unsqueeze(0) if single else wave
         if x.stride(-1) != 1:
@@ -58,7 +105,9 @@ class Resampler:
 class RaggedResampler:
     """Rows at mixed source rates to one target rate in ONE launch (``pe_resample_ragged_forward``).  Row r equals
     ``Resampler(rates[r], target_sr)`` on that row alone, bit for bit; a row already at the target is copied.  One
-    plan is cached per set of source rates and device."""
+    plan is cached per set of source rates and device.  Differentiable with respect to ``x`` as ``Resampler`` is
+    (``ops.resample_ragged_backward``, one launch, the gradient in ``x``'s own layout); ``out_lengths`` carries no
+    graph."""
 
     def __init__(self, target_sr: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
         self.target_sr = int(target_sr)
@@ -100,6 +149,8 @@ class RaggedResampler:
         B = len(rates)
         if len(lengths) != B:
             raise ValueError("one rate per row")
+        if _tracked(x):                                      # the same call below, with the backward behind it
+            return _RaggedResampleOfWave.apply(x, self, lambda w: self(w, rates, lengths, y_width), rates, lengths)
         distinct = tuple(sorted(set(rates)))
         index = {r: k for k, r in enumerate(distinct)}
         ridx = [index[r] for r in rates]
