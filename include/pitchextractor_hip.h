@@ -999,6 +999,48 @@ int pe_augment_biquad(const float* x, const long* meta, const long* host_meta, i
                       const double* sos, const double* host_sos, const int* n_stages, const int* host_n_stages,
                       float* y, void* stream);
 
+/* ---- Codec stress conditions (reference Utils/codec_and_bandwidth_torture.ipynb): a build-defined MDCT transform
+ * codec and G.711 mu-law on ragged batches (csrc/codec.hip; the specification is DESIGN.md section 28) --------------
+ * frame = M in {256, 512, 1024} (anything else: PE_E_UNSUPPORTED).  A row of n >= 1 samples has ceil(n / M) + 1
+ * frames, an empty row none; frame f reads the 2M samples from (f - 1) M on, zero outside the row.
+ * pe_codec_plan (host only): row r has n[r] samples at x + x_off[r] and is written to y + y_off[r].  consts4 = {M,
+ * floats of the table, bands, entries of a step table}; meta (n_rows x pe_codec_plan_fields() int64, to be copied to
+ * the device) = per row {sample offset, samples, output offset, frames, frame prefix}; totals2 = {samples, frames}.
+ * pe_codec_bands (host only): the band edges e_0 = 0, e_{b+1} = min(M, e_b + max(4, 4 (e_b / 32))) into edges (room
+ * for at least 49 ints); returns the number of bands.
+ * tables (n_table floats, device): exp(-2 pi i m / (M / 2)) for m < M / 2, exp(-i pi (8 n + 1) / 8M) for n < M / 2,
+ * the window sin(pi (j + 0.5) / 2M) for j < 2M, T[i] = 2^((i - 224) / 4) and R[i] = 2^(-(i - 224) / 4) for i < 448,
+ * all rounded from float64.
+ * pe_codec_mdct: the rows' frames, in plan order, to coefs (frames x M).  One launch.
+ * pe_codec_quantize: frames x M coefficients -> q (int32), the dequantised coefficients, and per frame the gain index
+ * g and the bits of the cost model.  Bins >= k_c count as zero; 1 <= k_c <= M; budget >= 8 + the bands that begin
+ * below k_c (else PE_E_ARG).  The arithmetic is exact, so the result is that of tests/codec_ref.py bit for bit.  One
+ * launch.
+ * pe_codec_imdct: coefs (frames x M, plan order) to the rows of y; workspace: pe_codec_workspace_bytes(M, frames), the
+ * windowed frames, which a second launch gathers.  Two launches.
+ * pe_codec_apply: mdct, quantize and imdct fused; the coefficients stay in LDS; the result is bit for bit that of the
+ * three calls.  g and bits (one int32 per frame) may be null.  Two launches.
+ * pe_codec_mulaw: G.711 mu-law encoded and decoded, y = decode(encode(x)), elementwise over the rows of any
+ * pe_codec_plan (its frame only sets the work split).  One launch.
+ * Every entry point checks its plan's host copy before any device call; a row's result is bit-identical alone, packed
+ * at any offset, padded, and beside any other rows; the launch count does not depend on the rows. */
+int pe_codec_plan_fields(void);
+int pe_codec_plan(int n_rows, int frame, const long* n, const long* x_off, const long* y_off, long* consts4, long* meta,
+                  long* totals2);
+int pe_codec_bands(int frame, int* edges, int n_edges);
+size_t pe_codec_workspace_bytes(int frame, long frames);
+int pe_codec_mdct(const float* x, const long* meta, const long* host_meta, int n_rows, int frame, const float* tables,
+                  long n_table, float* coefs, void* stream);
+int pe_codec_quantize(const float* coefs, long frames, int frame, int k_c, int budget, const float* tables,
+                      long n_table, int* q, int* g, int* bits, float* dequantised, void* stream);
+int pe_codec_imdct(const float* coefs, const long* meta, const long* host_meta, int n_rows, int frame,
+                   const float* tables, long n_table, float* y, void* workspace, size_t workspace_bytes, void* stream);
+int pe_codec_apply(const float* x, const long* meta, const long* host_meta, int n_rows, int frame, int k_c, int budget,
+                   const float* tables, long n_table, float* y, int* g, int* bits, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int pe_codec_mulaw(const float* x, const long* meta, const long* host_meta, int n_rows, int frame, float* y,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,15 @@ PROTOTYPES = {
     "pe_augment_biquad_consts": (_i, [_p]),
     "pe_augment_biquad": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "pe_augment_gain": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "pe_codec_plan_fields": (_i, []),
+    "pe_codec_plan": (_i, [_i, _i, _p, _p, _p, _p, _p, _p]),
+    "pe_codec_bands": (_i, [_i, _p, _i]),
+    "pe_codec_workspace_bytes": (_z, [_i, _l]),
+    "pe_codec_mdct": (_i, [_p, _p, _p, _i, _i, _p, _l, _p, _p]),
+    "pe_codec_quantize": (_i, [_p, _l, _i, _i, _i, _p, _l, _p, _p, _p, _p, _p]),
+    "pe_codec_imdct": (_i, [_p, _p, _p, _i, _i, _p, _l, _p, _p, _z, _p]),
+    "pe_codec_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _l, _p, _p, _p, _p, _z, _p]),
+    "pe_codec_mulaw": (_i, [_p, _p, _p, _i, _i, _p, _p]),
 }
 
 

@@ -652,6 +652,34 @@ def noise_sweep(model: JDCNet, items, snrs_db=(30, 20, 10, 5, 0, -5), sources=("
     return out
 
 
+def codec_sweep(model: JDCNet, items, bitrates_kbps=(16, 32, 64, 128), codecs=("transform",), frame: int = 1024,
+                batched: bool = True, **predict_kwargs) -> dict:
+    """The codec sweep of the reference's Utils/codec_and_bandwidth_torture.ipynb with the codecs this project builds
+    (``codec.py``): one ``codec.CodecCondition`` per (codec, bitrate), codecs outermost, run by ``stress_sweep`` (its
+    ``items``, ``batched`` and other keyword arguments).  ``"transform"`` is the build-defined MDCT codec at every
+    bitrate (its kbps are those of its own cost model, not of opus, mp3 or aac); ``"g711u"`` is one condition, G.711
+    mu-law at 8 kHz, recorded at 64 kbps.  Returns ``stress_sweep``'s dict, whose condition records also carry
+    ``codec`` and ``bitrate_kbps``, plus ``"summary"``: ``summarize_with_drop`` of them by ``("codec",
+    "bitrate_kbps")``, the grouping of the notebook's table."""
+    from .codec import CodecCondition
+    conditions, labels = [], {}
+    for name in codecs:
+        if name == "g711u":
+            conditions.append(CodecCondition("g711u 64 kbps", codec="g711u"))
+        else:
+            conditions += [CodecCondition(f"{name} {float(kbps):g} kbps", codec=name, bitrate_kbps=float(kbps),
+                                          frame=frame) for kbps in bitrates_kbps]
+    for cond in conditions:
+        labels[cond.label] = (cond.codec, cond.bitrate_kbps)
+    if len(labels) != len(conditions):
+        raise ValueError("codec_sweep: two conditions share a codec and a bitrate")
+    out = stress_sweep(model, items, conditions, batched=batched, **predict_kwargs)
+    for rec in out["conditions"]:
+        rec["codec"], rec["bitrate_kbps"] = labels[rec["condition"]]
+    out["summary"] = summarize_with_drop(out["conditions"], out["baseline"], ("codec", "bitrate_kbps"))
+    return out
+
+
 # ------------------------------------------------------------------------------------------- synthesized-stimulus sweeps
 def _score_set(model, st, stitch, voicing_threshold_hz, predict_kwargs):
     """One ``predict_f0_batch`` call over a ``stimuli.StimulusSet`` and its scores: ``(melody metrics, dynamic

@@ -309,12 +309,10 @@ def apply_agc_pumping(x: torch.Tensor, level_db: float, sr: int, target_rms: flo
 _RESAMPLERS = {}
 
 
-def apply_resample_condition(x: torch.Tensor, sr: int, target_rate: int, lengths=None):
-    """``RaggedResampler`` to ``target_rate`` and back to ``sr``: the notebook's ``apply_resample_condition``.  Returns
-    ``(y (B, width) padded, lengths)``: the round trip changes a row's length as the reference's does.
-    ``target_rate == sr`` is a copy."""
-    sr, target_rate = int(sr), int(target_rate)
-    check_waves(x, "apply_resample_condition")
+def resample_rows(x: torch.Tensor, sr: int, target_rate: int, lengths=None, who: str = "resample_rows"):
+    """``(y (B, width) padded, lengths)``: the rows of ``x`` at ``sr`` through ``RaggedResampler`` to ``target_rate``;
+    a copy when the two are equal."""
+    check_waves(x, who)
     row_lengths, _ = row_layout(x, lengths, whole_by_default=True)
     B = len(row_lengths)
     if target_rate == sr:
@@ -328,15 +326,23 @@ def apply_resample_condition(x: torch.Tensor, sr: int, target_rate: int, lengths
                 o += n
             y = pad
         return y, row_lengths
-    for rate in (sr, target_rate):
-        if rate not in _RESAMPLERS:
-            _RESAMPLERS[rate] = RaggedResampler(rate)
+    if target_rate not in _RESAMPLERS:
+        _RESAMPLERS[target_rate] = RaggedResampler(target_rate)
     if x.dim() == 1 and lengths is None:
         lengths = row_lengths
-    down, _ = _RESAMPLERS[target_rate](x, [sr] * B, lengths)
-    down_lengths = [_RESAMPLERS[target_rate].out_len(sr, n) for n in row_lengths]
-    up, _ = _RESAMPLERS[sr](down, [target_rate] * B, down_lengths)
-    return up, [_RESAMPLERS[sr].out_len(target_rate, n) for n in down_lengths]
+    y, _ = _RESAMPLERS[target_rate](x, [sr] * B, lengths)
+    return y, [_RESAMPLERS[target_rate].out_len(sr, n) for n in row_lengths]
+
+
+def apply_resample_condition(x: torch.Tensor, sr: int, target_rate: int, lengths=None):
+    """``RaggedResampler`` to ``target_rate`` and back to ``sr``: the notebook's ``apply_resample_condition``.  Returns
+    ``(y (B, width) padded, lengths)``: the round trip changes a row's length as the reference's does.
+    ``target_rate == sr`` is a copy."""
+    sr, target_rate = int(sr), int(target_rate)
+    down, down_lengths = resample_rows(x, sr, target_rate, lengths, "apply_resample_condition")
+    if target_rate == sr:
+        return down, down_lengths
+    return resample_rows(down, target_rate, sr, down_lengths, "apply_resample_condition")
 
 
 def apply_additive_noise(x: torch.Tensor, sr, snr_db, source="white", seed=0, bed_index=0, bed_start=0,
@@ -363,7 +369,10 @@ def apply_additive_noise(x: torch.Tensor, sr, snr_db, source="white", seed=0, be
 
 
 def apply_condition(cond: Condition, x: torch.Tensor, sr: int, lengths=None):
-    """``(y, lengths)`` of one ``Condition`` on a ragged batch."""
+    """``(y, lengths)`` of one ``Condition`` on a ragged batch.  A condition that brings its own ``apply(x, sr,
+    lengths)`` (``codec.CodecCondition``) is asked."""
+    if hasattr(cond, "apply"):
+        return cond.apply(x, sr, lengths)
     row_lengths, _ = row_layout(x, lengths, whole_by_default=True)
     p = cond.params
     if cond.kind == "rir":
