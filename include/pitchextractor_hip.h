@@ -1041,6 +1041,38 @@ int pe_codec_apply(const float* x, const long* meta, const long* host_meta, int 
 int pe_codec_mulaw(const float* x, const long* meta, const long* host_meta, int n_rows, int frame, float* y,
                    void* stream);
 
+/* ---- Pitch modulation of real audio: a per-sample time warp and its label pass, ragged batches (csrc/pitch_mod.hip;
+ * the specification is DESIGN.md section 29) ---------------------------------------------------------------------
+ * Row r of n[r] samples is warped over [t0[r], t1[r]] (samples; t1 - t0 a multiple of hop and >= hop, t1 <= n), the
+ * span its kept label frames cover: y(t) = x(t0 + tau(t - t0)) with tau the closed-form map of mods[r] = {d[4],
+ * rate_hz[4], phi[4], a} (up to 4 sinusoids, those with d = 0 absent, and one ramp), tau(0) = 0 and tau(T) = T pinned.
+ * pe_pitch_mod_plan (host only, no device call): fills meta (n_rows x pe_pitch_mod_plan_fields() int64, opening with
+ * offset and length), params (n_rows x 24 doubles: d, w = 2 pi rate / sr, phi, cos phi, a, mbar, T) and totals2 =
+ * {tiles, rows that are warped}.  on[r] = 0, or a modulation that is all zero, makes row r a copy.  PE_E_ARG for a
+ * selected row with a non-finite value, 2 sum|d| + |a| > 0.5, a rate below 0.05 Hz or a span as above it is not.
+ * pe_pitch_mod_consts (host only): consts4 = {output samples of a tile, threads, staged source samples, 4}.
+ * pe_pitch_mod_wave: one launch, one workgroup per (row, tile), out of place (x != y): y at y_off[r] gets row r of x
+ * read through the filter of res_type (0 = kaiser_best, 1 = kaiser_fast; table = its zeros * 512 + 1 pairs {value,
+ * forward difference}) with the cutoff scale = min(1, 1 / tau') per sample, float32 accumulation in a fixed tap order;
+ * samples outside (t0, t1) and rows that are copies keep their bits.  table_in_lds = 1 reads the table from a copy in
+ * LDS (kaiser_fast only, else PE_E_UNSUPPORTED); the result has the same bits.
+ * pe_pitch_mod_labels: f0 and sil (n_rows x width float32, row r's kept frames first) to f0_out and sil_out: frame j
+ * below the row's frame count (t1 - t0) / hop + 1 <= width reads position tau(j hop) / hop by the rule linear between
+ * two voiced frames (f0 > 0 and flag 0), else the nearer frame (the earlier on a tie); a voiced result is multiplied by
+ * tau' and gets flag 0, an unvoiced one copies f0 and flag; everything else is copied.  One launch.
+ * Both check the plan's and the parameters' host copies before any device call; a row's result is bit-identical alone,
+ * packed at any offset, padded, in any batch order and into any output stride. */
+int pe_pitch_mod_consts(long* consts4);
+int pe_pitch_mod_plan_fields(void);
+int pe_pitch_mod_plan(int n_rows, const long* n, const long* x_off, const long* y_off, const long* t0, const long* t1,
+                      const int* on, const double* mods, int sr, int hop, long* meta, double* params, long* totals2);
+int pe_pitch_mod_wave(const float* x, const long* meta, const long* host_meta, const double* params,
+                      const double* host_params, int n_rows, const float* table, int res_type, int table_in_lds,
+                      float* y, void* stream);
+int pe_pitch_mod_labels(const float* f0, const float* sil, const long* meta, const long* host_meta,
+                        const double* params, const double* host_params, int n_rows, int hop, int width,
+                        float* f0_out, float* sil_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

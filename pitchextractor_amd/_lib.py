@@ -219,6 +219,11 @@ PROTOTYPES = {
     "pe_codec_imdct": (_i, [_p, _p, _p, _i, _i, _p, _l, _p, _p, _z, _p]),
     "pe_codec_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _l, _p, _p, _p, _p, _z, _p]),
     "pe_codec_mulaw": (_i, [_p, _p, _p, _i, _i, _p, _p]),
+    "pe_pitch_mod_consts": (_i, [_p]),
+    "pe_pitch_mod_plan_fields": (_i, []),
+    "pe_pitch_mod_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "pe_pitch_mod_wave": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _p, _p]),
+    "pe_pitch_mod_labels": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
 }
 
 

@@ -50,6 +50,9 @@ to resampling that item alone.
 is built and becomes the loader's ``augment.Augmenter``: reverb, noise, a per-row biquad cascade, clipping, gain and
 polarity on the device after the stages above and before the mel launch, drawn from a generator of its own; without
 the key, or with ``enabled: false``, every batch is what it was.  Rows with a cached spectrogram are not augmented.
+``dataset_config["pitch_modulation"]`` (not a key of the reference either) becomes the loader's
+``pitch_mod.PitchModulator``, the stage ahead of the ``Augmenter``: a time warp of the selected rows over their kept
+label frames (vibrato, flutter, drift, glide) that moves ``f0s`` and ``is_silences`` with the audio.
 """
 from __future__ import annotations
 
@@ -896,10 +899,11 @@ class DeviceMelLoader:
     """Iterates a host DataLoader of raw-audio batches and yields the reference's batch tuple
     ``(mels (B,1,80,192), f0s, is_silences)`` with the mel computed on the GPU in one launch."""
 
-    def __init__(self, loader: DataLoader, mel: MelSpectrogram, device, augmenter=None):
+    def __init__(self, loader: DataLoader, mel: MelSpectrogram, device, augmenter=None, modulator=None):
         self.loader, self.mel, self.device = loader, mel, torch.device(device)
         self.dataset = loader.dataset
         self.augmenter = augmenter                 # augment.Augmenter or None: the stage ahead of the mel launch
+        self.modulator = modulator                 # pitch_mod.PitchModulator or None: the stage ahead of the Augmenter
         self._ragged = RaggedResampler(mel.sample_rate)
         self._h2d, self._host = None, []
 
@@ -923,7 +927,7 @@ class DeviceMelLoader:
 
     def _submit(self, host):
         """Start a collated batch's copies on the side stream -> ticket for ``_finish``.  What ``_finish`` reads on the
-        host waits in a FIFO: (lengths, per-row rates or None, {Batch type: host batch})."""
+        host waits in a FIFO: (lengths, per-row rates or None, {Batch type: host batch}, crops, cached-mel rows)."""
         if self._h2d is None:
             from . import distributed as pdist
             shared = None
@@ -933,12 +937,13 @@ class DeviceMelLoader:
                 shared = _side_stream(self.device)
             self._h2d = H2DPrefetcher(self.device, stream=shared)
         self._host.append((host[1].tolist(), host[5].tolist() if torch.is_tensor(host[5]) else None,
-                           {type(t): t for t in host[6:] if isinstance(t, tuple)}))
+                           {type(t): t for t in host[6:] if isinstance(t, tuple)}, host[2].tolist(),
+                           host[6].tolist() if len(host) > 6 and torch.is_tensor(host[6]) else []))
         return self._h2d.submit(host)
 
     def _finish(self, ticket):
         waves, lengths, crops, f0s, sils, src_sr, *rest = self._h2d.acquire(ticket)
-        host_lengths, host_rates, host_batches = self._host.pop(0)
+        host_lengths, host_rates, host_batches, host_crops, cached_rows = self._host.pop(0)
         batches = {type(t): (t, host_batches[type(t)]) for t in rest if type(t) in host_batches}
         cached = [t for t in rest if type(t) not in host_batches]
         sr = self.mel.sample_rate
@@ -953,12 +958,23 @@ class DeviceMelLoader:
         for kind in synthetic_items.KINDS:                    # after the resampler, before the one mel launch
             if kind.Batch in batches:
                 waves, lengths = self._run_stage(kind, waves, lengths, *batches[kind.Batch], src_sr)
-        if self.augmenter is not None and self.augmenter.active:
-            # the whole rows at their lengths after the stages above; labels, crops and cached mels are not touched
+        staged = (self.modulator is not None and self.modulator.active) or \
+            (self.augmenter is not None and self.augmenter.active)
+        if staged:
+            # the whole rows at their lengths after the stages above
             synthetic = [i for t in host_batches.values() for i in t.rows.tolist()]
             for t in host_batches.values():
                 for i, n in zip(t.rows.tolist(), t.out_len.tolist()):
                     host_lengths[i] = int(n)
+        if self.modulator is not None and self.modulator.active:
+            # the time warp moves the labels with the audio; reverb and noise then land on the modulated voice.  Rows
+            # with a cached spectrogram keep it, so they and their labels are left alone
+            mod_plan = self.modulator.draw(len(host_lengths)).without(cached_rows)
+            if synthetic and not self.modulator.config["apply_to_synthetic"]:
+                mod_plan = mod_plan.without(synthetic)
+            waves, f0s, sils = self.modulator.apply(waves, host_lengths, host_crops, f0s, sils, mod_plan)
+        if self.augmenter is not None and self.augmenter.active:
+            # labels, crops and cached mels are not touched
             plan = self.augmenter.draw(len(host_lengths))
             if synthetic and not self.augmenter.config["apply_to_synthetic"]:
                 plan = plan.without(synthetic)
@@ -990,6 +1006,7 @@ def build_dataloader(path_list, validation=False, batch_size=4, num_workers=1, d
     dataset_config = dict(dataset_config or {})
     dataloader_options = dataset_config.pop("dataloader", {}) or {}
     augmentation = dataset_config.pop("augmentation", None)      # the device stage's block: the dataset never sees it
+    pitch_modulation = dataset_config.pop("pitch_modulation", None)       # likewise
     if torch.device(device).type != "cuda":
         raise RuntimeError("build_dataloader (HIP path): device must be a HIP ('cuda') device; the mel stage has "
                            "no CPU fallback")
@@ -1027,4 +1044,12 @@ def build_dataloader(path_list, validation=False, batch_size=4, num_workers=1, d
             augmenter = None
         else:
             augmenter.prepare(device)
-    return DeviceMelLoader(DataLoader(dataset, **kwargs), dataset.to_melspec, device, augmenter)
+    modulator = None
+    if pitch_modulation is not None:
+        from .pitch_mod import PitchModulator
+        modulator = PitchModulator(pitch_modulation, dataset.sr, dataset.to_melspec.hop_length,
+                                   seed=int((pitch_modulation or {}).get("seed", 0)),
+                                   rank=int(shard[0]) if shard is not None else 0)
+        if not modulator.active or (validation and not modulator.config["apply_to_validation"]):
+            modulator = None
+    return DeviceMelLoader(DataLoader(dataset, **kwargs), dataset.to_melspec, device, augmenter, modulator)
