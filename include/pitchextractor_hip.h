@@ -532,7 +532,7 @@ int pe_pitch_shift_resample(const float* stretched, const long* meta, const doub
 /* ---- WORLD vocoder synthesis (reference Utils/synthetic.py:194-220 -> pyworld.synthesize, WORLD's Synthesis) ----
  * One minimum-phase impulse response of fft_size samples per glottal pulse, overlap-added; fft_size 512 / 1024 / 2048
  * (another power of two is PE_E_UNSUPPORTED, anything else PE_E_ARG).  The pulse positions are a sequential float64
- * recurrence and come from the host (pitchextractor_amd/world.py: time_base).
+ * recurrence and come from the host (pitchextractor_amd/world.py: time_base), or from pe_world_time_base below.
  * pe_world_plan (host only, no device call) lays out a ragged batch: row r has n_frames[r] frames (f0, nullable: the
  * rows' curves back to back, checked to be finite) and pulse_cnt[r] pulses, the rows' tables back to back in index
  * (sample, strictly increasing, inside the row's int(n_frames * frame_period_ms * fs / 1000) samples, consecutive
@@ -560,6 +560,41 @@ int pe_world_responses(const float* sp, const float* ap, const float* noise, con
                        float* responses, void* stream);
 int pe_world_overlap_add(const float* responses, const long* meta, const long* pulses, const float* gains,
                          const float* out_noise, int n_rows, long n_out, int fft_size, float* out, void* stream);
+
+/* ---- WORLD time base on the device: pulse positions from an exact integer phase (csrc/world_time_base.hip) ---------
+ * GetTimeBase + GetPulseLocationsForTimeBase for a ragged batch, opt-in beside the host's float64 recurrence.  Row r
+ * has L = n_frames[r] >= 2 frames and n = int(L * frame_period_ms * fs / 1000) samples; cf_ext / cv_ext hold the rows'
+ * extended coarse curves back to back, L + 1 doubles per row each (F0 with the frames below the synthesizer's floor at
+ * 0 and voicing as 0 / 1, each with one extrapolated frame 2 a[L-1] - a[L-2], the F0's clamped at 0 from below), built
+ * by the caller on the host.  With fp = frame_period_ms / 1000, t = i / fs and j the frame with j fp <= t < (j + 1) fp
+ * (from floor(t / fp), corrected by comparisons, within [0, L - 1]): interp(c) = ((c[j+1] - c[j]) / ((j + 1) fp - j fp))
+ * * (t - j fp) + c[j]; vuv_i = interp(cv) > 0.5; f0i = vuv_i ? interp(cf) : 500; inc_i = rint(f0i / fs * 2^64) as an
+ * unsigned 64-bit integer; T_i = the exact 128-bit sum of inc_0 .. inc_i with hi_i its high and lo_i its low word.
+ * Sample i <= n - 2 carries pulse number hi_i iff hi_(i+1) == hi_i + 1, with shift = (double(2^64 - lo_i) /
+ * double(inc_(i+1))) / fs seconds and voiced = vuv_i; the row has hi_(n-1) pulses.  All of it is IEEE double without
+ * contraction and integer addition, so a row's tables are the same bits alone, in any batch and for any piece size.
+ * pe_world_time_base_plan (host only, no device call) fills meta (n_rows x pe_world_time_base_plan_fields() int64:
+ * sample prefix, n, L, curve offset, pieces of 4096 samples counted from the row's own start, piece prefix, first pulse
+ * slot, slot capacity = floor(n * max(cf_ext, 500) / fs) + 1) and totals {pieces, pulse slots, samples}.  PE_E_ARG: a
+ * null pointer, n_rows outside 0 .. 65535, L < 2, a non-finite or negative curve value, a value of cf_ext, or 500, at
+ * or above fs / 2, a non-finite or non-positive fs or frame_period_ms, a row of 2^31 - 8 samples or more.
+ * pe_world_time_base chains three launches on the stream, none of which waits on another workgroup and none of which
+ * uses an atomic: piece sums (one workgroup per (row, piece)), the exclusive scan of each row's piece sums and
+ * counts[r] = hi_(n-1) (one workgroup per row), the pulses (one workgroup per (row, piece); every slot has exactly one
+ * writer).  stages: bit 0 / 1 / 2 selects the launches (7: all; a later stage alone reads what an earlier call left
+ * in the workspace).  host_meta: the host copy of meta (PE_E_ARG unless it is the plan's for fs and frame_period_ms).
+ * index / shift / vuv: totals[1] slots, row r's pulses from its first slot on, the slots beyond counts[r] untouched.
+ * status: one int the caller zeroes; set to 1 if a pulse fell at or beyond its row's capacity (it was not written;
+ * impossible with the plan's own meta).  f0i / lo / hi (each nullable, totals[2] values): per-sample f0i, lo_i and hi_i,
+ * for tests.  workspace: pe_world_time_base_workspace_bytes(totals[0]) bytes, else PE_E_WORKSPACE. */
+int pe_world_time_base_plan_fields(void);
+int pe_world_time_base_plan(int n_rows, const long* n_frames, const double* cf_ext, const double* cv_ext, double fs,
+                            double frame_period_ms, long* meta, long* totals);
+size_t pe_world_time_base_workspace_bytes(long pieces);
+int pe_world_time_base(const double* cf_ext, const double* cv_ext, const long* meta, const long* host_meta,
+                       int n_rows, double fs, double frame_period_ms, int stages, long* index, double* shift,
+                       unsigned char* vuv, long* counts, int* status, double* f0i, unsigned long* lo, long* hi,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- WORLD CheapTrick: the spectral envelope of a recording (pyworld.cheaptrick, WORLD's cheaptrick.cpp) ----------
  * One frame per F0 value, frame f at f * frame_period_ms with f0 = F0[f] (500 Hz where F0[f] <= 3 fs / (fft_size - 3),

@@ -141,6 +141,10 @@ PROTOTYPES = {
                            _p]),
     "pe_world_responses": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _p, _p]),
     "pe_world_overlap_add": (_i, [_p, _p, _p, _p, _p, _i, _l, _i, _p, _p]),
+    "pe_world_time_base_plan_fields": (_i, []),
+    "pe_world_time_base_plan": (_i, [_i, _p, _p, _p, _d, _d, _p, _p]),
+    "pe_world_time_base_workspace_bytes": (_z, [_l]),
+    "pe_world_time_base": (_i, [_p, _p, _p, _p, _i, _d, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
     "pe_cheaptrick_plan_fields": (_i, []),
     "pe_cheaptrick_plan": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _i, _p, _p]),
     "pe_cheaptrick": (_i, [_p, _p, _p, _p, _p, _i, _d, _d, _d, _d, _i, _p, _p]),

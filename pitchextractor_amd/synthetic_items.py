@@ -22,10 +22,11 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from . import world
 from .mel import MAX_MEL_LENGTH
 from .pitch_shift import pitch_shift_ragged
 from .world import (CHEAPTRICK_Q1, VoiceTransform, check_fft_size, cheaptrick_fft_size, label_curve, noise_seed,
-                    output_length, resynthesize_ragged, source_positions, time_base, time_warp_curve, warped_frames,
+                    output_length, resynthesize_ragged, source_positions, time_warp_curve, warped_frames,
                     warped_length, world_synthesize_ragged)
 
 logger = logging.getLogger(__name__)
@@ -71,8 +72,8 @@ class WorldRequest(NamedTuple):
     out_len: int
     frame_start: int
     curve: np.ndarray                          # float64 (frames,) the drawn F0 curve
-    index: np.ndarray                          # the pulse table (world.time_base)
-    shift: np.ndarray
+    index: np.ndarray                          # the pulse table (world.time_base); with ``time_base: device`` all
+    shift: np.ndarray                          # three are empty and the device stage computes the batch's tables
     vuv: np.ndarray
     seed: int                                  # of the aperiodic noise, drawn on the device
     noise: np.ndarray | None                   # float32 (out_len,) slice of the reference's full-length draw
@@ -107,7 +108,8 @@ class ResynthesisRequest(NamedTuple):
     frame_start: int
     base_curve: np.ndarray                     # float64 (frames,) the file's F0 labels, one per hop
     curve: np.ndarray                          # float64 (frames,) the new curve = the labels (world.label_curve)
-    index: np.ndarray                          # the new curve's pulse table (world.time_base)
+    index: np.ndarray                          # the new curve's pulse table (world.time_base; empty, as shift and
+                                               # vuv, with ``time_base: device``)
     shift: np.ndarray
     vuv: np.ndarray
     seed: int                                  # of the aperiodic noise, drawn on the device
@@ -255,7 +257,8 @@ class PitchShift:
 
 class WorldVocoder:
     """``synthetic_data.world_vocoder``: Utils/synthetic.py:194-220 + _build_training_example (meldataset.py:629-677)
-    with the synthesis left to the device: the generator's draws in its order, then the crop draw; labels built here."""
+    with the synthesis left to the device: the generator's draws in its order, then the crop draw; labels built here.
+    With ``time_base: device`` in the block the request's pulse table is empty and ``run`` asks for the device's."""
     name, Request, Batch = "world_vocoder", WorldRequest, WorldBatch
 
     def generate(self, ds):
@@ -282,7 +285,8 @@ class WorldVocoder:
                                 pack.templates * (gen.fft_size // 2 + 1), np.zeros(len(pack.curves), np.int64),
                                 pack.gains, waves, host.rows.numpy(), pack.out_start, host.out_len.numpy(),
                                 fs=gen.sample_rate, frame_period=gen.frame_period, fft_size=gen.fft_size,
-                                tables=pack.tables, seeds=pack.seeds, out_noise=pack.noise)
+                                tables="device" if gen.time_base == "device" else pack.tables, seeds=pack.seeds,
+                                out_noise=pack.noise)
         return waves, lengths
 
 
@@ -297,10 +301,13 @@ class WorldResynthesis:
     and the noise: ``random.random`` against the probability and, when the transform applies, one ``random.uniform``
     per range that is not a single value, in the order formant, rate, tilt, breath; the noise and the crop are then
     drawn for the output length ``round(n / rate)``.  An unreadable, unlabelled or too sparsely voiced file ends the attempt after the
-    file draw; ``generate`` returns None when every attempt failed."""
+    file draw; ``generate`` returns None when every attempt failed.  ``time_base: host`` (the default) computes the new
+    curve's pulse table in the worker, ``time_base: device`` ships an empty one and has the device stage compute the
+    batch's tables (``world.time_base_device``); the time base consumes no draw, so every draw, label and crop is the
+    same in both."""
     name, Request, Batch = "world_resynthesis", ResynthesisRequest, ResynthesisBatch
     KEYS = ("enabled", "backend", "semitones", "gain_db_range", "noise_db", "min_voiced_fraction", "max_attempts",
-            "modulation", "aperiodicity", "d4c_threshold", "q1", "transform")
+            "modulation", "aperiodicity", "d4c_threshold", "q1", "transform", "time_base")
     MODULATION_KEYS = ("vibrato_probability", "vibrato_semitones", "vibrato_rate_range")
     TRANSFORM_KEYS = ("probability", "formant_ratio_range", "rate_range", "tilt_db_per_octave_range", "breath_db_range",
                       "f_hi")
@@ -371,7 +378,7 @@ class WorldResynthesis:
                 "vibrato_semitones": float(mod.get("vibrato_semitones", 0.35)), "vibrato_rate_range": rate,
                 "aperiodicity": aperiodicity, "d4c_threshold": d4c_threshold, "q1": float(cfg.get("q1", CHEAPTRICK_Q1)),
                 "fft_size": check_fft_size(cheaptrick_fft_size(ds.sr)), "frame_period": 1000.0 * hop / ds.sr,
-                "transform": transform}
+                "transform": transform, "time_base": world.check_time_base_mode(cfg.get("time_base", "host"))}
 
     @staticmethod
     def _draw_transform(tcfg):
@@ -421,7 +428,9 @@ class WorldResynthesis:
             curve = label_curve(new, ds.sr, fft_size)
             noise = _draw_noise(cfg["noise_db"], n_out)
             f0, sil, crop, start, count, first = ds._labels_and_window(curve.astype(np.float32), n_out)
-            table = time_base(curve, ds.sr, frame_period, fft_size)
+            # the time base consumes no draw: with ``time_base: device`` the device stage computes the batch's tables
+            table = world.no_table() if cfg.get("time_base", "host") == "device" else \
+                world.time_base(curve, ds.sr, frame_period, fft_size)
             req = ResynthesisRequest(base_path, float(gain), int(n), crop, start, count, first, base, curve,
                                      table.index, table.shift, table.vuv, noise_seed(curve),
                                      _noise_window(noise, start, count),
@@ -456,7 +465,8 @@ class WorldResynthesis:
         resynthesize_ragged(src, host.n.tolist(), pack.base.split(base_len), host.curves,
                             loader.mel.sample_rate, cfg["frame_period"], ap=ap, seeds=host.seeds, gains=pack.gains,
                             out=waves, out_rows=host.rows.numpy(), out_start=host.out_start, out_noise=pack.noise,
-                            out_len=host.out_len.numpy(), tables=host.tables, q1=cfg["q1"], fft_size=cfg["fft_size"],
+                            out_len=host.out_len.numpy(), q1=cfg["q1"], fft_size=cfg["fft_size"],
+                            tables="device" if cfg.get("time_base", "host") == "device" else host.tables,
                             d4c_threshold=cfg.get("d4c_threshold", 0.0), transforms=host.transforms,
                             positions=None if host.transforms is None else
                             [source_positions(len(c), 1.0, len(c)) if p is None else p

@@ -9,7 +9,10 @@ there is no CPU path.  Two stated deviations from WORLD: pulse p's aperiodic noi
 noise_size[p]]`` of a caller-given array of standard normals, or drawn in the kernel from Philox keyed by ``(seed,
 sample)`` (WORLD draws from a process-global xorshift stream), and the per-pulse arithmetic is float32.  pyworld is not
 available here: parity with its binary is unpinned, the yardstick is a float64 restatement of the published algorithm
-(``tests/world_ref.py``), see DESIGN.md.
+(``tests/world_ref.py``), see DESIGN.md.  Opt-in, the time base runs on the device as well (``time_base_device``,
+``tables="device"``, ``time_base="device"``; ``csrc/world_time_base.hip``): the phase as an exact 128-bit integer in
+turns of 2^-64, which no order of addition can change, pinned bit for bit by ``tests/world_time_base_ref.py`` (DESIGN.md
+section 30).
 
 Also WORLD's CheapTrick (``pyworld.cheaptrick``), the spectral envelope of a recording (``cheaptrick``,
 ``cheaptrick_ragged``, ``csrc/cheaptrick.hip``), and analysis / resynthesis on top of both (``resynthesize``,
@@ -111,6 +114,158 @@ def time_base(f0, fs, frame_period_ms: float, fft_size: int) -> PulseTable:
     noise_size = np.zeros_like(index)
     noise_size[:-1] = np.diff(index)
     return PulseTable(index, shift, vuv[index], noise_size)
+
+
+# --------------------------------------------------------------------------- the time base on the device
+TIME_BASE_MODES = ("host", "device")
+
+
+def check_time_base_mode(mode) -> str:
+    if mode not in TIME_BASE_MODES:
+        raise ValueError(f"WORLD time base {mode!r} is not a mode: use one of {list(TIME_BASE_MODES)}")
+    return mode
+
+
+def no_table() -> PulseTable:
+    """The empty table a request carries when the device computes the time base."""
+    return PulseTable(np.zeros(0, np.int64), np.zeros(0, np.float64), np.zeros(0, bool), np.zeros(0, np.int64))
+
+
+def coarse_curves(f0, fs, fft_size: int):
+    """The extended coarse curves of ``time_base_device``, built as ``time_base`` builds them: F0 with the frames below
+    ``lowest_f0`` at 0 and the voicing as 0 / 1, each with one extrapolated frame -- the F0's clamped at 0 from below
+    (the one deviation: WORLD's goes negative after a steep final fall and runs the phase backwards)."""
+    f0 = np.asarray(f0, dtype=np.float64).reshape(-1)
+    L = f0.shape[0]
+    if L < 2:
+        raise ValueError("WORLD synthesis needs at least two frames")
+    if not np.all(np.isfinite(f0)):
+        raise ValueError("WORLD synthesis: f0 must be finite")
+    cf = np.where(f0 >= lowest_f0(fs, fft_size), f0, 0.0)
+    cv = (cf != 0.0).astype(np.float64)
+    cf = np.append(cf, max(2 * cf[L - 1] - cf[L - 2], 0.0))
+    cv = np.append(cv, 2 * cv[L - 1] - cv[L - 2])
+    if not max(float(cf.max()), UNVOICED_F0) < fs / 2.0:
+        raise ValueError("WORLD time base: F0 (and the unvoiced 500 Hz) must stay below half the sample rate")
+    return cf, cv
+
+
+class TimeBasePlan:
+    """Host layout of a ragged batch of curves for ``pe_world_time_base`` (``pe_world_time_base_plan``, no device call):
+    the packed extended coarse curves, the per-row int64 fields and the totals {pieces, pulse slots, samples}."""
+
+    def __init__(self, f0s, fs, frame_period_ms: float, fft_size: int):
+        curves = [coarse_curves(f, fs, fft_size) for f in f0s]
+        R = self.n_rows = len(curves)
+        self.fs, self.frame_period_ms = float(fs), float(frame_period_ms)
+        self.n_frames = _i64([c[0].size - 1 for c in curves], R)
+        cat = lambda k: np.ascontiguousarray(np.concatenate([c[k] for c in curves]) if R else np.zeros(1))  # noqa: E731
+        self.cf, self.cv = cat(0), cat(1)
+        self.meta = plan_meta("pe_world_time_base_plan_fields", R)
+        self.totals = np.zeros(3, np.int64)
+        _lib.check(_lib.load().pe_world_time_base_plan(
+            R, *host_ptrs(self.n_frames, self.cf, self.cv), self.fs, self.frame_period_ms,
+            *host_ptrs(self.meta, self.totals)), "pe_world_time_base_plan")
+        self.n_pieces, self.n_slots, self.n_samples = (int(v) for v in self.totals)
+        self.samples = self.meta[:R, 1].copy()
+        self.sample_offsets = self.meta[:R, 0].copy()
+        self.slot_offsets = self.meta[:R, 6].copy()
+        self.capacity = self.meta[:R, 7].copy()
+
+
+class DevicePulseTables(NamedTuple):
+    """The pulse tables of a ragged batch on the device (``time_base_device``).  Row r's pulses are the first
+    ``counts[r]`` of the slots from ``slot_offsets[r]`` on (its capacity: up to ``slot_offsets[r + 1]``) of the flat
+    ``index`` / ``shift`` / ``vuv``; the slots beyond them are not written.  ``index``, ``shift``, ``vuv``, ``counts``
+    and ``status`` are views of ``buffer``, so ``host`` copies the batch in one piece."""
+    index: torch.Tensor                        # int64 (slots,) sample of each pulse
+    shift: torch.Tensor                        # float64 (slots,) fractional delay in seconds
+    vuv: torch.Tensor                          # uint8 (slots,) voicing at the pulse's sample
+    counts: torch.Tensor                       # int64 (R,) pulses of each row, on the device
+    slot_offsets: np.ndarray                   # int64 (R + 1,) host: first slot of each row, and the slot total
+    status: torch.Tensor                       # int32 (2,) nonzero first word: a pulse fell outside its row's slots
+    buffer: torch.Tensor                       # uint8: the one allocation the others are views of
+
+    def host(self):
+        """One device-to-host copy for the whole batch; a list of ``PulseTable`` with ``noise_size`` filled."""
+        raw = self.buffer.cpu().numpy()
+        S, R = int(self.slot_offsets[-1]), int(self.counts.numel())
+        index = raw[:8 * S].view(np.int64)
+        shift = raw[8 * S:16 * S].view(np.float64)
+        counts = raw[16 * S:16 * S + 8 * R].view(np.int64)
+        status = raw[16 * S + 8 * R:16 * S + 8 * R + 8].view(np.int32)
+        vuv = raw[16 * S + 8 * R + 8:16 * S + 8 * R + 8 + S]
+        if int(status[0]) != 0:
+            raise _lib.HipLibraryError("pe_world_time_base: a pulse fell outside its row's slots (foreign plan)")
+        tables = []
+        for r in range(R):
+            a, c = int(self.slot_offsets[r]), int(counts[r])
+            if c < 0 or a + c > int(self.slot_offsets[r + 1]):
+                raise _lib.HipLibraryError("pe_world_time_base: a row's pulse count exceeds its slots")
+            idx = index[a:a + c].copy()
+            noise_size = np.zeros_like(idx)
+            noise_size[:-1] = np.diff(idx)
+            tables.append(PulseTable(idx, shift[a:a + c].copy(), vuv[a:a + c].astype(bool), noise_size))
+        return tables
+
+
+def time_base_buffer(n_slots: int, n_rows: int, device) -> torch.Tensor:
+    """The zeroed byte buffer ``DevicePulseTables`` is laid out in: index, shift, counts, status, vuv."""
+    return torch.zeros((16 * n_slots + 8 * n_rows + 8 + n_slots,), dtype=torch.uint8, device=device)
+
+
+def time_base_device(f0s, fs, frame_period_ms: float, fft_size: int, device, *, buffer: torch.Tensor | None = None,
+                     hooks: bool = False, stages: int = 7, workspace: torch.Tensor | None = None):
+    """``time_base`` for a ragged batch of host curves on the device (``csrc/world_time_base.hip``), with the phase as
+    an exact integer in turns of 2^-64 instead of a float64 running sum: the same pulses as ``time_base`` wherever a
+    pulse has a phase margin, shifts within the host's own accumulated rounding, and the same bits whatever the batch
+    around a row (the definition: DESIGN.md section 30, ``tests/world_time_base_ref.py``).  One deviation: the
+    extrapolated last frame of the F0 is clamped at 0.  Returns ``DevicePulseTables``; with ``hooks`` also a dict of
+    the per-sample ``f0i`` (float64), ``lo`` (uint64 as int64 bits) and ``hi`` (int64) of every row back to back, and
+    the plan.  ``buffer``: a ``time_base_buffer`` of the caller's to write into.  There is no CPU path."""
+    from .ragged import gpu_device, workspace as scratch
+    device = gpu_device(device, "WORLD time base")
+    plan = TimeBasePlan([_host_f0(f) for f in f0s], fs, frame_period_ms, check_fft_size(fft_size))
+    R, S = plan.n_rows, plan.n_slots
+    slot_offsets = np.concatenate([plan.slot_offsets, [S]]).astype(np.int64)
+    if buffer is None:
+        buffer = time_base_buffer(S, R, device)
+    check_device_tensor(buffer, "WORLD time base", torch.uint8)
+    if buffer.numel() != 16 * S + 8 * R + 8 + S:
+        raise ValueError("WORLD time base: the buffer is not the plan's size")
+    a, b, c = 16 * S, 16 * S + 8 * R, 16 * S + 8 * R + 8
+    tables = DevicePulseTables(buffer[:8 * S].view(torch.int64), buffer[8 * S:a].view(torch.float64), buffer[c:],
+                               buffer[a:b].view(torch.int64), slot_offsets, buffer[b:c].view(torch.int32), buffer)
+    hook = None
+    if hooks:
+        N = max(plan.n_samples, 1)
+        hook = {"f0i": torch.zeros(N, dtype=torch.float64, device=device),
+                "lo": torch.zeros(N, dtype=torch.int64, device=device),
+                "hi": torch.zeros(N, dtype=torch.int64, device=device), "plan": plan}
+    if R:
+        up = lambda x: torch.from_numpy(x).to(device)  # noqa: E731
+        meta_d, cf_d, cv_d = up(plan.meta), up(plan.cf), up(plan.cv)
+        n_bytes = _lib.load().pe_world_time_base_workspace_bytes(plan.n_pieces)
+        ws = scratch(n_bytes, device) if workspace is None else workspace
+        with torch.cuda.device(device):
+            ops._call("pe_world_time_base", cf_d.data_ptr(), cv_d.data_ptr(), meta_d.data_ptr(), plan.meta.ctypes.data,
+                      R, plan.fs, plan.frame_period_ms, int(stages), _lib.ptr(tables.index), _lib.ptr(tables.shift),
+                      _lib.ptr(tables.vuv), _lib.ptr(tables.counts), _lib.ptr(tables.status),
+                      _lib.ptr(hook and hook["f0i"]), _lib.ptr(hook and hook["lo"]), _lib.ptr(hook and hook["hi"]),
+                      ws.data_ptr(), ws.numel(), _lib.stream_ptr(), work=float(plan.n_samples * 16))
+    return (tables, hook) if hooks else tables
+
+
+def _tables_of(tables, f0s, fs, frame_period, fft_size, device):
+    """``tables`` as a list of pulse tables: the string ``"device"`` is one device time base for all rows and one copy
+    back; ``None`` the host's ``time_base`` row by row."""
+    if isinstance(tables, str):
+        if tables != "device":
+            raise ValueError(f"WORLD synthesis: tables {tables!r} is neither a list of pulse tables nor 'device'")
+        return time_base_device(f0s, fs, frame_period, fft_size, device).host() if len(f0s) else []
+    if tables is None:
+        return [time_base(f, fs, frame_period, fft_size) for f in f0s]
+    return tables
 
 
 def dc_remover(fft_size: int) -> np.ndarray:
@@ -259,7 +414,8 @@ def world_synthesize_ragged(f0s, sp, sp_offsets, sp_strides, gains: torch.Tensor
                             ap_offsets=None, ap_strides=None, tables=None, noise=None, noise_offsets=None, seeds=None,
                             out_noise=None) -> torch.Tensor:
     """Ragged batch.  Row r has the host curve ``f0s[r]`` (``tables[r]`` its pulse table; computed here when not
-    given); frame f of its envelope is the ``fft_size // 2 + 1`` floats of the flat float32 device tensor ``sp`` at
+    given: by ``time_base`` on the host, or with ``tables="device"`` by one ``time_base_device`` for all rows and one
+    copy back, after which the host plan runs unchanged); frame f of its envelope is the ``fft_size // 2 + 1`` floats of the flat float32 device tensor ``sp`` at
     ``sp_offsets[r] + f * sp_strides[r]`` (stride 0: one template for every frame), ``ap`` likewise (``ap_offsets[r] <
     0`` or no ``ap``: zeros).  The row's aperiodic noise is ``noise`` at ``noise_offsets[r]`` (one standard normal per
     sample of the row) or, without it, drawn on the device from ``seeds[r]``.  Samples ``[out_start[r], out_start[r] +
@@ -275,8 +431,7 @@ def world_synthesize_ragged(f0s, sp, sp_offsets, sp_strides, gains: torch.Tensor
                                                               ("out_noise", out_noise)))
     f0s = [_host_f0(f) for f in f0s]
     R = len(f0s)
-    if tables is None:
-        tables = [time_base(f, fs, frame_period, fft_size) for f in f0s]
+    tables = _tables_of(tables, f0s, fs, frame_period, fft_size, out.device)
     n_frames = [f.size for f in f0s]
     y_len = np.array([output_length(n, fs, frame_period) for n in n_frames], dtype=np.int64)
     out_start = np.zeros(R, np.int64) if out_start is None else _i64(out_start, R)
@@ -312,12 +467,14 @@ def world_synthesize_ragged(f0s, sp, sp_offsets, sp_strides, gains: torch.Tensor
 
 
 def world_synthesize(f0, sp: torch.Tensor, ap: torch.Tensor | None = None, fs=24000, frame_period: float = 5.0, *,
-                     noise: torch.Tensor | None = None, seed: int = 0) -> torch.Tensor:
+                     noise: torch.Tensor | None = None, seed: int = 0, time_base: str = "host") -> torch.Tensor:
     """pyworld's ``synthesize(f0, sp, ap, fs, frame_period)`` on the device.  ``f0``: host curve (a tensor is brought
     to the host); ``sp`` / ``ap``: float32 device tensors ``(len(f0), fft_size / 2 + 1)``, or one ``(fft_size / 2 +
     1,)`` template for every frame; ``ap=None`` is all zeros.  ``noise``: one standard normal per output sample (device
-    float32) for the aperiodic part; drawn on the device from ``seed`` when not given.  Returns a 1-D float32 device
-    tensor of ``int(len(f0) * frame_period * fs / 1000)`` samples."""
+    float32) for the aperiodic part; drawn on the device from ``seed`` when not given.  ``time_base``: ``"host"`` (the
+    float64 recurrence of the module's ``time_base``) or ``"device"`` (``time_base_device``).  Returns a 1-D float32
+    device tensor of ``int(len(f0) * frame_period * fs / 1000)`` samples."""
+    tables = "device" if check_time_base_mode(time_base) == "device" else None
     f0 = _host_f0(f0)
     sp = _device_f32("sp", sp)
     ap = _device_f32("ap", ap)
@@ -338,7 +495,7 @@ def world_synthesize(f0, sp: torch.Tensor, ap: torch.Tensor | None = None, fs=24
                             ap=None if ap is None else ap.reshape(-1), ap_offsets=None if ap is None else [0],
                             ap_strides=None if ap is None else stride(ap),
                             noise=None if noise is None else noise.reshape(-1),
-                            noise_offsets=None if noise is None else [0], seeds=[seed])
+                            noise_offsets=None if noise is None else [0], seeds=[seed], tables=tables)
     return out[0, :n]
 
 
@@ -786,14 +943,16 @@ def resynthesize_ragged(x: torch.Tensor, lengths, f0s, new_f0s, fs, frame_period
 def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, ap=None, seed: int = 0,
                  noise: torch.Tensor | None = None, q1: float = CHEAPTRICK_Q1, f0_floor: float = CHEAPTRICK_F0_FLOOR,
                  fft_size: int | None = None, d4c_threshold: float = D4C_THRESHOLD,
-                 transform: VoiceTransform | None = None):
+                 transform: VoiceTransform | None = None, time_base: str = "host"):
     """The recording ``x`` (1-D float32 device wave with the curve ``f0``) resynthesized on ``new_f0``: its CheapTrick
     envelope through WORLD's ``Synthesis``, with no aperiodicity (``ap=None``), one ``(bins,)`` template, or the
     recording's own as D4C estimates it (``ap="d4c"``, ``d4c_threshold``).  Returns ``(audio, label)``: the 1-D float32 device wave of
     ``int(len(f0) * frame_period * fs / 1000)`` samples and the float64 host curve it was synthesized from
     (``label_curve``), exact by construction.  With ``transform`` (a ``VoiceTransform``) the speaker changes as well:
     ``new_f0`` then has one value per output frame (``time_warp_curve`` brings a curve there), and the wave has
-    ``int(len(new_f0) * frame_period * fs / 1000)`` samples."""
+    ``int(len(new_f0) * frame_period * fs / 1000)`` samples.  ``time_base``: ``"host"`` or ``"device"``, where the
+    pulse positions are computed (``time_base_device``)."""
+    tables = "device" if check_time_base_mode(time_base) == "device" else None
     if not torch.is_tensor(x) or x.dim() != 1:
         raise RuntimeError("WORLD resynthesis (HIP) needs a 1-D float32 device wave; no CPU fallback exists")
     n = output_length(len(_host_f0(new_f0)), fs, frame_period)
@@ -802,7 +961,7 @@ def resynthesize(x: torch.Tensor, f0, new_f0, fs, frame_period: float = 5.0, *, 
     out, labels = resynthesize_ragged(x, None, [f0], [new_f0], fs, frame_period, ap=ap, seeds=[seed],
                                       noise=None if noise is None else noise.reshape(-1),
                                       noise_offsets=None if noise is None else [0], q1=q1, f0_floor=f0_floor,
-                                      fft_size=fft_size, d4c_threshold=d4c_threshold,
+                                      fft_size=fft_size, d4c_threshold=d4c_threshold, tables=tables,
                                       transforms=None if transform is None else [transform])
     return out[0, :n], labels[0]
 
@@ -876,6 +1035,9 @@ class WorldGenerator:
         if gain_min > gain_max:
             gain_min, gain_max = gain_max, gain_min
         self.gain_db_range = (gain_min, gain_max)
+        # where the pulse tables are computed: "host" (draw() calls time_base) or "device" (draw() leaves the table
+        # empty and the device stage computes the batch's tables at once); no draw depends on it
+        self.time_base = check_time_base_mode(cfg.get("time_base", "host"))
         self.modulation = ModulationConfig(**(cfg.get("modulation", {}) or {}))
         self.templates = formant_templates(cfg.get("vowel_profiles") or DEFAULT_VOWELS, self.sample_rate,
                                            self.fft_size)
@@ -927,5 +1089,5 @@ class WorldGenerator:
             noise_gain = float(10.0 ** (self.noise_db / 20.0))
             if noise_gain > 0:
                 noise = np.random.normal(scale=noise_gain, size=(n,))
-        return WorldDraw(curve, template, gain, noise,
+        return WorldDraw(curve, template, gain, noise, no_table() if self.time_base == "device" else
                          time_base(curve, self.sample_rate, self.frame_period, self.fft_size))
