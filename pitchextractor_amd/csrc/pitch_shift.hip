@@ -10,15 +10,17 @@
 // (its phase is a running sum), nothing after it is needed.
 //
 //   1. STFT: one wave per frame; the 2048 real samples are packed as 1024 complex points and run through five radix-4
-//      Stockham passes in LDS (fft_lds, dsp.h), then split into the 1025 bins of the real transform.
+//      Stockham passes in LDS, then split into the 1025 bins of the real transform -- in fp64, rounded at the store
+//      (the inverse transform of stage 3 is fft_lds of dsp.h in fp32).
 //   2. Phase vocoder: one lane per (row, bin) walks the output columns.  The phase advance of bin k per column is
 //      k * pi / 2 exactly, so the accumulated phase is carried as an integer quarter-turn count (t * k) mod 4 plus an
-//      fp32 residual reduced to [-pi, pi) every column; a plain fp32 running phase grows to 1e5-1e6 rad on long files.
+//      fp64 residual reduced to [-pi, pi) every column; a plain fp32 running phase grows to 1e5-1e6 rad on long files.
 //   3. iSTFT: one wave per column (inverse real FFT x window), then an overlap-add in gather form -- every output
 //      sample reads its <= 4 frames, no atomics -- divided by the window sum-square where that exceeds FLT_MIN.
 //   4. Resampler: one thread per output sample of the kept window; the read position j / r is formed in fp64 (fp32
-//      is 0.06 samples off at 1e6); the filter table (host-built, 128 KB / 32 KB) stays in L2.  Gain, optional noise
-//      and the write into the caller's batch row are the epilogue.
+//      is 0.06 samples off at 1e6); the filter table (host-built, 128 KB / 32 KB) stays in L2.  At ratio 1 exactly
+//      (n_steps = 0) the sample is copied, as librosa's resample hands its input back when the rates are equal.
+//      Gain, optional noise and the write into the caller's batch row are the epilogue.
 #include <float.h>
 #include <math.h>
 #include "common.h"
@@ -35,9 +37,7 @@ constexpr int kLog2C = 10;
 constexpr int kC = 1 << kLog2C;    // complex FFT length kN / 2; one wave per transform: fft_lds<kLog2C, INV, 64>
 static_assert(2 * kC == kN, "the real frame is packed as kN / 2 complex points");
 constexpr int kP = 512;           // resampy table precision 2^9
-constexpr float kPi = 3.14159265358979323846f;
-constexpr float kTwoPiHi = 6.28318548202514648438f;       // float(2 pi)
-constexpr float kTwoPiLo = -1.74845553e-7f;                // 2 pi - float(2 pi)
+constexpr double kPiD = 3.14159265358979323846;
 
 // per-row plan fields (int64); see pe_pitch_shift_plan
 enum {
@@ -62,17 +62,69 @@ __device__ void init_tables(float2* s_tw, float2* s_tr, float* s_win) {
 }
 
 // ---- 1. STFT ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ps_stft_kernel(const float* __restrict__ x, const long* __restrict__ meta,
-                                                      int n_rows, long total, float2* __restrict__ spec) {
-  __shared__ float2 s_tw[kC];
-  __shared__ float2 s_tr[kBins];
-  __shared__ float s_win[kN];
-  __shared__ float2 s_buf[4][kC];
-  init_tables(s_tw, s_tr, s_win);
+// The forward transform runs in fp64 and rounds once, at the store.  A float32 transform leaves a noise floor under
+// every bin of a frame (the packed radix-4 passes: 4.5e-9 rms of the largest bin, three times numpy's float32 FFT); the
+// phase vocoder reads the phase of bins that rise out of that floor on a glide, and end to end the stage alone cost
+// 2.3 times the error of a float32 librosa at an octave.  Same algorithm as fft_lds (dsp.h: radix-4 Stockham passes in
+// place, one wave per buffer), on double2, with one table: the 2048th roots 0 .. 1024, which also hold the 1024th roots
+// (every other one, mirrored past the half turn) and the Hann window (0.5 - 0.5 cos).
+constexpr int kStftWaves = 2;                             // 2 x 16 KB of buffers + 16 KB of roots per workgroup
+
+__device__ __forceinline__ double2 dmul(double2 a, double2 b) {
+  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+// exp(-2 pi i j / 2048), j in [0, 2048)
+__device__ __forceinline__ double2 root2048(const double2* tr, int j) {
+  if (j <= kC) return tr[j];
+  const double2 w = tr[kN - j];
+  return make_double2(w.x, -w.y);
+}
+
+__device__ __forceinline__ void fft1024_fwd_f64(double2* buf, const double2* tr, int lane) {
+  constexpr int NB = kC / 4 / 64;
+#pragma unroll
+  for (int p = 0; p < kLog2C / 2; ++p) {
+    const int ns = 1 << (2 * p), shift = kLog2C - 2 - 2 * p;
+    double2 v[NB][4];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[b][r] = buf[lane + 64 * b + (kC / 4) * r];
+    wave_lds_sync();
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int j = lane + 64 * b, k = j & (ns - 1);
+#pragma unroll
+      for (int r = 1; r < 4; ++r) v[b][r] = dmul(v[b][r], root2048(tr, 2 * ((r * k) << shift)));
+      const double2 t0 = make_double2(v[b][0].x + v[b][2].x, v[b][0].y + v[b][2].y);
+      const double2 t1 = make_double2(v[b][0].x - v[b][2].x, v[b][0].y - v[b][2].y);
+      const double2 t2 = make_double2(v[b][1].x + v[b][3].x, v[b][1].y + v[b][3].y);
+      const double2 t3 = make_double2(v[b][1].y - v[b][3].y, v[b][3].x - v[b][1].x);      // (v1 - v3) * -i
+      const int o = ((j >> (2 * p)) << (2 * p + 2)) + k;
+      buf[o] = make_double2(t0.x + t2.x, t0.y + t2.y);
+      buf[o + ns] = make_double2(t1.x + t3.x, t1.y + t3.y);
+      buf[o + 2 * ns] = make_double2(t0.x - t2.x, t0.y - t2.y);
+      buf[o + 3 * ns] = make_double2(t1.x - t3.x, t1.y - t3.y);
+    }
+    wave_lds_sync();
+  }
+}
+
+__global__ __launch_bounds__(64 * kStftWaves) void ps_stft_kernel(const float* __restrict__ x,
+                                                                  const long* __restrict__ meta, int n_rows,
+                                                                  long total, float2* __restrict__ spec) {
+  __shared__ double2 s_tr[kBins];
+  __shared__ double2 s_buf[kStftWaves][kC];
+  for (int m = threadIdx.x; m < kBins; m += blockDim.x) {
+    double s, c;
+    sincospi(-2.0 * m / kN, &s, &c);
+    s_tr[m] = make_double2(c, s);
+  }
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float2* buf = s_buf[wv];
-  for (long g = (long)blockIdx.x * 4 + wv; g < total; g += (long)gridDim.x * 4) {
+  double2* buf = s_buf[wv];
+  auto hann = [&](int i) { return 0.5 - 0.5 * s_tr[i <= kC ? i : kN - i].x; };
+  for (long g = (long)blockIdx.x * kStftWaves + wv; g < total; g += (long)gridDim.x * kStftWaves) {
     const int row = find_row(meta, n_rows, M_K, M_FOFF, g);
     const long* m = meta + (long)row * M_K;
     const long f = g - m[M_FOFF], n = m[M_N];
@@ -82,29 +134,31 @@ __global__ __launch_bounds__(256) void ps_stft_kernel(const float* __restrict__ 
     for (int q = 0; q < 16; ++q) {
       const int i = 2 * (lane + 64 * q);
       const long a = base + i;
-      const float v0 = (a >= 0 && a < n) ? xr[a] : 0.f;
-      const float v1 = (a + 1 >= 0 && a + 1 < n) ? xr[a + 1] : 0.f;
-      buf[i >> 1] = make_float2(v0 * s_win[i], v1 * s_win[i + 1]);
+      const double v0 = (a >= 0 && a < n) ? (double)xr[a] : 0.0;
+      const double v1 = (a + 1 >= 0 && a + 1 < n) ? (double)xr[a + 1] : 0.0;
+      buf[i >> 1] = make_double2(v0 * hann(i), v1 * hann(i + 1));
     }
     wave_lds_sync();
-    fft_lds<kLog2C, false, 64>(buf, s_tw, lane);
+    fft1024_fwd_f64(buf, s_tr, lane);
     float2* out = spec + g * kBins;
 #pragma unroll
     for (int q = 0; q < 17; ++q) {
       const int k = lane + 64 * q;
       if (k > kC) break;
-      float2 e, o;
-      const float2 t = real_fft_bin(buf, s_tr[k], kC, k & (kC - 1), e, o);
-      out[k] = cadd(e, t);
+      // bin k of the real transform from the packed one (real_fft_bin of dsp.h, in fp64): e + w o
+      const double2 zk = buf[k & (kC - 1)], zc = buf[(kC - k) & (kC - 1)];
+      const double2 e = make_double2(0.5 * (zk.x + zc.x), 0.5 * (zk.y - zc.y));
+      const double2 o = make_double2(0.5 * (zk.y + zc.y), -0.5 * (zk.x - zc.x));
+      const double2 t = dmul(s_tr[k], o);
+      out[k] = make_float2((float)(e.x + t.x), (float)(e.y + t.y));
     }
     wave_lds_sync();                                      // buffer reads done before the next frame's writes
   }
 }
 
 // ---- 2. phase vocoder ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wrap_pi(float p) {       // p - 2 pi round(p / 2 pi), round half to even like numpy
-  const float n = rintf(p * (0.5f / kPi));
-  return fmaf(-n, kTwoPiLo, fmaf(-n, kTwoPiHi, p));
+__device__ __forceinline__ double wrap_pi(double p) {     // p - 2 pi round(p / 2 pi), round half to even like numpy
+  return fma(-rint(p * (0.5 / kPiD)), 2.0 * kPiD, p);
 }
 
 __global__ __launch_bounds__(256) void ps_vocoder_kernel(const float2* __restrict__ spec, const long* __restrict__ meta,
@@ -121,9 +175,11 @@ __global__ __launch_bounds__(256) void ps_vocoder_kernel(const float2* __restric
   // x + 0 turns -0 into +0: the phase of an exactly silent bin is then atan2(+0, +0) = 0, as numpy's spectrum of
   // silence gives; a -0 from the FFT's sign flips would put pi into the running phase of every later column
   auto ld = [&](long f) { const float2 v = D[f * kBins]; return make_float2(v.x + 0.f, v.y + 0.f); };
-  const float adv = (float)(k & 3) * (0.5f * kPi);        // k pi / 2 mod 2 pi
+  // The residual and its increments are fp64: float(k pi / 2) is off by up to 2.4e-7 rad, and subtracting it every
+  // column walked the fp32 residual away from float64 at that rate (8e-4 rad after 8192 columns, a 3-minute file).
+  const double adv = (double)(k & 3) * (0.5 * kPiD);      // k pi / 2 mod 2 pi
   const float2 d0 = ld(0);
-  float rho = atan2f(d0.y, d0.x);                         // phase residual in [-pi, pi]
+  double rho = (double)atan2f(d0.y, d0.x);                // phase residual in [-pi, pi]
   int q = 0;                                              // quarter turns (t k) mod 4
   long i0 = 0;
   float2 A = d0, B = f_use > 1 ? ld(1) : zero;
@@ -138,16 +194,15 @@ __global__ __launch_bounds__(256) void ps_vocoder_kernel(const float2* __restric
     const float mag = (1.f - alpha) * ma + alpha * mb;
     if (t >= c_lo) {
       float s, c;
-      sincosf(rho, &s, &c);
+      sincosf((float)rho, &s, &c);
       float2 ph = make_float2(c, s);
       if (q & 1) ph = make_float2(-ph.y, ph.x);           // * i
       if (q & 2) ph = make_float2(-ph.x, -ph.y);          // * -1
       out[(t - c_lo) * kBins] = make_float2(mag * ph.x, mag * ph.y);
     }
-    const float dphi = wrap_pi(atan2f(B.y, B.x) - atan2f(A.y, A.x) - adv);
-    rho += dphi;
-    if (rho >= kPi) rho = (rho - kTwoPiHi) - kTwoPiLo;
-    else if (rho < -kPi) rho = (rho + kTwoPiHi) + kTwoPiLo;
+    rho += wrap_pi((double)atan2f(B.y, B.x) - (double)atan2f(A.y, A.x) - adv);
+    if (rho >= kPiD) rho -= 2.0 * kPiD;
+    else if (rho < -kPiD) rho += 2.0 * kPiD;
     q = (q + k) & 3;
     A = nA; B = nB; i0 = i1;
   }
@@ -227,12 +282,16 @@ __global__ __launch_bounds__(256) void ps_resample_kernel(const float* __restric
     const long* m = meta + (long)row * M_K;
     const long i = g - m[M_JOFF], j = m[M_JLO] + i;
     float v = 0.f;
-    if (j < m[M_NRES]) {
-      const double r = ratios[2 * row + 1];
+    const double r = ratios[2 * row + 1];
+    const long s_lo = m[M_SLO], s_hi = m[M_SHI];
+    const float* x = st + m[M_SOFF] - s_lo;                   // x[s] for s in [s_lo, s_hi)
+    if (r == 1.0) {
+      // n_steps = 0: librosa's resample returns its input when the two rates are equal, no low-pass is applied
+      if (j < m[M_NRES] && j >= s_lo && j < s_hi) v = x[j];
+    } else if (j < m[M_NRES]) {
       const double scale = r < 1.0 ? r : 1.0;
       const long step = (long)(scale * kP);
-      const long M = m[M_M], s_lo = m[M_SLO], s_hi = m[M_SHI];
-      const float* x = st + m[M_SOFF] - s_lo;                 // x[s] for s in [s_lo, s_hi)
+      const long M = m[M_M];
       const double T = (double)j / r;
       const long n = (long)T;
       double frac = scale * (T - (double)n);
@@ -322,8 +381,8 @@ extern "C" int pe_pitch_shift_stft(const float* x, const long* meta, int n_rows,
   if (n_rows < 0 || n_rows > kMaxRows || n_frames < 0) return PE_E_ARG;
   if (n_frames == 0 || n_rows == 0) return PE_OK;
   if (!x || !meta || !spec) return PE_E_ARG;
-  hipLaunchKernelGGL(ps_stft_kernel, dim3(grid_for(n_frames, 4, 2048)), dim3(256), 0, pe_stream(stream), x, meta,
-                     n_rows, n_frames, reinterpret_cast<float2*>(spec));
+  hipLaunchKernelGGL(ps_stft_kernel, dim3(grid_for(n_frames, kStftWaves, 1024)), dim3(64 * kStftWaves), 0,
+                     pe_stream(stream), x, meta, n_rows, n_frames, reinterpret_cast<float2*>(spec));
   PE_LAUNCH_CHECK();
   return PE_OK;
 }

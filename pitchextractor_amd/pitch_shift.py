@@ -3,7 +3,8 @@ defaults, as the reference's synthetic-data generator calls it (meldataset.py:32
 
 STFT (n_fft 2048, hop 512, periodic Hann, centre zero padding) -> phase vocoder at ``rate = 2**(-s/12)`` -> iSTFT to
 ``round(N / rate)`` samples -> resampy's band-limited sinc interpolation from ``sr / rate`` back to ``sr`` -> fixed to
-N samples.  Four HIP stages (``csrc/pitch_shift.hip``); there is no CPU path.  The resampling filters are resampy's
+N samples (at ``n_steps = 0`` the two rates are equal and the stretched signal is copied, as librosa's ``resample``
+returns its input then).  Four HIP stages (``csrc/pitch_shift.hip``); there is no CPU path.  The resampling filters are resampy's
 ``kaiser_best`` / ``kaiser_fast`` rebuilt from their published parameters (not from resampy's data files, which are not
 available here): parity with librosa / resampy is unpinned, see DESIGN.md.
 """
@@ -28,7 +29,10 @@ MAX_SEMITONES = 24.0
 
 # --------------------------------------------------------------------------- host-side lengths (no device needed)
 def stretch_rate(n_steps: float) -> float:
-    return 2.0 ** (-float(n_steps) / 12)
+    """2 ** (-s / 12) at the step the plan sees: ``Plan`` hands ``n_steps`` over as float32, so every length below
+    is formed from the rounded step too (0.35 or 7.3 are not float32 numbers; M, int(M r) and the column count
+    differ at some lengths otherwise)."""
+    return 2.0 ** (-float(np.float32(n_steps)) / 12)
 
 
 def stft_frames(n: int) -> int:

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from pitchextractor_amd.pitch_shift import (HOP, N_FFT, resample_filter, resample_ratio, stretch_rate,
+from pitchextractor_amd.pitch_shift import (HOP, N_FFT, RES_TYPES, resample_filter, resample_ratio, stretch_rate,
                                             stretched_len, TABLE_PRECISION)
 
 N_BINS = N_FFT // 2 + 1
@@ -83,8 +83,11 @@ def filter_tables(res_type, ratio):
 
 
 def resample(x, ratio, res_type="kaiser_best"):
-    """resampy.resample(x, sr_orig, sr_new) with sr_new / sr_orig = ratio: int(len(x) * ratio) samples."""
+    """resampy.resample(x, sr_orig, sr_new) with sr_new / sr_orig = ratio: int(len(x) * ratio) samples.  At ratio 1
+    the input comes back unfiltered, as librosa.resample returns it when orig_sr == target_sr (n_steps = 0)."""
     x = np.asarray(x, dtype=np.float64)
+    if ratio == 1.0:
+        return x.copy()
     W, dW = filter_tables(res_type, ratio)
     nwin = W.size
     scale = min(1.0, ratio)
@@ -105,6 +108,92 @@ def resample(x, ratio, res_type="kaiser_best"):
             src = n[m] - a if sgn < 0 else n[m] + 1 + a
             y[m] += (W[w] + eta[m] * dW[w]) * x[src]
     return y
+
+
+def resample_at(x, ratio, res_type, j):
+    """``resample(x, ratio, res_type)[j]`` for an array of output indices ``j < int(len(x) * ratio)``, each output
+    summed tap by tap on its own: for slices of rows too long to resample whole."""
+    x = np.asarray(x, dtype=np.float64)
+    j = np.asarray(j, dtype=np.int64)
+    if ratio == 1.0:
+        return x[j]
+    W, dW = filter_tables(res_type, ratio)
+    scale = min(1.0, ratio)
+    step = int(scale * TABLE_PRECISION)
+    y = np.zeros(j.size)
+    for q, jj in enumerate(j):
+        T = float(jj) / ratio
+        n = int(T)
+        frac = scale * (T - n)
+        idx = frac * TABLE_PRECISION
+        off = int(idx)
+        a = np.arange(max(0, min(n + 1, (W.size - off) // step)))
+        left = np.dot(W[off + a * step] + (idx - off) * dW[off + a * step], x[n - a])
+        idx = (scale - frac) * TABLE_PRECISION
+        off = int(idx)
+        a = np.arange(max(0, min(x.size - n - 1, (W.size - off) // step)))
+        y[q] = left + np.dot(W[off + a * step] + (idx - off) * dW[off + a * step], x[n + 1 + a])
+    return y
+
+
+# --------------------------------------------------------------------------- what the kernels read (plan coverage)
+def resampler_reads(j, ratio, M, res_type):
+    """(lo, hi): the stretched samples lo .. hi (inclusive; lo > hi: none) that ps_resample_kernel's two tap loops
+    read for output indices ``j``, from the kernel's own off, step, i_max and k_max; the one sample j at ratio 1."""
+    j = np.asarray(j, dtype=np.int64)
+    if ratio == 1.0:
+        return j.copy(), j.copy()
+    nwin = RES_TYPES[res_type][0] * TABLE_PRECISION + 1
+    scale = min(1.0, ratio)
+    step = int(scale * TABLE_PRECISION)
+    T = j.astype(np.float64) / ratio
+    n = T.astype(np.int64)
+    frac = scale * (T - n)
+    off = (frac * TABLE_PRECISION).astype(np.int64)
+    i_max = np.minimum(n + 1, (nwin - off) // step)
+    off = ((scale - frac) * TABLE_PRECISION).astype(np.int64)
+    k_max = np.minimum(M - n - 1, (nwin - off) // step)
+    return n + 1 - np.maximum(i_max, 0), n + np.maximum(k_max, 0)
+
+
+def ola_reads(s, n_ola):
+    """(t_lo, t_hi): the frames t_lo .. t_hi (inclusive; t_lo > t_hi: none) that ps_ola_kernel sums into stretched
+    samples ``s``."""
+    p = np.asarray(s, dtype=np.int64) + N_FFT // 2
+    t_lo = np.where(p < N_FFT, 0, (p - N_FFT) // HOP + 1)
+    t_hi = np.minimum(n_ola - 1, p // HOP)
+    past = p >= N_FFT + HOP * (n_ola - 1)
+    return np.where(past, 1, t_lo), np.where(past, 0, t_hi)
+
+
+def vocoder_last_frame(c_hi, rate):
+    """The last input frame that output columns 0 .. c_hi - 1 of ps_vocoder_kernel read."""
+    return int(float(c_hi - 1) * rate) + 1
+
+
+# --------------------------------------------------------------------------- shared test signals
+def three_sines(n, sr=24000):
+    t = np.arange(n) / sr
+    return sum(a * np.sin(2 * np.pi * f * t + p)
+               for a, f, p in ((0.3, 180.0, 0.1), (0.2, 523.0, 1.0), (0.1, 1710.0, 2.0))).astype(np.float32)
+
+
+def silence_then_signal(n_silent=8192, n_signal=12000):
+    """Exact zeros, then the three-sine signal: the spectra of the first frames are digital silence."""
+    return np.concatenate([np.zeros(n_silent, np.float32), three_sines(n_signal)])
+
+
+SILENCE_FLOOR, SILENCE_WIDE_FLOOR = 1e-3, 1e-4              # masks of the silence tests, as shares of the largest bin
+
+
+def loud_cells(want, floor):
+    """(mask, onset, share) of a vocoder reference ``want`` (columns, bins): the cells whose magnitude exceeds
+    ``floor`` of the largest, the first column that is not exact silence, and the share of the cells at and after
+    that column which the mask keeps."""
+    mag = np.abs(want)
+    mask = mag > floor * mag.max()
+    onset = int(np.argmax(mag.max(axis=1) > 0))
+    return mask, onset, float(mask[onset:].mean())
 
 
 def pitch_shift(y, sr, n_steps, res_type="kaiser_best", fp32=False):

@@ -106,20 +106,41 @@ def _signals():
     return sig
 
 
-def test_end_to_end_within_twice_float32_librosa(hip_device):
-    sig = _signals()
-    steps = [4, -2, 1, -4, 2]
-    _, _, out = _run(sig, steps, hip_device)
+def _within_twice_float32(sig, steps, dev):
+    """Every row is measured before the first miss is raised, so a failure names all of them."""
+    _, _, out = _run(sig, steps, dev)
+    misses = []
     for r, (w, s) in enumerate(zip(sig, steps)):
         N = w.size
         got = out[r, :N]
         f64 = ref.pitch_shift(w, SR, s)
         f32 = ref.pitch_shift(w, SR, s, fp32=True)
         e_gpu, e_32 = np.abs(got - f64).max(), np.abs(f32 - f64).max()
-        assert e_gpu <= 2 * e_32 + 1e-5, (r, e_gpu, e_32)
+        print(f"row {r} n={N} s={s}: gpu {e_gpu:.3e}, float32 {e_32:.3e}")
+        if not e_gpu <= 2 * e_32 + 1e-5:
+            misses.append((r, "wave", e_gpu, e_32))
         if N > 1024:
             m64, m32, mg = (mel_ref.log_mel(np.asarray(x, np.float64)) for x in (f64, f32, got))
-            assert np.abs(mg - m64).max() <= 2 * np.abs(m32 - m64).max() + 1e-3, r
+            e_gpu, e_32 = np.abs(mg - m64).max(), np.abs(m32 - m64).max()
+            print(f"row {r} log-mel: gpu {e_gpu:.3e}, float32 {e_32:.3e}")
+            if not e_gpu <= 2 * e_32 + 1e-3:
+                misses.append((r, "log-mel", e_gpu, e_32))
+    assert not misses, misses
+
+
+def test_end_to_end_within_twice_float32_librosa(hip_device):
+    _within_twice_float32(_signals(), [4, -2, 1, -4, 2], hip_device)
+
+
+@pytest.mark.parametrize("s", [12, -12, 7.3])
+def test_end_to_end_within_twice_float32_librosa_wide_steps(hip_device, s):
+    """An octave either way and a step float32 does not represent, on speech-like and stationary signals (white noise
+    bounds nothing here: its float32 yardstick is itself 1e-3).
+
+    With a float32 forward transform the utterance missed this bound at an octave (2.30 times the yardstick at
+    s = 12, 2.05 times at -12); the STFT stage runs in fp64 since, and the GPU's error against float64 is 8e-7 on
+    every row here where the float32 restatement's is 2e-3 .. 4e-2."""
+    _within_twice_float32([synthetic.utterance(0, duration=1.5)[0], ref.three_sines(77777)], [s, s], hip_device)
 
 
 def test_row_alone_equals_row_in_ragged_batch(hip_device):
@@ -146,8 +167,10 @@ def test_window_write_matches_full_shift(hip_device):
     f = full.cpu().numpy()
     n = noise.cpu().numpy()
     o = out.cpu().numpy()
-    np.testing.assert_allclose(o[2, :58412], np.float32(0.5) * f[100000:158412] + n[:58412], rtol=0, atol=1e-6)
-    np.testing.assert_allclose(o[0, :58412], np.float32(2.0) * f[:58412] + n[58412:], rtol=0, atol=1e-6)
+    # bit for bit: the window only skips reads outside ranges the plan proves sufficient (test_pitch_shift_edges_cpu.py),
+    # and with power-of-two gains the epilogue rounds once whether or not gain and noise are fused
+    np.testing.assert_array_equal(o[2, :58412], np.float32(0.5) * f[100000:158412] + n[:58412])
+    np.testing.assert_array_equal(o[0, :58412], np.float32(2.0) * f[:58412] + n[58412:])
     assert (o[1] == 0).all() and (o[0, 58412:] == 0).all()
 
 
