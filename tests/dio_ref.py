@@ -444,46 +444,83 @@ def stage_deviation(a, b):
                 best_band_gap=band_gap, stonemask_cents=sm_c, stonemask_flips=sm_flips, frames=T)
 
 
-@functools.lru_cache(maxsize=None)
-def reference_pairs(sr, hop, stonemask_on=True):
-    """(float64 run, float32 run) of the whole tracker for every margin input of one configuration."""
-    return tuple((track(y, sr, hop, stonemask_on=stonemask_on),
-                  track(y, sr, hop, dtype=np.float32, stonemask_on=stonemask_on)) for y in margin_inputs(sr))
+def config_margin_inputs(sr, inputs=None):
+    """The margin inputs of a configuration: the rate's own (``margin_inputs``), or with ``inputs`` one glide voiced
+    from end to end per entry (seconds, from Hz, to Hz, seed)."""
+    if inputs is None:
+        return margin_inputs(sr)
+    return [voiced_glide(seconds, f_a, f_b, sr, seed) for seconds, f_a, f_b, seed in inputs]
+
+
+def _pairs(waves, sr, hop, stonemask_on, config):
+    cfg = dict(config)
+    return tuple((track(y, sr, hop, stonemask_on=stonemask_on, **cfg),
+                  track(y, sr, hop, dtype=np.float32, stonemask_on=stonemask_on, **cfg)) for y in waves)
 
 
 @functools.lru_cache(maxsize=None)
-def natural_pairs(sr, hop, stonemask_on=True):
-    return tuple((track(y, sr, hop, stonemask_on=stonemask_on),
-                  track(y, sr, hop, dtype=np.float32, stonemask_on=stonemask_on)) for y in natural_inputs(sr))
+def reference_pairs(sr, hop, stonemask_on=True, config=(), inputs=None):
+    """(float64 run, float32 run) of the whole tracker for every margin input of one configuration.  ``config``: keys
+    of ``DEFAULTS`` as a tuple of (key, value) pairs; ``inputs``: see ``config_margin_inputs``."""
+    return _pairs(config_margin_inputs(sr, inputs), sr, hop, stonemask_on, config)
 
 
 @functools.lru_cache(maxsize=None)
-def stage_pairs(sr, hop):
+def natural_pairs(sr, hop, stonemask_on=True, config=(), inputs=None):
+    """The natural inputs belong to the default batches: a configuration with its own ``inputs`` has none."""
+    return _pairs(natural_inputs(sr) if inputs is None else [], sr, hop, stonemask_on, config)
+
+
+@functools.lru_cache(maxsize=None)
+def stage_pairs(sr, hop, config=(), inputs=None):
     """(float64 run, float32 stage run) for every margin and then every natural input."""
-    ys = margin_inputs(sr) + natural_inputs(sr)
-    refs = [a for a, _ in reference_pairs(sr, hop)] + [a for a, _ in natural_pairs(sr, hop)]
+    ys = config_margin_inputs(sr, inputs) + (natural_inputs(sr) if inputs is None else [])
+    refs = [a for a, _ in reference_pairs(sr, hop, True, config, inputs)] + \
+        [a for a, _ in natural_pairs(sr, hop, True, config, inputs)]
     return tuple((a, stage_run(y, a)) for y, a in zip(ys, refs))
 
 
 @functools.lru_cache(maxsize=None)
-def config_yardstick(sr, hop):
+def config_yardstick(sr, hop, config=(), inputs=None):
     """float32-vs-float64 deviation of the restatement on ONE configuration's own inputs.  Stage figures (band signal
     error relative to the row's peak, fine edge in samples, candidate cents and score, StoneMask cents) come from
     ``stage_run``; the contour figures (``dio_cents``, ``cents``, and ``natural_*``) from the whole float32 run."""
-    n_margin = len(margin_inputs(sr))
-    st = [stage_deviation(a, b) for a, b in stage_pairs(sr, hop)]
+    n_margin = len(config_margin_inputs(sr, inputs))
+    st = [stage_deviation(a, b) for a, b in stage_pairs(sr, hop, config, inputs)]
     full = [(contour_deviation(a["dio"], b["dio"]), contour_deviation(a["f0"], b["f0"]))
-            for a, b in reference_pairs(sr, hop)]
+            for a, b in reference_pairs(sr, hop, True, config, inputs)]
     nat = [(contour_deviation(a["dio"], b["dio"]), contour_deviation(a["f0"], b["f0"]))
-           for a, b in natural_pairs(sr, hop)]
+           for a, b in natural_pairs(sr, hop, True, config, inputs)]
     m = st[:n_margin]
     return dict(band=max(d["band"] for d in st), edge=max(d["edge"] for d in m),
                 cand_cents=max(d["cand_cents"] for d in m), score=max(d["score"] for d in m),
                 stonemask_cents=max(d["stonemask_cents"] for d in m),
                 dio_cents=max(d[0][0] for d in full), cents=max(d[1][0] for d in full),
-                natural_dio_cents=max(d[0][0] for d in nat), natural_cents=max(d[1][0] for d in nat),
+                natural_dio_cents=max((d[0][0] for d in nat), default=0.0),
+                natural_cents=max((d[1][0] for d in nat), default=0.0),
                 stage_dev=st, full_flips=[(d[0][1], d[1][1]) for d in full],
                 natural_flips=[(d[0][1], d[1][1]) for d in nat])
+
+
+# Configurations off the defaults: (name, sr, hop, config, margin glides (seconds, from Hz, to Hz, seed)).  What each
+# reaches is said in DESIGN.md "F0 tracking: DIO + StoneMask".  As with ``_DOWN_GLIDE_SECONDS`` the durations were picked
+# per configuration so that, on the float64 run, no deciding test lands on its threshold (tests/test_f0_dio_cpu.py
+# asserts the condition itself); ``allowed_0.5`` glides fast enough for a frame-to-frame change between 0.1 and 0.5.
+_UP, _DOWN = (75.0, 780.0, 11), (420.0, 95.0, 12)
+CONFIG_CASES = [
+    ("sr8000", 8000, 80, (), ((1.0,) + _UP, (1.35,) + _DOWN)),
+    ("sr22050", 22050, 256, (), ((1.4,) + _UP, (1.2,) + _DOWN)),
+    ("sr44100", 44100, 512, (), ((1.2,) + _UP, (0.9,) + _DOWN)),
+    ("one_band", 16000, 160, (("f0_floor", 200.0), ("f0_ceil", 250.0)),
+     ((0.95, 190.0, 260.0, 11), (0.95, 260.0, 190.0, 12))),
+    ("sixteen_bands", 16000, 160, (("channels_in_octave", 4.5),), ((1.2,) + _UP, (0.9,) + _DOWN)),
+    ("wide", 24000, 300, (("f0_floor", 50.0), ("f0_ceil", 1000.0), ("channels_in_octave", 3.0)),
+     ((1.05, 55.0, 950.0, 11), (1.0, 900.0, 60.0, 12))),
+    ("narrow", 16000, 128, (("f0_floor", 120.0), ("f0_ceil", 400.0)), ((0.9,) + _UP, (1.0,) + _DOWN)),
+    ("allowed_0.02", 16000, 160, (("allowed_range", 0.02),), ((1.1,) + _UP, (1.25,) + _DOWN)),
+    ("allowed_0.5", 16000, 160, (("allowed_range", 0.5),), ((0.45,) + _UP, (0.45, 780.0, 75.0, 12))),
+]
+CASE_IDS = [c[0] for c in CONFIG_CASES]
 
 
 def is_margin_input(res64, yard):

@@ -8,6 +8,9 @@ Steps (numbers as in DESIGN.md "F0 tracking"):
  1. constants of (sr, hop, config): ``Consts``;
  2. frame count / first centre: ``frame_layout`` (float64, in this order of operations);
  3. whole-file mean and peak; 4. per-frame r[lag]; 5. candidates; 6. path: ``track`` / ``viterbi``.
+
+The fixtures at the end (``reference_pairs``, ``natural_pairs``, ``config_yardstick``) are cached per (sr, hop, min_pitch,
+seconds of the long row) and, for the cases off the defaults (``CONFIG_CASES``), per configuration and input set.
 """
 from __future__ import annotations
 
@@ -145,7 +148,7 @@ def candidates(x, c: Consts, dtype=np.float64, return_r=False):
     cand_s = np.zeros((T, N_CAND), dtype)
     cand_n = np.ones((T,), np.int32)
     cand_s[:, 0] = dt(c.voicing) + np.maximum(dt(0), dt(2) - intensity / (dt(c.silence) / (dt(1) + dt(c.voicing))))
-    info = dict(r=r, silent=silent, gap15=np.inf, thr_gap=np.inf)
+    info = dict(r=r, silent=silent, gap15=np.inf, thr_gap=np.inf, n_maxima=np.zeros((T,), np.int64))
     if T == 0:
         return (cand_f, cand_s, cand_n, info) if return_r else (cand_f, cand_s, cand_n)
     lags = np.arange(2, c.maxlag)
@@ -167,6 +170,7 @@ def candidates(x, c: Consts, dtype=np.float64, return_r=False):
         score = s - dt(c.octave_cost) * np.log2(dt(c.min_pitch) / (dt(c.sr) / x0))
         keep = np.ones(rows.size, bool)
         counts = np.bincount(rows, minlength=T)
+        info["n_maxima"] = counts                                      # local maxima above the threshold, per frame
         for t in np.nonzero(counts > N_CAND - 1)[0]:
             sel = np.nonzero(rows == t)[0]
             order = sorted(sel, key=lambda m: (-score[m], m))
@@ -259,9 +263,13 @@ def track(x, sr, hop, dtype=np.float64, **config):
     cand_f, cand_s, cand_n, info = candidates(x, c, dtype, return_r=True)
     path, f0, margin = viterbi(cand_f, cand_s, cand_n, c, return_margin=True)
     n, t1 = frame_layout(np.asarray(x).size, c)
+    # relative distance of any candidate frequency from the ceiling (margin condition d): a candidate on the ceiling is
+    # voiced or voiceless with the last bit, which moves its local score and every transition to it
+    live = (np.arange(N_CAND)[None, :] < cand_n[:, None]) & (np.arange(N_CAND)[None, :] > 0)
+    ceil_gap = float(np.min(np.abs(cand_f.astype(np.float64)[live] / c.ceiling - 1.0))) if live.any() else np.inf
     return dict(f0=f0.astype(np.float32), cand_f=cand_f, cand_s=cand_s, cand_n=cand_n, path=path,
                 times=t1 + np.arange(n) * c.dt, margin=margin, consts=c, silent=info["silent"],
-                gap15=info["gap15"], thr_gap=info["thr_gap"], r=info["r"])
+                gap15=info["gap15"], thr_gap=info["thr_gap"], ceil_gap=ceil_gap, r=info["r"], n_maxima=info["n_maxima"])
 
 
 # --------------------------------------------------------------------------- comparison helpers
@@ -300,6 +308,27 @@ def deviation(res_a, res_b):
     both = (fa > 0) & (fb > 0)
     cc = float(np.max(cents(fa[both], fb[both]))) if both.any() else 0.0
     return dict(cents=worst_c, strength=worst_s, set_mismatches=mism, voicing_flips=flips, contour_cents=cc, frames=T)
+
+
+SAME_MAXIMUM_CENTS = 1.0
+
+
+def set_deviation(res_a, res_b):
+    """The selected candidate sets of two runs, frame by frame.  Two candidates are the same maximum of r when they lie
+    within ``SAME_MAXIMUM_CENTS``: maxima of one frame are at least 2 lags apart, which at the longest lag searched
+    (1201 samples at 48 kHz, min_pitch 40) is 2.9 cents, while a maximum moves by 1e-2 cents between float32 and
+    float64.  The cent is argued from the lag grid alone, not fitted to a kernel.  dict(mismatches: frames whose counts differ or that hold a different maximum; cents / strength: largest
+    deviation over the other frames)."""
+    T = res_a["cand_n"].shape[0]
+    mism, worst_c, worst_s = 0, 0.0, 0.0
+    for t in range(T):
+        ok, dc, ds = match_candidates(res_a["cand_f"][t], res_a["cand_s"][t], int(res_a["cand_n"][t]),
+                                      res_b["cand_f"][t], res_b["cand_s"][t], int(res_b["cand_n"][t]))
+        if not ok or dc > SAME_MAXIMUM_CENTS:
+            mism += 1
+            continue
+        worst_c, worst_s = max(worst_c, dc), max(worst_s, ds)
+    return dict(mismatches=mism, cents=worst_c, strength=worst_s, frames=T)
 
 
 # --------------------------------------------------------------------------- test signals (shared by CPU and GPU tests)
@@ -374,38 +403,150 @@ def yardstick(margin_results):
     return max(d["cents"] for d in dev), max(d["strength"] for d in dev), dev
 
 
-def is_margin_input(res64, strength_yardstick):
-    """Conditions (a)-(c) of a margin input, on the float64 result."""
+def is_margin_input(res64, strength_yardstick, cents_yardstick=None):
+    """Conditions (a)-(c) of a margin input, on the float64 result; with ``cents_yardstick`` also (d): no candidate
+    frequency of any frame within 1000x that yardstick (cents, as a frequency ratio) of the ceiling."""
     bound = 1000.0 * strength_yardstick
-    return res64["margin"] >= bound and res64["thr_gap"] > bound and res64["gap15"] > bound
+    ok = res64["margin"] >= bound and res64["thr_gap"] > bound and res64["gap15"] > bound
+    if cents_yardstick is not None:
+        ok = ok and res64["ceil_gap"] >= 1000.0 * (2.0 ** (cents_yardstick / 1200.0) - 1.0)
+    return ok
 
 
-def config_margin_inputs(sr, hop, min_pitch, long_seconds):
+def config_margin_inputs(sr, hop, min_pitch, long_seconds, inputs=None):
     """Margin inputs of one test configuration.  The spill configuration's small hop scales every transition cost up
-    (c = 0.01 / time_step), which leaves the 0.9-s glide a path margin of only 2x the bound: it is left out there."""
+    (c = 0.01 / time_step), which leaves the 0.9-s glide a path margin of only 2x the bound: it is left out there.
+    ``inputs`` names an input set of the configuration cases (``CASE_INPUTS``) instead."""
+    if inputs is not None:
+        return CASE_INPUTS[inputs](sr)[0]
     waves = margin_inputs(sr, long_seconds)
     return waves[1:] if (sr, hop, min_pitch, long_seconds) == SPILL_CONFIG else waves
 
 
-@functools.lru_cache(maxsize=None)
-def reference_pairs(sr, hop, min_pitch, long_seconds):
-    """(float64 result, float32 result) of the restatement for every margin input of one configuration."""
-    return tuple((track(y, sr, hop, min_pitch=min_pitch), track(y, sr, hop, dtype=np.float32, min_pitch=min_pitch))
-                 for y in config_margin_inputs(sr, hop, min_pitch, long_seconds))
+def _pairs(waves, sr, hop, min_pitch, config):
+    cfg = dict(config, min_pitch=min_pitch)
+    return tuple((track(y, sr, hop, **cfg), track(y, sr, hop, dtype=np.float32, **cfg)) for y in waves)
 
 
 @functools.lru_cache(maxsize=None)
-def natural_pairs(sr, hop, min_pitch):
-    return tuple((track(y, sr, hop, min_pitch=min_pitch), track(y, sr, hop, dtype=np.float32, min_pitch=min_pitch))
-                 for y in natural_inputs(sr))
+def reference_pairs(sr, hop, min_pitch, long_seconds, config=(), inputs=None):
+    """(float64 result, float32 result) of the restatement for every margin input of one configuration.  ``config``:
+    further keys of ``DEFAULTS`` as a tuple of (key, value) pairs."""
+    return _pairs(config_margin_inputs(sr, hop, min_pitch, long_seconds, inputs), sr, hop, min_pitch, config)
 
 
 @functools.lru_cache(maxsize=None)
-def config_yardstick(sr, hop, min_pitch, long_seconds):
+def natural_pairs(sr, hop, min_pitch, config=(), inputs=None):
+    return _pairs(natural_inputs(sr) if inputs is None else CASE_INPUTS[inputs](sr)[1], sr, hop, min_pitch, config)
+
+
+@functools.lru_cache(maxsize=None)
+def config_yardstick(sr, hop, min_pitch, long_seconds, config=(), inputs=None):
     """The yardsticks of ONE configuration: the deviation of the float32 run of the restatement from its float64 run
     on that configuration's own inputs, for exactly the quantities the GPU test asserts there.  ``cents`` / ``strength``:
     candidates of the margin inputs (also the bound of their contours, which are candidates); ``natural_cents``: the
     contour of the natural inputs (their weak candidates are not compared)."""
-    cents_m, strength_m, _ = yardstick(reference_pairs(sr, hop, min_pitch, long_seconds))
-    nat = [deviation(a, b)["contour_cents"] for a, b in natural_pairs(sr, hop, min_pitch)]
-    return dict(cents=cents_m, strength=strength_m, natural_cents=max(nat))
+    margin = reference_pairs(sr, hop, min_pitch, long_seconds, config, inputs)
+    cents_m, strength_m, _ = yardstick(margin) if margin else (0.0, 0.0, [])
+    nat_pairs = natural_pairs(sr, hop, min_pitch, config, inputs)
+    nat = [deviation(a, b)["contour_cents"] for a, b in nat_pairs]
+    out = dict(cents=cents_m, strength=strength_m, natural_cents=max(nat, default=0.0))
+    if inputs is not None:                                             # the selected sets of the natural rows
+        sets = [set_deviation(a, b) for a, b in nat_pairs]
+        out.update(natural_set_cents=max((d["cents"] for d in sets), default=0.0),
+                   natural_set_strength=max((d["strength"] for d in sets), default=0.0))
+    return out
+
+
+# --------------------------------------------------------------------------- configurations off the defaults
+def stepped_signal(segments, sr, gap=0.06, lead=0.05):
+    """Steady three-partial tones (seconds, Hz, amplitude), each followed by ``gap`` seconds of digital silence (longer
+    than a window at min_pitch 75, so no frame sees two tones) and no noise floor: every frame's maxima of r are those
+    of one steady tone, which keeps them away from a threshold or a ceiling that a glide would sweep across."""
+    parts = [np.zeros(int(lead * sr), np.float32)]
+    for seconds, hz, amplitude in segments:
+        parts.append(harmonic(np.full(int(seconds * sr), float(hz)), sr, amplitude=amplitude))
+        parts.append(np.zeros(int(gap * sr), np.float32))
+    return np.concatenate(parts).astype(np.float32)
+
+
+def white_noise(seconds, sr, seed, amplitude=0.3):
+    return (amplitude * np.random.default_rng(seed).standard_normal(int(seconds * sr))).astype(np.float32)
+
+
+def weak_burst_signal(sr, seed=1, sigma=0.12):
+    """Digital silence, 0.12 s of a 400 Hz tone in white noise (strength near 0.6), silence, a clean 150 Hz tone.  Under
+    costs_a the burst gains more over its unvoiced candidate than two voicing changes cost at 0.14 and less than they
+    would at 0.35, so the path says which factor the change was charged with."""
+    rng = np.random.default_rng(seed)
+    n = int(0.12 * sr)
+    burst = harmonic(np.full(n, 400.0), sr, amplitude=0.3) + (sigma * rng.standard_normal(n)).astype(np.float32)
+    z = lambda seconds: np.zeros(int(seconds * sr), np.float32)  # noqa: E731
+    return np.concatenate([z(0.1), burst, z(0.1), harmonic(np.full(int(0.3 * sr), 150.0), sr), z(0.06)]).astype(np.float32)
+
+
+def weak_fundamental_bursts(sr, hz=200.0, seconds=0.1):
+    """Two 0.1-s bursts of a 200 Hz tone whose second partial dominates (0.2, 1, 0, 0.5), then a clean 150 Hz tone, all
+    between digital silence.  Under max_pitch 300 the strongest maximum of a burst, 400 Hz, counts as voiceless, so the
+    path enters and leaves it for nothing, while the slightly stronger 200 Hz candidate would pay two voicing changes:
+    the burst comes out unvoiced.  A path that forgets the ceiling pays the changes either way and comes out at 200 Hz."""
+    z = lambda s: np.zeros(int(s * sr), np.float32)  # noqa: E731
+    burst = harmonic(np.full(int(seconds * sr), hz), sr, partials=(0.2, 1.0, 0.0, 0.5))
+    return np.concatenate([z(0.1), burst, z(0.1), burst, z(0.1), harmonic(np.full(int(0.3 * sr), 150.0), sr),
+                           z(0.06)]).astype(np.float32)
+
+
+_GLIDES = ((0.9, 80.0, 380.0, 0), (1.0, 400.0, 150.0, 1), (1.3, 200.0, 800.0, 2))
+_QUIET = ((0.4, 150.0, 0.5), (0.4, 200.0, 0.05), (0.4, 240.0, 0.001), (0.4, 180.0, 0.5))
+
+
+def _glide_rows(sr, noise):
+    return [glide_signal(s, a, b, sr, seed=k, noise=noise)[0] for s, a, b, k in _GLIDES]
+
+
+# name -> sr -> (margin inputs, natural inputs).  "glides": an up-, a down- and a wide glide over the usual noise floor.
+# "costs": two of the glides and the weak burst.  "ceiling": stepped tones on both sides of 300 Hz and the weak-fundamental bursts.  "quiet": at a low candidate
+# threshold the maxima of a noise lead-in land anywhere, also on the threshold, so the glides come without a noise floor
+# (their lead-in is digital silence), and a stepped row holds passages 20 and 54 dB under the peak.  "noise": white
+# noise alone, two natural rows of unequal length (no margin exists in noise).
+CASE_INPUTS = {
+    "glides": lambda sr: (_glide_rows(sr, 1e-3), natural_inputs(sr)[:1]),
+    "costs": lambda sr: (_glide_rows(sr, 1e-3)[:2] + [weak_burst_signal(sr)], natural_inputs(sr)[:1]),
+    "ceiling": lambda sr: ([stepped_signal([(0.4, 150.0, 0.5), (0.4, 420.0, 0.5), (0.4, 220.0, 0.5), (0.4, 500.0, 0.5)], sr),
+                            stepped_signal([(0.4, 350.0, 0.5), (0.4, 250.0, 0.5), (0.4, 520.0, 0.5)], sr),
+                            weak_fundamental_bursts(sr)], natural_inputs(sr)[:1]),
+    "quiet": lambda sr: (_glide_rows(sr, 0.0)[:2] + [stepped_signal(_QUIET, sr)], natural_inputs(sr)[:1]),
+    "noise": lambda sr: ([], [white_noise(0.6, sr, seed=21), white_noise(0.25, sr, seed=22)]),
+}
+
+# (name, sr, hop, min_pitch, config, input set): what each reaches is said in DESIGN.md "F0 tracking"
+CONFIG_CASES = [
+    ("ceiling_300", 16000, 160, 75.0, (("max_pitch", 300.0),), "ceiling"),
+    ("ceiling_nyquist", 16000, 160, 75.0, (("max_pitch", 20000.0),), "glides"),
+    ("costs_a", 16000, 160, 75.0, (("octave_cost", 0.05), ("octave_jump_cost", 0.35), ("voiced_unvoiced_cost", 0.14)),
+     "costs"),
+    ("costs_zero", 16000, 160, 75.0, (("octave_cost", 0.0), ("octave_jump_cost", 0.0), ("voiced_unvoiced_cost", 0.0)),
+     "glides"),
+    ("thresholds_low", 16000, 160, 75.0, (("voicing_threshold", 0.2), ("silence_threshold", 0.09)), "quiet"),
+    ("thresholds_high", 16000, 160, 75.0, (("voicing_threshold", 0.8), ("silence_threshold", 0.003)), "quiet"),
+    ("maxima_48k", 48000, 480, 40.0, (("voicing_threshold", 0.01),), "noise"),
+    ("maxima_16k", 16000, 160, 75.0, (("voicing_threshold", 0.01),), "noise"),
+]
+CASE_IDS = [c[0] for c in CONFIG_CASES]
+
+
+def case_fixtures(case):
+    """(margin waves, natural waves, margin pairs, natural pairs, yardstick) of one entry of ``CONFIG_CASES``.  A case
+    has no long row: the fixtures' seconds argument is 0.0 there and only part of their cache key (the input set names
+    the rows)."""
+    _, sr, hop, min_pitch, config, inputs = case
+    margin, natural = CASE_INPUTS[inputs](sr)
+    return (margin, natural, reference_pairs(sr, hop, min_pitch, 0.0, config, inputs),
+            natural_pairs(sr, hop, min_pitch, config, inputs), config_yardstick(sr, hop, min_pitch, 0.0, config, inputs))
+
+
+def unvoiced_by_ceiling(res64):
+    """Frames whose path takes a pitch candidate at or above the ceiling: unvoiced for that reason alone."""
+    T = res64["path"].size
+    chosen = res64["cand_f"].astype(np.float64)[np.arange(T), res64["path"]]
+    return (res64["path"] > 0) & (chosen >= res64["consts"].ceiling)

@@ -107,20 +107,29 @@ def _tracker(sr, hop, **config):
     return WorldDioTracker(sr, hop, **config)
 
 
-@pytest.mark.parametrize("sr,hop", [(16000, 160), (24000, 300), (48000, 480)])
-def test_plan_matches_the_restatement(sr, hop):
-    tr = _tracker(sr, hop)
-    c = D.Consts(sr, hop)
+PLAN_CONFIGS = [(16000, 160, ()), (24000, 300, ()), (48000, 480, ())] + [c[1:4] for c in D.CONFIG_CASES]
+
+
+@pytest.mark.parametrize("sr,hop,config", PLAN_CONFIGS,
+                         ids=["16000-160", "24000-300", "48000-480"] + D.CASE_IDS)
+def test_plan_matches_the_restatement(sr, hop, config):
+    tr = _tracker(sr, hop, **dict(config))
+    c = D.Consts(sr, hop, **dict(config))
     assert (tr.bands, tr.half_average_length, tr.cut, tr.voice_range_minimum) == (c.bands, c.half, c.cut, c.vrm)
-    assert tr.bands == 7 and np.allclose(tr.boundary, c.boundary, rtol=1e-15, atol=0)
+    default = (sr, hop, config) in PLAN_CONFIGS[:3]                   # the literal figures below are theirs
+    if default:
+        assert tr.bands == 7
+    assert len(tr.boundary) == c.bands and np.allclose(tr.boundary, c.boundary, rtol=1e-15, atol=0)
     assert (tr.n_fft, tr.taps, tr.block_step, tr.lead) == (c.nfft, c.taps, c.step, c.lead)
     assert tr.frame_period == c.frame_period
     for n in (0, 1, hop - 1, hop, 10 ** 7):
         assert tr.frame_count(n) == D.frame_count(n, c)
         assert np.array_equal(tr.frame_times(n), D.frame_times(n, c))
-    assert tr.frame_count(0) == 1 and tr.frame_count(hop - 1) == 1 and tr.frame_count(hop) == 2
+    assert tr.frame_count(0) == 1 and tr.frame_count(hop - 1) == 1
+    if default:
+        assert tr.frame_count(hop) == 2
     pl = tr.plan([0, 100, 5 * tr.block_step + 1])
-    assert list(pl["frames"]) == [1, 1, D.frame_count(5 * tr.block_step + 1, c)]
+    assert list(pl["frames"]) == [1, 1 if default else D.frame_count(100, c), D.frame_count(5 * tr.block_step + 1, c)]
     assert pl["n_blocks"] == 0 + 1 + 6 and pl["n_samples"] == 101 + 5 * tr.block_step
     # the tables' band filters are the restatement's combined filters
     tab = tr.host_tables()
@@ -133,6 +142,88 @@ def test_plan_matches_the_restatement(sr, hop):
         gd[shift:shift + g.size] = g
         ref = np.fft.rfft(gd) / C
         assert np.allclose(G[b, :, 0] + 1j * G[b, :, 1], ref, atol=1e-9)
+
+
+def test_configurations_reach_their_plans():
+    """What each configuration of ``dio_ref.CONFIG_CASES`` is there for, on the plan."""
+    plans = {name: _tracker(sr, hop, **dict(config)) for name, sr, hop, config, _ in D.CONFIG_CASES}
+    assert plans["sr8000"].n_fft == 1024 and plans["sr8000"].taps == 480
+    assert (plans["sr22050"].cut, plans["sr44100"].cut) == (441, 882)
+    for name in ("sr22050", "sr44100"):
+        assert plans[name].frame_period != round(plans[name].frame_period * 2) / 2       # no whole or half millisecond
+    assert plans["one_band"].bands == 1 and plans["sixteen_bands"].bands == 16
+    assert plans["wide"].bands == 13 and plans["wide"].voice_range_minimum == 5
+    assert plans["narrow"].frame_period == 8.0 and plans["narrow"].bands == 4
+    assert plans["narrow"].voice_range_minimum != _tracker(16000, 128).voice_range_minimum
+
+
+@pytest.mark.parametrize("sr,hop", [(22050, 256), (44100, 512), (16000, 128)])
+def test_frame_counts_on_the_integer_boundary(sr, hop):
+    """n = k hop: 1000 n / sr / frame_period is k in exact arithmetic, and k or k - 1 after the truncation of its
+    float64 value.  The plan and the restatement divide in the same order, so they agree whichever it is."""
+    tr, c = _tracker(sr, hop), D.Consts(sr, hop)
+    k = np.arange(1, 2001, dtype=np.int64)
+    lengths = np.stack([k * hop - 1, k * hop, k * hop + 1], axis=1).reshape(-1)
+    got = tr.plan(lengths.tolist())["frames"]
+    want = np.array([D.frame_count(int(n), c) for n in lengths], np.int64)
+    below = int(np.count_nonzero(want.reshape(-1, 3)[:, 1] == k))
+    print(f"[f0_dio] sr {sr} hop {hop}: frame counts at n = k hop - 1, k hop, k hop + 1 for k = 1 .. 2000; the quotient "
+          f"at n = k hop truncates to k - 1 in {below} cases")
+    assert np.array_equal(got, want)
+    assert np.all(want.reshape(-1, 3)[:, 0] == k) and np.all(want.reshape(-1, 3)[:, 2] == k + 1)
+
+
+def test_configurations_refused_by_the_plan():
+    from pitchextractor_amd import _lib
+    _tracker(16000, 160, channels_in_octave=4.5)                       # log2(800 / 71) 4.5 = 15.7: sixteen bands
+    for sr, hop, bad in ((16000, 160, dict(channels_in_octave=4.6)),   # 16.07: a seventeenth band
+                         (48000, 480, dict(f0_floor=30.0)),            # band filter of 2 * 960 + 4 * 566 taps: 16384 points
+                         (48000, 480, dict(f0_floor=70.3))):           # StoneMask window of 2 * 1025 + 1 samples: 8192 points
+        with pytest.raises(_lib.HipLibraryError, match="unsupported"):
+            _tracker(sr, hop, **bad)
+    _tracker(48000, 480, f0_floor=70.5)
+    c = D.Consts(48000, 480, f0_floor=30.0)
+    assert 2 * c.taps > 8192 and D.Consts(48000, 480, f0_floor=70.3).nfft == 8192
+
+
+@pytest.mark.parametrize("case", D.CONFIG_CASES, ids=D.CASE_IDS)
+def test_configuration_yardstick_and_margin_inputs(case):
+    name, sr, hop, config, inputs = case
+    yard = D.config_yardstick(sr, hop, config, inputs)
+    print(f"[f0_dio] {name} sr {sr} hop {hop} {dict(config)}: " +
+          " ".join(f"{k} {v:.3e}" for k, v in yard.items() if isinstance(v, float)))
+    pairs = D.reference_pairs(sr, hop, True, config, inputs)
+    assert len(pairs) == 2 and all(seconds <= 1.5 for seconds, _, _, _ in inputs)
+    tol = 4 * yard["cand_cents"]
+    changed = np.zeros(4, np.int64)
+    for r, ((a, b), st) in enumerate(zip(pairs, yard["stage_dev"])):
+        print(f"[f0_dio]   margin row {r}: frames {a['f0'].size} voiced {int((a['f0'] > 0).sum())} margins {a['margin']} "
+              f"stage {st}")
+        assert D.is_margin_input(a, yard)
+        assert st["same_counts"] and st["cand_flips"] == 0
+        assert st["best_band_differs"] == 0 or st["best_band_gap"] <= tol
+        assert st["stonemask_flips"] == 0
+        assert np.array_equal(a["f0"] > 0, b["f0"] > 0) and np.array_equal(a["dio"] > 0, b["dio"] > 0)
+        assert int(np.count_nonzero(a["f0"] > 0)) >= 40
+        before = [a["best"]] + list(a["steps"][:3])
+        changed += [int(np.count_nonzero(a["steps"][s] != before[s])) for s in range(4)]
+    c = pairs[0][0]["consts"]
+    assert min(len(y) for y in D.config_margin_inputs(sr, inputs)) >= 3 * c.step or c.nfft == 8192
+    print(f"[f0_dio]   frames changed by steps 1 .. 4 of the contour fix: {changed.tolist()}")
+    if name == "allowed_0.02":
+        assert changed.max() > 20                                  # far more than the ends any configuration trims
+    if name == "allowed_0.5":                                      # a change the default allowed_range would refuse
+        for a, _ in pairs:
+            at_default = D.fix_contour(a["best"], a["cand"], D.Consts(sr, hop), np.float64)
+            assert any(not np.array_equal(x, y) for x, y in zip(at_default, a["steps"]))
+    if name == "sr8000":
+        above = [(a["dio"] > sr / 12.0, a, b) for a, b in pairs]
+        total = sum(int(m.sum()) for m, _, _ in above)
+        print(f"[f0_dio]   frames with a DIO value above fs / 12 = {sr / 12.0:.1f} Hz: {total}")
+        assert total >= 10
+        for m, a, b in above:
+            assert not np.any(a["f0"][m] > 0) and not np.any(b["f0"][m] > 0)
+            assert np.array_equal(b["dio"] > sr / 12.0, m)
 
 
 def test_argument_checks_run_before_any_device_call():

@@ -12,6 +12,7 @@ line.  Needs a GPU.
 
     python tools/bench_f0_dio.py               # time, trace, training step
     python tools/bench_f0_dio.py --trace-run   # what the traced child runs: a few calls on the batch
+    python tools/bench_f0_dio.py --configurations-only   # only re-measure the configuration cases, in place
 
 Not a gate: labelling happens once per file, not once per step.
 """
@@ -121,9 +122,32 @@ def deviation_records(dev):
     return out
 
 
+def configuration_records(dev):
+    """What tests/test_f0_dio_config_gpu.py asserts, as figures: per case of ``dio_ref.CONFIG_CASES`` the yardstick of
+    its own rows and, stage by stage and end to end, the kernels' deviation from the float64 restatement on the margin
+    rows (the tests' assertions run on the way)."""
+    from tests import dio_ref as D
+    from tests import test_f0_dio_gpu as G
+    out = []
+    for name, sr, hop, config, inputs in D.CONFIG_CASES:
+        B = G._batch(sr, hop, config, inputs)
+        tr = B["tr"]
+        device = {}
+        for check in (G.check_band_signals, G.check_events, G.check_candidates, G.check_contour_fix,
+                      G.check_stonemask):
+            device.update(check(B))
+        device.update(G.check_end_to_end(B, True))
+        out.append({"case": name, "sr": sr, "hop": hop, "config": dict(config), "inputs": [list(i) for i in inputs],
+                    "block_fft": tr.n_fft, "bands": tr.bands, "voice_range_minimum": tr.voice_range_minimum,
+                    "yardstick": {k: v for k, v in B["yard"].items() if isinstance(v, float)}, "device": device})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=2.0, help="seconds of timed work")
+    ap.add_argument("--configurations-only", action="store_true",
+                    help="measure only tracker_vs_float64_restatement_configurations and put it into the existing --out")
     ap.add_argument("--trace-run", action="store_true")
     ap.add_argument("--no-train-step", action="store_true")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "bench_f0_dio.json"))
@@ -133,6 +157,12 @@ def main():
     dev = torch.device("cuda:0")
     if args.trace_run:
         trace_run(dev)
+        return
+    if args.configurations_only:
+        res = json.loads(Path(args.out).read_text())
+        res["tracker_vs_float64_restatement_configurations"] = configuration_records(dev)
+        Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res["tracker_vs_float64_restatement_configurations"]))
         return
     tr = WorldDioTracker(SR, HOP)
     flat, lengths = make_batch(dev)
@@ -153,6 +183,7 @@ def main():
     out.parent.mkdir(parents=True, exist_ok=True)
     res["kernels"] = kernel_rows(out.with_name(out.stem + "_kernel_stats.csv"))
     res["tracker_vs_float64_restatement"] = deviation_records(dev)
+    res["tracker_vs_float64_restatement_configurations"] = configuration_records(dev)
     if not args.no_train_step:
         step = training_step_ms()
         res["training_step_ms_fp32_batch256"] = step

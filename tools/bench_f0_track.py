@@ -11,6 +11,7 @@ profiles/bench_f0_track.json and profiles/bench_f0_track_kernel_stats.csv and pr
 
     python tools/bench_f0_track.py               # time, trace, training step
     python tools/bench_f0_track.py --trace-run   # what the traced child runs: a few calls on each batch
+    python tools/bench_f0_track.py --configurations-only   # only re-measure the configuration cases, in place
 
 Not a gate: labelling happens once per file, not once per step.  The frame kernel is bound by VALU and LDS (two
 4096-point real transforms and about 15 x 13 sinc evaluations of 140 taps per frame), the path kernel by latency (one
@@ -148,9 +149,37 @@ def deviation_records(dev):
     return out
 
 
+def configuration_records(dev):
+    """What tests/test_f0_track_config_gpu.py asserts, as figures: per case of ``f0_track_ref.CONFIG_CASES`` the
+    yardsticks of its own rows and the kernel's deviation from the float64 restatement, per row kind (the test's
+    assertions run on the way)."""
+    from tests import f0_track_ref as R
+    from tests.test_f0_track_config_gpu import run_case
+    out = []
+    for case in R.CONFIG_CASES:
+        name, sr, hop, mp, config, inputs = case
+        yard, devs = run_case(case)
+        rec = {"case": name, "sr": sr, "hop": hop, "min_pitch": mp, "config": dict(config), "inputs": inputs,
+               "yardstick": yard}
+        for kind in ("margin", "natural"):
+            rows = [d for d in devs if d["kind"] == kind]
+            if rows:
+                rec[kind] = {"rows": len(rows), "frames": sum(d["frames"] for d in rows),
+                             "voicing_flips": sum(d["voicing_flips"] for d in rows),
+                             "set_mismatches": sum(d["set_mismatches"] for d in rows),
+                             "frames_with_another_set": sum(d["set_other"] for d in rows),
+                             "candidate_cents": max(d["cents" if kind == "margin" else "set_cents"] for d in rows),
+                             "strength": max(d["strength" if kind == "margin" else "set_strength"] for d in rows),
+                             "contour_cents": max(d["contour_cents"] for d in rows)}
+        out.append(rec)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=2.0, help="seconds of timed work per batch")
+    ap.add_argument("--configurations-only", action="store_true",
+                    help="measure only kernel_vs_float64_restatement_configurations and put it into the existing --out")
     ap.add_argument("--rounds", type=int, default=4, help="alternating rounds the window is split into")
     ap.add_argument("--trace-run", action="store_true")
     ap.add_argument("--no-train-step", action="store_true")
@@ -161,6 +190,12 @@ def main():
     dev = torch.device("cuda:0")
     if args.trace_run:
         trace_run(dev)
+        return
+    if args.configurations_only:
+        res = json.loads(Path(args.out).read_text())
+        res["kernel_vs_float64_restatement_configurations"] = configuration_records(dev)
+        Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res["kernel_vs_float64_restatement_configurations"]))
         return
     tr = PraatACTracker(SR, HOP)
     batches = make_batches(dev)
@@ -209,6 +244,7 @@ def main():
                                        max(b["longest_row_frames"], 1), bound="latency (one dependent step per frame)")
         res["batches"][name] = b
     res["kernel_vs_float64_restatement"] = deviation_records(dev)
+    res["kernel_vs_float64_restatement_configurations"] = configuration_records(dev)
     if not args.no_train_step:
         step = training_step_ms()
         res["training_step_ms_fp32_batch256"] = step
